@@ -21,12 +21,23 @@ BASELINE.json configurations: 2 = ``--particles 1024``; 3 = default (sawyer.xml 
 4 = ``--controller cem --particles 16384 --scaling strong --gpus 4``;
 5 = ``--workload hand24 --controller dmd --particles 65536 --horizon 64 --scaling strong --gpus 8`` (stand-in model).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel = the rollout kernel, timed live with
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0): `value` (particle-steps/s),
+`ms_per_step` (one timed control step), `unit`, `higher_is_better`, `dtype`, the configuration and the solver counters.
+
+    --dump-outputs DIR  after the timed steps, what the timed path computed in its last step - the action optimize()
+                        returned, the controller's mean (and covariance) after the shift, the real env's observation and
+                        cost after that action - as DIR/<name>.npy (float64, or float32 where the run keeps an array in
+                        float32); the inputs are seeded, so the same arguments give the same inputs run after run
+    --full              after the headline, everything else the line can carry (below): measurements and checks that
+                        take runs of their own
+
+With --full the line also holds `roofline` (dominant kernel = the rollout kernel, timed live with
 events on the launch stream; the HBM block SURVEY 8d defines plus `valu`, the roofline that actually binds:
 FLOPs per particle-step COUNTED by the instrumented oracle build, oracle/flop_count.cpp, beside the kernel's own count
 and issue fraction from the SQ counter passes kept under profiles/), `cpu_baseline` (oracle/ on the host cores, N = 1
-only) and, for the fused two-launch iteration on one GPU, `pipelined`: the same closed loop with the next iteration
-enqueued before the host waits for the current action (reported beside the headline, never as it).
+only, unless --no-cpu-baseline), where the closed loop ended (`final_distance_to_target` / `forward_progress_m`), for the
+fused two-launch iteration on one GPU `pipelined`: the same closed loop with the next iteration enqueued before the host
+waits for the current action (reported beside the headline, never as it), and at N > 1 `strong` and `collectives_ab`.
 """
 import argparse
 import json
@@ -82,6 +93,11 @@ def parse(argv=None):
     ap.add_argument("--process-warmup", type=int, default=60,
                     help="throw-away control steps before controller and env are reset and the W warm-up steps begin, so that "
                          "the timed steps do not pay for a fresh process (idle clocks, first-touch, lazy runtime initialisation)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else: pipelined loop, kernel timings and "
+                         "roofline, CPU baseline, final state, strong scaling and the exchange-path A/B (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--engine", choices=["auto", "tree"], default="auto",
@@ -198,6 +214,18 @@ def profile_figure(name, dtype, P, H, prefix=""):
             with open(path) as f:
                 return json.load(f), os.path.relpath(path, ROOT)
     return None, None
+
+
+def dump_outputs(outdir, ctrl, eng, action):
+    """--dump-outputs: what the last timed step computed, as its caller receives it - the action optimize() returned,
+    the controller's mean and covariance after the shift, and the device-resident real env's observation and cost after
+    that action (the buffers the env step of the iteration writes) - one DIR/<name>.npy each, a few kB in all."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {"action": action, "mean_action": ctrl.mean_action, "cov_action": ctrl.cov_action,
+              "env_obs": eng._buffer("step_obs", (eng.d_obs,)), "env_cost": eng._buffer("step_cost", (1,))}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+        np.save(os.path.join(outdir, name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 # ---------------------------------------------------------------------------------------------------------- workloads
@@ -385,6 +413,7 @@ def main():
 
         def control_step():
             action, _ = ctrl.optimize(state)
+            last["action"] = action
             if not graphed:
                 eng.step_state(action)          # (in graph mode the env step is part of the captured iteration)
 
@@ -417,8 +446,71 @@ def main():
             dt = float(t.item())
         return dt
 
+    def close_world():
+        if world > 1:
+            # captured graphs that hold RCCL kernels go before the group does (its watchdog thread otherwise races the
+            # interpreter's shutdown: an abort at exit, one run in a few, after the line has been printed)
+            import gc
+            ctrl._graph = None
+            gc.collect()
+            torch.cuda.synchronize()
+            dist.barrier()
+            if comm is not None:
+                comm.close()            # (the library's own RCCL communicator, TorchDistComm.lib_collectives)
+            dist.destroy_process_group()
+
     graphed, control_step = wire(ctrl)
     dt = timed_loop(ctrl, control_step, w["reset"], args.process_warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctrl, eng, last["action"])
+
+    # the headline line; a plain run prints it here, --full adds the rest below
+    launch_kind = launch_kind_of(ctrl, graphed)
+    mono = graphed and getattr(ctrl, "_mono", False)
+    out = {
+        "metric": "particle-steps/sec (%s %s %dp x H%d per GPU, control loop incl. noise, rollout, update, shift)"
+                  % (w["name"], args.controller.upper() if args.controller != "dmd" else "DMD-MPC", P_loc, H),
+        "value": P_tot * H * ctrl.n_iters * args.steps / dt, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling,
+        "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+        "config": {"workload": "%s %s H=%d, %d particles per GPU (%d total), frame_skip %d, %d dofs, filter [0.25,0.8,0], %s"
+                               % (w["name"], w["desc"], H, P_loc, P_tot, w["frame_skip"], w["nv"], w["tail"]),
+                   "controller": args.controller, "noise": args.noise, "particles_per_gpu": P_loc, "particles_total": P_tot,
+                   "horizon": H, "ranks_seen": dist.get_world_size() if world > 1 else 1,
+                   "backend": (dist.get_backend() if world > 1 else None),
+                   # which path carried the exchanges of the timed loop, what making the library's communicator took, and
+                   # whether any rank fell back from it (then EVERY rank did: TorchDistComm decides by all-reduce)
+                   "collectives": (comm.collectives if world > 1 else None),
+                   "comm_init_s": (round(comm.init_seconds, 4) if world > 1 else None),
+                   "collectives_fallback": ((comm.why_fell_back or True) if (world > 1 and comm.fell_back) else False),
+                   "collectives_per_step": (0 if world == 1 else (2 if args.controller == "cem" else 1)),
+                   "launch": launch_kind + (", rollout + record launches, all-gather, combine, env step" if (mono and world > 1) else "")
+                             + (", next iteration enqueued ahead" if (mono and args.lookahead and world == 1) else ""),
+                   "process_warmup_steps": args.process_warmup,
+                   # which tuning alternative each HIP source was compiled with (mjmpc_amd/build.py: the first that this
+                   # compiler accepts; profiles/ were measured with alternative 0 of every source)
+                   "build": {k: (v["flags"] or "default") + ("" if v.get("alternative", 0) == 0 else " [FALLBACK alternative %d of %d]" % (v["alternative"], v["of"]))
+                             for k, v in build_info().get("sources", {}).items() if v.get("of", 0) > 0 or v.get("alternative", 0) != 0}},
+        "control_loop_hz": args.steps / dt,
+    }
+
+    def counters():
+        out["solver_failures"] = eng.solver_failures()
+        if hasattr(eng, "env_resets"):
+            # resets of the device-resident REAL env (the reference raises MujocoException there; bench.py reports instead)
+            out["env_resets"] = eng.env_resets()
+        if hasattr(eng, "diverged_substeps"):
+            # particle-substeps in which MuJoCo would have reset the simulation (NaN / > 1e10 in qpos, qvel, qacc) and the kernel did:
+            # such particles go on from qpos0 with finite costs (engine.set_reset_returns('inf') gives them +inf instead)
+            # in the update; apart from solver_failures (= a finite problem the iteration cap ended)
+            out["diverged_particle_substeps"] = eng.diverged_substeps()
+
+    counters()
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        close_world()
+        return
 
     # where the closed loop ended up (read BEFORE the launches below)
     extra = {}
@@ -466,7 +558,6 @@ def main():
         noise_t = last.get("noise")
     coeffs = ctrl.dev.record("coeffs", 3)
 
-    mono = graphed and getattr(ctrl, "_mono", False)
     sampled_entry = graphed and hasattr(ctrl, "_cem_in_kernel") and ctrl._cem_in_kernel()
     if mono:
         chol_t, coeffs_t, _ = ctrl.dev.prepare_noise(ctrl._cov_host, ctrl.filter_coeffs)
@@ -565,7 +656,6 @@ def main():
                       "launch": kind_s, "collectives": comm.collectives,
                       "what": "the same closed loop with --particles as the TOTAL population, split over the ranks "
                               "(subproc_vec_env.py:161-168); same steps / warmup, MAX over ranks"}
-    fails = eng.solver_failures()
 
     # HBM bytes of one launch of the dominant kernel from the PMC counters (separate rocprofv3 passes,
     # FETCH_SIZE x2 on gfx950, calibrated on a known copy): measured offline, kept under profiles/
@@ -574,7 +664,6 @@ def main():
     traffic = tj["traffic_bytes_per_launch"] if tj else None
     ij, issue_src = profile_figure("valu_issue", args.dtype, P_loc, H, prefix)
 
-    psteps = P_tot * H * ctrl.n_iters * args.steps
     s = 8 if args.dtype == "f64" else 4
     b_alg = (3 * A + 2) * s                       # delta in, action + cost out, action + cost re-read
     achieved = b_alg * P_loc * H / (kern_ms * 1e-3) / 1e9
@@ -604,32 +693,11 @@ def main():
                     "issue_frac_source": issue_src}
         except Exception as e:          # the counting build is measurement infrastructure: never lose the line over it
             valu = {"bound": "valu", "error": "FLOP-counting oracle build unavailable: %s" % (e,)}
+    # (the launch kind as the loops above left the controller, as the line has always reported it with these measurements)
     launch_kind = launch_kind_of(ctrl, graphed)
-    out = {
-        "metric": "particle-steps/sec (%s %s %dp x H%d per GPU, control loop incl. noise, rollout, update, shift)"
-                  % (w["name"], args.controller.upper() if args.controller != "dmd" else "DMD-MPC", P_loc, H),
-        "value": psteps / dt, "unit": "particle-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-        "dtype": args.dtype, "data": "synthetic",
-        "config": {"workload": "%s %s H=%d, %d particles per GPU (%d total), frame_skip %d, %d dofs, filter [0.25,0.8,0], %s"
-                               % (w["name"], w["desc"], H, P_loc, P_tot, w["frame_skip"], w["nv"], w["tail"]),
-                   "controller": args.controller, "noise": args.noise, "particles_per_gpu": P_loc, "particles_total": P_tot,
-                   "horizon": H, "ranks_seen": dist.get_world_size() if world > 1 else 1,
-                   "backend": (dist.get_backend() if world > 1 else None),
-                   # which path carried the exchanges of the timed loop, what making the library's communicator took, and
-                   # whether any rank fell back from it (then EVERY rank did: TorchDistComm decides by all-reduce)
-                   "collectives": (comm.collectives if world > 1 else None),
-                   "comm_init_s": (round(comm.init_seconds, 4) if world > 1 else None),
-                   "collectives_fallback": ((comm.why_fell_back or True) if (world > 1 and comm.fell_back) else False),
-                   "collectives_per_step": (0 if world == 1 else (2 if args.controller == "cem" else 1)),
-                   "launch": launch_kind + (", rollout + record launches, all-gather, combine, env step" if (mono and world > 1) else "")
-                             + (", next iteration enqueued ahead" if (mono and args.lookahead and world == 1) else ""),
-                   "process_warmup_steps": args.process_warmup,
-                   # which tuning alternative each HIP source was compiled with (mjmpc_amd/build.py: the first that this
-                   # compiler accepts; profiles/ were measured with alternative 0 of every source)
-                   "build": {k: (v["flags"] or "default") + ("" if v.get("alternative", 0) == 0 else " [FALLBACK alternative %d of %d]" % (v["alternative"], v["of"]))
-                             for k, v in build_info().get("sources", {}).items() if v.get("of", 0) > 0 or v.get("alternative", 0) != 0}},
-        "control_loop_hz": args.steps / dt,
+    out["config"]["launch"] = (launch_kind + (", rollout + record launches, all-gather, combine, env step" if (mono and world > 1) else "")
+                               + (", next iteration enqueued ahead" if (mono and args.lookahead and world == 1) else ""))
+    out.update({
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "traffic_source": ("offline PMC passes, %s" % traffic_src) if traffic_src else None,
@@ -651,16 +719,8 @@ def main():
                      "alg_bytes_per_particle_step": b_alg,
                      "note": "latency/VALU-bound path (SURVEY 8d): >100 counted FLOP per algorithmic byte, HBM fraction is small by "
                              "construction; `valu` is the roofline that binds"},
-        "solver_failures": fails,
-    }
-    if hasattr(eng, "env_resets"):
-        # resets of the device-resident REAL env (the reference raises MujocoException there; bench.py reports instead)
-        out["env_resets"] = eng.env_resets()
-    if hasattr(eng, "diverged_substeps"):
-        # particle-substeps in which MuJoCo would have reset the simulation (NaN / > 1e10 in qpos, qvel, qacc) and the kernel did:
-        # such particles go on from qpos0 with finite costs (engine.set_reset_returns('inf') gives them +inf instead)
-        # in the update; apart from solver_failures (= a finite problem the iteration cap ended)
-        out["diverged_particle_substeps"] = eng.diverged_substeps()
+    })
+    counters()                          # (again: after every launch above, as the line has always counted them)
     if pipelined:
         out["pipelined"] = pipelined
     if strong:
@@ -714,17 +774,7 @@ def main():
             out["cpu_baseline"] = cpu_baseline(P_loc, H, args.cpu_seconds, raw=raw, qpos=qpos, qvel=qvel,
                                                noise_scale=noise_scale)
         print(json.dumps(out), flush=True)
-    if world > 1:
-        # captured graphs that hold RCCL kernels go before the group does (its watchdog thread otherwise races the
-        # interpreter's shutdown: an abort at exit, one run in a few, after the line has been printed)
-        import gc
-        ctrl._graph = None
-        gc.collect()
-        torch.cuda.synchronize()
-        dist.barrier()
-        if comm is not None:
-            comm.close()            # (the library's own RCCL communicator, TorchDistComm.lib_collectives)
-        dist.destroy_process_group()
+    close_world()
 
 
 if __name__ == "__main__":

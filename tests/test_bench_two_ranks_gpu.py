@@ -28,7 +28,7 @@ def test_two_ranks_on_one_gpu():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6",
-           "--warmup", "2", "--particles", "512", "--backend", "gloo", "--device", "0", "--no-cpu-baseline"]
+           "--warmup", "2", "--particles", "512", "--backend", "gloo", "--device", "0", "--no-cpu-baseline", "--full"]
     j = _line(subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT))
     assert j["n_gpus"] == 2 and j["scaling"] == "weak" and j["solver_failures"] == 0
     assert j["config"]["particles_per_gpu"] == 512
@@ -61,7 +61,7 @@ def _self_launched(*flags):
     """``python bench.py --gpus 2 ...`` with no launcher and no WORLD_SIZE in the environment."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--device", "0",
-           "--particles", "512", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"] + list(flags)
+           "--particles", "512", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full"] + list(flags)
     return _line(subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env))
 
 
@@ -100,7 +100,7 @@ def test_sharded_equals_unsharded_action_sequence():
     loop (device noise is keyed by the global particle index; the records combine in rank order)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--particles", "512", "--steps", "10", "--warmup", "2",
-            "--no-cpu-baseline", "--scaling", "strong"]
+            "--no-cpu-baseline", "--full", "--scaling", "strong"]
     one = _line(subprocess.run(base, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env))
     two = _line(subprocess.run(base + ["--gpus", "2", "--backend", "gloo", "--device", "0"], capture_output=True,
                                text=True, timeout=900, cwd=ROOT, env=env))

@@ -201,7 +201,7 @@ def test_bench_line_for_a_tree_workload():
     for a tree-engine model."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "swimmer", "--particles", "256",
-                          "--horizon", "8", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1"],
+                          "--horizon", "8", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--full"],
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])

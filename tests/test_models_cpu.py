@@ -9,7 +9,7 @@ from mjmpc_amd.models.compile import ARM_BLOB_LEN, compile_arm
 from mjmpc_amd.models.mjcf import load_mjcf
 from mjmpc_amd.models.reacher7dof import reacher7dof_raw
 
-SAWYER = "/root/reference/mjmpc/envs/assets/xml/sawyer.xml"
+SAWYER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "mjcf", "sawyer.xml")   # the reference's own file
 
 
 def test_blob_layout_and_kinematic_constants():
@@ -28,7 +28,6 @@ def test_blob_layout_and_kinematic_constants():
     assert m.field("sph_margin")[0] == 0.002 and m.field("n_sphere")[0] == 1
 
 
-@pytest.mark.skipif(not os.path.exists(SAWYER), reason="reference tree not mounted")
 def test_loader_reproduces_builtin_table_from_the_reference_xml():
     a = load_mjcf(SAWYER).to_flat()
     b = reacher7dof_raw().to_flat()

@@ -196,7 +196,7 @@ def main():
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "pen_hand", "--controller", "dmd",
                         "--particles", str(args.tree_particles), "--horizon", "64", "--steps", str(max(3, args.steps // 10)),
-                        "--warmup", "1", "--process-warmup", "0", "--no-cpu-baseline", "--dtype", args.dtype], check=True)
+                        "--warmup", "1", "--process-warmup", "0", "--no-cpu-baseline", "--full", "--dtype", args.dtype], check=True)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ OUT=$PWD/gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
 for DT in f64 f32; do
-  python3 bench.py --steps 200 --warmup 20 --dtype $DT $([ $DT = f32 ] && echo --no-cpu-baseline) > $OUT/${TAG}_bench_${DT}_line.json 2> $OUT/${TAG}_bench_${DT}.err
+  python3 bench.py --full --steps 200 --warmup 20 --dtype $DT $([ $DT = f32 ] && echo --no-cpu-baseline) > $OUT/${TAG}_bench_${DT}_line.json 2> $OUT/${TAG}_bench_${DT}.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_$DT -o ${TAG}_$DT -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline --dtype $DT > $OUT/${TAG}_bench_${DT}_line_under_rocprof.json 2> $OUT/${TAG}_prof_${DT}.err
 done
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY --output-format csv -d $OUT/${TAG}_pmcS1 -o s1 -- python3 tools/pmc_run.py 4096 f64 > $OUT/${TAG}_pmcS1.log 2>&1

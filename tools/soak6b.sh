@@ -11,7 +11,7 @@ done
 python tools/soak_summary.py $S >> $O
 for w in half_cheetah swimmer hand24 pen_hand tray door gripper; do
   for dt in f64 f32; do
-    timeout 900 python bench.py --workload $w --dtype $dt --steps 400 --warmup 5 --process-warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    timeout 900 python bench.py --full --workload $w --dtype $dt --steps 400 --warmup 5 --process-warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); c=j['config']; print('$w $dt ms/step', round(j['ms_per_step'],4), {k:v for k,v in list(j.items())+list(c.items()) if any(t in k for t in ('fail','diverg','reset','cap'))})" >> $O 2>&1
   done

@@ -6,4 +6,4 @@ cd "$(dirname "$0")/.."
 echo "== (a) nccl world 1, graph"
 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 timeout 180 python tools/rccl_world1.py
 echo "== (b) gloo world 2 on cuda:0"
-timeout 300 python bench.py --gpus 2 --steps 20 --warmup 3 --backend gloo --device 0 --no-cpu-baseline 2>&1 | tail -2 | cut -c1-700
+timeout 300 python bench.py --full --gpus 2 --steps 20 --warmup 3 --backend gloo --device 0 --no-cpu-baseline 2>&1 | tail -2 | cut -c1-700
