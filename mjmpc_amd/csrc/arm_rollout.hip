@@ -464,7 +464,6 @@ __device__ __forceinline__ T mass_matrix_tile(const LinkFrame<T>& L, int l8, T* 
     return d[0];
 }
 
-#ifndef ARM_NO_FLAGS_CODE
 // The same with the diagonals S0 <= s < S1 only (the four-wave shape splits them between two wavefronts: the suffix sums and
 // the composite-inertia products are repeated by both, the shifted dot products and the tile stores are shared out).
 template <int S0, int S1, typename T>
@@ -506,7 +505,6 @@ __device__ __forceinline__ T mass_matrix_tile_part(const LinkFrame<T>& L, int l8
     return d[0];
 }
 
-#endif
 // plane-sphere contact geometry (mjc_PlaneSphere): signed distance, and - if some particle of the wave is within
 // the margin - my dof's entry of the contact Jacobian row and the row velocity J v
 template <typename T, typename MT>
@@ -706,18 +704,6 @@ __device__ __forceinline__ T xj_line_search(const MT& M, T* ldsM, int l8, T a_pr
     return a_prev + alpha * d;
 }
 
-// Developer build -DARM_PER_PARTICLE (round 6, measured: profiles/r06_arm_per_particle_ab.txt): the solver's decisions per
-// PARTICLE (8-lane group) instead of per wavefront, as the tree kernels take them since this round - a particle none of whose
-// rows changes is frozen while its seven wave-mates iterate on, the rank-one correction is taken by the particles with exactly
-// one flipped limit row, the long sine / cosine series by the lanes whose step needs it.
-template <typename T>
-struct ParticleFreeze {
-    bool done = false, act = false, cact = false;
-    T aw = T(0);
-    int z = 0;
-};
-__device__ __forceinline__ bool gany(bool x) { return gsum(x ? 1.0f : 0.0f) > 0.5f; }
-
 // active-set test of the constraint rows at acceleration aw (f32: a row whose residual is within rounding of zero
 // keeps its state - such rows otherwise flip back and forth until the iteration cap, seen a few times per 5e8
 // solves; f64 has never failed to settle and keeps the plain sign test)
@@ -736,29 +722,9 @@ __device__ __forceinline__ void active_set(T aw, T sig, T aref, T jc, T arefc, b
     }
 }
 
-// developer A/B switch (round 4): the two waves of a DUO group trade their chains - see arm_front
-#ifdef ARM_SWAP_ROLES
-constexpr bool ARM_SWAP = true;
-#else
-constexpr bool ARM_SWAP = false;
-#endif
-// developer A/B switch: the SOLVE wave takes E2 (the Euler inverse's hand-over) after its Newton iterations instead of
-// inside the first one - measured (round 4, 4096 x 32 f64): rollout kernel 0.1775 -> 0.186 ms, the inverse's row then
-// arrives with its LDS latency in front of the Euler product; off
-#if defined(ARM_E2_LATE) || defined(ARM_SWAP_ROLES)
-constexpr bool E2_LATE = true;
-#else
-constexpr bool E2_LATE = false;
-#endif
 // DUO launches: which wave evaluates the joint-limit rows (see arm_front)
 template <typename T>
-__device__ __forceinline__ constexpr bool rows_by_dyn() {
-#ifdef ARM_ROWS_IN_SOLVE
-    return false;
-#else
-    return sizeof(T) == 8;
-#endif
-}
+__device__ __forceinline__ constexpr bool rows_by_dyn() { return sizeof(T) == 8; }
 
 // joint-limit row of my dof (MuJoCo mj_instantiateLimit, strict dist < margin(=0)): sig = +-1 (0: no row), and - when
 // some lane of the wavefront has a row - its regulariser D = 1 / R and reference acceleration
@@ -882,30 +848,7 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
     link_frames(M, L);
     ST.mark(1);         // world-frame link quantities
 
-    if constexpr (ROLE == DYN && ARM_SWAP) {
-        // (ARM_SWAP) this wave - the one that also reads the inputs, draws the samples and writes the records - takes the
-        // LIGHT chain: mass matrix, limit rows, then the Euler inverse; the other wave the heavy one: bias forces, constraint
-        // solve, Euler product.  The motor torque travels to it through LDS (read after E1).
-        ldsM[V_TAU + l8] = tau_act;
-        T dg = mass_matrix_tile(L, l8, ldsM);
-        dg += M.link(O_ARMATURE);
-        ldsM[V_JC + l8] = dg;                           // (the Newton matrix's diagonal starts from it; the slot is the other wave's own after E1)
-        ldsM[V_DE + l8] = dg + M.glob(O_TIMESTEP) * M.link(O_DAMPING);
-        ST.mark(4);
-        duo_barrier();                                  // E1: tile, Euler diagonal, limit rows, motor torque out
-        ST.mark(3);
-        Dense<T> F;
-        F.load(ldsM, ldsM + V_DE);
-        F.factor();
-        T col[MAX_LINKS];
-#pragma unroll
-        for (int i = 0; i < MAX_LINKS; ++i) col[i] = (i == l8) ? T(1) : T(0);
-        F.solve(col);
-#pragma unroll
-        for (int i = 0; i < MAX_LINKS; ++i) ldsM[V_EI + l8 * LANES + i] = col[i];
-        ST.mark(6);
-        return;                                         // (E2 is taken in arm_back, behind this wave's records and sampler)
-    }
+    // (the two waves trading chains - this wave the light one - was measured and removed: profiles/r04_arm_swap_phase_clocks.txt)
     if constexpr (ROLE == DYN) {
         // 5. smooth force: -bias + passive damping + motor, handed to the SOLVE wave
         const T bias = bias_force(M, L, v, l8);
@@ -913,7 +856,7 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
         // the joint-limit rows too (a function of q and v alone): this wave reaches E1 ~700 cycles before the SOLVE
         // wave, which used to spend ~800 on them right after it
         // (f64 only: 181 -> 176.5 us per 4096 x 32 launch; in f32, whose scans are single instructions, the DYN wave has
-        // no such slack and the move costs 3 %.  ARM_ROWS_IN_SOLVE: developer A/B switch back to the round-2 split)
+        // no such slack and the move costs 3 %)
         if constexpr (rows_by_dyn<T>()) {
             T sg, Dl, al;
             limit_row(M, q, v, sg, Dl, al);
@@ -943,43 +886,29 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
     }
 
     T bias = T(0);
-    if constexpr (ROLE == SOLO || (ROLE == SOLVE && ARM_SWAP)) bias = bias_force(M, L, v, l8);
+    if constexpr (ROLE == SOLO) bias = bias_force(M, L, v, l8);
     T dgM = T(0);
     const T damping = M.link(O_DAMPING), h = M.glob(O_TIMESTEP);
-    if constexpr (!(ROLE == SOLVE && ARM_SWAP)) {
-        dgM = mass_matrix_tile(L, l8, ldsM);
-        dgM += M.link(O_ARMATURE);
-        ldsM[V_DE + l8] = dgM + h * damping;
-    }
+    dgM = mass_matrix_tile(L, l8, ldsM);
+    dgM += M.link(O_ARMATURE);
+    ldsM[V_DE + l8] = dgM + h * damping;
     if constexpr (ROLE == SOLO) LDS_WAVE_SYNC();
     ST.mark(4);         // (bias forces,) composite inertia, mass matrix, tile
 
     // 5. smooth force: -bias + passive damping + motor (SOLVE: arrives from the DYN wave at E1)
     T tau = -bias - damping * v + tau_act;
-    T sw_sg = T(0), sw_D = T(0), sw_a = T(0);           // (ARM_SWAP: my limit row, evaluated in front of E1 - this wave gets there first)
-    if constexpr (ROLE == SOLVE && ARM_SWAP) limit_row(M, q, v, sw_sg, sw_D, sw_a);
     if constexpr (ROLE == SOLVE) {
         duo_barrier();                                  // E1: tau in; tile and Euler diagonal out
         ST.mark(3);
-        if constexpr (ARM_SWAP) {
-            tau += ldsM[V_TAU + l8];                    // (the motor torque; bias and damping are this wave's own)
-            dgM = ldsM[V_JC + l8];
-        } else {
-            tau = ldsM[V_TAU + l8];
-        }
+        tau = ldsM[V_TAU + l8];
     }
     T ei[MAX_LINKS];            // SOLVE: my row of (M + h B)^-1 (read once the DYN wave has published it)
 
     // 6. constraint rows.  Limits (SOLVE: evaluated by the DYN wave before E1)
     T sig = T(0), dist = T(0), D = T(0), aref = T(0);
     bool inst = false;
-    constexpr bool rows_from_dyn = ROLE == SOLVE && (rows_by_dyn<T>() || ARM_SWAP);
-    if constexpr (ROLE == SOLVE && ARM_SWAP) {
-        sig = sw_sg;
-        D = sw_D;
-        aref = sw_a;
-        inst = sig != T(0);
-    } else if constexpr (rows_from_dyn) {
+    constexpr bool rows_from_dyn = ROLE == SOLVE && rows_by_dyn<T>();
+    if constexpr (rows_from_dyn) {
         sig = ldsM[V_LS + l8];
         D = ldsM[V_LD + l8];
         aref = ldsM[V_LA + l8];
@@ -1027,6 +956,8 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
 
     // 7. primal active-set Newton on  1/2 a'Ma - tau'a + sum_active 1/2 D (J a - aref)^2, and
     // 8. mj_Euler with implicit joint damping:  (M + h B) qacc = qfrc_smooth + qfrc_constraint.
+    // The iteration's decisions (stop, Sherman-Morrison update) are taken per wavefront.  Per-particle decisions were
+    // measured +4.5 % on the headline and removed (profiles/r06_arm_per_particle_ab.txt); commit d8a81fb has them.
     if constexpr (ROLE == SOLVE) {
         // DUO: every lane factors the Newton matrix H = M + J'DJ and substitutes its own unit vector, i.e. holds one
         // column (= row) of H^-1; the acceleration is then a dot product with the right-hand side, and the Euler
@@ -1034,9 +965,6 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
         if (any_rows) {
             if (any_c) ldsM[V_JC + l8] = jc;
             changed = true;
-#ifdef ARM_PER_PARTICLE
-            ParticleFreeze<T> fz;
-#endif
             for (int it = 0; it < newton_maxit<T>(); ++it) {
                 T rhs = tau + (act ? D * sig * aref : T(0));
                 if (any_c) rhs += cact ? Dc * jc * arefc : T(0);
@@ -1062,7 +990,7 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
                 for (int i = 0; i < MAX_LINKS; ++i) col[i] = (i == l8) ? T(1) : T(0);
                 F.solve(col);
                 ST.mark(it == 0 ? 6 : 9);               // factorisation + inverse / further iterations
-                if (it == 0 && !(rows_by_dyn<T>() || ARM_SWAP) && !E2_LATE) {     // (E2 where round 2 had it: this wave arrives ~2000 cycles after E1)
+                if (it == 0 && !rows_by_dyn<T>()) {     // (E2 where round 2 had it: this wave arrives ~2000 cycles after E1)
                     duo_barrier();
 #pragma unroll
                     for (int i = 0; i < MAX_LINKS; ++i) ei[i] = ldsM[V_EI + l8 * LANES + i];
@@ -1087,14 +1015,12 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
                     fl.z = z2;
                     changed = changed || fflip;
                 }
-#ifdef ARM_PER_PARTICLE
-                if (fz.done) { aw = fz.aw; act = fz.act; cact = fz.cact; if constexpr (XJ) fl.z = fz.z; changed = flip = cflip = fflip = false; }
-#endif
                 // E2: the DYN wave needs ~1000 cycles after E1 for (M + h B)^-1; with the limit rows arriving from it
                 // this wave gets HERE in about as many (after the first factorisation it would still wait ~400).  Taking
                 // the rendezvous inside the first iteration rather than at the end of the substep leaves only E3
-                // between the last Newton iteration and the integration.
-                if (it == 0 && (rows_by_dyn<T>() || ARM_SWAP) && !E2_LATE) {
+                // between the last Newton iteration and the integration.  (E2 after the iterations instead: measured in round 4,
+                // 0.1775 -> 0.186 ms per 4096 x 32 f64 launch, and removed.)
+                if (it == 0 && rows_by_dyn<T>()) {
                     duo_barrier();
 #pragma unroll
                     for (int i = 0; i < MAX_LINKS; ++i) ei[i] = ldsM[V_EI + l8 * LANES + i];   // my row of (M + h B)^-1, early
@@ -1107,42 +1033,6 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
                 // dozen instructions instead of a second factorisation.  Several flips in one particle, or a flip of
                 // the contact row, take the general path (next iteration refactors).
                 const float nflip = gsum(flip ? 1.0f : 0.0f);
-#ifdef ARM_PER_PARTICLE
-                if (!fz.done && !gany(changed)) { fz.done = true; fz.aw = aw; fz.act = act; fz.cact = cact; fz.z = fl.z; }
-                const bool single = !XJ && !fz.done && nflip > 0.5f && nflip < 1.5f && !gany(cflip);
-                if (__any(single)) {
-                    if (single && flip) {
-                        T zjj = col[0];
-#pragma unroll
-                        for (int i = 1; i < MAX_LINKS; ++i) zjj = (l8 == i) ? col[i] : zjj;
-                        const T c = act ? D : -D;
-                        ldsM[V_XH + 0] = (T)l8;
-                        ldsM[V_XH + 1] = c;
-                        ldsM[V_XH + 2] = c * sig * aref;
-                        ldsM[V_XH + 3] = zjj;
-                        ldsM[V_XH + 4] = aw;
-                    }
-                    LDS_WAVE_SYNC();
-                    if (single) {
-                        const int j = (int)ldsM[V_XH + 0];
-                        const T c = ldsM[V_XH + 1], dl = ldsM[V_XH + 2], zjj = ldsM[V_XH + 3], aj = ldsM[V_XH + 4];
-                        T z = col[0];
-#pragma unroll
-                        for (int i = 1; i < MAX_LINKS; ++i) z = (j == i) ? col[i] : z;
-                        const T yj = aj + dl * zjj;
-                        aw = (aw + dl * z) - c * z * yj * rcp_(T(1) + c * zjj);
-                    }
-                    active_set(aw, sig, aref, jc, arefc, inst, cinst, act, cact, act2, cact2);
-                    if (single) {
-                        changed = (act2 != act) || (cact2 != cact);
-                        act = act2;
-                        cact = cact2;
-                    }
-                    if (!fz.done && !gany(changed)) { fz.done = true; fz.aw = aw; fz.act = act; fz.cact = cact; fz.z = fl.z; }
-                    ST.mark(9);
-                    if (!__any(changed)) break;
-                }
-#else
                 if (!XJ && !__any(cflip || nflip > 1.5f || fflip)) {   // (XJ: every change refactors and goes through the line search)
                     if (flip) {
                         T zjj = col[0];
@@ -1177,7 +1067,6 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
                     ST.mark(9);
                     if (!__any(changed)) break;
                 }
-#endif
                 LDS_WAVE_SYNC();                        // V_RH is rewritten
             }
             if (changed && diag) atomicAdd(diag, 1u);
@@ -1191,7 +1080,7 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
             }
         }
         ldsM[V_RE + l8] = tau + qfrc_c;
-        if (!any_rows || E2_LATE) {
+        if (!any_rows) {
             duo_barrier();                              // E2 (substeps without rows; otherwise taken inside the loop)
 #pragma unroll
             for (int i = 0; i < MAX_LINKS; ++i) ei[i] = ldsM[V_EI + l8 * LANES + i];
@@ -1215,9 +1104,6 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
     if (any_rows) {
         changed = true;
         if (any_c) ldsM[V_JC + l8] = jc;
-#ifdef ARM_PER_PARTICLE
-        ParticleFreeze<T> fz;
-#endif
         for (int it = 0; it < newton_maxit<T>(); ++it) {
             T rhs = tau + (act ? D * sig * aref : T(0));
             if (any_c) rhs += cact ? Dc * jc * arefc : T(0);
@@ -1263,10 +1149,6 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
                 changed = changed || z2 != fl.z;
                 fl.z = z2;
             }
-#ifdef ARM_PER_PARTICLE
-            if (fz.done) { aw = fz.aw; act = fz.act; cact = fz.cact; if constexpr (XJ) fl.z = fz.z; changed = false; }
-            else if (!gany(changed)) { fz.done = true; fz.aw = aw; fz.act = act; fz.cact = cact; fz.z = fl.z; }
-#endif
             ST.mark(it == 0 ? 8 : 9);                   // first solve + active-set check / further iterations
             if (!__any(changed)) break;
         }
@@ -1342,14 +1224,8 @@ __device__ __forceinline__ void q_post(qflag_ptr qf, int which, int seq, int lan
 // the wait after 2^21 polls (~0.1 s) with the sticky flag QF_STUCK, which the launch reports through the solver-failure counter
 // instead of hanging the GPU)
 __device__ __forceinline__ void q_wait(qflag_ptr qf, int which, int seq) {
-#ifdef ARM_QWAIT_NOP            // developer timing experiment: no waiting at all (the results are void)
-    return;
-#endif
     int spins = 0;
     while (__builtin_amdgcn_readfirstlane(q_read(qf, which)) < seq) {
-#ifdef ARM_QUAD_SLEEP           // developer A/B: sleep between polls (s_sleep n = 64 n + 1..64 clocks)
-        __builtin_amdgcn_s_sleep(ARM_QUAD_SLEEP);
-#endif
         if (++spins > (1 << 21)) { q_write(qf, QF_STUCK, 1); break; }
     }
     asm volatile("" ::: "memory");
@@ -1370,7 +1246,6 @@ __device__ __forceinline__ void q_take(qflag_ptr qf, int which, int seq, F&& loa
     asm volatile("" ::: "memory");          // (the data loads stay behind the flag loads)
     loads();
     asm volatile("" ::: "memory");
-#ifndef ARM_QWAIT_NOP
     if (__builtin_expect(!(__builtin_amdgcn_readfirstlane(tag) >= seq && __builtin_amdgcn_readfirstlane(tag2) >= seq), 0)) {
         int spins = 0;
         for (;;) {
@@ -1383,27 +1258,19 @@ __device__ __forceinline__ void q_take(qflag_ptr qf, int which, int seq, F&& loa
             if (++spins > (1 << 21)) { q_write(qf, QF_STUCK, 1); break; }
         }
     }
-#endif
     __builtin_amdgcn_sched_barrier(0);
 }
 
-#ifndef ARM_NO_FLAGS_CODE
 // NW = 4: the diagonals 0 ... ARM_NEAR_DIAGS - 1 of the mass matrix stay with the solving wave, the others go to QMASS (which
 // starts a hand-over later but has nothing else to do).  Measured at 1024 x 32 f64: 1: 176.0, 2: 174.4, 3: 171.1, 4: 172.7 us
-#ifndef ARM_NEAR_DIAGS
-#define ARM_NEAR_DIAGS 3
-#endif
+constexpr int ARM_NEAR_DIAGS = 3;
 template <int ROLE, int NW, typename T, typename MT>
 __device__ __forceinline__ void flag_front(const MT& M, const ArmInts& I, T& q, T& v, T& aw, T& sq, T& cq, int& rows,
                                            T tau_act, T* ldsM, qflag_ptr qf, int seq, int lane, int l8, T* site,
                                            unsigned* diag, bool& free_step, Stamps& ST, ResetCtl* rc = nullptr) {
     constexpr bool ROWS_MINE = ROLE == QAUX || (ROLE == QDYN && NW == 2);       // who evaluates the limit rows and inverts M + h B
     constexpr bool SPLIT = NW == 4;                                             // the mass matrix's diagonals on two waves
-#ifdef ARM_CONTACT_IN_SOLVE     // developer A/B
-    constexpr bool CONTACT_BY_AUX = false;
-#else
     constexpr bool CONTACT_BY_AUX = NW == 4;        // the contact row comes from QAUX (which waits ~2900 cycles per substep for the tile)
-#endif
     free_step = false;
 #ifdef MJMPC_NO_RESET
     rc = nullptr;
@@ -1561,9 +1428,6 @@ __device__ __forceinline__ void flag_front(const MT& M, const ArmInts& I, T& q, 
         if (any_rows) {
             if (!CONTACT_BY_AUX && any_c) ldsM[V_JC + l8] = jc;
             changed = true;
-#ifdef ARM_PER_PARTICLE
-            ParticleFreeze<T> fz;
-#endif
             for (int it = 0; it < newton_maxit<T>(); ++it) {
                 // the rows' parts of the right-hand side; tau joins them when it has arrived:  rhs = (tau + limit) + contact
                 ldsM[V_DH + l8] = dgM + (act ? D : T(0));
@@ -1613,9 +1477,6 @@ __device__ __forceinline__ void flag_front(const MT& M, const ArmInts& I, T& q, 
                 changed = flip || cflip;
                 act = act2;
                 cact = cact2;
-#ifdef ARM_PER_PARTICLE
-                if (fz.done) { aw = fz.aw; act = fz.act; cact = fz.cact; changed = flip = cflip = false; }
-#endif
                 if (it == 0) {
                     ST.mark(8);
                     q_take(qf, QF_EI, seq, [&]() {          // my row of (M + h B)^-1
@@ -1628,43 +1489,6 @@ __device__ __forceinline__ void flag_front(const MT& M, const ArmInts& I, T& q, 
                 if (!__any(changed)) break;
                 // one limit row of a particle changed state: Sherman-Morrison instead of a second factorisation (arm_front)
                 const float nflip = gsum(flip ? 1.0f : 0.0f);
-#ifdef ARM_PER_PARTICLE
-                if (!fz.done && !gany(changed)) { fz.done = true; fz.aw = aw; fz.act = act; fz.cact = cact; }
-                const bool single = !fz.done && nflip > 0.5f && nflip < 1.5f && !gany(cflip);
-                if (__any(single)) {
-                    LDS_WAVE_SYNC();                    // (V_XH: the contact parts have been read)
-                    if (single && flip) {
-                        T zjj = col[0];
-#pragma unroll
-                        for (int i = 1; i < MAX_LINKS; ++i) zjj = (l8 == i) ? col[i] : zjj;
-                        const T c = act ? D : -D;
-                        ldsM[V_XH + 0] = (T)l8;
-                        ldsM[V_XH + 1] = c;
-                        ldsM[V_XH + 2] = c * sig * aref;
-                        ldsM[V_XH + 3] = zjj;
-                        ldsM[V_XH + 4] = aw;
-                    }
-                    LDS_WAVE_SYNC();
-                    if (single) {
-                        const int j = (int)ldsM[V_XH + 0];
-                        const T c = ldsM[V_XH + 1], dl = ldsM[V_XH + 2], zjj = ldsM[V_XH + 3], aj = ldsM[V_XH + 4];
-                        T z = col[0];
-#pragma unroll
-                        for (int i = 1; i < MAX_LINKS; ++i) z = (j == i) ? col[i] : z;
-                        const T yj = aj + dl * zjj;
-                        aw = (aw + dl * z) - c * z * yj * rcp_(T(1) + c * zjj);
-                    }
-                    active_set(aw, sig, aref, jc, arefc, inst, cinst, act, cact, act2, cact2);
-                    if (single) {
-                        changed = (act2 != act) || (cact2 != cact);
-                        act = act2;
-                        cact = cact2;
-                    }
-                    if (!fz.done && !gany(changed)) { fz.done = true; fz.aw = aw; fz.act = act; fz.cact = cact; }
-                    ST.mark(9);
-                    if (!__any(changed)) break;
-                }
-#else
                 if (!__any(cflip || nflip > 1.5f)) {
                     LDS_WAVE_SYNC();                    // (V_XH: the contact parts have been read)
                     if (flip) {
@@ -1695,7 +1519,6 @@ __device__ __forceinline__ void flag_front(const MT& M, const ArmInts& I, T& q, 
                     ST.mark(9);
                     if (!__any(changed)) break;
                 }
-#endif
                 LDS_WAVE_SYNC();                        // V_RH / V_XH are rewritten
             }
             if (changed && diag) atomicAdd(diag, 1u);
@@ -1730,7 +1553,6 @@ __device__ __forceinline__ void flag_front(const MT& M, const ArmInts& I, T& q, 
     }
 }
 
-#endif
 // second half of a substep: take delivery of qacc and integrate (every role runs the same instructions)
 template <int ROLE, typename T, typename MT, typename RST = NoResetRecord>
 __device__ __forceinline__ void arm_back(const MT& M, T& q, T& v, T& aw, T& sq, T& cq, T* ldsM, int l8,
@@ -1738,15 +1560,6 @@ __device__ __forceinline__ void arm_back(const MT& M, T& q, T& v, T& aw, T& sq, 
                                          unsigned* diag = nullptr, RST record = RST(), qflag_ptr qf = nullptr,
                                          int seq = 0) {
     ST.mark(11);        // DYN: env-step records
-    if constexpr (ROLE == DYN && ARM_SWAP) { duo_barrier(); ST.mark(7); }      // E2: inverse out (the other wave takes it after its Newton iterations)
-#ifdef ARM_AB_BACK
-    if constexpr (ROLE == SOLO) LDS_WAVE_SYNC();
-    else duo_barrier();
-    ST.mark(12);
-    const T h = M.glob(O_TIMESTEP);
-    {
-        T x = ldsM[V_XE + l8];
-#else
     T x;
     if constexpr (ROLE == QDYN || ROLE == QMASS || ROLE == QAUX) {
         q_take(qf, QF_X, seq, [&]() { x = ldsM[V_XE + l8]; });          // flag shapes: qacc is out
@@ -1757,65 +1570,59 @@ __device__ __forceinline__ void arm_back(const MT& M, T& q, T& v, T& aw, T& sq, 
     }
     ST.mark(12);        // wait at B
     const T h = M.glob(O_TIMESTEP);
-    {
-#endif
-        if (free_step) aw = x;
-        // explicitly rounded products and sums: the two waves of a DUO group must compute bit-identical (q, v), so the
-        // compiler may not contract these differently in the two instantiations
-        v = add_rn(v, mul_rn(h, x));
-        const T dq = mul_rn(h, v);
-        q = add_rn(q, dq);
-        const bool slide = M.xj_slide();                // (XJ: a slide joint advances q alone - its (sin, cos) stay (0, 1))
-        const T dqa = slide ? T(0) : dq;
-        // advance (sin q, cos q) by dq: angle addition with a short series, one Newton step of renormalisation.
-        // Large steps (|dq| > 0.25 rad per substep, never seen with h = 0.01): series at dq / 256, doubled back up.
-        // (ONE wave-level test guards everything rare about the integration - this, and MuJoCo's reset on instability below: a
-        // NaN or an entry beyond mjMAXVAL = 1e10 in the acceleration or the integrated state makes |dq| = h |v| huge or NaN)
-        T sd, cd;
-        const bool big = __any(!(fabs(dq) <= (slide ? T(1e5) : T(0.25))));
-        if (__builtin_expect(big, 0)) {
-            sincos_small(dqa * T(1.0 / 256.0), sd, cd);
-            for (int k = 0; k < 8; ++k) {
-                const T s2 = T(2) * sd * cd;
-                cd = T(1) - T(2) * sd * sd;
-                sd = s2;
-            }
-#ifdef ARM_PER_PARTICLE
-            if (fabs(dq) <= (slide ? T(1e5) : T(0.25))) sincos_small(dqa, sd, cd);     // (the long series in the lanes that need it)
-#endif
-        } else {
-            sincos_small(dqa, sd, cd);
+    if (free_step) aw = x;
+    // explicitly rounded products and sums: the two waves of a DUO group must compute bit-identical (q, v), so the
+    // compiler may not contract these differently in the two instantiations
+    v = add_rn(v, mul_rn(h, x));
+    const T dq = mul_rn(h, v);
+    q = add_rn(q, dq);
+    const bool slide = M.xj_slide();                // (XJ: a slide joint advances q alone - its (sin, cos) stay (0, 1))
+    const T dqa = slide ? T(0) : dq;
+    // advance (sin q, cos q) by dq: angle addition with a short series, one Newton step of renormalisation.
+    // Large steps (|dq| > 0.25 rad per substep, never seen with h = 0.01): series at dq / 256, doubled back up.
+    // (ONE wave-level test guards everything rare about the integration - this, and MuJoCo's reset on instability below: a
+    // NaN or an entry beyond mjMAXVAL = 1e10 in the acceleration or the integrated state makes |dq| = h |v| huge or NaN)
+    T sd, cd;
+    const bool big = __any(!(fabs(dq) <= (slide ? T(1e5) : T(0.25))));
+    if (__builtin_expect(big, 0)) {
+        sincos_small(dqa * T(1.0 / 256.0), sd, cd);
+        for (int k = 0; k < 8; ++k) {
+            const T s2 = T(2) * sd * cd;
+            cd = T(1) - T(2) * sd * sd;
+            sd = s2;
         }
-        const T s1 = sq * cd + cq * sd, c1 = cq * cd - sq * sd;
-        const T k = T(1.5) - T(0.5) * (s1 * s1 + c1 * c1);
-        sq = s1 * k;
-        cq = c1 * k;
+    } else {
+        sincos_small(dqa, sd, cd);
+    }
+    const T s1 = sq * cd + cq * sd, c1 = cq * cd - sq * sd;
+    const T k = T(1.5) - T(0.5) * (s1 * s1 + c1 * c1);
+    sq = s1 * k;
+    cq = c1 * k;
 #ifdef MJMPC_NO_RESET
-        rc = nullptr;
+    rc = nullptr;
 #endif
-        if (rc && __builtin_expect(big, 0)) {
-            // the substep's test (ResetCtl).  The acceleration every role holds is the Euler solve's (M + h B)^-1
-            // (qfrc_smooth + qfrc_constraint), which stands in for mj_forward's qacc
-            const unsigned long long bal = __ballot(mj_is_bad(x) || mj_is_bad(q) || mj_is_bad(v));
-            if (bal != 0ull) {
-                rc->any = true;
-                const unsigned long long mine = particle_lanes(lane);
-                const double* rst = record();
-                if (rst == nullptr) {
-                    // (no record: the launch that makes it)
-                } else if (__ballot(mj_is_bad(x)) & mine) {
-                    // mj_checkAcc: mj_resetData, mj_forward again, mj_Euler from the reset state = the record
-                    q = (T)rst[l8];
-                    v = (T)rst[LANES + l8];
-                    sq = (T)rst[2 * LANES + 3 + l8];
-                    cq = (T)rst[3 * LANES + 3 + l8];
-                    aw = T(0);
-                    const int f0 = rflags<ROLE>(ldsM);
-                    rflags_set<ROLE>(ldsM, f0 | 1 | 4 | RST_EVER);
-                    if (role_counts<ROLE>() && diag && l8 == 0 && rc->count) { atomicAdd(diag + 1, 1u); if (f0 & RST_REAL) atomicAdd(diag + 2, 1u); }
-                } else if (bal & mine) {
-                    rflags_set<ROLE>(ldsM, rflags<ROLE>(ldsM) | 2);
-                }
+    if (rc && __builtin_expect(big, 0)) {
+        // the substep's test (ResetCtl).  The acceleration every role holds is the Euler solve's (M + h B)^-1
+        // (qfrc_smooth + qfrc_constraint), which stands in for mj_forward's qacc
+        const unsigned long long bal = __ballot(mj_is_bad(x) || mj_is_bad(q) || mj_is_bad(v));
+        if (bal != 0ull) {
+            rc->any = true;
+            const unsigned long long mine = particle_lanes(lane);
+            const double* rst = record();
+            if (rst == nullptr) {
+                // (no record: the launch that makes it)
+            } else if (__ballot(mj_is_bad(x)) & mine) {
+                // mj_checkAcc: mj_resetData, mj_forward again, mj_Euler from the reset state = the record
+                q = (T)rst[l8];
+                v = (T)rst[LANES + l8];
+                sq = (T)rst[2 * LANES + 3 + l8];
+                cq = (T)rst[3 * LANES + 3 + l8];
+                aw = T(0);
+                const int f0 = rflags<ROLE>(ldsM);
+                rflags_set<ROLE>(ldsM, f0 | 1 | 4 | RST_EVER);
+                if (role_counts<ROLE>() && diag && l8 == 0 && rc->count) { atomicAdd(diag + 1, 1u); if (f0 & RST_REAL) atomicAdd(diag + 2, 1u); }
+            } else if (bal & mine) {
+                rflags_set<ROLE>(ldsM, rflags<ROLE>(ldsM) | 2);
             }
         }
     }
@@ -2107,7 +1914,6 @@ __global__ __launch_bounds__(DUO ? 128 : 64) __attribute__((amdgpu_waves_per_eu(
     int seq = 0;
 #include "arm_rollout_body.inc"
 }
-#ifndef ARM_NO_FLAGS_CODE
 // The flag-synchronised shapes: NW = 2 (a 128-thread workgroup, as DUO) and NW = 4 (P <= 2048 on 256 CUs: a 256-thread
 // workgroup = the four waves of a particle group, one per SIMD of a CU)
 template <typename T, int NW, bool MONO>
@@ -2126,8 +1932,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1)))
     int seq = 0;                            // substep sequence number
 #include "arm_rollout_body.inc"
 }
-
-#endif
 }  // namespace
 
 // (the extended-joint build exports the same two entry points under its own names: arm_rollout.h)
@@ -2179,28 +1983,29 @@ hipError_t launch_arm_rollout(const T* model, const double* state, long P, int H
     const bool one_per_simd = !duo && !fuse.clw && (one_env >= 0 ? one_env != 0 : (long)grid <= simds);
     const MonoStep mono_arg = mono ? *mono : MonoStep();
     const size_t dyn = mono ? sizeof(double) * MONO_RED + sizeof(T) * LANES * (size_t)H * A : 0;
-#ifndef ARM_NO_FLAGS_CODE
     // Round 6: the flag-synchronised shape with four wavefronts per particle group while every one of them still has a SIMD
     // of its own (P <= 2048 on 256 CUs) - the launches that are BASELINE config 2 and the shards of a strong-scaling run.
     // Above that DUO stays (the two-wave flag shape measures 4 % slower than DUO at 4096 particles: profiles/r06_arm_shapes.txt).
     // The real-env step (state_out) keeps DUO.  MJMPC_ARM_FLAGS=0 (DUO) / 2 / 4 overrides the choice (developer A/B switch).
-    static const int flags_env = [] { const char* e = getenv("MJMPC_ARM_FLAGS"); return e ? atoi(e) : -1; }();
-    int nw = 0;
-    if (duo && !state_out && duo_env < 0) nw = flags_env >= 0 ? flags_env : (4L * grid <= simds ? 4 : 0);
-    if (nw == 2 || nw == 4) {
-        if (mono) {
-            if (obs || nobs || !fuse.gseq || !mono->chol || !mono->tree) return hipErrorInvalidValue;
-            if (dyn + sizeof(T) * (LANES * PSTRIDE + ARM_BLOB_LEN + 3) > 64 * 1024) return hipErrorInvalidValue;
-        }
+    // The extended-joint build leaves these shapes out (arm_rollout_xj.hip).
+    if constexpr (!XJ) {
+        static const int flags_env = [] { const char* e = getenv("MJMPC_ARM_FLAGS"); return e ? atoi(e) : -1; }();
+        int nw = 0;
+        if (duo && !state_out && duo_env < 0) nw = flags_env >= 0 ? flags_env : (4L * grid <= simds ? 4 : 0);
+        if (nw == 2 || nw == 4) {
+            if (mono) {
+                if (obs || nobs || !fuse.gseq || !mono->chol || !mono->tree) return hipErrorInvalidValue;
+                if (dyn + sizeof(T) * (LANES * PSTRIDE + ARM_BLOB_LEN + 3) > 64 * 1024) return hipErrorInvalidValue;
+            }
 #define MJMPC_LAUNCH_F(NW_, MONO_)                                                                                        \
-        hipLaunchKernelGGL((arm_rollout_flags_kernel<T, NW_, MONO_>), dim3(grid), dim3(64 * NW_), dyn, stream, model, state, P, H, A, \
-                           mean, noise, cost, act, obs, nobs, diag, fuse, mono_arg)
-        if (nw == 4) { if (mono) MJMPC_LAUNCH_F(4, true); else MJMPC_LAUNCH_F(4, false); }
-        else { if (mono) MJMPC_LAUNCH_F(2, true); else MJMPC_LAUNCH_F(2, false); }
+            hipLaunchKernelGGL((arm_rollout_flags_kernel<T, NW_, MONO_>), dim3(grid), dim3(64 * NW_), dyn, stream, model, state, P, H, A, \
+                               mean, noise, cost, act, obs, nobs, diag, fuse, mono_arg)
+            if (nw == 4) { if (mono) MJMPC_LAUNCH_F(4, true); else MJMPC_LAUNCH_F(4, false); }
+            else { if (mono) MJMPC_LAUNCH_F(2, true); else MJMPC_LAUNCH_F(2, false); }
 #undef MJMPC_LAUNCH_F
-        return hipGetLastError();
+            return hipGetLastError();
+        }
     }
-#endif
 #define MJMPC_LAUNCH_W(STEP_, CL_, W_, DUO_, MONO_)                                                                   \
     hipLaunchKernelGGL((arm_rollout_kernel<T, STEP_, CL_, W_, DUO_, MONO_>), dim3(grid), dim3(DUO_ ? 128 : 64), dyn,  \
                        stream, model, state, P, H, A, mean, noise, cost, act, obs, nobs, state_out, diag, fuse, mono_arg)

@@ -104,7 +104,6 @@
             ST.flush(diag, 1, lane);
         }
         if constexpr (!MONO) return;
-#ifndef ARM_NO_FLAGS_CODE
     } else if (QUAD && wave >= 1) { // flag shapes: the waves beside the one that owns inputs and records (flag_front)
         if constexpr (QUAD) {
             bool fs;
@@ -123,7 +122,6 @@
             ST.flush(diag, wave, lane);
         }
         if constexpr (!MONO) return;
-#endif
     } else {
 
     // inputs of step t+1 are fetched while step t computes (a lone wave would otherwise sit out the full
@@ -152,9 +150,6 @@
         key_h = (unsigned long long)((pid + mop->particle_offset) * A + l8);
     }
     auto draw = [&](int t) -> T {
-#ifdef MONO_NO_DRAW                 // developer A/B builds (tools/mono_time.py; NB: constant actions change the physics too)
-        return T(0.25);
-#endif
         const double chol_aa = chol_h;
         float z = 0.0f;
         if (sampled) {
@@ -231,13 +226,10 @@
         if (__builtin_expect(rc.any, 0)) rflags_set<R>(ldsM, rflags<R>(ldsM) & (2 | RST_EVER | RST_OPTS));     // a new env step: do_simulation writes data.ctrl again (a pending reset stays)
         for (int sub = 0; sub < I.frame_skip; ++sub) {
             if ((R == DYN || R == QDYN) && sub > 0) arm_back<R>(M, q, v, aw, sinq, cosq, ldsM, l8, fs, ST, lane, &rc, diag, record, qf, seq);
-#ifndef ARM_NO_FLAGS_CODE
             if constexpr (QUAD) {
                 ++seq;
                 flag_front<R, NW>(M, I, q, v, aw, sinq, cosq, rows, tau_act, ldsM, qf, seq, lane, l8, site, diag, fs, ST, &rc);
-            } else
-#endif
-            {
+            } else {
                 arm_front<R>(M, I, q, v, aw, sinq, cosq, rows, tau_act, ldsM, lane, l8, site, diag, fs, ST, &rc);
             }
             if constexpr (R == SOLO) arm_back<R>(M, q, v, aw, sinq, cosq, ldsM, l8, fs, ST, lane, &rc, diag, record);
@@ -274,19 +266,13 @@
                     if (fuse.gseq) q0acc = INFINITY;
                 }
             }
-#ifndef ARM_NO_FIXUP            // (developer A/B)
             if (__builtin_expect(rc.any, 0) && !(rflags<R>(ldsM) & RST_INF)) {
                 // the last substep ended in mj_checkAcc's reset: site_xpos is the reset state's (mj_forward ran again) - the
                 // cost written ahead of the integration above is written again
                 // (the substep began from a state mj_checkPos / mj_checkVel passed: its site and the cost from it are finite)
                 if (rflags<R>(ldsM) & 4) {
-#ifdef ARM_FIXUP_LIVE           // (developer A/B: the cost written above kept live instead of made again)
-                    T ex, ey, ez;
-                    const T c_old = cst;
-#else
                     T ex = site[0] - tgt[0], ey = site[1] - tgt[1], ez = site[2] - tgt[2];
                     const T c_old = fabs(ex) + fabs(ey) + fabs(ez) + T(5) * sqrt_(ex * ex + ey * ey + ez * ez);
-#endif
                     for (int k = 0; k < 3; ++k) site[k] = (T)record()[2 * LANES + k];
                     ex = site[0] - tgt[0]; ey = site[1] - tgt[1]; ez = site[2] - tgt[2];
                     const T c_new = fabs(ex) + fabs(ey) + fabs(ez) + T(5) * sqrt_(ex * ex + ey * ey + ez * ez);
@@ -294,7 +280,6 @@
                     if (fuse.gseq) q0acc += fuse.gseq[t] * ((double)c_new - (double)c_old);
                 }
             }
-#endif
         }
         if (live && (obs || nobs)) {
             const long o = (pid * H + t) * dobs;

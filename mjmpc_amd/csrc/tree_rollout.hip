@@ -57,15 +57,12 @@ constexpr int TREE_MAXIT = 16;
 // proper, which terminates - a finite number of active sets, a strictly decreasing convex cost) may run on to MuJoCo's own
 // cap: round 3 stopped it at 16 and counted a handful of particle-substeps per 10^8 on the pen-in-hand model as failures
 constexpr int TREE_MAXIT_LS = 100;
-#ifndef TREE_DPP_SUBTREE
-#define TREE_DPP_SUBTREE 1
-#endif
-// developer switch for phase timing (tools/tree_time.py with a build -DTREE_SKIP=bits): 1 = no Newton iteration,
-// 2 = no Euler factor/solve, 4 = no mass-matrix assembly, 8 = no bias forces, 16 = the constraint stage without its iterations,
-// 32 = with exactly one, 64 = no cone line search.  Product builds: 0.
-#ifndef TREE_SKIP
-#define TREE_SKIP 0
-#endif
+// the iteration from which the exact line search takes over, with / without friction-loss rows (LS_START in the kernel)
+template <typename T>
+constexpr int tree_ls_start_floss() { return sizeof(T) == 8 ? 1 : 2; }
+constexpr int TREE_LS_START_PYR = 5;
+// dense instantiations of up to this many lanes refactor instead of taking the rank-one correction (RANK1 in the kernel)
+constexpr int TREE_RANK1_OFF_DN = 16;
 // developer builds (-DTREE_STATS, tools/tree_stats.py): shader-clock per phase and Newton iteration counts of the first
 // particle of the launch, accumulated behind the failure counter (diag + 2 ... as 64-bit words)
 #ifdef TREE_STATS
@@ -399,74 +396,42 @@ __device__ __forceinline__ void path_sum(T* x, const Topo& tp, T* X, int l) {
     }
 }
 
-// x[c] <- sum over my subtree (myself included) of x[c]; subtree = links [l, l + subsize): doubling tables in two
-// LDS buffers of NC x 32, the blocks of sizes 2^k that tile the range are added as the tables appear
+// x[c] <- sum over my subtree (myself included) of x[c]; subtree = links [l, l + tp.subsize)
 template <int NC, int PL, int NL = 32, typename T>
-__device__ __forceinline__ void subtree_sum(T* x, const Topo& tp, T* X, int l) {
-    static_assert(NC <= 6, "two buffers of NC x PL must fit the 12 x PL exchange area");
-    if constexpr (TREE_DPP_SUBTREE) {
-        // The suffix sums S_l = x_l + ... + x_(end of my TREE) are zero-filling DPP row shifts (a 16-lane particle is one
-        // row; a 32-lane one adds the second row's total to the first: its lane 0, by a row swap and a broadcast), and
-        // the subtree [l, l + n) is S_l - S_{l+n}, one ds_bpermute per dword - no LDS round trip.  The scan is SEGMENTED at
-        // the roots (tp.seg_end): a light object listed before a heavy manipulator would otherwise lose its inertia in
-        // the difference.  Inside one tree the difference still cancels: relative error eps * (what follows me in my tree
-        // / my subtree), a few tens on the models here - against the exact doubling tables below (TREE_DPP_SUBTREE = 0).
-        const int end = l + tp.subsize;
+__device__ __forceinline__ void subtree_sum(T* x, const Topo& tp, int l) {
+    // The suffix sums S_l = x_l + ... + x_(end of my TREE) are zero-filling DPP row shifts (a 16-lane particle is one
+    // row; a 32-lane one adds the second row's total to the first: its lane 0, by a row swap and a broadcast), and
+    // the subtree [l, l + n) is S_l - S_{l+n}, one ds_bpermute per dword - no LDS round trip.  The scan is SEGMENTED at
+    // the roots (tp.seg_end): a light object listed before a heavy manipulator would otherwise lose its inertia in
+    // the difference.  Inside one tree the difference still cancels: relative error eps * (what follows me in my tree
+    // / my subtree), a few tens on the models here - against exact doubling tables in LDS.
+    const int end = l + tp.subsize;
 #pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            // (round 5: shifts beyond the instantiation's link count NL move nothing - compiled out: a chain of two links takes
-            // one of the four steps.  As wave-uniform run-time branches on the model's link count they cost the cheetah 1.5 %)
-            T s = x[c];
-            T t = dpp_zero<0x101>(s);
-            s += l + 1 < tp.seg_end ? t : T(0);
-            if constexpr (NL > 2) {
-                t = dpp_zero<0x102>(s);
-                s += l + 2 < tp.seg_end ? t : T(0);
-            }
-            if constexpr (NL > 4) {
-                t = dpp_zero<0x104>(s);
-                s += l + 4 < tp.seg_end ? t : T(0);
-            }
-            if constexpr (NL > 8) {
-                t = dpp_zero<0x108>(s);
-                s += l + 8 < tp.seg_end ? t : T(0);
-            }
-            if constexpr (PL == 32) {
-                const T other = bcast_row<0>(swap_rows(s));     // lane 0 of the particle's OTHER row, in every lane of mine
-                s += (l < 16 && tp.seg_end > 16) ? other : T(0);
-            }
-            const T tail = __shfl(s, end & (PL - 1), PL);
-            x[c] = s - (end < tp.seg_end ? tail : T(0));
+    for (int c = 0; c < NC; ++c) {
+        // (round 5: shifts beyond the instantiation's link count NL move nothing - compiled out: a chain of two links takes
+        // one of the four steps.  As wave-uniform run-time branches on the model's link count they cost the cheetah 1.5 %)
+        T s = x[c];
+        T t = dpp_zero<0x101>(s);
+        s += l + 1 < tp.seg_end ? t : T(0);
+        if constexpr (NL > 2) {
+            t = dpp_zero<0x102>(s);
+            s += l + 2 < tp.seg_end ? t : T(0);
         }
-        return;
+        if constexpr (NL > 4) {
+            t = dpp_zero<0x104>(s);
+            s += l + 4 < tp.seg_end ? t : T(0);
+        }
+        if constexpr (NL > 8) {
+            t = dpp_zero<0x108>(s);
+            s += l + 8 < tp.seg_end ? t : T(0);
+        }
+        if constexpr (PL == 32) {
+            const T other = bcast_row<0>(swap_rows(s));     // lane 0 of the particle's OTHER row, in every lane of mine
+            s += (l < 16 && tp.seg_end > 16) ? other : T(0);
+        }
+        const T tail = __shfl(s, end & (PL - 1), PL);
+        x[c] = s - (end < tp.seg_end ? tail : T(0));
     }
-    constexpr int LOG = PL == 32 ? 5 : 4;
-    T cur[NC], acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) { cur[c] = x[c]; acc[c] = T(0); }
-    int pos = l;
-#pragma unroll
-    for (int k = 0; k <= LOG; ++k) {
-        T* buf = X + (k & 1) * NC * PL;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) buf[c * PL + l] = cur[c];      // T_k[l]
-        TSYNC();
-        if ((tp.subsize >> k) & 1) {
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[c] += buf[c * PL + pos];
-            pos += 1 << k;
-        }
-        if (k < LOG) {
-            const int nb = l + (1 << k);
-            if (nb < PL) {
-#pragma unroll
-                for (int c = 0; c < NC; ++c) cur[c] += buf[c * PL + nb];   // T_{k+1}[l] = T_k[l] + T_k[l + 2^k]
-            }
-        }
-    }
-    TSYNC();
-#pragma unroll
-    for (int c = 0; c < NC; ++c) x[c] = acc[c];
 }
 
 // first tangent of the contact frame: mju_makeFrame's rule - the hint (capsule axis) made orthogonal to the normal, or,
@@ -519,12 +484,7 @@ __device__ __forceinline__ void tree_row_params(const T* sol, T r, T diag_approx
 // triangular solves take the trunk's levels as broadcast FMAs.  kt is the same for every particle of a launch.
 template <int DP>
 struct Trunk { static constexpr int KT = DP < 16 ? DP : 16; };
-// pivot reciprocals of the in-register factorisations (-DTREE_PIVOT_RCP_FAST: developer A/B switch, one Newton step on v_rcp_f64)
-#ifdef TREE_PIVOT_RCP_FAST
-#define PIVOT_RCP rcp_fast
-#else
-#define PIVOT_RCP rcp_
-#endif
+// (pivot reciprocals with one Newton step on v_rcp_f64: measured and removed, profiles/r05_tail24_ab.txt)
 
 // ra[col] = A[l][col] (col <= l < kt, absolute columns) in, the factor out: ra[l] = D_l, ra[col] = L[l][col]
 template <int K, int KT, typename T>
@@ -532,7 +492,7 @@ struct TrunkStep {
     static __device__ __forceinline__ void run(T* ra, int l, int kt) {
         if (K < kt) {
             asm volatile("" : "+v"(l));     // (lane masks recomputed here, not kept - and spilled - across the substep)
-            const T invd = PIVOT_RCP(bcast_row<K>(ra[K]));
+            const T invd = rcp_(bcast_row<K>(ra[K]));
             T fj = T(0);                        // A[K][l] / D_K for lanes l < K: lane K's entry of MY column
 #pragma unroll
             for (int col = 0; col < K; ++col) {
@@ -860,7 +820,7 @@ __device__ __forceinline__ void dense_contact(T* r, T jn, T j1, T j2, T wn, T w1
 template <int K, int DN, typename T>
 struct DenseStep {
     static __device__ __forceinline__ void run(T* r, T& dinv, int l) {
-        const T inv = PIVOT_RCP(bcast_row<K>(r[K]));
+        const T inv = rcp_(bcast_row<K>(r[K]));
         dinv = l == K ? inv : dinv;
         const T lik = l > K ? r[K] * inv : T(0), nlik = -lik;
         fma_bcast_self_range<K, K + 1, DN>(r, nlik);        // r[j] -= lik * (lane K's r[j]), j > K
@@ -955,8 +915,8 @@ __device__ __forceinline__ void dense32_cols(T* r, T x, T m) {
 // the reciprocal of pivot K (the diagonal entry of lane K), in every lane that will use it
 template <int K, typename T>
 __device__ __forceinline__ T dense32_pivot_inv(const T* r) {
-    if constexpr (K < 16) return PIVOT_RCP(bcast_row<K>(row_even(r[K])));
-    else return PIVOT_RCP(bcast_row<K - 16>(r[K]));          // (only the odd-row lanes use it: theirs is the right one)
+    if constexpr (K < 16) return rcp_(bcast_row<K>(row_even(r[K])));
+    else return rcp_(bcast_row<K - 16>(r[K]));          // (only the odd-row lanes use it: theirs is the right one)
 }
 // Step K.  A[K][j] = A[j][K] (the matrix is symmetric and lane j > K has not scaled its entry K yet), so the pivot row is
 // never sent anywhere: every lane broadcasts-reads "entry K of lane j" - from its own row for columns of its own half,
@@ -1084,12 +1044,8 @@ __device__ __forceinline__ T dense_solve_any(const T* r, T dinv, T b, int l) {
     else return dense_solve<DN>(r, dinv, b, l);
 }
 
-// round 5's colliders (GEN >= 2): functions of their own or inlined into the record walk (developer A/B: -DTREE_GEOM_INLINE)
-#ifdef TREE_GEOM_INLINE
-#define TREE_GEOM_FN __forceinline__
-#else
-#define TREE_GEOM_FN __noinline__
-#endif
+// round 5's colliders (GEN >= 2) are functions of their own: inlined into the record walk they were measured and removed
+// (profiles/r06_gen_scratch.txt)
 // The surface point of a solid box (half sizes h, its own frame) nearest to `loc` (that frame): outside - the clamped point,
 // normal towards `loc`; inside - the nearest face and its outward normal; len = signed distance (mjc_SphereBox's geometry;
 // the oracle's box_point).  false: `loc` lies on the surface to rounding (no normal).
@@ -1130,7 +1086,7 @@ __device__ __forceinline__ bool box_point(const T* h, const T* loc, T* cl, T* nb
 // the solid nearest to c, normal from it to c; inside - the nearest of the side and the two caps.  len = signed distance of c
 // from the surface; false when c lies on it to rounding.  (The oracle's cyl_point, operation for operation.)
 template <typename T>
-__device__ TREE_GEOM_FN bool cyl_point(const T* p0, const T* d, T r, const T* c, T* q, T* n, T& len) {
+__device__ __noinline__ bool cyl_point(const T* p0, const T* d, T r, const T* c, T* q, T* n, T& len) {
     const T L = sqrt_(dot3(d, d));
     T u[3], w[3], rv[3], rh[3];
     for (int i = 0; i < 3; ++i) { u[i] = d[i] / L; w[i] = c[i] - p0[i]; }
@@ -1171,7 +1127,7 @@ __device__ TREE_GEOM_FN bool cyl_point(const T* p0, const T* d, T r, const T* c,
 }
 
 template <typename T>
-__device__ TREE_GEOM_FN T seg_box_param(const T* h, const T* a, const T* b) {
+__device__ __noinline__ T seg_box_param(const T* h, const T* a, const T* b) {
     T bp[8];
     bp[0] = T(0);
     bp[7] = T(1);
@@ -1237,7 +1193,7 @@ __device__ __forceinline__ void seg_seg_params(const T* o1, const T* d1, const T
 // face's side planes, the same edge-pair closest points, in the same order of operations.  R0 / R1: row-major, their COLUMNS
 // are the boxes' axes in the world.  n: unit normal from box 1 to box 0.  false: no such contact.
 template <typename T>
-__device__ TREE_GEOM_FN bool box_box_contact(const T* c0, const T* R0, const T* h0, const T* c1, const T* R1, const T* h1, T margin,
+__device__ __noinline__ bool box_box_contact(const T* c0, const T* R0, const T* h0, const T* c1, const T* R1, const T* h1, T margin,
                                              int want, T* n, T* pos, T& dist) {
     T A[3][3], B[3][3], d[3];
     for (int i = 0; i < 3; ++i)
@@ -1542,17 +1498,10 @@ __device__ __noinline__ T exact_line_search(T g0, T dg, T Dl, T rl, T drl, T Dc,
     if (!(fhi > T(0))) return T(1);
     T lo = T(0), hi = T(1), flo = phi(T(0));
     if (!(flo < T(0))) return T(0);             // (numerically not a descent direction: the gradient at the base point is zero to rounding - stay)
-#ifdef TREE_LS_BISECT           // developer A/B: rounds 3 - 5's root finder (24 bisections, then the secant of the last bracket)
-    for (int b = 0; b < 24; ++b) {
-        const T mid = T(0.5) * (lo + hi), fm = phi(mid);
-        if (fm > T(0)) { hi = mid; fhi = fm; } else { lo = mid; flo = fm; }
-    }
-    const T den = fhi - flo;
-    return den > T(0) ? lo - flo * (hi - lo) * rcp_(den) : lo;
-#else
     // Round 6: false position with the Illinois rule (the end that has not moved twice running gives up half its value) - on a
     // piecewise LINEAR phi' the secant is the root as soon as the bracket lies on the root's piece, i.e. after a few evaluations
     // instead of 25; a bisection step whenever the secant leaves the bracket.  Particles of a wavefront leave the loop together.
+    // (Rounds 3 - 5's 24 bisections and a secant: measured and removed, profiles/r06_illinois_ab.txt.)
     const T tol = T(sizeof(T) == 4 ? 1e-6 : 1e-14) * (fabs(flo) + fabs(fhi));
     T al = T(0);
     int side = 0;
@@ -1569,7 +1518,6 @@ __device__ __noinline__ T exact_line_search(T g0, T dg, T Dl, T rl, T drl, T Dc,
         }
     }
     return al;
-#endif
 }
 
 // The same root with ELLIPTIC cones among the particle's records (GEN = 3): phi' is increasing and continuous but no longer
@@ -1584,7 +1532,6 @@ __device__ __noinline__ T cone_line_search(T g0, T dg, T Dl, T rl, T drl, T Dc, 
     // (the rows arrive BY VALUE and the floor flag leaves as a negative return: arrays behind pointers and a flag behind a
     // reference would live in scratch memory on both sides of this call)
     const T rb[4] = {rb0, rb1, rb2, rb3}, drb[4] = {drb0, drb1, drb2, drb3}, Dk[4] = {Dk0, Dk1, Dk2, Dk3};
-    if (TREE_SKIP & 64) return T(1);        // (developer timing: the full step, no search)
     bool at_floor;
     // (no lane-dependent branch in here: the lane sums below are DPP exchanges, every lane of the particle must arrive at
     // them together - the cone's and the plain rows' parts are both computed and one selected)
@@ -1657,11 +1604,9 @@ __device__ __noinline__ T cone_line_search(T g0, T dg, T Dl, T rl, T drl, T Dc, 
 }
 
 // waves per SIMD the register allocation aims at: the lean kernels for short paths fit three (f32) / two (f64)
-// workgroups' LDS on a CU
-constexpr int min_waves(int scalar_bytes, int DP, bool fric, int gen = 0) {
-#ifdef TREE_GEN_F32_ONE_WAVE            // developer A/B (round 4): the general f32 kernels spill 512 B per lane at two waves per SIMD; at one
-    if (gen) return 1;                  // they gain 3-5 % on 4096-particle launches and lose a third at 32768 (cart-pole 2.11 -> 3.13 ms): off
-#endif
+// workgroups' LDS on a CU.  (One wave per SIMD for the general f32 kernels, round 4: 3-5 % faster at 4096 particles, a third
+// slower at 32768 - cart-pole 2.11 -> 3.13 ms: measured and removed.)
+constexpr int min_waves(int scalar_bytes, int DP, bool fric) {
     return (DP <= 8 && !fric) ? (scalar_bytes == 4 ? 3 : 2) : ((DP <= 8 && scalar_bytes == 4) ? 2 : 1);
 }
 
@@ -1674,7 +1619,7 @@ constexpr int min_waves(int scalar_bytes, int DP, bool fric, int gen = 0) {
 // Models that need none of it run GEN = 0, whose code
 // is the earlier rounds' to the instruction.
 template <typename T, int DP, int NS, bool FRIC, int PL, int DN, int GEN = 0>
-__global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(sizeof(T), DP, FRIC, GEN)) void tree_rollout_kernel(
+__global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(sizeof(T), DP, FRIC)) void tree_rollout_kernel(
     const T* __restrict__ model_all, int model_stride, const double* __restrict__ state, int state_stride, long P, long shard_size, int H,
     int A, const double* __restrict__ mean,
     const T* __restrict__ noise, T* __restrict__ cost, T* __restrict__ act, T* __restrict__ obs, T* __restrict__ nobs,
@@ -1854,7 +1799,9 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
     // closed_loop_linear (gym_env_wrapper.py:135-136): the first action needs the site of the fresh observation, which
     // a one-particle launch left in the state vector beforehand (site_out below, mjmpc_tree_rollout_cl)
     T hand_prev[3] = {T(0), T(0), T(0)}, q_prev = q, v_prev = v;
-    T xa_prev = T(0);               // the constraint solver's acceleration of the previous substep (its warm start)
+    // (the constraint solver's acceleration of the previous substep: read by nothing since the warm-start A/B was removed,
+    // but taking it out moves the register allocation of the dense and 32-lane kernels - it goes with their next re-measurement)
+    T xa_prev = T(0);
     T qy_prev = qy, qz_prev = qz, qw_prev = qw;
     if (clw)
         for (int k = 0; k < 3; ++k) hand_prev[k] = (T)state[2 * TL + 3 + k];
@@ -2492,7 +2439,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                     if (mass > T(0))
                         for (int k = 0; k < 3; ++k) { f[k] -= wt[k] + t3[k]; f[3 + k] -= wf[k]; }
                 }
-                subtree_sum<6, PL, NLINKS>(f, tp, X, l);
+                subtree_sum<6, PL, NLINKS>(f, tp, l);
                 bias = dot3(sw, f) + dot3(sv, f + 3);
             }
 
@@ -2505,8 +2452,8 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
             T md[DN > 0 ? DN : 1];
             {
                 T c6[6] = {Ib[0], Ib[1], Ib[2], Ib[3], Ib[4], Ib[5]}, c4[4] = {mass, hm[0], hm[1], hm[2]};
-                subtree_sum<6, PL, NLINKS>(c6, tp, X, l);
-                subtree_sum<4, PL, NLINKS>(c4, tp, X, l);
+                subtree_sum<6, PL, NLINKS>(c6, tp, l);
+                subtree_sum<4, PL, NLINKS>(c4, tp, l);
                 T F[6], t1[3], t2[3];
                 symv3(c6, sw, F);
                 cross3(c4 + 1, sv, t1);
@@ -2735,7 +2682,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                 }
             }
             TSYNC();
-            const bool any_rows = !(TREE_SKIP & 1) && (__any(inst || cinst != 0) || any_floss);
+            const bool any_rows = __any(inst || cinst != 0) || any_floss;
             T qfrc_c = T(0);
             // mj_forward's acceleration (the constraint solver's) where the wavefront has rows: what mj_checkAcc looks at - kept as
             // the two tests' outcomes, not as a value that would stay live through the Euler solve
@@ -3016,46 +2963,8 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                         cact |= ((cinst_mem >> s) & 1u) ? (cact_mem & (rows << (s * NR))) : (rows << (s * NR));
                     }
                 }
-#ifdef TREE_WARM_START
-                // developer A/B (round 6, measured and NOT kept: profiles/r06_warm_start_ab.txt - HalfCheetah 2.02 -> 2.045 ms per
-                // 4096 x 32 launch, tray 2.755 -> 2.79, f32 32768 x 32 8.40 -> 8.565: the walk costs what the saved re-iterations
-                // were worth).  MuJoCo's warm start for the rows that are NEW this substep: instead of "a new row is active", a new
-                // row is active if its residual at the PREVIOUS substep's acceleration is not positive (mj_fwdConstraint starts
-                // from qacc_warmstart and takes the rows that are violated there) - one walk of the owners' paths in the
-                // substeps where a point comes into contact, against a re-iteration when a new pyramid's four rows do not
-                // all end up active (the usual case: a sliding contact holds two or three)
-                if constexpr (FRIC && GEN < 3) {
-                    const unsigned newpts = cinst & ~cinst_mem;
-                    if (__any(newpts != 0u)) {
-                        T r0[NR];
-#if TREE_WARM_START == 2        // ... at ZERO acceleration: the rows whose reference acceleration is positive - no walk (the owner's record)
-                        {
-                            const T* cs0 = X + A_CS + (l < NS ? l : 0) * CS;
-                            const T mu0 = M[T_SPH + (l < NS ? l : 0) * TREE_SPH_STRIDE + 7];
-                            r0[0] = -(cs0[5] - cs0[6]);
-                            r0[1 % NR] = -(cs0[5] + cs0[6]);
-                            r0[2 % NR] = -(cs0[5] - cs0[7]);
-                            r0[3 % NR] = -(cs0[5] + cs0[7]);
-                            if (!(mu0 > T(0))) r0[0] = -cs0[5];
-                            if (GEN && (my_kind == PT_CONNECT || my_kind == PT_WELD)) { r0[0] = -cs0[5]; r0[1 % NR] = -cs0[6]; r0[2 % NR] = -cs0[7]; r0[3 % NR] = T(0); }
-                        }
-#else
-                        point_residuals(xa_prev, r0);
-#endif
-                        const mask_t pred = rows_from_res(r0, cact);
-                        unsigned long long x = newpts;          // bit s -> bit 4 s
-                        x = (x | (x << 24)) & 0x000000ff000000ffull;
-                        x = (x | (x << 12)) & 0x000f000f000f000full;
-                        x = (x | (x << 6)) & 0x0303030303030303ull;
-                        x = (x | (x << 3)) & 0x1111111111111111ull;
-                        const mask_t nm = (mask_t)(x * 15ull);
-                        cact = (cact & ~nm) | (pred & nm);
-                    }
-#if TREE_WARM_START != 2
-                    if (inst && !(lim_mem & 1)) actv = !(sig * xa_prev - aref > T(0));
-#endif
-                }
-#endif
+                // (MuJoCo's warm start for the rows that are new this substep, at the previous substep's acceleration or at zero:
+                // measured and removed, profiles/r06_warm_start_ab.txt)
                 if constexpr (GEN >= 3) {
                     if (my_ell && my_pt) {
                         const T r0[3] = {T(0), T(0), T(0)};
@@ -3072,13 +2981,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                 // pyramids only LOSES by an earlier search - tray 2.755 -> 2.975 - and keeps 5; profiles/r06_ls_start_ab.txt)
                 // (... and, once the search found its root by false position: from the SECOND iteration on in f64 - door 0.885 -> 0.86,
                 // dry-jointed pen-in-hand 17.6 -> 16.5; f32 keeps the third: door 0.715 -> 0.775 with the second; r06_ls_start2_ab.txt)
-#ifndef TREE_LS_START_FLOSS
-#define TREE_LS_START_FLOSS (sizeof(T) == 8 ? 1 : 2)
-#endif
-#ifndef TREE_LS_START_PYR
-#define TREE_LS_START_PYR 5
-#endif
-                const int LS_START = GEN >= 3 ? 0 : ((GEN && any_floss) ? TREE_LS_START_FLOSS : TREE_LS_START_PYR);      // iterations before the safeguard takes over (friction instantiation; elliptic cones: MuJoCo's Newton method from the start)
+                const int LS_START = GEN >= 3 ? 0 : ((GEN && any_floss) ? tree_ls_start_floss<T>() : TREE_LS_START_PYR);      // iterations before the safeguard takes over (friction instantiation; elliptic cones: MuJoCo's Newton method from the start)
                 bool ls_on = false;
                 T a_b = T(0), g_b = T(0), rb[NR];
 #pragma unroll
@@ -3105,7 +3008,6 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                 TREE_FLAP(31);
                 clk.lap(-1);
                 for (int it = 0; it < (FRIC ? TREE_MAXIT_LS : TREE_MAXIT); ++it) {
-                    if ((TREE_SKIP & 16) || ((TREE_SKIP & 32) && it == 1)) { changed = false; break; }      // (developer timing: no iteration / one)
                     T hrow[DP];
                     T hd[DN > 0 ? DN : 1], hdinv = T(1);        // DN > 0: my dense row of H, then of its factor
                     const T Dfq = (GEN && fstate == 0) ? Df : T(0);     // the friction-loss row in its quadratic zone
@@ -3195,7 +3097,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                     clk.lap(12);
                     if constexpr (DN > 0) {
                         dense_factor_any<DN>(hd, hdinv, l, X + A_ROW);
-                    } else if (MERGE && it == 0 && !(TREE_SKIP & 2)) {      // ... and the Euler matrix M + h B rides along (consumed in step 6)
+                    } else if (MERGE && it == 0) {      // ... and the Euler matrix M + h B rides along (consumed in step 6)
 #pragma unroll
                         for (int c = 0; c < DP; ++c) erow[c] = mrow[c];
                         erow[0] += dof ? h * damping : T(0);
@@ -3311,16 +3213,6 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                                     cact2 = rows_from_res(rb, cact);
                                     if constexpr (GEN) fst2 = fl_state_of(xa, 0);
                                     changed = pmoved;
-#ifdef TREE_DEBUG_CAP
-                                    if (it >= TREE_MAXIT_LS - 6) {
-                                        const unsigned am = (unsigned)(__ballot(actv) >> (PL * half)) & (PL == 32 ? ~0u : 0xFFFFu);
-                                        const unsigned am2 = (unsigned)(__ballot(act2) >> (PL * half)) & (PL == 32 ? ~0u : 0xFFFFu);
-                                        const T pn = sum_lanes<PL>(pv * pv), an = sum_lanes<PL>(a_b * a_b);
-                                        if (l == 0) printf("cap pid=%ld t=%d sub=%d it=%d al=%.17g |p|=%.3g |a|=%.3g gbp=%.3g gNp=%.3g act=%x->%x cact=%llx->%llx\n",
-                                                           (long)pid, t, sub, it, (double)al, (double)sqrt_(pn), (double)sqrt_(an), (double)gbp, (double)gNp,
-                                                           am, am2, (unsigned long long)cact, (unsigned long long)cact2);
-                                    }
-#endif
                                 } else {
                                     a_b = xa;
                                     g_b = gN;
@@ -3374,9 +3266,6 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                         // one-change AND a several-changes particle pays both - closed-loop HalfCheetah 1.957 -> 1.871 ms per
                         // step without it, the others within 0.4 %: profiles/r06_rank_one_ab.txt; the 32-lane dense and the
                         // tree-sparse instantiations, whose factorisations cost 9 - 12 k, keep the correction)
-#ifndef TREE_RANK1_OFF_DN
-#define TREE_RANK1_OFF_DN 16
-#endif
                         constexpr bool RANK1 = !(DN > 0 && DN <= TREE_RANK1_OFF_DN);
                         const bool single = RANK1 && !pdone && nflip + ncf == 1u && !fchg;        // (uniform over my particle)
                         if (!(FRIC && it >= LS_START) && __any(single)) {
@@ -3520,9 +3409,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
             clk.mark(4);
             T qacc;
             {
-                if (TREE_SKIP & 2) {
-                    qacc = (tau + qfrc_c) * rcp_(mrow[0] + (dof ? h * damping : T(0)));
-                } else if (MERGE && any_rows) {
+                if (MERGE && any_rows) {
                     qacc = tree_solve<DP, PL>(erow, tau + qfrc_c, ELIM, AT, ROW2, VEC, l, n_rounds, depth, max_depth, kt);
                 } else if constexpr (DN > 0) {
                     T ed[DN > 0 ? DN : 1], edinv;

@@ -1,5 +1,5 @@
 """Do a particle's costs in the ARM kernels depend on its wave-mates?  python tools/arm_mates_check.py
-(MJMPC_AMD_LIB selects a build, e.g. one made by `tools/dev_build.sh armpp -DARM_PER_PARTICLE`).  For every launch shape
+(MJMPC_AMD_LIB selects a build, e.g. one made by `tools/ab_build.py NAME -DFLAG ...`).  For every launch shape
 (four-wave flags up to 2048 particles, DUO up to 4096, SOLO above) the same particles are rolled out in another order."""
 import sys
 import numpy as np

@@ -1,4 +1,5 @@
-"""Launches for PMC collection (rocprofv3 --pmc passes, tools/profile_round3.sh):
+"""Launches for PMC collection (rocprofv3 --kernel-trace --pmc <counters> ... -- python3 tools/pmc_run.py ..., one pass per
+counter set: tools/pmc_summarize.py lists them):
     python tools/pmc_run.py [reacher|half_cheetah|swimmer|hand24|pen_hand|cartpole|door|tray|gripper] [P] [dtype] [H]
 reacher: three fused control iterations (mjmpc_arm_mppi_step: rollout kernel + finish kernel, the default loop) and three
 plain rollouts - above 4096 particles four launches of mjmpc_arm_rollout_fused, the captured iteration's rollout; the tree models: three rollouts from their bench start state.  Then a calibration copy (64 MiB)."""

@@ -1,4 +1,9 @@
-"""Turn the PMC passes of tools/profile_round3.sh into the per-launch figures bench.py reports:
+"""Turn PMC passes into the per-launch figures bench.py reports.  Each pass is a run of its own:
+    rocprofv3 --kernel-trace --pmc <counters> --output-format csv -d <out>/<tag>_<workload>_pmc<pass> -o <pass> -- \
+        python3 tools/pmc_run.py <workload> 4096 f64
+with the passes S1 = SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY,
+S2 = SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_BUSY_CYCLES,
+S3 / S4 = SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 / _F32, F = FETCH_SIZE, W = WRITE_SIZE.  Then
     python tools/pmc_summarize.py r03 gpurun_out
 writes, per workload, <out>/<tag>_[<workload>_]traffic_f64_4096x32.json and <tag>_[<workload>_]valu_issue_f64_4096x32.json
 (copy them to profiles/): HBM bytes per launch (FETCH_SIZE / WRITE_SIZE, calibrated on a known copy), the share of the
@@ -131,8 +136,7 @@ for wl, prefix, KERNEL, others, P, H in JOBS:
                                   "own instruction stream executes, spare lanes and the work both wavefronts of a particle "
                                   "group duplicate included",
           "other_kernels": {},
-          "method": "rocprofv3 --kernel-trace --pmc <SQ counters> in four passes over tools/pmc_run.py %s 4096 f64 "
-                    "(tools/profile_round3.sh)" % wl}
+          "method": "rocprofv3 --kernel-trace --pmc <SQ counters> in four passes over tools/pmc_run.py %s 4096 f64" % wl}
     for ok in others:
         o1, od = per_kernel(wl + "_pmcS1", ok)
         _, of64, of32 = flops(wl, ok)

@@ -9,6 +9,5 @@ for P in 16384 4096; do
   rm -rf $OUT/${TAG}_prof_cem
 done
 cp $OUT/${TAG}_cem_16384_line_under_rocprof.json $OUT/${TAG}_cem_line_under_rocprof.json
-bash tools/cem_phases.sh 16384 > $OUT/${TAG}_cem_select_phases.txt 2>&1; bash tools/cem_phases.sh 4096 >> $OUT/${TAG}_cem_select_phases.txt 2>&1
 python3 tools/cem_time.py 16384 2>&1 | tail -6 > $OUT/${TAG}_cem_time.txt; python3 tools/cem_time.py 4096 2>&1 | tail -6 >> $OUT/${TAG}_cem_time.txt
 cat $OUT/${TAG}_cem_time.txt; head -6 $OUT/${TAG}_cem_16384_kernel_stats.csv | cut -c1-60,200-400; head -6 $OUT/${TAG}_cem_4096_kernel_stats.csv | cut -c1-60,200-400

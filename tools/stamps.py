@@ -26,7 +26,7 @@ if __name__ == "__main__":
     if "--build" in sys.argv:
         build()
         sys.exit(0)
-    os.environ["MJMPC_AMD_LIB"] = os.environ.get("STAMPS_LIB", LIB)      # (STAMPS_LIB: a tools/dev_build.sh library)
+    os.environ["MJMPC_AMD_LIB"] = os.environ.get("STAMPS_LIB", LIB)      # (STAMPS_LIB: a tools/ab_build.py library)
     import torch
     from mjmpc_amd import _lib
     from mjmpc_amd.envs.arm_engine import ArmRolloutEngine

@@ -1,5 +1,5 @@
 """Rollout-kernel time of the tree engine: python tools/tree_time.py [P] [H] [dtype] [hand|handf|swimmer|cheetah|pen|penf|cartpole|tray|door]
-(MJMPC_AMD_LIB selects an alternative build of the library, e.g. one compiled with -DTREE_SKIP=...)."""
+(MJMPC_AMD_LIB selects an alternative build of the library, e.g. one made by tools/ab_build.py)."""
 import os, sys
 import numpy as np
 import torch
