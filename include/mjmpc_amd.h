@@ -229,6 +229,15 @@ int mjmpc_arm_step_state(mjmpc_arm_t h, int dtype, const double* d_action, void*
 #define MJMPC_TREE_DEVICE_STATE_LEN 102
 typedef struct mjmpc_tree_s* mjmpc_tree_t;
 int mjmpc_tree_create(const double* model_blob, int n_blob, int device, mjmpc_tree_t* out);
+/* The integrator of MJCF <option integrator>: Euler (MuJoCo's semi-implicit mj_Euler, implicit in joint damping; what
+ * mjmpc_tree_create makes) or RK4 (mj_RungeKutta with four stages: four forward evaluations per substep, joint damping
+ * explicit; models of up to 16 dofs without elliptic friction cones - MJMPC_E_BADMODEL otherwise).  It is not in the
+ * model blob, whose layout and length stay as above: the engine is created with it, every launch of the engine (its reset
+ * records included) steps with it, and mjmpc_tree_set_shard_models keeps it.  The flat blob of the reference-side
+ * physics (RawModel.to_flat) carries no integrator either: the reference oracle simulates Euler only. */
+#define MJMPC_INTEGRATOR_EULER 0
+#define MJMPC_INTEGRATOR_RK4 1
+int mjmpc_tree_create_ex(const double* model_blob, int n_blob, int device, int integrator, mjmpc_tree_t* out);
 int mjmpc_tree_destroy(mjmpc_tree_t h);
 int mjmpc_tree_dims(mjmpc_tree_t h, int* nv, int* nu, int* d_obs);
 /* entries of qpos in MuJoCo's layout (nv + one per ball / free joint); mjmpc_tree_set_state / _get_state take and return

@@ -41,6 +41,7 @@ SIGNATURES = {
     "mjmpc_arm_mppi_step": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp,
                                    _dbl, _dbl, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_create": (_int, [_dp, _int, _int, ctypes.POINTER(_vp)]),
+    "mjmpc_tree_create_ex": (_int, [_dp, _int, _int, _int, ctypes.POINTER(_vp)]),
     "mjmpc_tree_destroy": (_int, [_vp]),
     "mjmpc_tree_dims": (_int, [_vp, ctypes.POINTER(_int), ctypes.POINTER(_int), ctypes.POINTER(_int)]),
     "mjmpc_tree_nq": (_int, [_vp]),

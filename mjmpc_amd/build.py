@@ -38,6 +38,9 @@ PER_SOURCE_FLAGS = {"tree_rollout_dense.hip": [["-mllvm", "-amdgpu-sched-strateg
                     # 65 536 x 64 (52.7 -> 51.9 ms, 31.8 -> 31.0 ms from tools/tree_time.py's start state; two A/B pairs);
                     # max-ilp is 1-6 % slower everywhere, iterative-ilp has crashed the compiler on this source
                     "tree_rollout.hip": [["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
+                    # the RK4 instantiations (the dense family, four forward evaluations per substep): the dense source's alternatives
+                    "tree_rollout_rk4.hip": [["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+                                             ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
                     "tree_rollout_cone.hip": [["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
                                               ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
                     # the arm kernel: 1 % (f64 control step 0.2000 -> 0.1980 ms, three A/B pairs on one box; f32 2 %) with
@@ -62,7 +65,7 @@ def sources():
 
 def _headers():
     return (glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC, "*.inc")) + [os.path.join(HERE, "..", "include", "mjmpc_amd.h")]
-            + [os.path.join(CSRC, "tree_rollout.hip"),         # (tree_rollout_dense.hip and tree_rollout_cone.hip include it)
+            + [os.path.join(CSRC, "tree_rollout.hip"),         # (tree_rollout_dense.hip, _cone.hip and _rk4.hip include it)
                os.path.join(CSRC, "arm_rollout.hip")])         # (arm_rollout_xj.hip includes it)
 
 

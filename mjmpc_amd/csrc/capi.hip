@@ -120,6 +120,7 @@ struct mjmpc_tree_s {
     double* reset_rec = nullptr;    // n_shards records of TREE_RESET_LEN: MuJoCo's reset on instability (TreeFusion::reset_rec)
     int inf_on_reset = 0;           // mjmpc_tree_set_reset_returns
     std::vector<double*> reset_retired;     // (as mjmpc_arm_s::reset_retired)
+    int integrator = MJMPC_INTEGRATOR_EULER;    // mjmpc_tree_create_ex: every launch (the reset records' too) steps with it
 };
 
 extern "C" {
@@ -769,7 +770,7 @@ static mjmpc::TreeFusion tree_fuse(const mjmpc_tree_s* h, int shard = -1) {
 // The reset records of `n_shards` model blocks (host, TREE_BLOB_LEN each): per block ONE substep of the f64 kernel itself
 // from the reset state (qpos0 = the device's zero coordinates and identity quaternions, zero velocity, zero controls) on a
 // copy of the block with frame_skip 1 - state_out receives the state after it, site_out / axis_out the site and the object
-// axis at the reset state.  Synchronous; called when the engine is created and when its model blocks are replaced.
+// axis at the reset state (under RK4: at the substep's last stage, where mj_RungeKutta leaves them).  Synchronous; called when the engine is created and when its model blocks are replaced.
 // (as arm_make_reset_records: the records come back in *out, `full` is the kernel choice of the NEW blocks, the launches count
 // into a scratch counter block)
 static int tree_make_reset_records(mjmpc_tree_s* h, const double* blobs, int n_shards, bool full, double** out) {
@@ -795,7 +796,7 @@ static int tree_make_reset_records(mjmpc_tree_s* h, const double* blobs, int n_s
         f.axis_out = rk + mjmpc::TREE_STATE_LEN + 3;
         e = mjmpc::launch_tree_rollout<double>(tmp, 1, h->max_path, full, h->nv, st, 1, 1, h->nu, h->zero_action, nullptr,
                                                (double*)h->scratch, nullptr, nullptr, nullptr, sdiag, nullptr, rk, nullptr,
-                                               rk + mjmpc::TREE_STATE_LEN, 1, h->gen, f);
+                                               rk + mjmpc::TREE_STATE_LEN, 1, h->gen, f, h->integrator);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     hipFree(tmp);
@@ -828,7 +829,13 @@ static int tree_create_impl(mjmpc_tree_s* h, const double* blob, int n_blob) {
 }
 
 int mjmpc_tree_create(const double* blob, int n_blob, int device, mjmpc_tree_t* out) {
+    return mjmpc_tree_create_ex(blob, n_blob, device, MJMPC_INTEGRATOR_EULER, out);
+}
+
+int mjmpc_tree_create_ex(const double* blob, int n_blob, int device, int integrator, mjmpc_tree_t* out) {
     if (!blob || !out) return fail(MJMPC_E_BADARG, "null argument");
+    if (integrator != MJMPC_INTEGRATOR_EULER && integrator != MJMPC_INTEGRATOR_RK4)
+        return fail(MJMPC_E_BADARG, "unknown integrator %d", integrator);
     if (n_blob != mjmpc::TREE_BLOB_LEN)
         return fail(MJMPC_E_BADMODEL, "tree model blob has %d scalars, expected %d", n_blob, (int)mjmpc::TREE_BLOB_LEN);
     const int nv = (int)blob[mjmpc::T_NV];
@@ -853,6 +860,12 @@ int mjmpc_tree_create(const double* blob, int n_blob, int device, mjmpc_tree_t* 
     h->gen = (int)blob[mjmpc::T_GEN];
     for (int l = 0; l < nv; ++l) h->max_path = std::max(h->max_path, (int)blob[mjmpc::T_DEPTH + l] + 1);
     h->topo.assign(blob, blob + n_blob);
+    h->integrator = integrator;
+    if (integrator == MJMPC_INTEGRATOR_RK4 && (nv > 16 || h->gen >= 3)) {
+        delete h;
+        return fail(MJMPC_E_BADMODEL, "RK4 runs models of up to 16 dofs without elliptic friction cones (nv = %d, gen = %d)", nv,
+                    (int)blob[mjmpc::T_GEN]);
+    }
     if (int rc = tree_create_impl(h, blob, n_blob)) {       // a failed allocation leaves nothing behind
         mjmpc_tree_destroy(h);
         return rc;
@@ -994,11 +1007,11 @@ int mjmpc_tree_rollout(mjmpc_tree_t h, int dtype, int64_t P, int H, const double
     if (dtype == MJMPC_F32)
         e = mjmpc::launch_tree_rollout<float>(h->model_f32, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
                                               (const float*)d_noise, (float*)d_costs, (float*)d_actions, (float*)d_obs,
-                                              (float*)d_next_obs, h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, tree_fuse(h));
+                                              (float*)d_next_obs, h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
     else if (dtype == MJMPC_F64)
         e = mjmpc::launch_tree_rollout<double>(h->model_f64, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
                                                (const double*)d_noise, (double*)d_costs, (double*)d_actions,
-                                               (double*)d_obs, (double*)d_next_obs, h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, tree_fuse(h));
+                                               (double*)d_obs, (double*)d_next_obs, h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
     else
         return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
     if (e != hipSuccess) return hip_fail(e, "tree_rollout launch");
@@ -1025,11 +1038,11 @@ int mjmpc_tree_rollout_fused(mjmpc_tree_t h, int dtype, int64_t P, int H, const 
     if (dtype == MJMPC_F32)
         e = mjmpc::launch_tree_rollout<float>(h->model_f32, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
                                               (const float*)d_noise, (float*)d_costs, (float*)d_actions, nullptr, nullptr, h->diag,
-                                              s, nullptr, nullptr, nullptr, nss, h->gen, fuse);
+                                              s, nullptr, nullptr, nullptr, nss, h->gen, fuse, h->integrator);
     else if (dtype == MJMPC_F64)
         e = mjmpc::launch_tree_rollout<double>(h->model_f64, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
                                                (const double*)d_noise, (double*)d_costs, (double*)d_actions, nullptr, nullptr,
-                                               h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, fuse);
+                                               h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, fuse, h->integrator);
     else
         return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
     if (e != hipSuccess) return hip_fail(e, "tree_rollout_fused launch");
@@ -1056,11 +1069,11 @@ int mjmpc_tree_rollout_cl(mjmpc_tree_t h, int dtype, int64_t P, int H, const dou
         if (dtype == MJMPC_F32)
             e = mjmpc::launch_tree_rollout<float>(h->model_f32 + (h->n_shards > 1 ? (size_t)k * mjmpc::TREE_BLOB_LEN : 0), 1, h->max_path,
                                                   h->full, h->nv, sk, 1, 1, h->nu, h->zero_action, nullptr, (float*)h->scratch,
-                                                  nullptr, nullptr, nullptr, h->diag, s, nullptr, nullptr, site0, 1, h->gen, tree_fuse(h, k));
+                                                  nullptr, nullptr, nullptr, h->diag, s, nullptr, nullptr, site0, 1, h->gen, tree_fuse(h, k), h->integrator);
         else if (dtype == MJMPC_F64)
             e = mjmpc::launch_tree_rollout<double>(h->model_f64 + (h->n_shards > 1 ? (size_t)k * mjmpc::TREE_BLOB_LEN : 0), 1, h->max_path,
                                                    h->full, h->nv, sk, 1, 1, h->nu, h->zero_action, nullptr, (double*)h->scratch,
-                                                   nullptr, nullptr, nullptr, h->diag, s, nullptr, nullptr, site0, 1, h->gen, tree_fuse(h, k));
+                                                   nullptr, nullptr, nullptr, h->diag, s, nullptr, nullptr, site0, 1, h->gen, tree_fuse(h, k), h->integrator);
         else
             return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
     }
@@ -1068,11 +1081,11 @@ int mjmpc_tree_rollout_cl(mjmpc_tree_t h, int dtype, int64_t P, int H, const dou
         if (dtype == MJMPC_F32)
             e = mjmpc::launch_tree_rollout<float>(h->model_f32, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu,
                                                   d_weights, (const float*)d_noise, (float*)d_costs, (float*)d_actions, (float*)d_obs,
-                                                  (float*)d_next_obs, h->diag, s, nullptr, d_weights, nullptr, nss, h->gen, tree_fuse(h));
+                                                  (float*)d_next_obs, h->diag, s, nullptr, d_weights, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
         else
             e = mjmpc::launch_tree_rollout<double>(h->model_f64, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu,
                                                    d_weights, (const double*)d_noise, (double*)d_costs, (double*)d_actions,
-                                                   (double*)d_obs, (double*)d_next_obs, h->diag, s, nullptr, d_weights, nullptr, nss, h->gen, tree_fuse(h));
+                                                   (double*)d_obs, (double*)d_next_obs, h->diag, s, nullptr, d_weights, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
     }
     if (e != hipSuccess) return hip_fail(e, "tree_rollout_cl launch");
     return 0;
@@ -1086,10 +1099,10 @@ int mjmpc_tree_step_state(mjmpc_tree_t h, int dtype, const double* d_action, voi
     // one particle, one env step, no noise, shard 0's model; the state vector is advanced in place
     if (dtype == MJMPC_F32)
         e = mjmpc::launch_tree_rollout<float>(h->model_f32, 1, h->max_path, h->full, h->nv, h->state, 1, 1, h->nu, d_action, nullptr,
-                                              (float*)d_cost, nullptr, nullptr, (float*)d_next_obs, h->diag, s, h->state, nullptr, nullptr, 1, h->gen, tree_fuse(h, 0));
+                                              (float*)d_cost, nullptr, nullptr, (float*)d_next_obs, h->diag, s, h->state, nullptr, nullptr, 1, h->gen, tree_fuse(h, 0), h->integrator);
     else if (dtype == MJMPC_F64)
         e = mjmpc::launch_tree_rollout<double>(h->model_f64, 1, h->max_path, h->full, h->nv, h->state, 1, 1, h->nu, d_action, nullptr,
-                                               (double*)d_cost, nullptr, nullptr, (double*)d_next_obs, h->diag, s, h->state, nullptr, nullptr, 1, h->gen, tree_fuse(h, 0));
+                                               (double*)d_cost, nullptr, nullptr, (double*)d_next_obs, h->diag, s, h->state, nullptr, nullptr, 1, h->gen, tree_fuse(h, 0), h->integrator);
     else
         return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
     if (e != hipSuccess) return hip_fail(e, "tree_step_state launch");

@@ -36,6 +36,9 @@ struct TreeFusion {
     double* axis_out = nullptr;
     int inf_on_reset = 0;           // 1: a particle that has reset costs +inf from that env step on (RolloutFusion::inf_on_reset)
 };
+// integrator: 0 MuJoCo's Euler, 1 RK4 (mj_RungeKutta, four stages per substep: tree_rollout_rk4.hip - models of up to 16 dofs
+// without elliptic cones; hipErrorInvalidValue otherwise).  Under RK4 the iteration-cap hits and the counts of non-finite
+// accelerations of launches without a reset record are per STAGE (four forward evaluations per substep), the resets per substep.
 // diag (unsigned[]): [0] iteration-cap hits, [1] resets (live particles), developer clocks from byte 8 (TREE_STATS builds),
 // [TREE_DIAG_ENV_RESETS] resets of the REAL env (launches with state_out: mjmpc_tree_step_state, the control iteration's env step)
 constexpr int TREE_STAT_SLOTS = 48;         // 64-bit developer clocks / counts of -DTREE_STATS builds (tools/tree_stats.py)
@@ -46,6 +49,6 @@ hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path,
                                int A, const double* mean, const T* noise, T* cost, T* act, T* obs, T* nobs, unsigned* diag,
                                hipStream_t stream, double* state_out = nullptr, const double* clw = nullptr,
                                double* site_out = nullptr, int n_state_shards = 1, int gen = 0,
-                               TreeFusion fuse = TreeFusion());
+                               TreeFusion fuse = TreeFusion(), int integrator = 0);
 
 }  // namespace mjmpc

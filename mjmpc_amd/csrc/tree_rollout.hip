@@ -868,7 +868,7 @@ __device__ __forceinline__ T dense_solve(const T* r, T dinv, T b, int l) {
 // Right-looking L D L' - see Dense32Step for how a step gets by with one row exchange.  At the end the odd row's
 // L[j][0..15] are transposed through LDS into the even-row lanes' entries 16..31 (as D_i L[j][i], what the backward solve
 // reads).  Measured on the pen-in-hand model (30 dofs, elimination paths of 16 links), cycles per factorisation / solve:
-// tree-sparse 20.4 k / 10.6 k, this 8.6 k / 3.2 k (DESIGN 4.6.5).
+// tree-sparse 20.4 k / 10.6 k, this 8.6 k / 3.2 k (DESIGN 4.6.3).
 __device__ __forceinline__ void row_pair(float x, float& even, float& odd) {
     const unsigned u = __float_as_uint(x);
     const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
@@ -1618,7 +1618,9 @@ constexpr int min_waves(int scalar_bytes, int DP, bool fric) {
 // kernels they had (inlined into the one general kernel the new geometry cost the door model 6 %, behind a call 10 %).
 // Models that need none of it run GEN = 0, whose code
 // is the earlier rounds' to the instruction.
-template <typename T, int DP, int NS, bool FRIC, int PL, int DN, int GEN = 0>
+// RK4 = 1: MuJoCo's mj_RungeKutta instead of mj_Euler - stages 1-6 run four times per substep (tree_rollout_rk4.hip, DESIGN
+// 4.6.3); the 16-lane dense instantiations only.  RK4 = 0 compiles to the Euler kernel it was.
+template <typename T, int DP, int NS, bool FRIC, int PL, int DN, int GEN = 0, int RK4 = 0>
 __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(sizeof(T), DP, FRIC)) void tree_rollout_kernel(
     const T* __restrict__ model_all, int model_stride, const double* __restrict__ state, int state_stride, long P, long shard_size, int H,
     int A, const double* __restrict__ mean,
@@ -1632,6 +1634,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
     constexpr int NR = FRIC ? 4 : 1;        // constraint rows per contact point: Jn (+- mu Jt_k)
     typedef typename std::conditional<FRIC, unsigned long long, unsigned>::type mask_t;    // NR bits per contact point
     static_assert(!GEN || FRIC, "the general instantiation extends the full one");
+    static_assert(!RK4 || (FRIC && PL == 16 && DN > 0 && GEN < 3), "RK4: the 16-lane dense instantiations without elliptic cones");
     constexpr int CS = GEN ? CS_GEN : CS_BASE;
     constexpr int A_VEC = a_vec(DP, PL), A_JC = a_jc(DP, PL), A_CS = a_cs(DP, NS, NJ, PL), A_MISC = a_misc(DP, NS, NJ, PL, CS),
                   A_ROW2 = a_row2(DP, NS, NJ, PL, CS), A_LEN = a_len(DP, NS, NJ, PL, sizeof(T), DN, CS);
@@ -1830,6 +1833,11 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
             rst_pend = (bb & my_lanes) != 0ull;
         }
     }
+    // (RK4) the substep's start X0 - my coordinate and velocity, the quaternion a ball's first link owns, the sine and cosine of
+    // my coordinate - and the running sums of the stage derivatives, sum b_i v_i and sum b_i a_i (b = 1, 2, 2, 1); rk_hold: my
+    // particle reset at stage 0 (mj_checkAcc) and keeps the record's state to the end of the substep
+    T rq0 = T(0), rv0 = T(0), rqy0 = T(0), rqz0 = T(0), rqw0 = T(1), rsq0 = T(0), rcq0 = T(1), rsv = T(0), rsa = T(0);
+    bool rk_hold = false;
     TreeClock clk;
     clk.start(diag, blockIdx.x == 0 && threadIdx.x == 0);
 
@@ -1904,11 +1912,14 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
         T tau_act = act_id >= 0 ? M[T_GEAR + l] * fmin(fmax(u_dof, M[T_CTRL_LO + l]), M[T_CTRL_HI + l]) : T(0);
         if (task == 1 && l == 0) X[A_MISC + 4] = q;        // qpos[0] when the env step starts
         T hand[3] = {T(0), T(0), T(0)}, haxis[3] = {T(0), T(0), T(0)};
-        for (int sub = 0; sub < frame_skip; ++sub) {
+        // (RK4: NST = 4 forward evaluations per substep, stage st of substep sub; Euler: one, st = 0)
+        constexpr int NST = RK4 ? 4 : 1;
+        for (int ss = 0; ss < frame_skip * NST; ++ss) {
+            const int sub = RK4 ? ss >> 2 : ss, st = RK4 ? ss & 3 : 0;
             // ---- 0. mj_checkPos / mj_checkVel found a NaN or an entry beyond mjMAXVAL in my particle's state (noted where the
             //         previous substep ended): mj_resetData - qpos0, zero velocity, zero controls until the env step ends -
-            //         and the substep runs from there
-            if (__builtin_expect(rst_any, 0)) {
+            //         and the substep runs from there (RK4: the checks run at stage 0 only, as in mj_step)
+            if (__builtin_expect(rst_any, 0) && st == 0) {
                 if (rst_pend) {
                     rst_pend = false;
                     q = T(0); v = T(0); sq = T(0); cq = T(1);
@@ -1918,6 +1929,12 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                     xa_prev = T(0);
                     rst_ever = true;
                     if (diag && l == 0 && live) { atomicAdd(diag + 1, 1u); if (state_out) atomicAdd(diag + TREE_DIAG_ENV_RESETS, 1u); }
+                }
+            }
+            if constexpr (RK4) {
+                if (st == 0) {          // X0: every stage's state is X0 + c F(X_previous stage), never chained from the one before
+                    rq0 = q; rv0 = v; rqy0 = qy; rqz0 = qz; rqw0 = qw; rsq0 = sq; rcq0 = cq;
+                    rsv = T(0); rsa = T(0);
                 }
             }
             // ---- 1. forward kinematics: X_l = X_parent o (Rodrigues(axis, q), off), by pointer jumping
@@ -2317,12 +2334,13 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                 if (PL == 16) ucinst = (ucinst | (ucinst >> 16)) & 0xFFFFu;
             }
             TSYNC();
-            if (sub == frame_skip - 1 || (t == 0 && sub == 0))
+            // (RK4: site_xpos after mj_RungeKutta is the LAST stage's - the final state is not evaluated)
+            if ((sub == frame_skip - 1 && st == NST - 1) || (t == 0 && sub == 0 && st == 0))
                 for (int k = 0; k < 3; ++k) {
                     hand[k] = X[A_MISC + k];
                     if constexpr (FRIC) haxis[k] = X[A_MISC + 5 + k];      // (task 2 runs the full instantiation)
                 }
-            if (t == 0 && sub == 0) {
+            if (t == 0 && sub == 0 && st == 0) {
                 for (int k = 0; k < 3; ++k) hand_prev[k] = hand[k];     // fresh observation after set_env_state
                 if (site_out && pid == 0 && l < 3) site_out[l] = (double)hand[l];
                 if (fuse.axis_out && pid == 0 && l < 3) fuse.axis_out[l] = (double)haxis[l];
@@ -3414,7 +3432,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                 } else if constexpr (DN > 0) {
                     T ed[DN > 0 ? DN : 1], edinv;
 #pragma unroll
-                    for (int j = 0; j < DN; ++j) ed[j] = md[j] + ((j == l && dof) ? h * damping : T(0));
+                    for (int j = 0; j < DN; ++j) ed[j] = md[j] + ((j == l && dof && !RK4) ? h * damping : T(0));     // (RK4: M alone)
                     dense_factor_any<DN>(ed, edinv, l, X + A_ROW);
                     qacc = dense_solve_any<DN>(ed, edinv, tau + qfrc_c, l);
                 } else {
@@ -3424,6 +3442,103 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                 }
             }
             clk.mark(5);
+            if constexpr (RK4) {
+                // ---- 6'. mj_RungeKutta: qacc is stage st's a = M^-1 (qfrc_smooth + qfrc_constraint) - joint damping
+                //          sits in tau (qfrc_passive) in every stage, M carries no h B - for every particle alike, rows or none
+                //          (for a particle with rows it is the Newton solver's acceleration; solving here keeps its bits
+                //          independent of whether its wave-mates have rows).  X_st+1 = X0 + c_st (v_st, a_st), c = h/2, h/2, h;
+                //          after stage 3 the state is X0 + h (F0 + 2 F1 + 2 F2 + F3) / 6, F_i = (v_i, a_i).  The solver's warm
+                //          starts (lim_mem, fl_mem, cinst_mem, cact_mem) carry from one stage's forward to the next, as MuJoCo
+                //          warm-starts every forward from the one before.
+                if (!rst && diag) {  // (no reset record: one count per particle-STAGE whose acceleration has left the arithmetic)
+                    const unsigned long long nf = __ballot(!(fabs(qacc) < T(sizeof(T) == 4 ? 1e30 : 1e100)));
+                    if (l == 0 && ((unsigned)(nf >> (PL * half)) & 0xFFFFu) != 0u) atomicAdd(diag + 1, 1u);
+                }
+                // mj_checkAcc at stage 0 only (mj_step checks the forward it starts with; the stages are not checked)
+                const bool acc_bad = rst && dof && st == 0 && !(fabs(qacc) <= MJ_MAXVAL);
+                if (dof) {
+                    const T bw = (st == 0 || st == 3) ? T(1) : T(2);
+                    rsv += bw * v;
+                    rsa += bw * qacc;
+                }
+                const T c = st >= 2 ? h : T(0.5) * h;
+                const T w = st == 3 ? rsv * T(1.0 / 6.0) : v;           // what integratePos integrates over c
+                if (dof) v = st == 3 ? rv0 + h * (rsa * T(1.0 / 6.0)) : rv0 + c * qacc;
+                const bool angle = dof && !(GEN && ball_g >= 0);        // my coordinate integrates as q0 + c w
+                bool odd = false;
+                if (angle) {
+                    const T dq = c * w;
+                    q = rq0 + dq;
+                    odd = !slide && !(fabs(dq) <= T(0.25));
+                    // (the sine and cosine rebased on X0's, the series or - beyond its reach - the full evaluation, lane by lane)
+                    T sd, cd;
+                    sincos_small(dq, sd, cd);
+                    const T s1 = rsq0 * cd + rcq0 * sd, c1 = rcq0 * cd - rsq0 * sd;
+                    const T kk = T(1.5) - T(0.5) * (s1 * s1 + c1 * c1);
+                    sq = s1 * kk;
+                    cq = c1 * kk;
+                }
+                if (__builtin_expect(__any(odd), 0)) {
+                    if (odd) sincos_(q, sq, cq);
+                }
+                if (GEN && has_ball) {
+                    // a ball joint: q0 * exp(c w / 2), w = its three velocities (body frame), gathered by the first link
+                    const T wy = __shfl_down(w, 1, PL), wz = __shfl_down(w, 2, PL);
+                    if (ball_g == 0) {
+                        q = rq0; qy = rqy0; qz = rqz0; qw = rqw0;
+                        const T nn = sqrt_(w * w + wy * wy + wz * wz);
+                        if (nn > T(1e-15)) {
+                            T sh, ch;
+                            sincos_(T(0.5) * c * nn, sh, ch);
+                            const T k = sh / nn, rx = w * k, ry = wy * k, rz = wz * k;
+                            const T w2 = qw * ch - q * rx - qy * ry - qz * rz, x2 = qw * rx + q * ch + qy * rz - qz * ry,
+                                    y2 = qw * ry - q * rz + qy * ch + qz * rx, z2 = qw * rz + q * ry - qy * rx + qz * ch;
+                            const T inv = T(1) / sqrt_(w2 * w2 + x2 * x2 + y2 * y2 + z2 * z2);
+                            qw = w2 * inv; q = x2 * inv; qy = y2 * inv; qz = z2 * inv;
+                        }
+                    }
+                }
+                // Resets: the exact per-particle tests, no wave-level shortcut (Euler's h |qacc| and 0.25 rad screens bound ONE
+                // update from the state it starts from; the RK4 update combines four stages).  Stage 0: mj_checkAcc ->
+                // mj_resetData, mj_forward and mj_RungeKutta from the reset state: the record (made by this kernel) - my particle
+                // holds its state through stages 1-3.  Stage 3: the final state against mjMAXVAL, for the next substep's
+                // mj_checkPos / mj_checkVel (rst_pend).  Both ballots are per particle; the stage count never depends on them.
+                if (rst && st == 0 && __any(acc_bad)) {
+                    if ((__ballot(acc_bad) & my_lanes) != 0ull) {
+                        rst_any = true;
+                        rq0 = dof ? (T)rst[l] : T(0);
+                        rv0 = dof ? (T)rst[TL + l] : T(0);
+                        rqy0 = T(0); rqz0 = T(0); rqw0 = T(1);
+                        if constexpr (GEN) {
+                            if (ball_g == 0) { rqy0 = (T)rst[l + 1]; rqz0 = (T)rst[l + 2]; rqw0 = (T)rst[TREE_QW + l]; }
+                            if (ball_g > 0) rq0 = T(0);
+                        }
+                        sincos_(rq0, rsq0, rcq0);
+                        tau_act = act_id >= 0 ? M[T_GEAR + l] * fmin(fmax(T(0), M[T_CTRL_LO + l]), M[T_CTRL_HI + l]) : T(0);
+                        lim_mem = 0; fl_mem = 0; cinst_mem = 0; cact_mem = 0;
+                        xa_prev = T(0);
+                        rk_hold = true;
+                        rst_ever = true;
+                        if (diag && l == 0 && live) { atomicAdd(diag + 1, 1u); if (state_out) atomicAdd(diag + TREE_DIAG_ENV_RESETS, 1u); }
+                    }
+                }
+                if (__builtin_expect(rk_hold, 0)) {
+                    q = rq0; v = rv0; qy = rqy0; qz = rqz0; qw = rqw0; sq = rsq0; cq = rcq0;
+                    if (st == 3) {
+                        rk_hold = false;
+                        if (sub == frame_skip - 1)      // (site_xpos: the record's, its last stage's)
+                            for (int k = 0; k < 3; ++k) { hand[k] = (T)rst[TREE_STATE_LEN + k]; haxis[k] = (T)rst[TREE_STATE_LEN + 3 + k]; }
+                    }
+                }
+                if (rst && st == 3) {
+                    const unsigned long long bb = __ballot(state_is_bad());
+                    if (bb != 0ull) {
+                        rst_any = true;
+                        rst_pend = (bb & my_lanes) != 0ull;
+                    }
+                }
+                continue;           // (the Euler step below is not compiled in)
+            }
             // mj_checkAcc: a NaN or an entry beyond mjMAXVAL in the acceleration mj_forward arrived at - the constraint solver's
             // where the wavefront had rows (for a particle without rows of its own that is M^-1 qfrc_smooth, as in MuJoCo),
             // else the Euler solve's (M + h B)^-1 qfrc_smooth, which stands in for M^-1 qfrc_smooth
@@ -3511,6 +3626,14 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
                         if (diag && l == 0 && live) { atomicAdd(diag + 1, 1u); if (state_out) atomicAdd(diag + TREE_DIAG_ENV_RESETS, 1u); }
                     }
                 }
+            }
+        }
+        if constexpr (RK4) {
+            // the launch that makes the reset record (axis_out): under RK4 the record's site and axis are those of the substep's
+            // last stage, where mj_RungeKutta leaves site_xpos
+            if (fuse.axis_out && t == H - 1 && pid == 0 && l < 3) {
+                if (site_out) site_out[l] = (double)hand[l];
+                fuse.axis_out[l] = (double)haxis[l];
             }
         }
         T cst;
@@ -3613,6 +3736,10 @@ hipError_t launch_tree_rollout_dense(int max_path, int nv, int gen, const T* mod
 template <typename T>
 hipError_t launch_tree_rollout_cone(int max_path, int nv, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                     const TreeLaunchArgs& a);
+// ... and so do the RK4 instantiations (tree_rollout_rk4.hip: TREE_DENSE_TU = 4, the forward evaluations per substep)
+template <typename T>
+hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
+                                   const TreeLaunchArgs& a);
 
 #define MJMPC_TREE_LAUNCH(DP_, NS_, FR_, PL_) MJMPC_TREE_LAUNCH_D(DP_, NS_, FR_, PL_, 0, 0)
 #define MJMPC_TREE_LAUNCH_G(DP_, NS_, FR_, PL_, G_) MJMPC_TREE_LAUNCH_D(DP_, NS_, FR_, PL_, 0, G_)
@@ -3626,7 +3753,9 @@ hipError_t launch_tree_rollout_cone(int max_path, int nv, const T* model, const 
                            a.state_out, a.clw, a.site_out, a.fuse);                                                   \
     }
 
-#ifdef TREE_DENSE_TU
+#if defined(TREE_DENSE_TU) && TREE_DENSE_TU == 4
+// (tree_rollout_rk4.hip: the dense family with RK4's four forward evaluations per substep - launch_tree_rollout_rk4 below)
+#elif defined(TREE_DENSE_TU)
 template <typename T>
 hipError_t launch_tree_rollout_dense(int max_path, int nv, int gen, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                      const TreeLaunchArgs& a) {
@@ -3691,12 +3820,48 @@ hipError_t launch_tree_rollout_cone(int max_path, int nv, const T* model, const 
 template hipError_t launch_tree_rollout_cone<float>(int, int, const float*, const float*, float*, float*, float*, float*, const TreeLaunchArgs&);
 template hipError_t launch_tree_rollout_cone<double>(int, int, const double*, const double*, double*, double*, double*, double*,
                                                      const TreeLaunchArgs&);
-#else
+#endif
+#if defined(TREE_DENSE_TU) && TREE_DENSE_TU == 4
+// MuJoCo's RK4 (tree_rollout_kernel's RK4 = 1): every model of up to 16 dofs with pyramidal or no friction cones - the lean
+// 32-lane models too - runs the 16-lane dense family, in four sizes (rows and paths of 4, 8 and 16; rows of 12 on paths of 8 -
+// HalfCheetah, 9 dofs on paths of 8: 18.8 -> 7.6 ms per 4096 x 32 f64 launch against rows and paths of 16), the smallest that fits
+template <typename T>
+hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
+                                   const TreeLaunchArgs& a) {
+#define MJMPC_TREE_LAUNCH_RK4(DP_, DN_, GEN_)                                                                         \
+    {                                                                                                                 \
+        constexpr int per_wg = wg_waves(DP_, true, sizeof(T), 16) * 4;                                               \
+        hipLaunchKernelGGL((tree_rollout_kernel<T, DP_, 16, true, 16, DN_, GEN_, 1>),                                 \
+                           dim3((unsigned)((a.shard + per_wg - 1) / per_wg), (unsigned)a.n_shards),                   \
+                           dim3(64 * wg_waves(DP_, true, sizeof(T), 16)), 0, a.stream, model, a.model_stride, a.state, \
+                           a.state_stride, a.P, a.shard, a.H, a.A, a.mean, noise, cost, act, obs, nobs, a.diag,       \
+                           a.state_out, a.clw, a.site_out, a.fuse);                                                   \
+    }
+#define MJMPC_TREE_LAUNCH_RK4_SIZES(GEN_)                                                                             \
+    {                                                                                                                 \
+        if (max_path <= 4 && nv <= 4) MJMPC_TREE_LAUNCH_RK4(4, 4, GEN_)                                               \
+        else if (max_path <= 8 && nv <= 8) MJMPC_TREE_LAUNCH_RK4(8, 8, GEN_)                                          \
+        else if (max_path <= 8 && nv <= 12) MJMPC_TREE_LAUNCH_RK4(8, 12, GEN_)                                        \
+        else MJMPC_TREE_LAUNCH_RK4(16, 16, GEN_)                                                                      \
+    }
+    if (nv > 16 || gen >= 3) return hipErrorInvalidValue;
+    if (gen == 2) MJMPC_TREE_LAUNCH_RK4_SIZES(2)
+    else if (gen == 1) MJMPC_TREE_LAUNCH_RK4_SIZES(1)
+    else MJMPC_TREE_LAUNCH_RK4_SIZES(0)
+#undef MJMPC_TREE_LAUNCH_RK4_SIZES
+#undef MJMPC_TREE_LAUNCH_RK4
+    return hipGetLastError();
+}
+template hipError_t launch_tree_rollout_rk4<float>(int, int, int, const float*, const float*, float*, float*, float*, float*,
+                                                   const TreeLaunchArgs&);
+template hipError_t launch_tree_rollout_rk4<double>(int, int, int, const double*, const double*, double*, double*, double*, double*,
+                                                    const TreeLaunchArgs&);
+#elif !defined(TREE_DENSE_TU) && !defined(TREE_CONE_TU)
 template <typename T>
 hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path, bool full, int nv, const double* state, long P, int H,
                                int A, const double* mean, const T* noise, T* cost, T* act, T* obs, T* nobs, unsigned* diag,
                                hipStream_t stream, double* state_out, const double* clw, double* site_out, int n_state_shards,
-                               int gen, TreeFusion fuse) {
+                               int gen, TreeFusion fuse, int integrator) {
     if (P <= 0 || H <= 0) return hipSuccess;
     if (gen && !full) return hipErrorInvalidValue;
     if ((state_out || site_out) && P != 1) return hipErrorInvalidValue;
@@ -3722,6 +3887,8 @@ hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path,
     // hinge trees in air with up to 8 frictionless contact points keep the lean instantiation; slide joints, springs,
     // friction cones, more points or a medium take the full one (three Jacobians per point, 16 points, fluid forces),
     // which also comes with 16 lanes per particle for models of up to 16 dofs (the reference's swimmer and cheetah)
+    if (integrator == 1) return launch_tree_rollout_rk4<T>(max_path, nv, gen, model, noise, cost, act, obs, nobs, a);
+    if (integrator != 0) return hipErrorInvalidValue;
     if (gen >= 3) return launch_tree_rollout_cone<T>(max_path, nv, model, noise, cost, act, obs, nobs, a);
     if (!full) {
         if (max_path <= 8) MJMPC_TREE_LAUNCH(8, 8, false, 32)
@@ -3751,9 +3918,9 @@ hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path,
 }
 
 template hipError_t launch_tree_rollout<float>(const float*, int, int, bool, int, const double*, long, int, int, const double*,
-                                               const float*, float*, float*, float*, float*, unsigned*, hipStream_t, double*, const double*, double*, int, int, TreeFusion);
+                                               const float*, float*, float*, float*, float*, unsigned*, hipStream_t, double*, const double*, double*, int, int, TreeFusion, int);
 template hipError_t launch_tree_rollout<double>(const double*, int, int, bool, int, const double*, long, int, int, const double*,
-                                                const double*, double*, double*, double*, double*, unsigned*, hipStream_t, double*, const double*, double*, int, int, TreeFusion);
+                                                const double*, double*, double*, double*, double*, unsigned*, hipStream_t, double*, const double*, double*, int, int, TreeFusion, int);
 #endif
 #undef MJMPC_TREE_LAUNCH
 #undef MJMPC_TREE_LAUNCH_G

@@ -4,8 +4,9 @@
 def make_engine(raw, dtype="f64", device=0, num_shards=1):
     """The fastest engine that runs ``raw`` (a ``RawModel``): the serial-chain arm kernels where the model fits them - hinge /
     slide chains of at most seven dofs with joint limits, dry friction and one frictionless sphere-plane contact (since round 6:
-    the reference's classic-control models) - else the general tree engine.  ``ArmRolloutEngine`` / ``TreeRolloutEngine`` can
-    still be constructed directly."""
+    the reference's classic-control models) - else the general tree engine.  Models that ask for MuJoCo's RK4 integrator
+    (``<option integrator="RK4">``) always run on the tree engine: the arm kernels step with Euler only and refuse them.
+    ``ArmRolloutEngine`` / ``TreeRolloutEngine`` can still be constructed directly."""
     from ..models.compile import compile_arm
     from .arm_engine import ArmRolloutEngine
     from .tree_engine import TreeRolloutEngine

@@ -96,3 +96,11 @@ class GripperEnv(SyntheticEnv):
     model_name = "gripper"
     max_episode_steps = 100
     goal_radius = 0.03
+
+
+class DoublePendulumEnv(SyntheticEnv):
+    """Balance an inverted double pendulum on a cart (a model that asks for MuJoCo's RK4 integrator): the tracked site is
+    the upper pole's tip, the target the point above the rail's centre where the upright poles put it."""
+    model_name = "double_pendulum"
+    max_episode_steps = 200
+    goal_radius = 0.1

@@ -47,7 +47,8 @@ class TreeRolloutEngine(EnvResetWatch):
         self._tdtype = torch.float32 if dtype == "f32" else torch.float64
         h = ctypes.c_void_p()
         blob = np.ascontiguousarray(model.blob, np.float64)
-        _lib.check(self._lib.mjmpc_tree_create(blob.ctypes.data_as(_lib._dp), blob.size, device, ctypes.byref(h)))
+        integrator = {"Euler": 0, "RK4": 1}[getattr(model, "integrator", "Euler")]     # (MJMPC_INTEGRATOR_*)
+        _lib.check(self._lib.mjmpc_tree_create_ex(blob.ctypes.data_as(_lib._dp), blob.size, device, integrator, ctypes.byref(h)))
         self._h = h
         self.d_action, self.d_obs = model.nu, model.d_obs
         self.forward_task = model.task == TASK_FORWARD

@@ -144,6 +144,8 @@ def compile_arm(raw: RawModel, overrides=None, base: "ArmModel" = None) -> ArmMo
                          "(ball / free joints, springs, joint anchors, margin / ref: the tree engine)")
     if raw.equalities or raw.tendons or raw.world_geoms or any(b.inertial is not None for b in raw.bodies):
         raise ValueError("arm kernel: no equalities, tendons, static geoms or explicit inertials (the tree engine has them)")
+    if getattr(raw, "integrator", "Euler") != "Euler":
+        raise ValueError("arm kernel: the Euler integrator only (RK4: the tree engine)")
     if raw.density > 0 or raw.viscosity > 0 or raw.task != 0:
         raise ValueError("arm kernel: no medium, reach task only (the tree engine runs the locomotion models)")
     if raw.plane is not None and any(g.collide and max(g.condim, raw.plane.condim) > 1 for b in raw.bodies for g in b.geoms):

@@ -144,6 +144,7 @@ class TreeModel:
     link_of_body: list
     nq: int = 0
     qpos0: np.ndarray = None
+    integrator: str = "Euler"      # RawModel.integrator - not in the blob: the engine is created with it (mjmpc_tree_create_ex)
 
     def field(self, name):
         o, n = TREE_OFFSETS[name]
@@ -917,6 +918,14 @@ def compile_tree(raw: RawModel, overrides=None, base: "TreeModel" = None) -> Tre
                 f["pext"][k * PEXT_STRIDE + 21] = max(float(raw.impratio), 1e-15)
                 gen3 = True
     f["gen"][0] = 3.0 if gen3 else (2.0 if gen2 else (1.0 if gen else 0.0))
+    # RK4 (MuJoCo's mj_RungeKutta) runs in the 16-lane dense instantiations only (tree_rollout_rk4.hip)
+    integrator = getattr(raw, "integrator", "Euler")
+    if integrator not in ("Euler", "RK4"):
+        raise ValueError("integrator %r is not supported (supported: Euler, RK4)" % integrator)
+    if integrator == "RK4" and gen3:
+        raise ValueError("the RK4 integrator is not supported with elliptic friction cones (use cone=\"pyramidal\" or Euler)")
+    if integrator == "RK4" and nv > 16:
+        raise ValueError("the RK4 integrator is supported for models of up to 16 dofs (this one has %d)" % nv)
     f["nq"][0] = nq
     f["has_ball"][0] = 1.0 if any(k == LINK_BALL_X for k in link_kind) else 0.0
     f["any_friction"][0] = 1.0 if (any(f["spheres"][k * SPH_STRIDE + 7] > 0 for k in range(nsp)) or pair_geoms
@@ -946,7 +955,7 @@ def compile_tree(raw: RawModel, overrides=None, base: "TreeModel" = None) -> Tre
                    target_default=np.asarray(raw.target_pos, float), ctrl_lo=ctrl_lo, ctrl_hi=ctrl_hi, parent=parent,
                    task=int(raw.task), obs_skip=int(raw.obs_skip), max_path=int(edepth.max()),
                    body_mass=mass, body_inertia=inert, body_invweight0=body_iw, dof_invweight0=dof_iw, link_of_body=link_of_body,
-                   nq=nq, qpos0=raw.qpos0)
+                   nq=nq, qpos0=raw.qpos0, integrator=integrator)
     tm.tendon_invweight0 = tendon_iw
     tm.body_invweight0_rot = base.body_invweight0_rot.copy() if base is not None else body_iw_rot
     tm.general = bool(gen)

@@ -5,7 +5,7 @@ round 4, the kinds of model its other experiment files name (examples/configs/cl
 panda/tray_glass-v0.yml, sawyer/door-v0.yml, hand/*-v0.yml):
 
 * ``<compiler angle="radian|degree" coordinate="local" inertiafromgeom="true|auto" settotalmass>``,
-  ``<option timestep gravity density viscosity integrator="Euler" cone impratio collision>`` with ``<flag>`` (the parts a flag
+  ``<option timestep gravity density viscosity integrator="Euler" | "RK4" cone impratio collision>`` with ``<flag>`` (the parts a flag
   switches off are taken out of the model);
 * ``<default>`` with nested classes, ``class=`` / ``childclass=`` (joint, geom and motor attributes);
 * nested ``<body pos quat|axisangle|euler|xyaxes|zaxis>`` with any number of hinge / slide ``<joint>``s (anchor ``pos`` anywhere in
@@ -238,8 +238,9 @@ def load_mjcf(path, hand_site="finger", target_site="target", frame_skip=2, task
     oget = (lambda k, d: opt.get(k, d)) if opt is not None else (lambda k, d: d)
     timestep = float(oget("timestep", "0.002"))
     gravity = _floats(oget("gravity", None), 3, [0.0, 0.0, -9.81])
-    if oget("integrator", "Euler") != "Euler":
-        raise ValueError("only the Euler integrator is supported")
+    integrator = oget("integrator", "Euler")
+    if integrator not in ("Euler", "RK4"):
+        raise ValueError("integrator %r is not supported (supported: Euler, RK4)" % integrator)
     cone, impratio = oget("cone", "pyramidal"), float(oget("impratio", "1"))
     if cone not in ("pyramidal", "elliptic"):
         raise ValueError("cone must be pyramidal or elliptic")
@@ -673,7 +674,7 @@ def load_mjcf(path, hand_site="finger", target_site="target", frame_skip=2, task
                 sensors[e.get("name")] = float(e.get("noise", "0"))
     raw = RawModel(sensors=sensors, bodies=bodies, actuators=acts, site_body=site_body, site_pos=site_pos, target_pos=target, plane=plane,
                    timestep=timestep, frame_skip=frame_skip, gravity=gravity, solref=solref, solimp=full_solimp(solimp),
-                   solref_limit=lsolref, solimp_limit=full_solimp(lsolimp), density=density, viscosity=viscosity, cone=cone, impratio=impratio,
+                   solref_limit=lsolref, solimp_limit=full_solimp(lsolimp), density=density, viscosity=viscosity, cone=cone, impratio=impratio, integrator=integrator,
                    task=task, ctrl_cost=ctrl_cost, obs_skip=obs_skip, pairs=pairs, pair_params=pair_params, world_geoms=world_geoms,
                    equalities=equalities, tendons=tendons, solref_friction=fsolref, solimp_friction=full_solimp(fsolimp))
     return _apply_flags(raw, flags)

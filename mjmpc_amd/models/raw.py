@@ -253,6 +253,9 @@ class RawModel:
     # rows' regulariser R = R_normal / impratio (round 5; impratio has no effect on pyramidal cones)
     cone: str = "pyramidal"
     impratio: float = 1.0
+    # MJCF <option integrator>: "Euler" (semi-implicit, implicit in joint damping) or "RK4" (MuJoCo's mj_RungeKutta: four
+    # forward evaluations per step, joint damping explicit; the tree engine only - DESIGN 4.6.3)
+    integrator: str = "Euler"
     # MJCF <sensor> elements by name -> their ``noise`` attribute: nothing on the path reads a sensor (the envs' observations
     # are qpos / qvel / site positions) and MuJoCo itself does not apply the value; kept so that ``randomize_dynamics``'
     # ``sensor_noise`` entries (gym_env_wrapper.py:396-398) find their sensor and consume their draw

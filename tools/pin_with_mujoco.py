@@ -4,6 +4,7 @@ provide (physics parity is unpinned here; this script has never met a 
     pip install mujoco            # (or a machine with mujoco_py 2.0, the version the reference pins)
     python tools/pin_with_mujoco.py            # every model below, a per-feature PASS / FAIL table, exit code 0 iff all pass
     python tools/pin_with_mujoco.py reacher door random:17 ...     # a selection (random:SEED = tests/test_random_models_gpu.py)
+    python tools/pin_with_mujoco.py swimmer:rk4 double_pendulum   # MuJoCo's RK4 (NAME:rk4 = the model switched to RK4)
     python tools/pin_with_mujoco.py --tol 1e-8
     python tools/pin_with_mujoco.py --self-test       # no MuJoCo needed: the oracle stands in for it (plumbing check only)
 
@@ -20,6 +21,8 @@ built with capsule_cap_factor = 4/3; mujoco_py 2.0 keeps MuJoCo 2.0's pi r^2 (h 
 The table is BY FEATURE: a feature passes when every model that exercises it passes.  Three colliders are this repository's
 own closed forms, not MuJoCo's routines (capsule-box, box-box, sphere / capsule-cylinder: oracle/reacher_ref.c:1522,1986,2026) -
 models that can bring them into contact are listed as EXPECTED DEVIATIONS: their result is printed but does not fail the run.
+RK4 models (<option integrator="RK4">) are compared with the RK4 step composed from the oracle's forward evaluations
+(tests/rk4_ref.py; the oracle itself steps with Euler).
 Writes nothing."""
 import os
 import sys
@@ -28,6 +31,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))         # (rk4_ref: MuJoCo's RK4 step composed from the oracle's forwards)
 
 # model -> the features it exercises (what the pin of that model says something about)
 MODELS = {
@@ -45,10 +49,15 @@ MODELS = {
     "gripper":      ["elliptic cones + impratio", "position actuators", "box-plane contacts"],
     "hand24":       ["24-dof tree (elimination-tree LDL)", "position actuators", "joint limits"],
     "pen_hand":     ["free body in a 24-dof hand", "pyramidal condim-3 contacts: capsule-capsule, sphere-capsule"],
+    # MuJoCo's RK4 (mj_RungeKutta): a model that asks for it, and two vendored ones switched to it
+    "double_pendulum":  ["RK4 integrator (mj_RungeKutta)", "slide + hinge", "friction loss"],
+    "swimmer:rk4":      ["RK4 integrator (mj_RungeKutta)", "fluid forces (density, viscosity)"],
+    "half_cheetah:rk4": ["RK4 integrator (mj_RungeKutta)", "pyramidal condim-3 contacts: plane-capsule"],
 }
 # models whose geoms can meet through one of the own-scheme colliders: judged apart
 OWN_SCHEME = {"gripper": "box-box, capsule-box, capsule-cylinder (closed forms of this repository)"}
-DEFAULT = ["reacher", "half_cheetah", "swimmer", "cartpole", "door", "tray", "fourbar", "gripper", "hand24", "pen_hand"]
+DEFAULT = ["reacher", "half_cheetah", "swimmer", "cartpole", "door", "tray", "fourbar", "gripper", "hand24", "pen_hand",
+           "double_pendulum", "swimmer:rk4", "half_cheetah:rk4"]
 
 
 def _backend():
@@ -92,13 +101,17 @@ def _backend():
 
 
 def _model(name):
+    if name.endswith(":rk4"):
+        raw = _model(name[:-4])
+        raw.integrator = "RK4"
+        return raw
     if name.startswith("random:"):
         import importlib.util
         spec = importlib.util.spec_from_file_location("rm", os.path.join(ROOT, "tests", "test_random_models_gpu.py"))
         rm = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(rm)
         return rm.random_model(int(name.split(":")[1]))
-    if name in ("cartpole", "tray", "door", "fourbar", "gripper"):
+    if name in ("cartpole", "tray", "door", "fourbar", "gripper", "double_pendulum"):
         from mjmpc_amd.models.synthetic import synthetic_raw
         return synthetic_raw(name)
     from mjmpc_amd.models import half_cheetah, hand24, pen_hand, reacher7dof, swimmer
@@ -110,6 +123,15 @@ def _rel(a, b):
     return float(np.max(np.abs(np.asarray(a) - np.asarray(b)) / np.maximum(1.0, np.abs(np.asarray(b))))) if len(a) else 0.0
 
 
+def _oracle_step(ref, raw):
+    """(q, v, u) -> (q', v', resets) of one mj_step with the model's integrator: the oracle's own (Euler), or RK4 composed from
+    its forward evaluations"""
+    if getattr(raw, "integrator", "Euler") == "RK4":
+        from rk4_ref import rk4_step
+        return lambda q, v, u: (lambda r: (r[0], r[1], r[5]))(rk4_step(ref, raw, q, v, u))
+    return lambda q, v, u: (lambda r: (r[0], r[1], r[4]))(ref.step_mj(q, v, u))
+
+
 def compare(B, name, tol):
     """-> dict(one_step, traj, reset) for one model; one_step is what is judged."""
     from mjmpc_amd.models.export_mjcf import to_mjcf
@@ -117,6 +139,7 @@ def compare(B, name, tol):
     raw = _model(name)
     raw.capsule_cap_factor = B.cap
     mj, ref = B(to_mjcf(raw)), RefArm(raw.to_flat())
+    ostep = _oracle_step(ref, raw)
     rs = np.random.RandomState(0)
     nu = len(raw.actuators)
     worst = 0.0
@@ -125,21 +148,21 @@ def compare(B, name, tol):
         v = rs.standard_normal(raw.nv)
         u = rs.uniform(-1, 1, nu)
         q1, v1 = mj.step(q, v, u)
-        q2, v2, _, _ = ref.step(q, v, u)
+        q2, v2, _ = ostep(q, v, u)
         worst = max(worst, _rel(q2, q1), _rel(v2, v1))
     q, v = raw.qpos0.copy(), np.zeros(raw.nv)                   # a trajectory: both sides from their own previous state
     qo, vo = q.copy(), v.copy()
     for _ in range(200):
         u = rs.uniform(-1, 1, nu)
         q, v = mj.step(q, v, u)
-        qo, vo, _, _ = ref.step(qo, vo, u)
+        qo, vo, _ = ostep(qo, vo, u)
     traj = max(_rel(qo, q), _rel(vo, v))
     reset = None                                                # MuJoCo's reset on instability (mj_checkVel -> mj_resetData)
     if not B.raises_on_reset:
         v_bad = 1e11 * np.ones(raw.nv)
         u = np.zeros(nu)
         q1, v1 = mj.step(raw.qpos0.copy(), v_bad, u)
-        q2, v2, _, _, n_resets = ref.step_mj(raw.qpos0.copy(), v_bad, u)       # (or_step_mj: mj_step WITH its checks)
+        q2, v2, n_resets = ostep(raw.qpos0.copy(), v_bad, u)       # (or_step_mj: mj_step WITH its checks)
         assert n_resets >= 1, "the oracle did not reset from velocities of 1e11"
         reset = max(_rel(q2, q1), _rel(v2, v1))
     return dict(one_step=worst, traj=traj, reset=reset, ok=worst <= tol, reset_ok=(reset is None or reset <= tol))
@@ -168,12 +191,13 @@ def main(argv):
                 with tempfile.NamedTemporaryFile("w", suffix=".xml", delete=False) as f:
                     f.write(xml)                                # (through the exported text, like MuJoCo would)
                 try:
-                    self.ref = RefArm(load_mjcf(f.name).to_flat())
+                    raw = load_mjcf(f.name)
+                    self.step_fn = _oracle_step(RefArm(raw.to_flat()), raw)
                 finally:
                     os.unlink(f.name)
 
             def step(self, q, v, u):
-                q1, v1, _, _, _ = self.ref.step_mj(q, v, u)
+                q1, v1, _ = self.step_fn(q, v, u)
                 return q1, v1
         B = Self
     if B is None:

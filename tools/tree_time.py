@@ -1,4 +1,6 @@
 """Rollout-kernel time of the tree engine: python tools/tree_time.py [P] [H] [dtype] [hand|handf|swimmer|cheetah|pen|penf|cartpole|tray|door]
+(a workload name with the suffix _rk4, e.g. swimmer_rk4 or cheetah_rk4: the same model and start state stepped with MuJoCo's RK4
+integrator - tree_rollout_rk4.hip)
 (MJMPC_AMD_LIB selects an alternative build of the library, e.g. one made by tools/ab_build.py)."""
 import os, sys
 import numpy as np
@@ -10,6 +12,8 @@ P = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 dt = sys.argv[3] if len(sys.argv) > 3 else "f64"
 name = sys.argv[4] if len(sys.argv) > 4 else "hand"
+rk4 = name.endswith("_rk4")
+name = name[:-4] if rk4 else name
 start = None
 if name in ("hand", "handf"):
     raw = hand24_raw()
@@ -37,6 +41,8 @@ else:
     from mjmpc_amd.models.half_cheetah import half_cheetah_raw
     from mjmpc_amd.models.swimmer import swimmer_raw
     raw = dict(swimmer=swimmer_raw, cheetah=half_cheetah_raw)[name]()
+if rk4:
+    raw.integrator = "RK4"
 eng = TreeRolloutEngine(raw, dtype=dt)
 A = eng.d_action
 if start is not None:
@@ -74,4 +80,4 @@ e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / 3
 print("%s %s P=%d H=%d: %.2f ms/rollout, %.2f us per particle-pair substep per SIMD, fails=%d"
-      % (name, dt, P, H, ms, ms * 1e3 / (max(1.0, P / 2 / 1024) * H * raw.frame_skip), eng.solver_failures()), flush=True)
+      % (name + ("_rk4" if rk4 else ""), dt, P, H, ms, ms * 1e3 / (max(1.0, P / 2 / 1024) * H * raw.frame_skip), eng.solver_failures()), flush=True)
