@@ -1,0 +1,94 @@
+#!/usr/bin/env python
+"""The config's ``n_episodes`` MPPI episodes as ONE batch on the tree engine (``BatchedMPPI``).
+
+    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi]
+        [--dtype f64|f32] [--episodes N]
+
+examples/example_mpc.py runs the episodes one after another (as the reference's job_script.py:80-99): episode i with seed
+``seed + i*12345`` from the env class's ``reset(seed=...)``.  This driver takes the same seeds and start states and runs all
+episodes side by side - one sampling launch, one rollout launch, one update launch and one env-step launch per control
+step of the whole batch.  Each episode computes exactly what the single-episode device path (``noise_mode='device'``,
+``--graph``) computes for it on the tree engine.
+
+Only the ``mppi`` block runs here; other controller blocks are refused.  The reacher configs run on the TREE engine here
+(sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
+rewards are not expected to be equal.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+import yaml
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from example_mpc import ENVS, TREE_MODELS                           # noqa: E402
+from mjmpc_amd.control import BatchedMPPI                           # noqa: E402
+from mjmpc_amd.envs.tree_engine import TreeRolloutEngine            # noqa: E402
+from mjmpc_amd.models.reacher7dof import reacher7dof_raw            # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description="Run a config's MPPI episodes as one batch")
+    ap.add_argument("--config", required=True, help="yaml file with experiment parameters")
+    ap.add_argument("--controller", default="mppi", help="controller block of the config to run (mppi only)")
+    ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--episodes", type=int, help="override n_episodes")
+    args = ap.parse_args()
+    with open(args.config) as f:
+        exp = yaml.safe_load(f)
+    if exp["env_name"] not in ENVS:
+        raise SystemExit("environment %r is not built (have: %s)" % (exp["env_name"], ", ".join(ENVS)))
+    if args.controller != "mppi":
+        raise SystemExit("an episode batch runs MPPI only (--controller mppi); %r is not batched" % args.controller)
+    if not isinstance(exp.get("mppi"), dict):
+        raise SystemExit("the config has no 'mppi' controller block")
+    params = dict(exp["mppi"])
+    num_cpu = params.pop("num_cpu", 1)
+    if "particles_per_cpu" in params:
+        params["num_particles"] = num_cpu * params.pop("particles_per_cpu")
+    E = args.episodes or exp["n_episodes"]
+    T = exp["max_ep_length"]
+    seeds = [exp["seed"] + i * 12345 for i in range(E)]            # consistent episodes, as in the reference
+    raw = TREE_MODELS[exp["env_name"]]() if exp["env_name"] in TREE_MODELS else reacher7dof_raw()
+
+    # the start states: the env class's reset(seed) per episode (the reacher's env class on the tree engine)
+    env_cls = ENVS[exp["env_name"]]
+    env = env_cls(dtype=args.dtype) if exp["env_name"] in TREE_MODELS else env_cls(engine=TreeRolloutEngine(raw, dtype=args.dtype))
+    states = []
+    for s in seeds:
+        env.reset(seed=s)
+        states.append(env.get_env_state())
+    env.engine.close()
+
+    batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
+                        params["init_cov"], params["gamma"], params["filter_coeffs"],
+                        params.get("base_action", exp.get("base_action", "null")), seeds, dtype=args.dtype,
+                        n_iters=params.get("n_iters", 1), alpha=params.get("alpha", 1),
+                        time_based_weights=params.get("time_based_weights", False))
+    batch.set_states(states)
+    batch.run(1)                        # warm-up step (code objects, allocations), then back to the start
+    batch.reset()
+    batch.set_states(states)
+    t0 = time.perf_counter()
+    actions, costs, nobs = batch.run(T)     # (ends in a device-to-host copy: the clock covers the work)
+    dt = time.perf_counter() - t0
+    final = batch.get_states()
+    batch.close()
+
+    rewards = -costs.astype(np.float64).sum(axis=0)
+    for i in range(E):
+        if exp["env_name"] in ("Swimmer-v0", "HalfCheetah-v0"):
+            print("episode %d: reward %.3f, forward progress %.3f m" % (i, rewards[i], final[i]["qpos"][0]))
+        else:
+            print("episode %d: reward %.3f, final distance to target %.4f"
+                  % (i, rewards[i], np.linalg.norm(nobs[-1, i, -3:])))
+    print("Avg. reward = %.4f, Std. Reward = %.4f" % (rewards.mean(), rewards.std()))
+    print("mppi batch: %d episodes x %d particles x H%d, %.3f ms per batched control step (%.0f episode-steps/s)"
+          % (E, params["num_particles"], params["horizon"], 1e3 * dt / T, E * T / dt))
+
+
+if __name__ == "__main__":
+    main()

@@ -268,6 +268,23 @@ int mjmpc_tree_rollout_fused(mjmpc_tree_t h, int dtype, int64_t P, int H, const 
  * advanced in place; d_cost dtype[1], d_next_obs dtype[d_obs] or NULL.  mjmpc_tree_get_state reads qpos / qvel back. */
 int mjmpc_tree_step_state(mjmpc_tree_t h, int dtype, const double* d_action, void* d_cost, void* d_next_obs, void* stream);
 int mjmpc_tree_get_state(mjmpc_tree_t h, double* qpos, double* qvel, void* stream);
+/* Episode batches: E independent closed-loop MPC episodes side by side (the reference runs them one after another,
+ * examples/job_script.py:80-99 and the episode loop of examples/example_mpc.py).  The engine's E = n_state_shards start
+ * states (mjmpc_tree_set_shard_states, 1 <= E <= 65535) are the batch's E real envs; the engine must hold one model block
+ * (MJMPC_E_BADARG after mjmpc_tree_set_shard_models with more than one).
+ * mjmpc_tree_rollout_fused_batch: mjmpc_tree_rollout_fused (rollout, gym_env_wrapper.py:125-153) with one mean per state
+ * shard - d_means float64 [E][H][nu]; particles [e P_total / E, (e + 1) P_total / E) start from state shard e and follow
+ * mean e; P_total % E == 0.  Each episode's particles compute the bits a single-state engine computes for them. */
+int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                                   const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
+                                   double* d_q0, void* stream);
+/* env.step of every episode's real env in one launch (examples/example_mpc.py:165-168, as mjmpc_tree_step_state per state
+ * shard, bit for bit, resets counted as there): d_actions float64 [E][nu], d_costs dtype [E], d_next_obs dtype [E][d_obs]
+ * or NULL; every state shard is advanced in place. */
+int mjmpc_tree_step_shard_states(mjmpc_tree_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream);
+/* The E state shards read back in MuJoCo's layout (quaternions included): qpos [E][nq], qvel [E][nv] (host; synchronises
+ * the stream), as mjmpc_tree_get_state for the single state. */
+int mjmpc_tree_get_shard_states(mjmpc_tree_t h, double* qpos, double* qvel, void* stream);
 /* rollout(mode="closed_loop_linear") (gym_env_wrapper.py:135-136) as mjmpc_arm_rollout_cl: d_weights float64 [(d_obs + 1)][nu],
  * the nominal action of a step is weights' [observation the step starts from; 1]. */
 int mjmpc_tree_rollout_cl(mjmpc_tree_t h, int dtype, int64_t P, int H, const double* d_weights, const void* d_noise,
@@ -461,6 +478,17 @@ int mjmpc_mppi_fused_update_draw_next(int dtype, int64_t P, int H, int A, const 
                                       uint64_t seed, uint64_t offset, int64_t particle_offset, const int64_t* d_step,
                                       int chol_is_diagonal, void* stream);
 
+/* Episode batches: E independent MPPI updates (mppi.py:69-82 + olgaussian_mpc.py:71 + olgaussian_mpc.py:116-129, one per
+ * episode of the reference's episode loop, examples/job_script.py:80-99) in two launches, grid row e = episode e.  Each row
+ * is exactly mjmpc_mppi_fused_update of P particles: d_q0 float64 [E][P], d_actions dtype [E][P][H][A], d_lam and
+ * d_step_size float64 [E] (device), d_means float64 [E][H][A] (updated and shifted in place), d_actions_out float64 [E][A]
+ * (may be NULL); *d_step_counter (may be NULL) is incremented once - the episodes advance together.  d_ws: at least
+ * mjmpc_update_batch_workspace_bytes(E, P, H, A) bytes.  1 <= E <= 65535. */
+int64_t mjmpc_update_batch_workspace_bytes(int E, int64_t P, int H, int A);
+int mjmpc_mppi_fused_update_batch(int dtype, int E, int64_t P, int H, int A, const double* d_q0, const void* d_actions,
+                                  const double* d_lam, const double* d_step_size, int shift_mode, double* d_means,
+                                  double* d_actions_out, int64_t* d_step_counter, void* d_ws, void* stream);
+
 /* Sharded MPPI: the G all-gathered records d_records (float64 [G][2 + H*A], as left in d_record by
  * mjmpc_mppi_fused_update with step_size 0, shift_mode -1) merged in rank order -> mean update, action read-out,
  * shift, step counter and the mapped host copy with its completion flag, exactly as the single-GPU call does
@@ -539,6 +567,13 @@ int mjmpc_sample_noise_mt19937_jump(int dtype, void* d_noise, int64_t n_normals,
 int mjmpc_sample_noise(int dtype, void* d_noise, int64_t P, int H, int A, const double* d_chol,
                        const double* d_coeffs, uint64_t seed, uint64_t offset, int64_t particle_offset,
                        const int64_t* d_step, int chol_is_diagonal, void* stream);
+
+/* Episode batches: the RAW samples of E episodes in one launch (control_utils.py:24-34 of every episode, unfiltered as
+ * mjmpc_tree_rollout_fused_batch takes them).  Row e of d_noise (dtype [E][P][H][A]) is exactly what
+ * mjmpc_sample_noise(dtype, d_noise + e P H A, P, H, A, d_chols + e A A, NULL, d_seeds[e], offset, 0, d_step, 1) draws:
+ * d_chols float64 [E][A][A] DIAGONAL factors, d_seeds uint64 [E] (device), one step counter d_step (may be NULL) for all. */
+int mjmpc_sample_noise_batch(int dtype, int E, void* d_noise, int64_t P, int H, int A, const double* d_chols,
+                             const uint64_t* d_seeds, uint64_t offset, const int64_t* d_step, void* stream);
 
 #ifdef __cplusplus
 }

@@ -52,6 +52,9 @@ SIGNATURES = {
     "mjmpc_tree_rollout_cl": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_step_state": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_get_state": (_int, [_vp, _dp, _dp, _vp]),
+    "mjmpc_tree_rollout_fused_batch": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_tree_step_shard_states": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
+    "mjmpc_tree_get_shard_states": (_int, [_vp, _dp, _dp, _vp]),
     "mjmpc_tree_solver_failures": (_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mjmpc_tree_diverged": (_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mjmpc_analytic_rollout": (_int, [_int, _vp, _int, _int, _vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int,
@@ -85,6 +88,8 @@ SIGNATURES = {
     "mjmpc_rs_combine": (_int, [_vp, _int, _int, _int, _dbl, _vp, _vp]),
     "mjmpc_mppi_fused_update": (_int, [_int, _i64, _int, _int, _vp, _vp, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp]),
+    "mjmpc_update_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int]),
+    "mjmpc_mppi_fused_update_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_mppi_fused_combine": (_int, [_vp, _int, _dbl, _int, _int, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_mppi_fused_update_draw_next": (_int, [_int, _i64, _int, _int, _vp, _vp, _dbl, _dbl, _int, _vp, _vp, _vp, _vp,
                                                    _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp,
@@ -108,6 +113,7 @@ SIGNATURES = {
     "mjmpc_comm_all_gather_f64": (_int, [_vp, _vp, _vp, _i64, _vp]),
     "mjmpc_comm_destroy": (_int, [_vp]),
     "mjmpc_sample_noise": (_int, [_int, _vp, _i64, _int, _int, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp, _int, _vp]),
+    "mjmpc_sample_noise_batch": (_int, [_int, _int, _vp, _i64, _int, _int, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
 }
 
 _LIB = None

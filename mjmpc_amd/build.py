@@ -43,6 +43,13 @@ PER_SOURCE_FLAGS = {"tree_rollout_dense.hip": [["-mllvm", "-amdgpu-sched-strateg
                                              ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
                     "tree_rollout_cone.hip": [["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
                                               ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
+                    # (the episode batches' EB = 1 twins of the three units above: the same alternatives)
+                    "tree_rollout_dense_eb.hip": [["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+                                                  ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
+                    "tree_rollout_rk4_eb.hip": [["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+                                                ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
+                    "tree_rollout_cone_eb.hip": [["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+                                                 ["-mllvm", "-amdgpu-sched-strategy=iterative-maxocc"]],
                     # the arm kernel: 1 % (f64 control step 0.2000 -> 0.1980 ms, three A/B pairs on one box; f32 2 %) with
                     # iterative-maxocc; iterative-ilp another 1 % on the fused iteration's kernel and 3 % in f32 (two A/B
                     # pairs: f64 control step 0.1957 -> 0.1935 ms, pipelined 0.1910 -> 0.1883; the plain two-wave launch

@@ -6,6 +6,7 @@ _WHERE = {
     "Controller": "controller", "OLGaussianMPC": "controller", "CLGaussianMPC": "clgaussian_mpc",
     "MPPI": "mppi", "MPPIQ": "mppiq", "CEM": "cem", "DMDMPC": "gaussian_dmd",
     "RandomShooting": "random_shooting", "PFMPC": "particle_filter_controller",
+    "BatchedMPPI": "batched",           # (no reference counterpart: the reference's episode loop as one batch)
 }
 __all__ = sorted(_WHERE)
 

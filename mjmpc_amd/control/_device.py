@@ -226,6 +226,13 @@ class TorchDistComm:
         return bool(t.item())
 
 
+def noise_factor(cov):
+    """The Philox sampler's colouring of a HOST covariance: (lower Cholesky factor float64 [A][A], chol_is_diagonal) -
+    what ``DeviceUpdater.prepare_noise`` uploads, and what an episode batch (``BatchedMPPI``) uploads per episode."""
+    cov = np.asarray(cov, np.float64)
+    return np.linalg.cholesky(cov), int(np.count_nonzero(cov - np.diag(np.diag(cov))) == 0)
+
+
 class DeviceUpdater:
     def __init__(self, horizon, d_action, gamma_seq, device=0, comm=None):
         import torch
@@ -650,10 +657,11 @@ class DeviceUpdater:
         cov = np.asarray(cov, np.float64)
         cached = self._rec.get("noise_params")
         if cached is None or cached[0] is None or not (np.array_equal(cached[0], cov) and np.array_equal(cached[1], fc)):
-            self.record("chol", self.A * self.A).copy_(torch.from_numpy(np.linalg.cholesky(cov).reshape(-1).copy()))
+            chol, diag = noise_factor(cov)
+            self.record("chol", self.A * self.A).copy_(torch.from_numpy(chol.reshape(-1).copy()))
             self.record("coeffs", 3).copy_(torch.from_numpy(fc.copy()))
             self._rec["noise_params"] = (cov.copy(), fc.copy())
-            self._rec["chol_diag"] = int(np.count_nonzero(cov - np.diag(np.diag(cov))) == 0)
+            self._rec["chol_diag"] = diag
         return self._rec["chol"], self._rec["coeffs"], self._rec["chol_diag"]
 
     def sample_noise(self, P, cov, filter_coeffs, seed, offset, dtype="f64", particle_offset=0, d_step=None,

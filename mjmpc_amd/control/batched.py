@@ -1,0 +1,241 @@
+"""Episode batches: E independent MPPI episodes side by side on the tree engine.
+
+The reference runs its experiments one episode after another (examples/job_script.py:80-99, the episode loop of
+examples/example_mpc.py), each with its own seed (``seed + i*12345``) and start state, and its "tune" mode multiplies
+that loop by a grid of hyperparameters.  One small population leaves most of the MI355X idle; ``BatchedMPPI`` runs the
+episodes together instead.  A control step of the whole batch is four launches, with no host synchronisation:
+
+    batched Philox draw -> one rollout launch (grid row = episode) -> batched fused update -> batched real-env step
+
+Episode e computes the bits that the single-episode device path computes for it - ``MPPI(..., noise_mode='device',
+seed=seeds[e])`` on a ``TreeRolloutEngine`` of its own, ``make_device_rollout_fn`` and
+``enable_graph(post_step=engine.step_state)`` - so a batch replaces that loop exactly, not statistically.
+
+    batch = BatchedMPPI(half_cheetah_raw(), num_episodes=8, horizon=32, num_particles=512, lam=0.2, step_size=1.0,
+                        init_cov=0.3, gamma=1.0, filter_coeffs=[0.25, 0.8, 0.0], base_action="null",
+                        seeds=[123 + i * 12345 for i in range(8)])
+    batch.set_states(start_states)                  # one state dict per episode
+    actions, costs, next_obs = batch.run(100)       # [T][E][A], [T][E], [T][E][d_obs]
+
+Per episode: seed, start state (with ``target_pos``), initial mean, ``lam``, ``step_size`` and ``init_cov``.  Shared by
+the batch: the model, ``horizon``, ``num_particles`` (per episode), ``gamma``, ``filter_coeffs``, ``base_action`` and
+the dtype.  The batch's E real envs are the state shards of the batch's own engine (``mjmpc_tree_step_shard_states``).
+"""
+import ctypes
+
+import numpy as np
+
+from .. import _lib
+from ._device import noise_factor
+from .controller import _SHIFT_MODES, _seed_value
+
+
+def _vp(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _per_episode(name, value, E, shape=()):
+    """One value for every episode, or one per episode -> float64 [E, *shape]."""
+    a = np.asarray(value, np.float64)
+    if a.shape == tuple(shape):
+        return np.broadcast_to(a, (E,) + tuple(shape)).copy()
+    if a.shape == (E,) + tuple(shape):
+        return a.copy()
+    raise ValueError("%s takes one value of shape %s for every episode or %d of them, shape %s; got shape %s"
+                     % (name, tuple(shape), E, (E,) + tuple(shape), a.shape))
+
+
+class BatchedMPPI:
+    """``num_episodes`` MPPI controllers (mppi.py, ``alpha = 1``, one iteration per step) and their real envs, stepped together.
+
+    ``lam``, ``step_size``, ``init_cov`` (scalar covariance ``init_cov * I``, as ``MPPI`` takes it) and ``init_mean`` (``(H, A)``,
+    default zeros) take one value for every episode or one per episode; ``seeds`` one seed per episode.  Settings the
+    batch does not run raise ``ValueError`` before any engine or device memory exists: ``n_iters != 1``, ``alpha != 1``,
+    ``time_based_weights``, ``cov_type != 'diagonal'``, ``base_action`` other than ``'null'`` / ``'repeat'``,
+    ``use_zero_control_seq``, ``sample_mode != 'mean'``, ``gamma == 0`` and a model the tree engine refuses."""
+
+    def __init__(self, raw_model, num_episodes, horizon, num_particles, lam, step_size, init_cov, gamma, filter_coeffs,
+                 base_action, seeds, init_mean=None, dtype="f64", device=0, n_iters=1, alpha=1, time_based_weights=False,
+                 cov_type="diagonal", use_zero_control_seq=False, sample_mode="mean"):
+        # -- everything that can be refused is refused here, before the engine and its device memory exist
+        E, H, P = int(num_episodes), int(horizon), int(num_particles)
+        if not 1 <= E <= 65535:
+            raise ValueError("num_episodes must be in [1, 65535], got %d" % E)
+        if H < 1 or P < 1:
+            raise ValueError("horizon and num_particles must be positive")
+        if n_iters != 1:
+            raise ValueError("an episode batch runs one MPPI iteration per control step (n_iters = 1), got %r" % (n_iters,))
+        if alpha != 1:
+            raise ValueError("an episode batch runs MPPI without the control cost (alpha = 1), got %r" % (alpha,))
+        if time_based_weights:
+            raise ValueError("an episode batch does not run time_based_weights")
+        if cov_type != "diagonal":
+            raise ValueError("an episode batch samples with a diagonal covariance (cov_type 'diagonal'), got %r" % (cov_type,))
+        if base_action not in ("null", "repeat"):
+            raise ValueError("base_action must be 'null' or 'repeat' in an episode batch, got %r" % (base_action,))
+        if use_zero_control_seq:
+            raise ValueError("an episode batch does not run use_zero_control_seq")
+        if sample_mode != "mean":
+            raise ValueError("an episode batch acts with the mean (sample_mode 'mean'), got %r" % (sample_mode,))
+        if dtype not in ("f64", "f32"):
+            raise ValueError("dtype must be 'f64' or 'f32'")
+        if float(gamma) == 0.0:
+            raise ValueError("gamma = 0 leaves zeros in the discount sequence, which the fused update does not take")
+        fc = np.asarray(filter_coeffs, np.float64).reshape(-1)
+        if fc.size != 3:
+            raise ValueError("filter_coeffs must hold three coefficients")
+        lam = _per_episode("lam", lam, E)
+        step_size = _per_episode("step_size", step_size, E)
+        init_cov = _per_episode("init_cov", init_cov, E)
+        if not np.all(lam > 0):
+            raise ValueError("lam must be positive")
+        if not np.all(init_cov > 0):
+            raise ValueError("init_cov must be positive")
+        seeds = list(seeds) if isinstance(seeds, (list, tuple, np.ndarray)) else None
+        if seeds is None or len(seeds) != E:
+            raise ValueError("seeds must hold one seed per episode (%d)" % E)
+        self.seed_vals = [_seed_value(int(s) if isinstance(s, (np.integer,)) else s) for s in seeds]
+        from ..models.compile_tree import TreeModel, compile_tree
+        try:
+            model = raw_model if isinstance(raw_model, TreeModel) else compile_tree(raw_model)
+        except (ValueError, NotImplementedError, TypeError, AttributeError) as e:
+            raise ValueError("the tree engine cannot run this model: %s" % e) from e
+        gen = int(model.field("gen")[0])
+        if model.integrator == "RK4" and (model.nv > 16 or gen >= 3):
+            raise ValueError("the tree engine runs RK4 models of up to 16 dofs without elliptic friction cones")
+        A = model.nu
+        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
+        factors = [noise_factor(np.diag(np.array([c] * A))) for c in init_cov]      # (OLGaussianMPC: diag(init_cov))
+
+        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+        from ..envs.tree_engine import TreeRolloutEngine
+        import torch
+        self.torch = torch
+        self.engine = TreeRolloutEngine(model, device=device, dtype=dtype)
+        self.lib = self.engine._lib
+        self.model = model
+        self.num_episodes, self.horizon, self.num_particles, self.d_action = E, H, P, A
+        self.d_obs, self.dtype = model.d_obs, dtype
+        self.forward_task = self.engine.forward_task
+        self.base_action, self.gamma, self.filter_coeffs = base_action, float(gamma), fc.copy()
+        self.lam, self.step_size, self.init_cov, self.init_mean = lam, step_size, init_cov, init_mean
+        self.num_steps = 0
+        dev = self.device = torch.device("cuda", device)
+        self._code = _lib.F32 if dtype == "f32" else _lib.F64
+        tdt = self._tdtype = torch.float32 if dtype == "f32" else torch.float64
+        f64 = dict(dtype=torch.float64, device=dev)
+        self._means = torch.from_numpy(init_mean.copy()).to(dev)
+        self._gseq = torch.from_numpy(np.cumprod([1.0] + [self.gamma] * (H - 1))).to(dev)     # (Controller.gamma_seq)
+        self._coeffs = torch.from_numpy(fc.copy()).to(dev)
+        self._chols = torch.from_numpy(np.stack([f[0] for f in factors])).to(dev)
+        self._seeds = torch.from_numpy(np.array(self.seed_vals, np.uint64).view(np.int64)).to(dev)
+        self._lam = torch.from_numpy(lam.copy()).to(dev)
+        self._step = torch.from_numpy(step_size.copy()).to(dev)
+        self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._noise = torch.empty((E, P, H, A), dtype=tdt, device=dev)
+        self._costs = torch.empty((E * P, H), dtype=tdt, device=dev)
+        self._actions = torch.empty((E * P, H, A), dtype=tdt, device=dev)
+        self._q0 = torch.empty(E * P, **f64)
+        nbytes = self.lib.mjmpc_update_batch_workspace_bytes(E, P, H, A)
+        if nbytes < 0:
+            _lib.check(int(nbytes))
+        self._ws = torch.empty((nbytes + 7) // 8, **f64)
+        self._act = torch.empty((E, A), **f64)
+        self._env_cost = torch.empty(E, dtype=tdt, device=dev)
+        self._env_obs = torch.empty((E, self.d_obs), dtype=tdt, device=dev)
+        self._targets = [model.target_default.copy() for _ in range(E)]
+        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+
+    # ------------------------------------------------------------------ state of the E real envs
+    @property
+    def on_env_reset(self):
+        """What a reset of a real env does where ``run`` / ``get_states`` synchronise (``envs/_resets.py``)."""
+        return self.engine.on_env_reset
+
+    @on_env_reset.setter
+    def on_env_reset(self, mode):
+        self.engine.on_env_reset = mode
+
+    def set_states(self, states):
+        """One state dict per episode, in the env classes' format: ``{qp, qv, target_pos}`` or ``{qpos, qvel}``."""
+        if len(states) != self.num_episodes:
+            raise ValueError("set_states takes one state per episode (%d), got %d" % (self.num_episodes, len(states)))
+        m = self.model
+        unpacked = [self.engine._unpack(s) for s in states]
+        arr = np.zeros((self.num_episodes, 78))        # MJMPC_TREE_STATE_LEN: qpos[40] | qvel[32] | target[3] | -
+        for k, s in enumerate(unpacked):
+            arr[k, :m.nq], arr[k, 40:40 + m.nv], arr[k, 72:75] = s["qp"], s["qv"], s["target_pos"]
+        _lib.check(self.lib.mjmpc_tree_set_shard_states(self.engine._h, arr.ctypes.data_as(_lib._dp), self.num_episodes,
+                                                        self._stream()))
+        self._targets = [s["target_pos"].copy() for s in unpacked]
+
+    def get_states(self):
+        """The E real envs' states as state dicts (one device-to-host copy; synchronises the stream)."""
+        E, m = self.num_episodes, self.model
+        qp, qv = np.zeros((E, m.nq)), np.zeros((E, m.nv))
+        _lib.check(self.lib.mjmpc_tree_get_shard_states(self.engine._h, qp.ctypes.data_as(_lib._dp),
+                                                        qv.ctypes.data_as(_lib._dp), self._stream()))
+        self._check_resets()
+        if self.forward_task:
+            return [dict(qpos=qp[e].copy(), qvel=qv[e].copy()) for e in range(E)]
+        return [dict(qp=qp[e].copy(), qv=qv[e].copy(), qa=np.zeros(m.nv), target_pos=self._targets[e].copy(), timestep=0)
+                for e in range(E)]
+
+    @property
+    def mean_action(self):
+        """The E means, ``(E, H, A)`` (synchronises)."""
+        return self._means.cpu().numpy().copy()
+
+    def reset(self):
+        """Every episode back to its initial mean and step 0 (the real envs keep their states: ``set_states``)."""
+        self._means.copy_(self.torch.from_numpy(self.init_mean))
+        self._step_dev.zero_()
+        self.num_steps = 0
+
+    # ------------------------------------------------------------------ control steps
+    def step(self, _out=None):
+        """Enqueue one control step of every episode (sampling, rollouts, update, action, shift, real-env step) without a
+        host synchronisation.  The actions, real-env costs and next observations stay on the device."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
+        lib, h, code, s = self.lib, self.engine._h, self._code, self._stream()
+        _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
+                                                _vp(self._step_dev), s))
+        _lib.check(lib.mjmpc_tree_rollout_fused_batch(h, code, E * P, H, _vp(self._means), _vp(self._noise), _vp(self._coeffs),
+                                                      _vp(self._gseq), _vp(self._costs), _vp(self._actions), _vp(self._q0), s))
+        _lib.check(lib.mjmpc_mppi_fused_update_batch(code, E, P, H, A, _vp(self._q0), _vp(self._actions), _vp(self._lam),
+                                                     _vp(self._step), _SHIFT_MODES[self.base_action], _vp(self._means),
+                                                     _vp(act), _vp(self._step_dev), _vp(self._ws), s))
+        _lib.check(lib.mjmpc_tree_step_shard_states(h, code, _vp(act), _vp(cost), _vp(nobs), s))
+        self.num_steps += 1
+        return act, cost, nobs
+
+    def run(self, T):
+        """``T`` control steps of every episode -> actions ``[T][E][A]`` (float64), real-env costs ``[T][E]`` and next
+        observations ``[T][E][d_obs]`` (the batch's dtype), brought back with one device-to-host copy at the end."""
+        torch, T = self.torch, int(T)
+        E, A, D = self.num_episodes, self.d_action, self.d_obs
+        isz = 4 if self.dtype == "f32" else 8
+        na, nc = 8 * T * E * A, isz * T * E
+        buf = torch.empty(na + nc + isz * T * E * D, dtype=torch.uint8, device=self.device)
+        acts = buf[:na].view(torch.float64).view(T, E, A)
+        costs = buf[na:na + nc].view(self._tdtype).view(T, E)
+        nobs = buf[na + nc:].view(self._tdtype).view(T, E, D)
+        for t in range(T):
+            self.step(_out=(acts[t], costs[t], nobs[t]))
+        host = buf.cpu().numpy()
+        self._check_resets()
+        npt = np.float32 if self.dtype == "f32" else np.float64
+        return (host[:na].view(np.float64).reshape(T, E, A).copy(), host[na:na + nc].view(npt).reshape(T, E).copy(),
+                host[na + nc:].view(npt).reshape(T, E, D).copy())
+
+    def close(self):
+        self.engine.close()
+
+    # ------------------------------------------------------------------ helpers
+    def _check_resets(self):
+        if self.engine.on_env_reset != "ignore":
+            self.engine.check_env_resets("an episode batch's real envs (step_shard_states)")
+
+    def _stream(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)

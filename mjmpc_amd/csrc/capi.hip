@@ -1119,6 +1119,88 @@ int mjmpc_tree_get_state(mjmpc_tree_t h, double* qpos, double* qvel, void* strea
     return 0;
 }
 
+/* ---- episode batches: the engine's E state shards are the batch's E real envs ---------------------------- */
+// what every batch entry point asks of the engine: one model block, 1 .. 65535 state shards (grid rows), and - given a
+// particle count - the same number of particles per shard
+static int tree_batch_shape(mjmpc_tree_t h, int64_t P_total, int* E) {
+    if (!h) return fail(MJMPC_E_BADARG, "null engine");
+    if (h->n_shards > 1) return fail(MJMPC_E_BADARG, "an episode batch runs one model block; the engine has %d", h->n_shards);
+    const int e = h->n_state_shards;
+    if (e < 1 || e > 65535)
+        return fail(MJMPC_E_BADARG, "an episode batch needs 1 .. 65535 state shards (mjmpc_tree_set_shard_states); the engine has %d", e);
+    if (P_total < 1 || P_total % e != 0)
+        return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d episodes", (long long)P_total, e);
+    *E = e;
+    return 0;
+}
+
+int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                                   const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
+                                   double* d_q0, void* stream) {
+    if (!h || !d_means || !d_noise || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+    if ((d_q0 != nullptr) != (d_gseq != nullptr)) return fail(MJMPC_E_BADARG, "d_q0 and d_gseq go together");
+    if (H < 1) return fail(MJMPC_E_BADARG, "horizon %d", H);
+    int E = 0;
+    if (int rc = tree_batch_shape(h, P_total, &E)) return rc;
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    mjmpc::TreeFusion fuse = tree_fuse(h);
+    fuse.filt = d_filter_coeffs;
+    fuse.gseq = d_gseq;
+    fuse.q0_out = d_q0;
+    fuse.mean_stride = (long)H * h->nu;         // episode e's mean: d_means + e H A
+    hipError_t e;
+    if (dtype == MJMPC_F32)
+        e = mjmpc::launch_tree_rollout<float>(h->model_f32, 1, h->max_path, h->full, h->nv, h->shard_states, (long)P_total, H, h->nu,
+                                              d_means, (const float*)d_noise, (float*)d_costs, (float*)d_actions, nullptr, nullptr,
+                                              h->diag, s, nullptr, nullptr, nullptr, E, h->gen, fuse, h->integrator);
+    else
+        e = mjmpc::launch_tree_rollout<double>(h->model_f64, 1, h->max_path, h->full, h->nv, h->shard_states, (long)P_total, H, h->nu,
+                                               d_means, (const double*)d_noise, (double*)d_costs, (double*)d_actions, nullptr, nullptr,
+                                               h->diag, s, nullptr, nullptr, nullptr, E, h->gen, fuse, h->integrator);
+    if (e != hipSuccess) return hip_fail(e, "tree_rollout_fused_batch launch");
+    return 0;
+}
+
+int mjmpc_tree_step_shard_states(mjmpc_tree_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream) {
+    if (!h || !d_actions || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+    int E = 0;
+    if (int rc = tree_batch_shape(h, h->n_state_shards, &E)) return rc;
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    // mjmpc_tree_step_state once per row: one particle, one env step, no noise, the model block's instantiation and reset
+    // record; row e reads action e and advances state shard e in place
+    mjmpc::TreeFusion fuse = tree_fuse(h, 0);
+    fuse.mean_stride = h->nu;
+    fuse.state_out_stride = mjmpc::TREE_STATE_LEN;
+    hipError_t e;
+    if (dtype == MJMPC_F32)
+        e = mjmpc::launch_tree_rollout<float>(h->model_f32, 1, h->max_path, h->full, h->nv, h->shard_states, E, 1, h->nu, d_actions,
+                                              nullptr, (float*)d_costs, nullptr, nullptr, (float*)d_next_obs, h->diag, s,
+                                              h->shard_states, nullptr, nullptr, E, h->gen, fuse, h->integrator);
+    else
+        e = mjmpc::launch_tree_rollout<double>(h->model_f64, 1, h->max_path, h->full, h->nv, h->shard_states, E, 1, h->nu, d_actions,
+                                               nullptr, (double*)d_costs, nullptr, nullptr, (double*)d_next_obs, h->diag, s,
+                                               h->shard_states, nullptr, nullptr, E, h->gen, fuse, h->integrator);
+    if (e != hipSuccess) return hip_fail(e, "tree_step_shard_states launch");
+    return 0;
+}
+
+int mjmpc_tree_get_shard_states(mjmpc_tree_t h, double* qpos, double* qvel, void* stream) {
+    if (!h || !qpos || !qvel) return fail(MJMPC_E_BADARG, "null argument");
+    if (h->n_state_shards < 1) return fail(MJMPC_E_BADARG, "the engine has no state shards (mjmpc_tree_set_shard_states)");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t L = MJMPC_TREE_DEVICE_STATE_LEN;
+    std::vector<double> st((size_t)h->n_state_shards * L);
+    HIP_TRY(hipMemcpyAsync(st.data(), h->shard_states, sizeof(double) * st.size(), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int k = 0; k < h->n_state_shards; ++k)
+        tree_unpack_state(h, st.data() + (size_t)k * L, qpos + (size_t)k * h->nq, qvel + (size_t)k * h->nv);
+    return 0;
+}
+
 int mjmpc_tree_solver_failures(mjmpc_tree_t h, uint32_t* count) {
     if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
     HIP_TRY(hipSetDevice(h->device));
@@ -1407,6 +1489,27 @@ int mjmpc_mppi_fused_update_draw_next(int dtype, int64_t P, int H, int A, const 
                         d_value, h_action_mapped, d_step_counter, d_ws, stream, &nn);
 }
 
+int64_t mjmpc_update_batch_workspace_bytes(int E, int64_t P, int H, int A) {
+    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1)
+        return fail(MJMPC_E_BADARG, "bad batch shape E = %d, P = %lld, H = %d, A = %d", E, (long long)P, H, A);
+    return (int64_t)sizeof(double) * mjmpc::mppi_fused_batch_workspace_doubles(E, (long)P, H, A);
+}
+
+int mjmpc_mppi_fused_update_batch(int dtype, int E, int64_t P, int H, int A, const double* d_q0, const void* d_actions,
+                                  const double* d_lam, const double* d_step_size, int shift_mode, double* d_means,
+                                  double* d_actions_out, int64_t* d_step_counter, void* d_ws, void* stream) {
+    if (!d_q0 || !d_actions || !d_lam || !d_step_size || !d_means || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
+    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
+    if (P < 1 || H < 1 || A < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d, A = %d", (long long)P, H, A);
+    if (shift_mode < -1 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::mppi_fused_update_batch<float>(E, d_q0, (const float*)d_actions, d_lam, d_step_size, shift_mode, (long)P, H, A,
+                                                   d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws, s),
+             mjmpc::mppi_fused_update_batch<double>(E, d_q0, (const double*)d_actions, d_lam, d_step_size, shift_mode, (long)P, H,
+                                                    A, d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws, s));
+}
+
 int mjmpc_mppi_fused_combine(const double* d_records, int G, double P_total, int H, int A, double lam, double step_size,
                              int shift_mode, double* d_mean, double* d_action_out, double* d_value,
                              double* h_action_mapped, int64_t* d_step_counter, void* stream) {
@@ -1507,6 +1610,19 @@ int mjmpc_sample_noise(int dtype, void* d_noise, int64_t P, int H, int A, const 
                                         (long)particle_offset, (const long long*)d_step, s, chol_is_diagonal),
              mjmpc::sample_noise<double>((double*)d_noise, (long)P, H, A, d_chol, d_coeffs, seed, offset,
                                          (long)particle_offset, (const long long*)d_step, s, chol_is_diagonal));
+}
+
+int mjmpc_sample_noise_batch(int dtype, int E, void* d_noise, int64_t P, int H, int A, const double* d_chols,
+                             const uint64_t* d_seeds, uint64_t offset, const int64_t* d_step, void* stream) {
+    if (!d_noise || !d_chols || !d_seeds) return fail(MJMPC_E_BADARG, "null argument");
+    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
+    if (P < 1 || H < 1 || A < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d, A = %d", (long long)P, H, A);
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::sample_noise_batch<float>((float*)d_noise, E, (long)P, H, A, d_chols, (const unsigned long long*)d_seeds,
+                                              offset, (const long long*)d_step, s),
+             mjmpc::sample_noise_batch<double>((double*)d_noise, E, (long)P, H, A, d_chols, (const unsigned long long*)d_seeds,
+                                               offset, (const long long*)d_step, s));
 }
 
 }  // extern "C"

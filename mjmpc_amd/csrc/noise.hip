@@ -25,6 +25,18 @@ __global__ void noise_kernel(T* __restrict__ noise, long P, int H, int A, const 
                      diag_only);
 }
 
+// Episode batches: grid row e draws episode e's [P][H][A] block with its own seed and DIAGONAL factor; the element is
+// noise_kernel's with diag_only = 1 and particle_offset = 0 (one step counter: the episodes advance together).
+template <typename T>
+__global__ void noise_batch_kernel(T* __restrict__ noise, long P, int H, int A, const double* __restrict__ chols,
+                                   const unsigned long long* __restrict__ seeds, unsigned long long offset,
+                                   const long long* __restrict__ d_step) {
+    if (d_step) offset += (unsigned long long)*d_step;
+    const long e = blockIdx.y;
+    noise_element<T>(noise + e * P * H * A, (long)blockIdx.x * blockDim.x + threadIdx.x, P, H, A, chols + e * A * A, seeds[e],
+                     offset, 0, 1);
+}
+
 // Full (lower-triangular) colouring: one thread per (particle, t-quad) draws the A independent normal quadruples ONCE and
 // forms all A channels from them - the per-element kernel above would draw z_b again for every channel a >= b
 // (A (A+1) / 2 Philox blocks instead of A; 56 -> 16 us at 16384 x 32 x 7).  Same draws, same order of summation.
@@ -123,6 +135,17 @@ hipError_t sample_noise(T* noise, long P, int H, int A, const double* chol, cons
 }
 
 template <typename T>
+hipError_t sample_noise_batch(T* noise, int E, long P, int H, int A, const double* chols, const unsigned long long* seeds,
+                              unsigned long long offset, const long long* d_step, hipStream_t s) {
+    if (E < 1 || E > 65535) return hipErrorInvalidValue;
+    if (P <= 0 || H <= 0) return hipSuccess;
+    const long n = P * A * ((H + 3) / 4);
+    hipLaunchKernelGGL(noise_batch_kernel<T>, dim3((unsigned)((n + 255) / 256), (unsigned)E), dim3(256), 0, s, noise, P, H, A,
+                       chols, seeds, offset, d_step);
+    return hipGetLastError();
+}
+
+template <typename T>
 hipError_t filter_noise(T* noise, long P, int H, int A, const double* coeffs, hipStream_t s) {
     const long m = P * A;
     if (m <= 0) return hipSuccess;
@@ -157,6 +180,10 @@ hipError_t color_rows(T* x, long rows, int A, const double* B, hipStream_t s) {
 template hipError_t color_rows<float>(float*, long, int, const double*, hipStream_t);
 template hipError_t color_rows<double>(double*, long, int, const double*, hipStream_t);
 
+template hipError_t sample_noise_batch<float>(float*, int, long, int, int, const double*, const unsigned long long*,
+                                              unsigned long long, const long long*, hipStream_t);
+template hipError_t sample_noise_batch<double>(double*, int, long, int, int, const double*, const unsigned long long*,
+                                               unsigned long long, const long long*, hipStream_t);
 template hipError_t filter_noise<float>(float*, long, int, int, const double*, hipStream_t);
 template hipError_t filter_noise<double>(double*, long, int, int, const double*, hipStream_t);
 

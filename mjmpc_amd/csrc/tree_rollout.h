@@ -7,8 +7,9 @@ namespace mjmpc {
 // sphere/plane contact points, frictionless or with pyramidal friction cones); see tree_rollout.hip.  max_path = links
 // on the longest root-to-leaf path; full = the model needs the instantiation with slide joints / springs / friction
 // cones / more than 8 contact points / fluid forces (with nv <= 16 it runs 16 lanes per particle).  n_shards > 1: model holds one block per shard of P / n_shards
-// consecutive particles (dynamics randomization).  state_out (P = 1 only): the particle's final qpos / qvel are written
-// there in the layout of `state` (the device-resident real env).  clw: closed_loop_linear weights f64 [(d_obs + 1)][A]
+// consecutive particles (dynamics randomization).  state_out (P = 1, or one particle per state shard with
+// fuse.state_out_stride = TREE_STATE_LEN and one model block): the particle's final qpos / qvel are written there in the
+// layout of `state` (the device-resident real env; per row of an episode batch).  clw: closed_loop_linear weights f64 [(d_obs + 1)][A]
 // instead of `mean` (the fresh observation's site is read from state[2 * 32 + 3 ...], which a P = 1 launch with site_out
 // pointing there provides).  model: TREE_BLOB_LEN scalars of T; state: f64 TREE_STATE_LEN (tree_model.h);
 // gen: the model block's T_GEN - 1: the general instantiation (ball / free joints, friction loss, boxes, equalities), 2: with round
@@ -35,6 +36,10 @@ struct TreeFusion {
     int reset_stride = 0;
     double* axis_out = nullptr;
     int inf_on_reset = 0;           // 1: a particle that has reset costs +inf from that env step on (RolloutFusion::inf_on_reset)
+    // episode batches: row blockIdx.y reads its mean at mean + blockIdx.y * mean_stride (0: one mean for every
+    // row), and a launch of one particle per row writes that row's end state to state_out + blockIdx.y * state_out_stride
+    long mean_stride = 0;
+    int state_out_stride = 0;
 };
 // integrator: 0 MuJoCo's Euler, 1 RK4 (mj_RungeKutta, four stages per substep: tree_rollout_rk4.hip - models of up to 16 dofs
 // without elliptic cones; hipErrorInvalidValue otherwise).  Under RK4 the iteration-cap hits and the counts of non-finite

@@ -1620,7 +1620,9 @@ constexpr int min_waves(int scalar_bytes, int DP, bool fric) {
 // is the earlier rounds' to the instruction.
 // RK4 = 1: MuJoCo's mj_RungeKutta instead of mj_Euler - stages 1-6 run four times per substep (tree_rollout_rk4.hip, DESIGN
 // 4.6.3); the 16-lane dense instantiations only.  RK4 = 0 compiles to the Euler kernel it was.
-template <typename T, int DP, int NS, bool FRIC, int PL, int DN, int GEN = 0, int RK4 = 0>
+// EB = 1: an episode batch - row blockIdx.y reads its own mean (fuse.mean_stride) and, one particle per row,
+// writes its end state to its own state vector (fuse.state_out_stride).  EB = 0 compiles to the kernel it was.
+template <typename T, int DP, int NS, bool FRIC, int PL, int DN, int GEN = 0, int RK4 = 0, int EB = 0>
 __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(sizeof(T), DP, FRIC)) void tree_rollout_kernel(
     const T* __restrict__ model_all, int model_stride, const double* __restrict__ state, int state_stride, long P, long shard_size, int H,
     int A, const double* __restrict__ mean,
@@ -1651,6 +1653,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
     // a per-worker set_env_state (subproc_vec_env.py:242-251) its own start state (state_stride != 0).
     const T* model = model_all + (long)blockIdx.y * model_stride;
     state += (long)blockIdx.y * state_stride;
+    if constexpr (EB) mean += (long)blockIdx.y * fuse.mean_stride;      // (episode batches: one mean per row)
     T* M = lds;
     for (int k = threadIdx.x; k < NBLOB; k += blockDim.x) M[k] = model[k];
     for (int k = threadIdx.x; k < (PL - 1) * PL; k += blockDim.x) ELIM[k] = (int)model[T_ELIM + (k / PL) * TL + (k % PL)];
@@ -3703,8 +3706,10 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
     // the elite ranking - instead of a NaN in the mean (as the arm kernel)
     if (fuse.q0_out && live && l == 0) fuse.q0_out[pid] = fabs(q0acc) < (double)INFINITY ? q0acc : (double)INFINITY;
     // the "real env" kept on the device (mjmpc_tree_step_state): particle 0 leaves its state where the next rollout
-    // reads it (the launch has one particle; `state` was read before the first step)
-    if (state_out && pid == 0 && dof) {
+    // reads it (the launch has one particle; `state` was read before the first step).  An episode batch
+    // (mjmpc_tree_step_shard_states) has one particle per row, and each row its own state vector.
+    if (state_out && (EB ? in_shard == 0 : pid == 0) && dof) {
+        if constexpr (EB) state_out += (long)blockIdx.y * fuse.state_out_stride;
         if (!GEN || ball_g <= 0) state_out[l] = (double)q;         // (a ball's first link owns its followers' qpos entries)
         if (GEN && ball_g == 0) {
             state_out[l + 1] = (double)qy;
@@ -3729,24 +3734,25 @@ struct TreeLaunchArgs {
     hipStream_t stream;
     TreeFusion fuse;
 };
-template <typename T>
+template <typename T, int EB>
 hipError_t launch_tree_rollout_dense(int max_path, int nv, int gen, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                      const TreeLaunchArgs& a);
 // ... and so do the instantiations for models with ELLIPTIC friction cones (GEN = 3; tree_rollout_cone.hip, TREE_CONE_TU)
-template <typename T>
+template <typename T, int EB>
 hipError_t launch_tree_rollout_cone(int max_path, int nv, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                     const TreeLaunchArgs& a);
 // ... and so do the RK4 instantiations (tree_rollout_rk4.hip: TREE_DENSE_TU = 4, the forward evaluations per substep)
-template <typename T>
+template <typename T, int EB>
 hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                    const TreeLaunchArgs& a);
+// (each of the three units instantiates its launcher for EB = 0; its *_eb.hip twin, for the episode batches' EB = 1)
 
 #define MJMPC_TREE_LAUNCH(DP_, NS_, FR_, PL_) MJMPC_TREE_LAUNCH_D(DP_, NS_, FR_, PL_, 0, 0)
 #define MJMPC_TREE_LAUNCH_G(DP_, NS_, FR_, PL_, G_) MJMPC_TREE_LAUNCH_D(DP_, NS_, FR_, PL_, 0, G_)
 #define MJMPC_TREE_LAUNCH_D(DP_, NS_, FR_, PL_, DN_, GEN_)                                                            \
     {                                                                                                                 \
         constexpr int per_wg = wg_waves(DP_, FR_, sizeof(T), PL_) * (64 / PL_);                                       \
-        hipLaunchKernelGGL((tree_rollout_kernel<T, DP_, NS_, FR_, PL_, DN_, GEN_>),                                   \
+        hipLaunchKernelGGL((tree_rollout_kernel<T, DP_, NS_, FR_, PL_, DN_, GEN_, 0, EB>),                            \
                            dim3((unsigned)((a.shard + per_wg - 1) / per_wg), (unsigned)a.n_shards),                   \
                            dim3(64 * wg_waves(DP_, FR_, sizeof(T), PL_)), 0, a.stream, model, a.model_stride, a.state, \
                            a.state_stride, a.P, a.shard, a.H, a.A, a.mean, noise, cost, act, obs, nobs, a.diag,       \
@@ -3756,7 +3762,7 @@ hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model
 #if defined(TREE_DENSE_TU) && TREE_DENSE_TU == 4
 // (tree_rollout_rk4.hip: the dense family with RK4's four forward evaluations per substep - launch_tree_rollout_rk4 below)
 #elif defined(TREE_DENSE_TU)
-template <typename T>
+template <typename T, int EB>
 hipError_t launch_tree_rollout_dense(int max_path, int nv, int gen, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                      const TreeLaunchArgs& a) {
     // (16 lanes per particle: the dense in-register factorisation, sized for the model)
@@ -3798,12 +3804,13 @@ hipError_t launch_tree_rollout_dense(int max_path, int nv, int gen, const T* mod
     else MJMPC_TREE_LAUNCH_D(16, 16, true, 16, 16, 0)
     return hipGetLastError();
 }
-template hipError_t launch_tree_rollout_dense<float>(int, int, int, const float*, const float*, float*, float*, float*, float*,
-                                                     const TreeLaunchArgs&);
-template hipError_t launch_tree_rollout_dense<double>(int, int, int, const double*, const double*, double*, double*, double*, double*,
-                                                      const TreeLaunchArgs&);
+#define MJMPC_TREE_INSTANTIATE(EB_)                                                                                   \
+    template hipError_t launch_tree_rollout_dense<float, EB_>(int, int, int, const float*, const float*, float*, float*, float*, \
+                                                              float*, const TreeLaunchArgs&);                         \
+    template hipError_t launch_tree_rollout_dense<double, EB_>(int, int, int, const double*, const double*, double*, double*,   \
+                                                               double*, double*, const TreeLaunchArgs&);
 #elif defined(TREE_CONE_TU)
-template <typename T>
+template <typename T, int EB>
 hipError_t launch_tree_rollout_cone(int max_path, int nv, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                     const TreeLaunchArgs& a) {
     if (nv > 16) {
@@ -3817,21 +3824,23 @@ hipError_t launch_tree_rollout_cone(int max_path, int nv, const T* model, const 
     else MJMPC_TREE_LAUNCH_D(16, 16, true, 16, 16, 3)
     return hipGetLastError();
 }
-template hipError_t launch_tree_rollout_cone<float>(int, int, const float*, const float*, float*, float*, float*, float*, const TreeLaunchArgs&);
-template hipError_t launch_tree_rollout_cone<double>(int, int, const double*, const double*, double*, double*, double*, double*,
-                                                     const TreeLaunchArgs&);
+#define MJMPC_TREE_INSTANTIATE(EB_)                                                                                   \
+    template hipError_t launch_tree_rollout_cone<float, EB_>(int, int, const float*, const float*, float*, float*, float*,    \
+                                                             float*, const TreeLaunchArgs&);                          \
+    template hipError_t launch_tree_rollout_cone<double, EB_>(int, int, const double*, const double*, double*, double*,      \
+                                                              double*, double*, const TreeLaunchArgs&);
 #endif
 #if defined(TREE_DENSE_TU) && TREE_DENSE_TU == 4
 // MuJoCo's RK4 (tree_rollout_kernel's RK4 = 1): every model of up to 16 dofs with pyramidal or no friction cones - the lean
 // 32-lane models too - runs the 16-lane dense family, in four sizes (rows and paths of 4, 8 and 16; rows of 12 on paths of 8 -
 // HalfCheetah, 9 dofs on paths of 8: 18.8 -> 7.6 ms per 4096 x 32 f64 launch against rows and paths of 16), the smallest that fits
-template <typename T>
+template <typename T, int EB>
 hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model, const T* noise, T* cost, T* act, T* obs, T* nobs,
                                    const TreeLaunchArgs& a) {
 #define MJMPC_TREE_LAUNCH_RK4(DP_, DN_, GEN_)                                                                         \
     {                                                                                                                 \
         constexpr int per_wg = wg_waves(DP_, true, sizeof(T), 16) * 4;                                               \
-        hipLaunchKernelGGL((tree_rollout_kernel<T, DP_, 16, true, 16, DN_, GEN_, 1>),                                 \
+        hipLaunchKernelGGL((tree_rollout_kernel<T, DP_, 16, true, 16, DN_, GEN_, 1, EB>),                             \
                            dim3((unsigned)((a.shard + per_wg - 1) / per_wg), (unsigned)a.n_shards),                   \
                            dim3(64 * wg_waves(DP_, true, sizeof(T), 16)), 0, a.stream, model, a.model_stride, a.state, \
                            a.state_stride, a.P, a.shard, a.H, a.A, a.mean, noise, cost, act, obs, nobs, a.diag,       \
@@ -3852,11 +3861,49 @@ hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model
 #undef MJMPC_TREE_LAUNCH_RK4
     return hipGetLastError();
 }
-template hipError_t launch_tree_rollout_rk4<float>(int, int, int, const float*, const float*, float*, float*, float*, float*,
-                                                   const TreeLaunchArgs&);
-template hipError_t launch_tree_rollout_rk4<double>(int, int, int, const double*, const double*, double*, double*, double*, double*,
-                                                    const TreeLaunchArgs&);
+#define MJMPC_TREE_INSTANTIATE(EB_)                                                                                   \
+    template hipError_t launch_tree_rollout_rk4<float, EB_>(int, int, int, const float*, const float*, float*, float*, float*, \
+                                                            float*, const TreeLaunchArgs&);                           \
+    template hipError_t launch_tree_rollout_rk4<double, EB_>(int, int, int, const double*, const double*, double*, double*,   \
+                                                             double*, double*, const TreeLaunchArgs&);
 #elif !defined(TREE_DENSE_TU) && !defined(TREE_CONE_TU)
+// the instantiation the model takes: EB = 0 for every launch but the episode batches' (launch_tree_rollout below)
+template <typename T, int EB>
+static hipError_t launch_tree_rows(int max_path, bool full, int nv, int gen, int integrator, const T* model, const T* noise, T* cost,
+                                   T* act, T* obs, T* nobs, const TreeLaunchArgs& a) {
+    // hinge trees in air with up to 8 frictionless contact points keep the lean instantiation; slide joints, springs,
+    // friction cones, more points or a medium take the full one (three Jacobians per point, 16 points, fluid forces),
+    // which also comes with 16 lanes per particle for models of up to 16 dofs (the reference's swimmer and cheetah)
+    if (integrator == 1) return launch_tree_rollout_rk4<T, EB>(max_path, nv, gen, model, noise, cost, act, obs, nobs, a);
+    if (integrator != 0) return hipErrorInvalidValue;
+    if (gen >= 3) return launch_tree_rollout_cone<T, EB>(max_path, nv, model, noise, cost, act, obs, nobs, a);
+    if (!full) {
+        if (max_path <= 8) MJMPC_TREE_LAUNCH(8, 8, false, 32)
+        else if (max_path <= 16) MJMPC_TREE_LAUNCH(16, 8, false, 32)
+        else MJMPC_TREE_LAUNCH(32, 8, false, 32)
+    } else if (nv <= 16) {
+        return launch_tree_rollout_dense<T, EB>(max_path, nv, gen, model, noise, cost, act, obs, nobs, a);
+    } else if (gen >= 2 ? max_path <= 16 : (max_path > 8 && !(gen && max_path > 16) && !getenv("MJMPC_TREE_SPARSE"))) {
+        // 17 .. 32 dofs on elimination paths of more than 8 links: dense over the particle's 32 lanes - measured at 4096 x 32:
+        // pen-in-hand (paths of 16) f64 16.2 -> 9.8 ms, f32 13.8 -> 8.0; with paths of up to 8 links (a hand with friction
+        // cones) the tree-sparse factorisation with its merged Euler matrix stays ahead, 4.15 against 4.27 ms
+        // (MJMPC_TREE_SPARSE in the environment keeps the tree-sparse one everywhere: the A/B switch of tools/tree_time.py)
+        return launch_tree_rollout_dense<T, EB>(max_path, nv, gen, model, noise, cost, act, obs, nobs, a);
+    } else if (gen >= 2) {
+        // (round 5's record kinds: dense over 32 lanes whatever the path length up to 16 links - the one instantiation; the
+        // tree-sparse kernel only for elimination paths beyond that)
+        MJMPC_TREE_LAUNCH_G(32, 16, true, 32, 2)
+    } else if (gen) {
+        if (max_path <= 16) MJMPC_TREE_LAUNCH_G(16, 16, true, 32, 1)
+        else MJMPC_TREE_LAUNCH_G(32, 16, true, 32, 1)
+    } else {
+        if (max_path <= 8) MJMPC_TREE_LAUNCH(8, 16, true, 32)
+        else if (max_path <= 16) MJMPC_TREE_LAUNCH(16, 16, true, 32)
+        else MJMPC_TREE_LAUNCH(32, 16, true, 32)
+    }
+    return hipGetLastError();
+}
+
 template <typename T>
 hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path, bool full, int nv, const double* state, long P, int H,
                                int A, const double* mean, const T* noise, T* cost, T* act, T* obs, T* nobs, unsigned* diag,
@@ -3864,7 +3911,11 @@ hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path,
                                int gen, TreeFusion fuse, int integrator) {
     if (P <= 0 || H <= 0) return hipSuccess;
     if (gen && !full) return hipErrorInvalidValue;
-    if ((state_out || site_out) && P != 1) return hipErrorInvalidValue;
+    // (state_out with more than one particle: the real-env step of an episode batch, one particle per state shard)
+    const bool batch_step = state_out && !site_out && fuse.state_out_stride == TREE_STATE_LEN && n_model_shards == 1 &&
+                            P == n_state_shards;
+    if ((state_out || site_out) && P != 1 && !batch_step) return hipErrorInvalidValue;
+    if (fuse.state_out_stride != 0 && !batch_step) return hipErrorInvalidValue;
     if (n_model_shards < 1 || n_state_shards < 1) return hipErrorInvalidValue;
     if (n_model_shards > 1 && n_state_shards > 1 && n_model_shards != n_state_shards) return hipErrorInvalidValue;
     TreeLaunchArgs a;
@@ -3884,37 +3935,10 @@ hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path,
     a.site_out = site_out;
     a.stream = stream;
     a.fuse = fuse;
-    // hinge trees in air with up to 8 frictionless contact points keep the lean instantiation; slide joints, springs,
-    // friction cones, more points or a medium take the full one (three Jacobians per point, 16 points, fluid forces),
-    // which also comes with 16 lanes per particle for models of up to 16 dofs (the reference's swimmer and cheetah)
-    if (integrator == 1) return launch_tree_rollout_rk4<T>(max_path, nv, gen, model, noise, cost, act, obs, nobs, a);
-    if (integrator != 0) return hipErrorInvalidValue;
-    if (gen >= 3) return launch_tree_rollout_cone<T>(max_path, nv, model, noise, cost, act, obs, nobs, a);
-    if (!full) {
-        if (max_path <= 8) MJMPC_TREE_LAUNCH(8, 8, false, 32)
-        else if (max_path <= 16) MJMPC_TREE_LAUNCH(16, 8, false, 32)
-        else MJMPC_TREE_LAUNCH(32, 8, false, 32)
-    } else if (nv <= 16) {
-        return launch_tree_rollout_dense<T>(max_path, nv, gen, model, noise, cost, act, obs, nobs, a);
-    } else if (gen >= 2 ? max_path <= 16 : (max_path > 8 && !(gen && max_path > 16) && !getenv("MJMPC_TREE_SPARSE"))) {
-        // 17 .. 32 dofs on elimination paths of more than 8 links: dense over the particle's 32 lanes - measured at 4096 x 32:
-        // pen-in-hand (paths of 16) f64 16.2 -> 9.8 ms, f32 13.8 -> 8.0; with paths of up to 8 links (a hand with friction
-        // cones) the tree-sparse factorisation with its merged Euler matrix stays ahead, 4.15 against 4.27 ms
-        // (MJMPC_TREE_SPARSE in the environment keeps the tree-sparse one everywhere: the A/B switch of tools/tree_time.py)
-        return launch_tree_rollout_dense<T>(max_path, nv, gen, model, noise, cost, act, obs, nobs, a);
-    } else if (gen >= 2) {
-        // (round 5's record kinds: dense over 32 lanes whatever the path length up to 16 links - the one instantiation; the
-        // tree-sparse kernel only for elimination paths beyond that)
-        MJMPC_TREE_LAUNCH_G(32, 16, true, 32, 2)
-    } else if (gen) {
-        if (max_path <= 16) MJMPC_TREE_LAUNCH_G(16, 16, true, 32, 1)
-        else MJMPC_TREE_LAUNCH_G(32, 16, true, 32, 1)
-    } else {
-        if (max_path <= 8) MJMPC_TREE_LAUNCH(8, 16, true, 32)
-        else if (max_path <= 16) MJMPC_TREE_LAUNCH(16, 16, true, 32)
-        else MJMPC_TREE_LAUNCH(32, 16, true, 32)
-    }
-    return hipGetLastError();
+    // an episode batch (one mean per row, or one real env per row) runs the EB = 1 twin of the model's instantiation
+    if (fuse.mean_stride != 0 || fuse.state_out_stride != 0)
+        return launch_tree_rows<T, 1>(max_path, full, nv, gen, integrator, model, noise, cost, act, obs, nobs, a);
+    return launch_tree_rows<T, 0>(max_path, full, nv, gen, integrator, model, noise, cost, act, obs, nobs, a);
 }
 
 template hipError_t launch_tree_rollout<float>(const float*, int, int, bool, int, const double*, long, int, int, const double*,

@@ -3,3 +3,6 @@
 // other model runs the kernels it had.
 #define TREE_CONE_TU
 #include "tree_rollout.hip"
+namespace mjmpc {
+MJMPC_TREE_INSTANTIATE(0)
+}  // namespace mjmpc

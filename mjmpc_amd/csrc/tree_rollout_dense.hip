@@ -4,3 +4,6 @@
 // parallelism is all the scheduler can offer.
 #define TREE_DENSE_TU 1        // (forward evaluations per substep: Euler; tree_rollout_rk4.hip is the unit with 4)
 #include "tree_rollout.hip"
+namespace mjmpc {
+MJMPC_TREE_INSTANTIATE(0)
+}  // namespace mjmpc

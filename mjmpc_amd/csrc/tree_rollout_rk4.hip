@@ -4,3 +4,6 @@
 // evaluations per substep of the unit's instantiations (tree_rollout_dense.hip: 1).  Every Euler model runs the kernels it had.
 #define TREE_DENSE_TU 4
 #include "tree_rollout.hip"
+namespace mjmpc {
+MJMPC_TREE_INSTANTIATE(0)
+}  // namespace mjmpc

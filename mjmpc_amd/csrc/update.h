@@ -72,6 +72,15 @@ hipError_t mppi_fused_update(const double* q0, const T* actions, double lam, dou
                              hipStream_t s, double* action_host = nullptr, long long* step_counter = nullptr,
                              const NextNoise* next = nullptr);
 
+// E independent fused MPPI updates in the same two launches (grid row e = episode e): each row is mppi_fused_update of
+// P particles with q0 + e P, actions + e P H A, lam[e], step[e], mean + e H A, action_out + e A; row 0 increments the shared
+// step counter once.  ws: mppi_fused_batch_workspace_doubles(E, P, H, A).
+long mppi_fused_batch_workspace_doubles(int E, long P, int H, int A);
+template <typename T>
+hipError_t mppi_fused_update_batch(int E, const double* q0, const T* actions, const double* lam, const double* step,
+                                   int shift_mode, long P, int H, int A, double* mean, double* action_out,
+                                   long long* step_counter, double* ws, hipStream_t s);
+
 // the all-gathered records of G GPUs -> mean, action (device + mapped host copy with completion flag), step counter, shift
 hipError_t mppi_fused_combine(const double* records, int G, double P_total, double lam, double step, int shift_mode,
                               int H, int A, double* mean, double* action_out, double* value, double* action_host,
@@ -92,6 +101,12 @@ template <typename T>
 hipError_t sample_noise(T* noise, long P, int H, int A, const double* chol, const double* coeffs,
                         unsigned long long seed, unsigned long long offset, long particle_offset, const long long* d_step,
                         hipStream_t s, int diag_only = 0);
+
+// Episode batches: row e of noise [E][P][H][A] is sample_noise(..., chols + e A A, NULL, seeds[e], offset, 0, d_step,
+// diag_only = 1) - diagonal factors only.
+template <typename T>
+hipError_t sample_noise_batch(T* noise, int E, long P, int H, int A, const double* chols, const unsigned long long* seeds,
+                              unsigned long long offset, const long long* d_step, hipStream_t s);
 
 // the in-place recursive 3-tap filter of control_utils.py:32-33 on its own
 template <typename T>

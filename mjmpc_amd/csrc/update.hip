@@ -1168,11 +1168,12 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-// partial[b] = { m_b, S_b, W_b[H*A] } with weights exp(x_p - m_b), x_p = -q0_p / lam
+// partial[b] = { m_b, S_b, W_b[H*A] } with weights exp(x_p - m_b), x_p = -q0_p / lam (b = blockIdx.x; the body is shared
+// with the episode-batch kernel below, whose grid row picks the episode's arrays)
 template <typename T>
-__global__ void fused_partial_kernel(const double* __restrict__ q0, const T* __restrict__ actions, double lam, long P,
-                                     int HA, double* __restrict__ partial, const long long* __restrict__ d_step,
-                                     long long* __restrict__ step_snapshot) {
+__device__ __forceinline__ void fused_partial_body(const double* __restrict__ q0, const T* __restrict__ actions, double lam,
+                                                   long P, int HA, double* __restrict__ partial,
+                                                   const long long* __restrict__ d_step, long long* __restrict__ step_snapshot) {
     __shared__ double e_s[FCH];
     const long p0 = (long)blockIdx.x * FCH;
     const int n = (int)((P - p0) < FCH ? (P - p0) : FCH);
@@ -1205,24 +1206,34 @@ __global__ void fused_partial_kernel(const double* __restrict__ q0, const T* __r
     }
 }
 
+template <typename T>
+__global__ void fused_partial_kernel(const double* __restrict__ q0, const T* __restrict__ actions, double lam, long P,
+                                     int HA, double* __restrict__ partial, const long long* __restrict__ d_step,
+                                     long long* __restrict__ step_snapshot) {
+    fused_partial_body<T>(q0, actions, lam, P, HA, partial, d_step, step_snapshot);
+}
+
+// episode batches: grid row e runs fused_partial_kernel on episode e's particles into its own run of partials
+template <typename T>
+__global__ void fused_partial_batch_kernel(const double* __restrict__ q0, const T* __restrict__ actions,
+                                           const double* __restrict__ lam, long P, int HA, double* __restrict__ partial,
+                                           long partial_stride) {
+    const long e = blockIdx.y;
+    fused_partial_body<T>(q0 + e * P, actions + e * P * HA, lam[e], P, HA, partial + e * partial_stride, nullptr, nullptr);
+}
+
 // merge partials -> mean update (mppi.py:69-82) -> action = mean[0] (olgaussian_mpc.py:71) -> shift
 // (olgaussian_mpc.py:116-129; shift_mode < 0: no shift).  Optionally leaves the GPU record
 // [xmax | S | W] for the multi-GPU combine and the value -lam logsumexp (mppi.py:113-131).
 // Workgroups past the first belong to a different job riding in the same launch: they draw the raw samples of the
 // NEXT control step (the noise buffer is free once the rollout has finished).  Workgroup 0 publishes the action
 // first, so the sampler runs in the shadow of the host's round trip instead of on the critical path.
-template <typename T>
-__global__ void fused_final_kernel(const double* __restrict__ partial, int nb, int H, int A, double lam, double step,
-                                   int shift_mode, double P_total, double* __restrict__ mean,
-                                   double* __restrict__ action_out, double* __restrict__ record,
-                                   double* __restrict__ value, double* __restrict__ action_host,
-                                   long long* __restrict__ step_counter, NextNoise nn, long P,
-                                   const long long* __restrict__ step_snapshot) {
-    if (blockIdx.x > 0) {
-        noise_element<T>((T*)nn.noise, ((long)blockIdx.x - 1) * blockDim.x + threadIdx.x, P, H, A, nn.chol, nn.seed,
-                         nn.offset + (unsigned long long)*step_snapshot, nn.particle_offset, nn.diag_only);
-        return;
-    }
+// (the merging workgroup's part; shared with the episode-batch kernel below)
+__device__ __forceinline__ void fused_final_body(const double* __restrict__ partial, int nb, int H, int A, double lam,
+                                                 double step, int shift_mode, double P_total, double* __restrict__ mean,
+                                                 double* __restrict__ action_out, double* __restrict__ record,
+                                                 double* __restrict__ value, double* __restrict__ action_host,
+                                                 long long* __restrict__ step_counter) {
     // sc[nb] | ss[nb] | nm[H*A] | red[32] | part[nsl * H*A].  A workgroup of 1024 threads (launches with many partials:
     // the merge is a chain of nb / 8 trips to L2 per entry, 16 us of the critical path at 256 partials) splits the partials
     // into nsl = 4 slices, one per 256 threads, and adds the slices in order; 256 threads keep one slice and the order of
@@ -1316,6 +1327,32 @@ __global__ void fused_final_kernel(const double* __restrict__ partial, int nb, i
         }
         mean[j] = v;
     }
+}
+
+template <typename T>
+__global__ void fused_final_kernel(const double* __restrict__ partial, int nb, int H, int A, double lam, double step,
+                                   int shift_mode, double P_total, double* __restrict__ mean,
+                                   double* __restrict__ action_out, double* __restrict__ record,
+                                   double* __restrict__ value, double* __restrict__ action_host,
+                                   long long* __restrict__ step_counter, NextNoise nn, long P,
+                                   const long long* __restrict__ step_snapshot) {
+    if (blockIdx.x > 0) {
+        noise_element<T>((T*)nn.noise, ((long)blockIdx.x - 1) * blockDim.x + threadIdx.x, P, H, A, nn.chol, nn.seed,
+                         nn.offset + (unsigned long long)*step_snapshot, nn.particle_offset, nn.diag_only);
+        return;
+    }
+    fused_final_body(partial, nb, H, A, lam, step, shift_mode, P_total, mean, action_out, record, value, action_host,
+                     step_counter);
+}
+
+// episode batches: grid row e merges episode e's partials into its mean and action; row 0 advances the shared step counter
+__global__ void fused_final_batch_kernel(const double* __restrict__ partial, long partial_stride, int nb, int H, int A,
+                                         const double* __restrict__ lam, const double* __restrict__ step, int shift_mode,
+                                         double P_total, double* __restrict__ mean, double* __restrict__ action_out,
+                                         long long* __restrict__ step_counter) {
+    const long e = blockIdx.y;
+    fused_final_body(partial + e * partial_stride, nb, H, A, lam[e], step[e], shift_mode, P_total, mean + e * H * A,
+                     action_out ? action_out + e * A : nullptr, nullptr, nullptr, nullptr, e == 0 ? step_counter : nullptr);
 }
 
 inline int nblocks(long n, int b) { return (int)((n + b - 1) / b); }
@@ -1627,6 +1664,28 @@ hipError_t mppi_fused_update(const double* q0, const T* actions, double lam, dou
     return hipGetLastError();
 }
 
+long mppi_fused_batch_workspace_doubles(int E, long P, int H, int A) { return (long)E * nblocks(P, FCH) * (2 + (long)H * A); }
+
+// One episode per grid row, each row what mppi_fused_update does for its P particles: the same partials (FCH particles per
+// workgroup), the same merging workgroup (fth threads, the same slices) and so the same order of every sum.
+template <typename T>
+hipError_t mppi_fused_update_batch(int E, const double* q0, const T* actions, const double* lam, const double* step,
+                                   int shift_mode, long P, int H, int A, double* mean, double* action_out,
+                                   long long* step_counter, double* ws, hipStream_t s) {
+    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1) return hipErrorInvalidValue;
+    const int nb = nblocks(P, FCH), HA = H * A;
+    const long stride = (long)nb * (2 + HA);
+    const int fth = nb > 64 ? 1024 : BLK, nsl = fth >= 512 ? fth / 256 : 1;
+    hipLaunchKernelGGL(fused_partial_batch_kernel<T>, dim3(nb, E), dim3(BLK), 0, s, q0, actions, lam, P, HA, ws, stride);
+    const size_t lds = sizeof(double) * (2 * (size_t)nb + HA + 32 + (nsl > 1 ? (size_t)nsl * HA : 0));
+    if (lds > 150 * 1024) return hipErrorInvalidValue;
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)fused_final_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(fused_final_batch_kernel, dim3(1, E), dim3(fth), lds, s, (const double*)ws, stride, nb, H, A, lam, step,
+                       shift_mode, (double)P, mean, action_out, step_counter);
+    return hipGetLastError();
+}
+
 // Sharded runs: the G all-gathered records [xmax | S | W[H*A]] have the layout of the per-workgroup partials, so
 // the same kernel merges them (rank order = fixed order -> bit-identical on every rank), updates the mean, reads
 // out and publishes the action, advances the step counter and shifts - one launch after the all-gather.
@@ -1692,7 +1751,9 @@ hipError_t step_tail(double* mean, int H, int A, int mode, const double* row, do
     template hipError_t rs_best<T>(const T*, long, long, int, int, double*, double*, hipStream_t);                   \
     template hipError_t mppi_fused_update<T>(const double*, const T*, double, double, int, long, int, int, double*,  \
                                              double*, double*, double*, double*, hipStream_t, double*, long long*,   \
-                                             const NextNoise*);
+                                             const NextNoise*);                                                      \
+    template hipError_t mppi_fused_update_batch<T>(int, const double*, const T*, const double*, const double*, int, long, \
+                                                   int, int, double*, double*, long long*, double*, hipStream_t);
 INST(float)
 INST(double)
 
