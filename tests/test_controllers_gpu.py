@@ -225,6 +225,13 @@ def test_device_noise_statistics():
     np.testing.assert_allclose(flat.mean(0), 0, atol=5 * np.sqrt(np.diag(cov).max() / flat.shape[0]))      # five sigma of a sample mean
     np.testing.assert_allclose(np.cov(flat, rowvar=False), cov, rtol=0.05, atol=0.03)
     assert abs(np.corrcoef(raw[:, 0, 0], raw[:, 1, 0])[0, 1]) < 0.03          # white along the horizon
+    # ... and across every pair of (t, channel) columns of an uncoloured draw: the Gaussian bound on the largest of m
+    # correlations of n independent samples, sqrt(2 ln(2 m / 0.01) / n) (tests/test_philox_ref_cpu.py holds the reference
+    # generator to the same bound)
+    white = dev.sample_noise(Pn, np.eye(An), [1.0, 0.0, 0.0], 7, 3).cpu().numpy().reshape(Pn, Hn * An)
+    pairs = Hn * An * (Hn * An - 1) // 2
+    corr = np.corrcoef(white, rowvar=False) - np.eye(Hn * An)
+    assert np.abs(corr).max() < np.sqrt(2.0 * np.log(2.0 * pairs / 0.01) / Pn)
     co = [0.25, 0.8, 0.1]
     filt = dev.sample_noise(Pn, cov, co, 7, 3).cpu().numpy()
     want = raw.copy()
