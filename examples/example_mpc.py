@@ -91,7 +91,7 @@ def main():
         params.setdefault("base_action", exp.get("base_action", "null"))
         params.update(noise_mode=args.noise_mode, noise_dtype=args.dtype)
     else:
-        params.setdefault("base_action", exp.get("base_action", "null"))
+        params.setdefault("base_action", exp.get("base_action", "null"))     # (a pfmpc block may set noise_mode: 'device' itself)
     n_episodes = args.episodes or exp["n_episodes"]
     ep_rewards = np.zeros(n_episodes)
     trajectories = []
@@ -103,9 +103,12 @@ def main():
         policy = MPCPolicy(controller_type=controller_type, param_dict=params, batch_size=1)
         ctrl = policy.controller
         ctrl.set_sim_state_fn = sim.set_env_state
-        device_path = args.noise_mode != "host" and controller_type != "pfmpc"
+        if controller_type == "pfmpc":
+            device_path = params.get("noise_mode", "host") == "device"
+        else:
+            device_path = args.noise_mode != "host"
         ctrl.rollout_fn = make_device_rollout_fn(sim) if device_path else make_rollout_fn(sim)
-        if args.graph and device_path:
+        if args.graph and device_path and controller_type != "pfmpc":
             ctrl.enable_graph()
         rewards, infos, actions, observations = [], [], [], []
         for _ in range(exp["max_ep_length"]):

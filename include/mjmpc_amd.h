@@ -575,6 +575,40 @@ int mjmpc_sample_noise(int dtype, void* d_noise, int64_t P, int H, int A, const 
 int mjmpc_sample_noise_batch(int dtype, int E, void* d_noise, int64_t P, int H, int A, const double* d_chols,
                              const uint64_t* d_seeds, uint64_t offset, const int64_t* d_step, void* stream);
 
+/* PFMPC with the particle set on the device (mjmpc/control/particle_filter_controller.py:92-174; csrc/pfmpc.hip).  The set
+ * d_set (float64 [M][H][A]), its mean (float64 [H][A]) and the weights are float64; random numbers are the Philox stream of
+ * mjmpc_sample_noise.  One control step is  delta -> rollout -> weights -> resample -> gather_shift -> finish.
+ * d_ws: mjmpc_pf_workspace_bytes(M, H, A) bytes, 8-byte aligned, the same for resample, gather_shift and finish.
+ *
+ * mjmpc_pf_weights   d_weights[p] = softmax_p((-1 / lam) d_q0[p]) (:104-113; a non-finite q0 weighs nothing), one workgroup,
+ *                    fixed summation tree.  d_first (device float64, may be NULL) receives the resampling's first pointer,
+ *                    random.uniform(0, 1 / M)'s formula on a Philox uniform: (1.0 / M) * double(u), u = (float(c0) + 0.5f) *
+ *                    2^-32, c0 the first word of the block keyed (seed, offset + *d_step, chan = 2^64 - 1, quad 0) in
+ *                    mjmpc_sample_noise's key layout (no particle's channel index reaches that chan).
+ * mjmpc_pf_resample  the systematic resampling (:159-171): d_idx[m] = first i whose running sum of d_weights reaches the
+ *                    pointer *d_first + m / M, capped at M - 1; -1 (the last particle, as numpy's index -1) for a pointer
+ *                    <= 0.  The running sum is the strictly sequential left-to-right float64 sum - np.cumsum's bits -: one
+ *                    lane adds (M dependent additions), so the launch is linear in M.  One workgroup.
+ * mjmpc_pf_gather_shift  d_set_out[m] = d_set[d_idx[m]] (must not alias d_set), shifted unless shift_mode < 0 (:127-150):
+ *                    rows move up by one, every row gets + jitter - mjmpc_sample_noise(MJMPC_F64, ., M, H, A, d_chol,
+ *                    d_coeffs, seed, offset, 0, d_step, chol_is_diagonal = 1) element for element, drawn in the kernel -, then
+ *                    the last row becomes 0 (shift_mode 0, 'null') or the jittered row H - 2 (1, 'repeat').  d_gathered
+ *                    (float64 [M][H][A], may be NULL) receives the unshifted survivors; per-workgroup sums of them stay in
+ *                    d_ws for mjmpc_pf_finish.
+ * mjmpc_pf_finish    d_mean = the mean of the unshifted survivors (:97; fixed summation tree, no atomics), d_action_out
+ *                    (float64 [A], may be NULL) = d_mean[0], *d_step_counter += 1 (may be NULL).
+ * mjmpc_pf_delta     d_delta (dtype [M][H][A]) = d_set - d_mean: the deviations a rollout takes beside d_mean (:74-90).   */
+int64_t mjmpc_pf_workspace_bytes(int64_t M, int H, int A);
+int mjmpc_pf_weights(int64_t M, const double* d_q0, double lam, uint64_t seed, uint64_t offset, const int64_t* d_step,
+                     double* d_weights, double* d_first, void* stream);
+int mjmpc_pf_resample(int64_t M, const double* d_weights, const double* d_first, int32_t* d_idx, void* d_ws, void* stream);
+int mjmpc_pf_gather_shift(int64_t M, int H, int A, const double* d_set, const int32_t* d_idx, int shift_mode,
+                          const double* d_chol, const double* d_coeffs, uint64_t seed, uint64_t offset, const int64_t* d_step,
+                          double* d_set_out, double* d_gathered, void* d_ws, void* stream);
+int mjmpc_pf_finish(int64_t M, int H, int A, const void* d_ws, double* d_mean, double* d_action_out, int64_t* d_step_counter,
+                    void* stream);
+int mjmpc_pf_delta(int dtype, int64_t M, int H, int A, const double* d_set, const double* d_mean, void* d_delta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

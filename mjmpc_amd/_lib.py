@@ -114,6 +114,13 @@ SIGNATURES = {
     "mjmpc_comm_destroy": (_int, [_vp]),
     "mjmpc_sample_noise": (_int, [_int, _vp, _i64, _int, _int, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _i64, _vp, _int, _vp]),
     "mjmpc_sample_noise_batch": (_int, [_int, _int, _vp, _i64, _int, _int, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
+    "mjmpc_pf_workspace_bytes": (_i64, [_i64, _int, _int]),
+    "mjmpc_pf_weights": (_int, [_i64, _vp, _dbl, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "mjmpc_pf_resample": (_int, [_i64, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_pf_gather_shift": (_int, [_i64, _int, _int, _vp, _vp, _int, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    "mjmpc_pf_finish": (_int, [_i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_pf_delta": (_int, [_int, _i64, _int, _int, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

@@ -40,6 +40,22 @@ __device__ __forceinline__ void normal_quad(unsigned long long seed, unsigned lo
     z[3] = r1 * __builtin_amdgcn_sinf(a1);
 }
 
+// channel a of the coloured normals of (global particle, t-quad): x[k] = sum_{b <= a} L[a][b] z_b[k], ascending b
+__device__ __forceinline__ void coloured_quad(const double* __restrict__ chol, int A, int a, int diag_only,
+                                              unsigned long long seed, unsigned long long offset, long particle, int t4,
+                                              double* x) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) x[k] = 0.0;
+    for (int b = diag_only ? a : 0; b <= a; ++b) {
+        const double l = chol[a * A + b];
+        if (l == 0.0) continue;
+        float z[4];
+        normal_quad(seed, offset, (unsigned long long)(particle * A + b), (unsigned)t4, z);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x[k] += l * (double)z[k];
+    }
+}
+
 // coloured normals of one (particle, channel, t-quad): gid enumerates P x ceil(H/4) x A
 template <typename T>
 __device__ __forceinline__ void noise_element(T* __restrict__ noise, long gid, long P, int H, int A,
@@ -50,15 +66,8 @@ __device__ __forceinline__ void noise_element(T* __restrict__ noise, long gid, l
     const int a = (int)(gid % A);
     const int t4 = (int)((gid / A) % H4);
     const long p = gid / ((long)A * H4);
-    double x[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = diag_only ? a : 0; b <= a; ++b) {
-        const double l = chol[a * A + b];
-        if (l == 0.0) continue;
-        float z[4];
-        normal_quad(seed, offset, (unsigned long long)((p + particle_offset) * A + b), (unsigned)t4, z);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x[k] += l * (double)z[k];
-    }
+    double x[4];
+    coloured_quad(chol, A, a, diag_only, seed, offset, p + particle_offset, t4, x);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         if (4 * t4 + k < H) noise[(p * H + 4 * t4 + k) * A + a] = (T)x[k];
