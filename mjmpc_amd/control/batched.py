@@ -160,21 +160,14 @@ class BatchedMPPI:
         """One state dict per episode, in the env classes' format: ``{qp, qv, target_pos}`` or ``{qpos, qvel}``."""
         if len(states) != self.num_episodes:
             raise ValueError("set_states takes one state per episode (%d), got %d" % (self.num_episodes, len(states)))
-        m = self.model
         unpacked = [self.engine._unpack(s) for s in states]
-        arr = np.zeros((self.num_episodes, 78))        # MJMPC_TREE_STATE_LEN: qpos[40] | qvel[32] | target[3] | -
-        for k, s in enumerate(unpacked):
-            arr[k, :m.nq], arr[k, 40:40 + m.nv], arr[k, 72:75] = s["qp"], s["qv"], s["target_pos"]
-        _lib.check(self.lib.mjmpc_tree_set_shard_states(self.engine._h, arr.ctypes.data_as(_lib._dp), self.num_episodes,
-                                                        self._stream()))
+        self.engine.set_shard_states_raw(unpacked)
         self._targets = [s["target_pos"].copy() for s in unpacked]
 
     def get_states(self):
         """The E real envs' states as state dicts (one device-to-host copy; synchronises the stream)."""
         E, m = self.num_episodes, self.model
-        qp, qv = np.zeros((E, m.nq)), np.zeros((E, m.nv))
-        _lib.check(self.lib.mjmpc_tree_get_shard_states(self.engine._h, qp.ctypes.data_as(_lib._dp),
-                                                        qv.ctypes.data_as(_lib._dp), self._stream()))
+        qp, qv = self.engine.get_shard_states()
         self._check_resets()
         if self.forward_task:
             return [dict(qpos=qp[e].copy(), qvel=qv[e].copy()) for e in range(E)]

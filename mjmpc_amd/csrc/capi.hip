@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/mjmpc_amd.h"
@@ -51,33 +52,182 @@ int hip_fail(hipError_t e, const char* what) {
 
 }  // namespace
 
-struct mjmpc_arm_s {
+// The element type of a launch from the ABI's dtype code: f(float()) or f(double()) issues the launch(es) and returns
+// their hipError_t, `what` names them in the error message.
+template <typename F>
+static int with_dtype(int dtype, const char* what, F&& f) {
+    hipError_t e;
+    if (dtype == MJMPC_F32) e = f(float());
+    else if (dtype == MJMPC_F64) e = f(double());
+    else return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
+    if (e != hipSuccess) return hip_fail(e, what);
+    return 0;
+}
+
+/* ---- the engine core: what the arm and the tree engine are on the host, once ------------------------------------------ */
+struct engine_core {
     int device = 0;
     int nv = 0, nu = 0, d_obs = 0;
     float* model_f32 = nullptr;
     double* model_f64 = nullptr;
-    double* state = nullptr;        // MJMPC_ARM_STATE_LEN
+    double* state = nullptr;        // MJMPC_ARM_STATE_LEN / MJMPC_TREE_DEVICE_STATE_LEN
     unsigned* diag = nullptr;
-    double* pinned = nullptr;       // host staging for set_state: a ring of STAGE_SLOTS vectors, one event each
+    double* pinned = nullptr;       // host staging for set_state: a ring of 4 state vectors, one event each
     hipEvent_t staged[4] = {nullptr, nullptr, nullptr, nullptr};
     int stage_next = 0;
     int n_shards = 1;               // > 1: model_f32 / model_f64 hold one block per shard
-    double* zero_action = nullptr;  // [32] zeros (the kinematics-only launch of mjmpc_tree_rollout_cl)
-    double* scratch = nullptr;      // [8] a place for that launch's cost
     double* shard_states = nullptr; // n_state_shards state vectors (per-shard start states)
     int n_state_shards = 0;
+    double* reset_rec = nullptr;    // n_shards records: MuJoCo's reset on instability (RolloutFusion / TreeFusion::reset_rec)
+    int inf_on_reset = 0;           // mjmpc_*_set_reset_returns
+    std::vector<double*> reset_retired;     // reset records that were replaced: bound launchers / captured graphs carry the
+                                            // pointer by value (RolloutFusion, MonoStep), so they stay allocated until destroy
+};
+
+template <typename T>
+static const T* model(const engine_core* h) {
+    if constexpr (std::is_same<T, float>::value) return h->model_f32;
+    else return h->model_f64;
+}
+
+// create: the device and pinned memory every engine owns, and the upload of its one model block
+static int core_create(engine_core* h, const double* blob, int n_blob, size_t state_len, size_t diag_bytes) {
+    std::vector<float> f32(blob, blob + n_blob);
+    HIP_TRY(hipMalloc(&h->model_f32, sizeof(float) * n_blob));
+    HIP_TRY(hipMalloc(&h->model_f64, sizeof(double) * n_blob));
+    HIP_TRY(hipMalloc(&h->state, sizeof(double) * state_len));
+    HIP_TRY(hipMalloc(&h->diag, diag_bytes));
+    HIP_TRY(hipHostMalloc(&h->pinned, sizeof(double) * state_len * 4));
+    for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreateWithFlags(&h->staged[k], hipEventDisableTiming));
+    HIP_TRY(hipMemcpy(h->model_f32, f32.data(), sizeof(float) * n_blob, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(h->model_f64, blob, sizeof(double) * n_blob, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(h->state, 0, sizeof(double) * state_len));
+    HIP_TRY(hipMemset(h->diag, 0, diag_bytes));
+    return 0;
+}
+
+// destroy (also of a half-created engine: everything that is not there yet is null)
+static void core_free(engine_core* h) {
+    hipSetDevice(h->device);
+    hipFree(h->model_f32);
+    hipFree(h->model_f64);
+    hipFree(h->state);
+    hipFree(h->diag);
+    hipFree(h->shard_states);
+    hipFree(h->reset_rec);
+    for (double* p : h->reset_retired) hipFree(p);
+    if (h->pinned) hipHostFree(h->pinned);
+    for (int k = 0; k < 4; ++k) if (h->staged[k]) hipEventDestroy(h->staged[k]);
+}
+
+static int core_dims(const engine_core* h, int* nv, int* nu, int* d_obs) {
+    if (!h) return fail(MJMPC_E_BADARG, "null engine");
+    if (nv) *nv = h->nv;
+    if (nu) *nu = h->nu;
+    if (d_obs) *d_obs = h->d_obs;
+    return 0;
+}
+
+// set_state: pack(stage) writes the state vector into a pinned slot, which is copied to the device on `s`.
+// Staging ring: wait only for the copy that last used THIS slot (four calls ago), never for the stream - a
+// captured control iteration still running on `s` keeps running while the next state is being staged.
+template <typename Pack>
+static int core_set_state(engine_core* h, size_t state_len, hipStream_t s, Pack&& pack) {
+    HIP_TRY(hipSetDevice(h->device));
+    const int slot = h->stage_next;
+    h->stage_next = (slot + 1) & 3;
+    HIP_TRY(hipEventSynchronize(h->staged[slot]));
+    double* stage = h->pinned + (size_t)slot * state_len;
+    pack(stage);
+    HIP_TRY(hipMemcpyAsync(h->state, stage, sizeof(double) * state_len, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(h->staged[slot], s));
+    return 0;
+}
+
+// set_shard_models: n_shards validated blocks (host, blob_len each) replace the engine's.  make_records(&rec) builds the
+// reset records of the NEW blocks before anything is committed: if that (or an allocation, or a copy) fails the engine
+// keeps its old models, shard count and records.
+template <typename MakeRecords>
+static int core_swap_models(engine_core* h, const double* blobs, int n_shards, size_t blob_len, MakeRecords&& make_records) {
+    const size_t n = (size_t)n_shards * blob_len;
+    std::vector<float> f32(blobs, blobs + n);
+    HIP_TRY(hipDeviceSynchronize());
+    float* m32 = nullptr;
+    double* m64 = nullptr;
+    HIP_TRY(hipMalloc(&m32, sizeof(float) * n));
+    if (hipError_t e = hipMalloc(&m64, sizeof(double) * n); e != hipSuccess) {
+        hipFree(m32);
+        return hip_fail(e, "hipMalloc");
+    }
+    hipError_t e = hipMemcpy(m32, f32.data(), sizeof(float) * n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m64, blobs, sizeof(double) * n, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(m32);
+        hipFree(m64);
+        return hip_fail(e, "hipMemcpy");
+    }
+    double* rec = nullptr;
+    if (int rc = make_records(&rec); rc != 0) {
+        hipFree(m32);
+        hipFree(m64);
+        return rc;
+    }
+    hipFree(h->model_f32);
+    hipFree(h->model_f64);
+    h->model_f32 = m32;
+    h->model_f64 = m64;
+    h->n_shards = n_shards;
+    if (h->reset_rec) h->reset_retired.push_back(h->reset_rec);     // (launchers bound earlier still point at it)
+    h->reset_rec = rec;
+    return 0;
+}
+
+// set_shard_states: room for n_shards state vectors (0: none)
+static int core_resize_shard_states(engine_core* h, int n_shards, size_t state_len) {
+    if (n_shards == h->n_state_shards) return 0;
+    HIP_TRY(hipDeviceSynchronize());
+    hipFree(h->shard_states);
+    h->shard_states = nullptr;
+    h->n_state_shards = 0;
+    if (n_shards > 0) HIP_TRY(hipMalloc(&h->shard_states, sizeof(double) * state_len * n_shards));
+    h->n_state_shards = n_shards;
+    return 0;
+}
+
+// (`host` is pageable memory: the call returns when the copy has been made)
+static int core_upload_shard_states(engine_core* h, const double* host, size_t n_doubles, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(h->shard_states, host, sizeof(double) * n_doubles, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
+}
+
+static int read_counter(const engine_core* h, int index, uint32_t* count) {
+    if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    unsigned c = 0;
+    HIP_TRY(hipMemcpy(&c, h->diag + index, sizeof(unsigned), hipMemcpyDeviceToHost));
+    *count = c;
+    return 0;
+}
+
+static int set_reset_returns(engine_core* h, int inf_returns) {
+    if (!h) return fail(MJMPC_E_BADARG, "null argument");
+    h->inf_on_reset = inf_returns ? 1 : 0;
+    return 0;
+}
+
+/* ---- arm engine: what it adds to the core ------------------------------------------------------------------------------ */
+struct mjmpc_arm_s : engine_core {
+    bool xj = false;                // slide joints / friction loss: launches go to the extended-joint build (arm_blob_is_xj)
     // mjmpc_arm_mppi_step: the rollout workgroups' records.  The pointer travels to the kernels BY VALUE (MonoStep), so a
     // captured graph holds it: the buffer only ever GROWS, and a buffer it outgrew stays allocated until the handle is
     // destroyed (mono_retired) - a graph captured at one (P, H) survives later calls at another
-    double* reset_rec = nullptr;    // n_shards records of ARM_RESET_LEN: MuJoCo's reset on instability (RolloutFusion::reset_rec)
-    int inf_on_reset = 0;           // mjmpc_arm_set_reset_returns
-    bool xj = false;                // slide joints / friction loss: launches go to the extended-joint build (arm_blob_is_xj)
-    std::vector<double*> reset_retired;     // reset records that were replaced: bound launchers / captured graphs carry the
-                                            // pointer by value (RolloutFusion, MonoStep), so they stay allocated until destroy
     double* mono_tree = nullptr;
     size_t mono_cap = 0;            // doubles
     std::vector<double*> mono_retired;
 };
+constexpr int ARM_DIAG_ENV_RESETS = 2;      // (diag: [0] solver failures, [1] resets, [2] resets of the real env)
 
 // which build of the arm kernels an engine's launches go to: the extended-joint one (arm_rollout_xj.hip) when some block of its
 // model has a slide joint or a dof with friction loss
@@ -98,92 +248,6 @@ static hipError_t arm_finish_launch(const mjmpc_arm_s* h, A&&... a) {
     return h->xj ? mjmpc::launch_arm_mppi_finish_xj<T>(a...) : mjmpc::launch_arm_mppi_finish<T>(a...);
 }
 
-struct mjmpc_tree_s {
-    int device = 0;
-    int nv = 0, nu = 0, d_obs = 0, max_path = 0, nq = 0;
-    bool full = false;              // slide joints, springs, friction cones, > 8 contact points or a medium: the full kernel
-    int gen = 0;                    // T_GEN: 1 ball / free joints, friction loss, boxes, equalities, tendon limits (the general
-                                    // instantiation), 2 round 5's record kinds on top (instantiations of their own)
-    int n_shards = 1;               // > 1: model_f32 / model_f64 hold one block per shard
-    double* zero_action = nullptr;  // [32] zeros (the kinematics-only launch of mjmpc_tree_rollout_cl)
-    double* scratch = nullptr;      // [8] a place for that launch's cost
-    float* model_f32 = nullptr;
-    double* model_f64 = nullptr;
-    double* state = nullptr;        // MJMPC_TREE_DEVICE_STATE_LEN
-    unsigned* diag = nullptr;
-    double* shard_states = nullptr; // n_state_shards state vectors (per-shard start states)
-    int n_state_shards = 0;
-    double* pinned = nullptr;       // host staging for set_state: a ring of 4 vectors, one event each
-    hipEvent_t staged[4] = {nullptr, nullptr, nullptr, nullptr};
-    int stage_next = 0;
-    std::vector<double> topo;       // create-time topology tables (shard blocks must match them)
-    double* reset_rec = nullptr;    // n_shards records of TREE_RESET_LEN: MuJoCo's reset on instability (TreeFusion::reset_rec)
-    int inf_on_reset = 0;           // mjmpc_tree_set_reset_returns
-    std::vector<double*> reset_retired;     // (as mjmpc_arm_s::reset_retired)
-    int integrator = MJMPC_INTEGRATOR_EULER;    // mjmpc_tree_create_ex: every launch (the reset records' too) steps with it
-};
-
-extern "C" {
-
-int mjmpc_abi_version(void) { return MJMPC_ABI_VERSION; }
-
-const char* mjmpc_last_error(void) { return g_err; }
-
-int mjmpc_device_count(void) {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-int mjmpc_graph_kernel_nodes(void* hip_graph, int64_t* n_out) {
-    if (!hip_graph || !n_out) return fail(MJMPC_E_BADARG, "null argument");
-    size_t n = 0;
-    HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nullptr, &n));
-    std::vector<hipGraphNode_t> nodes(n);
-    if (n) HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nodes.data(), &n));
-    int64_t k = 0;
-    for (size_t i = 0; i < n; ++i) {
-        hipGraphNodeType t;
-        HIP_TRY(hipGraphNodeGetType(nodes[i], &t));
-        k += t == hipGraphNodeTypeKernel;
-    }
-    n_out[0] = k;
-    n_out[1] = (int64_t)n;
-    return 0;
-}
-
-// An order-independent signature of a captured graph: n_out[0] = sum over its KERNEL nodes of a hash of (function, grid,
-// block, dynamic LDS), n_out[1] = the same over every node's type.  (Argument VALUES are out of the runtime's reach - a
-// kernel node's parameter array comes without sizes - but they are the recorded ones by construction; what can differ
-// between an iteration and its tape is which kernels run and in what shape.)
-int mjmpc_graph_signature(void* hip_graph, uint64_t* n_out) {
-    if (!hip_graph || !n_out) return fail(MJMPC_E_BADARG, "null argument");
-    size_t n = 0;
-    HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nullptr, &n));
-    std::vector<hipGraphNode_t> nodes(n);
-    if (n) HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nodes.data(), &n));
-    auto mix = [](uint64_t h, uint64_t v) { return (h ^ v) * 1099511628211ull; };
-    uint64_t ksum = 0, tsum = 0;
-    for (size_t i = 0; i < n; ++i) {
-        hipGraphNodeType t;
-        HIP_TRY(hipGraphNodeGetType(nodes[i], &t));
-        tsum += mix(1469598103934665603ull, (uint64_t)t);
-        if (t != hipGraphNodeTypeKernel) continue;
-        hipKernelNodeParams kp;
-        HIP_TRY(hipGraphKernelNodeGetParams(nodes[i], &kp));
-        uint64_t h = 1469598103934665603ull;
-        h = mix(h, (uint64_t)(uintptr_t)kp.func);
-        h = mix(h, ((uint64_t)kp.gridDim.x << 32) | kp.gridDim.y);
-        h = mix(h, ((uint64_t)kp.gridDim.z << 32) | kp.blockDim.x);
-        h = mix(h, ((uint64_t)kp.blockDim.y << 32) | kp.blockDim.z);
-        h = mix(h, (uint64_t)kp.sharedMemBytes);
-        ksum += h;
-    }
-    n_out[0] = ksum;
-    n_out[1] = tsum;
-    return 0;
-}
-
 static mjmpc::RolloutFusion arm_fuse(const mjmpc_arm_s* h) {
     mjmpc::RolloutFusion f;
     f.reset_rec = h->reset_rec;
@@ -196,7 +260,7 @@ static mjmpc::RolloutFusion arm_fuse(const mjmpc_arm_s* h) {
 // receives the state after it, the next observation's site entries are the site at the reset state.  Synchronous; called
 // when the engine is created and when its model blocks are replaced.
 // The records are returned in *out and the handle is NOT touched: the caller commits them together with the model blocks
-// (mjmpc_arm_set_shard_models), so that a failure here leaves the engine as it was; the launches count into a scratch
+// (core_swap_models), so that a failure here leaves the engine as it was; the launches count into a scratch
 // counter block of their own, not into the engine's live diagnostics.
 static int arm_make_reset_records(mjmpc_arm_s* h, const double* blobs, int n_shards, double** out) {
     const size_t L = (size_t)mjmpc::ARM_BLOB_LEN, R = (size_t)mjmpc::ARM_RESET_LEN;
@@ -239,104 +303,7 @@ static int arm_make_reset_records(mjmpc_arm_s* h, const double* blobs, int n_sha
     return 0;
 }
 
-static int arm_create_impl(mjmpc_arm_s* h, const double* blob, int n_blob) {
-    std::vector<float> f32(blob, blob + n_blob);
-    h->xj = arm_blob_is_xj(blob, 1);
-    HIP_TRY(hipMalloc(&h->model_f32, sizeof(float) * n_blob));
-    HIP_TRY(hipMalloc(&h->model_f64, sizeof(double) * n_blob));
-    HIP_TRY(hipMalloc(&h->state, sizeof(double) * MJMPC_ARM_STATE_LEN));
-    HIP_TRY(hipMalloc(&h->diag, MJMPC_DIAG_BYTES));
-    HIP_TRY(hipHostMalloc(&h->pinned, sizeof(double) * MJMPC_ARM_STATE_LEN * 4));
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreateWithFlags(&h->staged[k], hipEventDisableTiming));
-    HIP_TRY(hipMemcpy(h->model_f32, f32.data(), sizeof(float) * n_blob, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->model_f64, blob, sizeof(double) * n_blob, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->state, 0, sizeof(double) * MJMPC_ARM_STATE_LEN));
-    HIP_TRY(hipMemset(h->diag, 0, MJMPC_DIAG_BYTES));
-    return arm_make_reset_records(h, blob, 1, &h->reset_rec);
-}
-
-int mjmpc_arm_create(const double* blob, int n_blob, int device, mjmpc_arm_t* out) {
-    if (!blob || !out) return fail(MJMPC_E_BADARG, "null argument");
-    if (n_blob != mjmpc::ARM_BLOB_LEN) return fail(MJMPC_E_BADMODEL, "model blob has %d scalars, expected %d", n_blob, (int)mjmpc::ARM_BLOB_LEN);
-    const int nv = (int)blob[mjmpc::O_NV];
-    if (nv < 1 || nv > mjmpc::MAX_LINKS) return fail(MJMPC_E_BADMODEL, "nv = %d outside 1..%d", nv, mjmpc::MAX_LINKS);
-    if (mjmpc_device_count() <= device) return fail(MJMPC_E_NOGPU, "HIP device %d not present", device);
-    HIP_TRY(hipSetDevice(device));
-    mjmpc_arm_s* h = new mjmpc_arm_s();
-    h->device = device;
-    h->nv = nv;
-    h->nu = (int)blob[mjmpc::O_NU] >= 1 && (int)blob[mjmpc::O_NU] <= nv ? (int)blob[mjmpc::O_NU] : nv;
-    h->d_obs = 2 * nv + 6;
-    if (int rc = arm_create_impl(h, blob, n_blob)) {        // a failed allocation leaves nothing behind
-        mjmpc_arm_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return 0;
-}
-
-int mjmpc_arm_set_shard_models(mjmpc_arm_t h, const double* blobs, int n_shards) {
-    if (!h || !blobs || n_shards < 1) return fail(MJMPC_E_BADARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    const size_t n = (size_t)n_shards * mjmpc::ARM_BLOB_LEN;
-    for (int s = 0; s < n_shards; ++s)
-        if ((int)blobs[(size_t)s * mjmpc::ARM_BLOB_LEN + mjmpc::O_NV] != h->nv)
-            return fail(MJMPC_E_BADMODEL, "shard %d has a different nv", s);
-    std::vector<float> f32(blobs, blobs + n);
-    HIP_TRY(hipDeviceSynchronize());
-    float* m32 = nullptr;
-    double* m64 = nullptr;
-    HIP_TRY(hipMalloc(&m32, sizeof(float) * n));
-    if (hipError_t e = hipMalloc(&m64, sizeof(double) * n); e != hipSuccess) {
-        hipFree(m32);
-        return hip_fail(e, "hipMalloc");
-    }
-    hipError_t e = hipMemcpy(m32, f32.data(), sizeof(float) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m64, blobs, sizeof(double) * n, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(m32);
-        hipFree(m64);
-        return hip_fail(e, "hipMemcpy");
-    }
-    // the reset records of the NEW blocks first: if that fails the engine keeps its old models, shard count and records
-    double* rec = nullptr;
-    const bool xj_old = h->xj;
-    h->xj = arm_blob_is_xj(blobs, n_shards);        // (the record launches run the build the NEW blocks need)
-    if (int rc = arm_make_reset_records(h, blobs, n_shards, &rec); rc != 0) {
-        h->xj = xj_old;
-        hipFree(m32);
-        hipFree(m64);
-        return rc;
-    }
-    hipFree(h->model_f32);
-    hipFree(h->model_f64);
-    h->model_f32 = m32;
-    h->model_f64 = m64;
-    h->n_shards = n_shards;
-    if (h->reset_rec) h->reset_retired.push_back(h->reset_rec);     // (launchers bound earlier still point at it)
-    h->reset_rec = rec;
-    return 0;
-}
-
-int mjmpc_arm_set_shard_states(mjmpc_arm_t h, const double* states, int n_shards, void* stream) {
-    if (!h || (n_shards > 0 && !states) || n_shards < 0) return fail(MJMPC_E_BADARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (n_shards != h->n_state_shards) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(h->shard_states);
-        h->shard_states = nullptr;
-        if (n_shards > 0) HIP_TRY(hipMalloc(&h->shard_states, sizeof(double) * MJMPC_ARM_STATE_LEN * n_shards));
-        h->n_state_shards = n_shards;
-    }
-    if (n_shards > 0) {
-        HIP_TRY(hipMemcpyAsync(h->shard_states, states, sizeof(double) * MJMPC_ARM_STATE_LEN * n_shards,
-                               hipMemcpyHostToDevice, (hipStream_t)stream));
-        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));      // `states` is pageable host memory
-    }
-    return 0;
-}
-
-static int shard_fusion(mjmpc_arm_t h, int64_t P, mjmpc::RolloutFusion& fuse) {
+static int shard_fusion(const mjmpc_arm_s* h, int64_t P, mjmpc::RolloutFusion& fuse) {
     if (h->n_state_shards > 1) {
         if (P % h->n_state_shards != 0 || (P / h->n_state_shards) % mjmpc::LANES != 0)
             return fail(MJMPC_E_BADARG, "with per-shard start states P / n_shards must be a multiple of 8");
@@ -350,350 +317,48 @@ static int shard_fusion(mjmpc_arm_t h, int64_t P, mjmpc::RolloutFusion& fuse) {
     return 0;
 }
 
-int mjmpc_arm_destroy(mjmpc_arm_t h) {
-    if (!h) return 0;
-    hipSetDevice(h->device);
-    hipFree(h->model_f32);
-    hipFree(h->model_f64);
-    hipFree(h->state);
-    hipFree(h->diag);
-    hipFree(h->shard_states);
-    hipFree(h->reset_rec);
-    for (double* p : h->reset_retired) hipFree(p);
-    hipFree(h->mono_tree);
-    for (double* p : h->mono_retired) hipFree(p);
-    hipHostFree(h->pinned);
-    for (int k = 0; k < 4; ++k) if (h->staged[k]) hipEventDestroy(h->staged[k]);
-    delete h;
-    return 0;
-}
-
-int mjmpc_arm_dims(mjmpc_arm_t h, int* nv, int* nu, int* d_obs) {
-    if (!h) return fail(MJMPC_E_BADARG, "null engine");
-    if (nv) *nv = h->nv;
-    if (nu) *nu = h->nu;
-    if (d_obs) *d_obs = h->d_obs;
-    return 0;
-}
-
-int mjmpc_arm_set_state(mjmpc_arm_t h, const double* qpos, const double* qvel, const double* target_pos,
-                        void* stream) {
-    if (!h || !qpos || !qvel || !target_pos) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(h->device));
-    // Staging ring: wait only for the copy that last used THIS slot (four calls ago), never for the stream - a
-    // captured control iteration still running on `s` keeps running while the next state is being staged.
-    const int slot = h->stage_next;
-    h->stage_next = (slot + 1) & 3;
-    HIP_TRY(hipEventSynchronize(h->staged[slot]));
-    double* stage = h->pinned + (size_t)slot * MJMPC_ARM_STATE_LEN;
-    std::memset(stage, 0, sizeof(double) * MJMPC_ARM_STATE_LEN);
-    std::memcpy(stage, qpos, sizeof(double) * h->nv);
-    std::memcpy(stage + mjmpc::LANES, qvel, sizeof(double) * h->nv);
-    std::memcpy(stage + 2 * mjmpc::LANES, target_pos, sizeof(double) * 3);
-    HIP_TRY(hipMemcpyAsync(h->state, stage, sizeof(double) * MJMPC_ARM_STATE_LEN, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(h->staged[slot], s));
-    return 0;
-}
-
-double* mjmpc_arm_state_ptr(mjmpc_arm_t h) { return h ? h->state : nullptr; }
-
-int mjmpc_arm_rollout(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, const void* d_noise,
-                      void* d_costs, void* d_actions, void* d_obs, void* d_next_obs, void* stream) {
-    if (!h || !d_mean || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+// what mjmpc_arm_rollout / _rollout_cl / _rollout_fused do between their null checks and their launch: the sizes, the device,
+// the engine's fusion with its shard arithmetic, and the start state(s) the launch reads
+static int arm_rollout_begin(const mjmpc_arm_s* h, int64_t P, int H, mjmpc::RolloutFusion* fuse, const double** st) {
     if (P < 0 || H < 0) return fail(MJMPC_E_BADARG, "negative size");
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    mjmpc::RolloutFusion fuse = arm_fuse(h);
-    if (int rc = shard_fusion(h, P, fuse)) return rc;
-    const double* st = fuse.state_shard_size > 0 ? h->shard_states : h->state;
-    if (dtype == MJMPC_F32) {
-        e = arm_rollout_launch<float>(h, h->model_f32, st, (long)P, H, h->nu, d_mean, (const float*)d_noise,
-                                             (float*)d_costs, (float*)d_actions, (float*)d_obs, (float*)d_next_obs,
-                                             nullptr, h->diag, s, fuse);
-    } else if (dtype == MJMPC_F64) {
-        e = arm_rollout_launch<double>(h, h->model_f64, st, (long)P, H, h->nu, d_mean,
-                                              (const double*)d_noise, (double*)d_costs, (double*)d_actions,
-                                              (double*)d_obs, (double*)d_next_obs, nullptr, h->diag, s, fuse);
-    } else {
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    }
-    if (e != hipSuccess) return hip_fail(e, "arm_rollout launch");
+    *fuse = arm_fuse(h);
+    if (int rc = shard_fusion(h, P, *fuse)) return rc;
+    *st = fuse->state_shard_size > 0 ? h->shard_states : h->state;
     return 0;
 }
 
-int mjmpc_arm_rollout_cl(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_weights, const void* d_noise,
-                         void* d_costs, void* d_actions, void* d_obs, void* d_next_obs, void* stream) {
-    if (!h || !d_weights || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
-    if (P < 0 || H < 0) return fail(MJMPC_E_BADARG, "negative size");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    mjmpc::RolloutFusion fuse = arm_fuse(h);
-    if (int rc = shard_fusion(h, P, fuse)) return rc;
-    const double* st = fuse.state_shard_size > 0 ? h->shard_states : h->state;
-    fuse.clw = d_weights;
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = arm_rollout_launch<float>(h, h->model_f32, st, (long)P, H, h->nu, d_weights, (const float*)d_noise,
-                                             (float*)d_costs, (float*)d_actions, (float*)d_obs, (float*)d_next_obs,
-                                             nullptr, h->diag, s, fuse);
-    else if (dtype == MJMPC_F64)
-        e = arm_rollout_launch<double>(h, h->model_f64, st, (long)P, H, h->nu, d_weights,
-                                              (const double*)d_noise, (double*)d_costs, (double*)d_actions,
-                                              (double*)d_obs, (double*)d_next_obs, nullptr, h->diag, s, fuse);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "arm_rollout_cl launch");
+// room for the records of a fused iteration / a sampled rollout at (P, H): grow only, never under a capture (an allocation
+// would invalidate it), and never free what an earlier graph may still point at
+static int arm_grow_mono(mjmpc_arm_s* h, size_t need, hipStream_t s) {
+    if (need <= h->mono_cap) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
+        return fail(MJMPC_E_BADARG, "the record buffer must grow for this (P, H): call once outside stream capture first");
+    double* bigger = nullptr;
+    HIP_TRY(hipMalloc(&bigger, sizeof(double) * need));
+    if (h->mono_tree) h->mono_retired.push_back(h->mono_tree);
+    h->mono_tree = bigger;
+    h->mono_cap = need;
     return 0;
 }
 
-int mjmpc_arm_rollout_fused(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, const void* d_noise,
-                            const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
-                            double* d_q0, void* stream) {
-    if (!h || !d_mean || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
-    if ((d_q0 != nullptr) != (d_gseq != nullptr)) return fail(MJMPC_E_BADARG, "d_q0 and d_gseq go together");
-    if (P < 0 || H < 0) return fail(MJMPC_E_BADARG, "negative size");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    mjmpc::RolloutFusion fuse = arm_fuse(h);
-    if (int rc = shard_fusion(h, P, fuse)) return rc;
-    const double* st = fuse.state_shard_size > 0 ? h->shard_states : h->state;
-    fuse.filt = d_filter_coeffs;
-    fuse.gseq = d_gseq;
-    fuse.q0_out = d_q0;
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = arm_rollout_launch<float>(h, h->model_f32, st, (long)P, H, h->nu, d_mean, (const float*)d_noise,
-                                             (float*)d_costs, (float*)d_actions, nullptr, nullptr, nullptr, h->diag, s,
-                                             fuse);
-    else if (dtype == MJMPC_F64)
-        e = arm_rollout_launch<double>(h, h->model_f64, st, (long)P, H, h->nu, d_mean,
-                                              (const double*)d_noise, (double*)d_costs, (double*)d_actions, nullptr,
-                                              nullptr, nullptr, h->diag, s, fuse);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "arm_rollout_fused launch");
-    return 0;
-}
-
-int mjmpc_arm_mppi_step(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, double* d_mean_out,
-                        const double* d_gseq, const double* d_filter_coeffs, const double* d_chol, uint64_t seed,
-                        uint64_t offset, int64_t particle_offset, int64_t* d_step_counter, double lam, double step_size,
-                        int shift_mode, double* d_action_out, double* h_action_slots, double* d_record, int env_step,
-                        void* d_step_cost, void* d_step_next_obs, void* d_costs, void* d_actions, double* d_q0, void* stream) {
-    if (!h || !d_mean || !d_gseq || !d_chol) return fail(MJMPC_E_BADARG, "null argument");
-    if (!d_record && shift_mode != -2 && (!d_mean_out || d_mean_out == d_mean))
-        return fail(MJMPC_E_BADARG, "d_mean_out must be a buffer of its own (the finish launch reads d_mean while it writes)");
-    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "P and H must be positive");
-    if (!(lam > 0) || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad lam / shift_mode");
-    const bool rollout_only = shift_mode == -2;         // (measurement: the first launch alone, records left in the engine)
-    if (h->n_shards > 1 || h->n_state_shards > 1)
-        return fail(MJMPC_E_BADARG, "the fused iteration runs one model and one start state (no per-shard blocks)");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const long groups = mjmpc::arm_rollout_groups((long)P);
-    const size_t need = (size_t)mjmpc::mono_record_doubles(groups, H, h->nu);
-    if (need > h->mono_cap) {
-        // grow only, never under a capture (an allocation would invalidate it), and never free what an earlier graph
-        // may still point at
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return fail(MJMPC_E_BADARG, "the record buffer must grow for this (P, H): call once outside stream capture first");
-        double* bigger = nullptr;
-        HIP_TRY(hipMalloc(&bigger, sizeof(double) * need));
-        if (h->mono_tree) h->mono_retired.push_back(h->mono_tree);
-        h->mono_tree = bigger;
-        h->mono_cap = need;
-    }
-    mjmpc::MonoStep mo;             // (travels to both kernels by value, as a kernel argument)
-    mo.chol = d_chol;
-    mo.seed = seed;
-    mo.offset = offset;
-    mo.particle_offset = (long)particle_offset;
-    mo.d_step = (const long long*)d_step_counter;
-    mo.lam = lam;
-    mo.step_size = step_size;
-    mo.shift_mode = shift_mode;
-    mo.tree = h->mono_tree;
-    mo.action_out = d_action_out;
-    mo.action_host = h_action_slots;
-    mo.step_counter = (long long*)d_step_counter;
-    mo.record = d_record;
-    mo.state_io = h->state;
-    mo.step_cost = d_step_cost;
-    mo.step_nobs = d_step_next_obs;
-    mo.reset_rec = h->reset_rec;
-    const int do_env = (env_step && !d_record) ? 1 : 0;
-    mjmpc::RolloutFusion fuse = arm_fuse(h);
-    fuse.filt = d_filter_coeffs;
-    fuse.gseq = d_gseq;
-    fuse.q0_out = d_q0;
-    hipError_t e;
-    if (dtype == MJMPC_F32) {
-        e = arm_rollout_launch<float>(h, h->model_f32, h->state, (long)P, H, h->nu, d_mean, nullptr, (float*)d_costs,
-                                             (float*)d_actions, nullptr, nullptr, nullptr, h->diag, s, fuse, &mo);
-        if (e == hipSuccess && !rollout_only)
-            e = arm_finish_launch<float>(h, h->model_f32, h->mono_tree, groups, H, h->nu, d_mean, d_mean_out, mo,
-                                                     do_env, h->diag, s);
-    } else if (dtype == MJMPC_F64) {
-        e = arm_rollout_launch<double>(h, h->model_f64, h->state, (long)P, H, h->nu, d_mean, nullptr, (double*)d_costs,
-                                              (double*)d_actions, nullptr, nullptr, nullptr, h->diag, s, fuse, &mo);
-        if (e == hipSuccess && !rollout_only)
-            e = arm_finish_launch<double>(h, h->model_f64, h->mono_tree, groups, H, h->nu, d_mean, d_mean_out, mo,
-                                                      do_env, h->diag, s);
-    } else {
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    }
-    if (e != hipSuccess) return hip_fail(e, "arm_mppi_step launch");
-    return 0;
-}
-
-int mjmpc_arm_rollout_sampled(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, const double* d_gseq,
-                              const double* d_filter_coeffs, const double* d_chol, int chol_full, uint64_t seed, uint64_t offset,
-                              int64_t particle_offset, const int64_t* d_step_counter, void* d_costs, void* d_actions,
-                              double* d_q0, void* stream) {
-    if (!h || !d_mean || !d_gseq || !d_chol) return fail(MJMPC_E_BADARG, "null argument");
-    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "P and H must be positive");
-    if (h->n_shards > 1 || h->n_state_shards > 1)
-        return fail(MJMPC_E_BADARG, "sampled rollouts run one model and one start state (no per-shard blocks)");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    const long groups = mjmpc::arm_rollout_groups((long)P);
-    const size_t need = (size_t)mjmpc::mono_record_doubles(groups, H, h->nu);      // (the launch also leaves its softmax partials)
-    if (need > h->mono_cap) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return fail(MJMPC_E_BADARG, "the record buffer must grow for this (P, H): call once outside stream capture first");
-        double* bigger = nullptr;
-        HIP_TRY(hipMalloc(&bigger, sizeof(double) * need));
-        if (h->mono_tree) h->mono_retired.push_back(h->mono_tree);
-        h->mono_tree = bigger;
-        h->mono_cap = need;
-    }
-    mjmpc::MonoStep mo;
-    mo.chol = d_chol;
-    mo.chol_full = chol_full ? 1 : 0;
-    mo.seed = seed;
-    mo.offset = offset;
-    mo.particle_offset = (long)particle_offset;
-    mo.d_step = (const long long*)d_step_counter;
-    mo.lam = 1.0;
-    mo.shift_mode = -2;
-    mo.tree = h->mono_tree;
-    mjmpc::RolloutFusion fuse = arm_fuse(h);
-    fuse.filt = d_filter_coeffs;
-    fuse.gseq = d_gseq;
-    fuse.q0_out = d_q0;
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = arm_rollout_launch<float>(h, h->model_f32, h->state, (long)P, H, h->nu, d_mean, nullptr, (float*)d_costs,
-                                             (float*)d_actions, nullptr, nullptr, nullptr, h->diag, s, fuse, &mo);
-    else if (dtype == MJMPC_F64)
-        e = arm_rollout_launch<double>(h, h->model_f64, h->state, (long)P, H, h->nu, d_mean, nullptr, (double*)d_costs,
-                                              (double*)d_actions, nullptr, nullptr, nullptr, h->diag, s, fuse, &mo);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "arm_rollout_sampled launch");
-    return 0;
-}
-
-int mjmpc_arm_mppi_combine(mjmpc_arm_t h, int dtype, const double* d_records, int n_records, int H, const double* d_mean,
-                           double* d_mean_out, int64_t* d_step_counter, double step_size, int shift_mode,
-                           double* d_action_out, double* h_action_slots, int env_step, void* d_step_cost,
-                           void* d_step_next_obs, void* stream) {
-    if (!h || !d_records || !d_mean || !d_mean_out || d_mean_out == d_mean) return fail(MJMPC_E_BADARG, "null / aliased argument");
-    if (n_records < 1 || H < 1 || shift_mode > 1 || shift_mode < -1) return fail(MJMPC_E_BADARG, "bad n_records / H / shift_mode");
-    if (env_step && (h->n_shards > 1 || h->n_state_shards > 1))
-        return fail(MJMPC_E_BADARG, "the fused env step runs one model and one state (no per-shard blocks)");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    mjmpc::MonoStep mo;
-    mo.step_size = step_size;
-    mo.shift_mode = shift_mode;
-    mo.action_out = d_action_out;
-    mo.action_host = h_action_slots;
-    mo.step_counter = (long long*)d_step_counter;
-    mo.state_io = h->state;
-    mo.step_cost = d_step_cost;
-    mo.step_nobs = d_step_next_obs;
-    mo.reset_rec = h->reset_rec;
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = arm_finish_launch<float>(h, h->model_f32, d_records, n_records, H, h->nu, d_mean, d_mean_out, mo,
-                                                 env_step ? 1 : 0, h->diag, s);
-    else if (dtype == MJMPC_F64)
-        e = arm_finish_launch<double>(h, h->model_f64, d_records, n_records, H, h->nu, d_mean, d_mean_out, mo,
-                                                  env_step ? 1 : 0, h->diag, s);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "arm_mppi_combine launch");
-    return 0;
-}
-
-int mjmpc_arm_step_state(mjmpc_arm_t h, int dtype, const double* d_action, void* d_cost, void* d_next_obs,
-                         void* stream) {
-    if (!h || !d_action || !d_cost) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = arm_rollout_launch<float>(h, h->model_f32, h->state, 1, 1, h->nu, d_action, nullptr, (float*)d_cost,
-                                             nullptr, nullptr, (float*)d_next_obs, h->state, h->diag, s, arm_fuse(h));
-    else if (dtype == MJMPC_F64)
-        e = arm_rollout_launch<double>(h, h->model_f64, h->state, 1, 1, h->nu, d_action, nullptr, (double*)d_cost,
-                                              nullptr, nullptr, (double*)d_next_obs, h->state, h->diag, s, arm_fuse(h));
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "arm_step_state launch");
-    return 0;
-}
-
-int mjmpc_arm_solver_failures(mjmpc_arm_t h, uint32_t* count) {
-    if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned c = 0;
-    HIP_TRY(hipMemcpy(&c, h->diag, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *count = c;
-    return 0;
-}
-
-int mjmpc_arm_diverged(mjmpc_arm_t h, uint32_t* count) {
-    if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned c = 0;
-    HIP_TRY(hipMemcpy(&c, h->diag + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *count = c;
-    return 0;
-}
-
-#ifdef MJMPC_STAMPS
-// developer builds only (not declared in include/mjmpc_amd.h): read and clear the phase clocks
-extern "C" int mjmpc_debug_stamps(mjmpc_arm_t h, unsigned long long* out32) {
-    if (!h || !out32) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out32, (char*)h->diag + 16, 8 * 64, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset((char*)h->diag + 16, 0, 8 * 64));
-    return 0;
-}
-#endif
-
-/* ---- tree engine ------------------------------------------------------------------------------------ */
+/* ---- tree engine: what it adds to the core ----------------------------------------------------------------------------- */
 static_assert(MJMPC_TREE_BLOB_LEN == mjmpc::TREE_BLOB_LEN && MJMPC_TREE_DEVICE_STATE_LEN == mjmpc::TREE_STATE_LEN &&
               MJMPC_TREE_STATE_LEN == mjmpc::TREE_PUBLIC_STATE_LEN, "include/mjmpc_amd.h and csrc/tree_model.h disagree");
 #define MJMPC_TREE_DIAG_BYTES (8 + 8 * mjmpc::TREE_STAT_SLOTS + 8)  /* counters, the developer clocks of -DTREE_STATS builds, the real env's resets (TREE_DIAG_ENV_RESETS) */
-#ifdef TREE_STATS
-// developer builds only (not declared in include/mjmpc_amd.h): read and clear the phase clocks / iteration counts
-extern "C" int mjmpc_debug_tree_stats(mjmpc_tree_t h, unsigned long long* out48) {
-    if (!h || !out48) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out48, (char*)h->diag + 8, 8 * mjmpc::TREE_STAT_SLOTS, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemset((char*)h->diag + 8, 0, 8 * mjmpc::TREE_STAT_SLOTS));
-    return 0;
-}
-#endif
+
+struct mjmpc_tree_s : engine_core {
+    int max_path = 0, nq = 0;
+    bool full = false;              // slide joints, springs, friction cones, > 8 contact points or a medium: the full kernel
+    int gen = 0;                    // T_GEN: 1 ball / free joints, friction loss, boxes, equalities, tendon limits (the general
+                                    // instantiation), 2 round 5's record kinds on top (instantiations of their own)
+    std::vector<double> topo;       // create-time topology tables (shard blocks must match them)
+    int integrator = MJMPC_INTEGRATOR_EULER;    // mjmpc_tree_create_ex: every launch (the reset records' too) steps with it
+    double* zero_action = nullptr;  // [32] zeros (the kinematics-only launch of mjmpc_tree_rollout_cl)
+    double* scratch = nullptr;      // [8] a place for that launch's cost
+};
+
 // MuJoCo's layout (qpos[nq], qvel[nv], target[3]) -> the device state vector: one coordinate per LINK, a ball joint's
 // quaternion as x, y, z in its three links' entries and w in its first link's w entry, a free joint's translations relative
 // to the body position (the links are slides from there)
@@ -767,6 +432,50 @@ static mjmpc::TreeFusion tree_fuse(const mjmpc_tree_s* h, int shard = -1) {
     return f;
 }
 
+// One launch of the tree kernel, by name: a call site says what is special about it, tree_launch adds what the handle knows
+// (max_path, full, nv, nu, gen, integrator, diag).  Made for the engine's model blocks - all of them (shard < 0) or one
+// (shard >= 0) - with the fusion every launch on them carries (tree_fuse).
+struct TreeCall {
+    size_t model_offset = 0;        // scalars from the start of model_f32 / model_f64
+    int n_model_shards = 1;
+    const double* state = nullptr;
+    long P = 1;
+    int H = 1;
+    const double* mean = nullptr;
+    const void* noise = nullptr;    // noise, cost, act, obs, nobs: of the launch's precision
+    void* cost = nullptr;
+    void* act = nullptr;
+    void* obs = nullptr;
+    void* nobs = nullptr;
+    double* state_out = nullptr;
+    const double* clw = nullptr;
+    double* site_out = nullptr;
+    int n_state_shards = 1;
+    mjmpc::TreeFusion fuse;
+    // a launch on blocks that are not (yet) the engine's (tree_make_reset_records): their device copy, of the launch's
+    // precision, their kernel choice and a counter block of their own
+    const void* other_model = nullptr;
+    bool other_full = false;
+    unsigned* other_diag = nullptr;
+
+    TreeCall() = default;
+    explicit TreeCall(const mjmpc_tree_s* h, int shard = -1)
+        : model_offset(shard > 0 && h->n_shards > 1 ? (size_t)shard * mjmpc::TREE_BLOB_LEN : 0),
+          n_model_shards(shard < 0 ? h->n_shards : 1), fuse(tree_fuse(h, shard)) {}
+};
+
+template <typename T>
+static hipError_t tree_launch(const mjmpc_tree_s* h, const TreeCall& c, hipStream_t s) {
+    const T* m = c.other_model ? (const T*)c.other_model : model<T>(h) + c.model_offset;
+    return mjmpc::launch_tree_rollout<T>(m, c.n_model_shards, h->max_path, c.other_model ? c.other_full : h->full, h->nv, c.state,
+                                         c.P, c.H, h->nu, c.mean, (const T*)c.noise, (T*)c.cost, (T*)c.act, (T*)c.obs,
+                                         (T*)c.nobs, c.other_model ? c.other_diag : h->diag, s, c.state_out, c.clw, c.site_out,
+                                         c.n_state_shards, h->gen, c.fuse, h->integrator);
+}
+static int tree_issue(const mjmpc_tree_s* h, int dtype, const TreeCall& c, hipStream_t s, const char* what) {
+    return with_dtype(dtype, what, [&](auto tag) { return tree_launch<decltype(tag)>(h, c, s); });
+}
+
 // The reset records of `n_shards` model blocks (host, TREE_BLOB_LEN each): per block ONE substep of the f64 kernel itself
 // from the reset state (qpos0 = the device's zero coordinates and identity quaternions, zero velocity, zero controls) on a
 // copy of the block with frame_skip 1 - state_out receives the state after it, site_out / axis_out the site and the object
@@ -792,11 +501,17 @@ static int tree_make_reset_records(mjmpc_tree_s* h, const double* blobs, int n_s
         e = hipMemcpy(tmp, b.data(), sizeof(double) * L, hipMemcpyHostToDevice);
         if (e != hipSuccess) break;
         double* rk = rec + (size_t)k * R;
-        mjmpc::TreeFusion f;
-        f.axis_out = rk + mjmpc::TREE_STATE_LEN + 3;
-        e = mjmpc::launch_tree_rollout<double>(tmp, 1, h->max_path, full, h->nv, st, 1, 1, h->nu, h->zero_action, nullptr,
-                                               (double*)h->scratch, nullptr, nullptr, nullptr, sdiag, nullptr, rk, nullptr,
-                                               rk + mjmpc::TREE_STATE_LEN, 1, h->gen, f, h->integrator);
+        TreeCall c;                 // (one particle, one step, zero controls; no reset record: this launch makes it)
+        c.other_model = tmp;
+        c.other_full = full;
+        c.other_diag = sdiag;
+        c.state = st;
+        c.mean = h->zero_action;
+        c.cost = h->scratch;
+        c.state_out = rk;
+        c.site_out = rk + mjmpc::TREE_STATE_LEN;
+        c.fuse.axis_out = rk + mjmpc::TREE_STATE_LEN + 3;
+        e = tree_launch<double>(h, c, nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
     }
     hipFree(tmp);
@@ -810,26 +525,372 @@ static int tree_make_reset_records(mjmpc_tree_s* h, const double* blobs, int n_s
     return 0;
 }
 
-static int tree_create_impl(mjmpc_tree_s* h, const double* blob, int n_blob) {
-    std::vector<float> f32(blob, blob + n_blob);
-    HIP_TRY(hipMalloc(&h->model_f32, sizeof(float) * n_blob));
-    HIP_TRY(hipMalloc(&h->model_f64, sizeof(double) * n_blob));
-    HIP_TRY(hipMalloc(&h->state, sizeof(double) * MJMPC_TREE_DEVICE_STATE_LEN));
-    HIP_TRY(hipMalloc(&h->diag, MJMPC_TREE_DIAG_BYTES));
-    HIP_TRY(hipMemcpy(h->model_f32, f32.data(), sizeof(float) * n_blob, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(h->model_f64, blob, sizeof(double) * n_blob, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(h->state, 0, sizeof(double) * MJMPC_TREE_DEVICE_STATE_LEN));
-    HIP_TRY(hipMemset(h->diag, 0, MJMPC_TREE_DIAG_BYTES));
-    HIP_TRY(hipMalloc(&h->zero_action, sizeof(double) * 40));
-    HIP_TRY(hipMemset(h->zero_action, 0, sizeof(double) * 40));
-    h->scratch = h->zero_action + 32;
-    HIP_TRY(hipHostMalloc(&h->pinned, sizeof(double) * MJMPC_TREE_DEVICE_STATE_LEN * 4));
-    for (int k = 0; k < 4; ++k) HIP_TRY(hipEventCreateWithFlags(&h->staged[k], hipEventDisableTiming));
-    return tree_make_reset_records(h, blob, 1, h->full, &h->reset_rec);
+// what mjmpc_tree_rollout / _rollout_cl / _rollout_fused do between their null checks and their launch: the sizes, the shard
+// arithmetic, the device, and the call on all model blocks from the start state(s)
+static int tree_rollout_begin(const mjmpc_tree_s* h, int64_t P, int H, TreeCall* c) {
+    if (P < 0 || H < 0) return fail(MJMPC_E_BADARG, "negative size");
+    const int nss = h->n_state_shards > 1 ? h->n_state_shards : 1;
+    if (P % h->n_shards != 0 || P % nss != 0)
+        return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d shards", (long long)P, std::max(h->n_shards, nss));
+    HIP_TRY(hipSetDevice(h->device));
+    *c = TreeCall(h);
+    c->state = nss > 1 ? h->shard_states : h->state;
+    c->n_state_shards = nss;
+    c->P = (long)P;
+    c->H = H;
+    return 0;
 }
+
+// what every batch entry point asks of the engine: one model block, 1 .. 65535 state shards (grid rows), and - given a
+// particle count - the same number of particles per shard
+static int tree_batch_shape(const mjmpc_tree_s* h, int64_t P_total, int* E) {
+    if (!h) return fail(MJMPC_E_BADARG, "null engine");
+    if (h->n_shards > 1) return fail(MJMPC_E_BADARG, "an episode batch runs one model block; the engine has %d", h->n_shards);
+    const int e = h->n_state_shards;
+    if (e < 1 || e > 65535)
+        return fail(MJMPC_E_BADARG, "an episode batch needs 1 .. 65535 state shards (mjmpc_tree_set_shard_states); the engine has %d", e);
+    if (P_total < 1 || P_total % e != 0)
+        return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d episodes", (long long)P_total, e);
+    *E = e;
+    return 0;
+}
+
+extern "C" {
+
+int mjmpc_abi_version(void) { return MJMPC_ABI_VERSION; }
+
+const char* mjmpc_last_error(void) { return g_err; }
+
+int mjmpc_device_count(void) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+int mjmpc_graph_kernel_nodes(void* hip_graph, int64_t* n_out) {
+    if (!hip_graph || !n_out) return fail(MJMPC_E_BADARG, "null argument");
+    size_t n = 0;
+    HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nullptr, &n));
+    std::vector<hipGraphNode_t> nodes(n);
+    if (n) HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nodes.data(), &n));
+    int64_t k = 0;
+    for (size_t i = 0; i < n; ++i) {
+        hipGraphNodeType t;
+        HIP_TRY(hipGraphNodeGetType(nodes[i], &t));
+        k += t == hipGraphNodeTypeKernel;
+    }
+    n_out[0] = k;
+    n_out[1] = (int64_t)n;
+    return 0;
+}
+
+// An order-independent signature of a captured graph: n_out[0] = sum over its KERNEL nodes of a hash of (function, grid,
+// block, dynamic LDS), n_out[1] = the same over every node's type.  (Argument VALUES are out of the runtime's reach - a
+// kernel node's parameter array comes without sizes - but they are the recorded ones by construction; what can differ
+// between an iteration and its tape is which kernels run and in what shape.)
+int mjmpc_graph_signature(void* hip_graph, uint64_t* n_out) {
+    if (!hip_graph || !n_out) return fail(MJMPC_E_BADARG, "null argument");
+    size_t n = 0;
+    HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nullptr, &n));
+    std::vector<hipGraphNode_t> nodes(n);
+    if (n) HIP_TRY(hipGraphGetNodes((hipGraph_t)hip_graph, nodes.data(), &n));
+    auto mix = [](uint64_t h, uint64_t v) { return (h ^ v) * 1099511628211ull; };
+    uint64_t ksum = 0, tsum = 0;
+    for (size_t i = 0; i < n; ++i) {
+        hipGraphNodeType t;
+        HIP_TRY(hipGraphNodeGetType(nodes[i], &t));
+        tsum += mix(1469598103934665603ull, (uint64_t)t);
+        if (t != hipGraphNodeTypeKernel) continue;
+        hipKernelNodeParams kp;
+        HIP_TRY(hipGraphKernelNodeGetParams(nodes[i], &kp));
+        uint64_t h = 1469598103934665603ull;
+        h = mix(h, (uint64_t)(uintptr_t)kp.func);
+        h = mix(h, ((uint64_t)kp.gridDim.x << 32) | kp.gridDim.y);
+        h = mix(h, ((uint64_t)kp.gridDim.z << 32) | kp.blockDim.x);
+        h = mix(h, ((uint64_t)kp.blockDim.y << 32) | kp.blockDim.z);
+        h = mix(h, (uint64_t)kp.sharedMemBytes);
+        ksum += h;
+    }
+    n_out[0] = ksum;
+    n_out[1] = tsum;
+    return 0;
+}
+
+/* ---- arm engine ------------------------------------------------------------------------------------- */
+int mjmpc_arm_create(const double* blob, int n_blob, int device, mjmpc_arm_t* out) {
+    if (!blob || !out) return fail(MJMPC_E_BADARG, "null argument");
+    if (n_blob != mjmpc::ARM_BLOB_LEN) return fail(MJMPC_E_BADMODEL, "model blob has %d scalars, expected %d", n_blob, (int)mjmpc::ARM_BLOB_LEN);
+    const int nv = (int)blob[mjmpc::O_NV];
+    if (nv < 1 || nv > mjmpc::MAX_LINKS) return fail(MJMPC_E_BADMODEL, "nv = %d outside 1..%d", nv, mjmpc::MAX_LINKS);
+    if (mjmpc_device_count() <= device) return fail(MJMPC_E_NOGPU, "HIP device %d not present", device);
+    HIP_TRY(hipSetDevice(device));
+    mjmpc_arm_s* h = new mjmpc_arm_s();
+    h->device = device;
+    h->nv = nv;
+    h->nu = (int)blob[mjmpc::O_NU] >= 1 && (int)blob[mjmpc::O_NU] <= nv ? (int)blob[mjmpc::O_NU] : nv;
+    h->d_obs = 2 * nv + 6;
+    h->xj = arm_blob_is_xj(blob, 1);
+    int rc = core_create(h, blob, n_blob, MJMPC_ARM_STATE_LEN, MJMPC_DIAG_BYTES);
+    if (rc == 0) rc = arm_make_reset_records(h, blob, 1, &h->reset_rec);
+    if (rc != 0) {          // a failed allocation leaves nothing behind
+        mjmpc_arm_destroy(h);
+        return rc;
+    }
+    *out = h;
+    return 0;
+}
+
+int mjmpc_arm_set_shard_models(mjmpc_arm_t h, const double* blobs, int n_shards) {
+    if (!h || !blobs || n_shards < 1) return fail(MJMPC_E_BADARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    for (int s = 0; s < n_shards; ++s)
+        if ((int)blobs[(size_t)s * mjmpc::ARM_BLOB_LEN + mjmpc::O_NV] != h->nv)
+            return fail(MJMPC_E_BADMODEL, "shard %d has a different nv", s);
+    const bool xj_old = h->xj;
+    const int rc = core_swap_models(h, blobs, n_shards, mjmpc::ARM_BLOB_LEN, [&](double** rec) {
+        h->xj = arm_blob_is_xj(blobs, n_shards);        // (the record launches run the build the NEW blocks need)
+        return arm_make_reset_records(h, blobs, n_shards, rec);
+    });
+    if (rc != 0) h->xj = xj_old;
+    return rc;
+}
+
+int mjmpc_arm_set_shard_states(mjmpc_arm_t h, const double* states, int n_shards, void* stream) {
+    if (!h || (n_shards > 0 && !states) || n_shards < 0) return fail(MJMPC_E_BADARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = core_resize_shard_states(h, n_shards, MJMPC_ARM_STATE_LEN)) return rc;
+    if (n_shards == 0) return 0;
+    return core_upload_shard_states(h, states, (size_t)n_shards * MJMPC_ARM_STATE_LEN, (hipStream_t)stream);
+}
+
+int mjmpc_arm_destroy(mjmpc_arm_t h) {
+    if (!h) return 0;
+    core_free(h);
+    hipFree(h->mono_tree);
+    for (double* p : h->mono_retired) hipFree(p);
+    delete h;
+    return 0;
+}
+
+int mjmpc_arm_dims(mjmpc_arm_t h, int* nv, int* nu, int* d_obs) { return core_dims(h, nv, nu, d_obs); }
+
+int mjmpc_arm_set_state(mjmpc_arm_t h, const double* qpos, const double* qvel, const double* target_pos,
+                        void* stream) {
+    if (!h || !qpos || !qvel || !target_pos) return fail(MJMPC_E_BADARG, "null argument");
+    return core_set_state(h, MJMPC_ARM_STATE_LEN, (hipStream_t)stream, [&](double* stage) {
+        std::memset(stage, 0, sizeof(double) * MJMPC_ARM_STATE_LEN);
+        std::memcpy(stage, qpos, sizeof(double) * h->nv);
+        std::memcpy(stage + mjmpc::LANES, qvel, sizeof(double) * h->nv);
+        std::memcpy(stage + 2 * mjmpc::LANES, target_pos, sizeof(double) * 3);
+    });
+}
+
+double* mjmpc_arm_state_ptr(mjmpc_arm_t h) { return h ? h->state : nullptr; }
+
+int mjmpc_arm_rollout(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, const void* d_noise,
+                      void* d_costs, void* d_actions, void* d_obs, void* d_next_obs, void* stream) {
+    if (!h || !d_mean || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+    mjmpc::RolloutFusion fuse;
+    const double* st = nullptr;
+    if (int rc = arm_rollout_begin(h, P, H, &fuse, &st)) return rc;
+    return with_dtype(dtype, "arm_rollout launch", [&](auto tag) {
+        using T = decltype(tag);
+        return arm_rollout_launch<T>(h, model<T>(h), st, (long)P, H, h->nu, d_mean, (const T*)d_noise, (T*)d_costs, (T*)d_actions,
+                                     (T*)d_obs, (T*)d_next_obs, nullptr, h->diag, (hipStream_t)stream, fuse);
+    });
+}
+
+int mjmpc_arm_rollout_cl(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_weights, const void* d_noise,
+                         void* d_costs, void* d_actions, void* d_obs, void* d_next_obs, void* stream) {
+    if (!h || !d_weights || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+    mjmpc::RolloutFusion fuse;
+    const double* st = nullptr;
+    if (int rc = arm_rollout_begin(h, P, H, &fuse, &st)) return rc;
+    fuse.clw = d_weights;
+    return with_dtype(dtype, "arm_rollout_cl launch", [&](auto tag) {
+        using T = decltype(tag);
+        return arm_rollout_launch<T>(h, model<T>(h), st, (long)P, H, h->nu, d_weights, (const T*)d_noise, (T*)d_costs,
+                                     (T*)d_actions, (T*)d_obs, (T*)d_next_obs, nullptr, h->diag, (hipStream_t)stream, fuse);
+    });
+}
+
+int mjmpc_arm_rollout_fused(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, const void* d_noise,
+                            const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
+                            double* d_q0, void* stream) {
+    if (!h || !d_mean || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+    if ((d_q0 != nullptr) != (d_gseq != nullptr)) return fail(MJMPC_E_BADARG, "d_q0 and d_gseq go together");
+    mjmpc::RolloutFusion fuse;
+    const double* st = nullptr;
+    if (int rc = arm_rollout_begin(h, P, H, &fuse, &st)) return rc;
+    fuse.filt = d_filter_coeffs;
+    fuse.gseq = d_gseq;
+    fuse.q0_out = d_q0;
+    return with_dtype(dtype, "arm_rollout_fused launch", [&](auto tag) {
+        using T = decltype(tag);
+        return arm_rollout_launch<T>(h, model<T>(h), st, (long)P, H, h->nu, d_mean, (const T*)d_noise, (T*)d_costs, (T*)d_actions,
+                                     nullptr, nullptr, nullptr, h->diag, (hipStream_t)stream, fuse);
+    });
+}
+
+int mjmpc_arm_mppi_step(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, double* d_mean_out,
+                        const double* d_gseq, const double* d_filter_coeffs, const double* d_chol, uint64_t seed,
+                        uint64_t offset, int64_t particle_offset, int64_t* d_step_counter, double lam, double step_size,
+                        int shift_mode, double* d_action_out, double* h_action_slots, double* d_record, int env_step,
+                        void* d_step_cost, void* d_step_next_obs, void* d_costs, void* d_actions, double* d_q0, void* stream) {
+    if (!h || !d_mean || !d_gseq || !d_chol) return fail(MJMPC_E_BADARG, "null argument");
+    if (!d_record && shift_mode != -2 && (!d_mean_out || d_mean_out == d_mean))
+        return fail(MJMPC_E_BADARG, "d_mean_out must be a buffer of its own (the finish launch reads d_mean while it writes)");
+    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "P and H must be positive");
+    if (!(lam > 0) || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad lam / shift_mode");
+    const bool rollout_only = shift_mode == -2;         // (measurement: the first launch alone, records left in the engine)
+    if (h->n_shards > 1 || h->n_state_shards > 1)
+        return fail(MJMPC_E_BADARG, "the fused iteration runs one model and one start state (no per-shard blocks)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const long groups = mjmpc::arm_rollout_groups((long)P);
+    if (int rc = arm_grow_mono(h, (size_t)mjmpc::mono_record_doubles(groups, H, h->nu), s)) return rc;
+    mjmpc::MonoStep mo;             // (travels to both kernels by value, as a kernel argument)
+    mo.chol = d_chol;
+    mo.seed = seed;
+    mo.offset = offset;
+    mo.particle_offset = (long)particle_offset;
+    mo.d_step = (const long long*)d_step_counter;
+    mo.lam = lam;
+    mo.step_size = step_size;
+    mo.shift_mode = shift_mode;
+    mo.tree = h->mono_tree;
+    mo.action_out = d_action_out;
+    mo.action_host = h_action_slots;
+    mo.step_counter = (long long*)d_step_counter;
+    mo.record = d_record;
+    mo.state_io = h->state;
+    mo.step_cost = d_step_cost;
+    mo.step_nobs = d_step_next_obs;
+    mo.reset_rec = h->reset_rec;
+    const int do_env = (env_step && !d_record) ? 1 : 0;
+    mjmpc::RolloutFusion fuse = arm_fuse(h);
+    fuse.filt = d_filter_coeffs;
+    fuse.gseq = d_gseq;
+    fuse.q0_out = d_q0;
+    return with_dtype(dtype, "arm_mppi_step launch", [&](auto tag) {
+        using T = decltype(tag);
+        hipError_t e = arm_rollout_launch<T>(h, model<T>(h), h->state, (long)P, H, h->nu, d_mean, nullptr, (T*)d_costs,
+                                             (T*)d_actions, nullptr, nullptr, nullptr, h->diag, s, fuse, &mo);
+        if (e == hipSuccess && !rollout_only)
+            e = arm_finish_launch<T>(h, model<T>(h), h->mono_tree, groups, H, h->nu, d_mean, d_mean_out, mo, do_env, h->diag, s);
+        return e;
+    });
+}
+
+int mjmpc_arm_rollout_sampled(mjmpc_arm_t h, int dtype, int64_t P, int H, const double* d_mean, const double* d_gseq,
+                              const double* d_filter_coeffs, const double* d_chol, int chol_full, uint64_t seed, uint64_t offset,
+                              int64_t particle_offset, const int64_t* d_step_counter, void* d_costs, void* d_actions,
+                              double* d_q0, void* stream) {
+    if (!h || !d_mean || !d_gseq || !d_chol) return fail(MJMPC_E_BADARG, "null argument");
+    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "P and H must be positive");
+    if (h->n_shards > 1 || h->n_state_shards > 1)
+        return fail(MJMPC_E_BADARG, "sampled rollouts run one model and one start state (no per-shard blocks)");
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)stream;
+    const long groups = mjmpc::arm_rollout_groups((long)P);
+    // (the launch also leaves its softmax partials)
+    if (int rc = arm_grow_mono(h, (size_t)mjmpc::mono_record_doubles(groups, H, h->nu), s)) return rc;
+    mjmpc::MonoStep mo;
+    mo.chol = d_chol;
+    mo.chol_full = chol_full ? 1 : 0;
+    mo.seed = seed;
+    mo.offset = offset;
+    mo.particle_offset = (long)particle_offset;
+    mo.d_step = (const long long*)d_step_counter;
+    mo.lam = 1.0;
+    mo.shift_mode = -2;
+    mo.tree = h->mono_tree;
+    mjmpc::RolloutFusion fuse = arm_fuse(h);
+    fuse.filt = d_filter_coeffs;
+    fuse.gseq = d_gseq;
+    fuse.q0_out = d_q0;
+    return with_dtype(dtype, "arm_rollout_sampled launch", [&](auto tag) {
+        using T = decltype(tag);
+        return arm_rollout_launch<T>(h, model<T>(h), h->state, (long)P, H, h->nu, d_mean, nullptr, (T*)d_costs, (T*)d_actions,
+                                     nullptr, nullptr, nullptr, h->diag, s, fuse, &mo);
+    });
+}
+
+int mjmpc_arm_mppi_combine(mjmpc_arm_t h, int dtype, const double* d_records, int n_records, int H, const double* d_mean,
+                           double* d_mean_out, int64_t* d_step_counter, double step_size, int shift_mode,
+                           double* d_action_out, double* h_action_slots, int env_step, void* d_step_cost,
+                           void* d_step_next_obs, void* stream) {
+    if (!h || !d_records || !d_mean || !d_mean_out || d_mean_out == d_mean) return fail(MJMPC_E_BADARG, "null / aliased argument");
+    if (n_records < 1 || H < 1 || shift_mode > 1 || shift_mode < -1) return fail(MJMPC_E_BADARG, "bad n_records / H / shift_mode");
+    if (env_step && (h->n_shards > 1 || h->n_state_shards > 1))
+        return fail(MJMPC_E_BADARG, "the fused env step runs one model and one state (no per-shard blocks)");
+    HIP_TRY(hipSetDevice(h->device));
+    mjmpc::MonoStep mo;
+    mo.step_size = step_size;
+    mo.shift_mode = shift_mode;
+    mo.action_out = d_action_out;
+    mo.action_host = h_action_slots;
+    mo.step_counter = (long long*)d_step_counter;
+    mo.state_io = h->state;
+    mo.step_cost = d_step_cost;
+    mo.step_nobs = d_step_next_obs;
+    mo.reset_rec = h->reset_rec;
+    return with_dtype(dtype, "arm_mppi_combine launch", [&](auto tag) {
+        using T = decltype(tag);
+        return arm_finish_launch<T>(h, model<T>(h), d_records, n_records, H, h->nu, d_mean, d_mean_out, mo, env_step ? 1 : 0,
+                                    h->diag, (hipStream_t)stream);
+    });
+}
+
+int mjmpc_arm_step_state(mjmpc_arm_t h, int dtype, const double* d_action, void* d_cost, void* d_next_obs,
+                         void* stream) {
+    if (!h || !d_action || !d_cost) return fail(MJMPC_E_BADARG, "null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    return with_dtype(dtype, "arm_step_state launch", [&](auto tag) {
+        using T = decltype(tag);
+        return arm_rollout_launch<T>(h, model<T>(h), h->state, 1, 1, h->nu, d_action, nullptr, (T*)d_cost, nullptr, nullptr,
+                                     (T*)d_next_obs, h->state, h->diag, (hipStream_t)stream, arm_fuse(h));
+    });
+}
+
+int mjmpc_arm_solver_failures(mjmpc_arm_t h, uint32_t* count) { return read_counter(h, 0, count); }
+int mjmpc_arm_diverged(mjmpc_arm_t h, uint32_t* count) { return read_counter(h, 1, count); }
+int mjmpc_arm_env_resets(mjmpc_arm_t h, uint32_t* count) { return read_counter(h, ARM_DIAG_ENV_RESETS, count); }
+int mjmpc_arm_set_reset_returns(mjmpc_arm_t h, int inf_returns) { return set_reset_returns(h, inf_returns); }
+
+#ifdef MJMPC_STAMPS
+// developer builds only (not declared in include/mjmpc_amd.h): read and clear the phase clocks
+extern "C" int mjmpc_debug_stamps(mjmpc_arm_t h, unsigned long long* out32) {
+    if (!h || !out32) return fail(MJMPC_E_BADARG, "null argument");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out32, (char*)h->diag + 16, 8 * 64, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset((char*)h->diag + 16, 0, 8 * 64));
+    return 0;
+}
+#endif
+
+/* ---- tree engine ------------------------------------------------------------------------------------ */
+#ifdef TREE_STATS
+// developer builds only (not declared in include/mjmpc_amd.h): read and clear the phase clocks / iteration counts
+extern "C" int mjmpc_debug_tree_stats(mjmpc_tree_t h, unsigned long long* out48) {
+    if (!h || !out48) return fail(MJMPC_E_BADARG, "null argument");
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out48, (char*)h->diag + 8, 8 * mjmpc::TREE_STAT_SLOTS, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemset((char*)h->diag + 8, 0, 8 * mjmpc::TREE_STAT_SLOTS));
+    return 0;
+}
+#endif
 
 int mjmpc_tree_create(const double* blob, int n_blob, int device, mjmpc_tree_t* out) {
     return mjmpc_tree_create_ex(blob, n_blob, device, MJMPC_INTEGRATOR_EULER, out);
+}
+
+static int tree_create_impl(mjmpc_tree_s* h, const double* blob, int n_blob) {
+    if (int rc = core_create(h, blob, n_blob, MJMPC_TREE_DEVICE_STATE_LEN, MJMPC_TREE_DIAG_BYTES)) return rc;
+    HIP_TRY(hipMalloc(&h->zero_action, sizeof(double) * 40));
+    HIP_TRY(hipMemset(h->zero_action, 0, sizeof(double) * 40));
+    h->scratch = h->zero_action + 32;
+    return tree_make_reset_records(h, blob, 1, h->full, &h->reset_rec);
 }
 
 int mjmpc_tree_create_ex(const double* blob, int n_blob, int device, int integrator, mjmpc_tree_t* out) {
@@ -879,47 +940,19 @@ int mjmpc_tree_set_shard_models(mjmpc_tree_t h, const double* blobs, int n_shard
     if (h->n_state_shards > 1 && n_shards > 1 && n_shards != h->n_state_shards)
         return fail(MJMPC_E_BADARG, "%d model shards but %d per-shard start states", n_shards, h->n_state_shards);
     HIP_TRY(hipSetDevice(h->device));
-    const size_t L = (size_t)mjmpc::TREE_BLOB_LEN, n = (size_t)n_shards * L;
     bool full = false;
     for (int s = 0; s < n_shards; ++s) {
-        const double* b = blobs + (size_t)s * L;
+        const double* b = blobs + (size_t)s * mjmpc::TREE_BLOB_LEN;
         if ((int)b[mjmpc::T_N_SPHERE] > mjmpc::TREE_MAX_SPHERES || !tree_same_topology(b, h->topo.data()))
             return fail(MJMPC_E_BADMODEL, "shard %d does not have the engine's topology / dimensions", s);
         full = full || tree_blob_is_full(b, h->nv);
         if ((int)b[mjmpc::T_GEN] != h->gen)
             return fail(MJMPC_E_BADMODEL, "shard %d needs a different kernel instantiation than the engine's model", s);
     }
-    std::vector<float> f32(blobs, blobs + n);
-    HIP_TRY(hipDeviceSynchronize());
-    float* m32 = nullptr;
-    double* m64 = nullptr;
-    HIP_TRY(hipMalloc(&m32, sizeof(float) * n));
-    if (hipError_t e = hipMalloc(&m64, sizeof(double) * n); e != hipSuccess) {
-        hipFree(m32);
-        return hip_fail(e, "hipMalloc");
-    }
-    hipError_t e = hipMemcpy(m32, f32.data(), sizeof(float) * n, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(m64, blobs, sizeof(double) * n, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        hipFree(m32);
-        hipFree(m64);
-        return hip_fail(e, "hipMemcpy");
-    }
-    double* rec = nullptr;      // the reset records of the NEW blocks first: a failure leaves the engine as it was
-    if (int rc = tree_make_reset_records(h, blobs, n_shards, full, &rec); rc != 0) {
-        hipFree(m32);
-        hipFree(m64);
-        return rc;
-    }
-    hipFree(h->model_f32);
-    hipFree(h->model_f64);
-    h->model_f32 = m32;
-    h->model_f64 = m64;
-    h->n_shards = n_shards;
-    h->full = full;             // of the NEW set of blocks (they replace the old ones)
-    if (h->reset_rec) h->reset_retired.push_back(h->reset_rec);
-    h->reset_rec = rec;
-    return 0;
+    const int rc = core_swap_models(h, blobs, n_shards, mjmpc::TREE_BLOB_LEN,
+                                    [&](double** rec) { return tree_make_reset_records(h, blobs, n_shards, full, rec); });
+    if (rc == 0) h->full = full;    // of the NEW set of blocks (they replace the old ones)
+    return rc;
 }
 
 int mjmpc_tree_set_shard_states(mjmpc_tree_t h, const double* states, int n_shards, void* stream) {
@@ -927,95 +960,48 @@ int mjmpc_tree_set_shard_states(mjmpc_tree_t h, const double* states, int n_shar
     if (h->n_shards > 1 && n_shards > 1 && n_shards != h->n_shards)
         return fail(MJMPC_E_BADARG, "%d per-shard start states but %d model shards", n_shards, h->n_shards);
     HIP_TRY(hipSetDevice(h->device));
-    if (n_shards != h->n_state_shards) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(h->shard_states);
-        h->shard_states = nullptr;
-        h->n_state_shards = 0;
-        if (n_shards > 0) HIP_TRY(hipMalloc(&h->shard_states, sizeof(double) * MJMPC_TREE_DEVICE_STATE_LEN * n_shards));
-        h->n_state_shards = n_shards;
+    if (int rc = core_resize_shard_states(h, n_shards, MJMPC_TREE_DEVICE_STATE_LEN)) return rc;
+    if (n_shards == 0) return 0;
+    std::vector<double> packed((size_t)n_shards * MJMPC_TREE_DEVICE_STATE_LEN);
+    for (int k = 0; k < n_shards; ++k) {
+        const double* pub = states + (size_t)k * MJMPC_TREE_STATE_LEN;     // qpos[40] | qvel[32] | target[3] | -
+        tree_pack_state(h, pub, pub + mjmpc::TREE_NQ_MAX, pub + mjmpc::TREE_NQ_MAX + mjmpc::TL,
+                        packed.data() + (size_t)k * MJMPC_TREE_DEVICE_STATE_LEN);
     }
-    if (n_shards > 0) {
-        std::vector<double> packed((size_t)n_shards * MJMPC_TREE_DEVICE_STATE_LEN);
-        for (int k = 0; k < n_shards; ++k) {
-            const double* pub = states + (size_t)k * MJMPC_TREE_STATE_LEN;     // qpos[40] | qvel[32] | target[3] | -
-            tree_pack_state(h, pub, pub + mjmpc::TREE_NQ_MAX, pub + mjmpc::TREE_NQ_MAX + mjmpc::TL,
-                            packed.data() + (size_t)k * MJMPC_TREE_DEVICE_STATE_LEN);
-        }
-        HIP_TRY(hipMemcpyAsync(h->shard_states, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice,
-                               (hipStream_t)stream));
-        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));      // `packed` is pageable host memory
-    }
-    return 0;
+    return core_upload_shard_states(h, packed.data(), packed.size(), (hipStream_t)stream);
 }
 
 int mjmpc_tree_destroy(mjmpc_tree_t h) {
     if (!h) return 0;
-    hipSetDevice(h->device);
-    hipFree(h->model_f32);
-    hipFree(h->model_f64);
-    hipFree(h->state);
-    hipFree(h->diag);
+    core_free(h);
     hipFree(h->zero_action);
-    hipFree(h->shard_states);
-    hipFree(h->reset_rec);
-    for (double* p : h->reset_retired) hipFree(p);
-    if (h->pinned) hipHostFree(h->pinned);
-    for (int k = 0; k < 4; ++k) if (h->staged[k]) hipEventDestroy(h->staged[k]);
     delete h;
     return 0;
 }
 
-int mjmpc_tree_dims(mjmpc_tree_t h, int* nv, int* nu, int* d_obs) {
-    if (!h) return fail(MJMPC_E_BADARG, "null engine");
-    if (nv) *nv = h->nv;
-    if (nu) *nu = h->nu;
-    if (d_obs) *d_obs = h->d_obs;
-    return 0;
-}
+int mjmpc_tree_dims(mjmpc_tree_t h, int* nv, int* nu, int* d_obs) { return core_dims(h, nv, nu, d_obs); }
 
 int mjmpc_tree_nq(mjmpc_tree_t h) { return h ? h->nq : -1; }
 
 int mjmpc_tree_set_state(mjmpc_tree_t h, const double* qpos, const double* qvel, const double* target_pos,
                          void* stream) {
     if (!h || !qpos || !qvel || !target_pos) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(hipSetDevice(h->device));
-    // staging ring as mjmpc_arm_set_state: wait only for the copy that last used THIS slot (four calls ago), never for
-    // the stream - a captured control iteration still running on `s` keeps running while the next state is staged
-    const int slot = h->stage_next;
-    h->stage_next = (slot + 1) & 3;
-    HIP_TRY(hipEventSynchronize(h->staged[slot]));
-    double* st = h->pinned + (size_t)slot * MJMPC_TREE_DEVICE_STATE_LEN;
-    tree_pack_state(h, qpos, qvel, target_pos, st);
-    HIP_TRY(hipMemcpyAsync(h->state, st, sizeof(double) * MJMPC_TREE_DEVICE_STATE_LEN, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(h->staged[slot], s));
-    return 0;
+    return core_set_state(h, MJMPC_TREE_DEVICE_STATE_LEN, (hipStream_t)stream,
+                          [&](double* stage) { tree_pack_state(h, qpos, qvel, target_pos, stage); });
 }
 
 int mjmpc_tree_rollout(mjmpc_tree_t h, int dtype, int64_t P, int H, const double* d_mean, const void* d_noise,
                        void* d_costs, void* d_actions, void* d_obs, void* d_next_obs, void* stream) {
     if (!h || !d_mean || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
-    if (P < 0 || H < 0) return fail(MJMPC_E_BADARG, "negative size");
-    const int nss = h->n_state_shards > 1 ? h->n_state_shards : 1;
-    if (P % h->n_shards != 0 || P % nss != 0)
-        return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d shards", (long long)P, std::max(h->n_shards, nss));
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    const double* st = nss > 1 ? h->shard_states : h->state;
-    if (dtype == MJMPC_F32)
-        e = mjmpc::launch_tree_rollout<float>(h->model_f32, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
-                                              (const float*)d_noise, (float*)d_costs, (float*)d_actions, (float*)d_obs,
-                                              (float*)d_next_obs, h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
-    else if (dtype == MJMPC_F64)
-        e = mjmpc::launch_tree_rollout<double>(h->model_f64, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
-                                               (const double*)d_noise, (double*)d_costs, (double*)d_actions,
-                                               (double*)d_obs, (double*)d_next_obs, h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "tree_rollout launch");
-    return 0;
+    TreeCall c;
+    if (int rc = tree_rollout_begin(h, P, H, &c)) return rc;
+    c.mean = d_mean;
+    c.noise = d_noise;
+    c.cost = d_costs;
+    c.act = d_actions;
+    c.obs = d_obs;
+    c.nobs = d_next_obs;
+    return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_rollout launch");
 }
 
 int mjmpc_tree_rollout_fused(mjmpc_tree_t h, int dtype, int64_t P, int H, const double* d_mean, const void* d_noise,
@@ -1023,90 +1009,56 @@ int mjmpc_tree_rollout_fused(mjmpc_tree_t h, int dtype, int64_t P, int H, const 
                              void* stream) {
     if (!h || !d_mean || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
     if ((d_q0 != nullptr) != (d_gseq != nullptr)) return fail(MJMPC_E_BADARG, "d_q0 and d_gseq go together");
-    if (P < 0 || H < 0) return fail(MJMPC_E_BADARG, "negative size");
-    const int nss = h->n_state_shards > 1 ? h->n_state_shards : 1;
-    if (P % h->n_shards != 0 || P % nss != 0)
-        return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d shards", (long long)P, std::max(h->n_shards, nss));
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    mjmpc::TreeFusion fuse = tree_fuse(h);
-    fuse.filt = d_filter_coeffs;
-    fuse.gseq = d_gseq;
-    fuse.q0_out = d_q0;
-    hipError_t e;
-    const double* st = nss > 1 ? h->shard_states : h->state;
-    if (dtype == MJMPC_F32)
-        e = mjmpc::launch_tree_rollout<float>(h->model_f32, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
-                                              (const float*)d_noise, (float*)d_costs, (float*)d_actions, nullptr, nullptr, h->diag,
-                                              s, nullptr, nullptr, nullptr, nss, h->gen, fuse, h->integrator);
-    else if (dtype == MJMPC_F64)
-        e = mjmpc::launch_tree_rollout<double>(h->model_f64, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu, d_mean,
-                                               (const double*)d_noise, (double*)d_costs, (double*)d_actions, nullptr, nullptr,
-                                               h->diag, s, nullptr, nullptr, nullptr, nss, h->gen, fuse, h->integrator);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "tree_rollout_fused launch");
-    return 0;
+    TreeCall c;
+    if (int rc = tree_rollout_begin(h, P, H, &c)) return rc;
+    c.mean = d_mean;
+    c.noise = d_noise;
+    c.cost = d_costs;
+    c.act = d_actions;
+    c.fuse.filt = d_filter_coeffs;
+    c.fuse.gseq = d_gseq;
+    c.fuse.q0_out = d_q0;
+    return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_rollout_fused launch");
 }
 
 int mjmpc_tree_rollout_cl(mjmpc_tree_t h, int dtype, int64_t P, int H, const double* d_weights, const void* d_noise,
                           void* d_costs, void* d_actions, void* d_obs, void* d_next_obs, void* stream) {
     if (!h || !d_weights || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
-    if (P < 0 || H < 0) return fail(MJMPC_E_BADARG, "negative size");
-    const int nss = h->n_state_shards > 1 ? h->n_state_shards : 1;
-    if (P % h->n_shards != 0 || P % nss != 0)
-        return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d shards", (long long)P, std::max(h->n_shards, nss));
-    HIP_TRY(hipSetDevice(h->device));
+    TreeCall c;
+    if (int rc = tree_rollout_begin(h, P, H, &c)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipSuccess;
-    double* st = nss > 1 ? h->shard_states : h->state;
     // the first action depends on the fresh observation, whose tracked site comes out of a kinematics pass: a
     // one-particle, one-step launch per start state (its cost lands in the workspace and is discarded) leaves it in
     // the state vector
-    for (int k = 0; k < nss && e == hipSuccess; ++k) {
-        double* sk = st + (size_t)k * MJMPC_TREE_DEVICE_STATE_LEN;
-        double* site0 = sk + 2 * mjmpc::TL + 3;
-        if (dtype == MJMPC_F32)
-            e = mjmpc::launch_tree_rollout<float>(h->model_f32 + (h->n_shards > 1 ? (size_t)k * mjmpc::TREE_BLOB_LEN : 0), 1, h->max_path,
-                                                  h->full, h->nv, sk, 1, 1, h->nu, h->zero_action, nullptr, (float*)h->scratch,
-                                                  nullptr, nullptr, nullptr, h->diag, s, nullptr, nullptr, site0, 1, h->gen, tree_fuse(h, k), h->integrator);
-        else if (dtype == MJMPC_F64)
-            e = mjmpc::launch_tree_rollout<double>(h->model_f64 + (h->n_shards > 1 ? (size_t)k * mjmpc::TREE_BLOB_LEN : 0), 1, h->max_path,
-                                                   h->full, h->nv, sk, 1, 1, h->nu, h->zero_action, nullptr, (double*)h->scratch,
-                                                   nullptr, nullptr, nullptr, h->diag, s, nullptr, nullptr, site0, 1, h->gen, tree_fuse(h, k), h->integrator);
-        else
-            return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
+    for (int k = 0; k < c.n_state_shards; ++k) {
+        double* sk = (c.n_state_shards > 1 ? h->shard_states : h->state) + (size_t)k * MJMPC_TREE_DEVICE_STATE_LEN;
+        TreeCall kin(h, k);
+        kin.state = sk;
+        kin.mean = h->zero_action;
+        kin.cost = h->scratch;
+        kin.site_out = sk + 2 * mjmpc::TL + 3;
+        if (int rc = tree_issue(h, dtype, kin, s, "tree_rollout_cl launch")) return rc;
     }
-    if (e == hipSuccess) {
-        if (dtype == MJMPC_F32)
-            e = mjmpc::launch_tree_rollout<float>(h->model_f32, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu,
-                                                  d_weights, (const float*)d_noise, (float*)d_costs, (float*)d_actions, (float*)d_obs,
-                                                  (float*)d_next_obs, h->diag, s, nullptr, d_weights, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
-        else
-            e = mjmpc::launch_tree_rollout<double>(h->model_f64, h->n_shards, h->max_path, h->full, h->nv, st, (long)P, H, h->nu,
-                                                   d_weights, (const double*)d_noise, (double*)d_costs, (double*)d_actions,
-                                                   (double*)d_obs, (double*)d_next_obs, h->diag, s, nullptr, d_weights, nullptr, nss, h->gen, tree_fuse(h), h->integrator);
-    }
-    if (e != hipSuccess) return hip_fail(e, "tree_rollout_cl launch");
-    return 0;
+    c.mean = d_weights;
+    c.clw = d_weights;
+    c.noise = d_noise;
+    c.cost = d_costs;
+    c.act = d_actions;
+    c.obs = d_obs;
+    c.nobs = d_next_obs;
+    return tree_issue(h, dtype, c, s, "tree_rollout_cl launch");
 }
 
 int mjmpc_tree_step_state(mjmpc_tree_t h, int dtype, const double* d_action, void* d_cost, void* d_next_obs, void* stream) {
     if (!h || !d_action || !d_cost) return fail(MJMPC_E_BADARG, "null argument");
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    // one particle, one env step, no noise, shard 0's model; the state vector is advanced in place
-    if (dtype == MJMPC_F32)
-        e = mjmpc::launch_tree_rollout<float>(h->model_f32, 1, h->max_path, h->full, h->nv, h->state, 1, 1, h->nu, d_action, nullptr,
-                                              (float*)d_cost, nullptr, nullptr, (float*)d_next_obs, h->diag, s, h->state, nullptr, nullptr, 1, h->gen, tree_fuse(h, 0), h->integrator);
-    else if (dtype == MJMPC_F64)
-        e = mjmpc::launch_tree_rollout<double>(h->model_f64, 1, h->max_path, h->full, h->nv, h->state, 1, 1, h->nu, d_action, nullptr,
-                                               (double*)d_cost, nullptr, nullptr, (double*)d_next_obs, h->diag, s, h->state, nullptr, nullptr, 1, h->gen, tree_fuse(h, 0), h->integrator);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "tree_step_state launch");
-    return 0;
+    TreeCall c(h, 0);       // one particle, one env step, no noise, shard 0's model; the state vector is advanced in place
+    c.state = h->state;
+    c.mean = d_action;
+    c.cost = d_cost;
+    c.nobs = d_next_obs;
+    c.state_out = h->state;
+    return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_step_state launch");
 }
 
 int mjmpc_tree_get_state(mjmpc_tree_t h, double* qpos, double* qvel, void* stream) {
@@ -1120,20 +1072,6 @@ int mjmpc_tree_get_state(mjmpc_tree_t h, double* qpos, double* qvel, void* strea
 }
 
 /* ---- episode batches: the engine's E state shards are the batch's E real envs ---------------------------- */
-// what every batch entry point asks of the engine: one model block, 1 .. 65535 state shards (grid rows), and - given a
-// particle count - the same number of particles per shard
-static int tree_batch_shape(mjmpc_tree_t h, int64_t P_total, int* E) {
-    if (!h) return fail(MJMPC_E_BADARG, "null engine");
-    if (h->n_shards > 1) return fail(MJMPC_E_BADARG, "an episode batch runs one model block; the engine has %d", h->n_shards);
-    const int e = h->n_state_shards;
-    if (e < 1 || e > 65535)
-        return fail(MJMPC_E_BADARG, "an episode batch needs 1 .. 65535 state shards (mjmpc_tree_set_shard_states); the engine has %d", e);
-    if (P_total < 1 || P_total % e != 0)
-        return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d episodes", (long long)P_total, e);
-    *E = e;
-    return 0;
-}
-
 int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
                                    const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
                                    double* d_q0, void* stream) {
@@ -1144,23 +1082,20 @@ int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, i
     if (int rc = tree_batch_shape(h, P_total, &E)) return rc;
     if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
-    mjmpc::TreeFusion fuse = tree_fuse(h);
-    fuse.filt = d_filter_coeffs;
-    fuse.gseq = d_gseq;
-    fuse.q0_out = d_q0;
-    fuse.mean_stride = (long)H * h->nu;         // episode e's mean: d_means + e H A
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = mjmpc::launch_tree_rollout<float>(h->model_f32, 1, h->max_path, h->full, h->nv, h->shard_states, (long)P_total, H, h->nu,
-                                              d_means, (const float*)d_noise, (float*)d_costs, (float*)d_actions, nullptr, nullptr,
-                                              h->diag, s, nullptr, nullptr, nullptr, E, h->gen, fuse, h->integrator);
-    else
-        e = mjmpc::launch_tree_rollout<double>(h->model_f64, 1, h->max_path, h->full, h->nv, h->shard_states, (long)P_total, H, h->nu,
-                                               d_means, (const double*)d_noise, (double*)d_costs, (double*)d_actions, nullptr, nullptr,
-                                               h->diag, s, nullptr, nullptr, nullptr, E, h->gen, fuse, h->integrator);
-    if (e != hipSuccess) return hip_fail(e, "tree_rollout_fused_batch launch");
-    return 0;
+    TreeCall c(h);
+    c.state = h->shard_states;
+    c.n_state_shards = E;
+    c.P = (long)P_total;
+    c.H = H;
+    c.mean = d_means;
+    c.noise = d_noise;
+    c.cost = d_costs;
+    c.act = d_actions;
+    c.fuse.filt = d_filter_coeffs;
+    c.fuse.gseq = d_gseq;
+    c.fuse.q0_out = d_q0;
+    c.fuse.mean_stride = (long)H * h->nu;       // episode e's mean: d_means + e H A
+    return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_rollout_fused_batch launch");
 }
 
 int mjmpc_tree_step_shard_states(mjmpc_tree_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream) {
@@ -1169,23 +1104,19 @@ int mjmpc_tree_step_shard_states(mjmpc_tree_t h, int dtype, const double* d_acti
     if (int rc = tree_batch_shape(h, h->n_state_shards, &E)) return rc;
     if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t s = (hipStream_t)stream;
     // mjmpc_tree_step_state once per row: one particle, one env step, no noise, the model block's instantiation and reset
     // record; row e reads action e and advances state shard e in place
-    mjmpc::TreeFusion fuse = tree_fuse(h, 0);
-    fuse.mean_stride = h->nu;
-    fuse.state_out_stride = mjmpc::TREE_STATE_LEN;
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = mjmpc::launch_tree_rollout<float>(h->model_f32, 1, h->max_path, h->full, h->nv, h->shard_states, E, 1, h->nu, d_actions,
-                                              nullptr, (float*)d_costs, nullptr, nullptr, (float*)d_next_obs, h->diag, s,
-                                              h->shard_states, nullptr, nullptr, E, h->gen, fuse, h->integrator);
-    else
-        e = mjmpc::launch_tree_rollout<double>(h->model_f64, 1, h->max_path, h->full, h->nv, h->shard_states, E, 1, h->nu, d_actions,
-                                               nullptr, (double*)d_costs, nullptr, nullptr, (double*)d_next_obs, h->diag, s,
-                                               h->shard_states, nullptr, nullptr, E, h->gen, fuse, h->integrator);
-    if (e != hipSuccess) return hip_fail(e, "tree_step_shard_states launch");
-    return 0;
+    TreeCall c(h, 0);
+    c.state = h->shard_states;
+    c.n_state_shards = E;
+    c.P = E;
+    c.mean = d_actions;
+    c.cost = d_costs;
+    c.nobs = d_next_obs;
+    c.state_out = h->shard_states;
+    c.fuse.mean_stride = h->nu;
+    c.fuse.state_out_stride = mjmpc::TREE_STATE_LEN;
+    return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_step_shard_states launch");
 }
 
 int mjmpc_tree_get_shard_states(mjmpc_tree_t h, double* qpos, double* qvel, void* stream) {
@@ -1201,76 +1132,21 @@ int mjmpc_tree_get_shard_states(mjmpc_tree_t h, double* qpos, double* qvel, void
     return 0;
 }
 
-int mjmpc_tree_solver_failures(mjmpc_tree_t h, uint32_t* count) {
-    if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned c = 0;
-    HIP_TRY(hipMemcpy(&c, h->diag, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *count = c;
-    return 0;
-}
-
-int mjmpc_tree_diverged(mjmpc_tree_t h, uint32_t* count) {
-    if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned c = 0;
-    HIP_TRY(hipMemcpy(&c, h->diag + 1, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *count = c;
-    return 0;
-}
-
-int mjmpc_tree_env_resets(mjmpc_tree_t h, uint32_t* count) {
-    if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned c = 0;
-    HIP_TRY(hipMemcpy(&c, h->diag + mjmpc::TREE_DIAG_ENV_RESETS, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *count = c;
-    return 0;
-}
-
-int mjmpc_arm_env_resets(mjmpc_arm_t h, uint32_t* count) {
-    if (!h || !count) return fail(MJMPC_E_BADARG, "null argument");
-    HIP_TRY(hipSetDevice(h->device));
-    HIP_TRY(hipDeviceSynchronize());
-    unsigned c = 0;
-    HIP_TRY(hipMemcpy(&c, h->diag + 2, sizeof(unsigned), hipMemcpyDeviceToHost));
-    *count = c;
-    return 0;
-}
-
-int mjmpc_tree_set_reset_returns(mjmpc_tree_t h, int inf_returns) {
-    if (!h) return fail(MJMPC_E_BADARG, "null argument");
-    h->inf_on_reset = inf_returns ? 1 : 0;
-    return 0;
-}
-
-int mjmpc_arm_set_reset_returns(mjmpc_arm_t h, int inf_returns) {
-    if (!h) return fail(MJMPC_E_BADARG, "null argument");
-    h->inf_on_reset = inf_returns ? 1 : 0;
-    return 0;
-}
+int mjmpc_tree_solver_failures(mjmpc_tree_t h, uint32_t* count) { return read_counter(h, 0, count); }
+int mjmpc_tree_diverged(mjmpc_tree_t h, uint32_t* count) { return read_counter(h, 1, count); }
+int mjmpc_tree_env_resets(mjmpc_tree_t h, uint32_t* count) { return read_counter(h, mjmpc::TREE_DIAG_ENV_RESETS, count); }
+int mjmpc_tree_set_reset_returns(mjmpc_tree_t h, int inf_returns) { return set_reset_returns(h, inf_returns); }
 
 int mjmpc_analytic_rollout(int kind, const double* d_params, int n_state, int n_action, const double* d_state, int dtype,
                            int64_t P, int H, const double* d_mean, const void* d_noise, void* d_costs, void* d_actions,
                            void* d_obs, void* d_next_obs, int closed_loop_linear, void* stream) {
     if (!d_params || !d_state || !d_mean || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
-    if (dtype == MJMPC_F32)
-        e = mjmpc::launch_analytic_rollout<float>(kind, d_params, n_state, n_action, d_state, (long)P, H, d_mean,
-                                                  (const float*)d_noise, (float*)d_costs, (float*)d_actions,
-                                                  (float*)d_obs, (float*)d_next_obs, s, closed_loop_linear);
-    else if (dtype == MJMPC_F64)
-        e = mjmpc::launch_analytic_rollout<double>(kind, d_params, n_state, n_action, d_state, (long)P, H, d_mean,
-                                                   (const double*)d_noise, (double*)d_costs, (double*)d_actions,
-                                                   (double*)d_obs, (double*)d_next_obs, s, closed_loop_linear);
-    else
-        return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
-    if (e != hipSuccess) return hip_fail(e, "analytic rollout launch");
-    return 0;
+    return with_dtype(dtype, "analytic rollout launch", [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::launch_analytic_rollout<T>(kind, d_params, n_state, n_action, d_state, (long)P, H, d_mean, (const T*)d_noise,
+                                                 (T*)d_costs, (T*)d_actions, (T*)d_obs, (T*)d_next_obs, (hipStream_t)stream,
+                                                 closed_loop_linear);
+    });
 }
 
 // ---- update / noise entry points -------------------------------------------------------------------

@@ -1,0 +1,344 @@
+"""The host side of a GPU rollout engine, once: ``RolloutEngine`` is what ``ArmRolloutEngine`` (arm_engine.py) and
+``TreeRolloutEngine`` (tree_engine.py) have in common - the reference-shaped surface of ``SubprocVecEnv``
+(mjmpc/envs/vec_env/subproc_vec_env.py:128-186, 235-256, 304-312), the device-resident rollouts, the per-shard models
+and start states - over the C ABI's ``mjmpc_<_abi>_*`` entry points.  A subclass says what differs: its model compiler and
+``create`` call, the layout of a shard's start state, how a state dictionary is read, and a few defaults.
+
+Every library function is looked up when it is called (``_fn``), never kept: ``_lib.recording`` swaps the library's
+attributes for recording wrappers while a launch tape is made.
+
+torch is used only as the owner of device memory and streams.
+"""
+import ctypes
+import time
+
+import numpy as np
+
+from .. import _lib
+from ..models.compile import principal_inertia
+from ..models.raw import RawModel
+from ._resets import EnvResetWatch, SimulationUnstableError  # noqa: F401
+from .seeding import np_random
+
+_DT = {"f32": (_lib.F32, np.float32), "f64": (_lib.F64, np.float64)}
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def _ptr(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _same_state(a, b):
+    return all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) for k in ("qp", "qv", "target_pos"))
+
+
+class RolloutEngine(EnvResetWatch):
+    """One GPU's worth of particles for a compiled model.  Subclasses set ``_abi``, ``_model_type``, ``_compile``,
+    ``_layout``, ``_qpos_len`` and define ``_create``, ``_unpack``, ``_start_qpos``, ``_default_geom_friction`` and
+    ``_default_frictionloss``."""
+    _model_type = None              # the compiled model's class; ``_compile(raw, overrides=, base=)`` makes one
+    _layout = None                  # a shard's start state in mjmpc_*_set_shard_states: (stride, qvel offset, target offset)
+    _qpos_len = "nv"                # the model attribute that is the length of qpos
+    forward_task = False            # the locomotion envs' {qpos, qvel} state dictionaries
+    _fused_checks_shards = False    # rollout_fused refuses an indivisible population in Python (else the C layer does)
+    _shard_states_set_state = False     # a per-shard set_env_state also makes shard 0's state ``_state``
+
+    def __init__(self, model, device=0, dtype="f64", num_shards=1):
+        self.raw = model if isinstance(model, RawModel) else None
+        if isinstance(model, RawModel):
+            model = self._compile(model)
+        if not isinstance(model, self._model_type):
+            raise TypeError("model must be a RawModel or a compiled %s" % self._model_type.__name__)
+        if dtype not in _DT:
+            raise ValueError("dtype must be 'f32' or 'f64'")
+        self.model, self.dtype = model, dtype
+        self._code, self._np = _DT[dtype]
+        self.num_shards = int(num_shards)       # reported like the reference's num_cpu (infos['total_time'])
+        self._lib = _lib.require_gpu()
+        torch = _torch()
+        self.device = torch.device("cuda", device)
+        self._tdtype = torch.float32 if dtype == "f32" else torch.float64
+        h = ctypes.c_void_p()
+        blob = np.ascontiguousarray(model.blob, np.float64)
+        _lib.check(self._create(blob.ctypes.data_as(_lib._dp), blob.size, device, ctypes.byref(h)))
+        self._h = h
+        self.d_action, self.d_obs = model.nu, model.d_obs
+        # qp, qv, qa, target_pos, timestep (reacher_env.py:81-85) or qpos, qvel
+        self.d_state = self._nq + model.nv if self.forward_task else self._nq + 2 * model.nv + 3 + 1
+        self.action_lows, self.action_highs = model.ctrl_lo.copy(), model.ctrl_hi.copy()
+        self.closed = False
+        self._buf = {}
+        self.default_dyn_params = [dict() for _ in range(self.num_shards)]
+        self.randomized_dyn_params = [dict() for _ in range(self.num_shards)]
+        self.reset()
+
+    def _fn(self, name):
+        return getattr(self._lib, "mjmpc_%s_%s" % (self._abi, name))
+
+    @property
+    def _nq(self):
+        return getattr(self.model, self._qpos_len)
+
+    # ------------------------------------------------------------------ reference-shaped API
+    def _checked_state(self, qp, qv, target_pos):
+        qp, qv, tg = (np.ascontiguousarray(x, np.float64).reshape(-1) for x in (qp, qv, target_pos))
+        if qp.size != self._nq or qv.size != self.model.nv or tg.size != 3:     # (qpos in MuJoCo's layout: nq entries)
+            raise ValueError("state has the wrong dimensions for this model")
+        return dict(qp=qp.copy(), qv=qv.copy(), target_pos=tg.copy())
+
+    def set_env_state(self, state_dicts):
+        """``SubprocVecEnv.set_env_state`` (subproc_vec_env.py:235-251): one dict (every shard starts from it), a list
+        holding one dict, or one dict per shard (shard k's particles start from states[k]).  Keys as reacher_env.py:81-85;
+        ``qa`` and ``timestep`` do not influence a rollout and are ignored."""
+        if isinstance(state_dicts, (list, tuple)):
+            if len(state_dicts) not in (1, self.num_shards):
+                raise AssertionError("num states should equal 1 (same for all envs) or 1 per env")
+            states = [self._unpack(s) for s in state_dicts]
+            if any(not _same_state(states[0], s) for s in states[1:]):
+                return self._set_shard_states(states)
+            state = states[0]
+        else:
+            state = self._unpack(state_dicts)
+        if getattr(self, "_per_shard_states", False):
+            _lib.check(self._fn("set_shard_states")(self._h, None, 0, self._stream()))
+            self._per_shard_states = False
+        self._state = state
+        _lib.check(self._fn("set_state")(self._h, state["qp"].ctypes.data_as(_lib._dp), state["qv"].ctypes.data_as(_lib._dp),
+                                         state["target_pos"].ctypes.data_as(_lib._dp), self._stream()))
+
+    def _pack_shard_states(self, states):
+        """Unpacked states -> the (n, stride) array of ``mjmpc_*_set_shard_states``: qpos | qvel | target_pos at ``_layout``."""
+        stride, ov, ot = self._layout
+        arr = np.zeros((len(states), stride))
+        for k, s in enumerate(states):
+            arr[k, :self._nq], arr[k, ov:ov + self.model.nv], arr[k, ot:ot + 3] = s["qp"], s["qv"], s["target_pos"]
+        return arr
+
+    def _set_shard_states(self, states):
+        arr = self._pack_shard_states(states)
+        _lib.check(self._fn("set_shard_states")(self._h, arr.ctypes.data_as(_lib._dp), self.num_shards, self._stream()))
+        self._per_shard_states = True
+        self._shard_state_list = states
+        if self._shard_states_set_state:
+            self._state = states[0]
+
+    def get_env_state(self):
+        """One state dict - or, after a per-shard ``set_env_state``, one per shard (subproc_vec_env.py:253-256)."""
+        states = self._shard_state_list if getattr(self, "_per_shard_states", False) else [self._state]
+        if self.forward_task:
+            return [dict(qpos=st["qp"].copy(), qvel=st["qv"].copy()) for st in states]
+        return [dict(qp=st["qp"].copy(), qv=st["qv"].copy(), qa=np.zeros(self.model.nv),
+                     target_pos=st["target_pos"].copy(), timestep=0) for st in states]
+
+    def reset(self):
+        self.set_env_state(dict(qp=self._start_qpos(), qv=np.zeros(self.model.nv),
+                                target_pos=self.model.target_default.copy()))
+
+    def close(self):
+        if not self.closed:
+            self._fn("destroy")(self._h)
+            self._h = None              # later calls fail with "null engine" instead of touching freed memory
+            self.closed = True
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def rollout(self, num_particles, horizon, mean, noise, mode="open_loop"):
+        """``SubprocVecEnv.rollout``: numpy in, numpy out, reference layouts.
+        Returns (obs, rew, act, done, info, next_obs); ``info`` is a list with one dict per shard."""
+        t0 = time.time()
+        out = self.rollout_device(num_particles, horizon, mean, noise, mode, want_obs=True)
+        costs, act, obs, nobs = (x.to("cpu").numpy().astype(np.float64, copy=False) for x in out)
+        done = np.zeros((num_particles, horizon))
+        dt = time.time() - t0
+        info = [{"total_time": dt} for _ in range(self.num_shards)]
+        return obs, -costs, act, done, info, nobs
+
+    def randomize_dynamics(self, param_dict, base_seed):
+        """``SubprocVecEnv.randomize_dynamics`` (subproc_vec_env.py:304-312): shard i draws from
+        ``np_random(base_seed + i*12345)`` a uniform value in ``m (1 +- noise)``, ``m = (1 + bias) * default``
+        for every ``{param_id: {name: [noise_scale, bias_scale]}}`` entry (gym_env_wrapper.py:367-416) and
+        from then on simulates its own model block (``mjmpc_*_set_shard_models``).  Supported: body_mass, body_inertia,
+        dof_damping, geom_size (collision geoms), geom_friction, dof_frictionloss, sensor_noise (a known sensor's draw is
+        consumed; no observation reads a sensor); what the engine's kernel makes of them: ``_overrides``.
+        Returns (default_params, randomized_params), one dict per shard."""
+        if self.raw is None:
+            raise ValueError("randomize_dynamics needs the engine to be built from a RawModel")
+        blobs = []
+        for i in range(self.num_shards):
+            rng, _ = np_random(int(base_seed) + i * 12345)
+            defaults, rand = self.default_dyn_params[i], self.randomized_dyn_params[i]
+            for param_id, entries in param_dict.items():
+                for name, (noise_scale, bias_scale) in entries.items():
+                    cur = defaults.setdefault(param_id, {}).get(name)
+                    if cur is None:
+                        cur = defaults[param_id][name] = self._default_param(param_id, name)
+                    mean = (1.0 + bias_scale) * np.asarray(cur, float)
+                    rand.setdefault(param_id, {})[name] = rng.uniform(mean - mean * noise_scale, mean + mean * noise_scale)
+            blobs.append(self._compile(self.raw, overrides=self._overrides(rand), base=self.model).blob)
+        blobs = np.ascontiguousarray(np.stack(blobs), np.float64)
+        _lib.check(self._fn("set_shard_models")(self._h, blobs.ctypes.data_as(_lib._dp), self.num_shards))
+        self.shard_blobs = blobs
+        return self.default_dyn_params, self.randomized_dyn_params
+
+    def _overrides(self, rand):
+        """What of a shard's randomized parameters reaches the model compiler."""
+        return rand
+
+    def _default_param(self, param_id, name):
+        raw, m = self.raw, self.model
+        names = [b.name for b in raw.bodies]
+        if param_id == "body_mass":
+            return float(m.body_mass[names.index(name)])
+        if param_id == "body_inertia":
+            return principal_inertia(m.body_inertia[names.index(name)])[0]
+        if param_id == "dof_damping":
+            return float(next(b.joint.damping for b in raw.bodies if b.joint is not None and b.joint.name == name))
+        if param_id in ("geom_size", "geom_friction"):
+            g = next(g for b in raw.bodies for g in b.geoms if g.name == name)
+            if param_id == "geom_friction":
+                return self._default_geom_friction(g)
+            half = 0.5 * np.linalg.norm(np.asarray(g.b, float) - np.asarray(g.a, float)) if g.type == 2 else 0.0
+            return np.array([g.radius, half, 0.0])
+        if param_id == "dof_frictionloss":
+            return self._default_frictionloss(next(b.joint for b in raw.bodies if b.joint is not None and b.joint.name == name))
+        if param_id == "sensor_noise":
+            # (gym_env_wrapper.py:396-398 - model.sensor_noise: MuJoCo keeps the value for the user and adds no noise itself, and no
+            # observation on the path reads a sensor: the draw is consumed, as in the reference, and changes nothing)
+            if name not in raw.sensors:
+                raise ValueError("no sensor named %r" % name)
+            return float(raw.sensors[name])
+        raise ValueError("Unknown dynamics field")
+
+    # ------------------------------------------------------------------ device-resident API
+    def rollout_device(self, num_particles, horizon, mean, noise, mode="open_loop", want_obs=False,
+                       want_actions=True):
+        """Launch the fused rollout.  ``mean`` / ``noise`` may be numpy arrays or CUDA tensors.
+        Returns device tensors (costs, actions, obs, next_obs); buffers are reused between calls."""
+        if mode not in ("open_loop", "closed_loop_linear"):
+            raise ValueError("unsupported rollout mode %r ('open_loop' or 'closed_loop_linear')" % (mode,))
+        if num_particles % self.num_shards != 0:
+            raise AssertionError("Number of particles must be divisible by number of shards")
+        torch = _torch()
+        P, H, A = int(num_particles), int(horizon), self.d_action
+        closed = mode == "closed_loop_linear"
+        mean_d = self._as_device(mean, torch.float64, (self.d_obs + 1, A) if closed else (H, A))
+        noise_d = None if noise is None else self._as_device(noise, self._tdtype, (P, H, A))
+        costs = self._buffer("costs", (P, H))
+        act = self._buffer("act", (P, H, A)) if want_actions else None
+        obs = self._buffer("obs", (P, H, self.d_obs)) if want_obs else None
+        nobs = self._buffer("nobs", (P, H, self.d_obs)) if want_obs else None
+        fn = self._fn("rollout_cl" if closed else "rollout")
+        _lib.check(fn(self._h, self._code, P, H, _ptr(mean_d), _ptr(noise_d), _ptr(costs), _ptr(act), _ptr(obs),
+                      _ptr(nobs), self._stream()))
+        return costs, act, obs, nobs
+
+    def rollout_fused(self, num_particles, horizon, mean, raw_noise, filter_coeffs, gamma_seq, q0_out=None):
+        """Device-resident rollout with the noise filter and the discounted cost-to-go fused into the
+        launch (``mjmpc_*_rollout_fused``).  All arguments are CUDA tensors (``filter_coeffs`` may be
+        None; ``q0_out``: a float64 [P] tensor the cost-to-go is written to instead of the engine's own
+        buffer).  Returns (costs, actions, q0)."""
+        if self._fused_checks_shards and num_particles % self.num_shards != 0:
+            raise AssertionError("Number of particles must be divisible by number of shards")
+        torch = _torch()
+        P, H, A = int(num_particles), int(horizon), self.d_action
+        mean_d = self._as_device(mean, torch.float64, (H, A))
+        noise_d = self._as_device(raw_noise, self._tdtype, (P, H, A))
+        costs = self._buffer("costs", (P, H))
+        act = self._buffer("act", (P, H, A))
+        q0 = self._q0_buffer(P, q0_out)
+        _lib.check(self._fn("rollout_fused")(self._h, self._code, P, H, _ptr(mean_d), _ptr(noise_d), _ptr(filter_coeffs),
+                                             _ptr(gamma_seq), _ptr(costs), _ptr(act), _ptr(q0), self._stream()))
+        return costs, act, q0
+
+    def step_state(self, action):
+        """Advance the engine state in place by one env step (the "real env" kept on the device).
+        ``action``: numpy (A,) or CUDA float64 tensor.  Returns (cost, next_obs) device tensors."""
+        torch = _torch()
+        a = self._as_device(action, torch.float64, (self.d_action,))
+        cost = self._buffer("step_cost", (1,))
+        nobs = self._buffer("step_obs", (self.d_obs,))
+        _lib.check(self._fn("step_state")(self._h, self._code, _ptr(a), _ptr(cost), _ptr(nobs), self._stream()))
+        return cost, nobs
+
+    def _counter(self, name):
+        c = ctypes.c_uint32()
+        _lib.check(self._fn(name)(self._h, ctypes.byref(c)))
+        return int(c.value)
+
+    def solver_failures(self):
+        return self._counter("solver_failures")
+
+    def diverged_substeps(self):
+        """Resets: particle-substeps in which MuJoCo's mj_checkPos / mj_checkVel / mj_checkAcc would have called mj_resetData
+        (a NaN or an entry beyond 1e10 in qpos / qvel / qacc); the kernel does the same and the particle rolls on from
+        qpos0 with finite costs - counted apart from solver_failures()."""
+        return self._counter("diverged")
+
+    # ------------------------------------------------------------------ helpers
+    def _stream(self):
+        return ctypes.c_void_p(_torch().cuda.current_stream(self.device).cuda_stream)
+
+    def _buffer(self, name, shape):
+        torch = _torch()
+        t = self._buf.get(name)
+        if t is None or tuple(t.shape) != tuple(shape):
+            t = torch.empty(shape, dtype=self._tdtype, device=self.device)
+            self._buf[name] = t
+        return t
+
+    def _q0_buffer(self, P, q0_out=None):
+        """Where a launch writes its cost-to-go: ``q0_out`` (float64 [P]), or the engine's own buffer of that shape."""
+        torch = _torch()
+        q0 = q0_out if q0_out is not None else self._buf.get("q0")
+        if q0 is None or q0.shape[0] != P:
+            q0 = self._buf["q0"] = torch.empty(P, dtype=torch.float64, device=self.device)
+        return q0
+
+    def _as_device(self, x, tdtype, shape):
+        torch = _torch()
+        if not isinstance(x, torch.Tensor):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        if tuple(x.shape) != tuple(shape):
+            raise ValueError("expected shape %s, got %s" % (shape, tuple(x.shape)))
+        return x.to(device=self.device, dtype=tdtype).contiguous()
+
+
+def make_device_rollout_fn(sim_env):
+    """Device-resident ``rollout_fn``: costs and actions come back as CUDA tensors (no observations,
+    which the MPPI / CEM / DMD / random-shooting updates never read - SURVEY 8b), so one control
+    iteration moves nothing across PCIe but the final action."""
+    def rollout_fn(num_particles, horizon, mean, noise, mode):
+        t0 = time.time()
+        costs, act, _, _ = sim_env.rollout_device(num_particles, horizon, mean, noise, mode, want_obs=False)
+        return dict(costs=costs, actions=act, observations=None, next_observations=None, dones=None,
+                    infos={"total_time": np.array([time.time() - t0] * sim_env.num_shards)})
+    rollout_fn.accepts_device = True          # controllers may hand over their device-resident mean
+    rollout_fn.engine = sim_env
+    if hasattr(sim_env, "rollout_fused"):   # filter + cost-to-go fused into the launch (graph fast path)
+        rollout_fn.fused = sim_env.rollout_fused
+    if hasattr(sim_env, "mppi_step"):       # the whole iteration in one launch (captured iterations of MPPI / DMD-MPC)
+        rollout_fn.mono = sim_env.mppi_step
+        rollout_fn.sampled = sim_env.rollout_sampled     # rollouts that draw their own samples (any update that reads q0 / actions)
+        rollout_fn.mono_launcher = sim_env.mppi_step_launcher
+        rollout_fn.combine_launcher = sim_env.mppi_combine_launcher
+    return rollout_fn
+
+
+def make_rollout_fn(sim_env):
+    """The ``rollout_fn`` closure of examples/example_mpc.py:112-133 over any engine with a
+    reference-shaped ``rollout``: negates rewards into costs and builds the trajectory dict."""
+    def rollout_fn(num_particles, horizon, mean, noise, mode):
+        obs, rew, act, done, info, nobs = sim_env.rollout(num_particles, horizon, np.array(mean, copy=True),
+                                                          noise, mode)
+        infos = {k: np.array([d[k] for d in info]) for k in info[0]}
+        return dict(observations=obs, actions=act, costs=-1.0 * rew, dones=done,
+                    next_observations=nobs, infos=infos)
+    return rollout_fn

@@ -9,12 +9,9 @@ import time
 import numpy as np
 
 from .. import _lib
+from ._engine import _ptr
 
 KIND_PENDULUM, KIND_LQR = 0, 1
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 class AnalyticRolloutEngine:
