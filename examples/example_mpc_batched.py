@@ -2,13 +2,18 @@
 """The config's ``n_episodes`` MPPI episodes as ONE batch on the tree engine (``BatchedMPPI``).
 
     python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi]
-        [--dtype f64|f32] [--episodes N]
+        [--dtype f64|f32] [--episodes N] [--dyn_randomize_config FILE [--num_cpu K] [--dyn_per_episode]]
 
 examples/example_mpc.py runs the episodes one after another (as the reference's job_script.py:80-99): episode i with seed
 ``seed + i*12345`` from the env class's ``reset(seed=...)``.  This driver takes the same seeds and start states and runs all
 episodes side by side - one sampling launch, one rollout launch, one update launch and one env-step launch per control
 step of the whole batch.  Each episode computes exactly what the single-episode device path (``noise_mode='device'``,
 ``--graph``) computes for it on the tree engine.
+
+``--dyn_randomize_config`` (the reference's example_mpc.py option; examples/configs/*_dyn_randomize.yml): every episode's
+particles are split into the config's ``num_cpu`` shards and each shard rolls out its own randomized model, drawn once for
+all episodes from the config's ``seed`` as the reference does before its episode loop (``--dyn_per_episode``: from every
+episode's own seed), while the real envs keep the nominal model - still one batch.
 
 Only the ``mppi`` block runs here; other controller blocks are refused.  The reacher configs run on the TREE engine here
 (sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
@@ -36,6 +41,9 @@ def main():
     ap.add_argument("--controller", default="mppi", help="controller block of the config to run (mppi only)")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--episodes", type=int, help="override n_episodes")
+    ap.add_argument("--dyn_randomize_config", help="yaml file with dynamics randomization parameters")
+    ap.add_argument("--num_cpu", type=int, help="override the config's num_cpu (the model shards of --dyn_randomize_config)")
+    ap.add_argument("--dyn_per_episode", action="store_true", help="a set of randomized models per episode (from its seed)")
     args = ap.parse_args()
     with open(args.config) as f:
         exp = yaml.safe_load(f)
@@ -46,7 +54,8 @@ def main():
     if not isinstance(exp.get("mppi"), dict):
         raise SystemExit("the config has no 'mppi' controller block")
     params = dict(exp["mppi"])
-    num_cpu = params.pop("num_cpu", 1)
+    num_cpu = args.num_cpu or params.pop("num_cpu", 1)
+    params.pop("num_cpu", None)
     if "particles_per_cpu" in params:
         params["num_particles"] = num_cpu * params.pop("particles_per_cpu")
     E = args.episodes or exp["n_episodes"]
@@ -68,6 +77,12 @@ def main():
                         params.get("base_action", exp.get("base_action", "null")), seeds, dtype=args.dtype,
                         n_iters=params.get("n_iters", 1), alpha=params.get("alpha", 1),
                         time_based_weights=params.get("time_based_weights", False))
+    if args.dyn_randomize_config:
+        with open(args.dyn_randomize_config) as f:
+            default_params, randomized = batch.randomize_dynamics(yaml.safe_load(f), seeds if args.dyn_per_episode else exp["seed"],
+                                                                  num_shards=num_cpu)
+        print("default params   :", default_params[0][0] if args.dyn_per_episode else default_params[0])
+        print("randomized params:", randomized)
     batch.set_states(states)
     batch.run(1)                        # warm-up step (code objects, allocations), then back to the start
     batch.reset()
@@ -86,8 +101,9 @@ def main():
             print("episode %d: reward %.3f, final distance to target %.4f"
                   % (i, rewards[i], np.linalg.norm(nobs[-1, i, -3:])))
     print("Avg. reward = %.4f, Std. Reward = %.4f" % (rewards.mean(), rewards.std()))
-    print("mppi batch: %d episodes x %d particles x H%d, %.3f ms per batched control step (%.0f episode-steps/s)"
-          % (E, params["num_particles"], params["horizon"], 1e3 * dt / T, E * T / dt))
+    print("mppi batch: %d episodes x %d particles x H%d%s, %.3f ms per batched control step (%.0f episode-steps/s)"
+          % (E, params["num_particles"], params["horizon"],
+             ", %d randomized model shards" % num_cpu if args.dyn_randomize_config else "", 1e3 * dt / T, E * T / dt))
 
 
 if __name__ == "__main__":

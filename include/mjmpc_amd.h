@@ -35,6 +35,8 @@ extern "C" {
  *      mjmpc_{arm,tree}_set_reset_returns (+inf returns for particles that reset, as an engine option);
  *      MJMPC_ARM_BLOB_LEN 229 -> 255 (joint type, friction loss, nu: the arm engine takes slide joints, dry friction and
  *      fewer motors than dofs). */
+/*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
+ *      device-resident particle filter's, mjmpc_tree_set_batch_models and mjmpc_tree_set_env_model.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -271,7 +273,8 @@ int mjmpc_tree_get_state(mjmpc_tree_t h, double* qpos, double* qvel, void* strea
 /* Episode batches: E independent closed-loop MPC episodes side by side (the reference runs them one after another,
  * examples/job_script.py:80-99 and the episode loop of examples/example_mpc.py).  The engine's E = n_state_shards start
  * states (mjmpc_tree_set_shard_states, 1 <= E <= 65535) are the batch's E real envs; the engine must hold one model block
- * (MJMPC_E_BADARG after mjmpc_tree_set_shard_models with more than one).
+ * (MJMPC_E_BADARG after mjmpc_tree_set_shard_models with more than one; a batch's per-shard models go through
+ * mjmpc_tree_set_batch_models below).
  * mjmpc_tree_rollout_fused_batch: mjmpc_tree_rollout_fused (rollout, gym_env_wrapper.py:125-153) with one mean per state
  * shard - d_means float64 [E][H][nu]; particles [e P_total / E, (e + 1) P_total / E) start from state shard e and follow
  * mean e; P_total % E == 0.  Each episode's particles compute the bits a single-state engine computes for them. */
@@ -282,6 +285,23 @@ int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, i
  * shard, bit for bit, resets counted as there): d_actions float64 [E][nu], d_costs dtype [E], d_next_obs dtype [E][d_obs]
  * or NULL; every state shard is advanced in place. */
 int mjmpc_tree_step_shard_states(mjmpc_tree_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream);
+/* Dynamics-randomized episode batches (the reference's example_mpc.py --dyn_randomize_config, whose randomized sim_env
+ * only does rollouts while the true env stays nominal): n_sets * K model blocks [n_sets][K][MJMPC_TREE_BLOB_LEN] of the
+ * engine's topology and kernel instantiation (as mjmpc_tree_set_shard_models checks them), kept apart from the engine's own
+ * block, with their reset records.  From then on mjmpc_tree_rollout_fused_batch runs E * K rows: row (e, k) holds the
+ * particles [(e K + k) P_total / (E K), (e K + k + 1) P_total / (E K)), starts from state shard e, follows mean e and
+ * simulates block [set(e)][k], set(e) = 0 with n_sets = 1 (every episode the same K blocks) and e with n_sets = E = the
+ * number of state shards (MJMPC_E_BADARG for any other n_sets); P_total % (E K) == 0, K <= 65535.  Each row computes the bits
+ * shard k of a single-state engine with these K blocks (mjmpc_tree_set_shard_models) computes for its particles.
+ * mjmpc_tree_step_shard_states keeps stepping the E real envs with the engine's own block.  n_sets = 0 (model_blobs and K
+ * ignored) drops the stored blocks: the batch rolls out the engine's own block again.  Synchronises the device. */
+int mjmpc_tree_set_batch_models(mjmpc_tree_t h, const double* model_blobs, int n_sets, int K);
+/* The model of the device-resident real env: with a block (MJMPC_TREE_BLOB_LEN scalars, checked as above)
+ * mjmpc_tree_step_state steps the engine's state with it and its own reset record instead of shard 0's block - after
+ * mjmpc_tree_set_shard_models the reference's pairing of a randomized sim_env with a nominal true env; an env step captured
+ * in a hipGraph AFTER this call does the same (one captured before keeps the block it was captured with, which stays
+ * allocated).  NULL restores the default, shard 0's block.  Rollouts are not affected. */
+int mjmpc_tree_set_env_model(mjmpc_tree_t h, const double* model_blob);
 /* The E state shards read back in MuJoCo's layout (quaternions included): qpos [E][nq], qvel [E][nv] (host; synchronises
  * the stream), as mjmpc_tree_get_state for the single state. */
 int mjmpc_tree_get_shard_states(mjmpc_tree_t h, double* qpos, double* qvel, void* stream);

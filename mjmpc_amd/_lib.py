@@ -55,6 +55,8 @@ SIGNATURES = {
     "mjmpc_tree_rollout_fused_batch": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_step_shard_states": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_get_shard_states": (_int, [_vp, _dp, _dp, _vp]),
+    "mjmpc_tree_set_batch_models": (_int, [_vp, _dp, _int, _int]),
+    "mjmpc_tree_set_env_model": (_int, [_vp, _dp]),
     "mjmpc_tree_solver_failures": (_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mjmpc_tree_diverged": (_int, [_vp, ctypes.POINTER(ctypes.c_uint32)]),
     "mjmpc_analytic_rollout": (_int, [_int, _vp, _int, _int, _vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _int,

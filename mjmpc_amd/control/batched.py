@@ -17,7 +17,8 @@ seed=seeds[e])`` on a ``TreeRolloutEngine`` of its own, ``make_device_rollout_fn
     batch.set_states(start_states)                  # one state dict per episode
     actions, costs, next_obs = batch.run(100)       # [T][E][A], [T][E], [T][E][d_obs]
 
-Per episode: seed, start state (with ``target_pos``), initial mean, ``lam``, ``step_size`` and ``init_cov``.  Shared by
+Per episode: seed, start state (with ``target_pos``), initial mean, ``lam``, ``step_size`` and ``init_cov`` - and, after
+``randomize_dynamics``, the model blocks its particle shards roll out (shared by the episodes, or a set per episode).  Shared by
 the batch: the model, ``horizon``, ``num_particles`` (per episode), ``gamma``, ``filter_coeffs``, ``base_action`` and
 the dtype.  The batch's E real envs are the state shards of the batch's own engine (``mjmpc_tree_step_shard_states``).
 """
@@ -96,6 +97,7 @@ class BatchedMPPI:
             raise ValueError("seeds must hold one seed per episode (%d)" % E)
         self.seed_vals = [_seed_value(int(s) if isinstance(s, (np.integer,)) else s) for s in seeds]
         from ..models.compile_tree import TreeModel, compile_tree
+        from ..models.raw import RawModel
         try:
             model = raw_model if isinstance(raw_model, TreeModel) else compile_tree(raw_model)
         except (ValueError, NotImplementedError, TypeError, AttributeError) as e:
@@ -114,6 +116,8 @@ class BatchedMPPI:
         self.engine = TreeRolloutEngine(model, device=device, dtype=dtype)
         self.lib = self.engine._lib
         self.model = model
+        self.raw = raw_model if isinstance(raw_model, RawModel) else None
+        self.shard_blobs = None         # randomize_dynamics: the model blocks of the rollouts, [sets][num_shards][blob length]
         self.num_episodes, self.horizon, self.num_particles, self.d_action = E, H, P, A
         self.d_obs, self.dtype = model.d_obs, dtype
         self.forward_task = self.engine.forward_task
@@ -184,6 +188,48 @@ class BatchedMPPI:
         self._means.copy_(self.torch.from_numpy(self.init_mean))
         self._step_dev.zero_()
         self.num_steps = 0
+
+    # ------------------------------------------------------------------ dynamics randomization
+    def randomize_dynamics(self, param_dict, base_seed, num_shards):
+        """``SubprocVecEnv.randomize_dynamics`` for every episode of the batch (the reference's ``example_mpc.py
+        --dyn_randomize_config``): each episode's particles are split into ``num_shards`` shards of consecutive particles
+        and shard i rolls out its own model block, while the E real envs keep the nominal model (the reference's randomized
+        ``sim_env`` only does rollouts).  ``base_seed``: one int - every episode's shard i draws from
+        ``np_random(base_seed + i*12345)``, one shared set of blocks, as the reference randomizes once before its episode
+        loop - or one int per episode: episode e's shard i draws from ``np_random(base_seed[e] + i*12345)``.  Episode e then
+        computes the bits of the single-episode path on ``TreeRolloutEngine(raw, num_shards=num_shards)`` after
+        ``randomize_dynamics(param_dict, base_seed[e])`` and ``set_real_env_model('nominal')``.  Every call draws from the
+        nominal model, as on a fresh engine.  Returns ``(default_params, randomized_params)``, one dict per shard - as a list
+        per episode with per-episode seeds.  Raises ``ValueError`` before anything reaches the device."""
+        from ..envs._engine import draw_shard_models
+        from ..envs.tree_engine import TreeRolloutEngine
+        E, K = self.num_episodes, int(num_shards)
+        if not 1 <= K <= 65535 or self.num_particles % K != 0:
+            raise ValueError("num_particles (%d) must divide into num_shards (%d) shards, 1 .. 65535" % (self.num_particles, K))
+        if self.raw is None:
+            raise ValueError("randomize_dynamics needs the batch to be built from a RawModel")
+        per_episode = isinstance(base_seed, (list, tuple, np.ndarray))
+        if per_episode and len(base_seed) != E:
+            raise ValueError("base_seed takes one int or one per episode (%d), got %d" % (E, len(base_seed)))
+        host = TreeRolloutEngine.host_only(self.raw, self.model)
+        defaults, rand, blobs = [], [], []
+        for seed in (base_seed if per_episode else [base_seed]):
+            d, r = [dict() for _ in range(K)], [dict() for _ in range(K)]
+            try:
+                blobs.append(draw_shard_models(host, param_dict, [int(seed) + i * 12345 for i in range(K)], d, r))
+            except (StopIteration, KeyError, IndexError) as e:
+                raise ValueError("the model has no such dynamics parameter: %r" % (e,)) from e
+            defaults.append(d)
+            rand.append(r)
+        blobs = np.ascontiguousarray(np.stack(blobs), np.float64)
+        _lib.check(self.lib.mjmpc_tree_set_batch_models(self.engine._h, blobs.ctypes.data_as(_lib._dp), len(blobs), K))
+        self.shard_blobs = blobs
+        return (defaults, rand) if per_episode else (defaults[0], rand[0])
+
+    def clear_dynamics(self):
+        """Back to the one nominal model block for every rollout."""
+        _lib.check(self.lib.mjmpc_tree_set_batch_models(self.engine._h, None, 0, 0))
+        self.shard_blobs = None
 
     # ------------------------------------------------------------------ control steps
     def step(self, _out=None):

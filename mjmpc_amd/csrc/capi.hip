@@ -357,6 +357,19 @@ struct mjmpc_tree_s : engine_core {
     int integrator = MJMPC_INTEGRATOR_EULER;    // mjmpc_tree_create_ex: every launch (the reset records' too) steps with it
     double* zero_action = nullptr;  // [32] zeros (the kinematics-only launch of mjmpc_tree_rollout_cl)
     double* scratch = nullptr;      // [8] a place for that launch's cost
+    // mjmpc_tree_set_batch_models: batch_sets * batch_k model blocks for the episode batches' rollouts, apart from the engine's
+    // own (which keep stepping the batch's real envs), with their reset records and their kernel choice
+    float* batch_f32 = nullptr;
+    double* batch_f64 = nullptr;
+    double* batch_rec = nullptr;
+    int batch_sets = 0, batch_k = 0;
+    bool batch_full = false;
+    // mjmpc_tree_set_env_model: the block the device-resident real env steps with instead of shard 0's (null: shard 0's)
+    float* env_f32 = nullptr;
+    double* env_f64 = nullptr;
+    double* env_rec = nullptr;
+    bool env_full = false;
+    std::vector<void*> env_retired; // replaced env blocks / records: a captured env step carries the pointers by value
 };
 
 // MuJoCo's layout (qpos[nq], qvel[nv], target[3]) -> the device state vector: one coordinate per LINK, a ball joint's
@@ -418,6 +431,41 @@ static bool tree_same_topology(const double* a, const double* b) {
            same(mjmpc::T_N_ROUNDS, 1) && same(mjmpc::T_ELIM, (mjmpc::TL - 1) * mjmpc::TL) && same(mjmpc::T_NV, 1) &&
            same(mjmpc::T_NU, 1) && same(mjmpc::T_TASK, 1) && same(mjmpc::T_OBS_SKIP, 1) && same(mjmpc::T_JUMPS, 1) &&
            same(mjmpc::T_NQ, 1) && same(mjmpc::T_QADR, mjmpc::TL) && same(mjmpc::T_HAS_BALL, 1) && same(mjmpc::T_QW0, mjmpc::TL);
+}
+
+// what a set of model blocks must pass before it replaces or joins the engine's (mjmpc_tree_set_shard_models, _set_batch_models,
+// _set_env_model): the engine's topology and dimensions, its kernel instantiation; *full = the kernel choice of the set
+static int tree_check_blocks(const mjmpc_tree_s* h, const double* blobs, int n, bool* full, const char* what) {
+    *full = false;
+    for (int s = 0; s < n; ++s) {
+        const double* b = blobs + (size_t)s * mjmpc::TREE_BLOB_LEN;
+        if ((int)b[mjmpc::T_N_SPHERE] > mjmpc::TREE_MAX_SPHERES || !tree_same_topology(b, h->topo.data()))
+            return fail(MJMPC_E_BADMODEL, "%s %d does not have the engine's topology / dimensions", what, s);
+        *full = *full || tree_blob_is_full(b, h->nv);
+        if ((int)b[mjmpc::T_GEN] != h->gen)
+            return fail(MJMPC_E_BADMODEL, "%s %d needs a different kernel instantiation than the engine's model", what, s);
+    }
+    return 0;
+}
+
+// n model blocks (host) -> device copies in both precisions
+static int tree_upload_blocks(const double* blobs, int n, float** m32_out, double** m64_out) {
+    const size_t len = (size_t)n * mjmpc::TREE_BLOB_LEN;
+    std::vector<float> f32(blobs, blobs + len);
+    float* m32 = nullptr;
+    double* m64 = nullptr;
+    HIP_TRY(hipMalloc(&m32, sizeof(float) * len));
+    hipError_t e = hipMalloc(&m64, sizeof(double) * len);
+    if (e == hipSuccess) e = hipMemcpy(m32, f32.data(), sizeof(float) * len, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(m64, blobs, sizeof(double) * len, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        hipFree(m32);
+        hipFree(m64);
+        return hip_fail(e, "model block upload");
+    }
+    *m32_out = m32;
+    *m64_out = m64;
+    return 0;
 }
 
 // what every rollout launch of the engine carries besides its own fusions: the reset records (one per model shard; shard >= 0:
@@ -941,18 +989,74 @@ int mjmpc_tree_set_shard_models(mjmpc_tree_t h, const double* blobs, int n_shard
         return fail(MJMPC_E_BADARG, "%d model shards but %d per-shard start states", n_shards, h->n_state_shards);
     HIP_TRY(hipSetDevice(h->device));
     bool full = false;
-    for (int s = 0; s < n_shards; ++s) {
-        const double* b = blobs + (size_t)s * mjmpc::TREE_BLOB_LEN;
-        if ((int)b[mjmpc::T_N_SPHERE] > mjmpc::TREE_MAX_SPHERES || !tree_same_topology(b, h->topo.data()))
-            return fail(MJMPC_E_BADMODEL, "shard %d does not have the engine's topology / dimensions", s);
-        full = full || tree_blob_is_full(b, h->nv);
-        if ((int)b[mjmpc::T_GEN] != h->gen)
-            return fail(MJMPC_E_BADMODEL, "shard %d needs a different kernel instantiation than the engine's model", s);
-    }
+    if (int rc = tree_check_blocks(h, blobs, n_shards, &full, "shard")) return rc;
     const int rc = core_swap_models(h, blobs, n_shards, mjmpc::TREE_BLOB_LEN,
                                     [&](double** rec) { return tree_make_reset_records(h, blobs, n_shards, full, rec); });
     if (rc == 0) h->full = full;    // of the NEW set of blocks (they replace the old ones)
     return rc;
+}
+
+int mjmpc_tree_set_batch_models(mjmpc_tree_t h, const double* blobs, int n_sets, int K) {
+    if (n_sets < 0) return fail(MJMPC_E_BADARG, "n_sets = %d is negative", n_sets);
+    if (n_sets > 0 && K < 1) return fail(MJMPC_E_BADARG, "K = %d model shards per episode", K);
+    if (n_sets > 0 && !blobs) return fail(MJMPC_E_BADARG, "null model blocks");
+    if (!h) return fail(MJMPC_E_BADARG, "null engine");
+    HIP_TRY(hipSetDevice(h->device));
+    float* m32 = nullptr;
+    double *m64 = nullptr, *rec = nullptr;
+    bool full = false;
+    if (n_sets > 0) {
+        if (n_sets != 1 && n_sets != h->n_state_shards)
+            return fail(MJMPC_E_BADARG, "%d sets of model blocks: one for every episode, or one per state shard (%d)", n_sets,
+                        h->n_state_shards);
+        if (K > 65535 || (int64_t)n_sets * K > (1 << 20))
+            return fail(MJMPC_E_BADARG, "%d sets of %d model shards are more than a batch launch takes", n_sets, K);
+        const int n = n_sets * K;
+        if (int rc = tree_check_blocks(h, blobs, n, &full, "batch block")) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        if (int rc = tree_upload_blocks(blobs, n, &m32, &m64)) return rc;
+        if (int rc = tree_make_reset_records(h, blobs, n, full, &rec)) {
+            hipFree(m32);
+            hipFree(m64);
+            return rc;
+        }
+    }
+    HIP_TRY(hipDeviceSynchronize());        // (no launch that reads the old blocks is still running)
+    hipFree(h->batch_f32);
+    hipFree(h->batch_f64);
+    hipFree(h->batch_rec);
+    h->batch_f32 = m32;
+    h->batch_f64 = m64;
+    h->batch_rec = rec;
+    h->batch_sets = n_sets;
+    h->batch_k = n_sets > 0 ? K : 0;
+    h->batch_full = full;
+    return 0;
+}
+
+int mjmpc_tree_set_env_model(mjmpc_tree_t h, const double* blob) {
+    if (!h) return fail(MJMPC_E_BADARG, "null engine");
+    HIP_TRY(hipSetDevice(h->device));
+    float* m32 = nullptr;
+    double *m64 = nullptr, *rec = nullptr;
+    bool full = false;
+    if (blob) {
+        if (int rc = tree_check_blocks(h, blob, 1, &full, "env block")) return rc;
+        HIP_TRY(hipDeviceSynchronize());
+        if (int rc = tree_upload_blocks(blob, 1, &m32, &m64)) return rc;
+        if (int rc = tree_make_reset_records(h, blob, 1, full, &rec)) {
+            hipFree(m32);
+            hipFree(m64);
+            return rc;
+        }
+    }
+    for (void* p : {(void*)h->env_f32, (void*)h->env_f64, (void*)h->env_rec})
+        if (p) h->env_retired.push_back(p);     // (env steps captured earlier still point at them)
+    h->env_f32 = m32;
+    h->env_f64 = m64;
+    h->env_rec = rec;
+    h->env_full = full;
+    return 0;
 }
 
 int mjmpc_tree_set_shard_states(mjmpc_tree_t h, const double* states, int n_shards, void* stream) {
@@ -975,6 +1079,10 @@ int mjmpc_tree_destroy(mjmpc_tree_t h) {
     if (!h) return 0;
     core_free(h);
     hipFree(h->zero_action);
+    for (void* p : {(void*)h->batch_f32, (void*)h->batch_f64, (void*)h->batch_rec, (void*)h->env_f32, (void*)h->env_f64,
+                    (void*)h->env_rec})
+        hipFree(p);
+    for (void* p : h->env_retired) hipFree(p);
     delete h;
     return 0;
 }
@@ -1058,6 +1166,13 @@ int mjmpc_tree_step_state(mjmpc_tree_t h, int dtype, const double* d_action, voi
     c.cost = d_cost;
     c.nobs = d_next_obs;
     c.state_out = h->state;
+    if (h->env_f64) {       // mjmpc_tree_set_env_model: the real env's own block and reset record
+        c.other_model = dtype == MJMPC_F32 ? (const void*)h->env_f32 : (const void*)h->env_f64;
+        c.other_full = h->env_full;
+        c.other_diag = h->diag;
+        c.fuse.reset_rec = h->env_rec;
+        c.fuse.reset_stride = 0;
+    }
     return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_step_state launch");
 }
 
@@ -1095,6 +1210,21 @@ int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, i
     c.fuse.gseq = d_gseq;
     c.fuse.q0_out = d_q0;
     c.fuse.mean_stride = (long)H * h->nu;       // episode e's mean: d_means + e H A
+    c.fuse.batch_k = 1;
+    if (h->batch_sets > 0) {        // mjmpc_tree_set_batch_models: row (e, k) runs block set(e) K + k of the stored blocks
+        const int K = h->batch_k;
+        if (h->batch_sets != 1 && h->batch_sets != E)
+            return fail(MJMPC_E_BADARG, "%d sets of batch model blocks but %d state shards", h->batch_sets, E);
+        if (P_total % ((int64_t)E * K) != 0)
+            return fail(MJMPC_E_BADARG, "%lld particles do not divide into %d episodes of %d model shards", (long long)P_total, E, K);
+        c.other_model = dtype == MJMPC_F32 ? (const void*)h->batch_f32 : (const void*)h->batch_f64;
+        c.other_full = h->batch_full;
+        c.other_diag = h->diag;
+        c.n_model_shards = h->batch_sets * K;
+        c.fuse.reset_rec = h->batch_rec;
+        c.fuse.reset_stride = c.n_model_shards > 1 ? mjmpc::TREE_RESET_LEN : 0;
+        c.fuse.batch_k = K;
+    }
     return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_rollout_fused_batch launch");
 }
 

@@ -16,7 +16,8 @@ namespace mjmpc {
 // 5's record kinds on top (a cylinder on the plane, capsule / box and box / box pairs, mjc_PlaneBox's corner rule);
 // mean f64 [H][A]; noise / cost / act / obs / nobs of T in the reference's C-order layouts (may be null except cost).
 // n_state_shards > 1: `state` holds one TREE_STATE_LEN vector per shard (per-worker start states); with both kinds of
-// shards their counts must agree.
+// shards their counts must agree - except in an episode batch (fuse.batch_k > 0), where n_model_shards is batch_k or
+// n_state_shards * batch_k, P % (n_state_shards * batch_k) == 0 and both counts are at most 65535 (a grid axis each).
 // Fusions riding in the rollout launch (as RolloutFusion of the arm kernel): the reference's recursive noise filter applied
 // to the raw samples on the fly (control_utils.py:32-33; filt = three float64 coefficients), and the discounted cost-to-go
 // of every particle, q0_out[p] = sum_t gseq[t] * cost[p][t] (control_utils.py:37-46 at t = 0; +inf for a diverged rollout).
@@ -36,10 +37,17 @@ struct TreeFusion {
     int reset_stride = 0;
     double* axis_out = nullptr;
     int inf_on_reset = 0;           // 1: a particle that has reset costs +inf from that env step on (RolloutFusion::inf_on_reset)
-    // episode batches: row blockIdx.y reads its mean at mean + blockIdx.y * mean_stride (0: one mean for every
-    // row), and a launch of one particle per row writes that row's end state to state_out + blockIdx.y * state_out_stride
+    // episode batches: episode blockIdx.z reads its mean at mean + blockIdx.z * mean_stride (0: one mean for every
+    // row), and a launch of one particle per episode writes its end state to state_out + blockIdx.z * state_out_stride
     long mean_stride = 0;
     int state_out_stride = 0;
+    // dynamics-randomized episode batches: batch_k > 0 asks for the (workgroups, K, E) grid - E = n_state_shards
+    // episodes (blockIdx.z) of K = batch_k model shards (blockIdx.y); row (e, k) holds P / (E K) consecutive particles, reads
+    // state e and mean e, and model block set(e) K + k with its reset record.  `model` holds K blocks (one set for every
+    // episode) or E K (a set per episode): launch_tree_rollout derives the two set strides below from n_model_shards.
+    int batch_k = 0;
+    long model_set_stride = 0;      // scalars of T between two episodes' sets of blocks (0: one shared set)
+    int reset_set_stride = 0;       // ... and between their reset records
 };
 // integrator: 0 MuJoCo's Euler, 1 RK4 (mj_RungeKutta, four stages per substep: tree_rollout_rk4.hip - models of up to 16 dofs
 // without elliptic cones; hipErrorInvalidValue otherwise).  Under RK4 the iteration-cap hits and the counts of non-finite

@@ -1620,8 +1620,12 @@ constexpr int min_waves(int scalar_bytes, int DP, bool fric) {
 // is the earlier rounds' to the instruction.
 // RK4 = 1: MuJoCo's mj_RungeKutta instead of mj_Euler - stages 1-6 run four times per substep (tree_rollout_rk4.hip, DESIGN
 // 4.6.3); the 16-lane dense instantiations only.  RK4 = 0 compiles to the Euler kernel it was.
-// EB = 1: an episode batch - row blockIdx.y reads its own mean (fuse.mean_stride) and, one particle per row,
-// writes its end state to its own state vector (fuse.state_out_stride).  EB = 0 compiles to the kernel it was.
+// EB = 1: an episode batch - the grid is (workgroups, K model shards, E episodes): row (e, k) =
+// (blockIdx.z, blockIdx.y) holds the particles [(e K + k) shard_size, (e K + k + 1) shard_size), starts from state e, follows
+// mean e (fuse.mean_stride) and simulates model block set(e) K + k with that block's reset record (set(e) = e when every
+// episode has its own set of K blocks - fuse.model_set_stride / reset_set_stride - else 0); one particle per episode (K = 1)
+// writes its end state to its own state vector (fuse.state_out_stride).  All of it is wavefront-uniform (workgroup ids and
+// kernel arguments).  EB = 0 compiles to the kernel it was.
 template <typename T, int DP, int NS, bool FRIC, int PL, int DN, int GEN = 0, int RK4 = 0, int EB = 0>
 __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(sizeof(T), DP, FRIC)) void tree_rollout_kernel(
     const T* __restrict__ model_all, int model_stride, const double* __restrict__ state, int state_stride, long P, long shard_size, int H,
@@ -1651,9 +1655,11 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
     // gridDim.y shards of shard_size consecutive particles (the reference's workers); a workgroup never straddles two.
     // Dynamics randomization (SubprocVecEnv.randomize_dynamics) gives each its own model block (model_stride != 0),
     // a per-worker set_env_state (subproc_vec_env.py:242-251) its own start state (state_stride != 0).
-    const T* model = model_all + (long)blockIdx.y * model_stride;
-    state += (long)blockIdx.y * state_stride;
-    if constexpr (EB) mean += (long)blockIdx.y * fuse.mean_stride;      // (episode batches: one mean per row)
+    // (an episode batch: the episode on blockIdx.z, its model shard on blockIdx.y)
+    const T* model = EB ? model_all + (long)blockIdx.y * model_stride + (long)blockIdx.z * fuse.model_set_stride
+                        : model_all + (long)blockIdx.y * model_stride;
+    state += (long)(EB ? blockIdx.z : blockIdx.y) * state_stride;
+    if constexpr (EB) mean += (long)blockIdx.z * fuse.mean_stride;      // (episode batches: one mean per episode)
     T* M = lds;
     for (int k = threadIdx.x; k < NBLOB; k += blockDim.x) M[k] = model[k];
     for (int k = threadIdx.x; k < (PL - 1) * PL; k += blockDim.x) ELIM[k] = (int)model[T_ELIM + (k / PL) * TL + (k % PL)];
@@ -1671,7 +1677,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l = lane & (PL - 1), half = lane / PL;        // `half`: which particle of the wavefront (0 .. PPW - 1)
     const long in_shard = ((long)blockIdx.x * WG_WAVES + wave) * PPW + half;
-    const long pid = (long)blockIdx.y * shard_size + in_shard;
+    const long pid = (EB ? (long)blockIdx.z * fuse.batch_k + blockIdx.y : (long)blockIdx.y) * shard_size + in_shard;
     const bool live = in_shard < shard_size && pid < P;
     T* X = lds + NBLOB + 1 + (wave * PPW + half) * A_LEN;
     T* ROW = X + A_ROW;
@@ -1815,7 +1821,9 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
 #ifdef MJMPC_NO_RESET         // developer A/B: the reset emulation compiled out (tools/ab_build.py)
     const double* rst = nullptr;
 #else
-    const double* rst = fuse.reset_rec ? fuse.reset_rec + (long)blockIdx.y * fuse.reset_stride : nullptr;
+    const double* rst = fuse.reset_rec ? fuse.reset_rec + (long)blockIdx.y * fuse.reset_stride +
+                                             (EB ? (long)blockIdx.z * fuse.reset_set_stride : 0l)
+                                       : nullptr;
 #endif
     const unsigned long long my_lanes = (PL == 32 ? 0xFFFFFFFFull : 0xFFFFull) << (PL * half);
     const T MJ_MAXVAL = T(1e10);
@@ -3709,7 +3717,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
     // reads it (the launch has one particle; `state` was read before the first step).  An episode batch
     // (mjmpc_tree_step_shard_states) has one particle per row, and each row its own state vector.
     if (state_out && (EB ? in_shard == 0 : pid == 0) && dof) {
-        if constexpr (EB) state_out += (long)blockIdx.y * fuse.state_out_stride;
+        if constexpr (EB) state_out += (long)blockIdx.z * fuse.state_out_stride;
         if (!GEN || ball_g <= 0) state_out[l] = (double)q;         // (a ball's first link owns its followers' qpos entries)
         if (GEN && ball_g == 0) {
             state_out[l + 1] = (double)qy;
@@ -3727,6 +3735,7 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
 // one-wave-per-SIMD kernels and not for the others (mjmpc_amd/build.py).
 struct TreeLaunchArgs {
     int model_stride, state_stride, n_shards, H, A;
+    int n_episodes = 1;             // grid z: the episodes of a batch launch (EB = 1; n_shards is then the model shards per episode)
     long P, shard;
     const double *state, *mean, *clw;
     unsigned* diag;
@@ -3753,7 +3762,8 @@ hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model
     {                                                                                                                 \
         constexpr int per_wg = wg_waves(DP_, FR_, sizeof(T), PL_) * (64 / PL_);                                       \
         hipLaunchKernelGGL((tree_rollout_kernel<T, DP_, NS_, FR_, PL_, DN_, GEN_, 0, EB>),                            \
-                           dim3((unsigned)((a.shard + per_wg - 1) / per_wg), (unsigned)a.n_shards),                   \
+                           dim3((unsigned)((a.shard + per_wg - 1) / per_wg), (unsigned)a.n_shards,                    \
+                                (unsigned)a.n_episodes),                                                              \
                            dim3(64 * wg_waves(DP_, FR_, sizeof(T), PL_)), 0, a.stream, model, a.model_stride, a.state, \
                            a.state_stride, a.P, a.shard, a.H, a.A, a.mean, noise, cost, act, obs, nobs, a.diag,       \
                            a.state_out, a.clw, a.site_out, a.fuse);                                                   \
@@ -3841,7 +3851,8 @@ hipError_t launch_tree_rollout_rk4(int max_path, int nv, int gen, const T* model
     {                                                                                                                 \
         constexpr int per_wg = wg_waves(DP_, true, sizeof(T), 16) * 4;                                               \
         hipLaunchKernelGGL((tree_rollout_kernel<T, DP_, 16, true, 16, DN_, GEN_, 1, EB>),                             \
-                           dim3((unsigned)((a.shard + per_wg - 1) / per_wg), (unsigned)a.n_shards),                   \
+                           dim3((unsigned)((a.shard + per_wg - 1) / per_wg), (unsigned)a.n_shards,                    \
+                                (unsigned)a.n_episodes),                                                              \
                            dim3(64 * wg_waves(DP_, true, sizeof(T), 16)), 0, a.stream, model, a.model_stride, a.state, \
                            a.state_stride, a.P, a.shard, a.H, a.A, a.mean, noise, cost, act, obs, nobs, a.diag,       \
                            a.state_out, a.clw, a.site_out, a.fuse);                                                   \
@@ -3913,16 +3924,33 @@ hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path,
     if (gen && !full) return hipErrorInvalidValue;
     // (state_out with more than one particle: the real-env step of an episode batch, one particle per state shard)
     const bool batch_step = state_out && !site_out && fuse.state_out_stride == TREE_STATE_LEN && n_model_shards == 1 &&
-                            P == n_state_shards;
+                            P == n_state_shards && fuse.batch_k <= 1;
     if ((state_out || site_out) && P != 1 && !batch_step) return hipErrorInvalidValue;
     if (fuse.state_out_stride != 0 && !batch_step) return hipErrorInvalidValue;
     if (n_model_shards < 1 || n_state_shards < 1) return hipErrorInvalidValue;
-    if (n_model_shards > 1 && n_state_shards > 1 && n_model_shards != n_state_shards) return hipErrorInvalidValue;
+    // an episode batch (one mean per episode, or one real env per episode) runs the EB = 1 twin of the model's instantiation
+    // on a (workgroups, K, E) grid: K model shards per episode, K or E K model blocks
+    const bool eb = fuse.mean_stride != 0 || fuse.state_out_stride != 0 || fuse.batch_k > 0;
     TreeLaunchArgs a;
-    a.n_shards = n_model_shards > n_state_shards ? n_model_shards : n_state_shards;
-    if (P % a.n_shards != 0) return hipErrorInvalidValue;
+    if (eb) {
+        const int E = n_state_shards, K = fuse.batch_k > 0 ? fuse.batch_k : 1;
+        if (fuse.batch_k < 0 || E > 65535 || K > 65535) return hipErrorInvalidValue;
+        if (n_model_shards != K && (long)n_model_shards != (long)E * K) return hipErrorInvalidValue;
+        if (P % ((long)E * K) != 0) return hipErrorInvalidValue;
+        a.n_shards = K;
+        a.n_episodes = E;
+        a.shard = P / ((long)E * K);
+        fuse.batch_k = K;
+        const bool own_sets = E > 1 && (long)n_model_shards == (long)E * K;
+        fuse.model_set_stride = own_sets ? (long)K * TREE_BLOB_LEN : 0;
+        fuse.reset_set_stride = own_sets ? K * fuse.reset_stride : 0;
+    } else {
+        if (n_model_shards > 1 && n_state_shards > 1 && n_model_shards != n_state_shards) return hipErrorInvalidValue;
+        a.n_shards = n_model_shards > n_state_shards ? n_model_shards : n_state_shards;
+        if (P % a.n_shards != 0) return hipErrorInvalidValue;
+        a.shard = P / a.n_shards;
+    }
     a.P = P;
-    a.shard = P / a.n_shards;
     a.H = H;
     a.A = A;
     a.model_stride = n_model_shards > 1 ? TREE_BLOB_LEN : 0;
@@ -3935,8 +3963,7 @@ hipError_t launch_tree_rollout(const T* model, int n_model_shards, int max_path,
     a.site_out = site_out;
     a.stream = stream;
     a.fuse = fuse;
-    // an episode batch (one mean per row, or one real env per row) runs the EB = 1 twin of the model's instantiation
-    if (fuse.mean_stride != 0 || fuse.state_out_stride != 0)
+    if (eb)
         return launch_tree_rows<T, 1>(max_path, full, nv, gen, integrator, model, noise, cost, act, obs, nobs, a);
     return launch_tree_rows<T, 0>(max_path, full, nv, gen, integrator, model, noise, cost, act, obs, nobs, a);
 }

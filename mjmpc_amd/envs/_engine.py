@@ -36,6 +36,27 @@ def _same_state(a, b):
     return all(np.array_equal(np.asarray(a[k]), np.asarray(b[k])) for k in ("qp", "qv", "target_pos"))
 
 
+def draw_shard_models(host, param_dict, seeds, defaults, rand):
+    """The draws and model blocks of ``randomize_dynamics``: shard i draws from ``np_random(seeds[i])`` a uniform value in
+    ``m (1 +- noise)``, ``m = (1 + bias) * default``, for every ``{param_id: {name: [noise_scale, bias_scale]}}`` entry
+    (gym_env_wrapper.py:367-416), in the order of ``param_dict``; ``defaults[i]`` / ``rand[i]`` (dicts, filled in place)
+    receive its default and randomized values, and ``host`` (an engine, or ``RolloutEngine.host_only``) compiles its block.
+    Returns the blocks, float64 ``[len(seeds), blob length]``.  Host only: nothing here touches the device."""
+    blobs = []
+    for i, seed in enumerate(seeds):
+        rng, _ = np_random(int(seed))
+        d, r = defaults[i], rand[i]
+        for param_id, entries in param_dict.items():
+            for name, (noise_scale, bias_scale) in entries.items():
+                cur = d.setdefault(param_id, {}).get(name)
+                if cur is None:
+                    cur = d[param_id][name] = host._default_param(param_id, name)
+                mean = (1.0 + bias_scale) * np.asarray(cur, float)
+                r.setdefault(param_id, {})[name] = rng.uniform(mean - mean * noise_scale, mean + mean * noise_scale)
+        blobs.append(host._compile(host.raw, overrides=host._overrides(r), base=host.model).blob)
+    return np.ascontiguousarray(np.stack(blobs), np.float64)
+
+
 class RolloutEngine(EnvResetWatch):
     """One GPU's worth of particles for a compiled model.  Subclasses set ``_abi``, ``_model_type``, ``_compile``,
     ``_layout``, ``_qpos_len`` and define ``_create``, ``_unpack``, ``_start_qpos``, ``_default_geom_friction`` and
@@ -171,22 +192,20 @@ class RolloutEngine(EnvResetWatch):
         Returns (default_params, randomized_params), one dict per shard."""
         if self.raw is None:
             raise ValueError("randomize_dynamics needs the engine to be built from a RawModel")
-        blobs = []
-        for i in range(self.num_shards):
-            rng, _ = np_random(int(base_seed) + i * 12345)
-            defaults, rand = self.default_dyn_params[i], self.randomized_dyn_params[i]
-            for param_id, entries in param_dict.items():
-                for name, (noise_scale, bias_scale) in entries.items():
-                    cur = defaults.setdefault(param_id, {}).get(name)
-                    if cur is None:
-                        cur = defaults[param_id][name] = self._default_param(param_id, name)
-                    mean = (1.0 + bias_scale) * np.asarray(cur, float)
-                    rand.setdefault(param_id, {})[name] = rng.uniform(mean - mean * noise_scale, mean + mean * noise_scale)
-            blobs.append(self._compile(self.raw, overrides=self._overrides(rand), base=self.model).blob)
-        blobs = np.ascontiguousarray(np.stack(blobs), np.float64)
+        seeds = [int(base_seed) + i * 12345 for i in range(self.num_shards)]
+        blobs = draw_shard_models(self, param_dict, seeds, self.default_dyn_params, self.randomized_dyn_params)
         _lib.check(self._fn("set_shard_models")(self._h, blobs.ctypes.data_as(_lib._dp), self.num_shards))
         self.shard_blobs = blobs
         return self.default_dyn_params, self.randomized_dyn_params
+
+    @classmethod
+    def host_only(cls, raw, model=None):
+        """The model-side half of an engine without a device: ``raw``, ``model``, the model compiler and the
+        dynamics-randomization defaults (``draw_shard_models``) - what an episode batch draws its model blocks with."""
+        self = cls.__new__(cls)
+        self.raw, self.model = raw, cls._compile(raw) if model is None else model
+        self.closed = True
+        return self
 
     def _overrides(self, rand):
         """What of a shard's randomized parameters reaches the model compiler."""

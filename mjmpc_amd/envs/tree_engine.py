@@ -69,6 +69,25 @@ class TreeRolloutEngine(RolloutEngine):
         self.set_env_state(dict(qp=nobs[0, 0, :nq], qv=nobs[0, 0, nq:nq + nv], target_pos=self._state["target_pos"]))
         return nobs[0, 0].copy(), float(rew[0, 0])
 
+    def set_real_env_model(self, model):
+        """The model ``step_state`` - the device-resident real env, also inside a captured control iteration - steps with:
+        a ``RawModel`` / compiled ``TreeModel`` of the engine's topology, ``"nominal"`` for the model the engine was built
+        from (the reference's pairing after ``randomize_dynamics``: a randomized ``sim_env`` that only does rollouts beside
+        a nominal true env, example_mpc.py), or ``None`` for the default, shard 0's block.  Call it before
+        ``enable_graph(post_step=engine.step_state)``: a captured env step keeps the block it was captured with."""
+        if model is None:
+            blob = None
+        else:
+            if isinstance(model, str):
+                if model != "nominal":
+                    raise ValueError("set_real_env_model takes a model, 'nominal' or None, got %r" % (model,))
+                model = self.model
+            elif not isinstance(model, TreeModel):
+                model = self._compile(model)
+            blob = np.ascontiguousarray(model.blob, np.float64)
+        _lib.check(self._lib.mjmpc_tree_set_env_model(self._h, None if blob is None else blob.ctypes.data_as(_lib._dp)))
+        self.real_env_blob = blob
+
     def get_state_device(self):
         """The device-resident state as the task's state dictionary (one D2H copy; synchronises the stream)."""
         qp, qv = np.zeros(self.model.nq), np.zeros(self.model.nv)

@@ -1,0 +1,149 @@
+"""CPU: dynamics-randomized episode batches refuse what they do not run before anything reaches the device, draw what
+``SubprocVecEnv.randomize_dynamics`` draws, and the two new entry points are declared, bound, built and refuse bad arguments."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from mjmpc_amd import _lib
+from mjmpc_amd.models.half_cheetah import half_cheetah_raw
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW_SYMBOLS = ["mjmpc_tree_set_batch_models", "mjmpc_tree_set_env_model"]
+CFG = {"body_mass": {"torso": [0.3, 0.1], "ffoot": [0.5, 0.0]}, "dof_damping": {"bshin": [0.4, 0.2]},
+       "geom_size": {"ffoot": [0.2, 0.0]}, "geom_friction": {"bfoot": [0.5, 0.5]}}
+
+
+@pytest.fixture
+def no_engine(monkeypatch):
+    """Making an engine fails the test: every refusal must come first (tests/test_batched_cpu.py's pattern)."""
+    from mjmpc_amd.envs import tree_engine
+
+    def refuse(*a, **k):
+        raise AssertionError("an engine was created before the settings were checked")
+    monkeypatch.setattr(tree_engine.TreeRolloutEngine, "__init__", refuse)
+
+
+class _Device:
+    """Stands where the batch keeps its library and its engine: touching it is reaching the device."""
+
+    def __getattr__(self, name):
+        raise AssertionError("the device was reached (%s)" % name)
+
+
+def _batch(E=3, P=48, raw=None):
+    """A ``BatchedMPPI`` as its constructor leaves it on the host, without an engine."""
+    from mjmpc_amd.control import BatchedMPPI
+    from mjmpc_amd.models.compile_tree import compile_tree
+    raw = half_cheetah_raw() if raw is None else raw
+    b = object.__new__(BatchedMPPI)
+    b.raw, b.model, b.num_episodes, b.num_particles, b.shard_blobs = raw, compile_tree(raw), E, P, None
+    b.engine = b.lib = _Device()
+    return b
+
+
+@pytest.mark.parametrize("cfg,seed,K", [
+    (CFG, 1, 5),                                            # 48 particles do not divide into 5 shards
+    (CFG, 1, 0), (CFG, 1, 65536),
+    ({"body_volume": {"torso": [0.1, 0.0]}}, 1, 2),         # an unknown parameter
+    ({"body_mass": {"no_such_body": [0.1, 0.0]}}, 1, 2),    # unknown names, by kind of lookup
+    ({"dof_damping": {"no_such_joint": [0.1, 0.0]}}, 1, 2),
+    ({"geom_size": {"no_such_geom": [0.1, 0.0]}}, 1, 2),
+    ({"sensor_noise": {"no_such_sensor": [0.1, 0.0]}}, 1, 2),
+    (CFG, [1, 2], 2), (CFG, [1, 2, 3, 4], 2), (CFG, [], 2),     # a seed list of the wrong length (E = 3)
+], ids=lambda v: re.sub(r"[^A-Za-z0-9_,]+", "", str(v))[:24])
+def test_randomize_dynamics_refuses_before_the_device(no_engine, cfg, seed, K):
+    with pytest.raises(ValueError):
+        _batch().randomize_dynamics(cfg, seed, K)
+
+
+def test_a_batch_built_from_a_compiled_model_cannot_randomize(no_engine):
+    b = _batch()
+    b.raw = None
+    with pytest.raises(ValueError, match="RawModel"):
+        b.randomize_dynamics(CFG, 1, 2)
+
+
+@pytest.mark.parametrize("seed", [7, [7, 8, 9], np.array([7, 8, 9])], ids=["one", "list", "array"])
+def test_supported_settings_reach_the_device(no_engine, seed):
+    with pytest.raises(AssertionError, match="the device was reached"):
+        _batch().randomize_dynamics(CFG, seed, 2)
+
+
+def test_draws_follow_the_reference_seeds():
+    """Shard i of a shared set draws from ``np_random(base_seed + i*12345)``; episode e's shard i, with per-episode seeds,
+    from ``np_random(base_seed[e] + i*12345)`` - each parameter in the order of the configuration, uniform in
+    ``m (1 +- noise)`` with ``m = (1 + bias) * default`` (gym_env_wrapper.py:367-416)."""
+    from mjmpc_amd.envs._engine import draw_shard_models
+    from mjmpc_amd.envs.seeding import np_random
+    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
+    raw = half_cheetah_raw()
+    host = TreeRolloutEngine.host_only(raw)
+    cfg = {"body_mass": {"torso": [0.3, 0.1], "ffoot": [0.5, 0.0]}, "dof_damping": {"bshin": [0.4, 0.2]}}
+    names = [b.name for b in raw.bodies]
+    for base in (321, 77):
+        K = 3
+        d, r = [dict() for _ in range(K)], [dict() for _ in range(K)]
+        blobs = draw_shard_models(host, cfg, [base + i * 12345 for i in range(K)], d, r)
+        assert blobs.shape == (K, host.model.blob.size) and blobs.dtype == np.float64
+        for i in range(K):
+            rng, _ = np_random(base + i * 12345)
+            for pid, entries in cfg.items():
+                for name, (noise, bias) in entries.items():
+                    default = d[i][pid][name]
+                    if pid == "body_mass":
+                        assert default == float(host.model.body_mass[names.index(name)])
+                    m = (1.0 + bias) * default
+                    assert r[i][pid][name] == rng.uniform(m - m * noise, m + m * noise)
+        assert not np.array_equal(blobs[0], blobs[1])
+        # the same seeds draw the same blocks: a set per episode whose seeds agree is the shared set
+        again = draw_shard_models(host, cfg, [base + i * 12345 for i in range(K)], [dict() for _ in range(K)],
+                                  [dict() for _ in range(K)])
+        assert np.array_equal(blobs, again)
+    # an empty configuration compiles the nominal block
+    same = draw_shard_models(host, {}, [1], [dict()], [dict()])
+    assert np.array_equal(same[0], np.asarray(host.model.blob, np.float64))
+
+
+def test_host_only_engine_owns_no_device_state(no_engine):
+    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
+    host = TreeRolloutEngine.host_only(half_cheetah_raw())
+    assert host.closed and not hasattr(host, "_h")
+    host.close()                    # (nothing to destroy)
+
+
+def test_new_entry_points_are_declared_bound_and_built():
+    with open(os.path.join(ROOT, "include", "mjmpc_amd.h")) as f:
+        header = f.read()
+    lib = _lib.load()
+    for name in NEW_SYMBOLS:
+        assert re.search(r"\b%s\(" % name, header), name
+        assert name in _lib.SIGNATURES, name
+        assert getattr(lib, name) is not None, name
+    assert len(_lib.SIGNATURES["mjmpc_tree_set_batch_models"][1]) == 4 and len(_lib.SIGNATURES["mjmpc_tree_set_env_model"][1]) == 2
+    assert re.search(r"mjmpc_tree_set_batch_models\(mjmpc_tree_t h, const double\* \w+, int n_sets, int K\)", header)
+    assert re.search(r"mjmpc_tree_set_env_model\(mjmpc_tree_t h, const double\* \w+\)", header)
+
+
+def test_new_entry_points_reject_bad_arguments():
+    """Null engine, null blocks, a negative set count, fewer than one model shard: a non-zero code and a message that names
+    the argument, nothing launched.  (What needs an engine to be refused - a set count that is neither 1 nor the number of
+    state shards, a block of another topology - is in tests/test_batched_dynrand_gpu.py.)"""
+    lib = _lib.load()
+    blob = np.zeros(8)
+    p = blob.ctypes.data_as(_lib._dp)
+    cases = [
+        (lambda: lib.mjmpc_tree_set_batch_models(None, p, 1, 2), "null engine"),
+        (lambda: lib.mjmpc_tree_set_batch_models(None, None, 0, 0), "null engine"),
+        (lambda: lib.mjmpc_tree_set_batch_models(None, None, 1, 2), "null model blocks"),
+        (lambda: lib.mjmpc_tree_set_batch_models(None, p, -1, 2), "n_sets"),
+        (lambda: lib.mjmpc_tree_set_batch_models(None, p, 1, 0), "K = 0"),
+        (lambda: lib.mjmpc_tree_set_batch_models(None, p, 3, -2), "K = -2"),
+        (lambda: lib.mjmpc_tree_set_env_model(None, p), "null engine"),
+        (lambda: lib.mjmpc_tree_set_env_model(None, None), "null engine"),
+    ]
+    for i, (call, what) in enumerate(cases):
+        rc = call()
+        assert rc != 0, i
+        assert what in lib.mjmpc_last_error().decode(), (i, lib.mjmpc_last_error())
