@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""The config's ``n_episodes`` MPPI episodes as ONE batch on the tree engine (``BatchedMPPI``).
+"""The config's ``n_episodes`` MPPI or CEM episodes as ONE batch on the tree engine (``BatchedMPPI`` / ``BatchedCEM``).
 
-    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi]
+    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi|cem]
         [--dtype f64|f32] [--episodes N] [--dyn_randomize_config FILE [--num_cpu K] [--dyn_per_episode]]
 
 examples/example_mpc.py runs the episodes one after another (as the reference's job_script.py:80-99): episode i with seed
@@ -15,7 +15,8 @@ particles are split into the config's ``num_cpu`` shards and each shard rolls ou
 all episodes from the config's ``seed`` as the reference does before its episode loop (``--dyn_per_episode``: from every
 episode's own seed), while the real envs keep the nominal model - still one batch.
 
-Only the ``mppi`` block runs here; other controller blocks are refused.  The reacher configs run on the TREE engine here
+The ``mppi`` and ``cem`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection + moments,
+refit + next samples and env-step launches per control step); other controller blocks are refused.  The reacher configs run on the TREE engine here
 (sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
 rewards are not expected to be equal.
 """
@@ -30,15 +31,16 @@ import yaml
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from example_mpc import ENVS, TREE_MODELS                           # noqa: E402
-from mjmpc_amd.control import BatchedMPPI                           # noqa: E402
+from mjmpc_amd.control import BatchedCEM, BatchedMPPI               # noqa: E402
 from mjmpc_amd.envs.tree_engine import TreeRolloutEngine            # noqa: E402
 from mjmpc_amd.models.reacher7dof import reacher7dof_raw            # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Run a config's MPPI episodes as one batch")
+    ap = argparse.ArgumentParser(description="Run a config's MPPI or CEM episodes as one batch")
     ap.add_argument("--config", required=True, help="yaml file with experiment parameters")
-    ap.add_argument("--controller", default="mppi", help="controller block of the config to run (mppi only)")
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem"],
+                    help="controller block of the config to run")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--episodes", type=int, help="override n_episodes")
     ap.add_argument("--dyn_randomize_config", help="yaml file with dynamics randomization parameters")
@@ -49,11 +51,9 @@ def main():
         exp = yaml.safe_load(f)
     if exp["env_name"] not in ENVS:
         raise SystemExit("environment %r is not built (have: %s)" % (exp["env_name"], ", ".join(ENVS)))
-    if args.controller != "mppi":
-        raise SystemExit("an episode batch runs MPPI only (--controller mppi); %r is not batched" % args.controller)
-    if not isinstance(exp.get("mppi"), dict):
-        raise SystemExit("the config has no 'mppi' controller block")
-    params = dict(exp["mppi"])
+    if not isinstance(exp.get(args.controller), dict):
+        raise SystemExit("the config has no %r controller block" % args.controller)
+    params = dict(exp[args.controller])
     num_cpu = args.num_cpu or params.pop("num_cpu", 1)
     params.pop("num_cpu", None)
     if "particles_per_cpu" in params:
@@ -72,11 +72,17 @@ def main():
         states.append(env.get_env_state())
     env.engine.close()
 
-    batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
-                        params["init_cov"], params["gamma"], params["filter_coeffs"],
-                        params.get("base_action", exp.get("base_action", "null")), seeds, dtype=args.dtype,
-                        n_iters=params.get("n_iters", 1), alpha=params.get("alpha", 1),
-                        time_based_weights=params.get("time_based_weights", False))
+    base_action = params.get("base_action", exp.get("base_action", "null"))
+    if args.controller == "cem":
+        batch = BatchedCEM(raw, E, params["horizon"], params["num_particles"], params["init_cov"], params["elite_frac"],
+                           params["step_size"], params.get("beta", 0.0), params["gamma"], params["filter_coeffs"], base_action,
+                           seeds, cov_type=params.get("cov_type", "diagonal"), dtype=args.dtype,
+                           n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
+    else:
+        batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
+                            params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
+                            n_iters=params.get("n_iters", 1), alpha=params.get("alpha", 1),
+                            time_based_weights=params.get("time_based_weights", False))
     if args.dyn_randomize_config:
         with open(args.dyn_randomize_config) as f:
             default_params, randomized = batch.randomize_dynamics(yaml.safe_load(f), seeds if args.dyn_per_episode else exp["seed"],
@@ -101,8 +107,8 @@ def main():
             print("episode %d: reward %.3f, final distance to target %.4f"
                   % (i, rewards[i], np.linalg.norm(nobs[-1, i, -3:])))
     print("Avg. reward = %.4f, Std. Reward = %.4f" % (rewards.mean(), rewards.std()))
-    print("mppi batch: %d episodes x %d particles x H%d%s, %.3f ms per batched control step (%.0f episode-steps/s)"
-          % (E, params["num_particles"], params["horizon"],
+    print("%s batch: %d episodes x %d particles x H%d%s, %.3f ms per batched control step (%.0f episode-steps/s)"
+          % (args.controller, E, params["num_particles"], params["horizon"],
              ", %d randomized model shards" % num_cpu if args.dyn_randomize_config else "", 1e3 * dt / T, E * T / dt))
 
 

@@ -36,7 +36,7 @@ extern "C" {
  *      MJMPC_ARM_BLOB_LEN 229 -> 255 (joint type, friction loss, nu: the arm engine takes slide joints, dry friction and
  *      fewer motors than dofs). */
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
- *      device-resident particle filter's, mjmpc_tree_set_batch_models and mjmpc_tree_set_env_model.) */
+ *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model and the CEM episode batches'.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -508,6 +508,36 @@ int64_t mjmpc_update_batch_workspace_bytes(int E, int64_t P, int H, int A);
 int mjmpc_mppi_fused_update_batch(int dtype, int E, int64_t P, int H, int A, const double* d_q0, const void* d_actions,
                                   const double* d_lam, const double* d_step_size, int shift_mode, double* d_means,
                                   double* d_actions_out, int64_t* d_step_counter, void* d_ws, void* stream);
+
+/* Episode batches of the fused CEM step: E independent CEM updates (cem.py:65-95, one per episode of the reference's
+ * episode loop) in the same two launches, grid row e = episode e, no host synchronisation.
+ *   mjmpc_cem_select_moments_batch  row e is exactly mjmpc_cem_select_moments on one GPU (d_q_all == NULL) for its P
+ *       particles with k = d_k[e] (device int64 [E]): the k-th smallest (q0, particle index) threshold, the elite list and
+ *       the per-workgroup partials, with the slice sizes and the merge order of the single launch of P particles; and the
+ *       snapshots of ITS mean and covariance and of *d_step_counter.  d_actions dtype [E][P][H][A], d_q0 float64 [E][P],
+ *       d_means float64 [E][H][A], d_covs float64 [E][A][A].
+ *   mjmpc_cem_finish_batch          row e is exactly mjmpc_cem_finish with d_records == NULL, G = 1, n_elite = d_k[e],
+ *       step size d_step_size[e], growth d_grow_scale[e] * diag(d_grow_diag[e]) (float64 [E][A] / [E]; NULL: identity /
+ *       no growth), factor -> d_chols [E][A][A] (may be NULL), d_status[e] = 1 (int [E], sticky, may be NULL) if row e's
+ *       covariance is indefinite or not finite, action -> d_actions_out [E][A] (may be NULL), horizon shift, and -
+ *       d_next_noise != NULL - row e's RAW Philox samples of the next step, sample for sample the stream of
+ *       mjmpc_sample_noise(dtype, d_next_noise + e P H A, P, H, A, d_chols + e A A, NULL, d_seeds[e], offset, 0,
+ *       d_step_counter, 0).  *d_step_counter (may be NULL) is advanced once, by row 0; every row takes the step from the
+ *       snapshot the select launch made, never from the counter.
+ * The host sees k only through d_k, so the workspace - mjmpc_cem_batch_workspace_bytes(E, P, k_max, H, A) bytes, the same
+ * d_ws for both calls - holds any 1 <= d_k[e] <= P (k_max is validated, not a size); a row with d_k[e] outside that range
+ * is left untouched and flagged in d_status[e].  mjmpc_cem_batch_supported(E, P, k_max, H, A): 1 <= E <= 65535,
+ * 1 <= k_max <= P, and mjmpc_cem_fused_supported(P, P, k, H, A) for every row (A <= 8, A <= H + 1, P <= 32768). */
+int mjmpc_cem_batch_supported(int E, int64_t P, int64_t k_max, int H, int A);
+int64_t mjmpc_cem_batch_workspace_bytes(int E, int64_t P, int64_t k_max, int H, int A);
+int mjmpc_cem_select_moments_batch(int dtype, int E, int64_t P, int H, int A, const void* d_actions, const double* d_q0,
+                                   const int64_t* d_k, const double* d_means, const double* d_covs,
+                                   const int64_t* d_step_counter, void* d_ws, void* stream);
+int mjmpc_cem_finish_batch(int dtype, int E, int64_t P, int H, int A, const int64_t* d_k, int full_cov,
+                           const double* d_step_size, int shift_mode, double* d_means, double* d_covs, double* d_chols,
+                           int* d_status, const double* d_grow_diag, const double* d_grow_scale, double* d_actions_out,
+                           int64_t* d_step_counter, void* d_next_noise, const uint64_t* d_seeds, uint64_t offset, void* d_ws,
+                           void* stream);
 
 /* Sharded MPPI: the G all-gathered records d_records (float64 [G][2 + H*A], as left in d_record by
  * mjmpc_mppi_fused_update with step_size 0, shift_mode -1) merged in rank order -> mean update, action read-out,

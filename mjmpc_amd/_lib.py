@@ -90,6 +90,11 @@ SIGNATURES = {
     "mjmpc_rs_combine": (_int, [_vp, _int, _int, _int, _dbl, _vp, _vp]),
     "mjmpc_mppi_fused_update": (_int, [_int, _i64, _int, _int, _vp, _vp, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _vp, _vp]),
+    "mjmpc_cem_batch_supported": (_int, [_int, _i64, _i64, _int, _int]),
+    "mjmpc_cem_batch_workspace_bytes": (_i64, [_int, _i64, _i64, _int, _int]),
+    "mjmpc_cem_select_moments_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_cem_finish_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp]),
     "mjmpc_update_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int]),
     "mjmpc_mppi_fused_update_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_mppi_fused_combine": (_int, [_vp, _int, _dbl, _int, _int, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _vp, _vp]),

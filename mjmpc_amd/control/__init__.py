@@ -7,6 +7,7 @@ _WHERE = {
     "MPPI": "mppi", "MPPIQ": "mppiq", "CEM": "cem", "DMDMPC": "gaussian_dmd",
     "RandomShooting": "random_shooting", "PFMPC": "particle_filter_controller",
     "BatchedMPPI": "batched",           # (no reference counterpart: the reference's episode loop as one batch)
+    "BatchedCEM": "batched",
 }
 __all__ = sorted(_WHERE)
 

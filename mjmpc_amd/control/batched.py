@@ -1,4 +1,4 @@
-"""Episode batches: E independent MPPI episodes side by side on the tree engine.
+"""Episode batches: E independent MPPI or CEM episodes side by side on the tree engine.
 
 The reference runs its experiments one episode after another (examples/job_script.py:80-99, the episode loop of
 examples/example_mpc.py), each with its own seed (``seed + i*12345``) and start state, and its "tune" mode multiplies
@@ -21,6 +21,10 @@ Per episode: seed, start state (with ``target_pos``), initial mean, ``lam``, ``s
 ``randomize_dynamics``, the model blocks its particle shards roll out (shared by the episodes, or a set per episode).  Shared by
 the batch: the model, ``horizon``, ``num_particles`` (per episode), ``gamma``, ``filter_coeffs``, ``base_action`` and
 the dtype.  The batch's E real envs are the state shards of the batch's own engine (``mjmpc_tree_step_shard_states``).
+
+``BatchedCEM`` is the same batch for the cross-entropy method (cem.py): per episode also ``elite_frac`` and
+``beta``, and a covariance that is refitted from the elites on the device.  Both classes share ``_EpisodeBatch``: the engine,
+the state shards, the buffers, the rollout launch, the env step, ``run`` and dynamics randomization.
 """
 import ctypes
 
@@ -46,32 +50,23 @@ def _per_episode(name, value, E, shape=()):
                      % (name, tuple(shape), E, (E,) + tuple(shape), a.shape))
 
 
-class BatchedMPPI:
-    """``num_episodes`` MPPI controllers (mppi.py, ``alpha = 1``, one iteration per step) and their real envs, stepped together.
+class _EpisodeBatch:
+    """What the episode batches share: the checks of the common settings, the engine whose state shards are the E real envs,
+    the device buffers of the rollout launch, the env step, ``run`` and dynamics randomization.  A subclass checks its own
+    settings, calls ``_check_common`` and ``_compile`` (both raise ``ValueError`` and touch no device), then ``_setup``,
+    and provides ``step``."""
 
-    ``lam``, ``step_size``, ``init_cov`` (scalar covariance ``init_cov * I``, as ``MPPI`` takes it) and ``init_mean`` (``(H, A)``,
-    default zeros) take one value for every episode or one per episode; ``seeds`` one seed per episode.  Settings the
-    batch does not run raise ``ValueError`` before any engine or device memory exists: ``n_iters != 1``, ``alpha != 1``,
-    ``time_based_weights``, ``cov_type != 'diagonal'``, ``base_action`` other than ``'null'`` / ``'repeat'``,
-    ``use_zero_control_seq``, ``sample_mode != 'mean'``, ``gamma == 0`` and a model the tree engine refuses."""
-
-    def __init__(self, raw_model, num_episodes, horizon, num_particles, lam, step_size, init_cov, gamma, filter_coeffs,
-                 base_action, seeds, init_mean=None, dtype="f64", device=0, n_iters=1, alpha=1, time_based_weights=False,
-                 cov_type="diagonal", use_zero_control_seq=False, sample_mode="mean"):
-        # -- everything that can be refused is refused here, before the engine and its device memory exist
+    @staticmethod
+    def _check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq, sample_mode, dtype,
+                      gamma, filter_coeffs, what):
+        """The settings every batch refuses alike -> (E, H, P, filter coefficients)."""
         E, H, P = int(num_episodes), int(horizon), int(num_particles)
         if not 1 <= E <= 65535:
             raise ValueError("num_episodes must be in [1, 65535], got %d" % E)
         if H < 1 or P < 1:
             raise ValueError("horizon and num_particles must be positive")
         if n_iters != 1:
-            raise ValueError("an episode batch runs one MPPI iteration per control step (n_iters = 1), got %r" % (n_iters,))
-        if alpha != 1:
-            raise ValueError("an episode batch runs MPPI without the control cost (alpha = 1), got %r" % (alpha,))
-        if time_based_weights:
-            raise ValueError("an episode batch does not run time_based_weights")
-        if cov_type != "diagonal":
-            raise ValueError("an episode batch samples with a diagonal covariance (cov_type 'diagonal'), got %r" % (cov_type,))
+            raise ValueError("an episode batch runs one %s iteration per control step (n_iters = 1), got %r" % (what, n_iters))
         if base_action not in ("null", "repeat"):
             raise ValueError("base_action must be 'null' or 'repeat' in an episode batch, got %r" % (base_action,))
         if use_zero_control_seq:
@@ -85,19 +80,19 @@ class BatchedMPPI:
         fc = np.asarray(filter_coeffs, np.float64).reshape(-1)
         if fc.size != 3:
             raise ValueError("filter_coeffs must hold three coefficients")
-        lam = _per_episode("lam", lam, E)
-        step_size = _per_episode("step_size", step_size, E)
-        init_cov = _per_episode("init_cov", init_cov, E)
-        if not np.all(lam > 0):
-            raise ValueError("lam must be positive")
-        if not np.all(init_cov > 0):
-            raise ValueError("init_cov must be positive")
+        return E, H, P, fc
+
+    @staticmethod
+    def _check_seeds(seeds, E):
         seeds = list(seeds) if isinstance(seeds, (list, tuple, np.ndarray)) else None
         if seeds is None or len(seeds) != E:
             raise ValueError("seeds must hold one seed per episode (%d)" % E)
-        self.seed_vals = [_seed_value(int(s) if isinstance(s, (np.integer,)) else s) for s in seeds]
+        return [_seed_value(int(s) if isinstance(s, (np.integer,)) else s) for s in seeds]
+
+    @staticmethod
+    def _compile(raw_model):
+        """The tree engine's model, or ``ValueError`` for a model it refuses."""
         from ..models.compile_tree import TreeModel, compile_tree
-        from ..models.raw import RawModel
         try:
             model = raw_model if isinstance(raw_model, TreeModel) else compile_tree(raw_model)
         except (ValueError, NotImplementedError, TypeError, AttributeError) as e:
@@ -105,12 +100,12 @@ class BatchedMPPI:
         gen = int(model.field("gen")[0])
         if model.integrator == "RK4" and (model.nv > 16 or gen >= 3):
             raise ValueError("the tree engine runs RK4 models of up to 16 dofs without elliptic friction cones")
-        A = model.nu
-        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
-        factors = [noise_factor(np.diag(np.array([c] * A))) for c in init_cov]      # (OLGaussianMPC: diag(init_cov))
+        return model
 
-        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+    def _setup(self, raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean):
+        """The engine (its state shards are the E real envs) and the device buffers every batch has."""
         from ..envs.tree_engine import TreeRolloutEngine
+        from ..models.raw import RawModel
         import torch
         self.torch = torch
         self.engine = TreeRolloutEngine(model, device=device, dtype=dtype)
@@ -118,11 +113,12 @@ class BatchedMPPI:
         self.model = model
         self.raw = raw_model if isinstance(raw_model, RawModel) else None
         self.shard_blobs = None         # randomize_dynamics: the model blocks of the rollouts, [sets][num_shards][blob length]
+        A = model.nu
         self.num_episodes, self.horizon, self.num_particles, self.d_action = E, H, P, A
         self.d_obs, self.dtype = model.d_obs, dtype
         self.forward_task = self.engine.forward_task
         self.base_action, self.gamma, self.filter_coeffs = base_action, float(gamma), fc.copy()
-        self.lam, self.step_size, self.init_cov, self.init_mean = lam, step_size, init_cov, init_mean
+        self.init_mean = init_mean
         self.num_steps = 0
         dev = self.device = torch.device("cuda", device)
         self._code = _lib.F32 if dtype == "f32" else _lib.F64
@@ -131,24 +127,17 @@ class BatchedMPPI:
         self._means = torch.from_numpy(init_mean.copy()).to(dev)
         self._gseq = torch.from_numpy(np.cumprod([1.0] + [self.gamma] * (H - 1))).to(dev)     # (Controller.gamma_seq)
         self._coeffs = torch.from_numpy(fc.copy()).to(dev)
-        self._chols = torch.from_numpy(np.stack([f[0] for f in factors])).to(dev)
         self._seeds = torch.from_numpy(np.array(self.seed_vals, np.uint64).view(np.int64)).to(dev)
-        self._lam = torch.from_numpy(lam.copy()).to(dev)
-        self._step = torch.from_numpy(step_size.copy()).to(dev)
         self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._noise = torch.empty((E, P, H, A), dtype=tdt, device=dev)
         self._costs = torch.empty((E * P, H), dtype=tdt, device=dev)
         self._actions = torch.empty((E * P, H, A), dtype=tdt, device=dev)
         self._q0 = torch.empty(E * P, **f64)
-        nbytes = self.lib.mjmpc_update_batch_workspace_bytes(E, P, H, A)
-        if nbytes < 0:
-            _lib.check(int(nbytes))
-        self._ws = torch.empty((nbytes + 7) // 8, **f64)
         self._act = torch.empty((E, A), **f64)
         self._env_cost = torch.empty(E, dtype=tdt, device=dev)
         self._env_obs = torch.empty((E, self.d_obs), dtype=tdt, device=dev)
         self._targets = [model.target_default.copy() for _ in range(E)]
-        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+        return f64
 
     # ------------------------------------------------------------------ state of the E real envs
     @property
@@ -173,6 +162,7 @@ class BatchedMPPI:
         E, m = self.num_episodes, self.model
         qp, qv = self.engine.get_shard_states()
         self._check_resets()
+        self._check_status()
         if self.forward_task:
             return [dict(qpos=qp[e].copy(), qvel=qv[e].copy()) for e in range(E)]
         return [dict(qp=qp[e].copy(), qv=qv[e].copy(), qa=np.zeros(m.nv), target_pos=self._targets[e].copy(), timestep=0)
@@ -181,7 +171,9 @@ class BatchedMPPI:
     @property
     def mean_action(self):
         """The E means, ``(E, H, A)`` (synchronises)."""
-        return self._means.cpu().numpy().copy()
+        out = self._means.cpu().numpy().copy()
+        self._check_status()
+        return out
 
     def reset(self):
         """Every episode back to its initial mean and step 0 (the real envs keep their states: ``set_states``)."""
@@ -233,21 +225,18 @@ class BatchedMPPI:
 
     # ------------------------------------------------------------------ control steps
     def step(self, _out=None):
-        """Enqueue one control step of every episode (sampling, rollouts, update, action, shift, real-env step) without a
-        host synchronisation.  The actions, real-env costs and next observations stay on the device."""
-        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
-        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
-        lib, h, code, s = self.lib, self.engine._h, self._code, self._stream()
-        _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
-                                                _vp(self._step_dev), s))
-        _lib.check(lib.mjmpc_tree_rollout_fused_batch(h, code, E * P, H, _vp(self._means), _vp(self._noise), _vp(self._coeffs),
-                                                      _vp(self._gseq), _vp(self._costs), _vp(self._actions), _vp(self._q0), s))
-        _lib.check(lib.mjmpc_mppi_fused_update_batch(code, E, P, H, A, _vp(self._q0), _vp(self._actions), _vp(self._lam),
-                                                     _vp(self._step), _SHIFT_MODES[self.base_action], _vp(self._means),
-                                                     _vp(act), _vp(self._step_dev), _vp(self._ws), s))
-        _lib.check(lib.mjmpc_tree_step_shard_states(h, code, _vp(act), _vp(cost), _vp(nobs), s))
-        self.num_steps += 1
-        return act, cost, nobs
+        raise NotImplementedError
+
+    def _rollout(self, s):
+        """The batch's rollout launch: grid row = episode, the cost-to-go of every particle into ``_q0``."""
+        E, P, H = self.num_episodes, self.num_particles, self.horizon
+        _lib.check(self.lib.mjmpc_tree_rollout_fused_batch(self.engine._h, self._code, E * P, H, _vp(self._means), _vp(self._noise),
+                                                           _vp(self._coeffs), _vp(self._gseq), _vp(self._costs),
+                                                           _vp(self._actions), _vp(self._q0), s))
+
+    def _env_step(self, act, cost, nobs, s):
+        """The E real envs take their episode's action in one launch."""
+        _lib.check(self.lib.mjmpc_tree_step_shard_states(self.engine._h, self._code, _vp(act), _vp(cost), _vp(nobs), s))
 
     def run(self, T):
         """``T`` control steps of every episode -> actions ``[T][E][A]`` (float64), real-env costs ``[T][E]`` and next
@@ -264,6 +253,7 @@ class BatchedMPPI:
             self.step(_out=(acts[t], costs[t], nobs[t]))
         host = buf.cpu().numpy()
         self._check_resets()
+        self._check_status()
         npt = np.float32 if self.dtype == "f32" else np.float64
         return (host[:na].view(np.float64).reshape(T, E, A).copy(), host[na:na + nc].view(npt).reshape(T, E).copy(),
                 host[na + nc:].view(npt).reshape(T, E, D).copy())
@@ -276,5 +266,192 @@ class BatchedMPPI:
         if self.engine.on_env_reset != "ignore":
             self.engine.check_env_resets("an episode batch's real envs (step_shard_states)")
 
+    def _check_status(self):
+        pass                    # (batches whose kernels can flag an episode override this: BatchedCEM)
+
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+
+class BatchedMPPI(_EpisodeBatch):
+    """``num_episodes`` MPPI controllers (mppi.py, ``alpha = 1``, one iteration per step) and their real envs, stepped together.
+
+    ``lam``, ``step_size``, ``init_cov`` (scalar covariance ``init_cov * I``, as ``MPPI`` takes it) and ``init_mean`` (``(H, A)``,
+    default zeros) take one value for every episode or one per episode; ``seeds`` one seed per episode.  Settings the
+    batch does not run raise ``ValueError`` before any engine or device memory exists: ``n_iters != 1``, ``alpha != 1``,
+    ``time_based_weights``, ``cov_type != 'diagonal'``, ``base_action`` other than ``'null'`` / ``'repeat'``,
+    ``use_zero_control_seq``, ``sample_mode != 'mean'``, ``gamma == 0`` and a model the tree engine refuses."""
+
+    def __init__(self, raw_model, num_episodes, horizon, num_particles, lam, step_size, init_cov, gamma, filter_coeffs,
+                 base_action, seeds, init_mean=None, dtype="f64", device=0, n_iters=1, alpha=1, time_based_weights=False,
+                 cov_type="diagonal", use_zero_control_seq=False, sample_mode="mean"):
+        # -- everything that can be refused is refused here, before the engine and its device memory exist
+        if alpha != 1:
+            raise ValueError("an episode batch runs MPPI without the control cost (alpha = 1), got %r" % (alpha,))
+        if time_based_weights:
+            raise ValueError("an episode batch does not run time_based_weights")
+        if cov_type != "diagonal":
+            raise ValueError("an episode batch samples with a diagonal covariance (cov_type 'diagonal'), got %r" % (cov_type,))
+        E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
+                                         sample_mode, dtype, gamma, filter_coeffs, "MPPI")
+        lam = _per_episode("lam", lam, E)
+        step_size = _per_episode("step_size", step_size, E)
+        init_cov = _per_episode("init_cov", init_cov, E)
+        if not np.all(lam > 0):
+            raise ValueError("lam must be positive")
+        if not np.all(init_cov > 0):
+            raise ValueError("init_cov must be positive")
+        self.seed_vals = self._check_seeds(seeds, E)
+        model = self._compile(raw_model)
+        A = model.nu
+        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
+        factors = [noise_factor(np.diag(np.array([c] * A))) for c in init_cov]      # (OLGaussianMPC: diag(init_cov))
+
+        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+        f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
+        torch, dev = self.torch, self.device
+        self.lam, self.step_size, self.init_cov = lam, step_size, init_cov
+        self._chols = torch.from_numpy(np.stack([f[0] for f in factors])).to(dev)
+        self._lam = torch.from_numpy(lam.copy()).to(dev)
+        self._step = torch.from_numpy(step_size.copy()).to(dev)
+        nbytes = self.lib.mjmpc_update_batch_workspace_bytes(E, P, H, A)
+        if nbytes < 0:
+            _lib.check(int(nbytes))
+        self._ws = torch.empty((nbytes + 7) // 8, **f64)
+        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+
+    def step(self, _out=None):
+        """Enqueue one control step of every episode (sampling, rollouts, update, action, shift, real-env step) without a
+        host synchronisation.  The actions, real-env costs and next observations stay on the device."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
+        lib, code, s = self.lib, self._code, self._stream()
+        _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
+                                                _vp(self._step_dev), s))
+        self._rollout(s)
+        _lib.check(lib.mjmpc_mppi_fused_update_batch(code, E, P, H, A, _vp(self._q0), _vp(self._actions), _vp(self._lam),
+                                                     _vp(self._step), _SHIFT_MODES[self.base_action], _vp(self._means),
+                                                     _vp(act), _vp(self._step_dev), _vp(self._ws), s))
+        self._env_step(act, cost, nobs, s)
+        self.num_steps += 1
+        return act, cost, nobs
+
+
+def _cem_limits():
+    return "the batched fused CEM step takes A <= 8, A <= H + 1, P <= 32768 and 1 <= num_elite <= num_particles"
+
+
+class BatchedCEM(_EpisodeBatch):
+    """``num_episodes`` CEM controllers (cem.py, one iteration per step) and their real envs, stepped together.
+
+    Episode e computes the bits of ``CEM(..., noise_mode='device', seed=seeds[e])`` on a ``TreeRolloutEngine`` of its own with
+    ``make_device_rollout_fn`` and ``enable_graph(post_step=engine.step_state)``, whose step is the fused one
+    (``mjmpc_cem_select_moments`` + ``mjmpc_cem_finish``).  ``init_cov`` (scalar: ``diag(init_cov)``, as ``CEM`` takes it),
+    ``elite_frac``, ``step_size`` and ``beta`` take one value for every episode or one per episode (``num_elite_e =
+    int(num_particles * elite_frac_e)``); ``seeds`` one seed per episode.  A control step is four launches - rollout,
+    selection + moments, finish (refit, covariance growth, factor, action, shift, the next step's samples), real-env step -
+    and a fifth, the first draw, on step 0.  Settings the batch does not run raise ``ValueError`` before any engine or
+    device memory exists: ``n_iters != 1``, ``sample_mode != 'mean'``, ``use_zero_control_seq``, ``gamma == 0``, ``cov_type``
+    other than ``'diagonal'`` / ``'full'``, ``base_action`` other than ``'null'`` / ``'repeat'``, a ``num_elite_e < 1``, a shape
+    outside ``mjmpc_cem_batch_supported`` and a model the tree engine refuses.  An episode whose covariance turns indefinite
+    raises ``MjmpcError`` where ``run`` / ``get_states`` / ``mean_action`` / ``cov`` synchronise."""
+
+    def __init__(self, raw_model, num_episodes, horizon, num_particles, init_cov, elite_frac, step_size, beta, gamma,
+                 filter_coeffs, base_action, seeds, cov_type="full", dtype="f64", device=0, n_iters=1, sample_mode="mean",
+                 use_zero_control_seq=False):
+        # -- everything that can be refused is refused here, before the engine and its device memory exist
+        if cov_type not in ("diagonal", "full"):
+            raise ValueError("cov_type must be 'diagonal' or 'full' in a CEM episode batch, got %r" % (cov_type,))
+        E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
+                                         sample_mode, dtype, gamma, filter_coeffs, "CEM")
+        init_cov = _per_episode("init_cov", init_cov, E)
+        elite_frac = _per_episode("elite_frac", elite_frac, E)
+        step_size = _per_episode("step_size", step_size, E)
+        beta = _per_episode("beta", beta, E)
+        if not np.all(init_cov > 0):
+            raise ValueError("init_cov must be positive")
+        num_elite = np.array([int(P * f) for f in elite_frac], np.int64)          # (cem.py:18)
+        if np.any(num_elite < 1) or np.any(num_elite > P):
+            raise ValueError("every episode needs 1 <= num_elite = int(num_particles * elite_frac) <= num_particles, got %s"
+                             % (num_elite.tolist(),))
+        self.seed_vals = self._check_seeds(seeds, E)
+        model = self._compile(raw_model)
+        A = model.nu
+        lib = _lib.load()
+        if not lib.mjmpc_cem_batch_supported(E, P, int(num_elite.max()), H, A):
+            raise ValueError("%s; got A = %d, H = %d, P = %d, num_elite up to %d"
+                             % (_cem_limits(), A, H, P, int(num_elite.max())))
+        init_mean = np.zeros((E, H, A))                                            # (CEM starts from a zero mean)
+
+        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+        f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
+        torch, dev = self.torch, self.device
+        self.init_cov, self.elite_frac, self.step_size, self.beta = init_cov, elite_frac, step_size, beta
+        self.num_elite, self.cov_type = num_elite, cov_type
+        # the first factor is the diagonal sqrt(init_cov): what the single path's first draw colours its samples with
+        self._init_covs = np.stack([np.diag(np.array([c] * A)) for c in init_cov])
+        self._init_chols = np.stack([noise_factor(c)[0] for c in self._init_covs])
+        self._covs = torch.from_numpy(self._init_covs.copy()).to(dev)
+        self._chols = torch.from_numpy(self._init_chols.copy()).to(dev)
+        self._k = torch.from_numpy(num_elite.copy()).to(dev)
+        self._step = torch.from_numpy(step_size.copy()).to(dev)
+        self._grow_diag = torch.from_numpy(np.repeat(init_cov[:, None], A, axis=1).copy()).to(dev)     # (cem.py:94)
+        self._grow_scale = torch.from_numpy(beta.copy()).to(dev)
+        self._status = torch.zeros(E, dtype=torch.int32, device=dev)
+        nbytes = self.lib.mjmpc_cem_batch_workspace_bytes(E, P, int(num_elite.max()), H, A)
+        if nbytes < 0:
+            _lib.check(int(nbytes))
+        self._ws = torch.empty((nbytes + 7) // 8, **f64)
+        self._noise_valid = False       # step 0 (and the step after reset) draws its own samples; later ones are drawn ahead
+        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+
+    @property
+    def cov(self):
+        """The E action covariances, ``(E, A, A)`` (synchronises)."""
+        out = self._covs.cpu().numpy().copy()
+        self._check_status()
+        return out
+
+    def reset(self):
+        """Every episode back to its initial mean, covariance and factor and to step 0 (the real envs keep their states)."""
+        super().reset()
+        self._covs.copy_(self.torch.from_numpy(self._init_covs))
+        self._chols.copy_(self.torch.from_numpy(self._init_chols))
+        self._noise_valid = False
+
+    def step(self, _out=None):
+        """Enqueue one control step of every episode (rollouts, selection + moments, refit + action + shift + the next step's
+        samples, real-env step) without a host synchronisation; step 0 draws its samples first.  The actions, real-env costs
+        and next observations stay on the device."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
+        lib, code, s = self.lib, self._code, self._stream()
+        if not self._noise_valid:
+            # (the factors are diagonal here - diag(sqrt(init_cov)) -, for which the diagonal draw and the general one of the
+            # single path's first step form the same 0 + l z per sample: DESIGN 10.2)
+            _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
+                                                    _vp(self._step_dev), s))
+            self._noise_valid = True
+        self._rollout(s)
+        _lib.check(lib.mjmpc_cem_select_moments_batch(code, E, P, H, A, _vp(self._actions), _vp(self._q0), _vp(self._k),
+                                                      _vp(self._means), _vp(self._covs), _vp(self._step_dev), _vp(self._ws), s))
+        _lib.check(lib.mjmpc_cem_finish_batch(code, E, P, H, A, _vp(self._k), int(self.cov_type == "full"), _vp(self._step),
+                                              _SHIFT_MODES[self.base_action], _vp(self._means), _vp(self._covs),
+                                              _vp(self._chols), _vp(self._status), _vp(self._grow_diag), _vp(self._grow_scale),
+                                              _vp(act), _vp(self._step_dev), _vp(self._noise), _vp(self._seeds), 0,
+                                              _vp(self._ws), s))
+        self._env_step(act, cost, nobs, s)
+        self.num_steps += 1
+        return act, cost, nobs
+
+    def _check_status(self):
+        """``DeviceUpdater.check_status`` per episode: raise for the episodes whose finish launch has flagged an indefinite or
+        non-finite covariance (the flags are sticky on the device) and clear exactly the flags reported."""
+        st = self._status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size == 0:
+            return
+        self._status[self.torch.from_numpy(bad).to(self.device)] = 0
+        raise _lib.MjmpcError("the action covariance of episode%s %s on the device is indefinite or not finite: its Cholesky "
+                              "factor (sampler colouring) does not exist"
+                              % ("" if bad.size == 1 else "s", ", ".join(str(int(e)) for e in bad)))

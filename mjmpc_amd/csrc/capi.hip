@@ -1516,6 +1516,58 @@ int mjmpc_mppi_fused_update_batch(int dtype, int E, int64_t P, int H, int A, con
                                                     A, d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws, s));
 }
 
+int mjmpc_cem_batch_supported(int E, int64_t P, int64_t k_max, int H, int A) {
+    return mjmpc::cem_batch_supported(E, (long)P, (long)k_max, H, A) ? 1 : 0;
+}
+
+static int cem_batch_shape(int E, int64_t P, int64_t k_max, int H, int A) {
+    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
+    if (!mjmpc::cem_batch_supported(E, (long)P, (long)k_max, H, A))
+        return fail(MJMPC_E_BADARG, "shape outside the batched fused CEM step (mjmpc_cem_batch_supported): P = %lld, "
+                    "k_max = %lld, H = %d, A = %d; it takes A <= 8, A <= H + 1, P <= 32768, 1 <= k <= P",
+                    (long long)P, (long long)k_max, H, A);
+    return 0;
+}
+
+int64_t mjmpc_cem_batch_workspace_bytes(int E, int64_t P, int64_t k_max, int H, int A) {
+    if (int rc = cem_batch_shape(E, P, k_max, H, A)) return rc;
+    return (int64_t)sizeof(double) * mjmpc::cem_batch_workspace_doubles(E, (long)P, H, A);
+}
+
+int mjmpc_cem_select_moments_batch(int dtype, int E, int64_t P, int H, int A, const void* d_actions, const double* d_q0,
+                                   const int64_t* d_k, const double* d_means, const double* d_covs,
+                                   const int64_t* d_step_counter, void* d_ws, void* stream) {
+    if (!d_actions || !d_q0 || !d_k || !d_means || !d_covs || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
+    if (int rc = cem_batch_shape(E, P, 1, H, A)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::cem_select_moments_batch<float>(E, (const float*)d_actions, d_q0, (const long long*)d_k, (long)P, H, A, d_means,
+                                                    d_covs, (const long long*)d_step_counter, (double*)d_ws, s),
+             mjmpc::cem_select_moments_batch<double>(E, (const double*)d_actions, d_q0, (const long long*)d_k, (long)P, H, A,
+                                                     d_means, d_covs, (const long long*)d_step_counter, (double*)d_ws, s));
+}
+
+int mjmpc_cem_finish_batch(int dtype, int E, int64_t P, int H, int A, const int64_t* d_k, int full_cov,
+                           const double* d_step_size, int shift_mode, double* d_means, double* d_covs, double* d_chols,
+                           int* d_status, const double* d_grow_diag, const double* d_grow_scale, double* d_actions_out,
+                           int64_t* d_step_counter, void* d_next_noise, const uint64_t* d_seeds, uint64_t offset, void* d_ws,
+                           void* stream) {
+    if (!d_k || !d_step_size || !d_means || !d_covs || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
+    if (d_next_noise && !d_seeds) return fail(MJMPC_E_BADARG, "d_next_noise without d_seeds");
+    if (shift_mode > 1) return fail(MJMPC_E_BADARG, "shift_mode must be < 0 (none), 0 (null) or 1 (repeat)");
+    if (int rc = cem_batch_shape(E, P, 1, H, A)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::cem_finish_batch<float>(E, (const long long*)d_k, (long)P, H, A, full_cov, d_step_size, shift_mode, d_means,
+                                            d_covs, d_chols, d_status, d_grow_diag, d_grow_scale, d_actions_out,
+                                            (long long*)d_step_counter, (float*)d_next_noise,
+                                            (const unsigned long long*)d_seeds, offset, (double*)d_ws, s),
+             mjmpc::cem_finish_batch<double>(E, (const long long*)d_k, (long)P, H, A, full_cov, d_step_size, shift_mode, d_means,
+                                             d_covs, d_chols, d_status, d_grow_diag, d_grow_scale, d_actions_out,
+                                             (long long*)d_step_counter, (double*)d_next_noise,
+                                             (const unsigned long long*)d_seeds, offset, (double*)d_ws, s));
+}
+
 int mjmpc_mppi_fused_combine(const double* d_records, int G, double P_total, int H, int A, double lam, double step_size,
                              int shift_mode, double* d_mean, double* d_action_out, double* d_value,
                              double* h_action_mapped, int64_t* d_step_counter, void* stream) {

@@ -58,6 +58,21 @@ hipError_t cem_finish(const double* records, int G, long k, long P, int H, int A
                       double grow_scale, double* action_out, double* action_host, long long* step_counter, T* noise,
                       unsigned long long seed, unsigned long long offset, long particle_offset, double* ws, hipStream_t s);
 
+// Episode batches of the fused CEM step: grid row e is cem_select_moments / cem_finish (one GPU) on episode e's P particles
+// with k[e] elites, its own step size, covariance growth, seed and status flag.  k lives on the device; the workspace holds
+// any 1 <= k[e] <= P (a row outside that is flagged in status and left alone).  noise == nullptr: no draw.
+bool cem_batch_supported(int E, long P, long k_max, int H, int A);
+long cem_batch_workspace_doubles(int E, long P, int H, int A);
+template <typename T>
+hipError_t cem_select_moments_batch(int E, const T* actions, const double* q0, const long long* k, long P, int H, int A,
+                                    const double* means, const double* covs, const long long* d_step, double* ws,
+                                    hipStream_t s);
+template <typename T>
+hipError_t cem_finish_batch(int E, const long long* k, long P, int H, int A, int full, const double* step, int shift_mode,
+                            double* means, double* covs, double* chols, int* status, const double* grow_diag,
+                            const double* grow_scale, double* actions_out, long long* step_counter, T* noise,
+                            const unsigned long long* seeds, unsigned long long offset, double* ws, hipStream_t s);
+
 // Random shooting: {min q0, global index, action[H*A]} record and the combine.
 template <typename T>
 hipError_t rs_best(const T* actions, long offset, long P, int H, int A, double* record, double* ws, hipStream_t s);

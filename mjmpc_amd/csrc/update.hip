@@ -12,6 +12,8 @@
 // atomics on floating point, so results are bit-reproducible run to run and identical on all ranks.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "noise_device.h"
 #include "update.h"
 
@@ -300,11 +302,70 @@ struct CemMoments {
     long long* step_prev;
     int H, A, E;
 };
-template <int NPER, typename TA = double, bool MOM = false>
+// EB = true (episode batches, DESIGN 10.2: cem_select_moments_batch): the same kernel with grid row e = episode e.  The last
+// argument is then the batch's CemSelectBatch, from which the row takes q_all, k, thr, list, count and its CemMoments (its
+// block of the batch workspace, CemRow); the other arguments are unused.  The grid is as wide as the largest k <= P needs;
+// a row's workgroups past its last slice leave at once.  EB = false compiles to what it was before the switch existed.
+// -- one episode's block of the batch workspace, laid out alike on host and device:
+// thr[3] | count | cprime[A <= 8] | step snapshot | elite list [P] | mean snapshot [HA] | cov snapshot [AA] | partials
+struct CemRow {
+    unsigned long long* thr;
+    int *count, *elite;
+    long long* step_prev;
+    double *cprime, *mean_prev, *cov_prev, *partial;
+    __host__ __device__ CemRow(double* base, long P, int HA, int AA) {
+        thr = (unsigned long long*)base;
+        count = (int*)(base + 8);
+        cprime = base + 16;
+        step_prev = (long long*)(base + 24);
+        elite = (int*)(base + 32);
+        mean_prev = base + 32 + (P + 1) / 2;
+        cov_prev = mean_prev + HA;
+        partial = cov_prev + AA;
+    }
+};
+__host__ __device__ inline long cem_row_doubles(long P, int HA, int AA, int nb_cap) {
+    return 32 + (P + 1) / 2 + HA + AA + (long)nb_cap * (1 + HA + AA);
+}
+// an elite count the row's partial area holds (the host sees k only through d_k: the kernels check it themselves)
+__device__ __forceinline__ bool cem_row_k_ok(long k, int rows, int nb_cap) { return k >= 1 && (k + rows - 1) / rows <= nb_cap; }
+template <typename TA>
+struct CemSelectBatch {
+    const TA* actions;
+    const double *q0, *means, *covs;
+    const long long *k, *d_step;
+    double* ws;
+    long stride, P;
+    int H, A, rows, nb_cap;
+};
+template <typename TA, bool EB>
+using CemSelectArg = std::conditional_t<EB, CemSelectBatch<TA>, CemMoments<TA>>;
+template <int NPER, typename TA = double, bool MOM = false, bool EB = false>
 __global__ __launch_bounds__(1024) void kth_key_kernel(const double* __restrict__ q_all, long P_all, long k,
                                                        unsigned long long* __restrict__ thr, long offset, long P_local,
                                                        int* __restrict__ list, int* __restrict__ count,
-                                                       CemMoments<TA> mo = CemMoments<TA>()) {
+                                                       CemSelectArg<TA, EB> arg = CemSelectArg<TA, EB>()) {
+    CemMoments<TA> mo_row;      // (EB: the episode's; otherwise unused)
+    if constexpr (EB) {
+        const long e = blockIdx.y;
+        const int HA = arg.H * arg.A, AA = arg.A * arg.A;
+        const CemRow r(arg.ws + e * arg.stride, arg.P, HA, AA);
+        k = arg.k[e];
+        if (!cem_row_k_ok(k, arg.rows, arg.nb_cap)) {       // (cem_finish_batch_kernel flags the row; it still needs the step)
+            if (blockIdx.x == 0 && threadIdx.x == 0) *r.step_prev = arg.d_step ? *arg.d_step : 0ll;
+            return;
+        }
+        if ((long)blockIdx.x * arg.rows >= k) return;
+        q_all = arg.q0 + e * arg.P; P_all = arg.P; thr = r.thr; offset = 0; P_local = arg.P; list = r.elite; count = r.count;
+        mo_row.actions = arg.actions + e * arg.P * HA; mo_row.mean = arg.means + e * HA; mo_row.cov = arg.covs + e * AA;
+        mo_row.d_step = arg.d_step; mo_row.partial = r.partial; mo_row.cprime = r.cprime; mo_row.mean_prev = r.mean_prev;
+        mo_row.cov_prev = r.cov_prev; mo_row.step_prev = r.step_prev;
+        mo_row.H = arg.H; mo_row.A = arg.A; mo_row.E = arg.rows;
+    }
+    const CemMoments<TA>& mo = [&]() -> const CemMoments<TA>& {
+        if constexpr (EB) return mo_row;
+        else return arg;
+    }();
     __shared__ unsigned hist[256];
     __shared__ unsigned long long prefix_s, red_and[16], red_or[16], cand_key[KTH_CAND];
     __shared__ long need_s, cut_s, sel_need, wtot[16], scan_v[256], cand_idx[KTH_CAND];
@@ -868,8 +929,9 @@ struct CemFinish {
     long particle_offset, P;
 };
 constexpr int CEM_FIN_THREADS = 256;
+// (the body is shared with the episode-batch kernel cem_finish_batch_kernel, whose grid row fills in the episode's CemFinish)
 template <typename T>
-__global__ __launch_bounds__(CEM_FIN_THREADS) void cem_finish_kernel(CemFinish f) {
+__device__ __forceinline__ void cem_finish_body(const CemFinish& f) {
     extern __shared__ double sh[];          // sumA[HA] | mu[(G + 1) * A] | C[AA] | L[AA] | per-wave store tiles
     const int H = f.H, A = f.A, HA = H * A, AA = A * A, R = 1 + HA + AA, G = f.n_in;
     const int tid = threadIdx.x;
@@ -1020,6 +1082,53 @@ __global__ __launch_bounds__(CEM_FIN_THREADS) void cem_finish_kernel(CemFinish f
             __builtin_amdgcn_wave_barrier();
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(CEM_FIN_THREADS) void cem_finish_kernel(CemFinish f) {
+    cem_finish_body<T>(f);
+}
+
+// Grid row e is cem_finish (one GPU: mode 0, the row's partials, n_elite = k = d_k[e]) on episode e's block of the workspace
+// with its own step size, covariance growth, seed, status flag and [P][H][A] block of the next samples.  Every row takes the
+// step from ITS snapshot (kth_key_kernel<.., EB = true>), never from the counter, which row 0 advances here.
+struct CemFinishBatch {
+    const long long* k;
+    const double *step, *grow_diag, *grow_scale;
+    const unsigned long long* seeds;
+    double *means, *covs, *chols, *actions_out, *ws;
+    int* status;
+    long long* step_counter;
+    void* noise;
+    long stride, P;
+    unsigned long long offset;
+    int H, A, rows, nb_cap, full, shift_mode;
+};
+template <typename T>
+__global__ __launch_bounds__(CEM_FIN_THREADS) void cem_finish_batch_kernel(CemFinishBatch b) {
+    const long e = blockIdx.y, k = b.k[e];
+    const int HA = b.H * b.A, AA = b.A * b.A;
+    const CemRow r(b.ws + e * b.stride, b.P, HA, AA);
+    if (!cem_row_k_ok(k, b.rows, b.nb_cap)) {       // no elite set the workspace holds: the row is flagged and left alone
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            if (b.status) b.status[e] = 1;
+            if (e == 0 && b.step_counter) *b.step_counter = *r.step_prev + 1;
+        }
+        return;
+    }
+    CemFinish f;
+    f.in = r.partial; f.cprime = r.cprime; f.mean_prev = r.mean_prev; f.cov_prev = r.cov_prev;
+    f.grow_diag = b.grow_diag ? b.grow_diag + e * b.A : nullptr;
+    f.step_prev = r.step_prev;
+    f.mean = b.means + e * HA; f.cov = b.covs + e * AA; f.chol = b.chols ? b.chols + e * AA : nullptr;
+    f.action_out = b.actions_out ? b.actions_out + e * b.A : nullptr; f.action_host = nullptr;
+    f.step_counter = e == 0 ? b.step_counter : nullptr;
+    f.status = b.status ? b.status + e : nullptr;
+    f.noise = b.noise ? (void*)((T*)b.noise + e * b.P * HA) : nullptr;
+    f.n_in = (int)((k + b.rows - 1) / b.rows); f.mode = 0; f.H = b.H; f.A = b.A; f.full = b.full; f.shift_mode = b.shift_mode;
+    f.n_elite = (double)k; f.step = b.step[e]; f.grow_scale = b.grow_scale ? b.grow_scale[e] : 0.0;
+    f.seed = b.seeds ? b.seeds[e] : 0ull; f.offset = b.offset; f.particle_offset = 0; f.P = b.P;
+    cem_finish_body<T>(f);
 }
 
 // ---- random shooting --------------------------------------------------------------------------------
@@ -1579,6 +1688,78 @@ hipError_t cem_finish(const double* records, int G, long k, long P, int H, int A
     return hipGetLastError();
 }
 
+// ---- episode batches of the fused CEM step ------------------------------------------------------------------
+// slices of the elite list a row's partial area holds: what any k <= P that cem_fused_supported takes can need (the launches
+// see k only on the device, so the layout cannot depend on it)
+static int cem_batch_slices(long P, int H, int A) {
+    const int E = cem_fused_rows(H, A);
+    const long a = (P + E - 1) / E, b = (P + CHUNK - 1) / CHUNK;
+    return (int)(a < b ? a : b);
+}
+template <typename T>
+static size_t cem_finish_batch_lds(long P, int H, int A) {
+    return sizeof(double) * ((size_t)H * A + (size_t)(cem_batch_slices(P, H, A) + 1) * A + 2 * (size_t)A * A) +
+           sizeof(T) * (CEM_FIN_THREADS / 64) * 64 * (4 * A + 1);
+}
+bool cem_batch_supported(int E, long P, long k_max, int H, int A) {
+    if (E < 1 || E > 65535 || k_max > P || !cem_fused_supported(P, P, k_max, H, A)) return false;
+    return cem_finish_batch_lds<double>(P, H, A) <= 150 * 1024;
+}
+long cem_batch_workspace_doubles(int E, long P, int H, int A) {
+    return (long)E * cem_row_doubles(P, H * A, A * A, cem_batch_slices(P, H, A));
+}
+
+template <typename T>
+hipError_t cem_select_moments_batch(int E, const T* actions, const double* q0, const long long* k, long P, int H, int A,
+                                    const double* means, const double* covs, const long long* d_step, double* ws,
+                                    hipStream_t s) {
+    if (!cem_batch_supported(E, P, 1, H, A)) return hipErrorInvalidValue;
+    const int rows = cem_fused_rows(H, A), HA = H * A, AA = A * A, NB = cem_batch_slices(P, H, A);
+    CemSelectBatch<T> b;
+    b.actions = actions; b.q0 = q0; b.means = means; b.covs = covs; b.k = k; b.d_step = d_step; b.ws = ws;
+    b.stride = cem_row_doubles(P, HA, AA, NB); b.P = P; b.H = H; b.A = A; b.rows = rows; b.nb_cap = NB;
+    const size_t lds = sizeof(double) * ((size_t)(rows > 4 ? rows : 4) * HA + (1024 / AA) * AA + HA + A);    // (cem_select_moments')
+#define MJMPC_SELECT_MOMENTS_BATCH(NPER_)                                                                                    \
+    do {                                                                                                                     \
+        if (lds > 64 * 1024)                                                                                                 \
+            (void)hipFuncSetAttribute((const void*)kth_key_kernel<NPER_, T, true, true>,                                     \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                 \
+        hipLaunchKernelGGL((kth_key_kernel<NPER_, T, true, true>), dim3(NB, E), dim3(1024), lds, s, (const double*)nullptr,  \
+                           0L, 0L, (unsigned long long*)nullptr, 0L, 0L, (int*)nullptr, (int*)nullptr, b);                   \
+    } while (0)
+    if (P <= 4096) MJMPC_SELECT_MOMENTS_BATCH(4);           // (keys per thread by the population, as cem_select_moments)
+    else if (P <= 8192) MJMPC_SELECT_MOMENTS_BATCH(8);
+    else if (P <= 16384) MJMPC_SELECT_MOMENTS_BATCH(16);
+    else MJMPC_SELECT_MOMENTS_BATCH(32);
+#undef MJMPC_SELECT_MOMENTS_BATCH
+    return hipGetLastError();
+}
+
+template <typename T>
+hipError_t cem_finish_batch(int E, const long long* k, long P, int H, int A, int full, const double* step, int shift_mode,
+                            double* means, double* covs, double* chols, int* status, const double* grow_diag,
+                            const double* grow_scale, double* actions_out, long long* step_counter, T* noise,
+                            const unsigned long long* seeds, unsigned long long offset, double* ws, hipStream_t s) {
+    if (!cem_batch_supported(E, P, 1, H, A)) return hipErrorInvalidValue;
+    const int HA = H * A, AA = A * A, NB = cem_batch_slices(P, H, A);
+    CemFinishBatch b;
+    b.k = k; b.step = step; b.grow_diag = grow_diag; b.grow_scale = grow_scale; b.seeds = seeds;
+    b.means = means; b.covs = covs; b.chols = chols; b.actions_out = actions_out; b.ws = ws; b.status = status;
+    b.step_counter = step_counter; b.noise = (void*)noise;
+    b.stride = cem_row_doubles(P, HA, AA, NB); b.P = P; b.offset = offset;
+    b.H = H; b.A = A; b.rows = cem_fused_rows(H, A); b.nb_cap = NB; b.full = full; b.shift_mode = shift_mode;
+    const long items = P * ((H + 3) / 4);
+    long nwg = noise ? (items + CEM_FIN_THREADS - 1) / CEM_FIN_THREADS : 1;       // (cem_finish's, per row)
+    if (nwg < 1) nwg = 1;
+    if (nwg > 1024) nwg = 1024;
+    const size_t lds = cem_finish_batch_lds<T>(P, H, A);
+    if (lds > 150 * 1024) return hipErrorInvalidValue;
+    if (lds > 64 * 1024)
+        (void)hipFuncSetAttribute((const void*)cem_finish_batch_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(cem_finish_batch_kernel<T>, dim3((unsigned)nwg, (unsigned)E), dim3(CEM_FIN_THREADS), lds, s, b);
+    return hipGetLastError();
+}
+
 template <typename T>
 hipError_t cem_elite_cov(const T* actions, const double* mean, const double* sum_records, int G, long P, int H, int A,
                          double* crecord, double* ws, hipStream_t s) {
@@ -1748,6 +1929,13 @@ hipError_t step_tail(double* mean, int H, int A, int mode, const double* row, do
     template hipError_t cem_finish<T>(const double*, int, long, long, int, int, double, int, double, int, double*,   \
                                       double*, double*, int*, const double*, double, double*, double*, long long*, T*, \
                                       unsigned long long, unsigned long long, long, double*, hipStream_t);           \
+    template hipError_t cem_select_moments_batch<T>(int, const T*, const double*, const long long*, long, int, int,  \
+                                                    const double*, const double*, const long long*, double*,         \
+                                                    hipStream_t);                                                    \
+    template hipError_t cem_finish_batch<T>(int, const long long*, long, int, int, int, const double*, int, double*, \
+                                            double*, double*, int*, const double*, const double*, double*,           \
+                                            long long*, T*, const unsigned long long*, unsigned long long, double*,  \
+                                            hipStream_t);                                                            \
     template hipError_t rs_best<T>(const T*, long, long, int, int, double*, double*, hipStream_t);                   \
     template hipError_t mppi_fused_update<T>(const double*, const T*, double, double, int, long, int, int, double*,  \
                                              double*, double*, double*, double*, hipStream_t, double*, long long*,   \

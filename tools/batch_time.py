@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Episode batches (BatchedMPPI): ms per batched control step and episode-steps/s, against the sequential loop.
+"""Episode batches (BatchedMPPI / BatchedCEM): ms per batched control step and episode-steps/s, against the sequential loop.
 
 For every model x E x P x H: one ``BatchedMPPI`` of E episodes of P particles (f64), timed with device events over
 --steps control steps after --warmup; in the same process the single-episode device path on its own engine (MPPI,
@@ -8,7 +8,11 @@ the same way.  The sequential loop of E episodes costs E times that per control 
 the same shape).  One JSON line per configuration, then a table.
 
     python tools/batch_time.py [--models half_cheetah,swimmer,sawyer] [--E 1,4,16,64] [--P 256,1024] [--H 16,32]
-        [--model-shards K]
+        [--model-shards K] [--controller mppi|cem] [--repeats R]
+
+--controller cem: ``BatchedCEM`` (full covariance, elite_frac 0.1, beta 0.45) against the single-episode fused CEM
+step (CEM, noise_mode='device', graph replay).  --repeats R: every configuration is timed R times, batch and single runs
+alternating; the medians are reported with the single path's own spread (max - min over its repeats, ``single_spread_ms``).
 
 --model-shards K: the batch rolls out K randomized model shards per episode (a set per episode, body masses
 +- 20 %) and the single-episode path is the sequential dynamics-randomized loop - a K-shard engine with randomized blocks
@@ -36,10 +40,17 @@ def dyn_cfg(raw):
     return {"body_mass": {b.name: [0.2, 0.0] for b in [b for b in raw.bodies if b.joint is not None][:3]}}
 
 
-def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0):
+ELITE_FRAC, BETA = 0.1, 0.45       # (--controller cem)
+
+
+def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     import torch
-    from mjmpc_amd.control import BatchedMPPI
-    b = BatchedMPPI(raw, E, H, P, lam, 1.0, cov, 1.0, FILT, "null", [123 + i * 12345 for i in range(E)])
+    from mjmpc_amd.control import BatchedCEM, BatchedMPPI
+    seeds = [123 + i * 12345 for i in range(E)]
+    if controller == "cem":
+        b = BatchedCEM(raw, E, H, P, cov, ELITE_FRAC, 1.0, BETA, 1.0, FILT, "null", seeds)
+    else:
+        b = BatchedMPPI(raw, E, H, P, lam, 1.0, cov, 1.0, FILT, "null", seeds)
     b.on_env_reset = "ignore"
     if K:
         b.randomize_dynamics(dyn_cfg(raw), [123 + i * 12345 for i in range(E)], K)
@@ -55,9 +66,9 @@ def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0):
     return s.elapsed_time(e) / steps
 
 
-def time_single(raw, P, H, lam, cov, steps, warmup, K=0):
+def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     import torch
-    from mjmpc_amd.control import MPPI
+    from mjmpc_amd.control import CEM, MPPI
     from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
     from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
     eng = TreeRolloutEngine(raw, num_shards=max(K, 1))
@@ -65,9 +76,15 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0):
     if K:
         eng.randomize_dynamics(dyn_cfg(raw), 123)
         eng.set_real_env_model("nominal")
-    c = MPPI(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov, base_action="null", lam=lam,
-             num_particles=P, step_size=1.0, alpha=1, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
-             action_highs=eng.action_highs, filter_coeffs=FILT, seed=123, noise_mode="device", noise_dtype="f64")
+    if controller == "cem":
+        c = CEM(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov, base_action="null",
+                elite_frac=ELITE_FRAC, num_particles=P, step_size=1.0, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
+                action_highs=eng.action_highs, beta=BETA, cov_type="full", filter_coeffs=FILT, seed=123, noise_mode="device",
+                noise_dtype="f64")
+    else:
+        c = MPPI(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov, base_action="null",
+                 lam=lam, num_particles=P, step_size=1.0, alpha=1, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
+                 action_highs=eng.action_highs, filter_coeffs=FILT, seed=123, noise_mode="device", noise_dtype="f64")
     c.rollout_fn = make_device_rollout_fn(eng)
     c.set_sim_state_fn = lambda st: None
     c.enable_graph(post_step=eng.step_state)
@@ -80,6 +97,8 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0):
         c.optimize(None)
     e.record()
     torch.cuda.synchronize()
+    if controller == "cem" and not c._cem_fused():
+        raise SystemExit("the single-episode CEM path did not take its fused step at %d x %d" % (P, H))
     eng.close()
     return s.elapsed_time(e) / steps
 
@@ -93,6 +112,8 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--model-shards", type=int, default=0, help="randomized model shards per episode (0: no randomization)")
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem"])
+    ap.add_argument("--repeats", type=int, default=1, help="timings per configuration, batch and single runs alternating")
     args = ap.parse_args()
     from mjmpc_amd import _lib
     _lib.require_gpu()          # (no GPU: no numbers)
@@ -103,12 +124,24 @@ def main():
         raw = fn()
         for H in [int(x) for x in args.H.split(",")]:
             for P in [int(x) for x in args.P.split(",")]:
-                single = time_single(raw, P, H, lam, cov, args.steps, args.warmup, args.model_shards)
+                if args.repeats <= 1:
+                    single = time_single(raw, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller)
                 for E in [int(x) for x in args.E.split(",")]:
-                    batch = time_batch(raw, E, P, H, lam, cov, args.steps, args.warmup, args.model_shards)
-                    row = dict(model=name, E=E, P=P, H=H, model_shards=args.model_shards, batch_ms_per_step=round(batch, 4),
+                    spread = None
+                    if args.repeats > 1:        # batch, single, batch, single, ...: medians, and the single path's own spread
+                        bs, ss = [], []
+                        for _ in range(args.repeats):
+                            bs.append(time_batch(raw, E, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller))
+                            ss.append(time_single(raw, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller))
+                        batch, single, spread = sorted(bs)[len(bs) // 2], sorted(ss)[len(ss) // 2], max(ss) - min(ss)
+                    else:
+                        batch = time_batch(raw, E, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller)
+                    row = dict(model=name, controller=args.controller, E=E, P=P, H=H, model_shards=args.model_shards,
+                               batch_ms_per_step=round(batch, 4),
                                batch_episode_steps_per_s=round(1e3 * E / batch, 1), single_ms_per_step=round(single, 4),
                                sequential_ms_per_step=round(E * single, 4), speedup=round(E * single / batch, 2))
+                    if spread is not None:
+                        row.update(repeats=args.repeats, single_spread_ms=round(spread, 4))
                     rows.append(row)
                     print(json.dumps(row), flush=True)
     print("%-13s %3s %5s %3s %10s %10s %12s %8s" % ("model", "E", "P", "H", "batch ms", "single ms", "E x single", "speedup"))
