@@ -1,7 +1,8 @@
 #!/usr/bin/env python
-"""The config's ``n_episodes`` MPPI or CEM episodes as ONE batch on the tree engine (``BatchedMPPI`` / ``BatchedCEM``).
+"""The config's ``n_episodes`` MPPI, CEM or PFMPC episodes as ONE batch on the tree engine (``BatchedMPPI`` / ``BatchedCEM`` /
+``BatchedPFMPC``).
 
-    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi|cem]
+    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi|cem|pfmpc]
         [--dtype f64|f32] [--episodes N] [--dyn_randomize_config FILE [--num_cpu K] [--dyn_per_episode]]
 
 examples/example_mpc.py runs the episodes one after another (as the reference's job_script.py:80-99): episode i with seed
@@ -15,8 +16,10 @@ particles are split into the config's ``num_cpu`` shards and each shard rolls ou
 all episodes from the config's ``seed`` as the reference does before its episode loop (``--dyn_per_episode``: from every
 episode's own seed), while the real envs keep the nominal model - still one batch.
 
-The ``mppi`` and ``cem`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection + moments,
-refit + next samples and env-step launches per control step); other controller blocks are refused.  The reacher configs run on the TREE engine here
+The ``mppi``, ``cem`` and ``pfmpc`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection +
+moments, refit + next samples and env-step launches per control step; ``--controller pfmpc``: ``BatchedPFMPC``, DESIGN 10.3 -
+deviations, rollout, weights, resampling, gather + shift, mean + action and env step, e.g. examples/configs/reacher_gpu.yml);
+other controller blocks are refused.  The reacher configs run on the TREE engine here
 (sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
 rewards are not expected to be equal.
 """
@@ -31,15 +34,15 @@ import yaml
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from example_mpc import ENVS, TREE_MODELS                           # noqa: E402
-from mjmpc_amd.control import BatchedCEM, BatchedMPPI               # noqa: E402
+from mjmpc_amd.control import BatchedCEM, BatchedMPPI, BatchedPFMPC  # noqa: E402
 from mjmpc_amd.envs.tree_engine import TreeRolloutEngine            # noqa: E402
 from mjmpc_amd.models.reacher7dof import reacher7dof_raw            # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Run a config's MPPI or CEM episodes as one batch")
+    ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM or PFMPC episodes as one batch")
     ap.add_argument("--config", required=True, help="yaml file with experiment parameters")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem"],
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc"],
                     help="controller block of the config to run")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--episodes", type=int, help="override n_episodes")
@@ -78,6 +81,10 @@ def main():
                            params["step_size"], params.get("beta", 0.0), params["gamma"], params["filter_coeffs"], base_action,
                            seeds, cov_type=params.get("cov_type", "diagonal"), dtype=args.dtype,
                            n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
+    elif args.controller == "pfmpc":
+        batch = BatchedPFMPC(raw, E, params["horizon"], params["num_particles"], params["cov_shift"], params["cov_resample"],
+                             params["lam"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
+                             n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
     else:
         batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
                             params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,

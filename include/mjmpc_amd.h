@@ -659,6 +659,30 @@ int mjmpc_pf_finish(int64_t M, int H, int A, const void* d_ws, double* d_mean, d
                     void* stream);
 int mjmpc_pf_delta(int dtype, int64_t M, int H, int A, const double* d_set, const double* d_mean, void* d_delta, void* stream);
 
+/* Episode batches of the PFMPC step: E independent particle sets, the episode on a grid axis, no host
+ * synchronisation.  Row e of every launch executes the single launch's instructions on episode e's slices - d_sets float64
+ * [E][M][H][A], d_means float64 [E][H][A], d_q0 / d_weights float64 [E][M], d_first float64 [E], d_idx int32 [E][M], d_lams
+ * float64 [E] (> 0: only the host can check it), d_seeds uint64 [E], d_chols float64 [E][A][A] (the jitters' factors), d_delta
+ * dtype [E][M][H][A], d_gathered float64 [E][M][H][A] (may be NULL), d_actions float64 [E][A] (may be NULL) -; nothing is
+ * exchanged between rows and no workgroup straddles two rows.  M, H, A, shift_mode, d_coeffs, offset and d_step are shared by
+ * the batch; the Philox key's particle index is the index inside the episode.  *d_step_counter (may be NULL) is advanced
+ * once, by row 0 of mjmpc_pf_finish_batch: the episodes advance together.  1 <= E <= 65535; the other refusals are those of
+ * the single entry points.  d_ws: mjmpc_pf_batch_workspace_bytes(E, M, H, A) = E * mjmpc_pf_workspace_bytes(M, H, A) bytes
+ * (0 for bad sizes), 8-byte aligned, the same for resample, gather_shift and finish: the running sums [E][M], then the
+ * partial sums [E][nb][H A]. */
+int64_t mjmpc_pf_batch_workspace_bytes(int E, int64_t M, int H, int A);
+int mjmpc_pf_delta_batch(int dtype, int E, int64_t M, int H, int A, const double* d_sets, const double* d_means, void* d_delta,
+                         void* stream);
+int mjmpc_pf_weights_batch(int E, int64_t M, const double* d_q0, const double* d_lams, const uint64_t* d_seeds, uint64_t offset,
+                           const int64_t* d_step, double* d_weights, double* d_first, void* stream);
+int mjmpc_pf_resample_batch(int E, int64_t M, const double* d_weights, const double* d_first, int32_t* d_idx, void* d_ws,
+                            void* stream);
+int mjmpc_pf_gather_shift_batch(int E, int64_t M, int H, int A, const double* d_sets, const int32_t* d_idx, int shift_mode,
+                                const double* d_chols, const double* d_coeffs, const uint64_t* d_seeds, uint64_t offset,
+                                const int64_t* d_step, double* d_sets_out, double* d_gathered, void* d_ws, void* stream);
+int mjmpc_pf_finish_batch(int E, int64_t M, int H, int A, const void* d_ws, double* d_means, double* d_actions,
+                          int64_t* d_step_counter, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

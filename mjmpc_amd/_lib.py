@@ -128,6 +128,13 @@ SIGNATURES = {
                                      _vp, _vp]),
     "mjmpc_pf_finish": (_int, [_i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_pf_delta": (_int, [_int, _i64, _int, _int, _vp, _vp, _vp, _vp]),
+    "mjmpc_pf_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int]),
+    "mjmpc_pf_delta_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp]),
+    "mjmpc_pf_weights_batch": (_int, [_int, _i64, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "mjmpc_pf_resample_batch": (_int, [_int, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_pf_gather_shift_batch": (_int, [_int, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,
+                                           _vp, _vp]),
+    "mjmpc_pf_finish_batch": (_int, [_int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

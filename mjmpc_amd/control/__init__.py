@@ -8,6 +8,7 @@ _WHERE = {
     "RandomShooting": "random_shooting", "PFMPC": "particle_filter_controller",
     "BatchedMPPI": "batched",           # (no reference counterpart: the reference's episode loop as one batch)
     "BatchedCEM": "batched",
+    "BatchedPFMPC": "batched",
 }
 __all__ = sorted(_WHERE)
 

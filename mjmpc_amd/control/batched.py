@@ -1,4 +1,4 @@
-"""Episode batches: E independent MPPI or CEM episodes side by side on the tree engine.
+"""Episode batches: E independent MPPI, CEM or PFMPC episodes side by side on the tree engine.
 
 The reference runs its experiments one episode after another (examples/job_script.py:80-99, the episode loop of
 examples/example_mpc.py), each with its own seed (``seed + i*12345``) and start state, and its "tune" mode multiplies
@@ -23,8 +23,10 @@ the batch: the model, ``horizon``, ``num_particles`` (per episode), ``gamma``, `
 the dtype.  The batch's E real envs are the state shards of the batch's own engine (``mjmpc_tree_step_shard_states``).
 
 ``BatchedCEM`` is the same batch for the cross-entropy method (cem.py): per episode also ``elite_frac`` and
-``beta``, and a covariance that is refitted from the elites on the device.  Both classes share ``_EpisodeBatch``: the engine,
-the state shards, the buffers, the rollout launch, the env step, ``run`` and dynamics randomization.
+``beta``, and a covariance that is refitted from the elites on the device.  ``BatchedPFMPC`` is the batch of particle-filter
+MPC (particle_filter_controller.py, ``noise_mode='device'``): per episode ``lam``, ``cov_shift`` and
+``cov_resample``, and a particle set that is resampled on the device.  The classes share ``_EpisodeBatch``: the engine, the
+state shards, the buffers, the rollout launch, the env step, ``run`` and dynamics randomization.
 """
 import ctypes
 
@@ -455,3 +457,122 @@ class BatchedCEM(_EpisodeBatch):
         raise _lib.MjmpcError("the action covariance of episode%s %s on the device is indefinite or not finite: its Cholesky "
                               "factor (sampler colouring) does not exist"
                               % ("" if bad.size == 1 else "s", ", ".join(str(int(e)) for e in bad)))
+
+
+class BatchedPFMPC(_EpisodeBatch):
+    """``num_episodes`` particle-filter MPC controllers (particle_filter_controller.py, one iteration per step) and their real
+    envs, stepped together.
+
+    Episode e computes the bits of ``PFMPC(..., noise_mode='device', seed=seeds[e])`` on a ``TreeRolloutEngine`` of its own with
+    ``make_device_rollout_fn``, ``set_sim_state_fn = resident_state`` and ``set_post_step(engine.step_state)``, whose
+    ``optimize()`` is called with ``hotstart=True``.  ``lam``, ``cov_shift`` and ``cov_resample`` (scalar variances, as ``PFMPC``
+    takes them) take one value for every episode or one per episode; ``seeds`` one seed per episode.  A control step is seven
+    launches - deviations, rollout, weights + first pointer, resampling, gather + shift, mean + action, real-env step - and
+    nothing synchronises.  ``keep_stages=True`` also keeps the unshifted survivors, for ``last_step()``.  Settings the batch
+    does not run raise ``ValueError`` before any engine or device memory exists: ``n_iters != 1``, ``sample_mode != 'mean'``,
+    ``gamma == 0``, ``base_action`` other than ``'null'`` / ``'repeat'``, ``lam <= 0``, a negative ``cov_shift``,
+    ``cov_resample <= 0``, a wrong seed count and a model the tree engine refuses."""
+
+    def __init__(self, raw_model, num_episodes, horizon, num_particles, cov_shift, cov_resample, lam, gamma, filter_coeffs,
+                 base_action, seeds, dtype="f64", device=0, n_iters=1, sample_mode="mean", keep_stages=False):
+        # -- everything that can be refused is refused here, before the engine and its device memory exist
+        E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, False, sample_mode, dtype,
+                                         gamma, filter_coeffs, "PFMPC")
+        if base_action == "repeat" and H < 2:
+            raise ValueError("base_action 'repeat' needs a horizon of at least 2")
+        lam = _per_episode("lam", lam, E)
+        cov_shift = _per_episode("cov_shift", cov_shift, E)
+        cov_resample = _per_episode("cov_resample", cov_resample, E)
+        if not np.all(lam > 0):
+            raise ValueError("lam must be positive")
+        if not np.all(cov_shift >= 0):
+            raise ValueError("cov_shift must not be negative")
+        if not np.all(cov_resample > 0):
+            raise ValueError("cov_resample must be positive")
+        self.seed_vals = self._check_seeds(seeds, E)
+        model = self._compile(raw_model)
+        A = model.nu
+        lib = _lib.load()
+        nbytes = lib.mjmpc_pf_batch_workspace_bytes(E, P, H, A)
+        if nbytes <= 0:
+            raise ValueError("no particle-filter workspace for E = %d, P = %d, H = %d, A = %d" % (E, P, H, A))
+        # the first sets' factors (DeviceUpdater.prepare_noise: the Cholesky factor of cov_resample I and its diagonal flag)
+        factors = [noise_factor(np.diag(np.full(A, c))) for c in cov_resample]
+
+        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+        f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, np.zeros((E, H, A)))
+        torch, dev = self.torch, self.device
+        self.lam, self.cov_shift, self.cov_resample, self.keep_stages = lam, cov_shift, cov_resample, bool(keep_stages)
+        self._set, self._set_alt = (torch.empty((E, P, H, A), **f64) for _ in range(2))
+        self._gathered = torch.empty((E, P, H, A), **f64) if self.keep_stages else None
+        self._w, self._first = torch.empty((E, P), **f64), torch.zeros(E, **f64)
+        self._idx = torch.empty((E, P), dtype=torch.int32, device=dev)
+        self._lam = torch.from_numpy(lam.copy()).to(dev)
+        # the jitters' factors: cov_shift is c I, its factor sqrt(c) I (a zero variance is a zero jitter, not an error)
+        self._chols = torch.from_numpy(np.stack([np.sqrt(np.diag(np.full(A, c))) for c in cov_shift])).to(dev)
+        self._init_chols = [(torch.from_numpy(np.ascontiguousarray(f[0])).to(dev), f[1]) for f in factors]
+        identity = fc[0] == 1.0 and fc[1] == 0.0 and fc[2] == 0.0
+        self._shift_coeffs = None if identity else self._coeffs           # (as the single path hands them to the gather)
+        self._ws = torch.empty((nbytes + 7) // 8, **f64)
+        self._delta = self._noise                                         # (the rollout launch's noise is set - mean)
+        self._stepped = False
+        self._draw_initial_sets()
+        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+
+    def _draw_initial_sets(self):
+        """Row e <- the single path's first set: ``DeviceUpdater.sample_noise(P, cov_resample_e I, filter_coeffs, seed_e, 0,
+        'f64')``, E calls of the single sampler (off the hot path)."""
+        P, H, A, s = self.num_particles, self.horizon, self.d_action, self._stream()
+        for e, (chol, diag) in enumerate(self._init_chols):
+            _lib.check(self.lib.mjmpc_sample_noise(_lib.F64, _vp(self._set[e]), P, H, A, _vp(chol), _vp(self._coeffs),
+                                                   int(self.seed_vals[e]) & (2 ** 64 - 1), 0, 0, None, diag, s))
+
+    @property
+    def action_samples(self):
+        """The E particle sets the next step rolls out, ``(E, P, H, A)`` (synchronises)."""
+        out = self._set.cpu().numpy().copy()
+        self._check_status()
+        return out
+
+    def reset(self):
+        """Every episode back to its initial set, a zero mean and step 0 (the real envs keep their states)."""
+        super().reset()
+        self._draw_initial_sets()
+        self._stepped = False
+
+    def step(self, _out=None):
+        """Enqueue one control step of every episode (deviations, rollouts, weights, resampling, gather + shift, mean + action,
+        real-env step) without a host synchronisation.  The actions, real-env costs and next observations stay on the device."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
+        lib, code, s = self.lib, self._code, self._stream()
+        _lib.check(lib.mjmpc_pf_delta_batch(code, E, P, H, A, _vp(self._set), _vp(self._means), _vp(self._delta), s))
+        # (the set is filtered already: the rollout takes the deviations as they are, as the single path's fused(.., None, ..))
+        _lib.check(lib.mjmpc_tree_rollout_fused_batch(self.engine._h, code, E * P, H, _vp(self._means), _vp(self._delta), None,
+                                                      _vp(self._gseq), _vp(self._costs), _vp(self._actions), _vp(self._q0), s))
+        _lib.check(lib.mjmpc_pf_weights_batch(E, P, _vp(self._q0), _vp(self._lam), _vp(self._seeds), 0, _vp(self._step_dev),
+                                              _vp(self._w), _vp(self._first), s))
+        _lib.check(lib.mjmpc_pf_resample_batch(E, P, _vp(self._w), _vp(self._first), _vp(self._idx), _vp(self._ws), s))
+        # (keyed with offset k + 1: the reference increments num_steps before _shift)
+        _lib.check(lib.mjmpc_pf_gather_shift_batch(E, P, H, A, _vp(self._set), _vp(self._idx), _SHIFT_MODES[self.base_action],
+                                                   _vp(self._chols), _vp(self._shift_coeffs), _vp(self._seeds), 1,
+                                                   _vp(self._step_dev), _vp(self._set_alt), _vp(self._gathered), _vp(self._ws),
+                                                   s))
+        _lib.check(lib.mjmpc_pf_finish_batch(E, P, H, A, _vp(self._ws), _vp(self._means), _vp(act), _vp(self._step_dev), s))
+        self._env_step(act, cost, nobs, s)
+        self._set, self._set_alt = self._set_alt, self._set
+        self.num_steps += 1
+        self._stepped = True
+        return act, cost, nobs
+
+    def last_step(self):
+        """The stages of the last step as device tensors with a leading E axis (valid until the next step), as
+        ``PFMPC.last_device_step`` names them: ``samples`` the sets that were rolled out, ``costs`` / ``q0`` what the rollout
+        returned, ``w``, ``first``, ``idx``, ``resampled`` = samples[idx], ``mean`` of it, ``shifted`` the sets the next step
+        rolls out, ``step`` the count k the step was keyed with.  Needs ``keep_stages=True`` and a step."""
+        if not self.keep_stages or not self._stepped:
+            raise ValueError("last_step needs keep_stages=True and a finished step")
+        E, P, H = self.num_episodes, self.num_particles, self.horizon
+        return dict(samples=self._set_alt, costs=self._costs.view(E, P, H), q0=self._q0.view(E, P), w=self._w,
+                    first=self._first, idx=self._idx, resampled=self._gathered, mean=self._means, shifted=self._set,
+                    step=self.num_steps - 1)

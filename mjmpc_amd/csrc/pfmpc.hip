@@ -49,10 +49,12 @@ __device__ __forceinline__ double block_reduce(double v, double* sm, bool is_max
     return r;
 }
 
-__global__ __launch_bounds__(PF_WG) void pf_weights_kernel(const double* __restrict__ q0, long M, double lam,
-                                                           unsigned long long seed, unsigned long long offset,
-                                                           const long long* __restrict__ d_step, double* __restrict__ w,
-                                                           double* __restrict__ first) {
+// The bodies below are what a launch does for ONE particle set: the single kernels run them on their arguments, the
+// episode batches' twins (pf_*_batch_kernel) on row e's slices - the same instructions, nothing is exchanged
+// between rows, no workgroup straddles two rows.
+__device__ __forceinline__ void pf_weights_body(const double* __restrict__ q0, long M, double lam, unsigned long long seed,
+                                                unsigned long long offset, const long long* __restrict__ d_step,
+                                                double* __restrict__ w, double* __restrict__ first) {
     __shared__ double sm[PF_WG / 64];
     const double neg_inv_lam = -1.0 / lam;
     // (a rollout that diverged carries a non-finite return: zero weight, as traj_cost_kernel has it)
@@ -82,16 +84,45 @@ __global__ __launch_bounds__(PF_WG) void pf_weights_kernel(const double* __restr
     }
 }
 
+__global__ __launch_bounds__(PF_WG) void pf_weights_kernel(const double* __restrict__ q0, long M, double lam,
+                                                           unsigned long long seed, unsigned long long offset,
+                                                           const long long* __restrict__ d_step, double* __restrict__ w,
+                                                           double* __restrict__ first) {
+    pf_weights_body(q0, M, lam, seed, offset, d_step, w, first);
+}
+
+// workgroup e = episode e: q0, w [E][M]; lams, seeds, first [E]
+__global__ __launch_bounds__(PF_WG) void pf_weights_batch_kernel(const double* __restrict__ q0, long M,
+                                                                 const double* __restrict__ lams,
+                                                                 const unsigned long long* __restrict__ seeds,
+                                                                 unsigned long long offset,
+                                                                 const long long* __restrict__ d_step,
+                                                                 double* __restrict__ w, double* __restrict__ first) {
+    const long e = blockIdx.x;
+    pf_weights_body(q0 + e * M, M, lams[e], seeds[e], offset, d_step, w + e * M, first + e);
+}
+
 // idx[m] of the systematic resampling.  The running sum is ONE chain of M dependent float64 additions (about M x the
 // latency of v_add_f64: linear in M, and nothing may reassociate it without changing np.cumsum's bits); per tile the
 // workgroup stages PF_TILE weights into LDS, lane 0 turns them into running sums in place, eight loads ahead of the chain,
 // and the workgroup copies the tile out, keeping every `stride`-th running sum (and the last) in LDS.  The search is one
 // binary search per pointer: over that coarse table in LDS, then over the one block of `stride` running sums it names.
+// EB (episode batches): workgroup e = episode e - w, running, idx [E][M], first [E] -, and the E serial chains
+// run side by side on different CUs.  A template switch and not a __device__ body as the other launches have it: the
+// body cost pf_resample_kernel two scalar registers, the switch none.
+template <bool EB>
 __global__ __launch_bounds__(PF_WG) void pf_resample_kernel(const double* __restrict__ w, const double* __restrict__ first,
                                                             long M, long stride, double* __restrict__ running,
                                                             int* __restrict__ idx) {
     __shared__ double tile[PF_TILE];
     __shared__ double coarse[PF_COARSE];
+    if (EB) {
+        const long e = blockIdx.x;
+        w += e * M;
+        first += e;
+        running += e * M;
+        idx += e * M;
+    }
     double c = 0.0;                             // (lane 0's: the running sum so far)
     for (long base = 0; base < M; base += PF_TILE) {
         const int n = (int)((M - base) < PF_TILE ? (M - base) : PF_TILE);
@@ -152,14 +183,11 @@ __global__ __launch_bounds__(PF_WG) void pf_resample_kernel(const double* __rest
 // filter's carry runs along it - and writes the shifted survivor into `dst` (shift_mode < 0: the survivor as it is); then
 // lanes along the contiguous H A axis add the chunk's survivors in particle order into partial[b][H A].  `gathered` (may
 // be null) receives the unshifted survivors.
-__global__ __launch_bounds__(PF_BLK) void pf_gather_shift_kernel(const double* __restrict__ src, const int* __restrict__ idx,
-                                                                 long M, int H, int A, int shift_mode,
-                                                                 const double* __restrict__ chol,
-                                                                 const double* __restrict__ coeffs, unsigned long long seed,
-                                                                 unsigned long long offset,
-                                                                 const long long* __restrict__ d_step,
-                                                                 double* __restrict__ dst, double* __restrict__ gathered,
-                                                                 double* __restrict__ partial) {
+__device__ __forceinline__ void pf_gather_shift_body(const double* __restrict__ src, const int* __restrict__ idx, long M,
+                                                     int H, int A, int shift_mode, const double* __restrict__ chol,
+                                                     const double* __restrict__ coeffs, unsigned long long seed,
+                                                     unsigned long long offset, const long long* __restrict__ d_step,
+                                                     double* __restrict__ dst, double* __restrict__ gathered) {
     const long p0 = (long)blockIdx.x * PF_CHUNK;
     const int n = (int)((M - p0) < PF_CHUNK ? (M - p0) : PF_CHUNK);
     const int HA = H * A;
@@ -199,6 +227,13 @@ __global__ __launch_bounds__(PF_BLK) void pf_gather_shift_kernel(const double* _
             }
         }
     }
+}
+
+// (the second half of the launch: the chunk's survivors added in particle order)
+__device__ __forceinline__ void pf_chunk_sum_body(const double* __restrict__ src, const int* __restrict__ idx, long M, int HA,
+                                                  double* __restrict__ partial) {
+    const long p0 = (long)blockIdx.x * PF_CHUNK;
+    const int n = (int)((M - p0) < PF_CHUNK ? (M - p0) : PF_CHUNK);
     for (int j = threadIdx.x; j < HA; j += PF_BLK) {
         double s = 0.0;
         for (int q = 0; q < n; ++q) {
@@ -209,9 +244,42 @@ __global__ __launch_bounds__(PF_BLK) void pf_gather_shift_kernel(const double* _
     }
 }
 
+__global__ __launch_bounds__(PF_BLK) void pf_gather_shift_kernel(const double* __restrict__ src, const int* __restrict__ idx,
+                                                                 long M, int H, int A, int shift_mode,
+                                                                 const double* __restrict__ chol,
+                                                                 const double* __restrict__ coeffs, unsigned long long seed,
+                                                                 unsigned long long offset,
+                                                                 const long long* __restrict__ d_step,
+                                                                 double* __restrict__ dst, double* __restrict__ gathered,
+                                                                 double* __restrict__ partial) {
+    pf_gather_shift_body(src, idx, M, H, A, shift_mode, chol, coeffs, seed, offset, d_step, dst, gathered);
+    pf_chunk_sum_body(src, idx, M, H * A, partial);
+}
+
+// grid (chunks of PF_CHUNK particles, E): src, dst, gathered [E][M][H A]; idx [E][M]; chols [E][A A]; seeds [E]; partial
+// [E][nb][H A].  p of the body - the Philox key's particle index - is the index inside the episode.  `set_n` = M H A and
+// `part_n` = nb H A come from the host (formed here they cost 2 SGPRs and 8 VGPRs).
+__global__ __launch_bounds__(PF_BLK) void pf_gather_shift_batch_kernel(const double* __restrict__ src,
+                                                                       const int* __restrict__ idx, long M, int H, int A,
+                                                                       int shift_mode, const double* __restrict__ chols,
+                                                                       const double* __restrict__ coeffs,
+                                                                       const unsigned long long* __restrict__ seeds,
+                                                                       unsigned long long offset,
+                                                                       const long long* __restrict__ d_step,
+                                                                       double* __restrict__ dst, double* __restrict__ gathered,
+                                                                       double* __restrict__ partial, long set_n, long part_n) {
+    const long e = blockIdx.y, set = e * set_n;
+    // (the two halves are independent - the sums read src and idx only -: the cheap one first, so that its operands are
+    // dead where the shift needs the scalar registers; in the single kernel's order this twin spills 4 to 6 SGPRs)
+    pf_chunk_sum_body(src + set, idx + e * M, M, H * A, partial + e * part_n);
+    pf_gather_shift_body(src + set, idx + e * M, M, H, A, shift_mode, chols ? chols + e * (A * A) : nullptr, coeffs, seeds[e],
+                         offset, d_step, dst + set, gathered ? gathered + set : nullptr);
+}
+
 // mean[j] = (sum over the workgroups' partials) / M, one wavefront per entry; action = mean[0 .. A); the step counter moves
-__global__ void pf_finish_kernel(const double* __restrict__ partial, int nb, int HA, int A, long M, double* __restrict__ mean,
-                                 double* __restrict__ action_out, long long* __restrict__ step_counter) {
+__device__ __forceinline__ void pf_finish_body(const double* __restrict__ partial, int nb, int HA, int A, long M,
+                                               double* __restrict__ mean, double* __restrict__ action_out,
+                                               long long* __restrict__ step_counter) {
     const int j = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (j >= HA) return;
     const int l = threadIdx.x & 63;
@@ -226,11 +294,40 @@ __global__ void pf_finish_kernel(const double* __restrict__ partial, int nb, int
     }
 }
 
+__global__ void pf_finish_kernel(const double* __restrict__ partial, int nb, int HA, int A, long M, double* __restrict__ mean,
+                                 double* __restrict__ action_out, long long* __restrict__ step_counter) {
+    pf_finish_body(partial, nb, HA, A, M, mean, action_out, step_counter);
+}
+
+// grid (entries of the mean / wavefronts per workgroup, E): partial [E][nb][H A]; mean [E][H A]; action_out [E][A].  The
+// episodes advance together: row 0 alone moves the one step counter (as mjmpc_mppi_fused_update_batch has it).
+__global__ void pf_finish_batch_kernel(const double* __restrict__ partial, int nb, int HA, int A, long M,
+                                       double* __restrict__ mean, double* __restrict__ action_out,
+                                       long long* __restrict__ step_counter) {
+    const long e = blockIdx.y;
+    pf_finish_body(partial + e * nb * HA, nb, HA, A, M, mean + e * HA, action_out ? action_out + e * A : nullptr,
+                   e == 0 ? step_counter : nullptr);
+}
+
+template <typename T>
+__device__ __forceinline__ void pf_delta_body(const double* __restrict__ set, const double* __restrict__ mean, long n, int HA,
+                                              T* __restrict__ delta) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) delta[i] = (T)(set[i] - mean[i % HA]);
+}
+
 template <typename T>
 __global__ void pf_delta_kernel(const double* __restrict__ set, const double* __restrict__ mean, long n, int HA,
                                 T* __restrict__ delta) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) delta[i] = (T)(set[i] - mean[i % HA]);
+    pf_delta_body(set, mean, n, HA, delta);
+}
+
+// grid (elements of one set / PF_BLK, E): sets, delta [E][n]; means [E][H A]
+template <typename T>
+__global__ void pf_delta_batch_kernel(const double* __restrict__ sets, const double* __restrict__ means, long n, int HA,
+                                      T* __restrict__ delta) {
+    const long e = blockIdx.y;
+    pf_delta_body(sets + e * n, means + e * HA, n, HA, delta + e * n);
 }
 
 int bad(const char* what, const char* detail) { return set_error(MJMPC_E_BADARG, what, detail); }
@@ -265,7 +362,7 @@ int mjmpc_pf_resample(int64_t M, const double* d_weights, const double* d_first,
     if (M < 1 || M > INT32_MAX) return mjmpc::bad("mjmpc_pf_resample", "needs 1 <= M < 2^31");
     long stride = 16;                   // a power of two: M / stride entries fit the coarse table
     while ((M + stride - 1) / stride > mjmpc::PF_COARSE) stride *= 2;
-    hipLaunchKernelGGL(mjmpc::pf_resample_kernel, dim3(1), dim3(mjmpc::PF_WG), 0, (hipStream_t)stream, d_weights, d_first,
+    hipLaunchKernelGGL(mjmpc::pf_resample_kernel<false>, dim3(1), dim3(mjmpc::PF_WG), 0, (hipStream_t)stream, d_weights, d_first,
                        (long)M, stride, (double*)d_ws, (int*)d_idx);
     return mjmpc::launched("mjmpc_pf_resample");
 }
@@ -311,6 +408,88 @@ int mjmpc_pf_delta(int dtype, int64_t M, int H, int A, const double* d_set, cons
         hipLaunchKernelGGL(mjmpc::pf_delta_kernel<double>, grid, block, 0, (hipStream_t)stream, d_set, d_mean, n, H * A,
                            (double*)d_delta);
     return mjmpc::launched("mjmpc_pf_delta");
+}
+
+// ---- episode batches: row e of every launch is the single launch on episode e's slices.  d_ws holds the
+// running sums [E][M], then the partial sums [E][nb][H A].
+int64_t mjmpc_pf_batch_workspace_bytes(int E, int64_t M, int H, int A) {
+    if (E < 1 || E > 65535) return 0;
+    return (int64_t)E * mjmpc_pf_workspace_bytes(M, H, A);
+}
+
+int mjmpc_pf_delta_batch(int dtype, int E, int64_t M, int H, int A, const double* d_sets, const double* d_means, void* d_delta,
+                         void* stream) {
+    if (!d_sets || !d_means || !d_delta) return mjmpc::bad("mjmpc_pf_delta_batch", "null argument");
+    if (E < 1 || E > 65535) return mjmpc::bad("mjmpc_pf_delta_batch", "needs 1 <= E <= 65535");
+    if (M < 1 || M > INT32_MAX || H < 1 || A < 1) return mjmpc::bad("mjmpc_pf_delta_batch", "bad shape");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64)
+        return mjmpc::bad("mjmpc_pf_delta_batch", "dtype must be MJMPC_F32 or MJMPC_F64");
+    const long n = (long)M * H * A;
+    const long blocks = (n + mjmpc::PF_BLK - 1) / mjmpc::PF_BLK;
+    if (blocks > INT32_MAX) return mjmpc::bad("mjmpc_pf_delta_batch", "a set of more than 2^31 workgroups");
+    const dim3 grid((unsigned)blocks, (unsigned)E), block(mjmpc::PF_BLK);
+    if (dtype == MJMPC_F32)
+        hipLaunchKernelGGL(mjmpc::pf_delta_batch_kernel<float>, grid, block, 0, (hipStream_t)stream, d_sets, d_means, n, H * A,
+                           (float*)d_delta);
+    else
+        hipLaunchKernelGGL(mjmpc::pf_delta_batch_kernel<double>, grid, block, 0, (hipStream_t)stream, d_sets, d_means, n,
+                           H * A, (double*)d_delta);
+    return mjmpc::launched("mjmpc_pf_delta_batch");
+}
+
+int mjmpc_pf_weights_batch(int E, int64_t M, const double* d_q0, const double* d_lams, const uint64_t* d_seeds, uint64_t offset,
+                           const int64_t* d_step, double* d_weights, double* d_first, void* stream) {
+    if (!d_q0 || !d_lams || !d_seeds || !d_weights || !d_first) return mjmpc::bad("mjmpc_pf_weights_batch", "null argument");
+    if (E < 1 || E > 65535) return mjmpc::bad("mjmpc_pf_weights_batch", "needs 1 <= E <= 65535");
+    if (M < 1 || M > INT32_MAX) return mjmpc::bad("mjmpc_pf_weights_batch", "needs 1 <= M < 2^31");
+    hipLaunchKernelGGL(mjmpc::pf_weights_batch_kernel, dim3((unsigned)E), dim3(mjmpc::PF_WG), 0, (hipStream_t)stream, d_q0,
+                       (long)M, d_lams, (const unsigned long long*)d_seeds, (unsigned long long)offset,
+                       (const long long*)d_step, d_weights, d_first);
+    return mjmpc::launched("mjmpc_pf_weights_batch");
+}
+
+int mjmpc_pf_resample_batch(int E, int64_t M, const double* d_weights, const double* d_first, int32_t* d_idx, void* d_ws,
+                            void* stream) {
+    if (!d_weights || !d_first || !d_idx || !d_ws) return mjmpc::bad("mjmpc_pf_resample_batch", "null argument");
+    if (E < 1 || E > 65535) return mjmpc::bad("mjmpc_pf_resample_batch", "needs 1 <= E <= 65535");
+    if (M < 1 || M > INT32_MAX) return mjmpc::bad("mjmpc_pf_resample_batch", "needs 1 <= M < 2^31");
+    long stride = 16;                   // (as mjmpc_pf_resample forms it: a row searches as the single launch does)
+    while ((M + stride - 1) / stride > mjmpc::PF_COARSE) stride *= 2;
+    hipLaunchKernelGGL(mjmpc::pf_resample_kernel<true>, dim3((unsigned)E), dim3(mjmpc::PF_WG), 0, (hipStream_t)stream,
+                       d_weights, d_first, (long)M, stride, (double*)d_ws, (int*)d_idx);
+    return mjmpc::launched("mjmpc_pf_resample_batch");
+}
+
+int mjmpc_pf_gather_shift_batch(int E, int64_t M, int H, int A, const double* d_sets, const int32_t* d_idx, int shift_mode,
+                                const double* d_chols, const double* d_coeffs, const uint64_t* d_seeds, uint64_t offset,
+                                const int64_t* d_step, double* d_sets_out, double* d_gathered, void* d_ws, void* stream) {
+    const char* what = "mjmpc_pf_gather_shift_batch";
+    if (!d_sets || !d_idx || !d_seeds || !d_sets_out || !d_ws) return mjmpc::bad(what, "null argument");
+    if (d_sets == d_sets_out) return mjmpc::bad(what, "the gather cannot be in place");
+    if (E < 1 || E > 65535) return mjmpc::bad(what, "needs 1 <= E <= 65535");
+    if (M < 1 || M > INT32_MAX || H < 1 || A < 1) return mjmpc::bad(what, "bad shape");
+    if (shift_mode > 1) return mjmpc::bad(what, "shift_mode must be 0 'null', 1 'repeat' or < 0 none");
+    if (shift_mode >= 0 && !d_chols) return mjmpc::bad(what, "the shift needs the jitter's factors");
+    if (shift_mode == 1 && H < 2) return mjmpc::bad(what, "'repeat' needs a horizon of at least 2");
+    const int64_t nb = (M + mjmpc::PF_CHUNK - 1) / mjmpc::PF_CHUNK;
+    hipLaunchKernelGGL(mjmpc::pf_gather_shift_batch_kernel, dim3((unsigned)nb, (unsigned)E), dim3(mjmpc::PF_BLK), 0,
+                       (hipStream_t)stream, d_sets, (const int*)d_idx, (long)M, H, A, shift_mode, d_chols, d_coeffs,
+                       (const unsigned long long*)d_seeds, (unsigned long long)offset, (const long long*)d_step, d_sets_out,
+                       d_gathered, (double*)d_ws + (int64_t)E * M, (long)M * H * A, (long)nb * H * A);
+    return mjmpc::launched(what);
+}
+
+int mjmpc_pf_finish_batch(int E, int64_t M, int H, int A, const void* d_ws, double* d_means, double* d_actions,
+                          int64_t* d_step_counter, void* stream) {
+    if (!d_ws || !d_means) return mjmpc::bad("mjmpc_pf_finish_batch", "null argument");
+    if (E < 1 || E > 65535) return mjmpc::bad("mjmpc_pf_finish_batch", "needs 1 <= E <= 65535");
+    if (M < 1 || M > INT32_MAX || H < 1 || A < 1) return mjmpc::bad("mjmpc_pf_finish_batch", "bad shape");
+    const int64_t nb = (M + mjmpc::PF_CHUNK - 1) / mjmpc::PF_CHUNK;
+    const int HA = H * A, per = mjmpc::PF_BLK / 64;
+    hipLaunchKernelGGL(mjmpc::pf_finish_batch_kernel, dim3((unsigned)((HA + per - 1) / per), (unsigned)E),
+                       dim3(mjmpc::PF_BLK), 0, (hipStream_t)stream, (const double*)d_ws + (int64_t)E * M, (int)nb, HA, A,
+                       (long)M, d_means, d_actions, (long long*)d_step_counter);
+    return mjmpc::launched("mjmpc_pf_finish_batch");
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Episode batches (BatchedMPPI / BatchedCEM): ms per batched control step and episode-steps/s, against the sequential loop.
+"""Episode batches (BatchedMPPI / BatchedCEM / BatchedPFMPC): ms per batched control step and episode-steps/s, against the sequential loop.
 
 For every model x E x P x H: one ``BatchedMPPI`` of E episodes of P particles (f64), timed with device events over
 --steps control steps after --warmup; in the same process the single-episode device path on its own engine (MPPI,
@@ -8,11 +8,16 @@ the same way.  The sequential loop of E episodes costs E times that per control 
 the same shape).  One JSON line per configuration, then a table.
 
     python tools/batch_time.py [--models half_cheetah,swimmer,sawyer] [--E 1,4,16,64] [--P 256,1024] [--H 16,32]
-        [--model-shards K] [--controller mppi|cem] [--repeats R]
+        [--model-shards K] [--controller mppi|cem|pfmpc] [--repeats R]
 
 --controller cem: ``BatchedCEM`` (full covariance, elite_frac 0.1, beta 0.45) against the single-episode fused CEM
 step (CEM, noise_mode='device', graph replay).  --repeats R: every configuration is timed R times, batch and single runs
 alternating; the medians are reported with the single path's own spread (max - min over its repeats, ``single_spread_ms``).
+
+--controller pfmpc: ``BatchedPFMPC`` (cov_shift 0.02, cov_resample = the model's init_cov, lam 1.0) against the
+single-episode device path of particle-filter MPC (PFMPC, noise_mode='device', the resident real env stepped by
+``set_post_step(engine.step_state)``; its ``optimize()`` waits for the action once per step, as that loop does).  After the
+table: the per-launch split of one batched step (device events around every launch, so their sum exceeds the step's time).
 
 --model-shards K: the batch rolls out K randomized model shards per episode (a set per episode, body masses
 +- 20 %) and the single-episode path is the sequential dynamics-randomized loop - a K-shard engine with randomized blocks
@@ -41,16 +46,62 @@ def dyn_cfg(raw):
 
 
 ELITE_FRAC, BETA = 0.1, 0.45       # (--controller cem)
+COV_SHIFT, PF_LAM, PF_GAMMA = 0.02, 1.0, 0.99       # (--controller pfmpc)
+PF_LAUNCHES = ("mjmpc_pf_delta_batch", "mjmpc_tree_rollout_fused_batch", "mjmpc_pf_weights_batch", "mjmpc_pf_resample_batch",
+               "mjmpc_pf_gather_shift_batch", "mjmpc_pf_finish_batch", "mjmpc_tree_step_shard_states")
+
+
+def make_batch(raw, E, P, H, lam, cov, controller):
+    from mjmpc_amd.control import BatchedCEM, BatchedMPPI, BatchedPFMPC
+    seeds = [123 + i * 12345 for i in range(E)]
+    if controller == "cem":
+        return BatchedCEM(raw, E, H, P, cov, ELITE_FRAC, 1.0, BETA, 1.0, FILT, "null", seeds)
+    if controller == "pfmpc":
+        return BatchedPFMPC(raw, E, H, P, COV_SHIFT, cov, PF_LAM, PF_GAMMA, FILT, "null", seeds)
+    return BatchedMPPI(raw, E, H, P, lam, 1.0, cov, 1.0, FILT, "null", seeds)
+
+
+class _TimedLib:
+    """The library with device events around the launches named in ``names``."""
+
+    def __init__(self, lib, names):
+        import torch
+        self._lib, self._names, self._torch, self.events = lib, set(names), torch, {n: [] for n in names}
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in self._names:
+            return fn
+
+        def timed(*a):
+            s, e = self._torch.cuda.Event(enable_timing=True), self._torch.cuda.Event(enable_timing=True)
+            s.record()
+            rc = fn(*a)
+            e.record()
+            self.events[name].append((s, e))
+            return rc
+        return timed
+
+
+def launch_split(raw, E, P, H, lam, cov, steps, warmup):
+    """ms per launch of one batched PFMPC step (mean over ``steps`` steps)."""
+    import torch
+    b = make_batch(raw, E, P, H, lam, cov, "pfmpc")
+    b.on_env_reset = "ignore"
+    for _ in range(warmup):
+        b.step()
+    b.lib = timed = _TimedLib(b.lib, PF_LAUNCHES)
+    for _ in range(steps):
+        b.step()
+    torch.cuda.synchronize()
+    b.lib = timed._lib
+    b.close()
+    return {n: sum(s.elapsed_time(e) for s, e in timed.events[n]) / steps for n in PF_LAUNCHES}
 
 
 def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     import torch
-    from mjmpc_amd.control import BatchedCEM, BatchedMPPI
-    seeds = [123 + i * 12345 for i in range(E)]
-    if controller == "cem":
-        b = BatchedCEM(raw, E, H, P, cov, ELITE_FRAC, 1.0, BETA, 1.0, FILT, "null", seeds)
-    else:
-        b = BatchedMPPI(raw, E, H, P, lam, 1.0, cov, 1.0, FILT, "null", seeds)
+    b = make_batch(raw, E, P, H, lam, cov, controller)
     b.on_env_reset = "ignore"
     if K:
         b.randomize_dynamics(dyn_cfg(raw), [123 + i * 12345 for i in range(E)], K)
@@ -68,7 +119,8 @@ def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
 
 def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     import torch
-    from mjmpc_amd.control import CEM, MPPI
+    from mjmpc_amd.control import CEM, MPPI, PFMPC
+    from mjmpc_amd.control.controller import resident_state
     from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
     from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
     eng = TreeRolloutEngine(raw, num_shards=max(K, 1))
@@ -76,7 +128,11 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     if K:
         eng.randomize_dynamics(dyn_cfg(raw), 123)
         eng.set_real_env_model("nominal")
-    if controller == "cem":
+    if controller == "pfmpc":
+        c = PFMPC(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, cov_shift=COV_SHIFT, cov_resample=cov,
+                  base_action="null", lam=PF_LAM, num_particles=P, gamma=PF_GAMMA, n_iters=1, action_lows=eng.action_lows,
+                  action_highs=eng.action_highs, filter_coeffs=FILT, seed=123, noise_mode="device")
+    elif controller == "cem":
         c = CEM(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov, base_action="null",
                 elite_frac=ELITE_FRAC, num_particles=P, step_size=1.0, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
                 action_highs=eng.action_highs, beta=BETA, cov_type="full", filter_coeffs=FILT, seed=123, noise_mode="device",
@@ -86,8 +142,12 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
                  lam=lam, num_particles=P, step_size=1.0, alpha=1, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
                  action_highs=eng.action_highs, filter_coeffs=FILT, seed=123, noise_mode="device", noise_dtype="f64")
     c.rollout_fn = make_device_rollout_fn(eng)
-    c.set_sim_state_fn = lambda st: None
-    c.enable_graph(post_step=eng.step_state)
+    if controller == "pfmpc":       # (the resident real env: no state is uploaded, the env step rides behind the finish launch)
+        c.set_sim_state_fn = resident_state
+        c.set_post_step(eng.step_state)
+    else:
+        c.set_sim_state_fn = lambda st: None
+        c.enable_graph(post_step=eng.step_state)
     for _ in range(warmup):
         c.optimize(None)
     torch.cuda.synchronize()
@@ -112,13 +172,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--model-shards", type=int, default=0, help="randomized model shards per episode (0: no randomization)")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem"])
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc"])
     ap.add_argument("--repeats", type=int, default=1, help="timings per configuration, batch and single runs alternating")
     args = ap.parse_args()
     from mjmpc_amd import _lib
     _lib.require_gpu()          # (no GPU: no numbers)
     ms = models()
-    rows = []
+    rows, splits = [], []
     for name in args.models.split(","):
         fn, lam, cov = ms[name]
         raw = fn()
@@ -144,10 +204,24 @@ def main():
                         row.update(repeats=args.repeats, single_spread_ms=round(spread, 4))
                     rows.append(row)
                     print(json.dumps(row), flush=True)
+                    if args.controller == "pfmpc" and not args.model_shards:
+                        split = launch_split(raw, E, P, H, lam, cov, args.steps, args.warmup)
+                        splits.append((name, E, P, H, split))
+                        print(json.dumps(dict(model=name, controller="pfmpc", E=E, P=P, H=H,
+                                              launch_ms={k: round(v, 4) for k, v in split.items()})), flush=True)
     print("%-13s %3s %5s %3s %10s %10s %12s %8s" % ("model", "E", "P", "H", "batch ms", "single ms", "E x single", "speedup"))
     for r in rows:
         print("%-13s %3d %5d %3d %10.3f %10.3f %12.3f %8.2f" % (r["model"], r["E"], r["P"], r["H"], r["batch_ms_per_step"],
                                                              r["single_ms_per_step"], r["sequential_ms_per_step"], r["speedup"]))
+    if any("single_spread_ms" in r for r in rows):
+        print("single path, max - min over its repeats (ms): "
+              + ", ".join("%d x %d: %.3f" % (r["E"], r["P"], r["single_spread_ms"]) for r in rows))
+    if splits:
+        short = [n.replace("mjmpc_", "").replace("_batch", "") for n in PF_LAUNCHES]
+        print("per-launch split of one batched step (ms, device events around each launch)")
+        print("%-13s %3s %5s %3s " % ("model", "E", "P", "H") + " ".join("%18s" % n for n in short))
+        for name, E, P, H, split in splits:
+            print("%-13s %3d %5d %3d " % (name, E, P, H) + " ".join("%18.4f" % split[n] for n in PF_LAUNCHES))
 
 
 if __name__ == "__main__":
