@@ -1,9 +1,10 @@
 #!/usr/bin/env python
-"""The config's ``n_episodes`` MPPI, CEM or PFMPC episodes as ONE batch on the tree engine (``BatchedMPPI`` / ``BatchedCEM`` /
-``BatchedPFMPC``).
+"""The config's ``n_episodes`` MPPI, CEM, PFMPC or DMD-MPC episodes as ONE batch on the tree engine (``BatchedMPPI`` /
+``BatchedCEM`` / ``BatchedPFMPC`` / ``BatchedDMDMPC``).
 
-    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi|cem|pfmpc]
+    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi|cem|pfmpc|dmd]
         [--dtype f64|f32] [--episodes N] [--dyn_randomize_config FILE [--num_cpu K] [--dyn_per_episode]]
+        [--update_cov] [--cov_type diagonal|full]
 
 examples/example_mpc.py runs the episodes one after another (as the reference's job_script.py:80-99): episode i with seed
 ``seed + i*12345`` from the env class's ``reset(seed=...)``.  This driver takes the same seeds and start states and runs all
@@ -16,10 +17,12 @@ particles are split into the config's ``num_cpu`` shards and each shard rolls ou
 all episodes from the config's ``seed`` as the reference does before its episode loop (``--dyn_per_episode``: from every
 episode's own seed), while the real envs keep the nominal model - still one batch.
 
-The ``mppi``, ``cem`` and ``pfmpc`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection +
+The ``mppi``, ``cem``, ``pfmpc`` and ``dmd`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection +
 moments, refit + next samples and env-step launches per control step; ``--controller pfmpc``: ``BatchedPFMPC``, DESIGN 10.3 -
-deviations, rollout, weights, resampling, gather + shift, mean + action and env step, e.g. examples/configs/reacher_gpu.yml);
-other controller blocks are refused.  The reacher configs run on the TREE engine here
+deviations, rollout, weights, resampling, gather + shift, mean + action and env step, e.g. examples/configs/reacher_gpu.yml;
+``--controller dmd``: with ``update_cov: true`` ``BatchedDMDMPC``, DESIGN 10.4 - factors, draw, filter, rollout, weights, partial
+moments, update + tail and env step -, with ``update_cov: false`` ``BatchedMPPI`` with the block's ``lam``, ``step_size`` and
+``init_cov``, which is that arithmetic; the class that ran is printed); other controller blocks are refused.  The reacher configs run on the TREE engine here
 (sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
 rewards are not expected to be equal.
 """
@@ -34,21 +37,23 @@ import yaml
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from example_mpc import ENVS, TREE_MODELS                           # noqa: E402
-from mjmpc_amd.control import BatchedCEM, BatchedMPPI, BatchedPFMPC  # noqa: E402
+from mjmpc_amd.control import BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedPFMPC  # noqa: E402
 from mjmpc_amd.envs.tree_engine import TreeRolloutEngine            # noqa: E402
 from mjmpc_amd.models.reacher7dof import reacher7dof_raw            # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM or PFMPC episodes as one batch")
+    ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM, PFMPC or DMD-MPC episodes as one batch")
     ap.add_argument("--config", required=True, help="yaml file with experiment parameters")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc"],
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd"],
                     help="controller block of the config to run")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--episodes", type=int, help="override n_episodes")
     ap.add_argument("--dyn_randomize_config", help="yaml file with dynamics randomization parameters")
     ap.add_argument("--num_cpu", type=int, help="override the config's num_cpu (the model shards of --dyn_randomize_config)")
     ap.add_argument("--dyn_per_episode", action="store_true", help="a set of randomized models per episode (from its seed)")
+    ap.add_argument("--update_cov", action="store_true", help="--controller dmd: adapt the covariance whatever the block says")
+    ap.add_argument("--cov_type", choices=["diagonal", "full"], help="--controller dmd / cem: override the block's cov_type")
     args = ap.parse_args()
     with open(args.config) as f:
         exp = yaml.safe_load(f)
@@ -59,6 +64,10 @@ def main():
     params = dict(exp[args.controller])
     num_cpu = args.num_cpu or params.pop("num_cpu", 1)
     params.pop("num_cpu", None)
+    if args.update_cov:
+        params["update_cov"] = True
+    if args.cov_type:
+        params["cov_type"] = args.cov_type
     if "particles_per_cpu" in params:
         params["num_particles"] = num_cpu * params.pop("particles_per_cpu")
     E = args.episodes or exp["n_episodes"]
@@ -85,11 +94,22 @@ def main():
         batch = BatchedPFMPC(raw, E, params["horizon"], params["num_particles"], params["cov_shift"], params["cov_resample"],
                              params["lam"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
                              n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
+    elif args.controller == "dmd" and params.get("update_cov", False):
+        batch = BatchedDMDMPC(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
+                              params["init_cov"], params.get("beta", 0.0), params["gamma"], params["filter_coeffs"], base_action,
+                              seeds, cov_type=params.get("cov_type", "diagonal"), dtype=args.dtype,
+                              n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
+    elif args.controller == "dmd":      # (without covariance adaptation DMD-MPC is MPPI with alpha = 1: gaussian_dmd.py:65-104)
+        batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
+                            params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
+                            n_iters=params.get("n_iters", 1))     # (the static covariance is diag(init_cov) for any cov_type)
     else:
         batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
                             params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
                             n_iters=params.get("n_iters", 1), alpha=params.get("alpha", 1),
                             time_based_weights=params.get("time_based_weights", False))
+    if args.controller == "dmd":
+        print("the dmd block (update_cov: %s) runs as %s" % (bool(params.get("update_cov", False)), type(batch).__name__))
     if args.dyn_randomize_config:
         with open(args.dyn_randomize_config) as f:
             default_params, randomized = batch.randomize_dynamics(yaml.safe_load(f), seeds if args.dyn_per_episode else exp["seed"],

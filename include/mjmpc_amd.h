@@ -36,7 +36,8 @@ extern "C" {
  *      MJMPC_ARM_BLOB_LEN 229 -> 255 (joint type, friction loss, nu: the arm engine takes slide joints, dry friction and
  *      fewer motors than dofs). */
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
- *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model and the CEM episode batches'.) */
+ *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
+ *      and the DMD-MPC episode batches'.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -538,6 +539,41 @@ int mjmpc_cem_finish_batch(int dtype, int E, int64_t P, int H, int A, const int6
                            int* d_status, const double* d_grow_diag, const double* d_grow_scale, double* d_actions_out,
                            int64_t* d_step_counter, void* d_next_noise, const uint64_t* d_seeds, uint64_t offset, void* d_ws,
                            void* stream);
+
+/* Episode batches of DMD-MPC's covariance-adapting step (gaussian_dmd.py:65-113 with update_cov, one per episode of the
+ * reference's episode loop): grid row e = episode e, no host synchronisation, nothing exchanged between rows.
+ *   mjmpc_cholesky_lower_batch    row e is exactly mjmpc_cholesky_lower(d_covs + e A A, A, d_chols + e A A, d_status + e) on
+ *       its block: d_covs / d_chols float64 [E][A][A]; d_status int [E] (may be NULL), d_status[e] = 1 if row e's covariance
+ *       is indefinite or not finite - sticky, and only that row's.  One launch.  A <= 64.
+ *   mjmpc_sample_noise_cov_batch  row e is exactly mjmpc_sample_noise(dtype, d_noise + e P H A, P, H, A, d_chols + e A A,
+ *       d_coeffs, d_seeds[e], offset, 0, d_step, chol_is_diagonal) on its slice: d_noise dtype [E][P][H][A], d_seeds uint64
+ *       [E] (device), one step counter d_step (may be NULL) and one d_coeffs (float64 [3]; NULL leaves the samples raw) for
+ *       all rows.  The draw is one launch of the kernel mjmpc_sample_noise would pick (all channels of a (particle, t-quad)
+ *       per thread for a general factor with A <= 8, per element above that and for chol_is_diagonal), the filter a second
+ *       launch over the E P particles - per (particle, channel), the instructions of the single pass.
+ *   mjmpc_dmd_update_batch        row e is exactly mjmpc_softmax_stats(dtype, P, H, A, d_costs + e P H, d_actions + e P H A,
+ *       d_means + e H A, NULL, d_gseq, gamma_zero = 0, d_lam[e], alpha = 1, time_based_weights = 0, want_cov = 1, record,
+ *       ws), then mjmpc_softmax_combine(record, G = 1, H, A, 0, d_lam[e], d_step_size[e], cov_mode, P, d_means + e H A,
+ *       d_covs + e A A, NULL, NULL), then mjmpc_step_tail(d_means + e H A, H, A, shift_mode, NULL, d_actions_out + e A, NULL,
+ *       counter, d_covs + e A A, NULL, d_beta[e]) on its slices: the same 16 particles per partial, the same merge tree
+ *       over the ceil(P / 16) partials, the same combine with one record, the covariance scatter about the mean from before
+ *       the update.  d_costs dtype [E][P][H], d_actions dtype [E][P][H][A], d_gseq float64 [H] without zeros, d_lam (> 0:
+ *       only the host can check it), d_step_size and d_beta float64 [E] (device), cov_mode 1 (diagonal) or 2 (full),
+ *       shift_mode 0 'null' or 1 'repeat', d_means float64 [E][H][A] and d_covs float64 [E][A][A] (updated in place; the means
+ *       shifted, the covariances grown by d_beta[e] I), d_actions_out float64 [E][A] (may be NULL).  *d_step_counter (may be
+ *       NULL) is advanced once, by row 0 of the last launch; no row reads it.  Three launches (cost-to-go weights + their
+ *       maximum; partial moments; record + combine + tail).  d_ws: mjmpc_dmd_batch_workspace_bytes(E, P, H, A) bytes, 8-byte
+ *       aligned (negative for bad sizes).
+ * 1 <= E <= 65535, A <= 64 (MJMPC_E_BADARG otherwise). */
+int mjmpc_cholesky_lower_batch(int E, const double* d_covs, int A, double* d_chols, int* d_status, void* stream);
+int mjmpc_sample_noise_cov_batch(int dtype, int E, void* d_noise, int64_t P, int H, int A, const double* d_chols,
+                                 const double* d_coeffs, const uint64_t* d_seeds, uint64_t offset, const int64_t* d_step,
+                                 int chol_is_diagonal, void* stream);
+int64_t mjmpc_dmd_batch_workspace_bytes(int E, int64_t P, int H, int A);
+int mjmpc_dmd_update_batch(int dtype, int E, int64_t P, int H, int A, const void* d_costs, const void* d_actions,
+                           const double* d_gseq, const double* d_lam, const double* d_step_size, int cov_mode,
+                           const double* d_beta, int shift_mode, double* d_means, double* d_covs, double* d_actions_out,
+                           int64_t* d_step_counter, void* d_ws, void* stream);
 
 /* Sharded MPPI: the G all-gathered records d_records (float64 [G][2 + H*A], as left in d_record by
  * mjmpc_mppi_fused_update with step_size 0, shift_mode -1) merged in rank order -> mean update, action read-out,

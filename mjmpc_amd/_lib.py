@@ -128,6 +128,11 @@ SIGNATURES = {
                                      _vp, _vp]),
     "mjmpc_pf_finish": (_int, [_i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_pf_delta": (_int, [_int, _i64, _int, _int, _vp, _vp, _vp, _vp]),
+    "mjmpc_cholesky_lower_batch": (_int, [_int, _vp, _int, _vp, _vp, _vp]),
+    "mjmpc_sample_noise_cov_batch": (_int, [_int, _int, _vp, _i64, _int, _int, _vp, _vp, _vp, ctypes.c_uint64, _vp, _int, _vp]),
+    "mjmpc_dmd_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int]),
+    "mjmpc_dmd_update_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
     "mjmpc_pf_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int]),
     "mjmpc_pf_delta_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_pf_weights_batch": (_int, [_int, _i64, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp, _vp]),

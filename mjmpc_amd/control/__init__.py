@@ -9,6 +9,7 @@ _WHERE = {
     "BatchedMPPI": "batched",           # (no reference counterpart: the reference's episode loop as one batch)
     "BatchedCEM": "batched",
     "BatchedPFMPC": "batched",
+    "BatchedDMDMPC": "batched",
 }
 __all__ = sorted(_WHERE)
 

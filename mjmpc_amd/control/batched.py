@@ -1,4 +1,4 @@
-"""Episode batches: E independent MPPI, CEM or PFMPC episodes side by side on the tree engine.
+"""Episode batches: E independent MPPI, CEM, PFMPC or DMD-MPC episodes side by side on the tree engine.
 
 The reference runs its experiments one episode after another (examples/job_script.py:80-99, the episode loop of
 examples/example_mpc.py), each with its own seed (``seed + i*12345``) and start state, and its "tune" mode multiplies
@@ -25,8 +25,12 @@ the dtype.  The batch's E real envs are the state shards of the batch's own engi
 ``BatchedCEM`` is the same batch for the cross-entropy method (cem.py): per episode also ``elite_frac`` and
 ``beta``, and a covariance that is refitted from the elites on the device.  ``BatchedPFMPC`` is the batch of particle-filter
 MPC (particle_filter_controller.py, ``noise_mode='device'``): per episode ``lam``, ``cov_shift`` and
-``cov_resample``, and a particle set that is resampled on the device.  The classes share ``_EpisodeBatch``: the engine, the
-state shards, the buffers, the rollout launch, the env step, ``run`` and dynamics randomization.
+``cov_resample``, and a particle set that is resampled on the device.  ``BatchedDMDMPC`` is the batch of DMD-MPC with an
+adapting covariance (gaussian_dmd.py with ``update_cov=True``): per episode ``lam``, ``step_size``, ``init_cov``
+and ``beta``, and a ``'diagonal'`` or ``'full'`` covariance that is re-estimated from the weighted samples, grown by
+``beta I`` and factored on the device every step (``update_cov=False`` is ``BatchedMPPI``'s arithmetic).  The classes share
+``_EpisodeBatch``: the engine, the state shards, the buffers, the rollout launch, the env step, ``run`` and dynamics
+randomization.
 """
 import ctypes
 
@@ -448,6 +452,120 @@ class BatchedCEM(_EpisodeBatch):
 
     def _check_status(self):
         """``DeviceUpdater.check_status`` per episode: raise for the episodes whose finish launch has flagged an indefinite or
+        non-finite covariance (the flags are sticky on the device) and clear exactly the flags reported."""
+        st = self._status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size == 0:
+            return
+        self._status[self.torch.from_numpy(bad).to(self.device)] = 0
+        raise _lib.MjmpcError("the action covariance of episode%s %s on the device is indefinite or not finite: its Cholesky "
+                              "factor (sampler colouring) does not exist"
+                              % ("" if bad.size == 1 else "s", ", ".join(str(int(e)) for e in bad)))
+
+
+class BatchedDMDMPC(_EpisodeBatch):
+    """``num_episodes`` DMD-MPC controllers that adapt their covariance (gaussian_dmd.py with ``update_cov=True``, one iteration
+    per step) and their real envs, stepped together.
+
+    Episode e computes the bits of ``DMDMPC(..., update_cov=True, cov_type=cov_type, noise_mode='device', noise_dtype=dtype,
+    seed=seeds[e])`` on a ``TreeRolloutEngine`` of its own with ``make_device_rollout_fn`` and
+    ``enable_graph(post_step=engine.step_state)``, whose step is the general one of ``OLGaussianMPC._device_iteration``: Cholesky
+    factor, draw + filter, plain rollout, ``softmax_update`` with the covariance, ``step_tail`` with the growth ``beta I``.
+    ``lam``, ``step_size``, ``init_cov`` (scalar: ``diag(init_cov)``, as ``DMDMPC`` takes it), ``beta`` and ``init_mean``
+    (``(H, A)``, default zeros) take one value for every episode or one per episode; ``seeds`` one seed per episode.  A control
+    step is eight launches - factors, draw, filter, rollout, weights + their maximum, partial moments, record + combine +
+    tail, real-env step (seven with the identity filter) - and nothing synchronises.  Settings the batch does not run raise
+    ``ValueError`` before any engine or device memory exists: ``update_cov=False`` (that arithmetic is ``BatchedMPPI``'s),
+    ``n_iters != 1``, ``sample_mode != 'mean'``, ``use_zero_control_seq``, ``gamma == 0``, ``cov_type`` other than
+    ``'diagonal'`` / ``'full'``, ``base_action`` other than ``'null'`` / ``'repeat'``, ``lam <= 0``, ``init_cov <= 0``,
+    ``beta < 0``, more than 64 action channels (the Cholesky kernel's limit) and a model the tree engine refuses.  An episode
+    whose covariance turns indefinite or non-finite raises ``MjmpcError`` where ``run`` / ``get_states`` / ``mean_action`` /
+    ``cov`` synchronise."""
+
+    def __init__(self, raw_model, num_episodes, horizon, num_particles, lam, step_size, init_cov, beta, gamma, filter_coeffs,
+                 base_action, seeds, cov_type="full", update_cov=True, init_mean=None, dtype="f64", device=0, n_iters=1,
+                 sample_mode="mean", use_zero_control_seq=False):
+        # -- everything that can be refused is refused here, before the engine and its device memory exist
+        if not update_cov:
+            raise ValueError("DMD-MPC without covariance adaptation (update_cov=False) is MPPI with alpha = 1: run it as "
+                             "BatchedMPPI with the same lam, step_size and init_cov")
+        if cov_type not in ("diagonal", "full"):
+            raise ValueError("cov_type must be 'diagonal' or 'full' in a DMD-MPC episode batch, got %r" % (cov_type,))
+        E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
+                                         sample_mode, dtype, gamma, filter_coeffs, "DMD-MPC")
+        lam = _per_episode("lam", lam, E)
+        step_size = _per_episode("step_size", step_size, E)
+        init_cov = _per_episode("init_cov", init_cov, E)
+        beta = _per_episode("beta", beta, E)
+        if not np.all(lam > 0):
+            raise ValueError("lam must be positive")
+        if not np.all(init_cov > 0):
+            raise ValueError("init_cov must be positive")
+        if not np.all(beta >= 0):
+            raise ValueError("beta must not be negative")
+        self.seed_vals = self._check_seeds(seeds, E)
+        model = self._compile(raw_model)
+        A = model.nu
+        if A > 64:
+            raise ValueError("a DMD-MPC episode batch factors covariances of up to 64 action channels, got %d" % A)
+        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
+        lib = _lib.load()
+        nbytes = lib.mjmpc_dmd_batch_workspace_bytes(E, P, H, A)
+        if nbytes <= 0:
+            raise ValueError("no DMD-MPC batch workspace for E = %d, P = %d, H = %d, A = %d" % (E, P, H, A))
+
+        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+        f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
+        torch, dev = self.torch, self.device
+        self.lam, self.step_size, self.init_cov, self.beta, self.cov_type = lam, step_size, init_cov, beta, cov_type
+        self._init_covs = np.stack([np.diag(np.array([c] * A)) for c in init_cov])      # (OLGaussianMPC: diag(init_cov))
+        self._covs = torch.from_numpy(self._init_covs.copy()).to(dev)
+        self._chols = torch.zeros((E, A, A), **f64)
+        self._lam = torch.from_numpy(lam.copy()).to(dev)
+        self._step = torch.from_numpy(step_size.copy()).to(dev)
+        self._beta = torch.from_numpy(beta.copy()).to(dev)
+        self._status = torch.zeros(E, dtype=torch.int32, device=dev)
+        identity = fc[0] == 1.0 and fc[1] == 0.0 and fc[2] == 0.0
+        self._draw_coeffs = None if identity else self._coeffs      # (the filter pass leaves an identity's samples as they are)
+        self._ws = torch.empty((nbytes + 7) // 8, **f64)
+        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+
+    @property
+    def cov(self):
+        """The E action covariances, ``(E, A, A)`` (synchronises)."""
+        out = self._covs.cpu().numpy().copy()
+        self._check_status()
+        return out
+
+    def reset(self):
+        """Every episode back to its initial mean and covariance and to step 0 (the real envs keep their states)."""
+        super().reset()
+        self._covs.copy_(self.torch.from_numpy(self._init_covs))
+
+    def step(self, _out=None):
+        """Enqueue one control step of every episode (factors, draw + filter, rollouts, weights, partial moments, update +
+        action + shift + covariance growth, real-env step) without a host synchronisation.  The actions, real-env costs and
+        next observations stay on the device."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
+        lib, code, s = self.lib, self._code, self._stream()
+        _lib.check(lib.mjmpc_cholesky_lower_batch(E, _vp(self._covs), A, _vp(self._chols), _vp(self._status), s))
+        _lib.check(lib.mjmpc_sample_noise_cov_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._draw_coeffs),
+                                                    _vp(self._seeds), 0, _vp(self._step_dev),
+                                                    int(self.cov_type == "diagonal"), s))
+        # (the samples are filtered already and the update forms its own cost-to-go: the single path's plain rollout)
+        _lib.check(lib.mjmpc_tree_rollout_fused_batch(self.engine._h, code, E * P, H, _vp(self._means), _vp(self._noise), None,
+                                                      None, _vp(self._costs), _vp(self._actions), None, s))
+        _lib.check(lib.mjmpc_dmd_update_batch(code, E, P, H, A, _vp(self._costs), _vp(self._actions), _vp(self._gseq),
+                                              _vp(self._lam), _vp(self._step), 2 if self.cov_type == "full" else 1,
+                                              _vp(self._beta), _SHIFT_MODES[self.base_action], _vp(self._means),
+                                              _vp(self._covs), _vp(act), _vp(self._step_dev), _vp(self._ws), s))
+        self._env_step(act, cost, nobs, s)
+        self.num_steps += 1
+        return act, cost, nobs
+
+    def _check_status(self):
+        """``DeviceUpdater.check_status`` per episode: raise for the episodes whose factor launch has flagged an indefinite or
         non-finite covariance (the flags are sticky on the device) and clear exactly the flags reported."""
         st = self._status.cpu().numpy()
         bad = np.nonzero(st)[0]

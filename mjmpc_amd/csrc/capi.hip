@@ -1601,6 +1601,43 @@ int mjmpc_cholesky_lower(const double* d_cov, int A, double* d_chol, int* d_stat
     PLAIN(mjmpc::cholesky_lower(d_cov, A, d_chol, d_status, (hipStream_t)stream));
 }
 
+static int dmd_batch_shape(int E, int64_t P, int H, int A) {
+    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
+    if (A < 1 || A > 64) return fail(MJMPC_E_BADARG, "A = %d outside 1 .. 64 (the Cholesky kernel's limit)", A);
+    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d", (long long)P, H);
+    return 0;
+}
+
+int mjmpc_cholesky_lower_batch(int E, const double* d_covs, int A, double* d_chols, int* d_status, void* stream) {
+    if (!d_covs || !d_chols) return fail(MJMPC_E_BADARG, "null argument");
+    if (int rc = dmd_batch_shape(E, 1, 1, A)) return rc;
+    PLAIN(mjmpc::cholesky_lower_batch(E, d_covs, A, d_chols, d_status, (hipStream_t)stream));
+}
+
+int64_t mjmpc_dmd_batch_workspace_bytes(int E, int64_t P, int H, int A) {
+    if (int rc = dmd_batch_shape(E, P, H, A)) return rc;
+    return (int64_t)sizeof(double) * mjmpc::dmd_batch_workspace_doubles(E, (long)P, H, A);
+}
+
+int mjmpc_dmd_update_batch(int dtype, int E, int64_t P, int H, int A, const void* d_costs, const void* d_actions,
+                           const double* d_gseq, const double* d_lam, const double* d_step_size, int cov_mode,
+                           const double* d_beta, int shift_mode, double* d_means, double* d_covs, double* d_actions_out,
+                           int64_t* d_step_counter, void* d_ws, void* stream) {
+    if (!d_costs || !d_actions || !d_gseq || !d_lam || !d_step_size || !d_beta || !d_means || !d_covs || !d_ws)
+        return fail(MJMPC_E_BADARG, "null argument");
+    if (int rc = dmd_batch_shape(E, P, H, A)) return rc;
+    if (cov_mode != 1 && cov_mode != 2) return fail(MJMPC_E_BADARG, "cov_mode %d (1 diagonal, 2 full)", cov_mode);
+    if (shift_mode < 0 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::dmd_update_batch<float>(E, (const float*)d_costs, (const float*)d_actions, d_gseq, d_lam, d_step_size,
+                                            cov_mode, d_beta, shift_mode, (long)P, H, A, d_means, d_covs, d_actions_out,
+                                            (long long*)d_step_counter, (double*)d_ws, s),
+             mjmpc::dmd_update_batch<double>(E, (const double*)d_costs, (const double*)d_actions, d_gseq, d_lam, d_step_size,
+                                             cov_mode, d_beta, shift_mode, (long)P, H, A, d_means, d_covs, d_actions_out,
+                                             (long long*)d_step_counter, (double*)d_ws, s));
+}
+
 int mjmpc_cov_add_diag(double* d_cov, int A, const double* d_diag, double scale, void* stream) {
     if (!d_cov || A < 1 || A > 64) return fail(MJMPC_E_BADARG, "bad argument (A <= 64)");
     PLAIN(mjmpc::cov_add_diag(d_cov, A, d_diag, scale, (hipStream_t)stream));
@@ -1681,6 +1718,21 @@ int mjmpc_sample_noise_batch(int dtype, int E, void* d_noise, int64_t P, int H, 
                                               offset, (const long long*)d_step, s),
              mjmpc::sample_noise_batch<double>((double*)d_noise, E, (long)P, H, A, d_chols, (const unsigned long long*)d_seeds,
                                                offset, (const long long*)d_step, s));
+}
+
+int mjmpc_sample_noise_cov_batch(int dtype, int E, void* d_noise, int64_t P, int H, int A, const double* d_chols,
+                                 const double* d_coeffs, const uint64_t* d_seeds, uint64_t offset, const int64_t* d_step,
+                                 int chol_is_diagonal, void* stream) {
+    if (!d_noise || !d_chols || !d_seeds) return fail(MJMPC_E_BADARG, "null argument");
+    if (int rc = dmd_batch_shape(E, P, H, A)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::sample_noise_cov_batch<float>((float*)d_noise, E, (long)P, H, A, d_chols, d_coeffs,
+                                                  (const unsigned long long*)d_seeds, offset, (const long long*)d_step, s,
+                                                  chol_is_diagonal),
+             mjmpc::sample_noise_cov_batch<double>((double*)d_noise, E, (long)P, H, A, d_chols, d_coeffs,
+                                                   (const unsigned long long*)d_seeds, offset, (const long long*)d_step, s,
+                                                   chol_is_diagonal));
 }
 
 }  // extern "C"

@@ -41,11 +41,10 @@ __global__ void noise_batch_kernel(T* __restrict__ noise, long P, int H, int A, 
 // forms all A channels from them - the per-element kernel above would draw z_b again for every channel a >= b
 // (A (A+1) / 2 Philox blocks instead of A; 56 -> 16 us at 16384 x 32 x 7).  Same draws, same order of summation.
 constexpr int NOISE_MAXA = 8;      // loops are unrolled to this bound so that the draws stay in registers
+// (the body is shared with the episode-batch kernel below, whose grid row picks the episode's block, factor and seed)
 template <typename T>
-__global__ void noise_full_kernel(T* __restrict__ noise, long P, int H, int A, const double* __restrict__ chol,
-                                  unsigned long long seed, unsigned long long offset, long particle_offset,
-                                  const long long* __restrict__ d_step) {
-    if (d_step) offset += (unsigned long long)*d_step;
+__device__ __forceinline__ void noise_full_body(T* __restrict__ noise, long P, int H, int A, const double* __restrict__ chol,
+                                                unsigned long long seed, unsigned long long offset, long particle_offset) {
     const int H4 = (H + 3) / 4;
     const long gid = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = gid < P * H4;         // (idle lanes of the last workgroup stay for the staged store)
@@ -91,6 +90,36 @@ __global__ void noise_full_kernel(T* __restrict__ noise, long P, int H, int A, c
         const int th = i / run, off = i - th * run;
         if (first + i < total) noise[first + i] = tile[th * pad + off];
     }
+}
+
+template <typename T>
+__global__ void noise_full_kernel(T* __restrict__ noise, long P, int H, int A, const double* __restrict__ chol,
+                                  unsigned long long seed, unsigned long long offset, long particle_offset,
+                                  const long long* __restrict__ d_step) {
+    if (d_step) offset += (unsigned long long)*d_step;
+    noise_full_body<T>(noise, P, H, A, chol, seed, offset, particle_offset);
+}
+
+// Episode batches whose factors need not be diagonal (DMD-MPC's adapting covariance): grid row e is
+// noise_full_kernel on episode e's [P][H][A] block with its own factor and seed, particle_offset = 0 ...
+template <typename T>
+__global__ void noise_full_batch_kernel(T* __restrict__ noise, long P, int H, int A, const double* __restrict__ chols,
+                                        const unsigned long long* __restrict__ seeds, unsigned long long offset,
+                                        const long long* __restrict__ d_step) {
+    if (d_step) offset += (unsigned long long)*d_step;
+    const long e = blockIdx.y;
+    noise_full_body<T>(noise + e * P * H * A, P, H, A, chols + e * A * A, seeds[e], offset, 0);
+}
+
+// ... and noise_kernel with the caller's diag_only (A above NOISE_MAXA, or a factor known to be diagonal)
+template <typename T>
+__global__ void noise_cov_batch_kernel(T* __restrict__ noise, long P, int H, int A, const double* __restrict__ chols,
+                                       const unsigned long long* __restrict__ seeds, unsigned long long offset,
+                                       const long long* __restrict__ d_step, int diag_only) {
+    if (d_step) offset += (unsigned long long)*d_step;
+    const long e = blockIdx.y;
+    noise_element<T>(noise + e * P * H * A, (long)blockIdx.x * blockDim.x + threadIdx.x, P, H, A, chols + e * A * A, seeds[e],
+                     offset, 0, diag_only);
 }
 
 // pass 2: eps[t] = b0 eps[t] + b1 eps[t-1] + b2 eps[t-2] for t >= 2, in place, in float64
@@ -145,6 +174,28 @@ hipError_t sample_noise_batch(T* noise, int E, long P, int H, int A, const doubl
     return hipGetLastError();
 }
 
+// the kernel by sample_noise's rule, one grid row per episode; the filter pass is filter_kernel over the E P particles (it
+// works per (particle, channel): the same instructions on the same data as E launches of P particles)
+template <typename T>
+hipError_t sample_noise_cov_batch(T* noise, int E, long P, int H, int A, const double* chols, const double* coeffs,
+                                  const unsigned long long* seeds, unsigned long long offset, const long long* d_step,
+                                  hipStream_t s, int diag_only) {
+    if (E < 1 || E > 65535) return hipErrorInvalidValue;
+    if (P <= 0 || H <= 0) return hipSuccess;
+    const long n = P * A * ((H + 3) / 4), m = (long)E * P * A;
+    if (!diag_only && A <= NOISE_MAXA) {
+        const long nf = P * ((H + 3) / 4);
+        hipLaunchKernelGGL(noise_full_batch_kernel<T>, dim3((unsigned)((nf + 63) / 64), (unsigned)E), dim3(64), 0, s, noise, P, H,
+                           A, chols, seeds, offset, d_step);
+    } else {
+        hipLaunchKernelGGL(noise_cov_batch_kernel<T>, dim3((unsigned)((n + 255) / 256), (unsigned)E), dim3(256), 0, s, noise, P, H,
+                           A, chols, seeds, offset, d_step, diag_only);
+    }
+    if (coeffs)
+        hipLaunchKernelGGL(filter_kernel<T>, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, noise, (long)E * P, H, A, coeffs);
+    return hipGetLastError();
+}
+
 template <typename T>
 hipError_t filter_noise(T* noise, long P, int H, int A, const double* coeffs, hipStream_t s) {
     const long m = P * A;
@@ -184,6 +235,12 @@ template hipError_t sample_noise_batch<float>(float*, int, long, int, int, const
                                               unsigned long long, const long long*, hipStream_t);
 template hipError_t sample_noise_batch<double>(double*, int, long, int, int, const double*, const unsigned long long*,
                                                unsigned long long, const long long*, hipStream_t);
+template hipError_t sample_noise_cov_batch<float>(float*, int, long, int, int, const double*, const double*,
+                                                  const unsigned long long*, unsigned long long, const long long*, hipStream_t,
+                                                  int);
+template hipError_t sample_noise_cov_batch<double>(double*, int, long, int, int, const double*, const double*,
+                                                   const unsigned long long*, unsigned long long, const long long*, hipStream_t,
+                                                   int);
 template hipError_t filter_noise<float>(float*, long, int, int, const double*, hipStream_t);
 template hipError_t filter_noise<double>(double*, long, int, int, const double*, hipStream_t);
 

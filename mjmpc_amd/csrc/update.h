@@ -96,6 +96,19 @@ hipError_t mppi_fused_update_batch(int E, const double* q0, const T* actions, co
                                    int shift_mode, long P, int H, int A, double* mean, double* action_out,
                                    long long* step_counter, double* ws, hipStream_t s);
 
+// Episode batches of the covariance-adapting DMD-MPC step (gaussian_dmd.py:65-113, update_cov): grid row e is softmax_stats
+// (gamma_zero 0, lam[e], alpha 1, one weight per particle, want_cov) + softmax_combine (one record, step[e], cov_mode) +
+// step_tail (shift_mode, cov += beta[e] I) on episode e's slices, in three launches; row 0 increments the shared step
+// counter once.  ws: dmd_batch_workspace_doubles(E, P, H, A).
+long dmd_batch_workspace_doubles(int E, long P, int H, int A);
+template <typename T>
+hipError_t dmd_update_batch(int E, const T* costs, const T* actions, const double* gseq, const double* lam,
+                            const double* step, int cov_mode, const double* beta, int shift_mode, long P, int H, int A,
+                            double* means, double* covs, double* actions_out, long long* step_counter, double* ws,
+                            hipStream_t s);
+// row e is cholesky_lower on covs + e A A -> chols + e A A with its own sticky flag status[e] (status may be null)
+hipError_t cholesky_lower_batch(int E, const double* covs, int A, double* chols, int* status, hipStream_t s);
+
 // the all-gathered records of G GPUs -> mean, action (device + mapped host copy with completion flag), step counter, shift
 hipError_t mppi_fused_combine(const double* records, int G, double P_total, double lam, double step, int shift_mode,
                               int H, int A, double* mean, double* action_out, double* value, double* action_host,
@@ -122,6 +135,14 @@ hipError_t sample_noise(T* noise, long P, int H, int A, const double* chol, cons
 template <typename T>
 hipError_t sample_noise_batch(T* noise, int E, long P, int H, int A, const double* chols, const unsigned long long* seeds,
                               unsigned long long offset, const long long* d_step, hipStream_t s);
+
+// Episode batches with a factor per episode that need not be diagonal (DMD-MPC's adapting covariance): row e is
+// sample_noise(noise + e P H A, P, H, A, chols + e A A, coeffs, seeds[e], offset, 0, d_step, s, diag_only) - the kernel chosen
+// by sample_noise's rule, the filter pass over all E P particles.
+template <typename T>
+hipError_t sample_noise_cov_batch(T* noise, int E, long P, int H, int A, const double* chols, const double* coeffs,
+                                  const unsigned long long* seeds, unsigned long long offset, const long long* d_step,
+                                  hipStream_t s, int diag_only);
 
 // the in-place recursive 3-tap filter of control_utils.py:32-33 on its own
 template <typename T>

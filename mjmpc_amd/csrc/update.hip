@@ -30,13 +30,12 @@ __device__ __forceinline__ double wave_max(double v) {
 // x[p][tw] = (-1/lam) * (cost_to_go(costs)[p][tw] + lam * cost_to_go(ctrl_cost)[p][tw]),  tw < Hw
 // q0[p]    = cost_to_go(costs)[p][0]                                    (optional output)
 // cost_to_go follows mjmpc/utils/control_utils.py:37-46 in the same summation order.
+// (particle p's part; the body is shared with the episode-batch kernel dmd_x_colmax_batch_kernel below)
 template <typename T>
-__global__ void traj_cost_kernel(const T* __restrict__ costs, const T* __restrict__ actions,
-                                 const double* __restrict__ mean, const double* __restrict__ un,
-                                 const double* __restrict__ gseq, int gamma_zero, double lam, long P, int H, int A,
-                                 int Hw, double* __restrict__ x, double* __restrict__ q0) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
+__device__ __forceinline__ void traj_cost_body(const T* __restrict__ costs, const T* __restrict__ actions,
+                                               const double* __restrict__ mean, const double* __restrict__ un,
+                                               const double* __restrict__ gseq, int gamma_zero, double lam, long p, int H,
+                                               int A, int Hw, double* __restrict__ x, double* __restrict__ q0) {
     const double neg_inv_lam = -1.0 / lam;
     double acc = 0.0, accc = 0.0;
     for (int t = H - 1; t >= 0; --t) {
@@ -69,6 +68,16 @@ __global__ void traj_cost_kernel(const T* __restrict__ costs, const T* __restric
         else if (t == 0) x[p] = neg_inv_lam * (qt + lam * cq);
         if (t == 0 && q0) q0[p] = qt;
     }
+}
+
+template <typename T>
+__global__ void traj_cost_kernel(const T* __restrict__ costs, const T* __restrict__ actions,
+                                 const double* __restrict__ mean, const double* __restrict__ un,
+                                 const double* __restrict__ gseq, int gamma_zero, double lam, long P, int H, int A,
+                                 int Hw, double* __restrict__ x, double* __restrict__ q0) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    traj_cost_body<T>(costs, actions, mean, un, gseq, gamma_zero, lam, p, H, A, Hw, x, q0);
 }
 
 // MPPIQ.calculate_returns (mjmpc/control/mppiq.py:104-126), one particle per thread:
@@ -141,10 +150,12 @@ __global__ void colmax_kernel(const double* __restrict__ x, long P, int Hw, doub
 }
 
 // partial[b] = { S[Hw], W[H*A], C[A*A] } over the particle chunk of workgroup b
+// (b = blockIdx.x; the body is shared with the episode-batch kernel below, whose grid row picks the episode's arrays)
 template <typename T>
-__global__ void softmax_partial_kernel(const double* __restrict__ x, const double* __restrict__ xmax,
-                                       const T* __restrict__ actions, const double* __restrict__ mean, long P, int H,
-                                       int A, int Hw, int chunk, int want_cov, double* __restrict__ partial) {
+__device__ __forceinline__ void softmax_partial_body(const double* __restrict__ x, const double* __restrict__ xmax,
+                                                     const T* __restrict__ actions, const double* __restrict__ mean, long P,
+                                                     int H, int A, int Hw, int chunk, int want_cov,
+                                                     double* __restrict__ partial) {
     extern __shared__ double e_s[];                 // chunk * Hw
     const int HA = H * A, rec = Hw + HA + A * A;
     const long p0 = (long)blockIdx.x * chunk;
@@ -179,6 +190,13 @@ __global__ void softmax_partial_kernel(const double* __restrict__ x, const doubl
     }
 }
 
+template <typename T>
+__global__ void softmax_partial_kernel(const double* __restrict__ x, const double* __restrict__ xmax,
+                                       const T* __restrict__ actions, const double* __restrict__ mean, long P, int H,
+                                       int A, int Hw, int chunk, int want_cov, double* __restrict__ partial) {
+    softmax_partial_body<T>(x, xmax, actions, mean, P, H, A, Hw, chunk, want_cov, partial);
+}
+
 // sum over workgroups of entry j of the partials: one wavefront per entry, lane l adds partials
 // l, l+64, ... in order, then a fixed butterfly - the same tree every run, on every GPU
 __device__ __forceinline__ double wave_entry_sum(const double* __restrict__ partial, int nb, int rec, int j) {
@@ -203,12 +221,12 @@ __global__ void softmax_record_kernel(const double* __restrict__ partial, const 
 
 // mean <- (1-eta) mean + eta * sum_g sc_g W_g / sum_g sc_g S_g,   sc_g = exp(xmax_g - max_g xmax_g);
 // cov likewise (mode 1: diagonal only, 2: full); value = -lam * logsumexp(x, b = 1/P_total).
-__global__ void softmax_combine_kernel(const double* __restrict__ records, int G, int H, int A, int Hw, double lam,
-                                       double step, int cov_mode, double P_total, double* __restrict__ mean,
-                                       double* __restrict__ cov, double* __restrict__ value,
-                                       double* __restrict__ wnorm) {
+// (entry j's part; the body is shared with the episode-batch kernel dmd_finish_batch_kernel below)
+__device__ __forceinline__ void softmax_combine_body(const double* __restrict__ records, int G, int H, int A, int Hw,
+                                                     double lam, double step, int cov_mode, double P_total,
+                                                     double* __restrict__ mean, double* __restrict__ cov,
+                                                     double* __restrict__ value, double* __restrict__ wnorm, int j) {
     const int HA = H * A, rlen = 2 * Hw + HA + A * A;
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
     auto scale = [&](int g, int tw, double M) { return exp(records[(long)g * rlen + tw] - M); };
     auto colmax = [&](int tw) {
         double M = -INFINITY;
@@ -241,6 +259,14 @@ __global__ void softmax_combine_kernel(const double* __restrict__ records, int G
         if (value) *value = -lam * (log(S / P_total) + M);
         if (wnorm) { wnorm[0] = M; wnorm[1] = S; }
     }
+}
+
+__global__ void softmax_combine_kernel(const double* __restrict__ records, int G, int H, int A, int Hw, double lam,
+                                       double step, int cov_mode, double P_total, double* __restrict__ mean,
+                                       double* __restrict__ cov, double* __restrict__ value,
+                                       double* __restrict__ wnorm) {
+    softmax_combine_body(records, G, H, A, Hw, lam, step, cov_mode, P_total, mean, cov, value, wnorm,
+                         blockIdx.x * blockDim.x + threadIdx.x);
 }
 
 // w[p] = exp(x[p] - M) / S          (PFMPC weights, particle_filter_controller.py:104-113)
@@ -1200,10 +1226,11 @@ __global__ void shift_kernel(double* __restrict__ mean, int H, int A, int mode, 
 // The tail of a control step in one launch: read the action out (mean[0] -> device copy and mapped host copy), shift the
 // horizon, advance the device step counter, and grow the covariance by scale * diag(d) (the shift of CEM / DMD-MPC with
 // update_cov) - five stream operations of ~5 us each when issued one by one.  Any of the outputs may be null.
-__global__ void step_tail_kernel(double* __restrict__ mean, int H, int A, int mode, const double* __restrict__ row,
-                                 double* __restrict__ action_out, double* __restrict__ action_host,
-                                 long long* __restrict__ step_counter, double* __restrict__ cov,
-                                 const double* __restrict__ d, double scale) {
+// (the body is shared with the episode-batch kernel dmd_finish_batch_kernel below)
+__device__ __forceinline__ void step_tail_body(double* __restrict__ mean, int H, int A, int mode,
+                                               const double* __restrict__ row, double* __restrict__ action_out,
+                                               double* __restrict__ action_host, long long* __restrict__ step_counter,
+                                               double* __restrict__ cov, const double* __restrict__ d, double scale) {
     const int a = threadIdx.x;
     long long count = 0;
     if (a == 0 && step_counter) count = (*step_counter += 1);
@@ -1223,6 +1250,13 @@ __global__ void step_tail_kernel(double* __restrict__ mean, int H, int A, int mo
     if (cov) cov[a * A + a] += scale * (d ? d[a] : 1.0);
 }
 
+__global__ void step_tail_kernel(double* __restrict__ mean, int H, int A, int mode, const double* __restrict__ row,
+                                 double* __restrict__ action_out, double* __restrict__ action_host,
+                                 long long* __restrict__ step_counter, double* __restrict__ cov,
+                                 const double* __restrict__ d, double scale) {
+    step_tail_body(mean, H, A, mode, row, action_out, action_host, step_counter, cov, d, scale);
+}
+
 // Device-resident covariance (CEM, DMD-MPC with update_cov): the factor the sampler colours its normals with is
 // computed where the covariance lives, so an adapting covariance never leaves the GPU.
 // chol = lower Cholesky factor of cov (numpy.linalg.cholesky in control_utils.generate_noise's place); one
@@ -1232,7 +1266,8 @@ __global__ void step_tail_kernel(double* __restrict__ mean, int H, int A, int mo
 // column - a valid factor L L' = cov of the rank-deficient matrix - instead of a NaN factor.  *status = 1 only for a
 // genuinely indefinite matrix (pivot below -tolerance) or non-finite input; the host raises on it
 // (DeviceUpdater.check_status).
-__global__ void cholesky_kernel(const double* __restrict__ cov, int A, double* __restrict__ chol, int* status) {
+// (the body is shared with the episode-batch kernel cholesky_batch_kernel below)
+__device__ __forceinline__ void cholesky_body(const double* __restrict__ cov, int A, double* __restrict__ chol, int* status) {
     __shared__ double L[64 * 64];
     __shared__ double tol;
     const int i = threadIdx.x;
@@ -1258,6 +1293,16 @@ __global__ void cholesky_kernel(const double* __restrict__ cov, int A, double* _
         __syncthreads();
     }
     if (i < A) for (int j = 0; j < A; ++j) chol[i * A + j] = L[i * A + j];
+}
+
+__global__ void cholesky_kernel(const double* __restrict__ cov, int A, double* __restrict__ chol, int* status) {
+    cholesky_body(cov, A, chol, status);
+}
+
+// episode batches: grid row e runs cholesky_kernel on episode e's covariance; status[e] is that row's flag
+__global__ void cholesky_batch_kernel(const double* __restrict__ covs, int A, double* __restrict__ chols, int* status) {
+    const long e = blockIdx.x;
+    cholesky_body(covs + e * A * A, A, chols + e * A * A, status ? status + e : nullptr);
 }
 
 // cov += scale * diag(d)   (CEM._shift cem.py:94, DMDMPC._shift gaussian_dmd.py:111-112); d == nullptr: identity
@@ -1462,6 +1507,93 @@ __global__ void fused_final_batch_kernel(const double* __restrict__ partial, lon
     const long e = blockIdx.y;
     fused_final_body(partial + e * partial_stride, nb, H, A, lam[e], step[e], shift_mode, P_total, mean + e * H * A,
                      action_out ? action_out + e * A : nullptr, nullptr, nullptr, nullptr, e == 0 ? step_counter : nullptr);
+}
+
+// ---- episode batches of the covariance-adapting DMD-MPC step --------------------------------------------------
+// Grid row e of every launch runs the text of the single path's kernels - traj_cost_body, colmax_kernel's maximum,
+// softmax_partial_body, wave_entry_sum, softmax_combine_body, step_tail_body - on episode e's slices.
+// -- one episode's block of the batch workspace, laid out alike on host and device:
+// x[P] | xmax (padded to 8) | record [2 + HA + AA] | partials [nb][1 + HA + AA]
+struct DmdRow {
+    double *x, *xmax, *record, *partial;
+    __host__ __device__ DmdRow(double* base, long P, int HA, int AA) {
+        x = base;
+        xmax = x + P;
+        record = xmax + 8;
+        partial = record + 2 + HA + AA;
+    }
+};
+__host__ __device__ inline long dmd_row_doubles(long P, int HA, int AA, int nb) {
+    return P + 8 + (2 + HA + AA) + (long)nb * (1 + HA + AA);
+}
+template <typename T>
+struct DmdBatch {
+    const T *costs, *actions;
+    const double *gseq, *lam, *step, *beta;
+    double *means, *covs, *actions_out, *ws;
+    long long* step_counter;
+    const double* un;           // (null: the control cost is off, alpha = 1 - a run-time null, as the single launch gets it)
+    double* q0;                 // (null: nobody reads the batch's cost-to-go)
+    long stride, P;
+    int H, A, nb, chunk, gamma_zero, want_cov, cov_mode, shift_mode, G;
+};
+
+// row e: x = traj_cost_kernel's (one weight per particle, Hw = 1) for its P particles, then colmax_kernel's maximum of them
+template <typename T>
+__global__ void dmd_x_colmax_batch_kernel(DmdBatch<T> b) {
+    __shared__ double sm[BLK / 64];
+    const long e = blockIdx.y, P = b.P;
+    const int HA = b.H * b.A;
+    const DmdRow r(b.ws + e * b.stride, P, HA, b.A * b.A);
+    for (long p = threadIdx.x; p < P; p += blockDim.x)
+        traj_cost_body<T>(b.costs + e * P * b.H, b.actions + e * P * HA, b.means + e * HA, b.un, b.gseq, b.gamma_zero,
+                          b.lam[e], p, b.H, b.A, 1, r.x, b.q0);
+    __syncthreads();
+    double m = -INFINITY;
+    for (long p = threadIdx.x; p < P; p += blockDim.x) m = fmax(m, r.x[p]);
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < BLK / 64; ++w) m = fmax(m, sm[w]);
+        r.xmax[0] = m;
+    }
+}
+
+// row e: softmax_partial_kernel on its particles (the same chunks, the mean from before the update) into its partials
+template <typename T>
+__global__ void softmax_partial_batch_kernel(DmdBatch<T> b) {
+    const long e = blockIdx.y;
+    const int HA = b.H * b.A;
+    const DmdRow r(b.ws + e * b.stride, b.P, HA, b.A * b.A);
+    softmax_partial_body<T>(r.x, r.xmax, b.actions + e * b.P * HA, b.means + e * HA, b.P, b.H, b.A, 1, b.chunk, b.want_cov,
+                            r.partial);
+}
+
+// row e: softmax_record_kernel (a wavefront per entry: wave_entry_sum over its nb partials), softmax_combine_kernel with that
+// one record, step_tail_kernel - one workgroup, a barrier where the single path has a launch boundary.  Row 0 advances the
+// shared step counter; no row reads it.
+template <typename T>
+__global__ void dmd_finish_batch_kernel(DmdBatch<T> b) {
+    const long e = blockIdx.y;
+    const int H = b.H, A = b.A, HA = H * A, AA = A * A, rec = 1 + HA + AA;
+    const DmdRow r(b.ws + e * b.stride, b.P, HA, AA);
+    for (int j = threadIdx.x >> 6; j < rec; j += blockDim.x >> 6) {
+        const double s = wave_entry_sum(r.partial, b.nb, rec, j);
+        if ((threadIdx.x & 63) == 0) {
+            r.record[1 + j] = s;
+            if (j < 1) r.record[j] = r.xmax[j];
+        }
+    }
+    __syncthreads();
+    double* mean = b.means + e * HA;
+    double* cov = b.covs + e * AA;
+    const int n = HA > AA ? HA : AA;
+    for (int j = threadIdx.x; j < n; j += blockDim.x)
+        softmax_combine_body(r.record, b.G, H, A, 1, b.lam[e], b.step[e], b.cov_mode, (double)b.P, mean, cov, nullptr, nullptr, j);
+    __syncthreads();
+    step_tail_body(mean, H, A, b.shift_mode, nullptr, b.actions_out ? b.actions_out + e * A : nullptr, nullptr,
+                   e == 0 ? b.step_counter : nullptr, cov, nullptr, b.beta[e]);
 }
 
 inline int nblocks(long n, int b) { return (int)((n + b - 1) / b); }
@@ -1892,6 +2024,38 @@ hipError_t cholesky_lower(const double* cov, int A, double* chol, int* status, h
     return hipGetLastError();
 }
 
+hipError_t cholesky_lower_batch(int E, const double* covs, int A, double* chols, int* status, hipStream_t s) {
+    if (E < 1 || E > 65535 || A < 1 || A > 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cholesky_batch_kernel, dim3(E), dim3(64), 0, s, covs, A, chols, status);
+    return hipGetLastError();
+}
+
+long dmd_batch_workspace_doubles(int E, long P, int H, int A) {
+    return (long)E * dmd_row_doubles(P, H * A, A * A, nblocks(P, CHUNK));
+}
+
+// One episode per grid row, each row what softmax_stats (one weight per particle, control cost off, want_cov) +
+// softmax_combine (one record) + step_tail do for its P particles: the same CHUNK particles per partial, the same
+// nb = ceil(P / CHUNK), the same wave_entry_sum tree over them, the same combine and tail - three launches.
+template <typename T>
+hipError_t dmd_update_batch(int E, const T* costs, const T* actions, const double* gseq, const double* lam,
+                            const double* step, int cov_mode, const double* beta, int shift_mode, long P, int H, int A,
+                            double* means, double* covs, double* actions_out, long long* step_counter, double* ws,
+                            hipStream_t s) {
+    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1 || A > 64) return hipErrorInvalidValue;
+    DmdBatch<T> b;
+    b.costs = costs; b.actions = actions; b.gseq = gseq; b.lam = lam; b.step = step; b.beta = beta;
+    b.means = means; b.covs = covs; b.actions_out = actions_out; b.ws = ws; b.step_counter = step_counter;
+    b.un = nullptr; b.q0 = nullptr;
+    b.nb = nblocks(P, CHUNK); b.chunk = CHUNK;
+    b.stride = dmd_row_doubles(P, H * A, A * A, b.nb); b.P = P; b.H = H; b.A = A;
+    b.gamma_zero = 0; b.want_cov = 1; b.cov_mode = cov_mode; b.shift_mode = shift_mode; b.G = 1;
+    hipLaunchKernelGGL(dmd_x_colmax_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
+    hipLaunchKernelGGL(softmax_partial_batch_kernel<T>, dim3(b.nb, E), dim3(BLK), sizeof(double) * CHUNK, s, b);
+    hipLaunchKernelGGL(dmd_finish_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
+    return hipGetLastError();
+}
+
 hipError_t cov_add_diag(double* cov, int A, const double* d, double scale, hipStream_t s) {
     if (A < 1 || A > 64) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cov_add_diag_kernel, dim3(1), dim3(64), 0, s, cov, A, d, scale);
@@ -1941,7 +2105,10 @@ hipError_t step_tail(double* mean, int H, int A, int mode, const double* row, do
                                              double*, double*, double*, double*, hipStream_t, double*, long long*,   \
                                              const NextNoise*);                                                      \
     template hipError_t mppi_fused_update_batch<T>(int, const double*, const T*, const double*, const double*, int, long, \
-                                                   int, int, double*, double*, long long*, double*, hipStream_t);
+                                                   int, int, double*, double*, long long*, double*, hipStream_t);    \
+    template hipError_t dmd_update_batch<T>(int, const T*, const T*, const double*, const double*, const double*, int, \
+                                            const double*, int, long, int, int, double*, double*, double*, long long*, \
+                                            double*, hipStream_t);
 INST(float)
 INST(double)
 

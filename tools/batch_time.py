@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Episode batches (BatchedMPPI / BatchedCEM / BatchedPFMPC): ms per batched control step and episode-steps/s, against the sequential loop.
+"""Episode batches (BatchedMPPI / BatchedCEM / BatchedPFMPC / BatchedDMDMPC): ms per batched control step and episode-steps/s, against the sequential loop.
 
 For every model x E x P x H: one ``BatchedMPPI`` of E episodes of P particles (f64), timed with device events over
 --steps control steps after --warmup; in the same process the single-episode device path on its own engine (MPPI,
@@ -8,7 +8,7 @@ the same way.  The sequential loop of E episodes costs E times that per control 
 the same shape).  One JSON line per configuration, then a table.
 
     python tools/batch_time.py [--models half_cheetah,swimmer,sawyer] [--E 1,4,16,64] [--P 256,1024] [--H 16,32]
-        [--model-shards K] [--controller mppi|cem|pfmpc] [--repeats R]
+        [--model-shards K] [--controller mppi|cem|pfmpc|dmd] [--repeats R]
 
 --controller cem: ``BatchedCEM`` (full covariance, elite_frac 0.1, beta 0.45) against the single-episode fused CEM
 step (CEM, noise_mode='device', graph replay).  --repeats R: every configuration is timed R times, batch and single runs
@@ -18,6 +18,10 @@ alternating; the medians are reported with the single path's own spread (max - m
 single-episode device path of particle-filter MPC (PFMPC, noise_mode='device', the resident real env stepped by
 ``set_post_step(engine.step_state)``; its ``optimize()`` waits for the action once per step, as that loop does).  After the
 table: the per-launch split of one batched step (device events around every launch, so their sum exceeds the step's time).
+
+--controller dmd: ``BatchedDMDMPC`` (full covariance, update_cov, beta 0.05) against the single-episode captured
+DMD-MPC loop (DMDMPC, update_cov=True, noise_mode='device', graph replay: the general step of about ten launches), with the
+per-launch split of one batched step as for pfmpc.
 
 --model-shards K: the batch rolls out K randomized model shards per episode (a set per episode, body masses
 +- 20 %) and the single-episode path is the sequential dynamics-randomized loop - a K-shard engine with randomized blocks
@@ -49,15 +53,21 @@ ELITE_FRAC, BETA = 0.1, 0.45       # (--controller cem)
 COV_SHIFT, PF_LAM, PF_GAMMA = 0.02, 1.0, 0.99       # (--controller pfmpc)
 PF_LAUNCHES = ("mjmpc_pf_delta_batch", "mjmpc_tree_rollout_fused_batch", "mjmpc_pf_weights_batch", "mjmpc_pf_resample_batch",
                "mjmpc_pf_gather_shift_batch", "mjmpc_pf_finish_batch", "mjmpc_tree_step_shard_states")
+DMD_BETA = 0.05                     # (--controller dmd)
+# (mjmpc_sample_noise_cov_batch is the draw and the filter launch, mjmpc_dmd_update_batch the three update launches)
+DMD_LAUNCHES = ("mjmpc_cholesky_lower_batch", "mjmpc_sample_noise_cov_batch", "mjmpc_tree_rollout_fused_batch",
+                "mjmpc_dmd_update_batch", "mjmpc_tree_step_shard_states")
 
 
 def make_batch(raw, E, P, H, lam, cov, controller):
-    from mjmpc_amd.control import BatchedCEM, BatchedMPPI, BatchedPFMPC
+    from mjmpc_amd.control import BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedPFMPC
     seeds = [123 + i * 12345 for i in range(E)]
     if controller == "cem":
         return BatchedCEM(raw, E, H, P, cov, ELITE_FRAC, 1.0, BETA, 1.0, FILT, "null", seeds)
     if controller == "pfmpc":
         return BatchedPFMPC(raw, E, H, P, COV_SHIFT, cov, PF_LAM, PF_GAMMA, FILT, "null", seeds)
+    if controller == "dmd":
+        return BatchedDMDMPC(raw, E, H, P, lam, 1.0, cov, DMD_BETA, 1.0, FILT, "null", seeds, cov_type="full")
     return BatchedMPPI(raw, E, H, P, lam, 1.0, cov, 1.0, FILT, "null", seeds)
 
 
@@ -83,20 +93,24 @@ class _TimedLib:
         return timed
 
 
-def launch_split(raw, E, P, H, lam, cov, steps, warmup):
-    """ms per launch of one batched PFMPC step (mean over ``steps`` steps)."""
+def launch_split(raw, E, P, H, lam, cov, steps, warmup, controller="pfmpc"):
+    """ms per library call of one batched PFMPC / DMD-MPC step (mean over ``steps`` steps)."""
     import torch
-    b = make_batch(raw, E, P, H, lam, cov, "pfmpc")
+    names = LAUNCHES[controller]
+    b = make_batch(raw, E, P, H, lam, cov, controller)
     b.on_env_reset = "ignore"
     for _ in range(warmup):
         b.step()
-    b.lib = timed = _TimedLib(b.lib, PF_LAUNCHES)
+    b.lib = timed = _TimedLib(b.lib, names)
     for _ in range(steps):
         b.step()
     torch.cuda.synchronize()
     b.lib = timed._lib
     b.close()
-    return {n: sum(s.elapsed_time(e) for s, e in timed.events[n]) / steps for n in PF_LAUNCHES}
+    return {n: sum(s.elapsed_time(e) for s, e in timed.events[n]) / steps for n in names}
+
+
+LAUNCHES = {"pfmpc": PF_LAUNCHES, "dmd": DMD_LAUNCHES}
 
 
 def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
@@ -119,7 +133,7 @@ def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
 
 def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     import torch
-    from mjmpc_amd.control import CEM, MPPI, PFMPC
+    from mjmpc_amd.control import CEM, DMDMPC, MPPI, PFMPC
     from mjmpc_amd.control.controller import resident_state
     from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
     from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
@@ -137,6 +151,11 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
                 elite_frac=ELITE_FRAC, num_particles=P, step_size=1.0, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
                 action_highs=eng.action_highs, beta=BETA, cov_type="full", filter_coeffs=FILT, seed=123, noise_mode="device",
                 noise_dtype="f64")
+    elif controller == "dmd":
+        c = DMDMPC(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov, beta=DMD_BETA,
+                   base_action="null", lam=lam, num_particles=P, step_size=1.0, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
+                   action_highs=eng.action_highs, update_cov=True, cov_type="full", filter_coeffs=FILT, seed=123,
+                   noise_mode="device", noise_dtype="f64")
     else:
         c = MPPI(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov, base_action="null",
                  lam=lam, num_particles=P, step_size=1.0, alpha=1, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
@@ -159,6 +178,8 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     torch.cuda.synchronize()
     if controller == "cem" and not c._cem_fused():
         raise SystemExit("the single-episode CEM path did not take its fused step at %d x %d" % (P, H))
+    if controller == "dmd" and (c._fused_capable() or not c._device_cov()):
+        raise SystemExit("the single-episode DMD-MPC path did not take its covariance-adapting step")
     eng.close()
     return s.elapsed_time(e) / steps
 
@@ -172,7 +193,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--model-shards", type=int, default=0, help="randomized model shards per episode (0: no randomization)")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc"])
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd"])
     ap.add_argument("--repeats", type=int, default=1, help="timings per configuration, batch and single runs alternating")
     args = ap.parse_args()
     from mjmpc_amd import _lib
@@ -204,10 +225,10 @@ def main():
                         row.update(repeats=args.repeats, single_spread_ms=round(spread, 4))
                     rows.append(row)
                     print(json.dumps(row), flush=True)
-                    if args.controller == "pfmpc" and not args.model_shards:
-                        split = launch_split(raw, E, P, H, lam, cov, args.steps, args.warmup)
+                    if args.controller in LAUNCHES and not args.model_shards:
+                        split = launch_split(raw, E, P, H, lam, cov, args.steps, args.warmup, args.controller)
                         splits.append((name, E, P, H, split))
-                        print(json.dumps(dict(model=name, controller="pfmpc", E=E, P=P, H=H,
+                        print(json.dumps(dict(model=name, controller=args.controller, E=E, P=P, H=H,
                                               launch_ms={k: round(v, 4) for k, v in split.items()})), flush=True)
     print("%-13s %3s %5s %3s %10s %10s %12s %8s" % ("model", "E", "P", "H", "batch ms", "single ms", "E x single", "speedup"))
     for r in rows:
@@ -217,11 +238,12 @@ def main():
         print("single path, max - min over its repeats (ms): "
               + ", ".join("%d x %d: %.3f" % (r["E"], r["P"], r["single_spread_ms"]) for r in rows))
     if splits:
-        short = [n.replace("mjmpc_", "").replace("_batch", "") for n in PF_LAUNCHES]
-        print("per-launch split of one batched step (ms, device events around each launch)")
+        names = LAUNCHES[args.controller]
+        short = [n.replace("mjmpc_", "").replace("_batch", "") for n in names]
+        print("per-launch split of one batched step (ms, device events around each library call)")
         print("%-13s %3s %5s %3s " % ("model", "E", "P", "H") + " ".join("%18s" % n for n in short))
         for name, E, P, H, split in splits:
-            print("%-13s %3d %5d %3d " % (name, E, P, H) + " ".join("%18.4f" % split[n] for n in PF_LAUNCHES))
+            print("%-13s %3d %5d %3d " % (name, E, P, H) + " ".join("%18.4f" % split[n] for n in names))
 
 
 if __name__ == "__main__":
