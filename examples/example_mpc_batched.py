@@ -1,8 +1,9 @@
 #!/usr/bin/env python
-"""The config's ``n_episodes`` MPPI, CEM, PFMPC or DMD-MPC episodes as ONE batch on the tree engine (``BatchedMPPI`` /
-``BatchedCEM`` / ``BatchedPFMPC`` / ``BatchedDMDMPC``).
+"""The config's ``n_episodes`` MPPI, CEM, PFMPC, DMD-MPC or random-shooting episodes as ONE batch on the tree engine
+(``BatchedMPPI`` / ``BatchedCEM`` / ``BatchedPFMPC`` / ``BatchedDMDMPC`` / ``BatchedRandomShooting``).
 
-    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml [--controller mppi|cem|pfmpc|dmd]
+    python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml
+        [--controller mppi|cem|pfmpc|dmd|random_shooting]
         [--dtype f64|f32] [--episodes N] [--dyn_randomize_config FILE [--num_cpu K] [--dyn_per_episode]]
         [--update_cov] [--cov_type diagonal|full]
 
@@ -17,12 +18,14 @@ particles are split into the config's ``num_cpu`` shards and each shard rolls ou
 all episodes from the config's ``seed`` as the reference does before its episode loop (``--dyn_per_episode``: from every
 episode's own seed), while the real envs keep the nominal model - still one batch.
 
-The ``mppi``, ``cem``, ``pfmpc`` and ``dmd`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection +
+The ``mppi``, ``cem``, ``pfmpc``, ``dmd`` and ``random_shooting`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection +
 moments, refit + next samples and env-step launches per control step; ``--controller pfmpc``: ``BatchedPFMPC``, DESIGN 10.3 -
 deviations, rollout, weights, resampling, gather + shift, mean + action and env step, e.g. examples/configs/reacher_gpu.yml;
 ``--controller dmd``: with ``update_cov: true`` ``BatchedDMDMPC``, DESIGN 10.4 - factors, draw, filter, rollout, weights, partial
 moments, update + tail and env step -, with ``update_cov: false`` ``BatchedMPPI`` with the block's ``lam``, ``step_size`` and
-``init_cov``, which is that arithmetic; the class that ran is printed); other controller blocks are refused.  The reacher configs run on the TREE engine here
+``init_cov``, which is that arithmetic; the class that ran is printed; ``--controller random_shooting``:
+``BatchedRandomShooting``, DESIGN 10.5 - draw, rollout, selection + blend + tail and env step); other controller blocks are
+refused.  The reacher configs run on the TREE engine here
 (sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
 rewards are not expected to be equal.
 """
@@ -37,15 +40,15 @@ import yaml
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from example_mpc import ENVS, TREE_MODELS                           # noqa: E402
-from mjmpc_amd.control import BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedPFMPC  # noqa: E402
+from mjmpc_amd.control import BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedPFMPC, BatchedRandomShooting  # noqa: E402
 from mjmpc_amd.envs.tree_engine import TreeRolloutEngine            # noqa: E402
 from mjmpc_amd.models.reacher7dof import reacher7dof_raw            # noqa: E402
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM, PFMPC or DMD-MPC episodes as one batch")
+    ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM, PFMPC, DMD-MPC or random-shooting episodes as one batch")
     ap.add_argument("--config", required=True, help="yaml file with experiment parameters")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd"],
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting"],
                     help="controller block of the config to run")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--episodes", type=int, help="override n_episodes")
@@ -99,6 +102,11 @@ def main():
                               params["init_cov"], params.get("beta", 0.0), params["gamma"], params["filter_coeffs"], base_action,
                               seeds, cov_type=params.get("cov_type", "diagonal"), dtype=args.dtype,
                               n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
+    elif args.controller == "random_shooting":
+        batch = BatchedRandomShooting(raw, E, params["horizon"], params["num_particles"], params["step_size"],
+                                      params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds,
+                                      dtype=args.dtype, n_iters=params.get("n_iters", 1),
+                                      sample_mode=params.get("sample_mode", "mean"))
     elif args.controller == "dmd":      # (without covariance adaptation DMD-MPC is MPPI with alpha = 1: gaussian_dmd.py:65-104)
         batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
                             params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,

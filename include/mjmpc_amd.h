@@ -575,6 +575,22 @@ int mjmpc_dmd_update_batch(int dtype, int E, int64_t P, int H, int A, const void
                            const double* d_beta, int shift_mode, double* d_means, double* d_covs, double* d_actions_out,
                            int64_t* d_step_counter, void* d_ws, void* stream);
 
+/* Episode batches of the random-shooting step (random_shooting.py:52-62, one per episode of the reference's episode loop):
+ * one launch, grid row e = episode e, no host synchronisation, no workspace.  Row e is mjmpc_rs_best(dtype, P, H, A,
+ * d_actions + e P H A, 0, record, ws) on the cost-to-go d_q0 + e P, then mjmpc_rs_combine(record, 1, H, A, d_step_size[e],
+ * d_means + e H A), then mjmpc_step_tail(d_means + e H A, H, A, shift_mode, NULL, d_actions_out + e A, NULL, counter, NULL,
+ * NULL, 0): the particle with the first minimum of its cost-to-go (numpy.argmin: ties go to the lowest index), mean <-
+ * (1 - step) mean + step * its actions, the action read-out and the horizon shift.  A row whose cost-to-go values are all
+ * +inf selects particle 0, as numpy.argmin does (the single calls are undefined for such a row).  d_q0 float64 [E][P] without
+ * NaN, d_actions dtype [E][P][H][A], d_step_size float64 [E] (device), shift_mode 0 'null' or 1 'repeat', d_means float64
+ * [E][H][A] (updated and shifted in place), d_actions_out float64 [E][A] (may be NULL), d_best int64 [E] (may be NULL): the
+ * selected particle of every row.  *d_step_counter (may be NULL) is advanced once, by row 0; no row reads it.
+ * mjmpc_rs_batch_supported(E, P, H, A): 1 <= E <= 65535, P >= 1, H >= 1, 1 <= A <= 256 (MJMPC_E_BADARG otherwise). */
+int mjmpc_rs_batch_supported(int E, int64_t P, int H, int A);
+int mjmpc_rs_update_batch(int dtype, int E, int64_t P, int H, int A, const double* d_q0, const void* d_actions,
+                          const double* d_step_size, int shift_mode, double* d_means, double* d_actions_out,
+                          int64_t* d_step_counter, int64_t* d_best, void* stream);
+
 /* Sharded MPPI: the G all-gathered records d_records (float64 [G][2 + H*A], as left in d_record by
  * mjmpc_mppi_fused_update with step_size 0, shift_mode -1) merged in rank order -> mean update, action read-out,
  * shift, step counter and the mapped host copy with its completion flag, exactly as the single-GPU call does

@@ -10,6 +10,7 @@ _WHERE = {
     "BatchedCEM": "batched",
     "BatchedPFMPC": "batched",
     "BatchedDMDMPC": "batched",
+    "BatchedRandomShooting": "batched",
 }
 __all__ = sorted(_WHERE)
 

@@ -1,4 +1,5 @@
-"""Episode batches: E independent MPPI, CEM, PFMPC or DMD-MPC episodes side by side on the tree engine.
+"""Episode batches: E independent MPPI, CEM, PFMPC, DMD-MPC or random-shooting episodes side by side on the tree engine (DESIGN
+10, 10.2 - 10.5).
 
 The reference runs its experiments one episode after another (examples/job_script.py:80-99, the episode loop of
 examples/example_mpc.py), each with its own seed (``seed + i*12345``) and start state, and its "tune" mode multiplies
@@ -28,7 +29,9 @@ MPC (particle_filter_controller.py, ``noise_mode='device'``): per e
 ``cov_resample``, and a particle set that is resampled on the device.  ``BatchedDMDMPC`` is the batch of DMD-MPC with an
 adapting covariance (gaussian_dmd.py with ``update_cov=True``): per episode ``lam``, ``step_size``, ``init_cov``
 and ``beta``, and a ``'diagonal'`` or ``'full'`` covariance that is re-estimated from the weighted samples, grown by
-``beta I`` and factored on the device every step (``update_cov=False`` is ``BatchedMPPI``'s arithmetic).  The classes share
+``beta I`` and factored on the device every step (``update_cov=False`` is ``BatchedMPPI``'s arithmetic).
+``BatchedRandomShooting`` is the batch of random shooting (random_shooting.py): per episode ``step_size`` and
+``init_cov``, and a mean that moves towards the best sample of the step.  The classes share
 ``_EpisodeBatch``: the engine, the state shards, the buffers, the rollout launch, the env step, ``run`` and dynamics
 randomization.
 """
@@ -694,3 +697,72 @@ class BatchedPFMPC(_EpisodeBatch):
         return dict(samples=self._set_alt, costs=self._costs.view(E, P, H), q0=self._q0.view(E, P), w=self._w,
                     first=self._first, idx=self._idx, resampled=self._gathered, mean=self._means, shifted=self._set,
                     step=self.num_steps - 1)
+
+
+class BatchedRandomShooting(_EpisodeBatch):
+    """``num_episodes`` random-shooting controllers (random_shooting.py, one iteration per step) and their real envs, stepped
+    together.
+
+    Episode e computes the bits of ``RandomShooting(..., noise_mode='device', noise_dtype=dtype, seed=seeds[e])`` on a
+    ``TreeRolloutEngine`` of its own with ``make_device_rollout_fn`` and ``enable_graph(post_step=engine.step_state)``: the
+    Philox draw with the static diagonal factor, the fused rollout (filter + rollout + cost-to-go), ``mjmpc_rs_best`` +
+    ``mjmpc_rs_combine`` and ``mjmpc_step_tail``.  ``step_size``, ``init_cov`` (scalar: ``diag(init_cov)``, as ``RandomShooting``
+    takes it) and ``init_mean`` (``(H, A)``, default zeros) take one value for every episode or one per episode; ``seeds`` one
+    seed per episode.  A control step is four launches - draw, rollout, selection + blend + action + shift, real-env step -
+    and nothing synchronises.  An episode whose cost-to-go values are all ``+inf`` takes particle 0, as ``np.argmin`` does (the
+    single path is undefined there).  Settings the batch does not run raise ``ValueError`` before any engine or device memory
+    exists: ``n_iters != 1``, ``sample_mode != 'mean'``, ``use_zero_control_seq``, ``gamma == 0``, ``base_action`` other than
+    ``'null'`` / ``'repeat'``, ``init_cov <= 0``, ``step_size < 0``, a wrong seed count, a shape outside
+    ``mjmpc_rs_batch_supported`` and a model the tree engine refuses."""
+
+    def __init__(self, raw_model, num_episodes, horizon, num_particles, step_size, init_cov, gamma, filter_coeffs, base_action,
+                 seeds, init_mean=None, dtype="f64", device=0, n_iters=1, use_zero_control_seq=False, sample_mode="mean"):
+        # -- everything that can be refused is refused here, before the engine and its device memory exist
+        E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
+                                         sample_mode, dtype, gamma, filter_coeffs, "random-shooting")
+        step_size = _per_episode("step_size", step_size, E)
+        init_cov = _per_episode("init_cov", init_cov, E)
+        if not np.all(init_cov > 0):
+            raise ValueError("init_cov must be positive")
+        if not np.all(step_size >= 0):
+            raise ValueError("step_size must not be negative")
+        self.seed_vals = self._check_seeds(seeds, E)
+        model = self._compile(raw_model)
+        A = model.nu
+        lib = _lib.load()
+        if not lib.mjmpc_rs_batch_supported(E, P, H, A):
+            raise ValueError("the batched random-shooting step takes up to 256 action channels, got A = %d" % A)
+        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
+        factors = [noise_factor(np.diag(np.array([c] * A))) for c in init_cov]      # (OLGaussianMPC: diag(init_cov))
+
+        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+        self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
+        torch, dev = self.torch, self.device
+        self.step_size, self.init_cov = step_size, init_cov
+        self._chols = torch.from_numpy(np.stack([f[0] for f in factors])).to(dev)
+        self._step = torch.from_numpy(step_size.copy()).to(dev)
+        self._best = torch.zeros(E, dtype=torch.int64, device=dev)
+        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+
+    @property
+    def best_particle(self):
+        """The particle every episode's last step moved its mean towards, ``(E,)`` int64 (synchronises)."""
+        out = self._best.cpu().numpy().copy()
+        self._check_status()
+        return out
+
+    def step(self, _out=None):
+        """Enqueue one control step of every episode (sampling, rollouts, selection + blend + action + shift, real-env step)
+        without a host synchronisation.  The actions, real-env costs and next observations stay on the device."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
+        lib, code, s = self.lib, self._code, self._stream()
+        _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
+                                                _vp(self._step_dev), s))
+        self._rollout(s)
+        _lib.check(lib.mjmpc_rs_update_batch(code, E, P, H, A, _vp(self._q0), _vp(self._actions), _vp(self._step),
+                                             _SHIFT_MODES[self.base_action], _vp(self._means), _vp(act), _vp(self._step_dev),
+                                             _vp(self._best), s))
+        self._env_step(act, cost, nobs, s)
+        self.num_steps += 1
+        return act, cost, nobs

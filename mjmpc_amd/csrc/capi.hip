@@ -1638,6 +1638,25 @@ int mjmpc_dmd_update_batch(int dtype, int E, int64_t P, int H, int A, const void
                                              (long long*)d_step_counter, (double*)d_ws, s));
 }
 
+int mjmpc_rs_batch_supported(int E, int64_t P, int H, int A) { return mjmpc::rs_batch_supported(E, (long)P, H, A) ? 1 : 0; }
+
+int mjmpc_rs_update_batch(int dtype, int E, int64_t P, int H, int A, const double* d_q0, const void* d_actions,
+                          const double* d_step_size, int shift_mode, double* d_means, double* d_actions_out,
+                          int64_t* d_step_counter, int64_t* d_best, void* stream) {
+    if (!d_q0 || !d_actions || !d_step_size || !d_means) return fail(MJMPC_E_BADARG, "null argument");
+    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
+    if (P < 1 || H < 1 || A < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d, A = %d", (long long)P, H, A);
+    if (!mjmpc::rs_batch_supported(E, (long)P, H, A))
+        return fail(MJMPC_E_BADARG, "A = %d outside 1 .. 256 (mjmpc_rs_batch_supported)", A);
+    if (shift_mode < 0 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::rs_update_batch<float>(E, d_q0, (const float*)d_actions, d_step_size, shift_mode, (long)P, H, A, d_means,
+                                           d_actions_out, (long long*)d_step_counter, (long long*)d_best, s),
+             mjmpc::rs_update_batch<double>(E, d_q0, (const double*)d_actions, d_step_size, shift_mode, (long)P, H, A, d_means,
+                                            d_actions_out, (long long*)d_step_counter, (long long*)d_best, s));
+}
+
 int mjmpc_cov_add_diag(double* d_cov, int A, const double* d_diag, double scale, void* stream) {
     if (!d_cov || A < 1 || A > 64) return fail(MJMPC_E_BADARG, "bad argument (A <= 64)");
     PLAIN(mjmpc::cov_add_diag(d_cov, A, d_diag, scale, (hipStream_t)stream));

@@ -109,6 +109,15 @@ hipError_t dmd_update_batch(int E, const T* costs, const T* actions, const doubl
 // row e is cholesky_lower on covs + e A A -> chols + e A A with its own sticky flag status[e] (status may be null)
 hipError_t cholesky_lower_batch(int E, const double* covs, int A, double* chols, int* status, hipStream_t s);
 
+// Episode batches of the random-shooting step (random_shooting.py:52-62): grid row e is rs_best + rs_combine (one record,
+// step[e]) + step_tail (shift_mode) on episode e's slices, in one launch and without a workspace; the first index of the
+// minimum of q0 + e P (particle 0 for a row of +inf) also goes to best[e] (may be null); row 0 increments the shared step
+// counter once.  rs_batch_supported: 1 <= E <= 65535, P, H >= 1, 1 <= A <= 256 (a thread per action channel in the tail).
+bool rs_batch_supported(int E, long P, int H, int A);
+template <typename T>
+hipError_t rs_update_batch(int E, const double* q0, const T* actions, const double* step, int shift_mode, long P, int H, int A,
+                           double* means, double* actions_out, long long* step_counter, long long* best, hipStream_t s);
+
 // the all-gathered records of G GPUs -> mean, action (device + mapped host copy with completion flag), step counter, shift
 hipError_t mppi_fused_combine(const double* records, int G, double P_total, double lam, double step, int shift_mode,
                               int H, int A, double* mean, double* action_out, double* value, double* action_host,

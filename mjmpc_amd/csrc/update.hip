@@ -1182,6 +1182,10 @@ __global__ void argmin_kernel(const double* __restrict__ q, long P, double* __re
     if (threadIdx.x == 0) { *out_val = sv[0]; *out_idx = si[0]; }
 }
 
+// one entry of the move towards the best action sequence (random_shooting.py:52-62)
+// (the body is shared with the episode-batch kernel rs_update_batch_kernel below: one expression, one contraction)
+__device__ __forceinline__ double rs_blend(double step, double mean, double best) { return (1.0 - step) * mean + step * best; }
+
 // best[g] = {value, global index, action[H*A]} records -> mean update (random_shooting.py:52-62)
 __global__ void rs_combine_kernel(const double* __restrict__ records, int G, int HA, double step, double* __restrict__ mean) {
     int best = 0;
@@ -1190,7 +1194,7 @@ __global__ void rs_combine_kernel(const double* __restrict__ records, int G, int
         if (v < b || (v == b && records[(long)g * (2 + HA) + 1] < records[(long)best * (2 + HA) + 1])) best = g;
     }
     for (int j = threadIdx.x; j < HA; j += blockDim.x)
-        mean[j] = (1.0 - step) * mean[j] + step * records[(long)best * (2 + HA) + 2 + j];
+        mean[j] = rs_blend(step, mean[j], records[(long)best * (2 + HA) + 2 + j]);
 }
 
 template <typename T>
@@ -1594,6 +1598,57 @@ __global__ void dmd_finish_batch_kernel(DmdBatch<T> b) {
     __syncthreads();
     step_tail_body(mean, H, A, b.shift_mode, nullptr, b.actions_out ? b.actions_out + e * A : nullptr, nullptr,
                    e == 0 ? b.step_counter : nullptr, cov, nullptr, b.beta[e]);
+}
+
+// ---- episode batches of the random-shooting step ---------------------------------------------------------------
+// Row e: the single path's argmin_kernel + rs_record_kernel + rs_combine_kernel (one record) + step_tail_kernel on episode e's
+// slices, one workgroup and one launch.  The selection is compares of (value, index) pairs - a strided scan per thread, a
+// butterfly over each wavefront, the BLK / 64 wave results through LDS - and so exact whatever its order: the first index of
+// the minimum, np.argmin's.  A row without an entry below +inf (all +inf; NaN is outside the contract) selects particle 0,
+// np.argmin's answer - never index P, which argmin_kernel gives for such a row.  The blend is rs_blend, the tail
+// step_tail_body; the barrier between them stands where the single path has a launch boundary.  Row 0 advances the shared
+// step counter; no row reads it.
+template <typename T>
+__global__ __launch_bounds__(BLK) void rs_update_batch_kernel(const double* __restrict__ q0, const T* __restrict__ actions,
+                                                              const double* __restrict__ step, long P, int H, int A,
+                                                              int shift_mode, double* __restrict__ means,
+                                                              double* __restrict__ actions_out,
+                                                              long long* __restrict__ step_counter,
+                                                              long long* __restrict__ best_out) {
+    __shared__ double sv[BLK / 64];
+    __shared__ long si[BLK / 64];
+    const long e = blockIdx.y;
+    const int HA = H * A;
+    const double* q = q0 + e * P;
+    double bv = INFINITY;
+    long bi = P;
+    for (long p = threadIdx.x; p < P; p += blockDim.x) {
+        const double v = q[p];
+        if (v < bv) { bv = v; bi = p; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const double v = __shfl_xor(bv, o);
+        const long i = __shfl_xor(bi, o);
+        if (v < bv || (v == bv && i < bi)) { bv = v; bi = i; }
+    }
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+    __syncthreads();
+    bv = sv[0];
+    bi = si[0];
+    for (int w = 1; w < BLK / 64; ++w) {
+        const double v = sv[w];
+        const long i = si[w];
+        if (v < bv || (v == bv && i < bi)) { bv = v; bi = i; }
+    }
+    const long best = bi < P ? bi : 0;
+    double* mean = means + e * HA;
+    const T* row = actions + (e * P + best) * HA;
+    const double st = step[e];
+    for (int j = threadIdx.x; j < HA; j += blockDim.x) mean[j] = rs_blend(st, mean[j], (double)row[j]);
+    if (threadIdx.x == 0 && best_out) best_out[e] = best;
+    __syncthreads();
+    step_tail_body(mean, H, A, shift_mode, nullptr, actions_out ? actions_out + e * A : nullptr, nullptr,
+                   e == 0 ? step_counter : nullptr, nullptr, nullptr, 0.0);
 }
 
 inline int nblocks(long n, int b) { return (int)((n + b - 1) / b); }
@@ -2056,6 +2111,19 @@ hipError_t dmd_update_batch(int E, const T* costs, const T* actions, const doubl
     return hipGetLastError();
 }
 
+// (a thread per action channel in the tail: A <= BLK)
+bool rs_batch_supported(int E, long P, int H, int A) { return E >= 1 && E <= 65535 && P >= 1 && H >= 1 && A >= 1 && A <= BLK; }
+
+// One episode per grid row, each row what rs_best + rs_combine (one record) + step_tail do for its P particles: one launch.
+template <typename T>
+hipError_t rs_update_batch(int E, const double* q0, const T* actions, const double* step, int shift_mode, long P, int H, int A,
+                           double* means, double* actions_out, long long* step_counter, long long* best, hipStream_t s) {
+    if (!rs_batch_supported(E, P, H, A)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rs_update_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, q0, actions, step, P, H, A, shift_mode, means,
+                       actions_out, step_counter, best);
+    return hipGetLastError();
+}
+
 hipError_t cov_add_diag(double* cov, int A, const double* d, double scale, hipStream_t s) {
     if (A < 1 || A > 64) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cov_add_diag_kernel, dim3(1), dim3(64), 0, s, cov, A, d, scale);
@@ -2108,7 +2176,9 @@ hipError_t step_tail(double* mean, int H, int A, int mode, const double* row, do
                                                    int, int, double*, double*, long long*, double*, hipStream_t);    \
     template hipError_t dmd_update_batch<T>(int, const T*, const T*, const double*, const double*, const double*, int, \
                                             const double*, int, long, int, int, double*, double*, double*, long long*, \
-                                            double*, hipStream_t);
+                                            double*, hipStream_t);                                                   \
+    template hipError_t rs_update_batch<T>(int, const double*, const T*, const double*, int, long, int, int, double*, \
+                                           double*, long long*, long long*, hipStream_t);
 INST(float)
 INST(double)
 

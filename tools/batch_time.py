@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Episode batches (BatchedMPPI / BatchedCEM / BatchedPFMPC / BatchedDMDMPC): ms per batched control step and episode-steps/s, against the sequential loop.
+"""Episode batches (BatchedMPPI / BatchedCEM / BatchedPFMPC / BatchedDMDMPC / BatchedRandomShooting): ms per batched control step and episode-steps/s, against the sequential loop.
 
 For every model x E x P x H: one ``BatchedMPPI`` of E episodes of P particles (f64), timed with device events over
 --steps control steps after --warmup; in the same process the single-episode device path on its own engine (MPPI,
@@ -8,7 +8,7 @@ the same way.  The sequential loop of E episodes costs E times that per control 
 the same shape).  One JSON line per configuration, then a table.
 
     python tools/batch_time.py [--models half_cheetah,swimmer,sawyer] [--E 1,4,16,64] [--P 256,1024] [--H 16,32]
-        [--model-shards K] [--controller mppi|cem|pfmpc|dmd] [--repeats R]
+        [--model-shards K] [--controller mppi|cem|pfmpc|dmd|random_shooting] [--repeats R]
 
 --controller cem: ``BatchedCEM`` (full covariance, elite_frac 0.1, beta 0.45) against the single-episode fused CEM
 step (CEM, noise_mode='device', graph replay).  --repeats R: every configuration is timed R times, batch and single runs
@@ -22,6 +22,10 @@ table: the per-launch split of one batched step (device events around every laun
 --controller dmd: ``BatchedDMDMPC`` (full covariance, update_cov, beta 0.05) against the single-episode captured
 DMD-MPC loop (DMDMPC, update_cov=True, noise_mode='device', graph replay: the general step of about ten launches), with the
 per-launch split of one batched step as for pfmpc.
+
+--controller random_shooting: ``BatchedRandomShooting`` (step_size 1.0, the model's init_cov) against the
+single-episode captured random-shooting loop (RandomShooting, noise_mode='device', graph replay: draw, fused rollout, argmin,
+record, combine, tail, env step), with the per-launch split of one batched step as for pfmpc.
 
 --model-shards K: the batch rolls out K randomized model shards per episode (a set per episode, body masses
 +- 20 %) and the single-episode path is the sequential dynamics-randomized loop - a K-shard engine with randomized blocks
@@ -57,10 +61,12 @@ DMD_BETA = 0.05                     # (--controller dmd)
 # (mjmpc_sample_noise_cov_batch is the draw and the filter launch, mjmpc_dmd_update_batch the three update launches)
 DMD_LAUNCHES = ("mjmpc_cholesky_lower_batch", "mjmpc_sample_noise_cov_batch", "mjmpc_tree_rollout_fused_batch",
                 "mjmpc_dmd_update_batch", "mjmpc_tree_step_shard_states")
+RS_LAUNCHES = ("mjmpc_sample_noise_batch", "mjmpc_tree_rollout_fused_batch", "mjmpc_rs_update_batch",
+               "mjmpc_tree_step_shard_states")      # (--controller random_shooting)
 
 
 def make_batch(raw, E, P, H, lam, cov, controller):
-    from mjmpc_amd.control import BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedPFMPC
+    from mjmpc_amd.control import BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedPFMPC, BatchedRandomShooting
     seeds = [123 + i * 12345 for i in range(E)]
     if controller == "cem":
         return BatchedCEM(raw, E, H, P, cov, ELITE_FRAC, 1.0, BETA, 1.0, FILT, "null", seeds)
@@ -68,6 +74,8 @@ def make_batch(raw, E, P, H, lam, cov, controller):
         return BatchedPFMPC(raw, E, H, P, COV_SHIFT, cov, PF_LAM, PF_GAMMA, FILT, "null", seeds)
     if controller == "dmd":
         return BatchedDMDMPC(raw, E, H, P, lam, 1.0, cov, DMD_BETA, 1.0, FILT, "null", seeds, cov_type="full")
+    if controller == "random_shooting":
+        return BatchedRandomShooting(raw, E, H, P, 1.0, cov, 1.0, FILT, "null", seeds)
     return BatchedMPPI(raw, E, H, P, lam, 1.0, cov, 1.0, FILT, "null", seeds)
 
 
@@ -94,7 +102,7 @@ class _TimedLib:
 
 
 def launch_split(raw, E, P, H, lam, cov, steps, warmup, controller="pfmpc"):
-    """ms per library call of one batched PFMPC / DMD-MPC step (mean over ``steps`` steps)."""
+    """ms per library call of one batched PFMPC / DMD-MPC / random-shooting step (mean over ``steps`` steps)."""
     import torch
     names = LAUNCHES[controller]
     b = make_batch(raw, E, P, H, lam, cov, controller)
@@ -110,7 +118,7 @@ def launch_split(raw, E, P, H, lam, cov, steps, warmup, controller="pfmpc"):
     return {n: sum(s.elapsed_time(e) for s, e in timed.events[n]) / steps for n in names}
 
 
-LAUNCHES = {"pfmpc": PF_LAUNCHES, "dmd": DMD_LAUNCHES}
+LAUNCHES = {"pfmpc": PF_LAUNCHES, "dmd": DMD_LAUNCHES, "random_shooting": RS_LAUNCHES}
 
 
 def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
@@ -133,7 +141,7 @@ def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
 
 def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     import torch
-    from mjmpc_amd.control import CEM, DMDMPC, MPPI, PFMPC
+    from mjmpc_amd.control import CEM, DMDMPC, MPPI, PFMPC, RandomShooting
     from mjmpc_amd.control.controller import resident_state
     from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
     from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
@@ -156,6 +164,10 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
                    base_action="null", lam=lam, num_particles=P, step_size=1.0, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
                    action_highs=eng.action_highs, update_cov=True, cov_type="full", filter_coeffs=FILT, seed=123,
                    noise_mode="device", noise_dtype="f64")
+    elif controller == "random_shooting":
+        c = RandomShooting(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov,
+                           base_action="null", num_particles=P, step_size=1.0, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
+                           action_highs=eng.action_highs, filter_coeffs=FILT, seed=123, noise_mode="device", noise_dtype="f64")
     else:
         c = MPPI(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, init_cov=cov, base_action="null",
                  lam=lam, num_particles=P, step_size=1.0, alpha=1, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
@@ -180,6 +192,8 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
         raise SystemExit("the single-episode CEM path did not take its fused step at %d x %d" % (P, H))
     if controller == "dmd" and (c._fused_capable() or not c._device_cov()):
         raise SystemExit("the single-episode DMD-MPC path did not take its covariance-adapting step")
+    if controller == "random_shooting" and not (c._wants_q0() and hasattr(c._rollout_fn, "fused")):
+        raise SystemExit("the single-episode random-shooting path did not take its q0-from-rollout step")
     eng.close()
     return s.elapsed_time(e) / steps
 
@@ -193,7 +207,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--model-shards", type=int, default=0, help="randomized model shards per episode (0: no randomization)")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd"])
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting"])
     ap.add_argument("--repeats", type=int, default=1, help="timings per configuration, batch and single runs alternating")
     args = ap.parse_args()
     from mjmpc_amd import _lib
