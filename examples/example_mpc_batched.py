@@ -45,6 +45,18 @@ from mjmpc_amd.envs.tree_engine import TreeRolloutEngine            # noqa: E402
 from mjmpc_amd.models.reacher7dof import reacher7dof_raw            # noqa: E402
 
 
+# controller block -> the batch class, the block's settings it takes between num_particles and gamma, and the optional ones
+# with the values they take where the block has none
+BATCHES = {
+    "mppi": (BatchedMPPI, ("lam", "step_size", "init_cov"), dict(alpha=1, time_based_weights=False)),
+    "cem": (BatchedCEM, ("init_cov", "elite_frac", "step_size", "beta"), dict(cov_type="diagonal", sample_mode="mean")),
+    "pfmpc": (BatchedPFMPC, ("cov_shift", "cov_resample", "lam"), dict(sample_mode="mean")),
+    "dmd": (BatchedDMDMPC, ("lam", "step_size", "init_cov", "beta"), dict(cov_type="diagonal", sample_mode="mean")),
+    "dmd_static": (BatchedMPPI, ("lam", "step_size", "init_cov"), dict()),
+    "random_shooting": (BatchedRandomShooting, ("step_size", "init_cov"), dict(sample_mode="mean")),
+}
+
+
 def main():
     ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM, PFMPC, DMD-MPC or random-shooting episodes as one batch")
     ap.add_argument("--config", required=True, help="yaml file with experiment parameters")
@@ -88,34 +100,14 @@ def main():
     env.engine.close()
 
     base_action = params.get("base_action", exp.get("base_action", "null"))
-    if args.controller == "cem":
-        batch = BatchedCEM(raw, E, params["horizon"], params["num_particles"], params["init_cov"], params["elite_frac"],
-                           params["step_size"], params.get("beta", 0.0), params["gamma"], params["filter_coeffs"], base_action,
-                           seeds, cov_type=params.get("cov_type", "diagonal"), dtype=args.dtype,
-                           n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
-    elif args.controller == "pfmpc":
-        batch = BatchedPFMPC(raw, E, params["horizon"], params["num_particles"], params["cov_shift"], params["cov_resample"],
-                             params["lam"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
-                             n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
-    elif args.controller == "dmd" and params.get("update_cov", False):
-        batch = BatchedDMDMPC(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
-                              params["init_cov"], params.get("beta", 0.0), params["gamma"], params["filter_coeffs"], base_action,
-                              seeds, cov_type=params.get("cov_type", "diagonal"), dtype=args.dtype,
-                              n_iters=params.get("n_iters", 1), sample_mode=params.get("sample_mode", "mean"))
-    elif args.controller == "random_shooting":
-        batch = BatchedRandomShooting(raw, E, params["horizon"], params["num_particles"], params["step_size"],
-                                      params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds,
-                                      dtype=args.dtype, n_iters=params.get("n_iters", 1),
-                                      sample_mode=params.get("sample_mode", "mean"))
-    elif args.controller == "dmd":      # (without covariance adaptation DMD-MPC is MPPI with alpha = 1: gaussian_dmd.py:65-104)
-        batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
-                            params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
-                            n_iters=params.get("n_iters", 1))     # (the static covariance is diag(init_cov) for any cov_type)
-    else:
-        batch = BatchedMPPI(raw, E, params["horizon"], params["num_particles"], params["lam"], params["step_size"],
-                            params["init_cov"], params["gamma"], params["filter_coeffs"], base_action, seeds, dtype=args.dtype,
-                            n_iters=params.get("n_iters", 1), alpha=params.get("alpha", 1),
-                            time_based_weights=params.get("time_based_weights", False))
+    # (without covariance adaptation DMD-MPC is MPPI with alpha = 1, gaussian_dmd.py:65-104, and its static covariance is
+    # diag(init_cov) for any cov_type)
+    name = "dmd_static" if args.controller == "dmd" and not params.get("update_cov", False) else args.controller
+    cls, names, optional = BATCHES[name]
+    params.setdefault("beta", 0.0)
+    batch = cls(raw, E, params["horizon"], params["num_particles"], *[params[n] for n in names], params["gamma"],
+                params["filter_coeffs"], base_action, seeds, dtype=args.dtype, n_iters=params.get("n_iters", 1),
+                **{k: params.get(k, default) for k, default in optional.items()})
     if args.controller == "dmd":
         print("the dmd block (update_cov: %s) runs as %s" % (bool(params.get("update_cov", False)), type(batch).__name__))
     if args.dyn_randomize_config:

@@ -32,8 +32,8 @@ and ``beta``, and a ``'diagonal'`` or ``'full'`` covariance that is re-estimated
 ``beta I`` and factored on the device every step (``update_cov=False`` is ``BatchedMPPI``'s arithmetic).
 ``BatchedRandomShooting`` is the batch of random shooting (random_shooting.py): per episode ``step_size`` and
 ``init_cov``, and a mean that moves towards the best sample of the step.  The classes share
-``_EpisodeBatch``: the engine, the state shards, the buffers, the rollout launch, the env step, ``run`` and dynamics
-randomization.
+``_EpisodeBatch``: the engine, the state shards, the buffers, the rollout launch, the env step, ``run``, dynamics
+randomization, the step frame, the bound checks and the covariance status.
 """
 import ctypes
 
@@ -48,22 +48,32 @@ def _vp(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def _per_episode(name, value, E, shape=()):
-    """One value for every episode, or one per episode -> float64 [E, *shape]."""
+def _per_episode(name, value, E, shape=(), sign=None):
+    """One value for every episode, or one per episode -> float64 [E, *shape].  ``sign``: ``'positive'`` or ``'not negative'``,
+    what every value must be (a NaN is neither)."""
     a = np.asarray(value, np.float64)
-    if a.shape == tuple(shape):
-        return np.broadcast_to(a, (E,) + tuple(shape)).copy()
-    if a.shape == (E,) + tuple(shape):
-        return a.copy()
-    raise ValueError("%s takes one value of shape %s for every episode or %d of them, shape %s; got shape %s"
-                     % (name, tuple(shape), E, (E,) + tuple(shape), a.shape))
+    if a.shape != tuple(shape) and a.shape != (E,) + tuple(shape):
+        raise ValueError("%s takes one value of shape %s for every episode or %d of them, shape %s; got shape %s"
+                         % (name, tuple(shape), E, (E,) + tuple(shape), a.shape))
+    if sign is not None and not np.all(a > 0 if sign == "positive" else a >= 0):
+        raise ValueError("%s must %s" % (name, "be positive" if sign == "positive" else "not be negative"))
+    return np.broadcast_to(a, (E,) + tuple(shape)).copy()
+
+
+def _cov(self):
+    """The E action covariances, ``(E, A, A)`` (synchronises)."""
+    out = self._covs.cpu().numpy().copy()
+    self._check_status()
+    return out
 
 
 class _EpisodeBatch:
     """What the episode batches share: the checks of the common settings, the engine whose state shards are the E real envs,
     the device buffers of the rollout launch, the env step, ``run`` and dynamics randomization.  A subclass checks its own
     settings, calls ``_check_common`` and ``_compile`` (both raise ``ValueError`` and touch no device), then ``_setup``,
-    and provides ``step``."""
+    and provides ``_launches``, its own launches of a ``step``."""
+
+    _status = None      # int32 [E] on the device in the batches whose kernels can flag an episode's covariance
 
     @staticmethod
     def _check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq, sample_mode, dtype,
@@ -111,6 +121,23 @@ class _EpisodeBatch:
             raise ValueError("the tree engine runs RK4 models of up to 16 dofs without elliptic friction cones")
         return model
 
+    def _seeds_and_model(self, seeds, E, raw_model):
+        """The last two refusals of every constructor: ``seed_vals`` and the compiled model."""
+        self.seed_vals = self._check_seeds(seeds, E)
+        return self._compile(raw_model)
+
+    @staticmethod
+    def _init_mean(init_mean, E, H, A):
+        return np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
+
+    @staticmethod
+    def _diag_factors(var, A):
+        """``diag(var_e)`` per episode, as the controllers take a scalar covariance, and what the sampler colours with
+        (``noise_factor``) -> the covariances [E, A, A], their lower factors [E, A, A] and the factors' diagonal flags."""
+        covs = np.stack([np.diag(np.full(A, c)) for c in var])
+        factors = [noise_factor(c) for c in covs]
+        return covs, np.stack([f[0] for f in factors]), [f[1] for f in factors]
+
     def _setup(self, raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean):
         """The engine (its state shards are the E real envs) and the device buffers every batch has."""
         from ..envs.tree_engine import TreeRolloutEngine
@@ -133,10 +160,10 @@ class _EpisodeBatch:
         self._code = _lib.F32 if dtype == "f32" else _lib.F64
         tdt = self._tdtype = torch.float32 if dtype == "f32" else torch.float64
         f64 = dict(dtype=torch.float64, device=dev)
-        self._means = torch.from_numpy(init_mean.copy()).to(dev)
-        self._gseq = torch.from_numpy(np.cumprod([1.0] + [self.gamma] * (H - 1))).to(dev)     # (Controller.gamma_seq)
-        self._coeffs = torch.from_numpy(fc.copy()).to(dev)
-        self._seeds = torch.from_numpy(np.array(self.seed_vals, np.uint64).view(np.int64)).to(dev)
+        self._means = self._upload(init_mean)
+        self._gseq = self._upload(np.cumprod([1.0] + [self.gamma] * (H - 1)))     # (Controller.gamma_seq)
+        self._coeffs = self._upload(fc)
+        self._seeds = self._upload(np.array(self.seed_vals, np.uint64).view(np.int64))
         self._step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         self._noise = torch.empty((E, P, H, A), dtype=tdt, device=dev)
         self._costs = torch.empty((E * P, H), dtype=tdt, device=dev)
@@ -145,8 +172,23 @@ class _EpisodeBatch:
         self._act = torch.empty((E, A), **f64)
         self._env_cost = torch.empty(E, dtype=tdt, device=dev)
         self._env_obs = torch.empty((E, self.d_obs), dtype=tdt, device=dev)
-        self._targets = [model.target_default.copy() for _ in range(E)]
+        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
         return f64
+
+    def _upload(self, a):
+        """A host array on the batch's device (a copy: the host array stays the caller's)."""
+        return self.torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+    def _workspace(self, nbytes):
+        """``nbytes`` of device workspace, as a library ``*_workspace_bytes`` call sized it (negative: that call's error)."""
+        if nbytes < 0:
+            _lib.check(int(nbytes))
+        return self.torch.empty((nbytes + 7) // 8, dtype=self.torch.float64, device=self.device)
+
+    def _coeffs_unless_identity(self):
+        """The filter coefficients on the device, or None where the filter leaves the samples as they are."""
+        fc = self.filter_coeffs
+        return None if fc[0] == 1.0 and fc[1] == 0.0 and fc[2] == 0.0 else self._coeffs
 
     # ------------------------------------------------------------------ state of the E real envs
     @property
@@ -234,14 +276,35 @@ class _EpisodeBatch:
 
     # ------------------------------------------------------------------ control steps
     def step(self, _out=None):
+        """Enqueue one control step of every episode - the subclass's ``_launches``, then the real-env step - without a host
+        synchronisation.  The actions, real-env costs and next observations stay on the device."""
+        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
+        s = self._stream()
+        self._launches(act, s)
+        self._env_step(act, cost, nobs, s)
+        self.num_steps += 1
+        return act, cost, nobs
+
+    def _launches(self, act, s):
+        """The controller's own launches of one step on stream ``s``, up to the E actions in ``act``.  Every one is looked up
+        on ``self.lib`` when it is made."""
         raise NotImplementedError
 
-    def _rollout(self, s):
-        """The batch's rollout launch: grid row = episode, the cost-to-go of every particle into ``_q0``."""
+    def _rollout(self, s, noise=None, filtered=True, gseq=True, q0=True):
+        """The batch's rollout launch: grid row = episode, the cost-to-go of every particle into ``_q0``.  ``noise``: the
+        deviations from the means, ``_noise`` by default; ``filtered=False``: they are filtered already; ``gseq=False`` /
+        ``q0=False``: no discount sequence / no cost-to-go (the update forms its own)."""
         E, P, H = self.num_episodes, self.num_particles, self.horizon
-        _lib.check(self.lib.mjmpc_tree_rollout_fused_batch(self.engine._h, self._code, E * P, H, _vp(self._means), _vp(self._noise),
-                                                           _vp(self._coeffs), _vp(self._gseq), _vp(self._costs),
-                                                           _vp(self._actions), _vp(self._q0), s))
+        _lib.check(self.lib.mjmpc_tree_rollout_fused_batch(
+            self.engine._h, self._code, E * P, H, _vp(self._means), _vp(self._noise if noise is None else noise),
+            _vp(self._coeffs) if filtered else None, _vp(self._gseq) if gseq else None, _vp(self._costs), _vp(self._actions),
+            _vp(self._q0) if q0 else None, s))
+
+    def _draw(self, s):
+        """The batched Philox draw with the static factors ``_chols``, keyed with the step count: ``_noise``."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        _lib.check(self.lib.mjmpc_sample_noise_batch(self._code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds),
+                                                     0, _vp(self._step_dev), s))
 
     def _env_step(self, act, cost, nobs, s):
         """The E real envs take their episode's action in one launch."""
@@ -276,7 +339,19 @@ class _EpisodeBatch:
             self.engine.check_env_resets("an episode batch's real envs (step_shard_states)")
 
     def _check_status(self):
-        pass                    # (batches whose kernels can flag an episode override this: BatchedCEM)
+        """``DeviceUpdater.check_status`` per episode: raise for the episodes whose finish launch (``BatchedCEM``) or factor
+        launch (``BatchedDMDMPC``) has flagged an indefinite or non-finite covariance (the flags are sticky on the device) and
+        clear exactly the flags reported.  Nothing to check in a batch without ``_status``."""
+        if self._status is None:
+            return
+        st = self._status.cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if bad.size == 0:
+            return
+        self._status[self.torch.from_numpy(bad).to(self.device)] = 0
+        raise _lib.MjmpcError("the action covariance of episode%s %s on the device is indefinite or not finite: its Cholesky "
+                              "factor (sampler colouring) does not exist"
+                              % ("" if bad.size == 1 else "s", ", ".join(str(int(e)) for e in bad)))
 
     def _stream(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -303,47 +378,29 @@ class BatchedMPPI(_EpisodeBatch):
             raise ValueError("an episode batch samples with a diagonal covariance (cov_type 'diagonal'), got %r" % (cov_type,))
         E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
                                          sample_mode, dtype, gamma, filter_coeffs, "MPPI")
-        lam = _per_episode("lam", lam, E)
+        lam = _per_episode("lam", lam, E, sign="positive")
         step_size = _per_episode("step_size", step_size, E)
-        init_cov = _per_episode("init_cov", init_cov, E)
-        if not np.all(lam > 0):
-            raise ValueError("lam must be positive")
-        if not np.all(init_cov > 0):
-            raise ValueError("init_cov must be positive")
-        self.seed_vals = self._check_seeds(seeds, E)
-        model = self._compile(raw_model)
+        init_cov = _per_episode("init_cov", init_cov, E, sign="positive")
+        model = self._seeds_and_model(seeds, E, raw_model)
         A = model.nu
-        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
-        factors = [noise_factor(np.diag(np.array([c] * A))) for c in init_cov]      # (OLGaussianMPC: diag(init_cov))
+        init_mean = self._init_mean(init_mean, E, H, A)
+        chols = self._diag_factors(init_cov, A)[1]                                  # (OLGaussianMPC: diag(init_cov))
 
         # -- the engine (its state shards are the E real envs) and the batch's device buffers
-        f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
-        torch, dev = self.torch, self.device
+        self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
         self.lam, self.step_size, self.init_cov = lam, step_size, init_cov
-        self._chols = torch.from_numpy(np.stack([f[0] for f in factors])).to(dev)
-        self._lam = torch.from_numpy(lam.copy()).to(dev)
-        self._step = torch.from_numpy(step_size.copy()).to(dev)
-        nbytes = self.lib.mjmpc_update_batch_workspace_bytes(E, P, H, A)
-        if nbytes < 0:
-            _lib.check(int(nbytes))
-        self._ws = torch.empty((nbytes + 7) // 8, **f64)
-        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+        self._chols, self._lam, self._step = self._upload(chols), self._upload(lam), self._upload(step_size)
+        self._ws = self._workspace(self.lib.mjmpc_update_batch_workspace_bytes(E, P, H, A))
 
-    def step(self, _out=None):
+    def _launches(self, act, s):
         """Enqueue one control step of every episode (sampling, rollouts, update, action, shift, real-env step) without a
         host synchronisation.  The actions, real-env costs and next observations stay on the device."""
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
-        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
-        lib, code, s = self.lib, self._code, self._stream()
-        _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
-                                                _vp(self._step_dev), s))
+        self._draw(s)
         self._rollout(s)
-        _lib.check(lib.mjmpc_mppi_fused_update_batch(code, E, P, H, A, _vp(self._q0), _vp(self._actions), _vp(self._lam),
-                                                     _vp(self._step), _SHIFT_MODES[self.base_action], _vp(self._means),
-                                                     _vp(act), _vp(self._step_dev), _vp(self._ws), s))
-        self._env_step(act, cost, nobs, s)
-        self.num_steps += 1
-        return act, cost, nobs
+        _lib.check(self.lib.mjmpc_mppi_fused_update_batch(self._code, E, P, H, A, _vp(self._q0), _vp(self._actions),
+                                                          _vp(self._lam), _vp(self._step), _SHIFT_MODES[self.base_action],
+                                                          _vp(self._means), _vp(act), _vp(self._step_dev), _vp(self._ws), s))
 
 
 def _cem_limits():
@@ -373,18 +430,15 @@ class BatchedCEM(_EpisodeBatch):
             raise ValueError("cov_type must be 'diagonal' or 'full' in a CEM episode batch, got %r" % (cov_type,))
         E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
                                          sample_mode, dtype, gamma, filter_coeffs, "CEM")
-        init_cov = _per_episode("init_cov", init_cov, E)
+        init_cov = _per_episode("init_cov", init_cov, E, sign="positive")
         elite_frac = _per_episode("elite_frac", elite_frac, E)
         step_size = _per_episode("step_size", step_size, E)
         beta = _per_episode("beta", beta, E)
-        if not np.all(init_cov > 0):
-            raise ValueError("init_cov must be positive")
         num_elite = np.array([int(P * f) for f in elite_frac], np.int64)          # (cem.py:18)
         if np.any(num_elite < 1) or np.any(num_elite > P):
             raise ValueError("every episode needs 1 <= num_elite = int(num_particles * elite_frac) <= num_particles, got %s"
                              % (num_elite.tolist(),))
-        self.seed_vals = self._check_seeds(seeds, E)
-        model = self._compile(raw_model)
+        model = self._seeds_and_model(seeds, E, raw_model)
         A = model.nu
         lib = _lib.load()
         if not lib.mjmpc_cem_batch_supported(E, P, int(num_elite.max()), H, A):
@@ -393,33 +447,20 @@ class BatchedCEM(_EpisodeBatch):
         init_mean = np.zeros((E, H, A))                                            # (CEM starts from a zero mean)
 
         # -- the engine (its state shards are the E real envs) and the batch's device buffers
-        f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
-        torch, dev = self.torch, self.device
+        self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
         self.init_cov, self.elite_frac, self.step_size, self.beta = init_cov, elite_frac, step_size, beta
         self.num_elite, self.cov_type = num_elite, cov_type
         # the first factor is the diagonal sqrt(init_cov): what the single path's first draw colours its samples with
-        self._init_covs = np.stack([np.diag(np.array([c] * A)) for c in init_cov])
-        self._init_chols = np.stack([noise_factor(c)[0] for c in self._init_covs])
-        self._covs = torch.from_numpy(self._init_covs.copy()).to(dev)
-        self._chols = torch.from_numpy(self._init_chols.copy()).to(dev)
-        self._k = torch.from_numpy(num_elite.copy()).to(dev)
-        self._step = torch.from_numpy(step_size.copy()).to(dev)
-        self._grow_diag = torch.from_numpy(np.repeat(init_cov[:, None], A, axis=1).copy()).to(dev)     # (cem.py:94)
-        self._grow_scale = torch.from_numpy(beta.copy()).to(dev)
-        self._status = torch.zeros(E, dtype=torch.int32, device=dev)
-        nbytes = self.lib.mjmpc_cem_batch_workspace_bytes(E, P, int(num_elite.max()), H, A)
-        if nbytes < 0:
-            _lib.check(int(nbytes))
-        self._ws = torch.empty((nbytes + 7) // 8, **f64)
+        self._init_covs, self._init_chols, _ = self._diag_factors(init_cov, A)
+        self._covs, self._chols = self._upload(self._init_covs), self._upload(self._init_chols)
+        self._k, self._step = self._upload(num_elite), self._upload(step_size)
+        self._grow_diag = self._upload(np.repeat(init_cov[:, None], A, axis=1))     # (cem.py:94)
+        self._grow_scale = self._upload(beta)
+        self._status = self.torch.zeros(E, dtype=self.torch.int32, device=self.device)
+        self._ws = self._workspace(self.lib.mjmpc_cem_batch_workspace_bytes(E, P, int(num_elite.max()), H, A))
         self._noise_valid = False       # step 0 (and the step after reset) draws its own samples; later ones are drawn ahead
-        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
 
-    @property
-    def cov(self):
-        """The E action covariances, ``(E, A, A)`` (synchronises)."""
-        out = self._covs.cpu().numpy().copy()
-        self._check_status()
-        return out
+    cov = property(_cov)
 
     def reset(self):
         """Every episode back to its initial mean, covariance and factor and to step 0 (the real envs keep their states)."""
@@ -428,18 +469,16 @@ class BatchedCEM(_EpisodeBatch):
         self._chols.copy_(self.torch.from_numpy(self._init_chols))
         self._noise_valid = False
 
-    def step(self, _out=None):
+    def _launches(self, act, s):
         """Enqueue one control step of every episode (rollouts, selection + moments, refit + action + shift + the next step's
         samples, real-env step) without a host synchronisation; step 0 draws its samples first.  The actions, real-env costs
         and next observations stay on the device."""
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
-        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
-        lib, code, s = self.lib, self._code, self._stream()
+        lib, code = self.lib, self._code
         if not self._noise_valid:
             # (the factors are diagonal here - diag(sqrt(init_cov)) -, for which the diagonal draw and the general one of the
             # single path's first step form the same 0 + l z per sample: DESIGN 10.2)
-            _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
-                                                    _vp(self._step_dev), s))
+            self._draw(s)
             self._noise_valid = True
         self._rollout(s)
         _lib.check(lib.mjmpc_cem_select_moments_batch(code, E, P, H, A, _vp(self._actions), _vp(self._q0), _vp(self._k),
@@ -449,21 +488,6 @@ class BatchedCEM(_EpisodeBatch):
                                               _vp(self._chols), _vp(self._status), _vp(self._grow_diag), _vp(self._grow_scale),
                                               _vp(act), _vp(self._step_dev), _vp(self._noise), _vp(self._seeds), 0,
                                               _vp(self._ws), s))
-        self._env_step(act, cost, nobs, s)
-        self.num_steps += 1
-        return act, cost, nobs
-
-    def _check_status(self):
-        """``DeviceUpdater.check_status`` per episode: raise for the episodes whose finish launch has flagged an indefinite or
-        non-finite covariance (the flags are sticky on the device) and clear exactly the flags reported."""
-        st = self._status.cpu().numpy()
-        bad = np.nonzero(st)[0]
-        if bad.size == 0:
-            return
-        self._status[self.torch.from_numpy(bad).to(self.device)] = 0
-        raise _lib.MjmpcError("the action covariance of episode%s %s on the device is indefinite or not finite: its Cholesky "
-                              "factor (sampler colouring) does not exist"
-                              % ("" if bad.size == 1 else "s", ", ".join(str(int(e)) for e in bad)))
 
 
 class BatchedDMDMPC(_EpisodeBatch):
@@ -496,88 +520,53 @@ class BatchedDMDMPC(_EpisodeBatch):
             raise ValueError("cov_type must be 'diagonal' or 'full' in a DMD-MPC episode batch, got %r" % (cov_type,))
         E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
                                          sample_mode, dtype, gamma, filter_coeffs, "DMD-MPC")
-        lam = _per_episode("lam", lam, E)
+        lam = _per_episode("lam", lam, E, sign="positive")
         step_size = _per_episode("step_size", step_size, E)
-        init_cov = _per_episode("init_cov", init_cov, E)
-        beta = _per_episode("beta", beta, E)
-        if not np.all(lam > 0):
-            raise ValueError("lam must be positive")
-        if not np.all(init_cov > 0):
-            raise ValueError("init_cov must be positive")
-        if not np.all(beta >= 0):
-            raise ValueError("beta must not be negative")
-        self.seed_vals = self._check_seeds(seeds, E)
-        model = self._compile(raw_model)
+        init_cov = _per_episode("init_cov", init_cov, E, sign="positive")
+        beta = _per_episode("beta", beta, E, sign="not negative")
+        model = self._seeds_and_model(seeds, E, raw_model)
         A = model.nu
         if A > 64:
             raise ValueError("a DMD-MPC episode batch factors covariances of up to 64 action channels, got %d" % A)
-        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
-        lib = _lib.load()
-        nbytes = lib.mjmpc_dmd_batch_workspace_bytes(E, P, H, A)
+        init_mean = self._init_mean(init_mean, E, H, A)
+        nbytes = _lib.load().mjmpc_dmd_batch_workspace_bytes(E, P, H, A)
         if nbytes <= 0:
             raise ValueError("no DMD-MPC batch workspace for E = %d, P = %d, H = %d, A = %d" % (E, P, H, A))
 
         # -- the engine (its state shards are the E real envs) and the batch's device buffers
         f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
-        torch, dev = self.torch, self.device
         self.lam, self.step_size, self.init_cov, self.beta, self.cov_type = lam, step_size, init_cov, beta, cov_type
-        self._init_covs = np.stack([np.diag(np.array([c] * A)) for c in init_cov])      # (OLGaussianMPC: diag(init_cov))
-        self._covs = torch.from_numpy(self._init_covs.copy()).to(dev)
-        self._chols = torch.zeros((E, A, A), **f64)
-        self._lam = torch.from_numpy(lam.copy()).to(dev)
-        self._step = torch.from_numpy(step_size.copy()).to(dev)
-        self._beta = torch.from_numpy(beta.copy()).to(dev)
-        self._status = torch.zeros(E, dtype=torch.int32, device=dev)
-        identity = fc[0] == 1.0 and fc[1] == 0.0 and fc[2] == 0.0
-        self._draw_coeffs = None if identity else self._coeffs      # (the filter pass leaves an identity's samples as they are)
-        self._ws = torch.empty((nbytes + 7) // 8, **f64)
-        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+        self._init_covs = self._diag_factors(init_cov, A)[0]                        # (OLGaussianMPC: diag(init_cov))
+        self._covs = self._upload(self._init_covs)
+        self._chols = self.torch.zeros((E, A, A), **f64)
+        self._lam, self._step, self._beta = self._upload(lam), self._upload(step_size), self._upload(beta)
+        self._status = self.torch.zeros(E, dtype=self.torch.int32, device=self.device)
+        self._draw_coeffs = self._coeffs_unless_identity()      # (the filter pass leaves an identity's samples as they are)
+        self._ws = self._workspace(nbytes)
 
-    @property
-    def cov(self):
-        """The E action covariances, ``(E, A, A)`` (synchronises)."""
-        out = self._covs.cpu().numpy().copy()
-        self._check_status()
-        return out
+    cov = property(_cov)
 
     def reset(self):
         """Every episode back to its initial mean and covariance and to step 0 (the real envs keep their states)."""
         super().reset()
         self._covs.copy_(self.torch.from_numpy(self._init_covs))
 
-    def step(self, _out=None):
+    def _launches(self, act, s):
         """Enqueue one control step of every episode (factors, draw + filter, rollouts, weights, partial moments, update +
         action + shift + covariance growth, real-env step) without a host synchronisation.  The actions, real-env costs and
         next observations stay on the device."""
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
-        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
-        lib, code, s = self.lib, self._code, self._stream()
+        lib, code = self.lib, self._code
         _lib.check(lib.mjmpc_cholesky_lower_batch(E, _vp(self._covs), A, _vp(self._chols), _vp(self._status), s))
         _lib.check(lib.mjmpc_sample_noise_cov_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._draw_coeffs),
                                                     _vp(self._seeds), 0, _vp(self._step_dev),
                                                     int(self.cov_type == "diagonal"), s))
         # (the samples are filtered already and the update forms its own cost-to-go: the single path's plain rollout)
-        _lib.check(lib.mjmpc_tree_rollout_fused_batch(self.engine._h, code, E * P, H, _vp(self._means), _vp(self._noise), None,
-                                                      None, _vp(self._costs), _vp(self._actions), None, s))
+        self._rollout(s, filtered=False, gseq=False, q0=False)
         _lib.check(lib.mjmpc_dmd_update_batch(code, E, P, H, A, _vp(self._costs), _vp(self._actions), _vp(self._gseq),
                                               _vp(self._lam), _vp(self._step), 2 if self.cov_type == "full" else 1,
                                               _vp(self._beta), _SHIFT_MODES[self.base_action], _vp(self._means),
                                               _vp(self._covs), _vp(act), _vp(self._step_dev), _vp(self._ws), s))
-        self._env_step(act, cost, nobs, s)
-        self.num_steps += 1
-        return act, cost, nobs
-
-    def _check_status(self):
-        """``DeviceUpdater.check_status`` per episode: raise for the episodes whose factor launch has flagged an indefinite or
-        non-finite covariance (the flags are sticky on the device) and clear exactly the flags reported."""
-        st = self._status.cpu().numpy()
-        bad = np.nonzero(st)[0]
-        if bad.size == 0:
-            return
-        self._status[self.torch.from_numpy(bad).to(self.device)] = 0
-        raise _lib.MjmpcError("the action covariance of episode%s %s on the device is indefinite or not finite: its Cholesky "
-                              "factor (sampler colouring) does not exist"
-                              % ("" if bad.size == 1 else "s", ", ".join(str(int(e)) for e in bad)))
 
 
 class BatchedPFMPC(_EpisodeBatch):
@@ -601,44 +590,34 @@ class BatchedPFMPC(_EpisodeBatch):
                                          gamma, filter_coeffs, "PFMPC")
         if base_action == "repeat" and H < 2:
             raise ValueError("base_action 'repeat' needs a horizon of at least 2")
-        lam = _per_episode("lam", lam, E)
-        cov_shift = _per_episode("cov_shift", cov_shift, E)
-        cov_resample = _per_episode("cov_resample", cov_resample, E)
-        if not np.all(lam > 0):
-            raise ValueError("lam must be positive")
-        if not np.all(cov_shift >= 0):
-            raise ValueError("cov_shift must not be negative")
-        if not np.all(cov_resample > 0):
-            raise ValueError("cov_resample must be positive")
-        self.seed_vals = self._check_seeds(seeds, E)
-        model = self._compile(raw_model)
+        lam = _per_episode("lam", lam, E, sign="positive")
+        cov_shift = _per_episode("cov_shift", cov_shift, E, sign="not negative")
+        cov_resample = _per_episode("cov_resample", cov_resample, E, sign="positive")
+        model = self._seeds_and_model(seeds, E, raw_model)
         A = model.nu
-        lib = _lib.load()
-        nbytes = lib.mjmpc_pf_batch_workspace_bytes(E, P, H, A)
+        nbytes = _lib.load().mjmpc_pf_batch_workspace_bytes(E, P, H, A)
         if nbytes <= 0:
             raise ValueError("no particle-filter workspace for E = %d, P = %d, H = %d, A = %d" % (E, P, H, A))
         # the first sets' factors (DeviceUpdater.prepare_noise: the Cholesky factor of cov_resample I and its diagonal flag)
-        factors = [noise_factor(np.diag(np.full(A, c))) for c in cov_resample]
+        _, init_chols, init_diag = self._diag_factors(cov_resample, A)
 
         # -- the engine (its state shards are the E real envs) and the batch's device buffers
         f64 = self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, np.zeros((E, H, A)))
-        torch, dev = self.torch, self.device
+        torch = self.torch
         self.lam, self.cov_shift, self.cov_resample, self.keep_stages = lam, cov_shift, cov_resample, bool(keep_stages)
         self._set, self._set_alt = (torch.empty((E, P, H, A), **f64) for _ in range(2))
         self._gathered = torch.empty((E, P, H, A), **f64) if self.keep_stages else None
         self._w, self._first = torch.empty((E, P), **f64), torch.zeros(E, **f64)
-        self._idx = torch.empty((E, P), dtype=torch.int32, device=dev)
-        self._lam = torch.from_numpy(lam.copy()).to(dev)
+        self._idx = torch.empty((E, P), dtype=torch.int32, device=self.device)
+        self._lam = self._upload(lam)
         # the jitters' factors: cov_shift is c I, its factor sqrt(c) I (a zero variance is a zero jitter, not an error)
-        self._chols = torch.from_numpy(np.stack([np.sqrt(np.diag(np.full(A, c))) for c in cov_shift])).to(dev)
-        self._init_chols = [(torch.from_numpy(np.ascontiguousarray(f[0])).to(dev), f[1]) for f in factors]
-        identity = fc[0] == 1.0 and fc[1] == 0.0 and fc[2] == 0.0
-        self._shift_coeffs = None if identity else self._coeffs           # (as the single path hands them to the gather)
-        self._ws = torch.empty((nbytes + 7) // 8, **f64)
+        self._chols = self._upload(np.stack([np.sqrt(np.diag(np.full(A, c))) for c in cov_shift]))
+        self._init_chols = [(self._upload(c), d) for c, d in zip(init_chols, init_diag)]
+        self._shift_coeffs = self._coeffs_unless_identity()               # (as the single path hands them to the gather)
+        self._ws = self._workspace(nbytes)
         self._delta = self._noise                                         # (the rollout launch's noise is set - mean)
         self._stepped = False
         self._draw_initial_sets()
-        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
 
     def _draw_initial_sets(self):
         """Row e <- the single path's first set: ``DeviceUpdater.sample_noise(P, cov_resample_e I, filter_coeffs, seed_e, 0,
@@ -664,13 +643,17 @@ class BatchedPFMPC(_EpisodeBatch):
     def step(self, _out=None):
         """Enqueue one control step of every episode (deviations, rollouts, weights, resampling, gather + shift, mean + action,
         real-env step) without a host synchronisation.  The actions, real-env costs and next observations stay on the device."""
+        out = super().step(_out)
+        self._set, self._set_alt = self._set_alt, self._set
+        self._stepped = True
+        return out
+
+    def _launches(self, act, s):
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
-        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
-        lib, code, s = self.lib, self._code, self._stream()
-        _lib.check(lib.mjmpc_pf_delta_batch(code, E, P, H, A, _vp(self._set), _vp(self._means), _vp(self._delta), s))
+        lib = self.lib
+        _lib.check(lib.mjmpc_pf_delta_batch(self._code, E, P, H, A, _vp(self._set), _vp(self._means), _vp(self._delta), s))
         # (the set is filtered already: the rollout takes the deviations as they are, as the single path's fused(.., None, ..))
-        _lib.check(lib.mjmpc_tree_rollout_fused_batch(self.engine._h, code, E * P, H, _vp(self._means), _vp(self._delta), None,
-                                                      _vp(self._gseq), _vp(self._costs), _vp(self._actions), _vp(self._q0), s))
+        self._rollout(s, noise=self._delta, filtered=False)
         _lib.check(lib.mjmpc_pf_weights_batch(E, P, _vp(self._q0), _vp(self._lam), _vp(self._seeds), 0, _vp(self._step_dev),
                                               _vp(self._w), _vp(self._first), s))
         _lib.check(lib.mjmpc_pf_resample_batch(E, P, _vp(self._w), _vp(self._first), _vp(self._idx), _vp(self._ws), s))
@@ -680,11 +663,6 @@ class BatchedPFMPC(_EpisodeBatch):
                                                    _vp(self._step_dev), _vp(self._set_alt), _vp(self._gathered), _vp(self._ws),
                                                    s))
         _lib.check(lib.mjmpc_pf_finish_batch(E, P, H, A, _vp(self._ws), _vp(self._means), _vp(act), _vp(self._step_dev), s))
-        self._env_step(act, cost, nobs, s)
-        self._set, self._set_alt = self._set_alt, self._set
-        self.num_steps += 1
-        self._stepped = True
-        return act, cost, nobs
 
     def last_step(self):
         """The stages of the last step as device tensors with a leading E axis (valid until the next step), as
@@ -720,29 +698,20 @@ class BatchedRandomShooting(_EpisodeBatch):
         # -- everything that can be refused is refused here, before the engine and its device memory exist
         E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
                                          sample_mode, dtype, gamma, filter_coeffs, "random-shooting")
-        step_size = _per_episode("step_size", step_size, E)
-        init_cov = _per_episode("init_cov", init_cov, E)
-        if not np.all(init_cov > 0):
-            raise ValueError("init_cov must be positive")
-        if not np.all(step_size >= 0):
-            raise ValueError("step_size must not be negative")
-        self.seed_vals = self._check_seeds(seeds, E)
-        model = self._compile(raw_model)
+        step_size = _per_episode("step_size", step_size, E, sign="not negative")
+        init_cov = _per_episode("init_cov", init_cov, E, sign="positive")
+        model = self._seeds_and_model(seeds, E, raw_model)
         A = model.nu
-        lib = _lib.load()
-        if not lib.mjmpc_rs_batch_supported(E, P, H, A):
+        if not _lib.load().mjmpc_rs_batch_supported(E, P, H, A):
             raise ValueError("the batched random-shooting step takes up to 256 action channels, got A = %d" % A)
-        init_mean = np.zeros((E, H, A)) if init_mean is None else _per_episode("init_mean", init_mean, E, (H, A))
-        factors = [noise_factor(np.diag(np.array([c] * A))) for c in init_cov]      # (OLGaussianMPC: diag(init_cov))
+        init_mean = self._init_mean(init_mean, E, H, A)
+        chols = self._diag_factors(init_cov, A)[1]                                  # (OLGaussianMPC: diag(init_cov))
 
         # -- the engine (its state shards are the E real envs) and the batch's device buffers
         self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean)
-        torch, dev = self.torch, self.device
         self.step_size, self.init_cov = step_size, init_cov
-        self._chols = torch.from_numpy(np.stack([f[0] for f in factors])).to(dev)
-        self._step = torch.from_numpy(step_size.copy()).to(dev)
-        self._best = torch.zeros(E, dtype=torch.int64, device=dev)
-        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+        self._chols, self._step = self._upload(chols), self._upload(step_size)
+        self._best = self.torch.zeros(E, dtype=self.torch.int64, device=self.device)
 
     @property
     def best_particle(self):
@@ -751,18 +720,12 @@ class BatchedRandomShooting(_EpisodeBatch):
         self._check_status()
         return out
 
-    def step(self, _out=None):
+    def _launches(self, act, s):
         """Enqueue one control step of every episode (sampling, rollouts, selection + blend + action + shift, real-env step)
         without a host synchronisation.  The actions, real-env costs and next observations stay on the device."""
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
-        act, cost, nobs = _out if _out is not None else (self._act, self._env_cost, self._env_obs)
-        lib, code, s = self.lib, self._code, self._stream()
-        _lib.check(lib.mjmpc_sample_noise_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._seeds), 0,
-                                                _vp(self._step_dev), s))
+        self._draw(s)
         self._rollout(s)
-        _lib.check(lib.mjmpc_rs_update_batch(code, E, P, H, A, _vp(self._q0), _vp(self._actions), _vp(self._step),
-                                             _SHIFT_MODES[self.base_action], _vp(self._means), _vp(act), _vp(self._step_dev),
-                                             _vp(self._best), s))
-        self._env_step(act, cost, nobs, s)
-        self.num_steps += 1
-        return act, cost, nobs
+        _lib.check(self.lib.mjmpc_rs_update_batch(self._code, E, P, H, A, _vp(self._q0), _vp(self._actions), _vp(self._step),
+                                                  _SHIFT_MODES[self.base_action], _vp(self._means), _vp(act),
+                                                  _vp(self._step_dev), _vp(self._best), s))

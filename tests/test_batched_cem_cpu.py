@@ -1,17 +1,13 @@
 """CPU: ``BatchedCEM`` refuses what it does not run before any engine or device memory exists, broadcasts its
 per-episode settings as ``BatchedMPPI`` does, and its entry points are declared, bound, built and reject bad arguments."""
-import dataclasses
-import os
-import re
-
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import no_engine  # noqa: F401
 from mjmpc_amd import _lib
 from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-from mjmpc_amd.models.hand24 import hand24_raw
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["mjmpc_cem_batch_supported", "mjmpc_cem_batch_workspace_bytes", "mjmpc_cem_select_moments_batch",
                "mjmpc_cem_finish_batch"]
 
@@ -23,38 +19,24 @@ def _kw(**over):
     return kw
 
 
-@pytest.fixture
-def no_engine(monkeypatch):
-    """Making an engine fails the test: every refusal must come first."""
-    from mjmpc_amd.envs import tree_engine
-
-    def refuse(*a, **k):
-        raise AssertionError("an engine was created before the settings were checked")
-    monkeypatch.setattr(tree_engine.TreeRolloutEngine, "__init__", refuse)
-
-
-@pytest.mark.parametrize("over", [
-    dict(n_iters=2), dict(sample_mode="sample"), dict(use_zero_control_seq=True), dict(gamma=0.0),
-    dict(cov_type="full_AxA"), dict(cov_type="sigma_I"), dict(base_action="random"), dict(base_action="zeros"),
-    dict(dtype="f16"), dict(num_episodes=0), dict(num_episodes=65536), dict(horizon=0), dict(num_particles=0),
-    dict(filter_coeffs=[1.0, 0.0]),
+@pytest.mark.parametrize("over", bc.COMMON_REFUSED + [
+    dict(use_zero_control_seq=True), dict(cov_type="full_AxA"), dict(cov_type="sigma_I"),
     # an episode without an elite particle (int(64 * 0.01) = 0), or with more elites than particles
     dict(elite_frac=0.01), dict(elite_frac=[0.1, 0.1, 0.001, 0.1]), dict(elite_frac=1.5),
     # shapes outside the batched fused CEM step: P > 32768, A = 6 > H + 1
     dict(num_particles=32769), dict(horizon=4),
     # per-episode arrays of the wrong length / shape, and values CEM cannot take
     dict(init_cov=[0.1] * 3), dict(elite_frac=[0.1, 0.2]), dict(step_size=np.ones(5)), dict(beta=np.zeros((4, 2))),
-    dict(seeds=[1, 2, 3]), dict(seeds=7), dict(seeds=[1, 2, 3, -4]), dict(init_cov=[0.3, 0.3, -1.0, 0.3]),
-    # a model the tree engine refuses: RK4 beyond 16 dofs
-    dict(raw_model=dataclasses.replace(hand24_raw(), integrator="RK4")),
-], ids=lambda d: ",".join("%s=%s" % (k, type(v).__name__ if k == "raw_model" else v) for k, v in d.items()))
-def test_unsupported_settings_raise_before_any_engine(no_engine, over):
+    dict(init_cov=[0.3, 0.3, -1.0, 0.3]),
+    dict(raw_model=bc.rk4_hand()),
+], ids=bc.refused_id())
+def test_unsupported_settings_raise_before_any_engine(no_engine, over):     # noqa: F811
     from mjmpc_amd.control import BatchedCEM
     with pytest.raises(ValueError):
         BatchedCEM(**_kw(**over))
 
 
-def test_the_shape_refusal_states_the_limits(no_engine):
+def test_the_shape_refusal_states_the_limits(no_engine):                    # noqa: F811
     from mjmpc_amd.control import BatchedCEM
     with pytest.raises(ValueError) as ei:
         BatchedCEM(**_kw(num_particles=32769))
@@ -62,35 +44,23 @@ def test_the_shape_refusal_states_the_limits(no_engine):
         assert limit in str(ei.value)
 
 
-def test_supported_settings_reach_the_engine(no_engine):
+def test_supported_settings_reach_the_engine(no_engine):                    # noqa: F811
     """The settings the batch runs pass the checks (and then get as far as making the engine)."""
     from mjmpc_amd.control import BatchedCEM
-    for over in (dict(), dict(cov_type="diagonal"),
-                 dict(init_cov=[0.1, 0.2, 0.3, 0.4], elite_frac=[1 / 64, 0.1, 0.5, 1.0], step_size=[1.0, 0.9, 0.8, 0.7],
-                      beta=[0.0, 0.45, 0.2, 1.0], base_action="repeat", dtype="f32", seeds=np.arange(4))):
-        with pytest.raises(AssertionError, match="engine was created"):
-            BatchedCEM(**_kw(**over))
+    bc.check_reaches_the_engine(BatchedCEM, [_kw(), _kw(cov_type="diagonal"), _kw(
+        init_cov=[0.1, 0.2, 0.3, 0.4], elite_frac=[1 / 64, 0.1, 0.5, 1.0], step_size=[1.0, 0.9, 0.8, 0.7],
+        beta=[0.0, 0.45, 0.2, 1.0], base_action="repeat", dtype="f32", seeds=np.arange(4))])
 
 
 def test_per_episode_broadcasting_and_num_elite(monkeypatch):
     """One value for every episode or one per episode; num_elite_e = int(num_particles * elite_frac_e) as cem.py computes it."""
-    from mjmpc_amd.control import BatchedCEM, batched
-    seen = {}
-
-    def stop(self, raw_model, model, E, H, P, *a):
-        seen.update(E=E, H=H, P=P)
-        raise RuntimeError("far enough")
-    monkeypatch.setattr(batched._EpisodeBatch, "_setup", stop)
+    from mjmpc_amd.control import BatchedCEM
+    seen = bc.stop_at_setup(monkeypatch)
     fracs = [0.1, 0.3, 1 / 3, 0.999]
     for P in (64, 50, 1000):
-        with pytest.raises(RuntimeError, match="far enough"):
-            BatchedCEM(**_kw(num_particles=P, elite_frac=fracs))
-        assert seen == dict(E=4, H=8, P=P)
+        bc.check_stops_at_setup(BatchedCEM, _kw(num_particles=P, elite_frac=fracs), seen, 4, 8, P)
     assert [int(1000 * f) for f in fracs] == [100, 300, 333, 999]          # (what the check below compares against)
-    a = batched._per_episode("beta", 0.45, 4)
-    assert a.shape == (4,) and np.all(a == 0.45)
-    a = batched._per_episode("beta", [0.1, 0.2, 0.3, 0.4], 4)
-    assert a.tolist() == [0.1, 0.2, 0.3, 0.4]
+    bc.check_per_episode("beta", 0.45, [0.1, 0.2, 0.3, 0.4])
     # the elite counts the constructor derives (it raises when one of them is 0)
     with pytest.raises(ValueError, match=r"\[6, 0, 6, 6\]"):
         BatchedCEM(**_kw(elite_frac=[0.1, 0.015, 0.1, 0.1]))
@@ -99,24 +69,13 @@ def test_per_episode_broadcasting_and_num_elite(monkeypatch):
 
 
 def test_batched_cem_is_exported():
-    import mjmpc_amd.control as control
-    from mjmpc_amd.control import BatchedCEM, BatchedMPPI
-    from mjmpc_amd.control.batched import _EpisodeBatch
-    assert "BatchedCEM" in control.__all__
-    assert issubclass(BatchedCEM, _EpisodeBatch) and issubclass(BatchedMPPI, _EpisodeBatch)
-    for name in ("set_states", "get_states", "mean_action", "reset", "step", "run", "close", "on_env_reset",
-                 "randomize_dynamics", "clear_dynamics", "cov"):
-        assert hasattr(BatchedCEM, name), name
+    bc.check_exported("BatchedCEM", ("set_states", "get_states", "mean_action", "reset", "step", "run", "close", "on_env_reset",
+                                     "randomize_dynamics", "clear_dynamics", "cov"), ())
+    bc.check_exported("BatchedMPPI", (), ())
 
 
 def test_new_entry_points_are_declared_bound_and_built():
-    with open(os.path.join(ROOT, "include", "mjmpc_amd.h")) as f:
-        header = f.read()
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(lib, name) is not None, name
+    bc.check_entry_points(NEW_SYMBOLS)
 
 
 def test_supported_shapes_and_workspace():

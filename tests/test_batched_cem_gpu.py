@@ -14,120 +14,25 @@ import ctypes
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import FILT, _cheetah_states, _torch, _vp
+from batched_cases import cheetah as _cheetah
+
 pytestmark = pytest.mark.gpu
 
-FILT = [0.25, 0.8, 0.0]
+
+def _took_the_fused_step(c):
+    assert c._cem_fused(), "the single path did not take its fused CEM step"
 
 
-def _torch():
-    import torch
-    return torch
+CEM = bc.case("BatchedCEM", "CEM", ("init_cov", "elite_frac", "step_size", "beta"), lambda dtype: dict(noise_dtype=dtype),
+              during=_took_the_fused_step, extra=("cov_action", "cov"))
 
 
-def _vp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _per(v, e):
-    return v[e] if np.ndim(v) > 0 else v
-
-
-def _single(raw, state, seed, P, H, T, init_cov, elite_frac, step_size, beta, dtype, cov_type="full", base_action="null",
-            K=1, cfg=None, dyn_seed=None):
-    """One episode on the single-episode device path -> (actions [T][A], costs [T], next obs [T][d_obs], mean, cov, state)."""
-    torch = _torch()
-    from mjmpc_amd.control import CEM
-    from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
-    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    eng = TreeRolloutEngine(raw, dtype=dtype, num_shards=K)
-    if cfg is not None:
-        eng.randomize_dynamics(cfg, dyn_seed)
-        eng.set_real_env_model("nominal")
-    eng.set_env_state(dict(state))
-    A = eng.d_action
-    c = CEM(d_state=eng.d_state, d_obs=eng.d_obs, d_action=A, horizon=H, init_cov=init_cov, base_action=base_action,
-            elite_frac=elite_frac, num_particles=P, step_size=step_size, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
-            action_highs=eng.action_highs, beta=beta, cov_type=cov_type, filter_coeffs=FILT, seed=seed, noise_mode="device",
-            noise_dtype=dtype)
-    c.rollout_fn = make_device_rollout_fn(eng)
-    c.set_sim_state_fn = lambda s: None
-    c.enable_graph(post_step=eng.step_state)
-    acts, costs, nobs = [], [], []
-    for _ in range(T):
-        a, _ = c.optimize(None)
-        torch.cuda.synchronize()
-        assert c._cem_fused(), "the single path did not take its fused CEM step"
-        acts.append(np.array(a, np.float64))
-        costs.append(eng._buf["step_cost"].cpu().numpy()[0])
-        nobs.append(eng._buf["step_obs"].cpu().numpy().copy())
-    mean, cov = np.array(c.mean_action), np.array(c.cov_action)
-    st = eng.get_state_device()
-    assert eng.env_resets() == 0, "the single path's real env reset"
-    eng.close()
-    return np.array(acts), np.array(costs), np.array(nobs), mean, cov, st
-
-
-def _batch(raw, states, seeds, P, H, T, init_cov, elite_frac, step_size, beta, dtype, cov_type="full", base_action="null",
-           K=1, cfg=None, dyn_seed=None):
-    from mjmpc_amd.control import BatchedCEM
-    b = BatchedCEM(raw, len(states), H, P, init_cov, elite_frac, step_size, beta, 1.0, FILT, base_action, seeds,
-                   cov_type=cov_type, dtype=dtype)
-    b.set_states([dict(s) for s in states])
-    if cfg is not None:
-        b.randomize_dynamics(cfg, dyn_seed, K)
-    acts, costs, nobs = b.run(T)
-    out = acts, costs, nobs, b.mean_action, b.cov, b.get_states()
-    assert b.engine.env_resets() == 0, "a real env of the batch reset"
-    b.close()
-    return out
-
-
-def _qpos_qvel(st):
-    return (st["qpos"], st["qvel"]) if "qpos" in st else (st["qp"], st["qv"])
-
-
-def _check_against_singles(raw, states, seeds, P, H, T, init_cov, elite_frac, step_size, beta, dtype, **kw):
-    E = len(states)
-    acts, costs, nobs, means, covs, fin = _batch(raw, states, seeds, P, H, T, init_cov, elite_frac, step_size, beta, dtype, **kw)
-    assert acts.shape[:2] == (T, E) and costs.shape == (T, E) and means.shape[0] == E and covs.shape[0] == E and len(fin) == E
-    assert np.all(np.isfinite(acts)) and np.all(np.isfinite(costs))
-    for e in range(E):
-        skw = dict(kw)
-        if isinstance(skw.get("dyn_seed"), (list, tuple)):
-            skw["dyn_seed"] = skw["dyn_seed"][e]
-        a1, c1, o1, m1, v1, s1 = _single(raw, states[e], seeds[e], P, H, T, _per(init_cov, e), _per(elite_frac, e),
-                                         _per(step_size, e), _per(beta, e), dtype, **skw)
-        assert np.all(np.isfinite(a1)) and np.all(np.isfinite(c1))
-        assert np.array_equal(acts[:, e], a1), "episode %d: actions differ (max %.3g)" % (e, np.abs(acts[:, e] - a1).max())
-        assert np.array_equal(costs[:, e], c1), "episode %d: real-env costs differ" % e
-        assert np.array_equal(nobs[:, e], o1), "episode %d: next observations differ" % e
-        assert np.array_equal(means[e], m1), "episode %d: final mean differs" % e
-        assert np.array_equal(covs[e], v1), "episode %d: final covariance differs (max %.3g)" % (e, np.abs(covs[e] - v1).max())
-        for x, y in zip(_qpos_qvel(fin[e]), _qpos_qvel(s1)):
-            assert np.array_equal(x, y), "episode %d: final state differs" % e
-    return acts, costs, covs
-
-
-_CHEETAH = {}
-
-
-def _cheetah_states(E):
-    """Start states of the env class's seeded resets, made once and shared (read-only)."""
-    if E not in _CHEETAH:
-        from mjmpc_amd.envs.locomotion_env import HalfCheetahEnv
-        env = HalfCheetahEnv()
-        out = []
-        for i in range(E):
-            env.reset(seed=123 + i * 12345)
-            out.append(env.get_env_state())
-        env.engine.close()
-        _CHEETAH[E] = out
-    return _CHEETAH[E]
-
-
-def _cheetah():
-    from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-    return half_cheetah_raw()
+def _check_against_singles(raw, states, seeds, P, H, T, init_cov, elite_frac, step_size, beta, dtype, cov_type="full", **kw):
+    out = bc.check_against_singles(CEM, raw, states, seeds, P, H, T, (init_cov, elite_frac, step_size, beta), dtype,
+                                   cov_type=cov_type, **kw)
+    return out["acts"], out["costs"], out["extra"]
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
@@ -157,32 +62,16 @@ def test_particles_not_a_multiple_of_the_tiles():
 
 
 def test_one_episode_and_permuted_episodes():
-    raw, E = _cheetah(), 3
+    raw = _cheetah()
     _check_against_singles(raw, _cheetah_states(1), [123], 64, 8, 6, 0.3, 0.1, 1.0, 0.45, "f64")
-    states, seeds = _cheetah_states(E), [5, 6, 7]
     cov, frac, step, beta = np.array([0.2, 0.3, 0.4]), np.array([0.1, 0.2, 0.3]), np.array([1.0, 0.9, 0.8]), np.array([0.45, 0.3, 0.1])
-    base = _batch(raw, states, seeds, 64, 8, 6, cov, frac, step, beta, "f64")
-    perm = [2, 0, 1]
-    got = _batch(raw, [states[k] for k in perm], [seeds[k] for k in perm], 64, 8, 6, cov[perm], frac[perm], step[perm],
-                 beta[perm], "f64")
-    for i in range(3):
-        assert np.array_equal(got[i], base[i][:, perm])
-    assert np.array_equal(got[3], base[3][perm]) and np.array_equal(got[4], base[4][perm])
-    for k, e in enumerate(perm):
-        for x, y in zip(_qpos_qvel(got[5][k]), _qpos_qvel(base[5][e])):
-            assert np.array_equal(x, y)
+    bc.check_permutation(CEM, raw, _cheetah_states(3), [5, 6, 7], 64, 8, 6, (cov, frac, step, beta), "f64", [2, 0, 1])
 
 
 def test_rk4_double_pendulum():
     """A non-HalfCheetah instantiation of the rollout kernel (RK4, one actuator... A <= H + 1 holds)."""
-    from mjmpc_amd.envs.synthetic_env import start_state
-    from mjmpc_amd.models.synthetic import synthetic_raw
-    raw = synthetic_raw("double_pendulum")
+    raw, states = bc.synthetic_states("double_pendulum", 2, seed=1)
     assert raw.integrator == "RK4"
-    st = start_state("double_pendulum", raw)
-    rng = np.random.RandomState(1)
-    states = [dict(qp=st["qp"].copy(), qv=st["qv"] + 0.05 * rng.randn(st["qv"].size), target_pos=st["target_pos"].copy())
-              for _ in range(2)]
     _check_against_singles(raw, states, [21, 22], 32, 6, 4, 0.3, 0.25, 1.0, 0.45, "f64")
 
 

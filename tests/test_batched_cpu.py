@@ -1,13 +1,12 @@
 """CPU: the episode-batch entry points refuse bad arguments without a GPU, and ``BatchedMPPI`` refuses what it does not run
 before it creates an engine."""
-import dataclasses
-
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import no_engine  # noqa: F401
 from mjmpc_amd import _lib
 from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-from mjmpc_amd.models.hand24 import hand24_raw
 
 
 def test_batch_entry_points_reject_bad_arguments():
@@ -52,38 +51,22 @@ def _kw(**over):
     return kw
 
 
-@pytest.fixture
-def no_engine(monkeypatch):
-    """Making an engine fails the test: every refusal must come first."""
-    from mjmpc_amd.envs import tree_engine
-
-    def refuse(*a, **k):
-        raise AssertionError("an engine was created before the settings were checked")
-    monkeypatch.setattr(tree_engine.TreeRolloutEngine, "__init__", refuse)
-
-
-@pytest.mark.parametrize("over", [
-    dict(n_iters=2), dict(alpha=0), dict(time_based_weights=True), dict(cov_type="full"), dict(base_action="random"),
-    dict(base_action="zeros"), dict(use_zero_control_seq=True), dict(sample_mode="sample"), dict(gamma=0.0),
-    dict(dtype="f16"), dict(num_episodes=0), dict(num_episodes=65536), dict(horizon=0), dict(num_particles=0),
-    dict(filter_coeffs=[1.0, 0.0]),
+@pytest.mark.parametrize("over", bc.COMMON_REFUSED + [
+    dict(use_zero_control_seq=True), dict(alpha=0), dict(time_based_weights=True), dict(cov_type="full"),
     # per-episode arrays of the wrong length / shape, and values MPPI cannot take
-    dict(lam=[0.1, 0.2, 0.3]), dict(step_size=np.ones(5)), dict(init_cov=[0.1] * 3), dict(seeds=[1, 2, 3]), dict(seeds=7),
-    dict(seeds=[1, 2, 3, -4]), dict(init_mean=np.zeros((3, 8, 6))), dict(init_mean=np.zeros((8, 5))), dict(lam=0.0),
-    dict(init_cov=[0.3, 0.3, -1.0, 0.3]),
-    # a model the tree engine refuses: RK4 beyond 16 dofs
-    dict(raw_model=dataclasses.replace(hand24_raw(), integrator="RK4")),
-], ids=lambda d: ",".join("%s=%s" % (k, type(v).__name__ if k == "raw_model" else v) for k, v in d.items()))
-def test_unsupported_settings_raise_before_any_engine(no_engine, over):
+    dict(lam=[0.1, 0.2, 0.3]), dict(step_size=np.ones(5)), dict(init_cov=[0.1] * 3), dict(init_mean=np.zeros((3, 8, 6))),
+    dict(init_mean=np.zeros((8, 5))), dict(lam=0.0), dict(init_cov=[0.3, 0.3, -1.0, 0.3]),
+    dict(raw_model=bc.rk4_hand()),
+], ids=bc.refused_id())
+def test_unsupported_settings_raise_before_any_engine(no_engine, over):     # noqa: F811
     from mjmpc_amd.control import BatchedMPPI
     with pytest.raises(ValueError):
         BatchedMPPI(**_kw(**over))
 
 
-def test_supported_settings_reach_the_engine(no_engine):
+def test_supported_settings_reach_the_engine(no_engine):                    # noqa: F811
     """The settings the batch runs pass the checks (and then get as far as making the engine)."""
     from mjmpc_amd.control import BatchedMPPI
-    for over in (dict(), dict(lam=[0.1, 0.2, 0.3, 0.4], step_size=[1.0, 0.9, 0.8, 0.7], init_cov=[0.1, 0.2, 0.3, 0.4],
-                              base_action="repeat", dtype="f32", init_mean=np.zeros((4, 8, 6)), seeds=np.arange(4))):
-        with pytest.raises(AssertionError, match="engine was created"):
-            BatchedMPPI(**_kw(**over))
+    bc.check_reaches_the_engine(BatchedMPPI, [_kw(), _kw(
+        lam=[0.1, 0.2, 0.3, 0.4], step_size=[1.0, 0.9, 0.8, 0.7], init_cov=[0.1, 0.2, 0.3, 0.4], base_action="repeat",
+        dtype="f32", init_mean=np.zeros((4, 8, 6)), seeds=np.arange(4))])

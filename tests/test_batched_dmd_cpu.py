@@ -1,19 +1,16 @@
 """CPU: ``BatchedDMDMPC`` refuses what it does not run before any engine or device memory exists, broadcasts its
 per-episode settings as the other batches do, and its entry points are declared, bound, built and reject bad arguments."""
 import ctypes
-import dataclasses
-import os
-import re
 import types
 
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import no_engine  # noqa: F401
 from mjmpc_amd import _lib
 from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-from mjmpc_amd.models.hand24 import hand24_raw
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["mjmpc_cholesky_lower_batch", "mjmpc_sample_noise_cov_batch", "mjmpc_dmd_batch_workspace_bytes",
                "mjmpc_dmd_update_batch"]
 
@@ -25,21 +22,8 @@ def _kw(**over):
     return kw
 
 
-@pytest.fixture
-def no_engine(monkeypatch):
-    """Making an engine fails the test: every refusal must come first."""
-    from mjmpc_amd.envs import tree_engine
-
-    def refuse(*a, **k):
-        raise AssertionError("an engine was created before the settings were checked")
-    monkeypatch.setattr(tree_engine.TreeRolloutEngine, "__init__", refuse)
-
-
-@pytest.mark.parametrize("over", [
-    # what _check_common refuses
-    dict(n_iters=2), dict(sample_mode="sample"), dict(use_zero_control_seq=True), dict(gamma=0.0),
-    dict(base_action="random"), dict(base_action="zeros"), dict(dtype="f16"), dict(num_episodes=0),
-    dict(num_episodes=65536), dict(horizon=0), dict(num_particles=0), dict(filter_coeffs=[1.0, 0.0]),
+@pytest.mark.parametrize("over", bc.COMMON_REFUSED + [
+    dict(use_zero_control_seq=True),
     # values DMD-MPC cannot take, for every episode or for one of them
     dict(lam=0.0), dict(lam=[0.2, 0.2, -0.1, 0.2]), dict(init_cov=0.0), dict(init_cov=[0.3, 0.3, -1.0, 0.3]),
     dict(beta=-0.1), dict(beta=[0.0, 0.1, -1e-9, 0.1]),
@@ -47,25 +31,24 @@ def no_engine(monkeypatch):
     dict(cov_type="full_AxA"), dict(cov_type="sigma_I"),
     # the arithmetic of BatchedMPPI
     dict(update_cov=False),
-    # per-episode arrays of the wrong length / shape, bad seeds
+    # per-episode arrays of the wrong length / shape
     dict(lam=[0.1] * 3), dict(step_size=np.ones(5)), dict(beta=np.zeros((4, 2))), dict(init_cov=[0.3, 0.3]),
-    dict(init_mean=np.zeros((8, 5))), dict(seeds=[1, 2, 3]), dict(seeds=7), dict(seeds=[1, 2, 3, -4]),
-    # a model the tree engine refuses: RK4 beyond 16 dofs
-    dict(raw_model=dataclasses.replace(hand24_raw(), integrator="RK4")),
-], ids=lambda d: ",".join("%s=%s" % (k, type(v).__name__ if k in ("raw_model", "init_mean") else v) for k, v in d.items()))
-def test_unsupported_settings_raise_before_any_engine(no_engine, over):
+    dict(init_mean=np.zeros((8, 5))),
+    dict(raw_model=bc.rk4_hand()),
+], ids=bc.refused_id(("raw_model", "init_mean")))
+def test_unsupported_settings_raise_before_any_engine(no_engine, over):     # noqa: F811
     from mjmpc_amd.control import BatchedDMDMPC
     with pytest.raises(ValueError):
         BatchedDMDMPC(**_kw(**over))
 
 
-def test_update_cov_false_names_batched_mppi(no_engine):
+def test_update_cov_false_names_batched_mppi(no_engine):                    # noqa: F811
     from mjmpc_amd.control import BatchedDMDMPC
     with pytest.raises(ValueError, match="BatchedMPPI"):
         BatchedDMDMPC(**_kw(update_cov=False))
 
 
-def test_more_than_64_action_channels_are_refused(no_engine, monkeypatch):
+def test_more_than_64_action_channels_are_refused(no_engine, monkeypatch):  # noqa: F811
     """A > 64 is the limit of the Cholesky kernel: refused on the compiled model's nu, before the engine."""
     from mjmpc_amd.control import BatchedDMDMPC, batched
     for nu, ok in ((64, True), (65, False)):
@@ -74,65 +57,38 @@ def test_more_than_64_action_channels_are_refused(no_engine, monkeypatch):
             BatchedDMDMPC(**_kw())
 
 
-def test_supported_settings_reach_the_engine(no_engine):
+def test_supported_settings_reach_the_engine(no_engine):                    # noqa: F811
     """The settings the batch runs pass the checks (and then get as far as making the engine)."""
     from mjmpc_amd.control import BatchedDMDMPC
-    for over in (dict(), dict(cov_type="diagonal"), dict(cov_type="full", update_cov=True), dict(beta=0.0),
-                 dict(init_mean=np.full((8, 6), 0.1)), dict(init_mean=np.zeros((4, 8, 6))),
-                 dict(lam=[0.1, 0.2, 0.3, 0.4], step_size=[1.0, 0.7, 0.5, 0.0], init_cov=[0.1, 0.2, 0.3, 0.4],
-                      beta=[0.0, 0.05, 0.2, 1.0], base_action="repeat", dtype="f32", seeds=np.arange(4),
-                      filter_coeffs=[1.0, 0.0, 0.0])):
-        with pytest.raises(AssertionError, match="engine was created"):
-            BatchedDMDMPC(**_kw(**over))
+    bc.check_reaches_the_engine(BatchedDMDMPC, [
+        _kw(), _kw(cov_type="diagonal"), _kw(cov_type="full", update_cov=True), _kw(beta=0.0),
+        _kw(init_mean=np.full((8, 6), 0.1)), _kw(init_mean=np.zeros((4, 8, 6))),
+        _kw(lam=[0.1, 0.2, 0.3, 0.4], step_size=[1.0, 0.7, 0.5, 0.0], init_cov=[0.1, 0.2, 0.3, 0.4],
+            beta=[0.0, 0.05, 0.2, 1.0], base_action="repeat", dtype="f32", seeds=np.arange(4), filter_coeffs=[1.0, 0.0, 0.0])])
 
 
 def test_per_episode_broadcasting(monkeypatch):
     """One value for every episode or one per episode reaches the batch as float64 [E] (``_per_episode``)."""
     from mjmpc_amd.control import BatchedDMDMPC, batched
-    seen = {}
-
-    def stop(self, raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean):
-        seen.update(E=E, H=H, P=P, init_mean=init_mean)
-        raise RuntimeError("far enough")
-    monkeypatch.setattr(batched._EpisodeBatch, "_setup", stop)
+    seen = bc.stop_at_setup(monkeypatch)
     for P in (64, 50, 1043):
-        with pytest.raises(RuntimeError, match="far enough"):
-            BatchedDMDMPC(**_kw(num_particles=P, lam=[0.1, 0.2, 0.3, 0.4]))
-        assert (seen["E"], seen["H"], seen["P"]) == (4, 8, P)
+        bc.check_stops_at_setup(BatchedDMDMPC, _kw(num_particles=P, lam=[0.1, 0.2, 0.3, 0.4]), seen, 4, 8, P)
         assert seen["init_mean"].shape == (4, 8, 6) and not seen["init_mean"].any()
-    with pytest.raises(RuntimeError, match="far enough"):
-        BatchedDMDMPC(**_kw(init_mean=np.full((8, 6), 0.25)))
+    bc.check_stops_at_setup(BatchedDMDMPC, _kw(init_mean=np.full((8, 6), 0.25)), seen, 4, 8, 64)
     assert seen["init_mean"].shape == (4, 8, 6) and np.all(seen["init_mean"] == 0.25)
-    a = batched._per_episode("beta", 0.05, 4)
-    assert a.shape == (4,) and a.dtype == np.float64 and np.all(a == 0.05)
-    a = batched._per_episode("beta", [0.1, 0.2, 0.3, 0.4], 4)
-    assert a.tolist() == [0.1, 0.2, 0.3, 0.4]
+    bc.check_per_episode("beta", 0.05, [0.1, 0.2, 0.3, 0.4])
     with pytest.raises(ValueError, match="beta"):
         batched._per_episode("beta", [0.1, 0.2], 4)
 
 
 def test_batched_dmdmpc_is_exported():
-    import mjmpc_amd.control as control
-    from mjmpc_amd.control import BatchedDMDMPC
-    from mjmpc_amd.control.batched import _EpisodeBatch
-    assert "BatchedDMDMPC" in control.__all__
-    assert issubclass(BatchedDMDMPC, _EpisodeBatch)
-    for name in ("set_states", "get_states", "mean_action", "reset", "step", "run", "close", "on_env_reset",
-                 "randomize_dynamics", "clear_dynamics", "cov"):
-        assert hasattr(BatchedDMDMPC, name), name
-    for name in ("randomize_dynamics", "set_states", "get_states", "run"):         # (from the base class, unchanged)
-        assert getattr(BatchedDMDMPC, name) is getattr(_EpisodeBatch, name), name
+    bc.check_exported("BatchedDMDMPC", ("set_states", "get_states", "mean_action", "reset", "step", "run", "close",
+                                        "on_env_reset", "randomize_dynamics", "clear_dynamics", "cov"),
+                      ("randomize_dynamics", "set_states", "get_states", "run"))         # (from the base class, unchanged)
 
 
 def test_new_entry_points_are_declared_bound_and_built():
-    with open(os.path.join(ROOT, "include", "mjmpc_amd.h")) as f:
-        header = f.read()
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(lib, name) is not None, name
-    assert re.search(r"#define MJMPC_ABI_VERSION 4\b", header) and lib.mjmpc_abi_version() == 4
+    bc.check_entry_points(NEW_SYMBOLS, abi=4)
 
 
 def test_workspace_is_positive_and_grows_with_E():

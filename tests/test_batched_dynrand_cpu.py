@@ -1,28 +1,18 @@
 """CPU: dynamics-randomized episode batches refuse what they do not run before anything reaches the device, draw what
 ``SubprocVecEnv.randomize_dynamics`` draws, and the two new entry points are declared, bound, built and refuse bad arguments."""
-import os
 import re
 
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import no_engine  # noqa: F401
 from mjmpc_amd import _lib
 from mjmpc_amd.models.half_cheetah import half_cheetah_raw
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["mjmpc_tree_set_batch_models", "mjmpc_tree_set_env_model"]
 CFG = {"body_mass": {"torso": [0.3, 0.1], "ffoot": [0.5, 0.0]}, "dof_damping": {"bshin": [0.4, 0.2]},
        "geom_size": {"ffoot": [0.2, 0.0]}, "geom_friction": {"bfoot": [0.5, 0.5]}}
-
-
-@pytest.fixture
-def no_engine(monkeypatch):
-    """Making an engine fails the test: every refusal must come first (tests/test_batched_cpu.py's pattern)."""
-    from mjmpc_amd.envs import tree_engine
-
-    def refuse(*a, **k):
-        raise AssertionError("an engine was created before the settings were checked")
-    monkeypatch.setattr(tree_engine.TreeRolloutEngine, "__init__", refuse)
 
 
 class _Device:
@@ -53,12 +43,12 @@ def _batch(E=3, P=48, raw=None):
     ({"sensor_noise": {"no_such_sensor": [0.1, 0.0]}}, 1, 2),
     (CFG, [1, 2], 2), (CFG, [1, 2, 3, 4], 2), (CFG, [], 2),     # a seed list of the wrong length (E = 3)
 ], ids=lambda v: re.sub(r"[^A-Za-z0-9_,]+", "", str(v))[:24])
-def test_randomize_dynamics_refuses_before_the_device(no_engine, cfg, seed, K):
+def test_randomize_dynamics_refuses_before_the_device(no_engine, cfg, seed, K):     # noqa: F811
     with pytest.raises(ValueError):
         _batch().randomize_dynamics(cfg, seed, K)
 
 
-def test_a_batch_built_from_a_compiled_model_cannot_randomize(no_engine):
+def test_a_batch_built_from_a_compiled_model_cannot_randomize(no_engine):     # noqa: F811
     b = _batch()
     b.raw = None
     with pytest.raises(ValueError, match="RawModel"):
@@ -66,7 +56,7 @@ def test_a_batch_built_from_a_compiled_model_cannot_randomize(no_engine):
 
 
 @pytest.mark.parametrize("seed", [7, [7, 8, 9], np.array([7, 8, 9])], ids=["one", "list", "array"])
-def test_supported_settings_reach_the_device(no_engine, seed):
+def test_supported_settings_reach_the_device(no_engine, seed):     # noqa: F811
     with pytest.raises(AssertionError, match="the device was reached"):
         _batch().randomize_dynamics(CFG, seed, 2)
 
@@ -106,7 +96,7 @@ def test_draws_follow_the_reference_seeds():
     assert np.array_equal(same[0], np.asarray(host.model.blob, np.float64))
 
 
-def test_host_only_engine_owns_no_device_state(no_engine):
+def test_host_only_engine_owns_no_device_state(no_engine):     # noqa: F811
     from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
     host = TreeRolloutEngine.host_only(half_cheetah_raw())
     assert host.closed and not hasattr(host, "_h")
@@ -114,13 +104,7 @@ def test_host_only_engine_owns_no_device_state(no_engine):
 
 
 def test_new_entry_points_are_declared_bound_and_built():
-    with open(os.path.join(ROOT, "include", "mjmpc_amd.h")) as f:
-        header = f.read()
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(lib, name) is not None, name
+    header = bc.check_entry_points(NEW_SYMBOLS)
     assert len(_lib.SIGNATURES["mjmpc_tree_set_batch_models"][1]) == 4 and len(_lib.SIGNATURES["mjmpc_tree_set_env_model"][1]) == 2
     assert re.search(r"mjmpc_tree_set_batch_models\(mjmpc_tree_t h, const double\* \w+, int n_sets, int K\)", header)
     assert re.search(r"mjmpc_tree_set_env_model\(mjmpc_tree_t h, const double\* \w+\)", header)

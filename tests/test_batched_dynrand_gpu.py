@@ -8,66 +8,29 @@ actions, real-env costs and next observations of every step, the final mean and 
 every (episode, shard) against the FP64 C oracle edited through its setters, independent of the single path.
 """
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import _torch
+from batched_cases import synthetic_states as _synthetic_states
+
 pytestmark = pytest.mark.gpu
 
-FILT = [0.25, 0.8, 0.0]
 # the configuration of test_dynamics_randomization_per_shard_on_the_tree_engine (tests/test_locomotion_gpu.py) minus sensor_noise
 CHEETAH_CFG = {"body_mass": {"torso": [0.3, 0.1], "ffoot": [0.5, 0.0]}, "body_inertia": {"bthigh": [0.3, 0.0]},
                "dof_damping": {"bshin": [0.4, 0.2]}, "geom_size": {"ffoot": [0.2, 0.0], "bfoot": [0.1, 0.0]},
                "geom_friction": {"bfoot": [0.5, 0.5]}, "dof_frictionloss": {"fshin": [0.5, 0.0]}}
 
 
-def _torch():
-    import torch
-    return torch
-
-
-def _single(raw, state, seed, P, H, T, lam, step_size, init_cov, dtype, K, cfg, dyn_seed):
-    """tests/test_batched_mppi_gpu.py's ``_single`` on a K-shard engine with randomized blocks and a nominal real env
-    -> (actions [T][A], costs [T], next obs [T][d_obs], mean, state, the engine's shard blocks)."""
-    torch = _torch()
-    from mjmpc_amd.control import MPPI
-    from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
-    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    eng = TreeRolloutEngine(raw, dtype=dtype, num_shards=K)
-    if cfg is not None:
-        eng.randomize_dynamics(cfg, dyn_seed)
-        eng.set_real_env_model("nominal")
-    eng.set_env_state(dict(state))
-    A = eng.d_action
-    c = MPPI(d_state=eng.d_state, d_obs=eng.d_obs, d_action=A, horizon=H, init_cov=init_cov, base_action="null", lam=lam,
-             num_particles=P, step_size=step_size, alpha=1, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
-             action_highs=eng.action_highs, filter_coeffs=FILT, seed=seed, noise_mode="device", noise_dtype=dtype)
-    c.rollout_fn = make_device_rollout_fn(eng)
-    c.set_sim_state_fn = lambda s: None
-    c.enable_graph(post_step=eng.step_state)
-    acts, costs, nobs = [], [], []
-    for _ in range(T):
-        a, _ = c.optimize(None)
-        torch.cuda.synchronize()
-        acts.append(np.array(a, np.float64))
-        costs.append(eng._buf["step_cost"].cpu().numpy()[0])
-        nobs.append(eng._buf["step_obs"].cpu().numpy().copy())
-    mean = np.array(c.mean_action)
-    st = eng.get_state_device()
-    blobs = getattr(eng, "shard_blobs", None)
-    eng.close()
-    return np.array(acts), np.array(costs), np.array(nobs), mean, st, blobs
+MPPI = bc.case("BatchedMPPI", "MPPI", ("lam", "step_size", "init_cov"), lambda dtype: dict(alpha=1, noise_dtype=dtype),
+               guards=False)          # (tests/test_batched_mppi_gpu.py's)
 
 
 def _make_batch(raw, states, seeds, P, H, lam, cov, dtype):
-    from mjmpc_amd.control import BatchedMPPI
-    b = BatchedMPPI(raw, len(states), H, P, lam, 1.0, cov, 1.0, FILT, "null", seeds, dtype=dtype)
-    b.set_states([dict(s) for s in states])
-    return b
-
-
-def _qpos_qvel(st):
-    return (st["qpos"], st["qvel"]) if "qpos" in st else (st["qp"], st["qv"])
+    return bc.make_batch(MPPI, raw, states, seeds, P, H, (lam, 1.0, cov), dtype)
 
 
 def _check(raw, states, seeds, P, H, T, lam, cov, dtype, K, cfg, dyn_seed):
@@ -77,48 +40,15 @@ def _check(raw, states, seeds, P, H, T, lam, cov, dtype, K, cfg, dyn_seed):
     per_episode = isinstance(dyn_seed, (list, tuple))
     defaults, rand = b.randomize_dynamics(cfg, dyn_seed, K)
     assert len(rand) == (E if per_episode else K) and b.shard_blobs.shape[:2] == ((E if per_episode else 1), K)
-    acts, costs, nobs = b.run(T)
-    means, fin = b.mean_action, b.get_states()
-    b.close()
-    assert np.all(np.isfinite(acts)) and np.all(np.isfinite(costs))
-    for e in range(E):
-        a1, c1, o1, m1, s1, blobs = _single(raw, states[e], seeds[e], P, H, T, lam, 1.0, cov, dtype, K, cfg,
-                                            dyn_seed[e] if per_episode else dyn_seed)
+    out = bc.check_against_singles(MPPI, raw, states, seeds, P, H, T, (lam, 1.0, cov), dtype, out=bc.run_batch(MPPI, b, T),
+                                   K=K, cfg=cfg, dyn_seed=dyn_seed)
+    for e, one in enumerate(out["singles"]):
         # the model-block bytes the batch uploads are the single engine's
-        assert np.array_equal(b.shard_blobs[e if per_episode else 0], blobs), "episode %d: model blocks differ" % e
-        assert np.array_equal(acts[:, e], a1), "episode %d: actions differ (max %.3g)" % (e, np.abs(acts[:, e] - a1).max())
-        assert np.array_equal(costs[:, e], c1), "episode %d: real-env costs differ" % e
-        assert np.array_equal(nobs[:, e], o1), "episode %d: next observations differ" % e
-        assert np.array_equal(means[e], m1), "episode %d: final mean differs" % e
-        for x, y in zip(_qpos_qvel(fin[e]), _qpos_qvel(s1)):
-            assert np.array_equal(x, y), "episode %d: final state differs" % e
-    return acts, b.shard_blobs
+        assert np.array_equal(b.shard_blobs[e if per_episode else 0], one["blobs"]), "episode %d: model blocks differ" % e
+    return out["acts"], b.shard_blobs
 
 
-_CHEETAH = {}
-
-
-def _cheetah_states(E):
-    """Start states of the env class's seeded resets, made once and shared (read-only)."""
-    if E not in _CHEETAH:
-        from mjmpc_amd.envs.locomotion_env import HalfCheetahEnv
-        env = HalfCheetahEnv()
-        out = []
-        for i in range(E):
-            env.reset(seed=123 + i * 12345)
-            out.append(env.get_env_state())
-        env.engine.close()
-        _CHEETAH[E] = out
-    return [dict(qpos=s["qpos"].copy(), qvel=s["qvel"].copy()) for s in _CHEETAH[E]]
-
-
-def _synthetic_states(name, E, seed=0):
-    from mjmpc_amd.models.synthetic import start_state, synthetic_raw
-    raw = synthetic_raw(name)
-    st = start_state(name, raw)
-    rng = np.random.RandomState(seed)
-    return raw, [dict(qp=st["qp"].copy(), qv=st["qv"] + 0.05 * rng.randn(st["qv"].size), target_pos=st["target_pos"].copy())
-                 for _ in range(E)]
+_cheetah_states = functools.partial(bc._cheetah_states, copy=True)      # (copies: the tests here may edit their start states)
 
 
 @pytest.mark.parametrize("dyn_seed", [321, [321, 77, 4242]], ids=["shared_set", "set_per_episode"])

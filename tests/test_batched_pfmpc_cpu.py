@@ -1,18 +1,15 @@
 """CPU: ``BatchedPFMPC`` refuses what it does not run before any engine or device memory exists, broadcasts its
 per-episode settings as the other batches do, and its entry points are declared, bound, built and reject bad arguments."""
 import ctypes
-import dataclasses
-import os
-import re
 
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import no_engine  # noqa: F401
 from mjmpc_amd import _lib
 from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-from mjmpc_amd.models.hand24 import hand24_raw
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["mjmpc_pf_batch_workspace_bytes", "mjmpc_pf_delta_batch", "mjmpc_pf_weights_batch", "mjmpc_pf_resample_batch",
                "mjmpc_pf_gather_shift_batch", "mjmpc_pf_finish_batch"]
 
@@ -24,93 +21,56 @@ def _kw(**over):
     return kw
 
 
-@pytest.fixture
-def no_engine(monkeypatch):
-    """Making an engine fails the test: every refusal must come first."""
-    from mjmpc_amd.envs import tree_engine
-
-    def refuse(*a, **k):
-        raise AssertionError("an engine was created before the settings were checked")
-    monkeypatch.setattr(tree_engine.TreeRolloutEngine, "__init__", refuse)
-
-
-@pytest.mark.parametrize("over", [
-    # what _check_common refuses (n_iters > 1 of the single path is not batched)
-    dict(n_iters=2), dict(n_iters=0), dict(sample_mode="sample"), dict(gamma=0.0), dict(dtype="f16"), dict(num_episodes=0),
-    dict(num_episodes=65536), dict(horizon=0), dict(num_particles=0), dict(filter_coeffs=[1.0, 0.0]),
-    dict(base_action="random"), dict(base_action="zeros"), dict(base_action="repeat", horizon=1),
+@pytest.mark.parametrize("over", bc.COMMON_REFUSED + [
+    # (n_iters > 1 of the single path is not batched)
+    dict(n_iters=0), dict(base_action="repeat", horizon=1), dict(seeds=[1, 2, 3, 4, 5]),
     # the controller's own values
     dict(lam=0.0), dict(lam=-1.0), dict(lam=[1.0, 1.0, 0.0, 1.0]), dict(cov_shift=-0.1), dict(cov_shift=[0.1, 0.0, -1e-9, 0.1]),
     dict(cov_resample=0.0), dict(cov_resample=-0.3), dict(cov_resample=[0.3, 0.3, 0.0, 0.3]),
     # per-episode arrays of the wrong length / shape
     dict(lam=[1.0] * 3), dict(cov_shift=np.zeros(5)), dict(cov_resample=np.ones((4, 2))),
-    dict(seeds=[1, 2, 3]), dict(seeds=7), dict(seeds=[1, 2, 3, -4]), dict(seeds=[1, 2, 3, 4, 5]),
-    # a model the tree engine refuses: RK4 beyond 16 dofs
-    dict(raw_model=dataclasses.replace(hand24_raw(), integrator="RK4")),
-], ids=lambda d: ",".join("%s=%s" % (k, type(v).__name__ if k == "raw_model" else v) for k, v in d.items()))
-def test_unsupported_settings_raise_before_any_engine(no_engine, over):
+    dict(raw_model=bc.rk4_hand()),
+], ids=bc.refused_id())
+def test_unsupported_settings_raise_before_any_engine(no_engine, over):     # noqa: F811
     from mjmpc_amd.control import BatchedPFMPC
     with pytest.raises(ValueError):
         BatchedPFMPC(**_kw(**over))
 
 
-def test_supported_settings_reach_the_engine(no_engine):
+def test_supported_settings_reach_the_engine(no_engine):                    # noqa: F811
     """The settings the batch runs pass the checks (and then get as far as making the engine); a zero cov_shift is one."""
     from mjmpc_amd.control import BatchedPFMPC
-    for over in (dict(), dict(cov_shift=0.0), dict(keep_stages=True), dict(filter_coeffs=[1.0, 0.0, 0.0]),
-                 dict(lam=[0.5, 1.0, 2.0, 4.0], cov_shift=[0.0, 0.01, 0.02, 0.03], cov_resample=[0.1, 0.2, 0.3, 0.4],
-                      base_action="repeat", dtype="f32", seeds=np.arange(4))):
-        with pytest.raises(AssertionError, match="engine was created"):
-            BatchedPFMPC(**_kw(**over))
+    bc.check_reaches_the_engine(BatchedPFMPC, [
+        _kw(), _kw(cov_shift=0.0), _kw(keep_stages=True), _kw(filter_coeffs=[1.0, 0.0, 0.0]),
+        _kw(lam=[0.5, 1.0, 2.0, 4.0], cov_shift=[0.0, 0.01, 0.02, 0.03], cov_resample=[0.1, 0.2, 0.3, 0.4],
+            base_action="repeat", dtype="f32", seeds=np.arange(4))])
 
 
 def test_per_episode_broadcasting(monkeypatch):
     """``lam``, ``cov_shift`` and ``cov_resample``: one value for every episode or one per episode, through ``_per_episode``."""
     from mjmpc_amd.control import BatchedPFMPC, batched
-    seen = {}
-
-    def stop(self, raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean):
-        seen.update(E=E, H=H, P=P, mean=init_mean)
-        raise RuntimeError("far enough")
-    monkeypatch.setattr(batched._EpisodeBatch, "_setup", stop)
-    with pytest.raises(RuntimeError, match="far enough"):
-        BatchedPFMPC(**_kw(lam=[0.5, 1.0, 2.0, 4.0], cov_shift=0.0, cov_resample=np.array([0.1, 0.2, 0.3, 0.4])))
-    assert (seen["E"], seen["H"], seen["P"]) == (4, 8, 64)
-    assert seen["mean"].shape == (4, 8, 6) and not seen["mean"].any()        # (the means start at zero)
+    seen = bc.stop_at_setup(monkeypatch)
+    bc.check_stops_at_setup(BatchedPFMPC, _kw(lam=[0.5, 1.0, 2.0, 4.0], cov_shift=0.0, cov_resample=np.array([0.1, 0.2, 0.3, 0.4])),
+                            seen, 4, 8, 64)
+    assert seen["init_mean"].shape == (4, 8, 6) and not seen["init_mean"].any()        # (the means start at zero)
     for name in ("lam", "cov_shift", "cov_resample"):
-        a = batched._per_episode(name, 0.45, 4)
-        assert a.shape == (4,) and a.dtype == np.float64 and np.all(a == 0.45)
-        a = batched._per_episode(name, [0.1, 0.2, 0.3, 0.4], 4)
-        assert a.tolist() == [0.1, 0.2, 0.3, 0.4]
+        bc.check_per_episode(name, 0.45, [0.1, 0.2, 0.3, 0.4])
         for bad in ([0.1, 0.2], np.zeros((4, 1)), np.zeros((2, 4))):
             with pytest.raises(ValueError, match=name):
                 batched._per_episode(name, bad, 4)
 
 
 def test_batched_pfmpc_is_exported():
-    import mjmpc_amd.control as control
-    from mjmpc_amd.control import BatchedCEM, BatchedMPPI, BatchedPFMPC
-    from mjmpc_amd.control.batched import _EpisodeBatch
-    assert "BatchedPFMPC" in control.__all__
-    assert issubclass(BatchedPFMPC, _EpisodeBatch) and not issubclass(BatchedPFMPC, (BatchedMPPI, BatchedCEM))
-    for name in ("set_states", "get_states", "mean_action", "action_samples", "last_step", "reset", "step", "run", "close",
-                 "on_env_reset", "randomize_dynamics", "clear_dynamics"):
-        assert hasattr(BatchedPFMPC, name), name
-    # the base class's parts are inherited, not copied
-    for name in ("set_states", "get_states", "run", "_env_step", "randomize_dynamics", "clear_dynamics", "close"):
-        assert getattr(BatchedPFMPC, name) is getattr(_EpisodeBatch, name), name
+    from mjmpc_amd.control import BatchedCEM, BatchedMPPI
+    cls = bc.check_exported("BatchedPFMPC", ("set_states", "get_states", "mean_action", "action_samples", "last_step", "reset",
+                                             "step", "run", "close", "on_env_reset", "randomize_dynamics", "clear_dynamics"),
+                            # the base class's parts are inherited, not copied
+                            ("set_states", "get_states", "run", "_env_step", "randomize_dynamics", "clear_dynamics", "close"))
+    assert not issubclass(cls, (BatchedMPPI, BatchedCEM))
 
 
 def test_new_entry_points_are_declared_bound_and_built():
-    with open(os.path.join(ROOT, "include", "mjmpc_amd.h")) as f:
-        header = f.read()
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(lib, name) is not None, name
-    assert re.search(r"#define\s+MJMPC_ABI_VERSION\s+4\b", header)          # additions do not move the version
-    assert _lib.ABI_VERSION == 4 and lib.mjmpc_abi_version() == 4
+    bc.check_entry_points(NEW_SYMBOLS, abi=4)
 
 
 def test_batch_workspace_is_e_rows_of_the_single_layout():

@@ -13,22 +13,15 @@ import ctypes
 import numpy as np
 import pytest
 
+import batched_cases as bc
 import pfmpc_cases as pc
+from batched_cases import FILT, _cheetah_states, _torch, _vp
+from batched_cases import cheetah as _cheetah
 
 pytestmark = pytest.mark.gpu
 
-FILT = [0.25, 0.8, 0.0]
 TOL = dict(rtol=1e-12, atol=1e-12)      # the controller-update tolerance of tests/test_controllers_gpu.py
 MODES = {"null": 0, "repeat": 1}
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _vp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def _dev(x):
@@ -38,10 +31,6 @@ def _dev(x):
 def _stream():
     torch = _torch()
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _per(v, e):
-    return v[e] if np.ndim(v) > 0 else v
 
 
 # ---------------------------------------------------------------------------------------------------------- the C ABI alone
@@ -197,114 +186,15 @@ def test_resampling_rows_return_the_indices_of_the_host_search():
 
 
 # ---------------------------------------------------------------------------------------------------------- closed loops
-def _single(raw, state, seed, P, H, T, cov_shift, cov_resample, lam, dtype, gamma=0.99, base_action="null", K=1, cfg=None,
-            dyn_seed=None):
-    """One episode on the single-episode device path -> (actions [T][A], costs [T], next obs [T][d_obs], mean, set, state)."""
-    torch = _torch()
-    from mjmpc_amd.control import PFMPC
-    from mjmpc_amd.control.controller import resident_state
-    from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
-    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    eng = TreeRolloutEngine(raw, dtype=dtype, num_shards=K)
-    if cfg is not None:
-        eng.randomize_dynamics(cfg, dyn_seed)
-        eng.set_real_env_model("nominal")
-    eng.set_env_state(dict(state))
-    c = PFMPC(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, cov_shift=cov_shift,
-              cov_resample=cov_resample, base_action=base_action, lam=lam, num_particles=P, gamma=gamma, n_iters=1,
-              action_lows=eng.action_lows, action_highs=eng.action_highs, filter_coeffs=FILT, seed=seed, noise_mode="device")
-    c.rollout_fn = make_device_rollout_fn(eng)
-    c.set_sim_state_fn = resident_state
-    c.set_post_step(eng.step_state)
-    acts, costs, nobs = [], [], []
-    for _ in range(T):
-        a, _ = c.optimize({"resident": True}, hotstart=True)
-        torch.cuda.synchronize()
-        acts.append(np.array(a, np.float64))
-        costs.append(eng._buf["step_cost"].cpu().numpy()[0])
-        nobs.append(eng._buf["step_obs"].cpu().numpy().copy())
-    mean, final_set = c.mean_action.cpu().numpy().copy(), c.action_samples.cpu().numpy().copy()
-    st = eng.get_state_device()
-    assert eng.env_resets() == 0, "the single path's real env reset"
-    assert eng.solver_failures() == 0
-    eng.close()
-    return np.array(acts), np.array(costs), np.array(nobs), mean, final_set, st
-
-
-def _batch(raw, states, seeds, P, H, T, cov_shift, cov_resample, lam, dtype, gamma=0.99, base_action="null", K=1, cfg=None,
-           dyn_seed=None):
-    from mjmpc_amd.control import BatchedPFMPC
-    b = BatchedPFMPC(raw, len(states), H, P, cov_shift, cov_resample, lam, gamma, FILT, base_action, seeds, dtype=dtype)
-    b.set_states([dict(s) for s in states])
-    if cfg is not None:
-        b.randomize_dynamics(cfg, dyn_seed, K)
-    acts, costs, nobs = b.run(T)
-    out = acts, costs, nobs, b.mean_action, b.action_samples, b.get_states()
-    assert b.num_steps == T
-    assert b.engine.env_resets() == 0, "a real env of the batch reset"
-    assert b.engine.solver_failures() == 0
-    b.close()
-    return out
-
-
-def _qpos_qvel(st):
-    return (st["qpos"], st["qvel"]) if "qpos" in st else (st["qp"], st["qv"])
+PF = bc.case("BatchedPFMPC", "PFMPC", ("cov_shift", "cov_resample", "lam"), lambda dtype: dict(), gamma=0.99, resident=True,
+             extra=("action_samples", "action_samples"), solver=True)
 
 
 def _check_against_singles(raw, states, seeds, P, H, T, cov_shift, cov_resample, lam, dtype, **kw):
-    E = len(states)
-    acts, costs, nobs, means, sets, fin = _batch(raw, states, seeds, P, H, T, cov_shift, cov_resample, lam, dtype, **kw)
-    assert acts.shape[:2] == (T, E) and costs.shape == (T, E) and means.shape[0] == E and len(fin) == E
-    assert sets.shape[:3] == (E, P, H)
-    assert np.all(np.isfinite(acts)) and np.all(np.isfinite(costs)) and np.abs(acts).max() > 0
-    for e in range(E):
-        skw = dict(kw)
-        if isinstance(skw.get("dyn_seed"), (list, tuple)):
-            skw["dyn_seed"] = skw["dyn_seed"][e]
-        a1, c1, o1, m1, x1, s1 = _single(raw, states[e], seeds[e], P, H, T, _per(cov_shift, e), _per(cov_resample, e),
-                                         _per(lam, e), dtype, **skw)
-        assert np.all(np.isfinite(a1)) and np.all(np.isfinite(c1))
-        assert np.array_equal(acts[:, e], a1), "episode %d: actions differ (max %.3g)" % (e, np.abs(acts[:, e] - a1).max())
-        assert np.array_equal(costs[:, e], c1), "episode %d: real-env costs differ" % e
-        assert np.array_equal(nobs[:, e], o1), "episode %d: next observations differ" % e
-        assert np.array_equal(means[e], m1), "episode %d: final mean differs" % e
-        assert np.array_equal(sets[e], x1), "episode %d: final set differs" % e
-        for x, y in zip(_qpos_qvel(fin[e]), _qpos_qvel(s1)):
-            assert np.array_equal(x, y), "episode %d: final state differs" % e
-    return acts
-
-
-_CHEETAH = {}
-
-
-def _cheetah_states(E):
-    """Start states of the env class's seeded resets, made once and shared (read-only)."""
-    if E not in _CHEETAH:
-        from mjmpc_amd.envs.locomotion_env import HalfCheetahEnv
-        env = HalfCheetahEnv()
-        out = []
-        for i in range(E):
-            env.reset(seed=123 + i * 12345)
-            out.append(env.get_env_state())
-        env.engine.close()
-        _CHEETAH[E] = out
-    return _CHEETAH[E]
-
-
-def _cheetah():
-    from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-    return half_cheetah_raw()
-
-
-def _synthetic_states(name, E, seed=0):
-    """The env class's start state with a small per-episode velocity offset (the synthetic envs start from one state)."""
-    from mjmpc_amd.envs.synthetic_env import start_state
-    from mjmpc_amd.models.synthetic import synthetic_raw
-    raw = synthetic_raw(name)
-    st = start_state(name, raw)
-    rng = np.random.RandomState(seed)
-    return raw, [dict(qp=st["qp"].copy(), qv=st["qv"] + 0.05 * rng.randn(st["qv"].size), target_pos=st["target_pos"].copy())
-                 for _ in range(E)]
+    out = bc.check_against_singles(PF, raw, states, seeds, P, H, T, (cov_shift, cov_resample, lam), dtype, **kw)
+    assert out["extra"].shape[:3] == (len(states), P, H)
+    assert np.abs(out["acts"]).max() > 0
+    return out["acts"]
 
 
 SEEDS3 = [123 + i * 12345 for i in range(3)]
@@ -326,21 +216,11 @@ def test_base_action_repeat():
 def test_one_episode_and_permuted_episodes():
     raw = _cheetah()
     _check_against_singles(raw, _cheetah_states(1), [123], 100, 6, 5, 0.02, 0.3, 1.0, "f64")
-    states = _cheetah_states(3)
-    base = _batch(raw, states, SEEDS3, 100, 6, 5, SHIFT3, RESAMPLE3, LAM3, "f64")
-    perm = [2, 0, 1]
-    got = _batch(raw, [states[k] for k in perm], [SEEDS3[k] for k in perm], 100, 6, 5, SHIFT3[perm], RESAMPLE3[perm], LAM3[perm],
-                 "f64")
-    for i in range(3):
-        assert np.array_equal(got[i], base[i][:, perm])
-    assert np.array_equal(got[3], base[3][perm]) and np.array_equal(got[4], base[4][perm])
-    for k, e in enumerate(perm):
-        for x, y in zip(_qpos_qvel(got[5][k]), _qpos_qvel(base[5][e])):
-            assert np.array_equal(x, y)
+    bc.check_permutation(PF, raw, _cheetah_states(3), SEEDS3, 100, 6, 5, (SHIFT3, RESAMPLE3, LAM3), "f64", [2, 0, 1])
 
 
 def test_rk4_double_pendulum():
-    raw, states = _synthetic_states("double_pendulum", 2, seed=1)
+    raw, states = bc.synthetic_states("double_pendulum", 2, seed=1)
     assert raw.integrator == "RK4"
     _check_against_singles(raw, states, [21, 22], 64, 4, 3, [0.02, 0.05], 0.3, [1.0, 0.5], "f64")
 
@@ -348,7 +228,7 @@ def test_rk4_double_pendulum():
 def test_free_joint_tray():
     """The general instantiation of the rollout kernel: a model with a free joint (the tray's glass)."""
     from mjmpc_amd.models.compile_tree import compile_tree
-    raw, states = _synthetic_states("tray", 2)
+    raw, states = bc.synthetic_states("tray", 2)
     m = compile_tree(raw)
     assert m.nq > m.nv
     _check_against_singles(raw, states, [11, 12], 64, 4, 3, [0.02, 0.05], 0.3, [1.0, 0.5], "f64")

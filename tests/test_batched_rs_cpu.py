@@ -2,18 +2,15 @@
 broadcasts its per-episode settings as ``BatchedMPPI`` does, and its entry points are declared, bound, built and reject bad
 arguments."""
 import ctypes
-import dataclasses
-import os
-import re
 
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import no_engine  # noqa: F401
 from mjmpc_amd import _lib
 from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-from mjmpc_amd.models.hand24 import hand24_raw
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW_SYMBOLS = ["mjmpc_rs_batch_supported", "mjmpc_rs_update_batch"]
 E_BADARG = -1               # (MJMPC_E_BADARG of include/mjmpc_amd.h)
 
@@ -25,95 +22,57 @@ def _kw(**over):
     return kw
 
 
-@pytest.fixture
-def no_engine(monkeypatch):
-    """Making an engine fails the test: every refusal must come first."""
-    from mjmpc_amd.envs import tree_engine
-
-    def refuse(*a, **k):
-        raise AssertionError("an engine was created before the settings were checked")
-    monkeypatch.setattr(tree_engine.TreeRolloutEngine, "__init__", refuse)
-
-
-@pytest.mark.parametrize("over", [
-    dict(n_iters=2), dict(sample_mode="sample"), dict(use_zero_control_seq=True), dict(gamma=0.0),
-    dict(base_action="random"), dict(base_action="zeros"), dict(dtype="f16"), dict(num_episodes=0), dict(num_episodes=65536),
-    dict(horizon=0), dict(num_particles=0), dict(filter_coeffs=[1.0, 0.0]),
+@pytest.mark.parametrize("over", bc.COMMON_REFUSED + [
+    dict(use_zero_control_seq=True),
     # per-episode arrays of the wrong length / shape, and values random shooting cannot take
     dict(init_cov=[0.1] * 3), dict(step_size=np.ones(5)), dict(step_size=np.zeros((4, 2))), dict(init_mean=np.zeros((8, 5))),
-    dict(init_mean=np.zeros((3, 8, 6))), dict(seeds=[1, 2, 3]), dict(seeds=7), dict(seeds=[1, 2, 3, -4]),
+    dict(init_mean=np.zeros((3, 8, 6))),
     dict(init_cov=[0.3, 0.3, -1.0, 0.3]), dict(init_cov=0.0), dict(step_size=-0.1), dict(step_size=[1.0, 0.7, -0.4, 0.2]),
     dict(init_cov=float("nan")), dict(step_size=float("nan")),
-    # a model the tree engine refuses: RK4 beyond 16 dofs
-    dict(raw_model=dataclasses.replace(hand24_raw(), integrator="RK4")),
-], ids=lambda d: ",".join("%s=%s" % (k, type(v).__name__ if k in ("raw_model", "init_mean") else v) for k, v in d.items()))
-def test_unsupported_settings_raise_before_any_engine(no_engine, over):
+    dict(raw_model=bc.rk4_hand()),
+], ids=bc.refused_id(("raw_model", "init_mean")))
+def test_unsupported_settings_raise_before_any_engine(no_engine, over):     # noqa: F811
     from mjmpc_amd.control import BatchedRandomShooting
     with pytest.raises(ValueError):
         BatchedRandomShooting(**_kw(**over))
 
 
-def test_supported_settings_reach_the_engine(no_engine):
+def test_supported_settings_reach_the_engine(no_engine):                    # noqa: F811
     """The settings the batch runs pass the checks (and then get as far as making the engine)."""
     from mjmpc_amd.control import BatchedRandomShooting
-    for over in (dict(), dict(step_size=0.0), dict(step_size=1.0), dict(num_particles=50), dict(num_episodes=1, seeds=[9]),
-                 dict(init_cov=[0.1, 0.2, 0.3, 0.4], step_size=[1.0, 0.9, 0.8, 0.7], base_action="repeat", dtype="f32",
-                      seeds=np.arange(4), init_mean=np.zeros((4, 8, 6))),
-                 dict(init_mean=np.full((8, 6), 0.1))):
-        with pytest.raises(AssertionError, match="engine was created"):
-            BatchedRandomShooting(**_kw(**over))
+    bc.check_reaches_the_engine(BatchedRandomShooting, [
+        _kw(), _kw(step_size=0.0), _kw(step_size=1.0), _kw(num_particles=50), _kw(num_episodes=1, seeds=[9]),
+        _kw(init_cov=[0.1, 0.2, 0.3, 0.4], step_size=[1.0, 0.9, 0.8, 0.7], base_action="repeat", dtype="f32",
+            seeds=np.arange(4), init_mean=np.zeros((4, 8, 6))),
+        _kw(init_mean=np.full((8, 6), 0.1))])
 
 
 def test_per_episode_broadcasting(monkeypatch):
     """One value for every episode or one per episode, as they reach the batch's set-up."""
-    from mjmpc_amd.control import BatchedRandomShooting, batched
-    seen = {}
-
-    def stop(self, raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean):
-        seen.update(E=E, H=H, P=P, init_mean=init_mean)
-        raise RuntimeError("far enough")
-    monkeypatch.setattr(batched._EpisodeBatch, "_setup", stop)
+    from mjmpc_amd.control import BatchedRandomShooting
+    seen = bc.stop_at_setup(monkeypatch)
     for P in (64, 50, 1000):
-        with pytest.raises(RuntimeError, match="far enough"):
-            BatchedRandomShooting(**_kw(num_particles=P))
-        assert (seen["E"], seen["H"], seen["P"]) == (4, 8, P)
+        bc.check_stops_at_setup(BatchedRandomShooting, _kw(num_particles=P), seen, 4, 8, P)
         assert seen["init_mean"].shape == (4, 8, 6) and not seen["init_mean"].any()
     one = np.random.RandomState(0).uniform(-1, 1, (8, 6))
-    with pytest.raises(RuntimeError, match="far enough"):
-        BatchedRandomShooting(**_kw(init_mean=one))
+    bc.check_stops_at_setup(BatchedRandomShooting, _kw(init_mean=one), seen, 4, 8, 64)
     assert all(np.array_equal(seen["init_mean"][e], one) for e in range(4))
     each = np.random.RandomState(1).uniform(-1, 1, (4, 8, 6))
-    with pytest.raises(RuntimeError, match="far enough"):
-        BatchedRandomShooting(**_kw(init_mean=each))
+    bc.check_stops_at_setup(BatchedRandomShooting, _kw(init_mean=each), seen, 4, 8, 64)
     assert np.array_equal(seen["init_mean"], each)
-    a = batched._per_episode("step_size", 0.7, 4)
-    assert a.shape == (4,) and np.all(a == 0.7)
-    a = batched._per_episode("step_size", [1.0, 0.7, 0.4, 0.0], 4)
-    assert a.tolist() == [1.0, 0.7, 0.4, 0.0]
+    bc.check_per_episode("step_size", 0.7, [1.0, 0.7, 0.4, 0.0])
 
 
 def test_batched_random_shooting_is_exported():
-    import mjmpc_amd.control as control
-    from mjmpc_amd.control import BatchedRandomShooting
-    from mjmpc_amd.control.batched import _EpisodeBatch
-    assert "BatchedRandomShooting" in control.__all__
-    assert issubclass(BatchedRandomShooting, _EpisodeBatch)
-    for name in ("set_states", "get_states", "mean_action", "reset", "step", "run", "close", "on_env_reset",
-                 "randomize_dynamics", "clear_dynamics", "best_particle"):
-        assert hasattr(BatchedRandomShooting, name), name
-    # the base class's, unchanged
-    for name in ("run", "set_states", "get_states", "mean_action", "reset", "randomize_dynamics", "clear_dynamics", "close"):
-        assert getattr(BatchedRandomShooting, name) is getattr(_EpisodeBatch, name), name
+    bc.check_exported("BatchedRandomShooting",
+                      ("set_states", "get_states", "mean_action", "reset", "step", "run", "close", "on_env_reset",
+                       "randomize_dynamics", "clear_dynamics", "best_particle"),
+                      # the base class's, unchanged
+                      ("run", "set_states", "get_states", "mean_action", "reset", "randomize_dynamics", "clear_dynamics", "close"))
 
 
 def test_new_entry_points_are_declared_bound_and_built():
-    with open(os.path.join(ROOT, "include", "mjmpc_amd.h")) as f:
-        header = f.read()
-    lib = _lib.load()
-    for name in NEW_SYMBOLS:
-        assert re.search(r"\b%s\(" % name, header), name
-        assert name in _lib.SIGNATURES, name
-        assert getattr(lib, name) is not None, name
+    bc.check_entry_points(NEW_SYMBOLS)
 
 
 def test_supported_shapes():

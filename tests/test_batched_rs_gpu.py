@@ -16,133 +16,30 @@ import os
 import numpy as np
 import pytest
 
+import batched_cases as bc
+from batched_cases import FILT, ROOT, _cheetah_states, _torch, _vp
+from batched_cases import cheetah as _cheetah
+
 pytestmark = pytest.mark.gpu
 
-FILT = [0.25, 0.8, 0.0]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-
-def _torch():
-    import torch
-    return torch
-
-
-def _vp(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _per(v, e):
-    return v[e] if np.ndim(v) > 0 else v
-
-
-_SINGLES = {}
-
-
-def _single(raw, state, seed, P, H, T, step_size, init_cov, dtype, base_action="null", K=1, cfg=None, dyn_seed=None, key=None):
-    """One episode on the single-episode device path -> (actions [T][A], costs [T], next obs [T][d_obs], mean, state).
-    ``key``: names the model and the start state; runs with a key are kept and shared."""
-    full_key = None if key is None else (key, seed, P, H, T, float(step_size), float(init_cov), dtype, base_action, K,
-                                         repr(cfg), dyn_seed)
-    if full_key in _SINGLES:
-        return _SINGLES[full_key]
-    torch = _torch()
-    from mjmpc_amd.control import RandomShooting
-    from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
-    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    eng = TreeRolloutEngine(raw, dtype=dtype, num_shards=K)
-    if cfg is not None:
-        eng.randomize_dynamics(cfg, dyn_seed)
-        eng.set_real_env_model("nominal")
-    eng.set_env_state(dict(state))
-    A = eng.d_action
-    c = RandomShooting(d_state=eng.d_state, d_obs=eng.d_obs, d_action=A, horizon=H, init_cov=init_cov, base_action=base_action,
-                       num_particles=P, step_size=step_size, gamma=1.0, n_iters=1, action_lows=eng.action_lows,
-                       action_highs=eng.action_highs, filter_coeffs=FILT, seed=seed, noise_mode="device", noise_dtype=dtype)
-    c.rollout_fn = make_device_rollout_fn(eng)
-    c.set_sim_state_fn = lambda s: None
-    c.enable_graph(post_step=eng.step_state)
+def _takes_q0_from_the_rollout(c):
     # the branch of the device iteration that takes q0 from the rollout launch (draw, fused rollout, rs_best + rs_combine, tail)
     assert c._wants_q0() and c.noise_mode == "device" and hasattr(c._rollout_fn, "fused")
     assert not c.dev.gamma_zero and not c.use_zero_control_seq
-    acts, costs, nobs = [], [], []
-    for _ in range(T):
-        a, _ = c.optimize(None)
-        torch.cuda.synchronize()
-        acts.append(np.array(a, np.float64))
-        costs.append(eng._buf["step_cost"].cpu().numpy()[0])
-        nobs.append(eng._buf["step_obs"].cpu().numpy().copy())
-    mean = np.array(c.mean_action)
-    st = eng.get_state_device()
-    assert eng.env_resets() == 0, "the single path's real env reset"
-    eng.close()
-    out = np.array(acts), np.array(costs), np.array(nobs), mean, st
-    if full_key is not None:
-        _SINGLES[full_key] = out
-    return out
 
 
-def _batch(raw, states, seeds, P, H, T, step_size, init_cov, dtype, base_action="null", K=1, cfg=None, dyn_seed=None):
-    from mjmpc_amd.control import BatchedRandomShooting
-    b = BatchedRandomShooting(raw, len(states), H, P, step_size, init_cov, 1.0, FILT, base_action, seeds, dtype=dtype)
-    b.set_states([dict(s) for s in states])
-    if cfg is not None:
-        b.randomize_dynamics(cfg, dyn_seed, K)
-    acts, costs, nobs = b.run(T)
-    out = acts, costs, nobs, b.mean_action, b.get_states()
-    assert b.engine.env_resets() == 0, "a real env of the batch reset"
-    b.close()
-    return out
+RS = bc.case("BatchedRandomShooting", "RandomShooting", ("step_size", "init_cov"), lambda dtype: dict(noise_dtype=dtype),
+             before=_takes_q0_from_the_rollout)
 
 
-def _qpos_qvel(st):
-    return (st["qpos"], st["qvel"]) if "qpos" in st else (st["qp"], st["qv"])
-
-
-def _check_against_singles(raw, states, seeds, P, H, T, step_size, init_cov, dtype, keys=None, **kw):
-    E = len(states)
-    acts, costs, nobs, means, fin = _batch(raw, states, seeds, P, H, T, step_size, init_cov, dtype, **kw)
-    assert acts.shape[:2] == (T, E) and costs.shape == (T, E) and means.shape[0] == E and len(fin) == E
-    assert np.all(np.isfinite(acts)) and np.all(np.isfinite(costs))
-    for e in range(E):
-        skw = dict(kw)
-        if isinstance(skw.get("dyn_seed"), (list, tuple)):
-            skw["dyn_seed"] = skw["dyn_seed"][e]
-        a1, c1, o1, m1, s1 = _single(raw, states[e], seeds[e], P, H, T, _per(step_size, e), _per(init_cov, e), dtype,
-                                     key=None if keys is None else keys[e], **skw)
-        assert np.all(np.isfinite(a1)) and np.all(np.isfinite(c1))
-        assert np.array_equal(acts[:, e], a1), "episode %d: actions differ (max %.3g)" % (e, np.abs(acts[:, e] - a1).max())
-        assert np.array_equal(costs[:, e], c1), "episode %d: real-env costs differ" % e
-        assert np.array_equal(nobs[:, e], o1), "episode %d: next observations differ" % e
-        assert np.array_equal(means[e], m1), "episode %d: final mean differs" % e
-        for x, y in zip(_qpos_qvel(fin[e]), _qpos_qvel(s1)):
-            assert np.array_equal(x, y), "episode %d: final state differs" % e
-    return acts, costs
-
-
-_CHEETAH = {}
-
-
-def _cheetah_states(E):
-    """Start states of the env class's seeded resets (state i does not depend on E), made once and shared (read-only)."""
-    if E not in _CHEETAH:
-        from mjmpc_amd.envs.locomotion_env import HalfCheetahEnv
-        env = HalfCheetahEnv()
-        out = []
-        for i in range(E):
-            env.reset(seed=123 + i * 12345)
-            out.append(env.get_env_state())
-        env.engine.close()
-        _CHEETAH[E] = out
-    return _CHEETAH[E]
+def _check_against_singles(raw, states, seeds, P, H, T, step_size, init_cov, dtype, **kw):
+    out = bc.check_against_singles(RS, raw, states, seeds, P, H, T, (step_size, init_cov), dtype, **kw)
+    return out["acts"], out["costs"]
 
 
 def _cheetah_keys(E):
     return [("half_cheetah", i) for i in range(E)]
-
-
-def _cheetah():
-    from mjmpc_amd.models.half_cheetah import half_cheetah_raw
-    return half_cheetah_raw()
 
 
 SEEDS = [123 + i * 12345 for i in range(3)]
@@ -180,32 +77,16 @@ def test_one_episode():
 
 
 def test_permuting_the_episodes_permutes_the_results():
-    raw, E = _cheetah(), 3
-    states = _cheetah_states(E)
     step, cov = np.array([1.0, 0.7, 0.4]), np.array([0.2, 0.3, 0.5])
-    base = _batch(raw, states, SEEDS, 64, 8, 6, step, cov, "f64")
-    perm = [2, 0, 1]
-    got = _batch(raw, [states[k] for k in perm], [SEEDS[k] for k in perm], 64, 8, 6, step[perm], cov[perm], "f64")
-    for i in range(3):
-        assert np.array_equal(got[i], base[i][:, perm])
-    assert np.array_equal(got[3], base[3][perm])
-    for k, e in enumerate(perm):
-        for x, y in zip(_qpos_qvel(got[4][k]), _qpos_qvel(base[4][e])):
-            assert np.array_equal(x, y)
+    bc.check_permutation(RS, _cheetah(), _cheetah_states(3), SEEDS, 64, 8, 6, (step, cov), "f64", [2, 0, 1])
 
 
 def test_free_joint_model():
     """A general instantiation of the rollout kernel: the tray, whose glass has a free joint."""
-    from mjmpc_amd.envs.synthetic_env import start_state
     from mjmpc_amd.models.compile_tree import compile_tree
-    from mjmpc_amd.models.synthetic import synthetic_raw
-    raw = synthetic_raw("tray")
+    raw, states = bc.synthetic_states("tray", 2)
     m = compile_tree(raw)
     assert m.nq > m.nv
-    st = start_state("tray", raw)
-    rng = np.random.RandomState(0)
-    states = [dict(qp=st["qp"].copy(), qv=st["qv"] + 0.05 * rng.randn(st["qv"].size), target_pos=st["target_pos"].copy())
-              for _ in range(2)]
     _check_against_singles(raw, states, [11, 12], 32, 4, 3, 0.7, 0.3, "f64")
 
 
