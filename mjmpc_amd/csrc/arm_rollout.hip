@@ -230,11 +230,12 @@ struct Dense {
     T d[MAX_LINKS];     // diagonal; 1 / pivot after factor()
     static __device__ __forceinline__ constexpr int ix(int i, int j) { return i * (i - 1) / 2 + j; }
 
+    // (the tile holds the UPPER triangle only - tile_store: a_ij = M[j][i] for j < i)
     __device__ __forceinline__ void load(const T* tile, const T* diag) {
 #pragma unroll
         for (int i = 1; i < MAX_LINKS; ++i)
 #pragma unroll
-            for (int j = 0; j < i; ++j) a[ix(i, j)] = tile[i * LANES + j];
+            for (int j = 0; j < i; ++j) a[ix(i, j)] = tile[j * LANES + i];
 #pragma unroll
         for (int i = 0; i < MAX_LINKS; ++i) d[i] = diag[i];
     }
@@ -284,8 +285,8 @@ struct Dense {
 constexpr int V_DH = LANES * LANES, V_RH = V_DH + LANES, V_DE = V_RH + LANES, V_RE = V_DE + LANES, V_XH = V_RE + LANES,
               V_XE = V_XH + LANES, V_JC = V_XE + LANES, V_TAU = V_JC + LANES, V_EI = V_TAU + LANES,
               PSTRIDE = V_EI + LANES * LANES + 4,      // V_EI: (M + h B)^-1, DUO only
-              // the limit rows the DYN wave hands to the SOLVE wave at E1 travel in vectors the SOLVE wave only
-              // (re)writes after it has taken them, and nobody touches between E3 and E1
+              // flag shapes: the limit rows QDYN / QAUX hand to the solving wave travel in vectors that wave only
+              // (re)writes after it has taken them, and nobody touches between two substeps
               V_LS = V_XH, V_LD = V_DH, V_LA = V_RH;
 
 // u_i += sum_k W[k][i] q_k + W[nv+k][i] v_k   (the joint part of clw^T obs), link values by DPP broadcast
@@ -309,6 +310,25 @@ __device__ __forceinline__ void mass_diagonals(const T* sw, const T* sv, const T
         d[S] = dot(sw, fn) + dot(sv, ff);
     }
     if constexpr (S + 1 < MAX_LINKS) mass_diagonals<S + 1, T>(sw, sv, Fn, Ff, d);
+}
+
+// My row of the mass matrix's upper triangle into the particle's 8x8 tile: lane i holds M[i][i + s] in d[s], contiguous from the
+// diagonal, so the diagonals S0 <= s < S1 go out as ONE run of stores at [i][i + s] (the compiler pairs them), the same run for
+// every link.  Past column 7 a run falls into the head of the next row - its lower triangle, which nobody reads (Dense::load
+// and xj_line_search take M[i][j], i > j, from [j][i]; the spare lane of xj_line_search reads column 7 - the products with the
+// massless spare link, zeros, and the never-written [0][7], zero since the launch began - for a row whose step is zero) - with the zeros shl_raw filled in past the end of the chain.  Only
+// the spare link stays out: its run would leave the tile (V_DH follows it, which other waves write meanwhile).
+// (Mirrored stores, each diagonal under its own lane mask - six exec-masked regions, their masks parked in SGPRs - were 13 LDS
+// stores and ~25 more instructions per substep.  Redirecting the spare link's run instead of masking it crashes this
+// compiler's register allocator on one f32 instantiation.)
+template <int S0, int S1, typename T>
+__device__ __forceinline__ void tile_store(const T* d, int l8, T* ldsM) {
+    static_assert(S0 >= 0 && S1 <= MAX_LINKS, "d[] holds the diagonals 0 ... MAX_LINKS - 1");
+    T* row = ldsM + l8 * (LANES + 1);
+    if (l8 < MAX_LINKS) {
+#pragma unroll
+        for (int sft = S0; sft < S1; ++sft) row[sft] = d[sft];
+    }
 }
 
 struct ArmInts {            // wave-uniform integers (SGPRs)
@@ -454,13 +474,7 @@ __device__ __forceinline__ T mass_matrix_tile(const LinkFrame<T>& L, int l8, T* 
         for (int k = 0; k < 3; ++k) { Fn[k] += t1[k]; Ff[k] = mc * sv[k] - t2[k]; }
         mass_diagonals<0, T>(sw, sv, Fn, Ff, d);
     }
-#pragma unroll
-    for (int sft = 0; sft < MAX_LINKS; ++sft) {
-        if (l8 + sft < MAX_LINKS) {
-            ldsM[l8 * LANES + l8 + sft] = d[sft];
-            ldsM[(l8 + sft) * LANES + l8] = d[sft];
-        }
-    }
+    tile_store<0, MAX_LINKS>(d, l8, ldsM);
     return d[0];
 }
 
@@ -495,13 +509,7 @@ __device__ __forceinline__ T mass_matrix_tile_part(const LinkFrame<T>& L, int l8
     diag_s(std::integral_constant<int, 0>()); diag_s(std::integral_constant<int, 1>()); diag_s(std::integral_constant<int, 2>());
     diag_s(std::integral_constant<int, 3>()); diag_s(std::integral_constant<int, 4>()); diag_s(std::integral_constant<int, 5>());
     diag_s(std::integral_constant<int, 6>());
-#pragma unroll
-    for (int sft = S0; sft < S1; ++sft) {
-        if (l8 + sft < MAX_LINKS) {
-            ldsM[l8 * LANES + l8 + sft] = d[sft];
-            ldsM[(l8 + sft) * LANES + l8] = d[sft];
-        }
-    }
+    tile_store<S0, S1>(d, l8, ldsM);
     return d[0];
 }
 
@@ -664,7 +672,7 @@ __device__ __forceinline__ T xj_line_search(const MT& M, T* ldsM, int l8, T a_pr
     T Ma = M.link(O_ARMATURE) * a_prev, Md = M.link(O_ARMATURE) * d;       // rows of M x (the tile holds M without the armature)
 #pragma unroll
     for (int j = 0; j < MAX_LINKS; ++j) {
-        const T m = ldsM[l8 * LANES + j];
+        const T m = ldsM[j < l8 ? j * LANES + l8 : l8 * LANES + j];        // (the tile holds the upper triangle)
         Ma += m * ldsM[V_XH + j];
         Md += m * ldsM[V_XE + j];
     }
@@ -722,9 +730,11 @@ __device__ __forceinline__ void active_set(T aw, T sig, T aref, T jc, T arefc, b
     }
 }
 
-// DUO launches: which wave evaluates the joint-limit rows (see arm_front)
+// DUO launches: the SOLVE wave evaluates the joint-limit rows (a function of q and v alone) BEFORE E1, in the slack it has
+// there, and takes E2 after its first solve and active-set test (see arm_front).  f64 only: in f32, whose scans are single
+// instructions, neither wave has that slack - its SOLVE wave evaluates the rows after E1 and takes E2 after the factorisation.
 template <typename T>
-__device__ __forceinline__ constexpr bool rows_by_dyn() { return sizeof(T) == 8; }
+__device__ __forceinline__ constexpr bool rows_before_e1() { return sizeof(T) == 8; }
 
 // joint-limit row of my dof (MuJoCo mj_instantiateLimit, strict dist < margin(=0)): sig = +-1 (0: no row), and - when
 // some lane of the wavefront has a row - its regulariser D = 1 / R and reference acceleration
@@ -853,18 +863,7 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
         // 5. smooth force: -bias + passive damping + motor, handed to the SOLVE wave
         const T bias = bias_force(M, L, v, l8);
         ldsM[V_TAU + l8] = -bias - M.link(O_DAMPING) * v + tau_act;
-        // the joint-limit rows too (a function of q and v alone): this wave reaches E1 ~700 cycles before the SOLVE
-        // wave, which used to spend ~800 on them right after it
-        // (f64 only: 181 -> 176.5 us per 4096 x 32 launch; in f32, whose scans are single instructions, the DYN wave has
-        // no such slack and the move costs 3 %)
-        if constexpr (rows_by_dyn<T>()) {
-            T sg, Dl, al;
-            limit_row(M, q, v, sg, Dl, al);
-            ldsM[V_LS + l8] = sg;
-            ldsM[V_LD + l8] = Dl;
-            ldsM[V_LA + l8] = al;
-        }
-        ST.mark(2);     // velocities, bias forces, limit rows
+        ST.mark(2);     // velocities, bias forces
         duo_barrier();                                  // E1: tau out; mass-matrix tile and Euler diagonal in
         ST.mark(3);
         // 8'. explicit inverse of the Euler matrix M + h B while the SOLVE wave works on the constraints: every lane
@@ -895,6 +894,17 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
     if constexpr (ROLE == SOLO) LDS_WAVE_SYNC();
     ST.mark(4);         // (bias forces,) composite inertia, mass matrix, tile
 
+    // 6. constraint rows.  Limits - SOLVE (f64): here, before E1, behind the tile's stores: the DYN wave, whose velocities and
+    // bias forces take longer than the mass matrix, is the later one at E1 (profiles/r06_arm_phase_clocks_4096.txt)
+    T sig = T(0), dist = T(0), D = T(0), aref = T(0);
+    bool inst = false;
+    constexpr bool rows_early = ROLE == SOLVE && rows_before_e1<T>();
+    if constexpr (rows_early) {
+        limit_row(M, q, v, sig, D, aref);
+        inst = sig != T(0);
+        ST.mark(2);     // limit rows
+    }
+
     // 5. smooth force: -bias + passive damping + motor (SOLVE: arrives from the DYN wave at E1)
     T tau = -bias - damping * v + tau_act;
     if constexpr (ROLE == SOLVE) {
@@ -904,19 +914,12 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
     }
     T ei[MAX_LINKS];            // SOLVE: my row of (M + h B)^-1 (read once the DYN wave has published it)
 
-    // 6. constraint rows.  Limits (SOLVE: evaluated by the DYN wave before E1)
-    T sig = T(0), dist = T(0), D = T(0), aref = T(0);
-    bool inst = false;
-    constexpr bool rows_from_dyn = ROLE == SOLVE && rows_by_dyn<T>();
-    if constexpr (rows_from_dyn) {
-        sig = ldsM[V_LS + l8];
-        D = ldsM[V_LD + l8];
-        aref = ldsM[V_LA + l8];
-        inst = sig != T(0);
-    } else if (M.link(O_LIMITED) != T(0)) {
-        T dlo = q - M.link(O_RANGE_LO), dhi = M.link(O_RANGE_HI) - q;
-        if (dlo < T(0)) { sig = T(1); dist = dlo; inst = true; }
-        else if (dhi < T(0)) { sig = T(-1); dist = dhi; inst = true; }
+    if constexpr (!rows_early) {
+        if (M.link(O_LIMITED) != T(0)) {
+            T dlo = q - M.link(O_RANGE_LO), dhi = M.link(O_RANGE_HI) - q;
+            if (dlo < T(0)) { sig = T(1); dist = dlo; inst = true; }
+            else if (dhi < T(0)) { sig = T(-1); dist = dhi; inst = true; }
+        }
     }
     // plane-sphere contact (condim 1): mjc_PlaneSphere + mj_instantiateContact
     bool cinst = false;
@@ -937,14 +940,14 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
     FlossRow<T> fl = floss_row(M, v, rows);             // (XJ: my dof's friction-loss row; otherwise empty)
     const bool any_rows = __any(inst || cinst || (XJ && fl.f > T(0)));
     if (!any_rows) rows = 0;
-    if constexpr (!rows_from_dyn) {
+    if constexpr (!rows_early) {
         if (any_rows) {
             row_params(M, dist, M.link(O_DOF_INVW), sig * v, D, aref);
             D = inst ? D : T(0);
             aref = inst ? aref : T(0);
         }
     }
-    ST.mark(5);         // constraint rows
+    ST.mark(5);         // constraint rows (SOLVE, f64: the contact row, any rows at all)
     // initial active set: a row that existed in the previous substep keeps its state, a new row is assumed
     // active (it appears because the joint moves into its limit); `rows` = inst | act<<1 | cinst<<2 | cact<<3
     // of the previous substep
@@ -990,7 +993,7 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
                 for (int i = 0; i < MAX_LINKS; ++i) col[i] = (i == l8) ? T(1) : T(0);
                 F.solve(col);
                 ST.mark(it == 0 ? 6 : 9);               // factorisation + inverse / further iterations
-                if (it == 0 && !rows_by_dyn<T>()) {     // (E2 where round 2 had it: this wave arrives ~2000 cycles after E1)
+                if (it == 0 && !rows_before_e1<T>()) {  // (E2 where round 2 had it: this wave arrives ~2000 cycles after E1)
                     duo_barrier();
 #pragma unroll
                     for (int i = 0; i < MAX_LINKS; ++i) ei[i] = ldsM[V_EI + l8 * LANES + i];
@@ -1015,12 +1018,12 @@ __device__ __forceinline__ void arm_front(const MT& M, const ArmInts& I, T& q, T
                     fl.z = z2;
                     changed = changed || fflip;
                 }
-                // E2: the DYN wave needs ~1000 cycles after E1 for (M + h B)^-1; with the limit rows arriving from it
+                // E2: the DYN wave needs ~1000 cycles after E1 for (M + h B)^-1; with the limit rows evaluated before E1
                 // this wave gets HERE in about as many (after the first factorisation it would still wait ~400).  Taking
                 // the rendezvous inside the first iteration rather than at the end of the substep leaves only E3
                 // between the last Newton iteration and the integration.  (E2 after the iterations instead: measured in round 4,
                 // 0.1775 -> 0.186 ms per 4096 x 32 f64 launch, and removed.)
-                if (it == 0 && rows_by_dyn<T>()) {
+                if (it == 0 && rows_before_e1<T>()) {
                     duo_barrier();
 #pragma unroll
                     for (int i = 0; i < MAX_LINKS; ++i) ei[i] = ldsM[V_EI + l8 * LANES + i];   // my row of (M + h B)^-1, early
@@ -1749,8 +1752,16 @@ __device__ __forceinline__ void mono_record(double lam, double* __restrict__ rec
 // latency of the record loads.  Sharded runs (mo.record): the rows of this GPU's record {max, S, W} instead.
 constexpr int MAX_A = 8;
 constexpr int FIN_CHUNK = 4;        // records per thread in flight
+// (The extended-joint build states what the launch amounts to anyway - H workgroups of two waves: at most one wave per SIMD.
+// Without the bound this compiler's register allocator crashes on its f64 instantiation under the iterative-ilp scheduler,
+// and the whole source would fall back to the next scheduler of build.py's list.)
+#ifdef MJMPC_ARM_XJ
+#define MJMPC_FINISH_WAVES __attribute__((amdgpu_waves_per_eu(1, 1)))
+#else
+#define MJMPC_FINISH_WAVES
+#endif
 template <typename T>
-__global__ __launch_bounds__(128) void arm_mppi_finish_kernel(const T* __restrict__ model, const double* __restrict__ recs, long n_rec,
+__global__ __launch_bounds__(128) MJMPC_FINISH_WAVES void arm_mppi_finish_kernel(const T* __restrict__ model, const double* __restrict__ recs, long n_rec,
                                                               int H, int A, const double* __restrict__ mean_in,
                                                               double* __restrict__ mean_out, const MonoStep mo,
                                                               int env_step, unsigned* diag) {

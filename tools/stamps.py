@@ -18,7 +18,7 @@ def build():
     subprocess.check_call(cmd)
 
 
-NAMES = ["kinematics", "link frames", "velocities+bias (DYN)", "wait A (DYN) / tiles (QUAD)", "CRBA+tile", "rows", "factor #1",
+NAMES = ["kinematics", "link frames", "velocities+bias (DYN) / limit rows (SOLVE)", "wait A (DYN) / tiles (QUAD)", "CRBA+tile", "rows", "factor #1",
          "wait A (SOLVE) / tau (QUAD)", "solve #1 + check", "more Newton iterations", "force + Euler solve", "records (DYN)", "wait B / X",
          "integrate", "obs records / loop | EI wait, rows (flags)", "EI wait, no rows (flags)"]
 
