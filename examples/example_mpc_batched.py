@@ -1,9 +1,9 @@
 #!/usr/bin/env python
-"""The config's ``n_episodes`` MPPI, CEM, PFMPC, DMD-MPC or random-shooting episodes as ONE batch on the tree engine
-(``BatchedMPPI`` / ``BatchedCEM`` / ``BatchedPFMPC`` / ``BatchedDMDMPC`` / ``BatchedRandomShooting``).
+"""The config's ``n_episodes`` MPPI, CEM, PFMPC, DMD-MPC, random-shooting or MPPIQ episodes as ONE batch on the tree engine
+(``BatchedMPPI`` / ``BatchedCEM`` / ``BatchedPFMPC`` / ``BatchedDMDMPC`` / ``BatchedRandomShooting`` / ``BatchedMPPIQ``).
 
     python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml
-        [--controller mppi|cem|pfmpc|dmd|random_shooting]
+        [--controller mppi|cem|pfmpc|dmd|random_shooting|mppiq]
         [--dtype f64|f32] [--episodes N] [--dyn_randomize_config FILE [--num_cpu K] [--dyn_per_episode]]
         [--update_cov] [--cov_type diagonal|full]
 
@@ -18,14 +18,15 @@ particles are split into the config's ``num_cpu`` shards and each shard rolls ou
 all episodes from the config's ``seed`` as the reference does before its episode loop (``--dyn_per_episode``: from every
 episode's own seed), while the real envs keep the nominal model - still one batch.
 
-The ``mppi``, ``cem``, ``pfmpc``, ``dmd`` and ``random_shooting`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection +
+The ``mppi``, ``cem``, ``pfmpc``, ``dmd``, ``random_shooting`` and ``mppiq`` blocks run here (``--controller cem``: ``BatchedCEM``, DESIGN 10.2 - the rollout, selection +
 moments, refit + next samples and env-step launches per control step; ``--controller pfmpc``: ``BatchedPFMPC``, DESIGN 10.3 -
 deviations, rollout, weights, resampling, gather + shift, mean + action and env step, e.g. examples/configs/reacher_gpu.yml;
 ``--controller dmd``: with ``update_cov: true`` ``BatchedDMDMPC``, DESIGN 10.4 - factors, draw, filter, rollout, weights, partial
 moments, update + tail and env step -, with ``update_cov: false`` ``BatchedMPPI`` with the block's ``lam``, ``step_size`` and
 ``init_cov``, which is that arithmetic; the class that ran is printed; ``--controller random_shooting``:
-``BatchedRandomShooting``, DESIGN 10.5 - draw, rollout, selection + blend + tail and env step); other controller blocks are
-refused.  The reacher configs run on the TREE engine here
+``BatchedRandomShooting``, DESIGN 10.5 - draw, rollout, selection + blend + tail and env step; ``--controller mppiq``:
+``BatchedMPPIQ``, DESIGN 10.6 - draw, filter, rollout, returns + weights, partial moments, update + tail and env step, with the
+block's ``alpha`` and ``time_based_weights``); other controller blocks are refused.  The reacher configs run on the TREE engine here
 (sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
 rewards are not expected to be equal.
 """
@@ -40,7 +41,8 @@ import yaml
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from example_mpc import ENVS, TREE_MODELS                           # noqa: E402
-from mjmpc_amd.control import BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedPFMPC, BatchedRandomShooting  # noqa: E402
+from mjmpc_amd.control import (BatchedCEM, BatchedDMDMPC, BatchedMPPI, BatchedMPPIQ, BatchedPFMPC,  # noqa: E402
+                               BatchedRandomShooting)
 from mjmpc_amd.envs.tree_engine import TreeRolloutEngine            # noqa: E402
 from mjmpc_amd.models.reacher7dof import reacher7dof_raw            # noqa: E402
 
@@ -54,13 +56,14 @@ BATCHES = {
     "dmd": (BatchedDMDMPC, ("lam", "step_size", "init_cov", "beta"), dict(cov_type="diagonal", sample_mode="mean")),
     "dmd_static": (BatchedMPPI, ("lam", "step_size", "init_cov"), dict()),
     "random_shooting": (BatchedRandomShooting, ("step_size", "init_cov"), dict(sample_mode="mean")),
+    "mppiq": (BatchedMPPIQ, ("beta", "step_size", "init_cov", "td_lam"), dict(alpha=1, time_based_weights=True)),
 }
 
 
 def main():
-    ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM, PFMPC, DMD-MPC or random-shooting episodes as one batch")
+    ap = argparse.ArgumentParser(description="Run a config's MPPI, CEM, PFMPC, DMD-MPC, random-shooting or MPPIQ episodes as one batch")
     ap.add_argument("--config", required=True, help="yaml file with experiment parameters")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting"],
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting", "mppiq"],
                     help="controller block of the config to run")
     ap.add_argument("--dtype", default="f64", choices=["f64", "f32"])
     ap.add_argument("--episodes", type=int, help="override n_episodes")

@@ -575,6 +575,32 @@ int mjmpc_dmd_update_batch(int dtype, int E, int64_t P, int H, int A, const void
                            const double* d_beta, int shift_mode, double* d_means, double* d_covs, double* d_actions_out,
                            int64_t* d_step_counter, void* d_ws, void* stream);
 
+/* Episode batches of the MPPIQ step (mppiq.py:73-136 without Q estimates, one per episode of the reference's episode loop):
+ * three launches, grid row e = episode e, no host synchronisation.  Row e is exactly mjmpc_td_lambda_returns(dtype, P, H, A,
+ * d_costs + e P H, d_actions + e P H A, NULL, d_means + e H A, d_covinv + e A A, d_wseq + e max(H-1, 1), d_wseq_has_zero[e],
+ * d_beta[e], alpha, gamma, d_td_lam[e], returns, ws), then mjmpc_softmax_stats(dtype, P, H, A, returns, d_actions + e P H A,
+ * d_means + e H A, NULL, any d_gseq, gamma_zero = 1, d_beta[e], alpha = 1, time_based_weights, want_cov = 0, record, ws), then
+ * mjmpc_softmax_combine(record, G = 1, H, A, time_based_weights, d_beta[e], d_step_size[e], cov_mode = 0, P, d_means + e H A,
+ * NULL, NULL, NULL), then mjmpc_step_tail(d_means + e H A, H, A, shift_mode, NULL, d_actions_out + e A, NULL, counter, NULL,
+ * NULL, 0) on its slices: the returns rounded to dtype before the weights read them, the same 16 particles per partial, the
+ * same merge tree over the ceil(P / 16) partials, the same combine with one record and H weight columns (time_based_weights)
+ * or one.  d_costs dtype [E][P][H], d_actions dtype [E][P][H][A], d_beta (> 0: only the host can check it), d_step_size and
+ * d_td_lam float64 [E] (device), d_wseq float64 [E][max(H-1, 1)] = cumprod(1, gamma d_td_lam[e], ...) per row and
+ * d_wseq_has_zero int [E] (device), alpha 0 (control cost on: d_covinv float64 [E][A][A] is read) or 1 (d_covinv may be NULL),
+ * shift_mode 0 'null' or 1 'repeat', d_means float64 [E][H][A] (updated and shifted in place), d_actions_out float64 [E][A]
+ * (may be NULL).  *d_step_counter (may be NULL) is advanced once, by row 0 of the last launch; no row reads it.  Launches:
+ * returns + weights + their column maxima; partial moments; record + combine + tail.
+ * mjmpc_mppiq_batch_supported: 1 <= E <= 65535, P >= 1, H >= 1, 1 <= A <= 64 (the tail's limit) and, with time_based_weights,
+ * H <= 512 (the partial launch's 8 * 16 * H bytes of LDS within 64 KB).  d_ws: mjmpc_mppiq_batch_workspace_bytes(E, P, H, A,
+ * time_based_weights) bytes, 8-byte aligned (negative for unsupported sizes).  MJMPC_E_BADARG otherwise, before any launch. */
+int mjmpc_mppiq_batch_supported(int E, int64_t P, int H, int A, int time_based_weights);
+int64_t mjmpc_mppiq_batch_workspace_bytes(int E, int64_t P, int H, int A, int time_based_weights);
+int mjmpc_mppiq_update_batch(int dtype, int E, int64_t P, int H, int A, const void* d_costs, const void* d_actions,
+                             const double* d_beta, const double* d_step_size, const double* d_td_lam, const double* d_wseq,
+                             const int* d_wseq_has_zero, double gamma, int alpha, const double* d_covinv,
+                             int time_based_weights, int shift_mode, double* d_means, double* d_actions_out,
+                             int64_t* d_step_counter, void* d_ws, void* stream);
+
 /* Episode batches of the random-shooting step (random_shooting.py:52-62, one per episode of the reference's episode loop):
  * one launch, grid row e = episode e, no host synchronisation, no workspace.  Row e is mjmpc_rs_best(dtype, P, H, A,
  * d_actions + e P H A, 0, record, ws) on the cost-to-go d_q0 + e P, then mjmpc_rs_combine(record, 1, H, A, d_step_size[e],

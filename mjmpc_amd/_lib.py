@@ -133,6 +133,10 @@ SIGNATURES = {
     "mjmpc_dmd_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int]),
     "mjmpc_dmd_update_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp, _int, _vp, _vp, _vp,
                                       _vp, _vp, _vp]),
+    "mjmpc_mppiq_batch_supported": (_int, [_int, _i64, _int, _int, _int]),
+    "mjmpc_mppiq_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int, _int]),
+    "mjmpc_mppiq_update_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _dbl, _int, _vp, _int,
+                                        _int, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_rs_batch_supported": (_int, [_int, _i64, _int, _int]),
     "mjmpc_rs_update_batch": (_int, [_int, _int, _i64, _int, _int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_pf_batch_workspace_bytes": (_i64, [_int, _i64, _int, _int]),

@@ -11,6 +11,7 @@ _WHERE = {
     "BatchedPFMPC": "batched",
     "BatchedDMDMPC": "batched",
     "BatchedRandomShooting": "batched",
+    "BatchedMPPIQ": "batched",
 }
 __all__ = sorted(_WHERE)
 

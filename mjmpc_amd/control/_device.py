@@ -292,6 +292,10 @@ class DeviceUpdater:
         import torch
         return _lib.F32 if t.dtype == torch.float32 else _lib.F64
 
+    def _upload(self, dst, host):
+        """Host array -> the device tensor ``dst`` (float64): the host uploads of ``td_lambda_returns``."""
+        dst.copy_(self.torch.from_numpy(np.ascontiguousarray(host, np.float64)).reshape(dst.shape))
+
     def set_mean(self, mean):
         self.mean.copy_(self.torch.from_numpy(np.ascontiguousarray(mean, np.float64)))
 
@@ -323,18 +327,24 @@ class DeviceUpdater:
             qvals = self.to_device(qvals, "qvals").to(costs.dtype).contiguous()
             if tuple(qvals.shape) != (P, self.H):
                 raise ValueError("qvals must have shape (P, H)")
-        wseq = np.cumprod([1.0] + [gamma * td_lam] * (self.H - 2)) if self.H > 1 else np.array([1.0])
+        # the weight table stays on the device: uploaded when (gamma, td_lam, H) change, so that a steady-state call with
+        # alpha == 1 copies nothing from the host (and can be captured)
         wd = self.record("td_wseq", max(self.H - 1, 1))
-        wd.copy_(torch.from_numpy(np.ascontiguousarray(wseq, np.float64)))
+        key = (float(gamma), float(td_lam), self.H)
+        cached = self._rec.get("td_wseq_host")
+        if cached is None or cached[0] != key:
+            wseq = np.cumprod([1.0] + [gamma * td_lam] * (self.H - 2)) if self.H > 1 else np.array([1.0])
+            self._upload(wd, wseq)
+            cached = self._rec["td_wseq_host"] = (key, int(bool(np.any(wseq == 0))))
         if alpha == 0:
-            self.covinv.copy_(torch.from_numpy(np.ascontiguousarray(covinv, np.float64)))
+            self._upload(self.covinv, covinv)
         key = ("td_returns", costs.dtype)
         out = self._rec.get(key)
         if out is None or tuple(out.shape) != (P, self.H):
             out = self._rec[key] = torch.empty((P, self.H), dtype=costs.dtype, device=self.device)
         _lib.check(self.lib.mjmpc_td_lambda_returns(self.code(costs), P, self.H, self.A, _vp(costs), _vp(actions),
                                                     _vp(qvals), _vp(self.mean), _vp(self.covinv), _vp(wd),
-                                                    int(bool(np.any(wseq == 0))), float(beta), int(alpha), float(gamma),
+                                                    cached[1], float(beta), int(alpha), float(gamma),
                                                     float(td_lam), _vp(out), _vp(self.workspace(P)), self.stream()))
         return out
 

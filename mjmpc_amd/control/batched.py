@@ -1,5 +1,5 @@
-"""Episode batches: E independent MPPI, CEM, PFMPC, DMD-MPC or random-shooting episodes side by side on the tree engine (DESIGN
-10, 10.2 - 10.5).
+"""Episode batches: E independent MPPI, CEM, PFMPC, DMD-MPC, random-shooting or MPPIQ episodes side by side on the tree engine
+(DESIGN 10, 10.2 - 10.6).
 
 The reference runs its experiments one episode after another (examples/job_script.py:80-99, the episode loop of
 examples/example_mpc.py), each with its own seed (``seed + i*12345``) and start state, and its "tune" mode multiplies
@@ -31,7 +31,9 @@ adapting covariance (gaussian_dmd.py with ``update_cov=True``): per
 and ``beta``, and a ``'diagonal'`` or ``'full'`` covariance that is re-estimated from the weighted samples, grown by
 ``beta I`` and factored on the device every step (``update_cov=False`` is ``BatchedMPPI``'s arithmetic).
 ``BatchedRandomShooting`` is the batch of random shooting (random_shooting.py): per episode ``step_size`` and
-``init_cov``, and a mean that moves towards the best sample of the step.  The classes share
+``init_cov``, and a mean that moves towards the best sample of the step.  ``BatchedMPPIQ`` is the batch of MPPIQ (mppiq.py;
+DESIGN 10.6): per episode ``beta``, ``step_size``, ``init_cov`` and ``td_lam``, TD(lambda) returns of the per-step costs and a
+softmax per horizon step.  The classes share
 ``_EpisodeBatch``: the engine, the state shards, the buffers, the rollout launch, the env step, ``run``, dynamics
 randomization, the step frame, the bound checks and the covariance status.
 """
@@ -567,6 +569,89 @@ class BatchedDMDMPC(_EpisodeBatch):
                                               _vp(self._lam), _vp(self._step), 2 if self.cov_type == "full" else 1,
                                               _vp(self._beta), _SHIFT_MODES[self.base_action], _vp(self._means),
                                               _vp(self._covs), _vp(act), _vp(self._step_dev), _vp(self._ws), s))
+
+
+class BatchedMPPIQ(_EpisodeBatch):
+    """``num_episodes`` MPPIQ controllers (mppiq.py, one iteration per step) and their real envs, stepped together.
+
+    Episode e computes the bits of ``MPPIQ(..., alpha=alpha, time_based_weights=time_based_weights, noise_mode='device',
+    noise_dtype=dtype, seed=seeds[e])`` on a ``TreeRolloutEngine`` of its own with ``make_device_rollout_fn``, whose step is the
+    general one of ``OLGaussianMPC._device_iteration``: draw + filter with the static diagonal factor, plain rollout,
+    ``mjmpc_td_lambda_returns``, ``softmax_update`` on the returns, ``step_tail`` - captured with
+    ``enable_graph(post_step=engine.step_state)`` for ``alpha = 1``, eager for ``alpha = 0`` (which uploads ``cov^-1`` per step).
+    ``beta`` (the temperature), ``step_size``, ``init_cov`` (scalar: ``diag(init_cov)``, as ``MPPIQ`` takes it) and ``td_lam``
+    take one value for every episode or one per episode; ``seeds`` one seed per episode; ``alpha`` (1: no control cost, 0: the
+    control cost with ``cov^-1 = diag(1 / init_cov_e)``), ``time_based_weights`` (a softmax per horizon step, ``MPPIQ``'s
+    default) and ``gamma`` are shared.  The mean starts at zero.  A control step is seven launches - draw, filter, rollout,
+    returns + weights + their maxima, partial moments, record + combine + tail, real-env step (six with the identity filter)
+    - and nothing synchronises.  Out of scope: terminal Q estimates (open-loop rollouts produce no ``qvals``), ``_calc_val``
+    and ``n_iters > 1``.  Settings the batch does not run raise ``ValueError`` before any engine or device memory exists:
+    ``n_iters != 1``, ``sample_mode != 'mean'``, ``gamma == 0``, ``base_action`` other than ``'null'`` / ``'repeat'``, ``alpha``
+    other than 0 / 1, ``beta <= 0``, ``init_cov <= 0``, ``td_lam`` outside [0, 1], a wrong seed count, a shape outside
+    ``mjmpc_mppiq_batch_supported`` and a model the tree engine refuses."""
+
+    def __init__(self, raw_model, num_episodes, horizon, num_particles, beta, step_size, init_cov, td_lam, gamma,
+                 filter_coeffs, base_action, seeds, alpha=1, time_based_weights=True, dtype="f64", device=0, n_iters=1,
+                 sample_mode="mean"):
+        # -- everything that can be refused is refused here, before the engine and its device memory exist
+        E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, False, sample_mode, dtype,
+                                         gamma, filter_coeffs, "MPPIQ")
+        if alpha not in (0, 1):
+            raise ValueError("alpha must be 0 (control cost on) or 1 (off) in an MPPIQ episode batch, got %r" % (alpha,))
+        beta = _per_episode("beta", beta, E, sign="positive")
+        step_size = _per_episode("step_size", step_size, E)
+        init_cov = _per_episode("init_cov", init_cov, E, sign="positive")
+        td_lam = _per_episode("td_lam", td_lam, E)
+        if not np.all((td_lam >= 0) & (td_lam <= 1)):
+            raise ValueError("td_lam must lie in [0, 1]")
+        tbw = int(bool(time_based_weights))
+        lib = _lib.load()
+        # (the support predicate's other limit, 1 <= A <= 64, needs the model: below)
+        if not lib.mjmpc_mppiq_batch_supported(E, P, H, 1, tbw):
+            raise ValueError("the batched MPPIQ step with time-based weights takes a horizon of up to 512, got %d" % H)
+        model = self._seeds_and_model(seeds, E, raw_model)
+        A = model.nu
+        if not lib.mjmpc_mppiq_batch_supported(E, P, H, A, tbw):
+            raise ValueError("the batched MPPIQ step takes up to 64 action channels, got A = %d" % A)
+        # the single path's tables, by its expressions and so with its bits (DeviceUpdater.td_lambda_returns, MPPIQ._returns)
+        wseq, wseq_zero = self._td_tables(td_lam, gamma, H)
+        covs, chols, _ = self._diag_factors(init_cov, A)                            # (OLGaussianMPC: diag(init_cov))
+        covinv = np.stack([np.linalg.inv(c) for c in covs]) if alpha == 0 else None
+
+        # -- the engine (its state shards are the E real envs) and the batch's device buffers
+        self._setup(raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, np.zeros((E, H, A)))
+        self.beta, self.step_size, self.init_cov, self.td_lam = beta, step_size, init_cov, td_lam
+        self.alpha, self.time_based_weights = int(alpha), bool(tbw)
+        self.wseq, self.wseq_zero = wseq, wseq_zero
+        self._chols, self._beta, self._step = self._upload(chols), self._upload(beta), self._upload(step_size)
+        self._td_lam, self._wseq, self._wseq_zero = self._upload(td_lam), self._upload(wseq), self._upload(wseq_zero)
+        self._covinv = None if covinv is None else self._upload(covinv)
+        self._draw_coeffs = self._coeffs_unless_identity()      # (the filter pass leaves an identity's samples as they are)
+        self._ws = self._workspace(self.lib.mjmpc_mppiq_batch_workspace_bytes(E, P, H, A, tbw))
+
+    @staticmethod
+    def _td_tables(td_lam, gamma, H):
+        """The TD(lambda) weight tables of the episodes, float64 ``[E][max(H - 1, 1)]``, and whether each holds a zero (int32
+        ``[E]``: cost_to_go's pass-through branch) - ``DeviceUpdater.td_lambda_returns``'s expression per episode."""
+        wseq = np.stack([np.cumprod([1.0] + [gamma * l] * (H - 2)) if H > 1 else np.array([1.0]) for l in td_lam])
+        return wseq, np.array([int(bool(np.any(w == 0))) for w in wseq], np.int32)
+
+    def _launches(self, act, s):
+        """Enqueue one control step of every episode (draw + filter, rollouts, returns + weights, partial moments, update +
+        action + shift, real-env step) without a host synchronisation.  The actions, real-env costs and next observations
+        stay on the device."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        lib, code = self.lib, self._code
+        # (the static factors diag(sqrt(init_cov_e)): row e is the single path's mjmpc_sample_noise, draw then filter)
+        _lib.check(lib.mjmpc_sample_noise_cov_batch(code, E, _vp(self._noise), P, H, A, _vp(self._chols), _vp(self._draw_coeffs),
+                                                    _vp(self._seeds), 0, _vp(self._step_dev), 1, s))
+        # (the samples are filtered already and the update forms its own returns: the single path's plain rollout)
+        self._rollout(s, filtered=False, gseq=False, q0=False)
+        _lib.check(lib.mjmpc_mppiq_update_batch(code, E, P, H, A, _vp(self._costs), _vp(self._actions), _vp(self._beta),
+                                                _vp(self._step), _vp(self._td_lam), _vp(self._wseq), _vp(self._wseq_zero),
+                                                self.gamma, self.alpha, _vp(self._covinv), int(self.time_based_weights),
+                                                _SHIFT_MODES[self.base_action], _vp(self._means), _vp(act),
+                                                _vp(self._step_dev), _vp(self._ws), s))
 
 
 class BatchedPFMPC(_EpisodeBatch):

@@ -29,8 +29,9 @@ class MPPIQ(OLGaussianMPC):
         return self.alpha == 1
 
     def _host_uploads_per_step(self):
-        return True             # td_lambda_returns uploads its weight table (and cov^-1) from the host on every update:
-                                # not capturable - enable_graph() refuses instead of failing inside the capture
+        return self.alpha != 1  # alpha == 0: td_lambda_returns uploads cov^-1 from the host on every update - not
+                                # capturable, enable_graph() refuses instead of failing inside the capture.  alpha == 1: its
+                                # weight table stays on the device and a steady-state update uploads nothing
 
     def _returns(self, trajectories):
         """mppiq.py:91-126: per-step total cost -> TD(lambda) returns, on the device."""

@@ -1638,6 +1638,47 @@ int mjmpc_dmd_update_batch(int dtype, int E, int64_t P, int H, int A, const void
                                              (long long*)d_step_counter, (double*)d_ws, s));
 }
 
+int mjmpc_mppiq_batch_supported(int E, int64_t P, int H, int A, int time_based_weights) {
+    return mjmpc::mppiq_batch_supported(E, (long)P, H, A, time_based_weights) ? 1 : 0;
+}
+
+static int mppiq_batch_shape(int E, int64_t P, int H, int A, int tbw) {
+    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
+    if (A < 1 || A > 64) return fail(MJMPC_E_BADARG, "A = %d outside 1 .. 64 (the tail's limit)", A);
+    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d", (long long)P, H);
+    if (!mjmpc::mppiq_batch_supported(E, (long)P, H, A, tbw))
+        return fail(MJMPC_E_BADARG, "H = %d above 512 with time-based weights (mjmpc_mppiq_batch_supported)", H);
+    return 0;
+}
+
+int64_t mjmpc_mppiq_batch_workspace_bytes(int E, int64_t P, int H, int A, int time_based_weights) {
+    if (int rc = mppiq_batch_shape(E, P, H, A, time_based_weights)) return rc;
+    return (int64_t)sizeof(double) * mjmpc::mppiq_batch_workspace_doubles(E, (long)P, H, A, time_based_weights);
+}
+
+int mjmpc_mppiq_update_batch(int dtype, int E, int64_t P, int H, int A, const void* d_costs, const void* d_actions,
+                             const double* d_beta, const double* d_step_size, const double* d_td_lam, const double* d_wseq,
+                             const int* d_wseq_has_zero, double gamma, int alpha, const double* d_covinv,
+                             int time_based_weights, int shift_mode, double* d_means, double* d_actions_out,
+                             int64_t* d_step_counter, void* d_ws, void* stream) {
+    if (!d_costs || !d_actions || !d_beta || !d_step_size || !d_td_lam || !d_wseq || !d_wseq_has_zero || !d_means || !d_ws)
+        return fail(MJMPC_E_BADARG, "null argument");
+    if (int rc = mppiq_batch_shape(E, P, H, A, time_based_weights)) return rc;
+    if (alpha != 0 && alpha != 1) return fail(MJMPC_E_BADARG, "alpha %d (0: control cost on, 1: off)", alpha);
+    if (alpha == 0 && !d_covinv) return fail(MJMPC_E_BADARG, "alpha = 0 needs d_covinv");
+    if (shift_mode < 0 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
+    const double* covinv = alpha == 0 ? d_covinv : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH(dtype,
+             mjmpc::mppiq_update_batch<float>(E, (const float*)d_costs, (const float*)d_actions, d_beta, d_step_size, d_td_lam,
+                                              d_wseq, d_wseq_has_zero, gamma, covinv, time_based_weights, shift_mode, (long)P,
+                                              H, A, d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws, s),
+             mjmpc::mppiq_update_batch<double>(E, (const double*)d_costs, (const double*)d_actions, d_beta, d_step_size,
+                                               d_td_lam, d_wseq, d_wseq_has_zero, gamma, covinv, time_based_weights,
+                                               shift_mode, (long)P, H, A, d_means, d_actions_out,
+                                               (long long*)d_step_counter, (double*)d_ws, s));
+}
+
 int mjmpc_rs_batch_supported(int E, int64_t P, int H, int A) { return mjmpc::rs_batch_supported(E, (long)P, H, A) ? 1 : 0; }
 
 int mjmpc_rs_update_batch(int dtype, int E, int64_t P, int H, int A, const double* d_q0, const void* d_actions,

@@ -109,6 +109,20 @@ hipError_t dmd_update_batch(int E, const T* costs, const T* actions, const doubl
 // row e is cholesky_lower on covs + e A A -> chols + e A A with its own sticky flag status[e] (status may be null)
 hipError_t cholesky_lower_batch(int E, const double* covs, int A, double* chols, int* status, hipStream_t s);
 
+// Episode batches of the MPPIQ step (mppiq.py:73-136, no Q estimates): grid row e is td_lambda_returns (beta[e], td_lam[e],
+// wseq + e max(H-1, 1), wseq_zero[e]; covinv + e A A when covinv is given: alpha 0) + softmax_stats on the returns (gamma_zero,
+// beta[e], alpha 1, Hw = tbw ? H : 1 weight columns, no covariance) + softmax_combine (one record, step[e]) + step_tail
+// (shift_mode) on episode e's slices, in three launches; row 0 increments the shared step counter once.
+// mppiq_batch_supported: 1 <= E <= 65535, P, H >= 1, 1 <= A <= 64, and H <= 512 with tbw (the partial launch's LDS).
+// ws: mppiq_batch_workspace_doubles(E, P, H, A, tbw).
+bool mppiq_batch_supported(int E, long P, int H, int A, int tbw);
+long mppiq_batch_workspace_doubles(int E, long P, int H, int A, int tbw);
+template <typename T>
+hipError_t mppiq_update_batch(int E, const T* costs, const T* actions, const double* beta, const double* step,
+                              const double* td_lam, const double* wseq, const int* wseq_zero, double gamma,
+                              const double* covinv, int tbw, int shift_mode, long P, int H, int A, double* means,
+                              double* actions_out, long long* step_counter, double* ws, hipStream_t s);
+
 // Episode batches of the random-shooting step (random_shooting.py:52-62): grid row e is rs_best + rs_combine (one record,
 // step[e]) + step_tail (shift_mode) on episode e's slices, in one launch and without a workspace; the first index of the
 // minimum of q0 + e P (particle 0 for a row of +inf) also goes to best[e] (may be null); row 0 increments the shared step

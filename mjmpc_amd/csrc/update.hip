@@ -85,13 +85,13 @@ __global__ void traj_cost_kernel(const T* __restrict__ costs, const T* __restric
 //   td[t]    = total[t] + gamma q[t+1] - q[t],  t < H-1;   q = qvals, or 0 with q[H-1] = total[H-1]
 //   out[t]   = q[t] + td_lam * cost_to_go(td, wseq)[t],    out[H-1] = q[H-1]
 // cost_to_go in the order of control_utils.py:37-46 (reverse running sum, then / wseq; unchanged if wseq has a 0).
+// (particle p's part; the body is shared with the episode-batch kernel mppiq_returns_x_batch_kernel below)
 template <typename T>
-__global__ void td_lambda_kernel(const T* __restrict__ costs, const T* __restrict__ actions, const T* __restrict__ qvals,
-                                 const double* __restrict__ mean, const double* __restrict__ un,
-                                 const double* __restrict__ wseq, int wseq_zero, double beta, double gamma,
-                                 double td_lam, long P, int H, int A, T* __restrict__ out) {
-    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
+__device__ __forceinline__ void td_lambda_body(const T* __restrict__ costs, const T* __restrict__ actions,
+                                               const T* __restrict__ qvals, const double* __restrict__ mean,
+                                               const double* __restrict__ un, const double* __restrict__ wseq, int wseq_zero,
+                                               double beta, double gamma, double td_lam, long p, int H, int A,
+                                               T* __restrict__ out) {
     auto total = [&](int t) {
         double c = (double)costs[p * H + t];
         if (un) {
@@ -123,15 +123,31 @@ __global__ void td_lambda_kernel(const T* __restrict__ costs, const T* __restric
     }
 }
 
+template <typename T>
+__global__ void td_lambda_kernel(const T* __restrict__ costs, const T* __restrict__ actions, const T* __restrict__ qvals,
+                                 const double* __restrict__ mean, const double* __restrict__ un,
+                                 const double* __restrict__ wseq, int wseq_zero, double beta, double gamma,
+                                 double td_lam, long P, int H, int A, T* __restrict__ out) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    td_lambda_body<T>(costs, actions, qvals, mean, un, wseq, wseq_zero, beta, gamma, td_lam, p, H, A, out);
+}
+
 // u_n = mean . cov^-1      (mppi.py:106)
-__global__ void un_kernel(const double* __restrict__ mean, const double* __restrict__ covinv, int H, int A,
-                          double* __restrict__ un) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= H * A) return;
+// (entry j's part; the body is shared with the episode-batch kernel mppiq_returns_x_batch_kernel below)
+__device__ __forceinline__ void un_body(const double* __restrict__ mean, const double* __restrict__ covinv, int A, int j,
+                                        double* __restrict__ un) {
     const int t = j / A, a = j % A;
     double s = 0.0;
     for (int b = 0; b < A; ++b) s += mean[t * A + b] * covinv[b * A + a];
     un[j] = s;
+}
+
+__global__ void un_kernel(const double* __restrict__ mean, const double* __restrict__ covinv, int H, int A,
+                          double* __restrict__ un) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= H * A) return;
+    un_body(mean, covinv, A, j, un);
 }
 
 // xmax[tw] = max_p x[p][tw]; one workgroup per column
@@ -1600,6 +1616,114 @@ __global__ void dmd_finish_batch_kernel(DmdBatch<T> b) {
                    e == 0 ? b.step_counter : nullptr, cov, nullptr, b.beta[e]);
 }
 
+// ---- episode batches of the MPPIQ step --------------------------------------------------------------------------
+// Grid row e of every launch runs the text of the single path's kernels - un_body, td_lambda_body, traj_cost_body, the column
+// maxima, softmax_partial_body, wave_entry_sum, softmax_combine_body, step_tail_body - on episode e's slices, with
+// Hw = H weight columns (time-based weights) or one.
+// -- one episode's block of the batch workspace, laid out alike on host and device:
+// un[HA] | returns [P][H] (dtype T, in P H doubles of room) | x[P Hw] | xmax[Hw] | record [2 Hw + HA + AA] |
+// partials [nb][Hw + HA + AA]
+struct MppiqRow {
+    double *un, *returns, *x, *xmax, *record, *partial;
+    __host__ __device__ MppiqRow(double* base, long P, int H, int A, int Hw) {
+        const long HA = (long)H * A, AA = (long)A * A;
+        un = base;
+        returns = un + HA;
+        x = returns + P * H;
+        xmax = x + P * Hw;
+        record = xmax + Hw;
+        partial = record + 2 * Hw + HA + AA;
+    }
+};
+__host__ __device__ inline long mppiq_row_doubles(long P, int H, int A, int Hw, int nb) {
+    const long HA = (long)H * A, AA = (long)A * A;
+    return HA + P * H + P * Hw + Hw + (2 * Hw + HA + AA) + (long)nb * (Hw + HA + AA);
+}
+template <typename T>
+struct MppiqBatch {
+    const T *costs, *actions;
+    const double *beta, *step, *td_lam, *wseq, *covinv;    // (covinv null: the control cost is off, alpha = 1)
+    const int* wseq_zero;
+    // (run-time nulls and a run-time 1, as the single launches get them: no Q estimates; the weights' own control cost off,
+    // no discount sequence and gamma_zero - the returns are per-step values already)
+    const T* qvals;
+    const double *x_un, *gseq;
+    int gamma_zero;
+    double *means, *actions_out, *ws;
+    long long* step_counter;
+    double gamma;
+    long stride, P;
+    int H, A, Hw, nb, chunk, shift_mode;
+};
+
+// row e: un_kernel (alpha = 0), td_lambda_kernel without Q estimates (returns rounded to T), traj_cost_kernel on the returns
+// (gamma_zero, no control cost) and colmax_kernel's maxima of the Hw columns - one workgroup, a barrier where the single path
+// has a launch boundary.  A maximum does not depend on the order it is taken in (no NaN reaches it: traj_cost_body), so a
+// wavefront takes a column instead of a workgroup.
+template <typename T>
+__global__ __launch_bounds__(BLK) void mppiq_returns_x_batch_kernel(MppiqBatch<T> b) {
+    const long e = blockIdx.y, P = b.P;
+    const int H = b.H, A = b.A, HA = H * A, Hw = b.Hw;
+    const MppiqRow r(b.ws + e * b.stride, P, H, A, Hw);
+    const T* costs = b.costs + e * P * H;
+    const T* actions = b.actions + e * P * HA;
+    const double* mean = b.means + e * HA;
+    const double* un = nullptr;
+    if (b.covinv) {
+        for (int j = threadIdx.x; j < HA; j += blockDim.x) un_body(mean, b.covinv + e * A * A, A, j, r.un);
+        un = r.un;
+        __syncthreads();
+    }
+    T* ret = (T*)r.returns;
+    const double beta = b.beta[e];
+    for (long p = threadIdx.x; p < P; p += blockDim.x)
+        td_lambda_body<T>(costs, actions, b.qvals, mean, un, b.wseq + e * (H > 1 ? H - 1 : 1), b.wseq_zero[e], beta,
+                          b.gamma, b.td_lam[e], p, H, A, ret);
+    __syncthreads();
+    for (long p = threadIdx.x; p < P; p += blockDim.x)
+        traj_cost_body<T>(ret, actions, mean, b.x_un, b.gseq, b.gamma_zero, beta, p, H, A, Hw, r.x, nullptr);
+    __syncthreads();
+    for (int tw = threadIdx.x >> 6; tw < Hw; tw += blockDim.x >> 6) {
+        double m = -INFINITY;
+        for (long p = threadIdx.x & 63; p < P; p += 64) m = fmax(m, r.x[p * Hw + tw]);
+        m = wave_max(m);
+        if ((threadIdx.x & 63) == 0) r.xmax[tw] = m;
+    }
+}
+
+// row e: softmax_partial_kernel on its particles with Hw weight columns (the same chunks) into its partials
+template <typename T>
+__global__ __launch_bounds__(BLK) void mppiq_partial_batch_kernel(MppiqBatch<T> b) {
+    const long e = blockIdx.y;
+    const int HA = b.H * b.A;
+    const MppiqRow r(b.ws + e * b.stride, b.P, b.H, b.A, b.Hw);
+    softmax_partial_body<T>(r.x, r.xmax, b.actions + e * b.P * HA, b.means + e * HA, b.P, b.H, b.A, b.Hw, b.chunk, 0, r.partial);
+}
+
+// row e: softmax_record_kernel (a wavefront per entry: wave_entry_sum over its nb partials), softmax_combine_kernel with that
+// one record and Hw columns, step_tail_kernel - one workgroup, a barrier where the single path has a launch boundary.  Row 0
+// advances the shared step counter; no row reads it.
+template <typename T>
+__global__ __launch_bounds__(BLK) void mppiq_finish_batch_kernel(MppiqBatch<T> b) {
+    const long e = blockIdx.y;
+    const int H = b.H, A = b.A, Hw = b.Hw, HA = H * A, rec = Hw + HA + A * A;
+    const MppiqRow r(b.ws + e * b.stride, b.P, H, A, Hw);
+    for (int j = threadIdx.x >> 6; j < rec; j += blockDim.x >> 6) {
+        const double s = wave_entry_sum(r.partial, b.nb, rec, j);
+        if ((threadIdx.x & 63) == 0) {
+            r.record[Hw + j] = s;
+            if (j < Hw) r.record[j] = r.xmax[j];
+        }
+    }
+    __syncthreads();
+    double* mean = b.means + e * HA;
+    for (int j = threadIdx.x; j < HA; j += blockDim.x)
+        softmax_combine_body(r.record, 1, H, A, Hw, b.beta[e], b.step[e], 0, (double)b.P, mean, nullptr, nullptr, nullptr, j);
+    __syncthreads();
+    step_tail_body(mean, H, A, b.shift_mode, nullptr, b.actions_out ? b.actions_out + e * A : nullptr, nullptr,
+                   e == 0 ? b.step_counter : nullptr, nullptr, nullptr, 0.0);
+}
+
 // ---- episode batches of the random-shooting step ---------------------------------------------------------------
 // Row e: the single path's argmin_kernel + rs_record_kernel + rs_combine_kernel (one record) + step_tail_kernel on episode e's
 // slices, one workgroup and one launch.  The selection is compares of (value, index) pairs - a strided scan per thread, a
@@ -2111,6 +2235,38 @@ hipError_t dmd_update_batch(int E, const T* costs, const T* actions, const doubl
     return hipGetLastError();
 }
 
+// (the tail takes a thread per action channel of one wavefront: A <= 64; with time-based weights the partial launch's
+// dynamic LDS, 8 CHUNK H bytes, stays within the 64 KB the single launch takes without an attribute)
+bool mppiq_batch_supported(int E, long P, int H, int A, int tbw) {
+    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1 || A > 64) return false;
+    return !tbw || sizeof(double) * CHUNK * (size_t)H <= 64 * 1024;
+}
+
+long mppiq_batch_workspace_doubles(int E, long P, int H, int A, int tbw) {
+    return (long)E * mppiq_row_doubles(P, H, A, tbw ? H : 1, nblocks(P, CHUNK));
+}
+
+// One episode per grid row, each row what td_lambda_returns (no Q estimates) + softmax_stats on the returns (gamma_zero,
+// alpha 1, no covariance) + softmax_combine (one record) + step_tail do for its P particles: the same CHUNK particles per
+// partial, the same nb = ceil(P / CHUNK), the same wave_entry_sum tree over them, the same combine and tail - three launches.
+template <typename T>
+hipError_t mppiq_update_batch(int E, const T* costs, const T* actions, const double* beta, const double* step,
+                              const double* td_lam, const double* wseq, const int* wseq_zero, double gamma,
+                              const double* covinv, int tbw, int shift_mode, long P, int H, int A, double* means,
+                              double* actions_out, long long* step_counter, double* ws, hipStream_t s) {
+    if (!mppiq_batch_supported(E, P, H, A, tbw)) return hipErrorInvalidValue;
+    MppiqBatch<T> b;
+    b.costs = costs; b.actions = actions; b.beta = beta; b.step = step; b.td_lam = td_lam; b.wseq = wseq; b.covinv = covinv;
+    b.wseq_zero = wseq_zero; b.means = means; b.actions_out = actions_out; b.ws = ws; b.step_counter = step_counter;
+    b.gamma = gamma; b.qvals = nullptr; b.x_un = nullptr; b.gseq = nullptr; b.gamma_zero = 1;
+    b.Hw = tbw ? H : 1; b.nb = nblocks(P, CHUNK); b.chunk = CHUNK;
+    b.stride = mppiq_row_doubles(P, H, A, b.Hw, b.nb); b.P = P; b.H = H; b.A = A; b.shift_mode = shift_mode;
+    hipLaunchKernelGGL(mppiq_returns_x_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
+    hipLaunchKernelGGL(mppiq_partial_batch_kernel<T>, dim3(b.nb, E), dim3(BLK), sizeof(double) * CHUNK * b.Hw, s, b);
+    hipLaunchKernelGGL(mppiq_finish_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
+    return hipGetLastError();
+}
+
 // (a thread per action channel in the tail: A <= BLK)
 bool rs_batch_supported(int E, long P, int H, int A) { return E >= 1 && E <= 65535 && P >= 1 && H >= 1 && A >= 1 && A <= BLK; }
 
@@ -2177,6 +2333,9 @@ hipError_t step_tail(double* mean, int H, int A, int mode, const double* row, do
     template hipError_t dmd_update_batch<T>(int, const T*, const T*, const double*, const double*, const double*, int, \
                                             const double*, int, long, int, int, double*, double*, double*, long long*, \
                                             double*, hipStream_t);                                                   \
+    template hipError_t mppiq_update_batch<T>(int, const T*, const T*, const double*, const double*, const double*,  \
+                                              const double*, const int*, double, const double*, int, int, long, int, int, \
+                                              double*, double*, long long*, double*, hipStream_t);                   \
     template hipError_t rs_update_batch<T>(int, const double*, const T*, const double*, int, long, int, int, double*, \
                                            double*, long long*, long long*, hipStream_t);
 INST(float)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Episode batches (BatchedMPPI / BatchedCEM / BatchedPFMPC / BatchedDMDMPC / BatchedRandomShooting): ms per batched control step and episode-steps/s, against the sequential loop.
+"""Episode batches (BatchedMPPI / BatchedCEM / BatchedPFMPC / BatchedDMDMPC / BatchedRandomShooting / BatchedMPPIQ): ms per batched control step and episode-steps/s, against the sequential loop.
 
 For every model x E x P x H: one ``BatchedMPPI`` of E episodes of P particles (f64), timed with device events over
 --steps control steps after --warmup; in the same process the single-episode device path on its own engine (MPPI,
@@ -8,7 +8,7 @@ the same way.  The sequential loop of E episodes costs E times that per control 
 the same shape).  One JSON line per configuration, then a table.
 
     python tools/batch_time.py [--models half_cheetah,swimmer,sawyer] [--E 1,4,16,64] [--P 256,1024] [--H 16,32]
-        [--model-shards K] [--controller mppi|cem|pfmpc|dmd|random_shooting] [--repeats R]
+        [--model-shards K] [--controller mppi|cem|pfmpc|dmd|random_shooting|mppiq] [--repeats R]
 
 --controller cem: ``BatchedCEM`` (full covariance, elite_frac 0.1, beta 0.45) against the single-episode fused CEM
 step (CEM, noise_mode='device', graph replay).  --repeats R: every configuration is timed R times, batch and single runs
@@ -26,6 +26,10 @@ per-launch split of one batched step as for pfmpc.
 --controller random_shooting: ``BatchedRandomShooting`` (step_size 1.0, the model's init_cov) against the
 single-episode captured random-shooting loop (RandomShooting, noise_mode='device', graph replay: draw, fused rollout, argmin,
 record, combine, tail, env step), with the per-launch split of one batched step as for pfmpc.
+
+--controller mppiq: ``BatchedMPPIQ`` (alpha 1, time-based weights, td_lam 0.9, beta = the model's lam) against the
+single-episode captured MPPIQ loop (MPPIQ, noise_mode='device', graph replay: draw, rollout, TD(lambda) returns, weights,
+maxima, partial moments, record, combine, tail, env step), with the per-launch split of one batched step as for pfmpc.
 
 --model-shards K: the batch rolls out K randomized model shards per episode (a set per episode, body masses
 +- 20 %) and the single-episode path is the sequential dynamics-randomized loop - a K-shard engine with randomized blocks
@@ -56,6 +60,7 @@ def dyn_cfg(raw):
 ELITE_FRAC, BETA = 0.1, 0.45       # (--controller cem)
 COV_SHIFT, PF_LAM, PF_GAMMA = 0.02, 1.0, 0.99       # (--controller pfmpc)
 DMD_BETA = 0.05                     # (--controller dmd)
+TD_LAM = 0.9                        # (--controller mppiq)
 
 # --controller -> ``batch``: the batch class and, from (lam, cov), its arguments between num_particles and filter_coeffs;
 # ``single``: the single-episode class and its own keywords; ``took``: whether that controller ran the intended branch, and the
@@ -92,6 +97,15 @@ CONTROLLERS = {
               "the single-episode random-shooting path did not take its q0-from-rollout step"),
         launches=("mjmpc_sample_noise_batch", "mjmpc_tree_rollout_fused_batch", "mjmpc_rs_update_batch",
                   "mjmpc_tree_step_shard_states")),
+    "mppiq": dict(
+        batch=("BatchedMPPIQ", lambda lam, cov: (lam, 1.0, cov, TD_LAM, 1.0)),
+        single=("MPPIQ", lambda lam, cov: dict(init_cov=cov, beta=lam, step_size=1.0, alpha=1, gamma=1.0, td_lam=TD_LAM,
+                                               time_based_weights=True, noise_dtype="f64")),
+        took=(lambda c: not c._fused_capable() and not c._wants_q0() and c._static_cov() and c._graph is not None,
+              "the single-episode MPPIQ path did not run its captured general step"),
+        # (mjmpc_sample_noise_cov_batch is the draw and the filter launch, mjmpc_mppiq_update_batch the three update launches)
+        launches=("mjmpc_sample_noise_cov_batch", "mjmpc_tree_rollout_fused_batch", "mjmpc_mppiq_update_batch",
+                  "mjmpc_tree_step_shard_states")),
 }
 LAUNCHES = {name: c["launches"] for name, c in CONTROLLERS.items() if "launches" in c}
 
@@ -125,7 +139,7 @@ class _TimedLib:
 
 
 def launch_split(raw, E, P, H, lam, cov, steps, warmup, controller="pfmpc"):
-    """ms per library call of one batched PFMPC / DMD-MPC / random-shooting step (mean over ``steps`` steps)."""
+    """ms per library call of one batched PFMPC / DMD-MPC / random-shooting / MPPIQ step (mean over ``steps`` steps)."""
     import torch
     names = LAUNCHES[controller]
     b = make_batch(raw, E, P, H, lam, cov, controller)
@@ -206,7 +220,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--model-shards", type=int, default=0, help="randomized model shards per episode (0: no randomization)")
-    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting"])
+    ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting", "mppiq"])
     ap.add_argument("--repeats", type=int, default=1, help="timings per configuration, batch and single runs alternating")
     args = ap.parse_args()
     from mjmpc_amd import _lib
