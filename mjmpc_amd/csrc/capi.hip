@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1280,21 +1281,17 @@ int mjmpc_analytic_rollout(int kind, const double* d_params, int n_state, int n_
 }
 
 // ---- update / noise entry points -------------------------------------------------------------------
-#define DISPATCH(dtype, CALL_F32, CALL_F64)                                   \
-    do {                                                                      \
-        hipError_t e_;                                                        \
-        if ((dtype) == MJMPC_F32) e_ = (CALL_F32);                            \
-        else if ((dtype) == MJMPC_F64) e_ = (CALL_F64);                       \
-        else return fail(MJMPC_E_BADARG, "unknown dtype %d", (int)(dtype));   \
-        if (e_ != hipSuccess) return hip_fail(e_, __func__);                  \
-        return 0;                                                             \
-    } while (0)
-#define PLAIN(CALL)                                           \
-    do {                                                      \
-        hipError_t e_ = (CALL);                               \
-        if (e_ != hipSuccess) return hip_fail(e_, __func__);  \
-        return 0;                                             \
-    } while (0)
+// (a launch that has no element type: its hipError_t as the entry point's return code)
+static int plain(hipError_t e, const char* what) { return e != hipSuccess ? hip_fail(e, what) : 0; }
+
+// what every episode-batch entry point asks of its shape: a grid row per episode (1 .. 65535), sizes of at least one and
+// A within the limit of its kernels (INT_MAX: none); checks that belong to one controller follow at the call
+static int batch_shape(int E, int64_t P, int H, int A, int A_max, const char* what) {
+    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%s: %d episodes outside 1 .. 65535", what, E);
+    if (P < 1 || H < 1 || A < 1) return fail(MJMPC_E_BADARG, "%s: bad sizes P = %lld, H = %d, A = %d", what, (long long)P, H, A);
+    if (A > A_max) return fail(MJMPC_E_BADARG, "%s: A = %d above %d, the limit of its kernels", what, A, A_max);
+    return 0;
+}
 
 int64_t mjmpc_update_workspace_bytes(int64_t P, int H, int A) {
     return (int64_t)sizeof(double) * mjmpc::update_workspace_doubles((long)P, H, A);
@@ -1305,12 +1302,11 @@ int mjmpc_softmax_record_len(int H, int A, int tbw) { return 2 * (tbw ? H : 1) +
 int mjmpc_traj_cost(int dtype, int64_t P, int H, int A, const void* d_costs, const double* d_gseq, int gamma_zero,
                     void* d_ws, void* stream) {
     if (!d_costs || !d_gseq || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::traj_cost<float>((const float*)d_costs, nullptr, nullptr, nullptr, d_gseq, gamma_zero, 1.0, 1, 0,
-                                     (long)P, H, A, (double*)d_ws, s),
-             mjmpc::traj_cost<double>((const double*)d_costs, nullptr, nullptr, nullptr, d_gseq, gamma_zero, 1.0, 1, 0,
-                                      (long)P, H, A, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::traj_cost<T>((const T*)d_costs, nullptr, nullptr, nullptr, d_gseq, gamma_zero, 1.0, 1, 0, (long)P, H, A,
+                                   (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 double* mjmpc_workspace_q0(void* d_ws, int64_t P, int H, int A) {
@@ -1323,14 +1319,12 @@ int mjmpc_td_lambda_returns(int dtype, int64_t P, int H, int A, const void* d_co
                             void* d_ws, void* stream) {
     if (!d_costs || !d_returns || !d_ws || (H > 1 && !d_wseq)) return fail(MJMPC_E_BADARG, "null argument");
     if (alpha == 0 && (!d_actions || !d_mean || !d_covinv)) return fail(MJMPC_E_BADARG, "control cost needs actions, mean, cov^-1");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::td_lambda_returns<float>((const float*)d_costs, (const float*)d_actions, (const float*)d_qvals, d_mean,
-                                             d_covinv, d_wseq, wseq_has_zero, beta, alpha, gamma, td_lam, (long)P, H, A,
-                                             (float*)d_returns, (double*)d_ws, s),
-             mjmpc::td_lambda_returns<double>((const double*)d_costs, (const double*)d_actions, (const double*)d_qvals,
-                                              d_mean, d_covinv, d_wseq, wseq_has_zero, beta, alpha, gamma, td_lam,
-                                              (long)P, H, A, (double*)d_returns, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::td_lambda_returns<T>((const T*)d_costs, (const T*)d_actions, (const T*)d_qvals, d_mean, d_covinv, d_wseq,
+                                           wseq_has_zero, beta, alpha, gamma, td_lam, (long)P, H, A, (T*)d_returns,
+                                           (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_softmax_stats(int dtype, int64_t P, int H, int A, const void* d_costs, const void* d_actions,
@@ -1340,14 +1334,11 @@ int mjmpc_softmax_stats(int dtype, int64_t P, int H, int A, const void* d_costs,
     if (alpha == 0 && !d_covinv) return fail(MJMPC_E_BADARG, "alpha == 0 needs d_covinv");
     if (tbw && want_cov) return fail(MJMPC_E_BADARG, "time_based_weights and want_cov are exclusive");
     if (!(lam > 0)) return fail(MJMPC_E_BADARG, "lam must be positive");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::softmax_stats<float>((const float*)d_costs, (const float*)d_actions, d_mean, d_covinv, d_gseq,
-                                         gamma_zero, lam, alpha, tbw, want_cov, (long)P, H, A, d_record,
-                                         (double*)d_ws, s),
-             mjmpc::softmax_stats<double>((const double*)d_costs, (const double*)d_actions, d_mean, d_covinv, d_gseq,
-                                          gamma_zero, lam, alpha, tbw, want_cov, (long)P, H, A, d_record,
-                                          (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::softmax_stats<T>((const T*)d_costs, (const T*)d_actions, d_mean, d_covinv, d_gseq, gamma_zero, lam, alpha,
+                                       tbw, want_cov, (long)P, H, A, d_record, (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_softmax_combine(const double* d_records, int G, int H, int A, int tbw, double lam, double step_size,
@@ -1355,49 +1346,48 @@ int mjmpc_softmax_combine(const double* d_records, int G, int H, int A, int tbw,
                           double* d_wnorm, void* stream) {
     if (!d_records || !d_mean || G < 1) return fail(MJMPC_E_BADARG, "bad argument");
     if (cov_mode && !d_cov) return fail(MJMPC_E_BADARG, "cov_mode needs d_cov");
-    PLAIN(mjmpc::softmax_combine(d_records, G, H, A, tbw, lam, step_size, cov_mode, P_total, d_mean, d_cov, d_value,
-                                 d_wnorm, (hipStream_t)stream));
+    return plain(mjmpc::softmax_combine(d_records, G, H, A, tbw, lam, step_size, cov_mode, P_total, d_mean, d_cov, d_value,
+                                        d_wnorm, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_softmax_weights(int64_t P, int H, int A, const double* d_wnorm, void* d_ws, double* d_weights,
                           void* stream) {
     if (!d_wnorm || !d_ws || !d_weights) return fail(MJMPC_E_BADARG, "null argument");
-    PLAIN(mjmpc::softmax_weights((long)P, d_wnorm, (double*)d_ws, H, A, d_weights, (hipStream_t)stream));
+    return plain(mjmpc::softmax_weights((long)P, d_wnorm, (double*)d_ws, H, A, d_weights, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_cem_elite_sums(int dtype, int64_t P, int H, int A, const void* d_actions, const double* d_q_all,
                          int64_t P_all, int64_t offset, int64_t k, double* d_sum_record, void* d_ws, void* stream) {
     if (!d_actions || !d_sum_record || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::cem_elite_sums<float>((const float*)d_actions, d_q_all, (long)P_all, (long)offset, (long)k, (long)P,
-                                          H, A, d_sum_record, (double*)d_ws, s),
-             mjmpc::cem_elite_sums<double>((const double*)d_actions, d_q_all, (long)P_all, (long)offset, (long)k,
-                                           (long)P, H, A, d_sum_record, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::cem_elite_sums<T>((const T*)d_actions, d_q_all, (long)P_all, (long)offset, (long)k, (long)P, H, A,
+                                        d_sum_record, (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_cem_elite_cov(int dtype, int64_t P, int H, int A, const void* d_actions, const double* d_mean,
                         const double* d_sum_records, int G, double* d_cov_record, void* d_ws, void* stream) {
     if (!d_actions || !d_mean || !d_sum_records || !d_cov_record || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::cem_elite_cov<float>((const float*)d_actions, d_mean, d_sum_records, G, (long)P, H, A, d_cov_record,
-                                         (double*)d_ws, s),
-             mjmpc::cem_elite_cov<double>((const double*)d_actions, d_mean, d_sum_records, G, (long)P, H, A,
-                                          d_cov_record, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::cem_elite_cov<T>((const T*)d_actions, d_mean, d_sum_records, G, (long)P, H, A, d_cov_record,
+                                       (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_cem_final(const double* d_cov_records, int G, int64_t P, int H, int A, double n_elite, int full_cov,
                     double step_size, double* d_mean, double* d_cov, void* d_ws, void* stream) {
     if (!d_cov_records || !d_mean || !d_cov || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    PLAIN(mjmpc::cem_final(d_cov_records, G, (long)P, H, A, n_elite, full_cov, step_size, d_mean, d_cov,
-                           (double*)d_ws, (hipStream_t)stream));
+    return plain(mjmpc::cem_final(d_cov_records, G, (long)P, H, A, n_elite, full_cov, step_size, d_mean, d_cov,
+                                  (double*)d_ws, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_cem_combine(const double* d_records, int G, int H, int A, double n_elite, int full_cov, double step_size,
                       double* d_mean, double* d_cov, void* stream) {
     if (!d_records || !d_mean || !d_cov) return fail(MJMPC_E_BADARG, "null argument");
-    PLAIN(mjmpc::cem_combine(d_records, G, H, A, n_elite, full_cov, step_size, d_mean, d_cov, (hipStream_t)stream));
+    return plain(mjmpc::cem_combine(d_records, G, H, A, n_elite, full_cov, step_size, d_mean, d_cov, (hipStream_t)stream),
+                 __func__);
 }
 
 int mjmpc_cem_fused_supported(int64_t P_all, int64_t P, int64_t k, int H, int A) {
@@ -1410,17 +1400,17 @@ int mjmpc_cem_select_moments(int dtype, int64_t P, int H, int A, const void* d_a
     if (!d_actions || !d_mean || !d_cov || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
     if (!mjmpc::cem_fused_supported(d_q_all ? (long)P_all : (long)P, (long)P, (long)k, H, A))
         return fail(MJMPC_E_BADARG, "shape outside the fused CEM step (mjmpc_cem_fused_supported)");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::cem_select_moments<float>((const float*)d_actions, d_q_all, (long)P_all, (long)offset, (long)k, (long)P, H, A,
-                                              d_mean, d_cov, (const long long*)d_step_counter, (double*)d_ws, s),
-             mjmpc::cem_select_moments<double>((const double*)d_actions, d_q_all, (long)P_all, (long)offset, (long)k, (long)P, H,
-                                               A, d_mean, d_cov, (const long long*)d_step_counter, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::cem_select_moments<T>((const T*)d_actions, d_q_all, (long)P_all, (long)offset, (long)k, (long)P, H, A,
+                                            d_mean, d_cov, (const long long*)d_step_counter, (double*)d_ws,
+                                            (hipStream_t)stream);
+    });
 }
 
 int mjmpc_cem_record(int64_t P, int H, int A, int64_t k, const double* d_mean, double* d_record, void* d_ws, void* stream) {
     if (!d_mean || !d_record || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    PLAIN(mjmpc::cem_record((long)k, (long)P, H, A, d_mean, d_record, (double*)d_ws, (hipStream_t)stream));
+    return plain(mjmpc::cem_record((long)k, (long)P, H, A, d_mean, d_record, (double*)d_ws, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_cem_finish(int dtype, int64_t P, int H, int A, int64_t k, const double* d_records, int G, double n_elite,
@@ -1432,30 +1422,27 @@ int mjmpc_cem_finish(int dtype, int64_t P, int H, int A, int64_t k, const double
     if (shift_mode > 1) return fail(MJMPC_E_BADARG, "shift_mode must be < 0 (none), 0 (null) or 1 (repeat)");
     if (!mjmpc::cem_fused_supported((long)P, (long)P, (long)k, H, A))
         return fail(MJMPC_E_BADARG, "shape outside the fused CEM step (mjmpc_cem_fused_supported)");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::cem_finish<float>(d_records, G, (long)k, (long)P, H, A, n_elite, full_cov, step_size, shift_mode, d_mean, d_cov,
-                                      d_chol, d_status, d_grow_diag, grow_scale, d_action_out, h_action_pinned,
-                                      (long long*)d_step_counter, (float*)d_next_noise, seed, offset, (long)particle_offset,
-                                      (double*)d_ws, s),
-             mjmpc::cem_finish<double>(d_records, G, (long)k, (long)P, H, A, n_elite, full_cov, step_size, shift_mode, d_mean, d_cov,
-                                       d_chol, d_status, d_grow_diag, grow_scale, d_action_out, h_action_pinned,
-                                       (long long*)d_step_counter, (double*)d_next_noise, seed, offset, (long)particle_offset,
-                                       (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::cem_finish<T>(d_records, G, (long)k, (long)P, H, A, n_elite, full_cov, step_size, shift_mode, d_mean, d_cov,
+                                    d_chol, d_status, d_grow_diag, grow_scale, d_action_out, h_action_pinned,
+                                    (long long*)d_step_counter, (T*)d_next_noise, seed, offset, (long)particle_offset,
+                                    (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_rs_best(int dtype, int64_t P, int H, int A, const void* d_actions, int64_t offset, double* d_record,
                   void* d_ws, void* stream) {
     if (!d_actions || !d_record || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::rs_best<float>((const float*)d_actions, (long)offset, (long)P, H, A, d_record, (double*)d_ws, s),
-             mjmpc::rs_best<double>((const double*)d_actions, (long)offset, (long)P, H, A, d_record, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::rs_best<T>((const T*)d_actions, (long)offset, (long)P, H, A, d_record, (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_rs_combine(const double* d_records, int G, int H, int A, double step_size, double* d_mean, void* stream) {
     if (!d_records || !d_mean || G < 1) return fail(MJMPC_E_BADARG, "bad argument");
-    PLAIN(mjmpc::rs_combine(d_records, G, H, A, step_size, d_mean, (hipStream_t)stream));
+    return plain(mjmpc::rs_combine(d_records, G, H, A, step_size, d_mean, (hipStream_t)stream), __func__);
 }
 
 static int fused_update(int dtype, int64_t P, int H, int A, const double* d_q0, const void* d_actions, double lam,
@@ -1464,14 +1451,12 @@ static int fused_update(int dtype, int64_t P, int H, int A, const double* d_q0, 
                         const mjmpc::NextNoise* next) {
     if (!d_actions || !d_mean || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
     if (!(lam > 0) || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad lam / shift_mode");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::mppi_fused_update<float>(d_q0, (const float*)d_actions, lam, step_size, shift_mode, (long)P, H, A,
-                                             d_mean, d_action_out, d_record, d_value, (double*)d_ws, s, h_action_mapped,
-                                             (long long*)d_step_counter, next),
-             mjmpc::mppi_fused_update<double>(d_q0, (const double*)d_actions, lam, step_size, shift_mode, (long)P, H, A,
-                                              d_mean, d_action_out, d_record, d_value, (double*)d_ws, s,
-                                              h_action_mapped, (long long*)d_step_counter, next));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::mppi_fused_update<T>(d_q0, (const T*)d_actions, lam, step_size, shift_mode, (long)P, H, A, d_mean,
+                                           d_action_out, d_record, d_value, (double*)d_ws, (hipStream_t)stream,
+                                           h_action_mapped, (long long*)d_step_counter, next);
+    });
 }
 
 int mjmpc_mppi_fused_update(int dtype, int64_t P, int H, int A, const double* d_q0, const void* d_actions, double lam,
@@ -1496,8 +1481,7 @@ int mjmpc_mppi_fused_update_draw_next(int dtype, int64_t P, int H, int A, const 
 }
 
 int64_t mjmpc_update_batch_workspace_bytes(int E, int64_t P, int H, int A) {
-    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1)
-        return fail(MJMPC_E_BADARG, "bad batch shape E = %d, P = %lld, H = %d, A = %d", E, (long long)P, H, A);
+    if (int rc = batch_shape(E, P, H, A, INT_MAX, __func__)) return rc;
     return (int64_t)sizeof(double) * mjmpc::mppi_fused_batch_workspace_doubles(E, (long)P, H, A);
 }
 
@@ -1505,23 +1489,22 @@ int mjmpc_mppi_fused_update_batch(int dtype, int E, int64_t P, int H, int A, con
                                   const double* d_lam, const double* d_step_size, int shift_mode, double* d_means,
                                   double* d_actions_out, int64_t* d_step_counter, void* d_ws, void* stream) {
     if (!d_q0 || !d_actions || !d_lam || !d_step_size || !d_means || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
-    if (P < 1 || H < 1 || A < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d, A = %d", (long long)P, H, A);
+    if (int rc = batch_shape(E, P, H, A, INT_MAX, __func__)) return rc;
     if (shift_mode < -1 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::mppi_fused_update_batch<float>(E, d_q0, (const float*)d_actions, d_lam, d_step_size, shift_mode, (long)P, H, A,
-                                                   d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws, s),
-             mjmpc::mppi_fused_update_batch<double>(E, d_q0, (const double*)d_actions, d_lam, d_step_size, shift_mode, (long)P, H,
-                                                    A, d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::mppi_fused_update_batch<T>(E, d_q0, (const T*)d_actions, d_lam, d_step_size, shift_mode, (long)P, H, A,
+                                                 d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws,
+                                                 (hipStream_t)stream);
+    });
 }
 
 int mjmpc_cem_batch_supported(int E, int64_t P, int64_t k_max, int H, int A) {
     return mjmpc::cem_batch_supported(E, (long)P, (long)k_max, H, A) ? 1 : 0;
 }
 
-static int cem_batch_shape(int E, int64_t P, int64_t k_max, int H, int A) {
-    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
+static int cem_batch_shape(int E, int64_t P, int64_t k_max, int H, int A, const char* what) {
+    if (int rc = batch_shape(E, P, H, A, INT_MAX, what)) return rc;
     if (!mjmpc::cem_batch_supported(E, (long)P, (long)k_max, H, A))
         return fail(MJMPC_E_BADARG, "shape outside the batched fused CEM step (mjmpc_cem_batch_supported): P = %lld, "
                     "k_max = %lld, H = %d, A = %d; it takes A <= 8, A <= H + 1, P <= 32768, 1 <= k <= P",
@@ -1530,7 +1513,7 @@ static int cem_batch_shape(int E, int64_t P, int64_t k_max, int H, int A) {
 }
 
 int64_t mjmpc_cem_batch_workspace_bytes(int E, int64_t P, int64_t k_max, int H, int A) {
-    if (int rc = cem_batch_shape(E, P, k_max, H, A)) return rc;
+    if (int rc = cem_batch_shape(E, P, k_max, H, A, __func__)) return rc;
     return (int64_t)sizeof(double) * mjmpc::cem_batch_workspace_doubles(E, (long)P, H, A);
 }
 
@@ -1538,13 +1521,13 @@ int mjmpc_cem_select_moments_batch(int dtype, int E, int64_t P, int H, int A, co
                                    const int64_t* d_k, const double* d_means, const double* d_covs,
                                    const int64_t* d_step_counter, void* d_ws, void* stream) {
     if (!d_actions || !d_q0 || !d_k || !d_means || !d_covs || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    if (int rc = cem_batch_shape(E, P, 1, H, A)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::cem_select_moments_batch<float>(E, (const float*)d_actions, d_q0, (const long long*)d_k, (long)P, H, A, d_means,
-                                                    d_covs, (const long long*)d_step_counter, (double*)d_ws, s),
-             mjmpc::cem_select_moments_batch<double>(E, (const double*)d_actions, d_q0, (const long long*)d_k, (long)P, H, A,
-                                                     d_means, d_covs, (const long long*)d_step_counter, (double*)d_ws, s));
+    if (int rc = cem_batch_shape(E, P, 1, H, A, __func__)) return rc;
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::cem_select_moments_batch<T>(E, (const T*)d_actions, d_q0, (const long long*)d_k, (long)P, H, A, d_means,
+                                                  d_covs, (const long long*)d_step_counter, (double*)d_ws,
+                                                  (hipStream_t)stream);
+    });
 }
 
 int mjmpc_cem_finish_batch(int dtype, int E, int64_t P, int H, int A, const int64_t* d_k, int full_cov,
@@ -1555,17 +1538,14 @@ int mjmpc_cem_finish_batch(int dtype, int E, int64_t P, int H, int A, const int6
     if (!d_k || !d_step_size || !d_means || !d_covs || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
     if (d_next_noise && !d_seeds) return fail(MJMPC_E_BADARG, "d_next_noise without d_seeds");
     if (shift_mode > 1) return fail(MJMPC_E_BADARG, "shift_mode must be < 0 (none), 0 (null) or 1 (repeat)");
-    if (int rc = cem_batch_shape(E, P, 1, H, A)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::cem_finish_batch<float>(E, (const long long*)d_k, (long)P, H, A, full_cov, d_step_size, shift_mode, d_means,
-                                            d_covs, d_chols, d_status, d_grow_diag, d_grow_scale, d_actions_out,
-                                            (long long*)d_step_counter, (float*)d_next_noise,
-                                            (const unsigned long long*)d_seeds, offset, (double*)d_ws, s),
-             mjmpc::cem_finish_batch<double>(E, (const long long*)d_k, (long)P, H, A, full_cov, d_step_size, shift_mode, d_means,
-                                             d_covs, d_chols, d_status, d_grow_diag, d_grow_scale, d_actions_out,
-                                             (long long*)d_step_counter, (double*)d_next_noise,
-                                             (const unsigned long long*)d_seeds, offset, (double*)d_ws, s));
+    if (int rc = cem_batch_shape(E, P, 1, H, A, __func__)) return rc;
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::cem_finish_batch<T>(E, (const long long*)d_k, (long)P, H, A, full_cov, d_step_size, shift_mode, d_means,
+                                          d_covs, d_chols, d_status, d_grow_diag, d_grow_scale, d_actions_out,
+                                          (long long*)d_step_counter, (T*)d_next_noise, (const unsigned long long*)d_seeds,
+                                          offset, (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_mppi_fused_combine(const double* d_records, int G, double P_total, int H, int A, double lam, double step_size,
@@ -1573,18 +1553,19 @@ int mjmpc_mppi_fused_combine(const double* d_records, int G, double P_total, int
                              double* h_action_mapped, int64_t* d_step_counter, void* stream) {
     if (!d_records || !d_mean || G < 1) return fail(MJMPC_E_BADARG, "null argument");
     if (!(lam > 0) || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad lam / shift_mode");
-    PLAIN(mjmpc::mppi_fused_combine(d_records, G, P_total, lam, step_size, shift_mode, H, A, d_mean, d_action_out, d_value,
-                                    h_action_mapped, (long long*)d_step_counter, (hipStream_t)stream));
+    return plain(mjmpc::mppi_fused_combine(d_records, G, P_total, lam, step_size, shift_mode, H, A, d_mean, d_action_out,
+                                           d_value, h_action_mapped, (long long*)d_step_counter, (hipStream_t)stream),
+                 __func__);
 }
 
 int mjmpc_q0_sum(int64_t P, int H, int A, double* d_out, void* d_ws, void* stream) {
     if (!d_out || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    PLAIN(mjmpc::q0_sum((long)P, H, A, d_out, (double*)d_ws, (hipStream_t)stream));
+    return plain(mjmpc::q0_sum((long)P, H, A, d_out, (double*)d_ws, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_shift_mean(double* d_mean, int H, int A, int mode, const double* d_row, void* stream) {
     if (!d_mean || (mode == 2 && !d_row) || mode < 0 || mode > 2) return fail(MJMPC_E_BADARG, "bad argument");
-    PLAIN(mjmpc::shift_mean(d_mean, H, A, mode, d_row, (hipStream_t)stream));
+    return plain(mjmpc::shift_mean(d_mean, H, A, mode, d_row, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_step_tail(double* d_mean, int H, int A, int shift_mode, const double* d_row, double* d_action_out,
@@ -1592,30 +1573,24 @@ int mjmpc_step_tail(double* d_mean, int H, int A, int shift_mode, const double* 
                     double cov_scale, void* stream) {
     if (!d_mean || (shift_mode == 2 && !d_row) || shift_mode < 0 || shift_mode > 2 || A < 1 || A > 64 || H < 1)
         return fail(MJMPC_E_BADARG, "bad argument");
-    PLAIN(mjmpc::step_tail(d_mean, H, A, shift_mode, d_row, d_action_out, h_action_mapped, (long long*)d_step_counter,
-                           d_cov, d_cov_diag, cov_scale, (hipStream_t)stream));
+    return plain(mjmpc::step_tail(d_mean, H, A, shift_mode, d_row, d_action_out, h_action_mapped, (long long*)d_step_counter,
+                                  d_cov, d_cov_diag, cov_scale, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_cholesky_lower(const double* d_cov, int A, double* d_chol, int* d_status, void* stream) {
     if (!d_cov || !d_chol || A < 1 || A > 64) return fail(MJMPC_E_BADARG, "bad argument (A <= 64)");
-    PLAIN(mjmpc::cholesky_lower(d_cov, A, d_chol, d_status, (hipStream_t)stream));
+    return plain(mjmpc::cholesky_lower(d_cov, A, d_chol, d_status, (hipStream_t)stream), __func__);
 }
 
-static int dmd_batch_shape(int E, int64_t P, int H, int A) {
-    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
-    if (A < 1 || A > 64) return fail(MJMPC_E_BADARG, "A = %d outside 1 .. 64 (the Cholesky kernel's limit)", A);
-    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d", (long long)P, H);
-    return 0;
-}
-
+// (A <= 64 below: the Cholesky kernel and the tail take a thread per action channel of one wavefront)
 int mjmpc_cholesky_lower_batch(int E, const double* d_covs, int A, double* d_chols, int* d_status, void* stream) {
     if (!d_covs || !d_chols) return fail(MJMPC_E_BADARG, "null argument");
-    if (int rc = dmd_batch_shape(E, 1, 1, A)) return rc;
-    PLAIN(mjmpc::cholesky_lower_batch(E, d_covs, A, d_chols, d_status, (hipStream_t)stream));
+    if (int rc = batch_shape(E, 1, 1, A, 64, __func__)) return rc;
+    return plain(mjmpc::cholesky_lower_batch(E, d_covs, A, d_chols, d_status, (hipStream_t)stream), __func__);
 }
 
 int64_t mjmpc_dmd_batch_workspace_bytes(int E, int64_t P, int H, int A) {
-    if (int rc = dmd_batch_shape(E, P, H, A)) return rc;
+    if (int rc = batch_shape(E, P, H, A, 64, __func__)) return rc;
     return (int64_t)sizeof(double) * mjmpc::dmd_batch_workspace_doubles(E, (long)P, H, A);
 }
 
@@ -1625,34 +1600,30 @@ int mjmpc_dmd_update_batch(int dtype, int E, int64_t P, int H, int A, const void
                            int64_t* d_step_counter, void* d_ws, void* stream) {
     if (!d_costs || !d_actions || !d_gseq || !d_lam || !d_step_size || !d_beta || !d_means || !d_covs || !d_ws)
         return fail(MJMPC_E_BADARG, "null argument");
-    if (int rc = dmd_batch_shape(E, P, H, A)) return rc;
+    if (int rc = batch_shape(E, P, H, A, 64, __func__)) return rc;
     if (cov_mode != 1 && cov_mode != 2) return fail(MJMPC_E_BADARG, "cov_mode %d (1 diagonal, 2 full)", cov_mode);
     if (shift_mode < 0 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::dmd_update_batch<float>(E, (const float*)d_costs, (const float*)d_actions, d_gseq, d_lam, d_step_size,
-                                            cov_mode, d_beta, shift_mode, (long)P, H, A, d_means, d_covs, d_actions_out,
-                                            (long long*)d_step_counter, (double*)d_ws, s),
-             mjmpc::dmd_update_batch<double>(E, (const double*)d_costs, (const double*)d_actions, d_gseq, d_lam, d_step_size,
-                                             cov_mode, d_beta, shift_mode, (long)P, H, A, d_means, d_covs, d_actions_out,
-                                             (long long*)d_step_counter, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::dmd_update_batch<T>(E, (const T*)d_costs, (const T*)d_actions, d_gseq, d_lam, d_step_size, cov_mode, d_beta,
+                                          shift_mode, (long)P, H, A, d_means, d_covs, d_actions_out,
+                                          (long long*)d_step_counter, (double*)d_ws, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_mppiq_batch_supported(int E, int64_t P, int H, int A, int time_based_weights) {
     return mjmpc::mppiq_batch_supported(E, (long)P, H, A, time_based_weights) ? 1 : 0;
 }
 
-static int mppiq_batch_shape(int E, int64_t P, int H, int A, int tbw) {
-    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
-    if (A < 1 || A > 64) return fail(MJMPC_E_BADARG, "A = %d outside 1 .. 64 (the tail's limit)", A);
-    if (P < 1 || H < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d", (long long)P, H);
+static int mppiq_batch_shape(int E, int64_t P, int H, int A, int tbw, const char* what) {
+    if (int rc = batch_shape(E, P, H, A, 64, what)) return rc;
     if (!mjmpc::mppiq_batch_supported(E, (long)P, H, A, tbw))
         return fail(MJMPC_E_BADARG, "H = %d above 512 with time-based weights (mjmpc_mppiq_batch_supported)", H);
     return 0;
 }
 
 int64_t mjmpc_mppiq_batch_workspace_bytes(int E, int64_t P, int H, int A, int time_based_weights) {
-    if (int rc = mppiq_batch_shape(E, P, H, A, time_based_weights)) return rc;
+    if (int rc = mppiq_batch_shape(E, P, H, A, time_based_weights, __func__)) return rc;
     return (int64_t)sizeof(double) * mjmpc::mppiq_batch_workspace_doubles(E, (long)P, H, A, time_based_weights);
 }
 
@@ -1663,20 +1634,18 @@ int mjmpc_mppiq_update_batch(int dtype, int E, int64_t P, int H, int A, const vo
                              int64_t* d_step_counter, void* d_ws, void* stream) {
     if (!d_costs || !d_actions || !d_beta || !d_step_size || !d_td_lam || !d_wseq || !d_wseq_has_zero || !d_means || !d_ws)
         return fail(MJMPC_E_BADARG, "null argument");
-    if (int rc = mppiq_batch_shape(E, P, H, A, time_based_weights)) return rc;
+    if (int rc = mppiq_batch_shape(E, P, H, A, time_based_weights, __func__)) return rc;
     if (alpha != 0 && alpha != 1) return fail(MJMPC_E_BADARG, "alpha %d (0: control cost on, 1: off)", alpha);
     if (alpha == 0 && !d_covinv) return fail(MJMPC_E_BADARG, "alpha = 0 needs d_covinv");
     if (shift_mode < 0 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
     const double* covinv = alpha == 0 ? d_covinv : nullptr;
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::mppiq_update_batch<float>(E, (const float*)d_costs, (const float*)d_actions, d_beta, d_step_size, d_td_lam,
-                                              d_wseq, d_wseq_has_zero, gamma, covinv, time_based_weights, shift_mode, (long)P,
-                                              H, A, d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws, s),
-             mjmpc::mppiq_update_batch<double>(E, (const double*)d_costs, (const double*)d_actions, d_beta, d_step_size,
-                                               d_td_lam, d_wseq, d_wseq_has_zero, gamma, covinv, time_based_weights,
-                                               shift_mode, (long)P, H, A, d_means, d_actions_out,
-                                               (long long*)d_step_counter, (double*)d_ws, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::mppiq_update_batch<T>(E, (const T*)d_costs, (const T*)d_actions, d_beta, d_step_size, d_td_lam, d_wseq,
+                                            d_wseq_has_zero, gamma, covinv, time_based_weights, shift_mode, (long)P, H, A,
+                                            d_means, d_actions_out, (long long*)d_step_counter, (double*)d_ws,
+                                            (hipStream_t)stream);
+    });
 }
 
 int mjmpc_rs_batch_supported(int E, int64_t P, int H, int A) { return mjmpc::rs_batch_supported(E, (long)P, H, A) ? 1 : 0; }
@@ -1685,36 +1654,36 @@ int mjmpc_rs_update_batch(int dtype, int E, int64_t P, int H, int A, const doubl
                           const double* d_step_size, int shift_mode, double* d_means, double* d_actions_out,
                           int64_t* d_step_counter, int64_t* d_best, void* stream) {
     if (!d_q0 || !d_actions || !d_step_size || !d_means) return fail(MJMPC_E_BADARG, "null argument");
-    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
-    if (P < 1 || H < 1 || A < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d, A = %d", (long long)P, H, A);
+    if (int rc = batch_shape(E, P, H, A, INT_MAX, __func__)) return rc;
     if (!mjmpc::rs_batch_supported(E, (long)P, H, A))
         return fail(MJMPC_E_BADARG, "A = %d outside 1 .. 256 (mjmpc_rs_batch_supported)", A);
     if (shift_mode < 0 || shift_mode > 1) return fail(MJMPC_E_BADARG, "bad shift_mode %d", shift_mode);
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::rs_update_batch<float>(E, d_q0, (const float*)d_actions, d_step_size, shift_mode, (long)P, H, A, d_means,
-                                           d_actions_out, (long long*)d_step_counter, (long long*)d_best, s),
-             mjmpc::rs_update_batch<double>(E, d_q0, (const double*)d_actions, d_step_size, shift_mode, (long)P, H, A, d_means,
-                                            d_actions_out, (long long*)d_step_counter, (long long*)d_best, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::rs_update_batch<T>(E, d_q0, (const T*)d_actions, d_step_size, shift_mode, (long)P, H, A, d_means,
+                                         d_actions_out, (long long*)d_step_counter, (long long*)d_best, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_cov_add_diag(double* d_cov, int A, const double* d_diag, double scale, void* stream) {
     if (!d_cov || A < 1 || A > 64) return fail(MJMPC_E_BADARG, "bad argument (A <= 64)");
-    PLAIN(mjmpc::cov_add_diag(d_cov, A, d_diag, scale, (hipStream_t)stream));
+    return plain(mjmpc::cov_add_diag(d_cov, A, d_diag, scale, (hipStream_t)stream), __func__);
 }
 
 int mjmpc_filter_noise(int dtype, void* d_noise, int64_t P, int H, int A, const double* d_coeffs, void* stream) {
     if (!d_noise || !d_coeffs) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype, mjmpc::filter_noise<float>((float*)d_noise, (long)P, H, A, d_coeffs, s),
-             mjmpc::filter_noise<double>((double*)d_noise, (long)P, H, A, d_coeffs, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::filter_noise<T>((T*)d_noise, (long)P, H, A, d_coeffs, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_color_noise(int dtype, void* d_noise, int64_t rows, int A, const double* d_B, void* stream) {
     if (!d_noise || !d_B) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype, mjmpc::color_rows<float>((float*)d_noise, (long)rows, A, d_B, s),
-             mjmpc::color_rows<double>((double*)d_noise, (long)rows, A, d_B, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::color_rows<T>((T*)d_noise, (long)rows, A, d_B, (hipStream_t)stream);
+    });
 }
 
 int64_t mjmpc_mt19937_workspace_bytes(int64_t n_normals) { return (int64_t)mjmpc::mt_workspace_bytes((long)n_normals); }
@@ -1722,12 +1691,11 @@ int64_t mjmpc_mt19937_workspace_bytes(int64_t n_normals) { return (int64_t)mjmpc
 int mjmpc_sample_noise_mt19937(int dtype, void* d_noise, int64_t n_normals, double scale, uint64_t seed,
                                const int64_t* d_step, void* d_ws, int* d_status, void* stream) {
     if (!d_noise || !d_ws) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::sample_noise_mt19937<float>((float*)d_noise, (long)n_normals, scale, seed, (const long long*)d_step,
-                                                d_ws, d_status, s),
-             mjmpc::sample_noise_mt19937<double>((double*)d_noise, (long)n_normals, scale, seed,
-                                                 (const long long*)d_step, d_ws, d_status, s));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::sample_noise_mt19937<T>((T*)d_noise, (long)n_normals, scale, seed, (const long long*)d_step, d_ws,
+                                              d_status, (hipStream_t)stream);
+    });
 }
 
 int64_t mjmpc_mt19937_stream_words(int64_t n_normals) { return 4 * (int64_t)mjmpc::mt_attempts_for((long)n_normals); }
@@ -1745,54 +1713,47 @@ int mjmpc_sample_noise_mt19937_jump(int dtype, void* d_noise, int64_t n_normals,
         if (head_words + seg_words * (int64_t)n_segments < mjmpc_mt19937_stream_words(first_normal + n_normals))
             return fail(MJMPC_E_BADARG, "segments do not cover the stream");
     }
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::sample_noise_mt19937<float>((float*)d_noise, (long)n_normals, scale, seed, (const long long*)d_step,
-                                                d_ws, d_status, s, d_jump_idx, d_jump_starts, (long)head_words,
-                                                (long)seg_words, n_segments, (long)first_normal),
-             mjmpc::sample_noise_mt19937<double>((double*)d_noise, (long)n_normals, scale, seed,
-                                                 (const long long*)d_step, d_ws, d_status, s, d_jump_idx, d_jump_starts,
-                                                 (long)head_words, (long)seg_words, n_segments, (long)first_normal));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::sample_noise_mt19937<T>((T*)d_noise, (long)n_normals, scale, seed, (const long long*)d_step, d_ws,
+                                              d_status, (hipStream_t)stream, d_jump_idx, d_jump_starts, (long)head_words,
+                                              (long)seg_words, n_segments, (long)first_normal);
+    });
 }
 
 int mjmpc_sample_noise(int dtype, void* d_noise, int64_t P, int H, int A, const double* d_chol,
                        const double* d_coeffs, uint64_t seed, uint64_t offset, int64_t particle_offset,
                        const int64_t* d_step, int chol_is_diagonal, void* stream) {
     if (!d_noise || !d_chol) return fail(MJMPC_E_BADARG, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::sample_noise<float>((float*)d_noise, (long)P, H, A, d_chol, d_coeffs, seed, offset,
-                                        (long)particle_offset, (const long long*)d_step, s, chol_is_diagonal),
-             mjmpc::sample_noise<double>((double*)d_noise, (long)P, H, A, d_chol, d_coeffs, seed, offset,
-                                         (long)particle_offset, (const long long*)d_step, s, chol_is_diagonal));
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::sample_noise<T>((T*)d_noise, (long)P, H, A, d_chol, d_coeffs, seed, offset, (long)particle_offset,
+                                      (const long long*)d_step, (hipStream_t)stream, chol_is_diagonal);
+    });
 }
 
 int mjmpc_sample_noise_batch(int dtype, int E, void* d_noise, int64_t P, int H, int A, const double* d_chols,
                              const uint64_t* d_seeds, uint64_t offset, const int64_t* d_step, void* stream) {
     if (!d_noise || !d_chols || !d_seeds) return fail(MJMPC_E_BADARG, "null argument");
-    if (E < 1 || E > 65535) return fail(MJMPC_E_BADARG, "%d episodes outside 1 .. 65535", E);
-    if (P < 1 || H < 1 || A < 1) return fail(MJMPC_E_BADARG, "bad sizes P = %lld, H = %d, A = %d", (long long)P, H, A);
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::sample_noise_batch<float>((float*)d_noise, E, (long)P, H, A, d_chols, (const unsigned long long*)d_seeds,
-                                              offset, (const long long*)d_step, s),
-             mjmpc::sample_noise_batch<double>((double*)d_noise, E, (long)P, H, A, d_chols, (const unsigned long long*)d_seeds,
-                                               offset, (const long long*)d_step, s));
+    if (int rc = batch_shape(E, P, H, A, INT_MAX, __func__)) return rc;
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::sample_noise_batch<T>((T*)d_noise, E, (long)P, H, A, d_chols, (const unsigned long long*)d_seeds, offset,
+                                            (const long long*)d_step, (hipStream_t)stream);
+    });
 }
 
 int mjmpc_sample_noise_cov_batch(int dtype, int E, void* d_noise, int64_t P, int H, int A, const double* d_chols,
                                  const double* d_coeffs, const uint64_t* d_seeds, uint64_t offset, const int64_t* d_step,
                                  int chol_is_diagonal, void* stream) {
     if (!d_noise || !d_chols || !d_seeds) return fail(MJMPC_E_BADARG, "null argument");
-    if (int rc = dmd_batch_shape(E, P, H, A)) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH(dtype,
-             mjmpc::sample_noise_cov_batch<float>((float*)d_noise, E, (long)P, H, A, d_chols, d_coeffs,
-                                                  (const unsigned long long*)d_seeds, offset, (const long long*)d_step, s,
-                                                  chol_is_diagonal),
-             mjmpc::sample_noise_cov_batch<double>((double*)d_noise, E, (long)P, H, A, d_chols, d_coeffs,
-                                                   (const unsigned long long*)d_seeds, offset, (const long long*)d_step, s,
-                                                   chol_is_diagonal));
+    if (int rc = batch_shape(E, P, H, A, 64, __func__)) return rc;
+    return with_dtype(dtype, __func__, [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::sample_noise_cov_batch<T>((T*)d_noise, E, (long)P, H, A, d_chols, d_coeffs,
+                                                (const unsigned long long*)d_seeds, offset, (const long long*)d_step,
+                                                (hipStream_t)stream, chol_is_diagonal);
+    });
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@
 // atomics on floating point, so results are bit-reproducible run to run and identical on all ranks.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <type_traits>
 
 #include "noise_device.h"
@@ -30,7 +31,7 @@ __device__ __forceinline__ double wave_max(double v) {
 // x[p][tw] = (-1/lam) * (cost_to_go(costs)[p][tw] + lam * cost_to_go(ctrl_cost)[p][tw]),  tw < Hw
 // q0[p]    = cost_to_go(costs)[p][0]                                    (optional output)
 // cost_to_go follows mjmpc/utils/control_utils.py:37-46 in the same summation order.
-// (particle p's part; the body is shared with the episode-batch kernel dmd_x_colmax_batch_kernel below)
+// (particle p's part; the body is shared with the episode-batch kernel softmax_x_batch_kernel below)
 template <typename T>
 __device__ __forceinline__ void traj_cost_body(const T* __restrict__ costs, const T* __restrict__ actions,
                                                const double* __restrict__ mean, const double* __restrict__ un,
@@ -85,7 +86,7 @@ __global__ void traj_cost_kernel(const T* __restrict__ costs, const T* __restric
 //   td[t]    = total[t] + gamma q[t+1] - q[t],  t < H-1;   q = qvals, or 0 with q[H-1] = total[H-1]
 //   out[t]   = q[t] + td_lam * cost_to_go(td, wseq)[t],    out[H-1] = q[H-1]
 // cost_to_go in the order of control_utils.py:37-46 (reverse running sum, then / wseq; unchanged if wseq has a 0).
-// (particle p's part; the body is shared with the episode-batch kernel mppiq_returns_x_batch_kernel below)
+// (particle p's part; the body is shared with the episode-batch kernel softmax_x_batch_kernel below)
 template <typename T>
 __device__ __forceinline__ void td_lambda_body(const T* __restrict__ costs, const T* __restrict__ actions,
                                                const T* __restrict__ qvals, const double* __restrict__ mean,
@@ -134,7 +135,7 @@ __global__ void td_lambda_kernel(const T* __restrict__ costs, const T* __restric
 }
 
 // u_n = mean . cov^-1      (mppi.py:106)
-// (entry j's part; the body is shared with the episode-batch kernel mppiq_returns_x_batch_kernel below)
+// (entry j's part; the body is shared with the episode-batch kernel softmax_x_batch_kernel below)
 __device__ __forceinline__ void un_body(const double* __restrict__ mean, const double* __restrict__ covinv, int A, int j,
                                         double* __restrict__ un) {
     const int t = j / A, a = j % A;
@@ -237,7 +238,7 @@ __global__ void softmax_record_kernel(const double* __restrict__ partial, const 
 
 // mean <- (1-eta) mean + eta * sum_g sc_g W_g / sum_g sc_g S_g,   sc_g = exp(xmax_g - max_g xmax_g);
 // cov likewise (mode 1: diagonal only, 2: full); value = -lam * logsumexp(x, b = 1/P_total).
-// (entry j's part; the body is shared with the episode-batch kernel dmd_finish_batch_kernel below)
+// (entry j's part; the body is shared with the episode-batch kernel softmax_finish_batch_kernel below)
 __device__ __forceinline__ void softmax_combine_body(const double* __restrict__ records, int G, int H, int A, int Hw,
                                                      double lam, double step, int cov_mode, double P_total,
                                                      double* __restrict__ mean, double* __restrict__ cov,
@@ -1246,7 +1247,7 @@ __global__ void shift_kernel(double* __restrict__ mean, int H, int A, int mode, 
 // The tail of a control step in one launch: read the action out (mean[0] -> device copy and mapped host copy), shift the
 // horizon, advance the device step counter, and grow the covariance by scale * diag(d) (the shift of CEM / DMD-MPC with
 // update_cov) - five stream operations of ~5 us each when issued one by one.  Any of the outputs may be null.
-// (the body is shared with the episode-batch kernel dmd_finish_batch_kernel below)
+// (the body is shared with the episode-batch kernel softmax_finish_batch_kernel below)
 __device__ __forceinline__ void step_tail_body(double* __restrict__ mean, int H, int A, int mode,
                                                const double* __restrict__ row, double* __restrict__ action_out,
                                                double* __restrict__ action_host, long long* __restrict__ step_counter,
@@ -1529,160 +1530,101 @@ __global__ void fused_final_batch_kernel(const double* __restrict__ partial, lon
                      action_out ? action_out + e * A : nullptr, nullptr, nullptr, nullptr, e == 0 ? step_counter : nullptr);
 }
 
-// ---- episode batches of the covariance-adapting DMD-MPC step --------------------------------------------------
-// Grid row e of every launch runs the text of the single path's kernels - traj_cost_body, colmax_kernel's maximum,
-// softmax_partial_body, wave_entry_sum, softmax_combine_body, step_tail_body - on episode e's slices.
+// ---- softmax episode batches: the covariance-adapting DMD-MPC step and the MPPIQ step -----------
+// Grid row e of every launch runs the text of the single path's kernels - un_body, td_lambda_body (the optional returns
+// stage), traj_cost_body, the column maxima, softmax_partial_body, wave_entry_sum, softmax_combine_body, step_tail_body - on
+// episode e's slices, with Hw = H weight columns (time-based weights) or one.
 // -- one episode's block of the batch workspace, laid out alike on host and device:
-// x[P] | xmax (padded to 8) | record [2 + HA + AA] | partials [nb][1 + HA + AA]
-struct DmdRow {
-    double *x, *xmax, *record, *partial;
-    __host__ __device__ DmdRow(double* base, long P, int HA, int AA) {
-        x = base;
-        xmax = x + P;
-        record = xmax + 8;
-        partial = record + 2 + HA + AA;
-    }
-};
-__host__ __device__ inline long dmd_row_doubles(long P, int HA, int AA, int nb) {
-    return P + 8 + (2 + HA + AA) + (long)nb * (1 + HA + AA);
-}
-template <typename T>
-struct DmdBatch {
-    const T *costs, *actions;
-    const double *gseq, *lam, *step, *beta;
-    double *means, *covs, *actions_out, *ws;
-    long long* step_counter;
-    const double* un;           // (null: the control cost is off, alpha = 1 - a run-time null, as the single launch gets it)
-    double* q0;                 // (null: nobody reads the batch's cost-to-go)
-    long stride, P;
-    int H, A, nb, chunk, gamma_zero, want_cov, cov_mode, shift_mode, G;
-};
-
-// row e: x = traj_cost_kernel's (one weight per particle, Hw = 1) for its P particles, then colmax_kernel's maximum of them
-template <typename T>
-__global__ void dmd_x_colmax_batch_kernel(DmdBatch<T> b) {
-    __shared__ double sm[BLK / 64];
-    const long e = blockIdx.y, P = b.P;
-    const int HA = b.H * b.A;
-    const DmdRow r(b.ws + e * b.stride, P, HA, b.A * b.A);
-    for (long p = threadIdx.x; p < P; p += blockDim.x)
-        traj_cost_body<T>(b.costs + e * P * b.H, b.actions + e * P * HA, b.means + e * HA, b.un, b.gseq, b.gamma_zero,
-                          b.lam[e], p, b.H, b.A, 1, r.x, b.q0);
-    __syncthreads();
-    double m = -INFINITY;
-    for (long p = threadIdx.x; p < P; p += blockDim.x) m = fmax(m, r.x[p]);
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < BLK / 64; ++w) m = fmax(m, sm[w]);
-        r.xmax[0] = m;
-    }
-}
-
-// row e: softmax_partial_kernel on its particles (the same chunks, the mean from before the update) into its partials
-template <typename T>
-__global__ void softmax_partial_batch_kernel(DmdBatch<T> b) {
-    const long e = blockIdx.y;
-    const int HA = b.H * b.A;
-    const DmdRow r(b.ws + e * b.stride, b.P, HA, b.A * b.A);
-    softmax_partial_body<T>(r.x, r.xmax, b.actions + e * b.P * HA, b.means + e * HA, b.P, b.H, b.A, 1, b.chunk, b.want_cov,
-                            r.partial);
-}
-
-// row e: softmax_record_kernel (a wavefront per entry: wave_entry_sum over its nb partials), softmax_combine_kernel with that
-// one record, step_tail_kernel - one workgroup, a barrier where the single path has a launch boundary.  Row 0 advances the
-// shared step counter; no row reads it.
-template <typename T>
-__global__ void dmd_finish_batch_kernel(DmdBatch<T> b) {
-    const long e = blockIdx.y;
-    const int H = b.H, A = b.A, HA = H * A, AA = A * A, rec = 1 + HA + AA;
-    const DmdRow r(b.ws + e * b.stride, b.P, HA, AA);
-    for (int j = threadIdx.x >> 6; j < rec; j += blockDim.x >> 6) {
-        const double s = wave_entry_sum(r.partial, b.nb, rec, j);
-        if ((threadIdx.x & 63) == 0) {
-            r.record[1 + j] = s;
-            if (j < 1) r.record[j] = r.xmax[j];
-        }
-    }
-    __syncthreads();
-    double* mean = b.means + e * HA;
-    double* cov = b.covs + e * AA;
-    const int n = HA > AA ? HA : AA;
-    for (int j = threadIdx.x; j < n; j += blockDim.x)
-        softmax_combine_body(r.record, b.G, H, A, 1, b.lam[e], b.step[e], b.cov_mode, (double)b.P, mean, cov, nullptr, nullptr, j);
-    __syncthreads();
-    step_tail_body(mean, H, A, b.shift_mode, nullptr, b.actions_out ? b.actions_out + e * A : nullptr, nullptr,
-                   e == 0 ? b.step_counter : nullptr, cov, nullptr, b.beta[e]);
-}
-
-// ---- episode batches of the MPPIQ step --------------------------------------------------------------------------
-// Grid row e of every launch runs the text of the single path's kernels - un_body, td_lambda_body, traj_cost_body, the column
-// maxima, softmax_partial_body, wave_entry_sum, softmax_combine_body, step_tail_body - on episode e's slices, with
-// Hw = H weight columns (time-based weights) or one.
-// -- one episode's block of the batch workspace, laid out alike on host and device:
-// un[HA] | returns [P][H] (dtype T, in P H doubles of room) | x[P Hw] | xmax[Hw] | record [2 Hw + HA + AA] |
-// partials [nb][Hw + HA + AA]
-struct MppiqRow {
+// un[HA] | returns [P][H] (dtype T, in P H doubles of room; only with a returns stage) | x[P Hw] | xmax[Hw] |
+// record [2 Hw + HA + AA] | partials [nb][Hw + HA + AA]
+struct SoftmaxRow {
     double *un, *returns, *x, *xmax, *record, *partial;
-    __host__ __device__ MppiqRow(double* base, long P, int H, int A, int Hw) {
+    __host__ __device__ SoftmaxRow(double* base, long P, int H, int A, int Hw, int with_returns) {
         const long HA = (long)H * A, AA = (long)A * A;
         un = base;
         returns = un + HA;
-        x = returns + P * H;
+        x = returns + (with_returns ? P * H : 0);
         xmax = x + P * Hw;
         record = xmax + Hw;
         partial = record + 2 * Hw + HA + AA;
     }
 };
-__host__ __device__ inline long mppiq_row_doubles(long P, int H, int A, int Hw, int nb) {
+__host__ __device__ inline long softmax_row_doubles(long P, int H, int A, int Hw, int with_returns, int nb) {
     const long HA = (long)H * A, AA = (long)A * A;
-    return HA + P * H + P * Hw + Hw + (2 * Hw + HA + AA) + (long)nb * (Hw + HA + AA);
+    return HA + (with_returns ? P * H : 0) + P * Hw + Hw + (2 * Hw + HA + AA) + (long)nb * (Hw + HA + AA);
 }
 template <typename T>
-struct MppiqBatch {
+struct SoftmaxBatch {
     const T *costs, *actions;
-    const double *beta, *step, *td_lam, *wseq, *covinv;    // (covinv null: the control cost is off, alpha = 1)
+    const double *temp, *step;          // per episode: the temperature (DMD-MPC's lam, MPPIQ's beta) and the step size
+    // the returns stage (wseq null: none - the weights are formed from the costs)
+    const double *td_lam, *wseq, *covinv;       // (covinv null: its control cost is off, alpha = 1)
     const int* wseq_zero;
-    // (run-time nulls and a run-time 1, as the single launches get them: no Q estimates; the weights' own control cost off,
-    // no discount sequence and gamma_zero - the returns are per-step values already)
+    double gamma;
+    // (run-time nulls and a run-time 1, as the single launches get them: no Q estimates; the weights' own control cost off
+    // (alpha = 1); nobody reads the batch's cost-to-go; after a returns stage no discount sequence and gamma_zero - the
+    // returns are per-step values already)
     const T* qvals;
     const double *x_un, *gseq;
+    double* q0;
     int gamma_zero;
+    double *covs;                       // (null: no covariance - want_cov and cov_mode are 0)
+    const double* growth;               // per episode: the tail's cov += growth I (null without a covariance)
     double *means, *actions_out, *ws;
     long long* step_counter;
-    double gamma;
     long stride, P;
-    int H, A, Hw, nb, chunk, shift_mode;
+    int H, A, Hw, nb, chunk, want_cov, cov_mode, shift_mode;
+    int G;                              // (1, the number of records the combine merges: a run-time 1, as the single launch gets it)
+
+    __device__ SoftmaxRow row(long e) const { return SoftmaxRow(ws + e * stride, P, H, A, Hw, wseq != nullptr); }
 };
 
-// row e: un_kernel (alpha = 0), td_lambda_kernel without Q estimates (returns rounded to T), traj_cost_kernel on the returns
-// (gamma_zero, no control cost) and colmax_kernel's maxima of the Hw columns - one workgroup, a barrier where the single path
-// has a launch boundary.  A maximum does not depend on the order it is taken in (no NaN reaches it: traj_cost_body), so a
-// wavefront takes a column instead of a workgroup.
-template <typename T>
-__global__ __launch_bounds__(BLK) void mppiq_returns_x_batch_kernel(MppiqBatch<T> b) {
+// row e, stage 1: with a returns stage un_kernel (alpha = 0) and td_lambda_kernel without Q estimates (returns rounded to T),
+// which then stand for the costs; traj_cost_kernel and colmax_kernel's maxima of the Hw columns - one workgroup, a barrier
+// where the single path has a launch boundary.  A maximum does not depend on the order it is taken in (no NaN reaches it:
+// traj_cost_body), so with Hw columns a wavefront takes a column instead of a workgroup; a single column keeps colmax_kernel's
+// workgroup (one wavefront walking all P weights measured 3 us slower at P = 256 and 12 us at P = 1024).
+// RETURNS (the host's b.wseq != null) compiles the returns stage in: behind its stores the compiler no longer reads gseq
+// through the scalar cache, which cost the batch without the stage 8 us at P = 1024.
+template <typename T, bool RETURNS>
+__global__ __launch_bounds__(BLK) void softmax_x_batch_kernel(SoftmaxBatch<T> b) {
+    __shared__ double sm[BLK / 64];
     const long e = blockIdx.y, P = b.P;
     const int H = b.H, A = b.A, HA = H * A, Hw = b.Hw;
-    const MppiqRow r(b.ws + e * b.stride, P, H, A, Hw);
+    const SoftmaxRow r = b.row(e);
     const T* costs = b.costs + e * P * H;
     const T* actions = b.actions + e * P * HA;
     const double* mean = b.means + e * HA;
-    const double* un = nullptr;
-    if (b.covinv) {
-        for (int j = threadIdx.x; j < HA; j += blockDim.x) un_body(mean, b.covinv + e * A * A, A, j, r.un);
-        un = r.un;
+    const double temp = b.temp[e];
+    if constexpr (RETURNS) {
+        const double* un = nullptr;
+        if (b.covinv) {
+            for (int j = threadIdx.x; j < HA; j += blockDim.x) un_body(mean, b.covinv + e * A * A, A, j, r.un);
+            un = r.un;
+            __syncthreads();
+        }
+        T* ret = (T*)r.returns;
+        for (long p = threadIdx.x; p < P; p += blockDim.x)
+            td_lambda_body<T>(costs, actions, b.qvals, mean, un, b.wseq + e * (H > 1 ? H - 1 : 1), b.wseq_zero[e], temp,
+                              b.gamma, b.td_lam[e], p, H, A, ret);
+        costs = ret;
         __syncthreads();
     }
-    T* ret = (T*)r.returns;
-    const double beta = b.beta[e];
     for (long p = threadIdx.x; p < P; p += blockDim.x)
-        td_lambda_body<T>(costs, actions, b.qvals, mean, un, b.wseq + e * (H > 1 ? H - 1 : 1), b.wseq_zero[e], beta,
-                          b.gamma, b.td_lam[e], p, H, A, ret);
+        traj_cost_body<T>(costs, actions, mean, b.x_un, b.gseq, b.gamma_zero, temp, p, H, A, Hw, r.x, b.q0);
     __syncthreads();
-    for (long p = threadIdx.x; p < P; p += blockDim.x)
-        traj_cost_body<T>(ret, actions, mean, b.x_un, b.gseq, b.gamma_zero, beta, p, H, A, Hw, r.x, nullptr);
-    __syncthreads();
+    if (Hw == 1) {
+        double m = -INFINITY;
+        for (long p = threadIdx.x; p < P; p += blockDim.x) m = fmax(m, r.x[p]);
+        m = wave_max(m);
+        if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int w = 1; w < BLK / 64; ++w) m = fmax(m, sm[w]);
+            r.xmax[0] = m;
+        }
+        return;
+    }
     for (int tw = threadIdx.x >> 6; tw < Hw; tw += blockDim.x >> 6) {
         double m = -INFINITY;
         for (long p = threadIdx.x & 63; p < P; p += 64) m = fmax(m, r.x[p * Hw + tw]);
@@ -1691,23 +1633,25 @@ __global__ __launch_bounds__(BLK) void mppiq_returns_x_batch_kernel(MppiqBatch<T
     }
 }
 
-// row e: softmax_partial_kernel on its particles with Hw weight columns (the same chunks) into its partials
+// row e, stage 2: softmax_partial_kernel on its particles (the same chunks, the mean from before the update) into its partials
 template <typename T>
-__global__ __launch_bounds__(BLK) void mppiq_partial_batch_kernel(MppiqBatch<T> b) {
+__global__ __launch_bounds__(BLK) void softmax_partial_batch_kernel(SoftmaxBatch<T> b) {
     const long e = blockIdx.y;
     const int HA = b.H * b.A;
-    const MppiqRow r(b.ws + e * b.stride, b.P, b.H, b.A, b.Hw);
-    softmax_partial_body<T>(r.x, r.xmax, b.actions + e * b.P * HA, b.means + e * HA, b.P, b.H, b.A, b.Hw, b.chunk, 0, r.partial);
+    const SoftmaxRow r = b.row(e);
+    softmax_partial_body<T>(r.x, r.xmax, b.actions + e * b.P * HA, b.means + e * HA, b.P, b.H, b.A, b.Hw, b.chunk, b.want_cov,
+                            r.partial);
 }
 
-// row e: softmax_record_kernel (a wavefront per entry: wave_entry_sum over its nb partials), softmax_combine_kernel with that
-// one record and Hw columns, step_tail_kernel - one workgroup, a barrier where the single path has a launch boundary.  Row 0
+// row e, stage 3: softmax_record_kernel (a wavefront per entry: wave_entry_sum over its nb partials), softmax_combine_kernel
+// with that one record, step_tail_kernel - one workgroup, a barrier where the single path has a launch boundary.  Row 0
 // advances the shared step counter; no row reads it.
+// (without a covariance cov_mode is 0, and softmax_combine_body does nothing for j >= HA but entry 0's value / wnorm, null here)
 template <typename T>
-__global__ __launch_bounds__(BLK) void mppiq_finish_batch_kernel(MppiqBatch<T> b) {
+__global__ __launch_bounds__(BLK) void softmax_finish_batch_kernel(SoftmaxBatch<T> b) {
     const long e = blockIdx.y;
-    const int H = b.H, A = b.A, Hw = b.Hw, HA = H * A, rec = Hw + HA + A * A;
-    const MppiqRow r(b.ws + e * b.stride, b.P, H, A, Hw);
+    const int H = b.H, A = b.A, Hw = b.Hw, HA = H * A, AA = A * A, rec = Hw + HA + AA;
+    const SoftmaxRow r = b.row(e);
     for (int j = threadIdx.x >> 6; j < rec; j += blockDim.x >> 6) {
         const double s = wave_entry_sum(r.partial, b.nb, rec, j);
         if ((threadIdx.x & 63) == 0) {
@@ -1717,11 +1661,13 @@ __global__ __launch_bounds__(BLK) void mppiq_finish_batch_kernel(MppiqBatch<T> b
     }
     __syncthreads();
     double* mean = b.means + e * HA;
-    for (int j = threadIdx.x; j < HA; j += blockDim.x)
-        softmax_combine_body(r.record, 1, H, A, Hw, b.beta[e], b.step[e], 0, (double)b.P, mean, nullptr, nullptr, nullptr, j);
+    double* cov = b.covs ? b.covs + e * AA : nullptr;
+    const int n = cov && AA > HA ? AA : HA;
+    for (int j = threadIdx.x; j < n; j += blockDim.x)
+        softmax_combine_body(r.record, b.G, H, A, Hw, b.temp[e], b.step[e], b.cov_mode, (double)b.P, mean, cov, nullptr, nullptr, j);
     __syncthreads();
     step_tail_body(mean, H, A, b.shift_mode, nullptr, b.actions_out ? b.actions_out + e * A : nullptr, nullptr,
-                   e == 0 ? b.step_counter : nullptr, nullptr, nullptr, 0.0);
+                   e == 0 ? b.step_counter : nullptr, cov, nullptr, b.growth ? b.growth[e] : 0.0);
 }
 
 // ---- episode batches of the random-shooting step ---------------------------------------------------------------
@@ -2156,6 +2102,11 @@ hipError_t mppi_fused_update(const double* q0, const T* actions, double lam, dou
     return hipGetLastError();
 }
 
+// what every episode-batch launcher below asks of its shape: a grid row per episode, A within its kernels' limit
+static bool batch_shape_ok(int E, long P, int H, int A, int A_max) {
+    return E >= 1 && E <= 65535 && P >= 1 && H >= 1 && A >= 1 && A <= A_max;
+}
+
 long mppi_fused_batch_workspace_doubles(int E, long P, int H, int A) { return (long)E * nblocks(P, FCH) * (2 + (long)H * A); }
 
 // One episode per grid row, each row what mppi_fused_update does for its P particles: the same partials (FCH particles per
@@ -2164,7 +2115,7 @@ template <typename T>
 hipError_t mppi_fused_update_batch(int E, const double* q0, const T* actions, const double* lam, const double* step,
                                    int shift_mode, long P, int H, int A, double* mean, double* action_out,
                                    long long* step_counter, double* ws, hipStream_t s) {
-    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1) return hipErrorInvalidValue;
+    if (!batch_shape_ok(E, P, H, A, INT_MAX)) return hipErrorInvalidValue;
     const int nb = nblocks(P, FCH), HA = H * A;
     const long stride = (long)nb * (2 + HA);
     const int fth = nb > 64 ? 1024 : BLK, nsl = fth >= 512 ? fth / 256 : 1;
@@ -2204,71 +2155,75 @@ hipError_t cholesky_lower(const double* cov, int A, double* chol, int* status, h
 }
 
 hipError_t cholesky_lower_batch(int E, const double* covs, int A, double* chols, int* status, hipStream_t s) {
-    if (E < 1 || E > 65535 || A < 1 || A > 64) return hipErrorInvalidValue;
+    if (!batch_shape_ok(E, 1, 1, A, 64)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(cholesky_batch_kernel, dim3(E), dim3(64), 0, s, covs, A, chols, status);
     return hipGetLastError();
 }
 
-long dmd_batch_workspace_doubles(int E, long P, int H, int A) {
-    return (long)E * dmd_row_doubles(P, H * A, A * A, nblocks(P, CHUNK));
+// The three launches of a softmax episode batch, one episode per grid row: the same CHUNK particles per partial as the
+// single path, the same nb = ceil(P / CHUNK), the same wave_entry_sum tree over them, the same combine and tail.  The
+// caller has filled in the arrays, Hw and the modes; the workspace is E rows of softmax_batch_row_doubles.
+static long softmax_batch_row_doubles(long P, int H, int A, int Hw, int with_returns) {
+    return softmax_row_doubles(P, H, A, Hw, with_returns, nblocks(P, CHUNK));
+}
+template <typename T>
+static hipError_t softmax_batch_launch(SoftmaxBatch<T> b, int E, long P, int H, int A, hipStream_t s) {
+    b.P = P; b.H = H; b.A = A; b.nb = nblocks(P, CHUNK); b.chunk = CHUNK; b.G = 1;
+    b.stride = softmax_batch_row_doubles(P, H, A, b.Hw, b.wseq != nullptr);
+    hipLaunchKernelGGL((b.wseq ? softmax_x_batch_kernel<T, true> : softmax_x_batch_kernel<T, false>), dim3(1, E), dim3(BLK), 0, s, b);
+    hipLaunchKernelGGL(softmax_partial_batch_kernel<T>, dim3(b.nb, E), dim3(BLK), sizeof(double) * CHUNK * b.Hw, s, b);
+    hipLaunchKernelGGL(softmax_finish_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
+    return hipGetLastError();
 }
 
-// One episode per grid row, each row what softmax_stats (one weight per particle, control cost off, want_cov) +
-// softmax_combine (one record) + step_tail do for its P particles: the same CHUNK particles per partial, the same
-// nb = ceil(P / CHUNK), the same wave_entry_sum tree over them, the same combine and tail - three launches.
+// (what mppiq_batch_workspace_doubles gives without time-based weights, less the returns block)
+long dmd_batch_workspace_doubles(int E, long P, int H, int A) { return (long)E * softmax_batch_row_doubles(P, H, A, 1, 0); }
+
+// Each row what softmax_stats (one weight per particle, control cost off, want_cov) + softmax_combine (one record) +
+// step_tail do for its P particles.
 template <typename T>
 hipError_t dmd_update_batch(int E, const T* costs, const T* actions, const double* gseq, const double* lam,
                             const double* step, int cov_mode, const double* beta, int shift_mode, long P, int H, int A,
                             double* means, double* covs, double* actions_out, long long* step_counter, double* ws,
                             hipStream_t s) {
-    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1 || A > 64) return hipErrorInvalidValue;
-    DmdBatch<T> b;
-    b.costs = costs; b.actions = actions; b.gseq = gseq; b.lam = lam; b.step = step; b.beta = beta;
+    if (!batch_shape_ok(E, P, H, A, 64)) return hipErrorInvalidValue;
+    SoftmaxBatch<T> b{};                // (no returns stage: wseq, td_lam, wseq_zero, covinv, qvals stay null)
+    b.costs = costs; b.actions = actions; b.temp = lam; b.step = step; b.growth = beta;
     b.means = means; b.covs = covs; b.actions_out = actions_out; b.ws = ws; b.step_counter = step_counter;
-    b.un = nullptr; b.q0 = nullptr;
-    b.nb = nblocks(P, CHUNK); b.chunk = CHUNK;
-    b.stride = dmd_row_doubles(P, H * A, A * A, b.nb); b.P = P; b.H = H; b.A = A;
-    b.gamma_zero = 0; b.want_cov = 1; b.cov_mode = cov_mode; b.shift_mode = shift_mode; b.G = 1;
-    hipLaunchKernelGGL(dmd_x_colmax_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
-    hipLaunchKernelGGL(softmax_partial_batch_kernel<T>, dim3(b.nb, E), dim3(BLK), sizeof(double) * CHUNK, s, b);
-    hipLaunchKernelGGL(dmd_finish_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
-    return hipGetLastError();
+    b.x_un = nullptr; b.q0 = nullptr; b.gseq = gseq; b.gamma_zero = 0;
+    b.Hw = 1; b.want_cov = 1; b.cov_mode = cov_mode; b.shift_mode = shift_mode;
+    return softmax_batch_launch(b, E, P, H, A, s);
 }
 
 // (the tail takes a thread per action channel of one wavefront: A <= 64; with time-based weights the partial launch's
 // dynamic LDS, 8 CHUNK H bytes, stays within the 64 KB the single launch takes without an attribute)
 bool mppiq_batch_supported(int E, long P, int H, int A, int tbw) {
-    if (E < 1 || E > 65535 || P < 1 || H < 1 || A < 1 || A > 64) return false;
-    return !tbw || sizeof(double) * CHUNK * (size_t)H <= 64 * 1024;
+    return batch_shape_ok(E, P, H, A, 64) && (!tbw || sizeof(double) * CHUNK * (size_t)H <= 64 * 1024);
 }
 
 long mppiq_batch_workspace_doubles(int E, long P, int H, int A, int tbw) {
-    return (long)E * mppiq_row_doubles(P, H, A, tbw ? H : 1, nblocks(P, CHUNK));
+    return (long)E * softmax_batch_row_doubles(P, H, A, tbw ? H : 1, 1);
 }
 
-// One episode per grid row, each row what td_lambda_returns (no Q estimates) + softmax_stats on the returns (gamma_zero,
-// alpha 1, no covariance) + softmax_combine (one record) + step_tail do for its P particles: the same CHUNK particles per
-// partial, the same nb = ceil(P / CHUNK), the same wave_entry_sum tree over them, the same combine and tail - three launches.
+// Each row what td_lambda_returns (no Q estimates) + softmax_stats on the returns (gamma_zero, alpha 1, no covariance) +
+// softmax_combine (one record) + step_tail do for its P particles.
 template <typename T>
 hipError_t mppiq_update_batch(int E, const T* costs, const T* actions, const double* beta, const double* step,
                               const double* td_lam, const double* wseq, const int* wseq_zero, double gamma,
                               const double* covinv, int tbw, int shift_mode, long P, int H, int A, double* means,
                               double* actions_out, long long* step_counter, double* ws, hipStream_t s) {
-    if (!mppiq_batch_supported(E, P, H, A, tbw)) return hipErrorInvalidValue;
-    MppiqBatch<T> b;
-    b.costs = costs; b.actions = actions; b.beta = beta; b.step = step; b.td_lam = td_lam; b.wseq = wseq; b.covinv = covinv;
-    b.wseq_zero = wseq_zero; b.means = means; b.actions_out = actions_out; b.ws = ws; b.step_counter = step_counter;
-    b.gamma = gamma; b.qvals = nullptr; b.x_un = nullptr; b.gseq = nullptr; b.gamma_zero = 1;
-    b.Hw = tbw ? H : 1; b.nb = nblocks(P, CHUNK); b.chunk = CHUNK;
-    b.stride = mppiq_row_doubles(P, H, A, b.Hw, b.nb); b.P = P; b.H = H; b.A = A; b.shift_mode = shift_mode;
-    hipLaunchKernelGGL(mppiq_returns_x_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
-    hipLaunchKernelGGL(mppiq_partial_batch_kernel<T>, dim3(b.nb, E), dim3(BLK), sizeof(double) * CHUNK * b.Hw, s, b);
-    hipLaunchKernelGGL(mppiq_finish_batch_kernel<T>, dim3(1, E), dim3(BLK), 0, s, b);
-    return hipGetLastError();
+    if (!mppiq_batch_supported(E, P, H, A, tbw) || !wseq) return hipErrorInvalidValue;
+    SoftmaxBatch<T> b{};                // (no covariance: covs and growth stay null, want_cov and cov_mode 0)
+    b.costs = costs; b.actions = actions; b.temp = beta; b.step = step;
+    b.td_lam = td_lam; b.wseq = wseq; b.wseq_zero = wseq_zero; b.covinv = covinv; b.gamma = gamma; b.qvals = nullptr;
+    b.means = means; b.actions_out = actions_out; b.ws = ws; b.step_counter = step_counter;
+    b.x_un = nullptr; b.q0 = nullptr; b.gseq = nullptr; b.gamma_zero = 1;
+    b.Hw = tbw ? H : 1; b.shift_mode = shift_mode;
+    return softmax_batch_launch(b, E, P, H, A, s);
 }
 
 // (a thread per action channel in the tail: A <= BLK)
-bool rs_batch_supported(int E, long P, int H, int A) { return E >= 1 && E <= 65535 && P >= 1 && H >= 1 && A >= 1 && A <= BLK; }
+bool rs_batch_supported(int E, long P, int H, int A) { return batch_shape_ok(E, P, H, A, BLK); }
 
 // One episode per grid row, each row what rs_best + rs_combine (one record) + step_tail do for its P particles: one launch.
 template <typename T>
