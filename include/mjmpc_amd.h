@@ -379,7 +379,12 @@ int mjmpc_comm_destroy(mjmpc_comm_t c);
  *   CEM cov record  [ sum over local elites and t of (d - dbar)(d - dbar)^T  [A*A] ]
  *   RS record       [ min q0 | global particle index | actions[H*A] of that particle ]
  * d_gseq is Controller.gamma_seq (controller.py:71) as float64[H]; gamma_zero = any(gseq == 0)
- * (control_utils.cost_to_go returns its input unchanged in that case, control_utils.py:41-42).   */
+ * (control_utils.cost_to_go returns its input unchanged in that case, control_utils.py:41-42).
+ * Diverged rollouts: for every entry below a return (cost-to-go or d_q0) that is not finite - +inf, -inf, NaN of either sign -
+ * means zero weight / ranked last, so the result is the update over the particles with a finite return, also where a whole
+ * workgroup's block, a whole record or a whole merge slice has none (a record without a finite return is {-inf, 0, 0...}).
+ * A row or run with NO finite return is outside that promise: the softmax entries give it a NaN mean, as the plain
+ * arithmetic does, the selections particle 0 / the first k by index; in a batch it leaves the other rows alone.        */
 int64_t mjmpc_update_workspace_bytes(int64_t P, int H, int A);
 int mjmpc_softmax_record_len(int H, int A, int time_based_weights);
 
@@ -606,9 +611,9 @@ int mjmpc_mppiq_update_batch(int dtype, int E, int64_t P, int H, int A, const vo
  * d_actions + e P H A, 0, record, ws) on the cost-to-go d_q0 + e P, then mjmpc_rs_combine(record, 1, H, A, d_step_size[e],
  * d_means + e H A), then mjmpc_step_tail(d_means + e H A, H, A, shift_mode, NULL, d_actions_out + e A, NULL, counter, NULL,
  * NULL, 0): the particle with the first minimum of its cost-to-go (numpy.argmin: ties go to the lowest index), mean <-
- * (1 - step) mean + step * its actions, the action read-out and the horizon shift.  A row whose cost-to-go values are all
- * +inf selects particle 0, as numpy.argmin does (the single calls are undefined for such a row).  d_q0 float64 [E][P] without
- * NaN, d_actions dtype [E][P][H][A], d_step_size float64 [E] (device), shift_mode 0 'null' or 1 'repeat', d_means float64
+ * (1 - step) mean + step * its actions, the action read-out and the horizon shift.  A row without a finite cost-to-go
+ * selects particle 0, as numpy.argmin does for a row of +inf (and as the single calls do).  d_q0 float64 [E][P] (a value that
+ * is not finite compares as +inf), d_actions dtype [E][P][H][A], d_step_size float64 [E] (device), shift_mode 0 'null' or 1 'repeat', d_means float64
  * [E][H][A] (updated and shifted in place), d_actions_out float64 [E][A] (may be NULL), d_best int64 [E] (may be NULL): the
  * selected particle of every row.  *d_step_counter (may be NULL) is advanced once, by row 0; no row reads it.
  * mjmpc_rs_batch_supported(E, P, H, A): 1 <= E <= 65535, P >= 1, H >= 1, 1 <= A <= 256 (MJMPC_E_BADARG otherwise). */

@@ -178,7 +178,12 @@ __device__ __forceinline__ void softmax_partial_body(const double* __restrict__ 
     const long p0 = (long)blockIdx.x * chunk;
     const int n = (int)((P - p0) < chunk ? (P - p0) : chunk);
     double* out = partial + (long)blockIdx.x * rec;
-    for (int i = threadIdx.x; i < n * Hw; i += blockDim.x) e_s[i] = exp(x[p0 * Hw + i] - xmax[i % Hw]);
+    // (a diverged particle's x is -inf: weight 0 also where its whole column is - xmax -inf, a shard without a finite return -
+    // instead of exp(-inf + inf) = NaN)
+    for (int i = threadIdx.x; i < n * Hw; i += blockDim.x) {
+        const double xi = x[p0 * Hw + i];
+        e_s[i] = xi == -INFINITY ? 0.0 : exp(xi - xmax[i % Hw]);
+    }
     __syncthreads();
     for (int tw = threadIdx.x; tw < Hw; tw += blockDim.x) {
         double s = 0.0;
@@ -238,13 +243,17 @@ __global__ void softmax_record_kernel(const double* __restrict__ partial, const 
 
 // mean <- (1-eta) mean + eta * sum_g sc_g W_g / sum_g sc_g S_g,   sc_g = exp(xmax_g - max_g xmax_g);
 // cov likewise (mode 1: diagonal only, 2: full); value = -lam * logsumexp(x, b = 1/P_total).
+// A record without a finite return (xmax_g = -inf, sums 0) has sc_g = 0 whatever the other records' maximum.
 // (entry j's part; the body is shared with the episode-batch kernel softmax_finish_batch_kernel below)
 __device__ __forceinline__ void softmax_combine_body(const double* __restrict__ records, int G, int H, int A, int Hw,
                                                      double lam, double step, int cov_mode, double P_total,
                                                      double* __restrict__ mean, double* __restrict__ cov,
                                                      double* __restrict__ value, double* __restrict__ wnorm, int j) {
     const int HA = H * A, rlen = 2 * Hw + HA + A * A;
-    auto scale = [&](int g, int tw, double M) { return exp(records[(long)g * rlen + tw] - M); };
+    auto scale = [&](int g, int tw, double M) {
+        const double m = records[(long)g * rlen + tw];
+        return m == -INFINITY ? 0.0 : exp(m - M);
+    };
     auto colmax = [&](int tw) {
         double M = -INFINITY;
         for (int g = 0; g < G; ++g) M = fmax(M, records[(long)g * rlen + tw]);
@@ -297,7 +306,9 @@ __global__ void softmax_weights_kernel(const double* __restrict__ x, const doubl
 // Elite selection = the k smallest particles in (q0, global index) order.  A most-significant-byte radix select
 // over the order-preserving integer image of the doubles finds the k-th smallest key in 8 passes of one
 // workgroup (the first version ranked every particle against every other: 1.2 ms at 16 384 particles);
+// (a return that is not finite - NaN of either sign, -inf - takes +inf's key: last in the ranking, ties by index)
 __device__ __forceinline__ unsigned long long order_key(double q) {
+    if (!(fabs(q) < INFINITY)) q = INFINITY;
     const unsigned long long b = (unsigned long long)__double_as_longlong(q);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
@@ -1175,14 +1186,15 @@ __global__ __launch_bounds__(CEM_FIN_THREADS) void cem_finish_batch_kernel(CemFi
 }
 
 // ---- random shooting --------------------------------------------------------------------------------
-// first index of the minimum (np.argmin), single workgroup
+// first index of the minimum (np.argmin), single workgroup; an entry that is not finite compares as +inf, and a row
+// without an entry below +inf gives index 0, np.argmin's answer
 __global__ void argmin_kernel(const double* __restrict__ q, long P, double* __restrict__ out_val, long* __restrict__ out_idx) {
     __shared__ double sv[BLK];
     __shared__ long si[BLK];
     double bv = INFINITY;
     long bi = P;
     for (long p = threadIdx.x; p < P; p += blockDim.x) {
-        const double v = q[p];
+        const double v = fabs(q[p]) < INFINITY ? q[p] : INFINITY;
         if (v < bv) { bv = v; bi = p; }
     }
     sv[threadIdx.x] = bv;
@@ -1196,7 +1208,7 @@ __global__ void argmin_kernel(const double* __restrict__ q, long P, double* __re
         }
         __syncthreads();
     }
-    if (threadIdx.x == 0) { *out_val = sv[0]; *out_idx = si[0]; }
+    if (threadIdx.x == 0) { *out_val = sv[0]; *out_idx = si[0] < P ? si[0] : 0; }
 }
 
 // one entry of the move towards the best action sequence (random_shooting.py:52-62)
@@ -1344,7 +1356,8 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // partial[b] = { m_b, S_b, W_b[H*A] } with weights exp(x_p - m_b), x_p = -q0_p / lam (b = blockIdx.x; the body is shared
-// with the episode-batch kernel below, whose grid row picks the episode's arrays)
+// with the episode-batch kernel below, whose grid row picks the episode's arrays).  A q0 that is not finite has x_p = -inf and
+// weight 0 (pf_weights_body's guard); a workgroup without a finite q0 leaves { -inf, 0, 0... }, as mono_record does
 template <typename T>
 __device__ __forceinline__ void fused_partial_body(const double* __restrict__ q0, const T* __restrict__ actions, double lam,
                                                    long P, int HA, double* __restrict__ partial,
@@ -1357,9 +1370,10 @@ __device__ __forceinline__ void fused_partial_body(const double* __restrict__ q0
     // launch's first workgroup advances the counter)
     if (step_snapshot && blockIdx.x == 0 && threadIdx.x == 0) *step_snapshot = d_step ? *d_step : 0;
     if (threadIdx.x < 64) {
-        const double x = threadIdx.x < n ? (-1.0 / lam) * q0[p0 + threadIdx.x] : -INFINITY;
+        const double q = threadIdx.x < n ? q0[p0 + threadIdx.x] : INFINITY;
+        const double x = fabs(q) < INFINITY ? (-1.0 / lam) * q : -INFINITY;
         const double m = wave_max(x);
-        const double e = threadIdx.x < n ? exp(x - m) : 0.0;
+        const double e = x == -INFINITY ? 0.0 : exp(x - m);
         e_s[threadIdx.x] = e;
         const double s = wave_sum(e);
         if (threadIdx.x == 0) { out[0] = m; out[1] = s; }
@@ -1429,7 +1443,8 @@ __device__ __forceinline__ void fused_final_body(const double* __restrict__ part
     double M = red[0];
     for (int w = 1; w < nw; ++w) M = fmax(M, red[w]);
     for (int b = tid; b < nb; b += nth) {
-        sc[b] = exp(partial[(long)b * rec] - M);
+        const double mb = partial[(long)b * rec];
+        sc[b] = mb == -INFINITY ? 0.0 : exp(mb - M);         // (a partial or record without a finite return)
         ss[b] = partial[(long)b * rec + 1];
     }
     __syncthreads();
@@ -1444,6 +1459,9 @@ __device__ __forceinline__ void fused_final_body(const double* __restrict__ part
         __syncthreads();
         for (int w = 0; w < nw; ++w) S += red[16 + w];
     }
+    // (record mode, step 0, on a shard without a finite return - S = 0 -: the shard's mean stays as it is for the combine
+    // instead of 0 * (0 / 0); with any other step such a run keeps its NaN mean, as the plain arithmetic gives it)
+    auto ratio = [&](double W) { return S == 0.0 && step == 0.0 ? 0.0 : W / S; };
     const int per = (nb + nsl - 1) / nsl, b0 = sl * per, b1 = b0 + per < nb ? b0 + per : nb;
     for (int j = jt; j < HA; j += jstep) {
         double W = 0.0;
@@ -1460,7 +1478,7 @@ __device__ __forceinline__ void fused_final_body(const double* __restrict__ part
             part[sl * HA + j] = W;
         } else {
             if (record) record[2 + j] = W;
-            nm[j] = (1.0 - step) * mean[j] + step * (W / S);
+            nm[j] = (1.0 - step) * mean[j] + step * ratio(W);
         }
     }
     if (nsl > 1) {
@@ -1469,7 +1487,7 @@ __device__ __forceinline__ void fused_final_body(const double* __restrict__ part
             double W = part[j];
             for (int q = 1; q < nsl; ++q) W += part[q * HA + j];
             if (record) record[2 + j] = W;
-            nm[j] = (1.0 - step) * mean[j] + step * (W / S);
+            nm[j] = (1.0 - step) * mean[j] + step * ratio(W);
         }
     }
     if (threadIdx.x == 0) {
@@ -1674,8 +1692,8 @@ __global__ __launch_bounds__(BLK) void softmax_finish_batch_kernel(SoftmaxBatch<
 // Row e: the single path's argmin_kernel + rs_record_kernel + rs_combine_kernel (one record) + step_tail_kernel on episode e's
 // slices, one workgroup and one launch.  The selection is compares of (value, index) pairs - a strided scan per thread, a
 // butterfly over each wavefront, the BLK / 64 wave results through LDS - and so exact whatever its order: the first index of
-// the minimum, np.argmin's.  A row without an entry below +inf (all +inf; NaN is outside the contract) selects particle 0,
-// np.argmin's answer - never index P, which argmin_kernel gives for such a row.  The blend is rs_blend, the tail
+// the minimum, np.argmin's.  An entry that is not finite compares as +inf; a row without an entry below +inf selects particle 0,
+// np.argmin's answer, as argmin_kernel does.  The blend is rs_blend, the tail
 // step_tail_body; the barrier between them stands where the single path has a launch boundary.  Row 0 advances the shared
 // step counter; no row reads it.
 template <typename T>
@@ -1693,7 +1711,7 @@ __global__ __launch_bounds__(BLK) void rs_update_batch_kernel(const double* __re
     double bv = INFINITY;
     long bi = P;
     for (long p = threadIdx.x; p < P; p += blockDim.x) {
-        const double v = q[p];
+        const double v = fabs(q[p]) < INFINITY ? q[p] : INFINITY;
         if (v < bv) { bv = v; bi = p; }
     }
     for (int o = 32; o > 0; o >>= 1) {

@@ -559,7 +559,8 @@ def test_semidefinite_covariance_samples_and_indefinite_raises():
 def test_diverged_rollouts_do_not_poison_the_update():
     """A rollout whose simulation diverged numerically carries NaN / inf costs (MuJoCo would have reset it): the
     MPPI and CEM updates treat its return as +inf - zero weight, never elite - i.e. they equal the update over the
-    finite particles alone, instead of a NaN mean."""
+    finite particles alone, instead of a NaN mean.  The diverged particles here are isolated ones; whole diverged blocks,
+    records and merge slices, every non-finite kind and every other update entry: tests/test_diverged_returns_gpu.py."""
     from mjmpc_amd.control._device import DeviceUpdater
     from oracle import controllers_ref as cr
     P, H, A = 256, 8, 3
