@@ -5,7 +5,7 @@
     python examples/example_mpc_batched.py --config examples/configs/half_cheetah_gpu.yml
         [--controller mppi|cem|pfmpc|dmd|random_shooting|mppiq]
         [--dtype f64|f32] [--episodes N] [--dyn_randomize_config FILE [--num_cpu K] [--dyn_per_episode]]
-        [--update_cov] [--cov_type diagonal|full]
+        [--update_cov] [--cov_type diagonal|full] [--engine tree|arm]
 
 examples/example_mpc.py runs the episodes one after another (as the reference's job_script.py:80-99): episode i with seed
 ``seed + i*12345`` from the env class's ``reset(seed=...)``.  This driver takes the same seeds and start states and runs all
@@ -29,6 +29,10 @@ moments, update + tail and env step -, with ``update_cov: false`` ``BatchedMPPI`
 block's ``alpha`` and ``time_based_weights``); other controller blocks are refused.  The reacher configs run on the TREE engine here
 (sawyer.xml compiled as a tree), while example_mpc.py steps them on the serial-chain arm engine: the two drivers' reacher
 rewards are not expected to be equal.
+
+``--engine arm`` runs the reacher configs' batch on the arm engine instead (``engine="arm"``: the arm kernels'
+episode-batch launches, ``num_particles`` a multiple of 8, start states from the env class on the arm engine); the other
+environments and ``--dyn_randomize_config`` need the default, ``--engine tree``.
 """
 import argparse
 import os
@@ -72,6 +76,7 @@ def main():
     ap.add_argument("--dyn_per_episode", action="store_true", help="a set of randomized models per episode (from its seed)")
     ap.add_argument("--update_cov", action="store_true", help="--controller dmd: adapt the covariance whatever the block says")
     ap.add_argument("--cov_type", choices=["diagonal", "full"], help="--controller dmd / cem: override the block's cov_type")
+    ap.add_argument("--engine", default="tree", choices=["tree", "arm"], help="the engine the batch runs on (arm: the reacher configs)")
     args = ap.parse_args()
     with open(args.config) as f:
         exp = yaml.safe_load(f)
@@ -79,6 +84,8 @@ def main():
         raise SystemExit("environment %r is not built (have: %s)" % (exp["env_name"], ", ".join(ENVS)))
     if not isinstance(exp.get(args.controller), dict):
         raise SystemExit("the config has no %r controller block" % args.controller)
+    if args.engine == "arm" and (exp["env_name"] in TREE_MODELS or args.dyn_randomize_config):
+        raise SystemExit("--engine arm runs the reacher configs without dynamics randomization; use --engine tree")
     params = dict(exp[args.controller])
     num_cpu = args.num_cpu or params.pop("num_cpu", 1)
     params.pop("num_cpu", None)
@@ -95,7 +102,10 @@ def main():
 
     # the start states: the env class's reset(seed) per episode (the reacher's env class on the tree engine)
     env_cls = ENVS[exp["env_name"]]
-    env = env_cls(dtype=args.dtype) if exp["env_name"] in TREE_MODELS else env_cls(engine=TreeRolloutEngine(raw, dtype=args.dtype))
+    if exp["env_name"] in TREE_MODELS or args.engine == "arm":
+        env = env_cls(dtype=args.dtype)
+    else:
+        env = env_cls(engine=TreeRolloutEngine(raw, dtype=args.dtype))
     states = []
     for s in seeds:
         env.reset(seed=s)
@@ -109,7 +119,7 @@ def main():
     cls, names, optional = BATCHES[name]
     params.setdefault("beta", 0.0)
     batch = cls(raw, E, params["horizon"], params["num_particles"], *[params[n] for n in names], params["gamma"],
-                params["filter_coeffs"], base_action, seeds, dtype=args.dtype, n_iters=params.get("n_iters", 1),
+                params["filter_coeffs"], base_action, seeds, dtype=args.dtype, n_iters=params.get("n_iters", 1), engine=args.engine,
                 **{k: params.get(k, default) for k, default in optional.items()})
     if args.controller == "dmd":
         print("the dmd block (update_cov: %s) runs as %s" % (bool(params.get("update_cov", False)), type(batch).__name__))
@@ -137,8 +147,8 @@ def main():
             print("episode %d: reward %.3f, final distance to target %.4f"
                   % (i, rewards[i], np.linalg.norm(nobs[-1, i, -3:])))
     print("Avg. reward = %.4f, Std. Reward = %.4f" % (rewards.mean(), rewards.std()))
-    print("%s batch: %d episodes x %d particles x H%d%s, %.3f ms per batched control step (%.0f episode-steps/s)"
-          % (args.controller, E, params["num_particles"], params["horizon"],
+    print("%s batch on the %s engine: %d episodes x %d particles x H%d%s, %.3f ms per batched control step (%.0f episode-steps/s)"
+          % (args.controller, args.engine, E, params["num_particles"], params["horizon"],
              ", %d randomized model shards" % num_cpu if args.dyn_randomize_config else "", 1e3 * dt / T, E * T / dt))
 
 

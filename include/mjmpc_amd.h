@@ -187,6 +187,26 @@ int mjmpc_arm_mppi_combine(mjmpc_arm_t h, int dtype, const double* d_records, in
  * resulting observation (dtype[2nv+6]).                                                          */
 int mjmpc_arm_step_state(mjmpc_arm_t h, int dtype, const double* d_action, void* d_cost, void* d_next_obs,
                          void* stream);
+/* The engine state read back: qpos[nv], qvel[nv] (host; synchronises the stream), as mjmpc_tree_get_state. */
+int mjmpc_arm_get_state(mjmpc_arm_t h, double* qpos, double* qvel, void* stream);
+/* Episode batches on the arm engine, as the tree engine's below: E independent closed-loop MPC episodes side by side.  The
+ * engine's E = n_state_shards start states (mjmpc_arm_set_shard_states, 1 <= E <= 65535; a batch of one episode sets one
+ * shard) are the batch's E real envs.  MJMPC_E_BADARG, before any launch: no state shards; more than one model block
+ * (mjmpc_arm_set_shard_models); an extended-joint model (slide joints / friction loss: the tree engine runs those batches).
+ * mjmpc_arm_rollout_fused_batch: mjmpc_arm_rollout_fused with one mean per state shard - d_means float64 [E][H][nu];
+ * particles [e P_total / E, (e + 1) P_total / E) start from state shard e and follow mean e; P_total % E == 0 and
+ * (P_total / E) % 8 == 0 (a particle group never straddles two episodes), d_noise required, d_q0 and d_gseq both or
+ * neither.  The launch shape is chosen from the TOTAL grid, as mjmpc_arm_rollout_fused chooses it for P = P_total: each
+ * episode's rows are, bit for bit, those rows of a plain launch of all P_total particles under episode e's state and mean. */
+int mjmpc_arm_rollout_fused_batch(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                                  const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
+                                  double* d_q0, void* stream);
+/* env.step of every episode's real env in one launch (as mjmpc_arm_step_state per state shard, bit for bit, resets
+ * counted as there): d_actions float64 [E][nu], d_costs dtype [E], d_next_obs dtype [E][d_obs] or NULL; every state shard is
+ * advanced in place. */
+int mjmpc_arm_step_shard_states(mjmpc_arm_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream);
+/* The E state shards read back: qpos [E][nv], qvel [E][nv] (host; synchronises the stream). */
+int mjmpc_arm_get_shard_states(mjmpc_arm_t h, double* qpos, double* qvel, void* stream);
 
 /* ---- tree engine: the same worker-pool replacement for models the serial-chain arm engine cannot hold ----------
  * (SURVEY 8f rank 4): a kinematic TREE of up to 32 hinge / slide dofs (the reference's vendored sawyer.xml, swimmer.xml

@@ -33,7 +33,15 @@ and ``beta``, and a ``'diagonal'`` or ``'full'`` covariance that is re-estimated
 ``BatchedRandomShooting`` is the batch of random shooting (random_shooting.py): per episode ``step_size`` and
 ``init_cov``, and a mean that moves towards the best sample of the step.  ``BatchedMPPIQ`` is the batch of MPPIQ (mppiq.py;
 DESIGN 10.6): per episode ``beta``, ``step_size``, ``init_cov`` and ``td_lam``, TD(lambda) returns of the per-step costs and a
-softmax per horizon step.  The classes share
+softmax per horizon step.
+
+Every class takes ``engine="tree"`` (the default, all of the above) or ``engine="arm"``: the same batch on
+``ArmRolloutEngine`` for the models the arm kernels run without slide joints or friction loss (``reacher_7dof-v0``), with
+``num_particles`` a multiple of 8.  The sampler and the update launches are the same; the rollout and the real-env step are the
+arm kernels' episode-batch twins (``mjmpc_arm_rollout_fused_batch``, ``mjmpc_arm_step_shard_states``).  Episode e's rollout rows
+are, bit for bit, those of a plain ``mjmpc_arm_rollout_fused`` launch of all ``E * num_particles`` particles under its state and
+mean (the arm kernels choose their launch shape from the grid), its env steps those of ``mjmpc_arm_step_state``.  Dynamics
+randomization stays with ``engine="tree"``.  The classes share
 ``_EpisodeBatch``: the engine, the state shards, the buffers, the rollout launch, the env step, ``run``, dynamics
 randomization, the step frame, the bound checks and the covariance status.
 """
@@ -76,6 +84,16 @@ class _EpisodeBatch:
     and provides ``_launches``, its own launches of a ``step``."""
 
     _status = None      # int32 [E] on the device in the batches whose kernels can flag an episode's covariance
+    _engine_kind = "tree"   # ``engine=``: "tree" (TreeRolloutEngine) or "arm" (ArmRolloutEngine, DESIGN 10.7)
+
+    def _pick_engine(self, engine, num_particles):
+        """The first refusals of every constructor: the ``engine`` keyword, and what the arm engine asks of the population."""
+        if engine not in ("tree", "arm"):
+            raise ValueError("engine must be 'tree' or 'arm', got %r" % (engine,))
+        if engine == "arm" and int(num_particles) % 8 != 0:
+            raise ValueError("with engine='arm' every episode holds a multiple of 8 particles (a particle group of the arm "
+                             "kernels must not straddle two episodes), got num_particles = %d" % int(num_particles))
+        self._engine_kind = engine
 
     @staticmethod
     def _check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq, sample_mode, dtype,
@@ -123,10 +141,23 @@ class _EpisodeBatch:
             raise ValueError("the tree engine runs RK4 models of up to 16 dofs without elliptic friction cones")
         return model
 
+    @staticmethod
+    def _compile_arm(raw_model):
+        """The arm engine's model, or ``ValueError`` for a model it refuses or has no episode-batch kernels for."""
+        from ..models.compile import ArmModel, compile_arm
+        try:
+            model = raw_model if isinstance(raw_model, ArmModel) else compile_arm(raw_model)
+        except (ValueError, NotImplementedError, TypeError, AttributeError) as e:
+            raise ValueError("the arm engine cannot run this model (engine='tree' runs the general models): %s" % e) from e
+        if np.any(model.field("jtype") != 0) or np.any(model.field("frictionloss") > 0):
+            raise ValueError("the arm engine's extended-joint kernels (slide joints, friction loss) have no episode-batch "
+                             "twins: run this model with engine='tree'")
+        return model
+
     def _seeds_and_model(self, seeds, E, raw_model):
         """The last two refusals of every constructor: ``seed_vals`` and the compiled model."""
         self.seed_vals = self._check_seeds(seeds, E)
-        return self._compile(raw_model)
+        return self._compile_arm(raw_model) if self._engine_kind == "arm" else self._compile(raw_model)
 
     @staticmethod
     def _init_mean(init_mean, E, H, A):
@@ -142,11 +173,15 @@ class _EpisodeBatch:
 
     def _setup(self, raw_model, model, E, H, P, dtype, device, base_action, gamma, fc, init_mean):
         """The engine (its state shards are the E real envs) and the device buffers every batch has."""
-        from ..envs.tree_engine import TreeRolloutEngine
         from ..models.raw import RawModel
         import torch
         self.torch = torch
-        self.engine = TreeRolloutEngine(model, device=device, dtype=dtype)
+        if self._engine_kind == "arm":
+            from ..envs.arm_engine import ArmRolloutEngine
+            self.engine = ArmRolloutEngine(model, device=device, dtype=dtype)
+        else:
+            from ..envs.tree_engine import TreeRolloutEngine
+            self.engine = TreeRolloutEngine(model, device=device, dtype=dtype)
         self.lib = self.engine._lib
         self.model = model
         self.raw = raw_model if isinstance(raw_model, RawModel) else None
@@ -174,7 +209,7 @@ class _EpisodeBatch:
         self._act = torch.empty((E, A), **f64)
         self._env_cost = torch.empty(E, dtype=tdt, device=dev)
         self._env_obs = torch.empty((E, self.d_obs), dtype=tdt, device=dev)
-        self.set_states([dict(qp=model.qpos0.copy(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
+        self.set_states([dict(qp=self.engine._start_qpos(), qv=np.zeros(model.nv), target_pos=model.target_default.copy())] * E)
         return f64
 
     def _upload(self, a):
@@ -248,6 +283,7 @@ class _EpisodeBatch:
         per episode with per-episode seeds.  Raises ``ValueError`` before anything reaches the device."""
         from ..envs._engine import draw_shard_models
         from ..envs.tree_engine import TreeRolloutEngine
+        self._tree_only("randomize_dynamics")
         E, K = self.num_episodes, int(num_shards)
         if not 1 <= K <= 65535 or self.num_particles % K != 0:
             raise ValueError("num_particles (%d) must divide into num_shards (%d) shards, 1 .. 65535" % (self.num_particles, K))
@@ -273,6 +309,7 @@ class _EpisodeBatch:
 
     def clear_dynamics(self):
         """Back to the one nominal model block for every rollout."""
+        self._tree_only("clear_dynamics")
         _lib.check(self.lib.mjmpc_tree_set_batch_models(self.engine._h, None, 0, 0))
         self.shard_blobs = None
 
@@ -297,7 +334,7 @@ class _EpisodeBatch:
         deviations from the means, ``_noise`` by default; ``filtered=False``: they are filtered already; ``gseq=False`` /
         ``q0=False``: no discount sequence / no cost-to-go (the update forms its own)."""
         E, P, H = self.num_episodes, self.num_particles, self.horizon
-        _lib.check(self.lib.mjmpc_tree_rollout_fused_batch(
+        _lib.check(self._fn("rollout_fused_batch")(
             self.engine._h, self._code, E * P, H, _vp(self._means), _vp(self._noise if noise is None else noise),
             _vp(self._coeffs) if filtered else None, _vp(self._gseq) if gseq else None, _vp(self._costs), _vp(self._actions),
             _vp(self._q0) if q0 else None, s))
@@ -310,7 +347,7 @@ class _EpisodeBatch:
 
     def _env_step(self, act, cost, nobs, s):
         """The E real envs take their episode's action in one launch."""
-        _lib.check(self.lib.mjmpc_tree_step_shard_states(self.engine._h, self._code, _vp(act), _vp(cost), _vp(nobs), s))
+        _lib.check(self._fn("step_shard_states")(self.engine._h, self._code, _vp(act), _vp(cost), _vp(nobs), s))
 
     def run(self, T):
         """``T`` control steps of every episode -> actions ``[T][E][A]`` (float64), real-env costs ``[T][E]`` and next
@@ -336,6 +373,14 @@ class _EpisodeBatch:
         self.engine.close()
 
     # ------------------------------------------------------------------ helpers
+    def _fn(self, name):
+        """The engine kind's entry point ``mjmpc_<tree|arm>_<name>``, looked up on ``self.lib`` when the launch is made."""
+        return getattr(self.lib, "mjmpc_%s_%s" % (self._engine_kind, name))
+
+    def _tree_only(self, what):
+        if self._engine_kind != "tree":
+            raise ValueError("%s: an arm batch rolls out one model block; per-episode model blocks need engine='tree'" % what)
+
     def _check_resets(self):
         if self.engine.on_env_reset != "ignore":
             self.engine.check_env_resets("an episode batch's real envs (step_shard_states)")
@@ -370,7 +415,8 @@ class BatchedMPPI(_EpisodeBatch):
 
     def __init__(self, raw_model, num_episodes, horizon, num_particles, lam, step_size, init_cov, gamma, filter_coeffs,
                  base_action, seeds, init_mean=None, dtype="f64", device=0, n_iters=1, alpha=1, time_based_weights=False,
-                 cov_type="diagonal", use_zero_control_seq=False, sample_mode="mean"):
+                 cov_type="diagonal", use_zero_control_seq=False, sample_mode="mean", engine="tree"):
+        self._pick_engine(engine, num_particles)
         # -- everything that can be refused is refused here, before the engine and its device memory exist
         if alpha != 1:
             raise ValueError("an episode batch runs MPPI without the control cost (alpha = 1), got %r" % (alpha,))
@@ -426,7 +472,8 @@ class BatchedCEM(_EpisodeBatch):
 
     def __init__(self, raw_model, num_episodes, horizon, num_particles, init_cov, elite_frac, step_size, beta, gamma,
                  filter_coeffs, base_action, seeds, cov_type="full", dtype="f64", device=0, n_iters=1, sample_mode="mean",
-                 use_zero_control_seq=False):
+                 use_zero_control_seq=False, engine="tree"):
+        self._pick_engine(engine, num_particles)
         # -- everything that can be refused is refused here, before the engine and its device memory exist
         if cov_type not in ("diagonal", "full"):
             raise ValueError("cov_type must be 'diagonal' or 'full' in a CEM episode batch, got %r" % (cov_type,))
@@ -513,7 +560,8 @@ class BatchedDMDMPC(_EpisodeBatch):
 
     def __init__(self, raw_model, num_episodes, horizon, num_particles, lam, step_size, init_cov, beta, gamma, filter_coeffs,
                  base_action, seeds, cov_type="full", update_cov=True, init_mean=None, dtype="f64", device=0, n_iters=1,
-                 sample_mode="mean", use_zero_control_seq=False):
+                 sample_mode="mean", use_zero_control_seq=False, engine="tree"):
+        self._pick_engine(engine, num_particles)
         # -- everything that can be refused is refused here, before the engine and its device memory exist
         if not update_cov:
             raise ValueError("DMD-MPC without covariance adaptation (update_cov=False) is MPPI with alpha = 1: run it as "
@@ -592,7 +640,8 @@ class BatchedMPPIQ(_EpisodeBatch):
 
     def __init__(self, raw_model, num_episodes, horizon, num_particles, beta, step_size, init_cov, td_lam, gamma,
                  filter_coeffs, base_action, seeds, alpha=1, time_based_weights=True, dtype="f64", device=0, n_iters=1,
-                 sample_mode="mean"):
+                 sample_mode="mean", engine="tree"):
+        self._pick_engine(engine, num_particles)
         # -- everything that can be refused is refused here, before the engine and its device memory exist
         E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, False, sample_mode, dtype,
                                          gamma, filter_coeffs, "MPPIQ")
@@ -669,7 +718,9 @@ class BatchedPFMPC(_EpisodeBatch):
     ``cov_resample <= 0``, a wrong seed count and a model the tree engine refuses."""
 
     def __init__(self, raw_model, num_episodes, horizon, num_particles, cov_shift, cov_resample, lam, gamma, filter_coeffs,
-                 base_action, seeds, dtype="f64", device=0, n_iters=1, sample_mode="mean", keep_stages=False):
+                 base_action, seeds, dtype="f64", device=0, n_iters=1, sample_mode="mean", keep_stages=False,
+                 engine="tree"):
+        self._pick_engine(engine, num_particles)
         # -- everything that can be refused is refused here, before the engine and its device memory exist
         E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, False, sample_mode, dtype,
                                          gamma, filter_coeffs, "PFMPC")
@@ -779,7 +830,9 @@ class BatchedRandomShooting(_EpisodeBatch):
     ``mjmpc_rs_batch_supported`` and a model the tree engine refuses."""
 
     def __init__(self, raw_model, num_episodes, horizon, num_particles, step_size, init_cov, gamma, filter_coeffs, base_action,
-                 seeds, init_mean=None, dtype="f64", device=0, n_iters=1, use_zero_control_seq=False, sample_mode="mean"):
+                 seeds, init_mean=None, dtype="f64", device=0, n_iters=1, use_zero_control_seq=False, sample_mode="mean",
+                 engine="tree"):
+        self._pick_engine(engine, num_particles)
         # -- everything that can be refused is refused here, before the engine and its device memory exist
         E, H, P, fc = self._check_common(num_episodes, horizon, num_particles, n_iters, base_action, use_zero_control_seq,
                                          sample_mode, dtype, gamma, filter_coeffs, "random-shooting")

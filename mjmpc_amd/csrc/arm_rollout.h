@@ -69,7 +69,10 @@ template <typename T>
 hipError_t launch_arm_rollout(const T* model, const double* state, long P, int H, int A, const double* mean,
                               const T* noise, T* cost, T* act, T* obs, T* nobs, double* state_out,
                               unsigned* diag, hipStream_t stream, RolloutFusion fuse = RolloutFusion(),
-                              const MonoStep* mono = nullptr);
+                              const MonoStep* mono = nullptr, int eb = 0);
+// (eb: the episode batches' launches, DESIGN 10.7 - 1: `mean` holds one row [H][A] per state shard (fuse.state_shard_size),
+// the shape is chosen from the total grid as ever; 2: the real-env step of P = E state shards, one workgroup each, `mean`
+// = actions [E][A], cost [E], nobs [E][d_obs], `state_out` = the state shards, advanced in place)
 // (mono: the fused iteration's parameters; the kernels take the structure BY VALUE - a kernel argument arrives with the
 // launch, where a block in device memory cost every workgroup a dependent round trip before its first useful load)
 // the finish launch: records [n_rec][2 + H A] -> mean_out (mean_in is only read; the two must not alias), action, step
@@ -84,7 +87,7 @@ template <typename T>
 hipError_t launch_arm_rollout_xj(const T* model, const double* state, long P, int H, int A, const double* mean,
                                  const T* noise, T* cost, T* act, T* obs, T* nobs, double* state_out,
                                  unsigned* diag, hipStream_t stream, RolloutFusion fuse = RolloutFusion(),
-                                 const MonoStep* mono = nullptr);
+                                 const MonoStep* mono = nullptr, int eb = 0);     // (eb: refused, the build has no twins)
 template <typename T>
 hipError_t launch_arm_mppi_finish_xj(const T* model, const double* records, long n_rec, int H, int A, const double* mean_in,
                                      double* mean_out, const MonoStep& mono, int env_step, unsigned* diag, hipStream_t stream);

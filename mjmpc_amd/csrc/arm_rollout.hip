@@ -1909,9 +1909,14 @@ __global__ __launch_bounds__(128) MJMPC_FINISH_WAVES void arm_mppi_finish_kernel
 // kernel, actions kept in LDS, ONE softmax record {max, S, W[H A]} per workgroup left in the engine's record buffer; the
 // merge, mean update, action, shift and real-env step are launch 2 (arm_mppi_finish_kernel).  (An in-kernel merge behind
 // arrival counters was measured and dropped: agent-scope fences / dependent L2 round trips cost more than a launch.)
+// EB = the episode batches' twins: the launch's E state shards are E episodes, and a workgroup reads the mean
+// row of its state shard (mean + row H A) - a particle group never straddles two episodes, so its bits are those of a plain
+// launch of the same grid under that episode's state and mean.  With STEP the grid is E workgroups of ONE live particle
+// (slot 0, as the single step's): workgroup e advances state shard e in place with action e.  Compile-time-off in every
+// other instantiation (profiles/r15_arm_eb_resources.txt); the extended-joint build has no twins.
 // (the kernels' body: arm_rollout_body.inc, #included into the two __global__ functions below)
 
-template <typename T, bool STEP, bool CL, int WAVES, bool DUO, bool MONO>
+template <typename T, bool STEP, bool CL, int WAVES, bool DUO, bool MONO, bool EB = false>
 __global__ __launch_bounds__(DUO ? 128 : 64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES))) void arm_rollout_kernel(const T* __restrict__ model, const double* state,
                                                          long P, int H, int A, const double* mean,
                                                          const T* __restrict__ noise, T* __restrict__ cost,
@@ -1927,7 +1932,7 @@ __global__ __launch_bounds__(DUO ? 128 : 64) __attribute__((amdgpu_waves_per_eu(
 }
 // The flag-synchronised shapes: NW = 2 (a 128-thread workgroup, as DUO) and NW = 4 (P <= 2048 on 256 CUs: a 256-thread
 // workgroup = the four waves of a particle group, one per SIMD of a CU)
-template <typename T, int NW, bool MONO>
+template <typename T, int NW, bool MONO, bool EB = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(1, 1))) void arm_rollout_flags_kernel(const T* __restrict__ model, const double* state,
                                                          long P, int H, int A, const double* mean,
                                                          const T* __restrict__ noise, T* __restrict__ cost,
@@ -1971,9 +1976,16 @@ template <typename T>
 hipError_t launch_arm_rollout(const T* model, const double* state, long P, int H, int A, const double* mean,
                               const T* noise, T* cost, T* act, T* obs, T* nobs, double* state_out,
                               unsigned* diag, hipStream_t stream, RolloutFusion fuse,
-                              const MonoStep* mono) {
+                              const MonoStep* mono, int eb) {
     if (P <= 0 || H <= 0) return hipSuccess;
-    const unsigned grid = (unsigned)((P + LANES - 1) / LANES);
+    // eb (episode batches, the kernels' EB twins): 1 the batch rollout - `mean` holds one row [H][A] per state shard and the
+    // shape is chosen from the TOTAL grid exactly as for a plain launch; 2 the batch's real-env step - P = E envs, one
+    // workgroup each (the single step's wave: DUO, one live particle), `state_out` the state shards themselves (always the DUO
+    // twin: MJMPC_ARM_DUO=0 moves the single step to the one-wave kernel, not this launch)
+    if (eb && (XJ || mono || fuse.clw || obs || fuse.state_shard_size <= 0 || fuse.shard_size > 0)) return hipErrorInvalidValue;
+    if (eb == 1 && (state_out || nobs || fuse.state_shard_size % LANES != 0 || P % fuse.state_shard_size != 0)) return hipErrorInvalidValue;
+    if (eb == 2 && (!state_out || H != 1 || noise || act || fuse.state_shard_size != LANES)) return hipErrorInvalidValue;
+    const unsigned grid = eb == 2 ? (unsigned)P : (unsigned)((P + LANES - 1) / LANES);
     // Cap the resident waves per SIMD at what this launch needs (2, or - f32 only, f64 does not fit - 3): the
     // dispatcher then has to spread the workgroups evenly instead of crowding some SIMDs.  (A cap of 1 for launches
     // of at most one wave per SIMD measured 3 % slower than 2.)
@@ -2008,41 +2020,53 @@ hipError_t launch_arm_rollout(const T* model, const double* state, long P, int H
                 if (obs || nobs || !fuse.gseq || !mono->chol || !mono->tree) return hipErrorInvalidValue;
                 if (dyn + sizeof(T) * (LANES * PSTRIDE + ARM_BLOB_LEN + 3) > 64 * 1024) return hipErrorInvalidValue;
             }
-#define MJMPC_LAUNCH_F(NW_, MONO_)                                                                                        \
-            hipLaunchKernelGGL((arm_rollout_flags_kernel<T, NW_, MONO_>), dim3(grid), dim3(64 * NW_), dyn, stream, model, state, P, H, A, \
+#define MJMPC_LAUNCH_F(NW_, MONO_, EB_)                                                                                   \
+            hipLaunchKernelGGL((arm_rollout_flags_kernel<T, NW_, MONO_, EB_>), dim3(grid), dim3(64 * NW_), dyn, stream, model, state, P, H, A, \
                                mean, noise, cost, act, obs, nobs, diag, fuse, mono_arg)
-            if (nw == 4) { if (mono) MJMPC_LAUNCH_F(4, true); else MJMPC_LAUNCH_F(4, false); }
-            else { if (mono) MJMPC_LAUNCH_F(2, true); else MJMPC_LAUNCH_F(2, false); }
+            if (nw == 4) { if (mono) MJMPC_LAUNCH_F(4, true, false); else if (eb) MJMPC_LAUNCH_F(4, false, true); else MJMPC_LAUNCH_F(4, false, false); }
+            else { if (mono) MJMPC_LAUNCH_F(2, true, false); else if (eb) MJMPC_LAUNCH_F(2, false, true); else MJMPC_LAUNCH_F(2, false, false); }
 #undef MJMPC_LAUNCH_F
             return hipGetLastError();
         }
     }
-#define MJMPC_LAUNCH_W(STEP_, CL_, W_, DUO_, MONO_)                                                                   \
-    hipLaunchKernelGGL((arm_rollout_kernel<T, STEP_, CL_, W_, DUO_, MONO_>), dim3(grid), dim3(DUO_ ? 128 : 64), dyn,  \
+#define MJMPC_LAUNCH_W(STEP_, CL_, W_, DUO_, MONO_, EB_)                                                              \
+    hipLaunchKernelGGL((arm_rollout_kernel<T, STEP_, CL_, W_, DUO_, MONO_, EB_>), dim3(grid), dim3(DUO_ ? 128 : 64), dyn,  \
                        stream, model, state, P, H, A, mean, noise, cost, act, obs, nobs, state_out, diag, fuse, mono_arg)
-#define MJMPC_LAUNCH(STEP_, CL_, MONO_)                                 \
-    do {                                                                \
-        if (one_per_simd) {                                             \
-            MJMPC_LAUNCH_W(STEP_, CL_, 1, false, MONO_);                \
-        } else if constexpr (sizeof(T) == 8) {                          \
-            MJMPC_LAUNCH_W(STEP_, CL_, 2, false, MONO_);                \
-        } else {                                                        \
-            if (cap == 2) MJMPC_LAUNCH_W(STEP_, CL_, 2, false, MONO_);  \
-            else MJMPC_LAUNCH_W(STEP_, CL_, 3, false, MONO_);           \
-        }                                                               \
+#define MJMPC_LAUNCH(STEP_, CL_, MONO_, EB_)                                 \
+    do {                                                                     \
+        if (one_per_simd) {                                                  \
+            MJMPC_LAUNCH_W(STEP_, CL_, 1, false, MONO_, EB_);                \
+        } else if constexpr (sizeof(T) == 8) {                               \
+            MJMPC_LAUNCH_W(STEP_, CL_, 2, false, MONO_, EB_);                \
+        } else {                                                             \
+            if (cap == 2) MJMPC_LAUNCH_W(STEP_, CL_, 2, false, MONO_, EB_);  \
+            else MJMPC_LAUNCH_W(STEP_, CL_, 3, false, MONO_, EB_);           \
+        }                                                                    \
     } while (0)
+    // the episode batches' twins (not in the extended-joint build: refused above)
+    if constexpr (!XJ) {
+        if (eb == 2) {
+            MJMPC_LAUNCH_W(true, false, 1, true, false, true);
+            return hipGetLastError();
+        }
+        if (eb) {
+            if (duo) MJMPC_LAUNCH_W(false, false, 1, true, false, true);
+            else MJMPC_LAUNCH(false, false, false, true);
+            return hipGetLastError();
+        }
+    }
     if (mono) {
         if (fuse.clw || state_out || obs || nobs || !fuse.gseq || !mono->chol || !mono->tree)
             return hipErrorInvalidValue;
         if (dyn + sizeof(T) * (LANES * PSTRIDE + ARM_BLOB_LEN + 3) > 64 * 1024) return hipErrorInvalidValue;     // H A too large for the LDS tile
-        if (duo) MJMPC_LAUNCH_W(false, false, 1, true, true);
-        else MJMPC_LAUNCH(false, false, true);
+        if (duo) MJMPC_LAUNCH_W(false, false, 1, true, true, false);
+        else MJMPC_LAUNCH(false, false, true, false);
     }
-    else if (fuse.clw) MJMPC_LAUNCH(false, true, false);
-    else if (duo && state_out) MJMPC_LAUNCH_W(true, false, 1, true, false);
-    else if (duo) MJMPC_LAUNCH_W(false, false, 1, true, false);
-    else if (state_out) MJMPC_LAUNCH(true, false, false);
-    else MJMPC_LAUNCH(false, false, false);
+    else if (fuse.clw) MJMPC_LAUNCH(false, true, false, false);
+    else if (duo && state_out) MJMPC_LAUNCH_W(true, false, 1, true, false, false);
+    else if (duo) MJMPC_LAUNCH_W(false, false, 1, true, false, false);
+    else if (state_out) MJMPC_LAUNCH(true, false, false, false);
+    else MJMPC_LAUNCH(false, false, false, false);
 #undef MJMPC_LAUNCH
 #undef MJMPC_LAUNCH_W
     return hipGetLastError();
@@ -2050,9 +2074,9 @@ hipError_t launch_arm_rollout(const T* model, const double* state, long P, int H
 
 template hipError_t launch_arm_rollout<float>(const float*, const double*, long, int, int, const double*,
                                               const float*, float*, float*, float*, float*, double*, unsigned*,
-                                              hipStream_t, RolloutFusion, const MonoStep*);
+                                              hipStream_t, RolloutFusion, const MonoStep*, int);
 template hipError_t launch_arm_rollout<double>(const double*, const double*, long, int, int, const double*,
                                                const double*, double*, double*, double*, double*, double*, unsigned*,
-                                               hipStream_t, RolloutFusion, const MonoStep*);
+                                               hipStream_t, RolloutFusion, const MonoStep*, int);
 
 }  // namespace mjmpc

@@ -13,7 +13,8 @@
     const int lane = threadIdx.x & 63;
     const int wave = NW > 1 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : 0;
     const int l8 = lane_link(lane), g = lane_slot(lane);
-    const long pid = (long)blockIdx.x * LANES + g;
+    // (EB && STEP: workgroup e is env e of P = E - its one live particle sits in slot 0 and is record e of cost / next_obs)
+    const long pid = (EB && STEP) ? (g == 0 ? (long)blockIdx.x : P) : (long)blockIdx.x * LANES + g;
     const bool live = pid < P;
     for (int k = threadIdx.x; k < LANES * STRIDE; k += NT) lds[k] = T(0);
     if constexpr (QUAD) { if (threadIdx.x < QF_COUNT) q_write(qf, threadIdx.x, 0); }
@@ -32,6 +33,7 @@
     const bool resets = fuse.reset_rec != nullptr;
     if (fuse.shard_size > 0) model += ((long)blockIdx.x * LANES / fuse.shard_size) * ARM_BLOB_LEN;
     if (fuse.state_shard_size > 0) state += ((long)blockIdx.x * LANES / fuse.state_shard_size) * (2 * LANES + 3);
+    if constexpr (EB) mean += ((long)blockIdx.x * LANES / fuse.state_shard_size) * ((long)H * A);       // my episode's mean row
     for (int k = threadIdx.x; k < ARM_BLOB_LEN; k += NT) ldsModel[k] = model[k];
     __syncthreads();
     T* ldsM = lds + g * STRIDE;
@@ -315,9 +317,11 @@
     if (!(fabs(q0acc) < INFINITY)) q0acc = INFINITY;
     if (fuse.q0_out && live && l8 == 0) fuse.q0_out[pid] = q0acc;
     // "real env" stepping on the device: particle 0 writes its final (qpos, qvel) back into a state vector
-    if (state_out && pid == 0 && l8 < nv) {
-        state_out[l8] = (double)q;
-        state_out[LANES + l8] = (double)v;
+    // (EB: every workgroup's live particle, into its own state shard)
+    if (state_out && (EB ? live : pid == 0) && l8 < nv) {
+        double* so = EB ? state_out + (long)blockIdx.x * (2 * LANES + 3) : state_out;
+        so[l8] = (double)q;
+        so[LANES + l8] = (double)v;
     }
     if constexpr (MONO) { if (l8 == 0) dyn_lds[g] = live ? q0acc : INFINITY; }     // cost-to-go of my particle
     }   // (wave 0 / the one wave)

@@ -902,6 +902,88 @@ int mjmpc_arm_step_state(mjmpc_arm_t h, int dtype, const double* d_action, void*
     });
 }
 
+int mjmpc_arm_get_state(mjmpc_arm_t h, double* qpos, double* qvel, void* stream) {
+    if (!h || !qpos || !qvel) return fail(MJMPC_E_BADARG, "null argument");
+    HIP_TRY(hipSetDevice(h->device));
+    double st[MJMPC_ARM_STATE_LEN];
+    HIP_TRY(hipMemcpyAsync(st, h->state, sizeof(st), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    std::memcpy(qpos, st, sizeof(double) * h->nv);
+    std::memcpy(qvel, st + mjmpc::LANES, sizeof(double) * h->nv);
+    return 0;
+}
+
+/* ---- episode batches: the engine's E state shards are the batch's E real envs -------------------------- */
+// E of a batch call on this engine; refuses what the twins do not run
+static int arm_batch_shape(const mjmpc_arm_s* h, int* E) {
+    if (h->n_state_shards < 1) return fail(MJMPC_E_BADARG, "the engine has no state shards (mjmpc_arm_set_shard_states)");
+    if (h->n_state_shards > 65535) return fail(MJMPC_E_BADARG, "%d state shards: a batch holds at most 65535 episodes", h->n_state_shards);
+    if (h->n_shards > 1) return fail(MJMPC_E_BADARG, "an episode batch runs one model block (the engine holds %d)", h->n_shards);
+    if (h->xj) return fail(MJMPC_E_BADARG, "extended-joint models (slide joints / friction loss) have no episode-batch kernels: use the tree engine");
+    *E = h->n_state_shards;
+    return 0;
+}
+
+int mjmpc_arm_rollout_fused_batch(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                                  const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
+                                  double* d_q0, void* stream) {
+    if (!h || !d_means || !d_noise || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+    if ((d_q0 != nullptr) != (d_gseq != nullptr)) return fail(MJMPC_E_BADARG, "d_q0 and d_gseq go together");
+    if (H < 1) return fail(MJMPC_E_BADARG, "horizon %d", H);
+    int E = 0;
+    if (int rc = arm_batch_shape(h, &E)) return rc;
+    if (P_total < 1 || P_total % E != 0)
+        return fail(MJMPC_E_BADARG, "P_total = %lld is not divisible by %d episodes", (long long)P_total, E);
+    if ((P_total / E) % mjmpc::LANES != 0)
+        return fail(MJMPC_E_BADARG, "an episode must hold a multiple of 8 particles (got %lld)", (long long)(P_total / E));
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
+    HIP_TRY(hipSetDevice(h->device));
+    mjmpc::RolloutFusion fuse = arm_fuse(h);
+    fuse.state_shard_size = (long)(P_total / E);        // (also the rows of episode e's mean: d_means + e H A)
+    fuse.filt = d_filter_coeffs;
+    fuse.gseq = d_gseq;
+    fuse.q0_out = d_q0;
+    return with_dtype(dtype, "arm_rollout_fused_batch launch", [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::launch_arm_rollout<T>(model<T>(h), h->shard_states, (long)P_total, H, h->nu, d_means, (const T*)d_noise,
+                                            (T*)d_costs, (T*)d_actions, nullptr, nullptr, nullptr, h->diag, (hipStream_t)stream,
+                                            fuse, nullptr, 1);
+    });
+}
+
+int mjmpc_arm_step_shard_states(mjmpc_arm_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream) {
+    if (!h || !d_actions || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
+    int E = 0;
+    if (int rc = arm_batch_shape(h, &E)) return rc;
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return fail(MJMPC_E_BADARG, "unknown dtype %d", dtype);
+    HIP_TRY(hipSetDevice(h->device));
+    // mjmpc_arm_step_state once per workgroup: one live particle, one env step, no noise, the engine's model block and reset
+    // record; workgroup e reads action e and advances state shard e in place
+    mjmpc::RolloutFusion fuse = arm_fuse(h);
+    fuse.state_shard_size = mjmpc::LANES;
+    return with_dtype(dtype, "arm_step_shard_states launch", [&](auto tag) {
+        using T = decltype(tag);
+        return mjmpc::launch_arm_rollout<T>(model<T>(h), h->shard_states, (long)E, 1, h->nu, d_actions, nullptr, (T*)d_costs,
+                                            nullptr, nullptr, (T*)d_next_obs, h->shard_states, h->diag, (hipStream_t)stream,
+                                            fuse, nullptr, 2);
+    });
+}
+
+int mjmpc_arm_get_shard_states(mjmpc_arm_t h, double* qpos, double* qvel, void* stream) {
+    if (!h || !qpos || !qvel) return fail(MJMPC_E_BADARG, "null argument");
+    if (h->n_state_shards < 1) return fail(MJMPC_E_BADARG, "the engine has no state shards (mjmpc_arm_set_shard_states)");
+    HIP_TRY(hipSetDevice(h->device));
+    const size_t L = MJMPC_ARM_STATE_LEN;
+    std::vector<double> st((size_t)h->n_state_shards * L);
+    HIP_TRY(hipMemcpyAsync(st.data(), h->shard_states, sizeof(double) * st.size(), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    for (int k = 0; k < h->n_state_shards; ++k) {
+        std::memcpy(qpos + (size_t)k * h->nv, st.data() + (size_t)k * L, sizeof(double) * h->nv);
+        std::memcpy(qvel + (size_t)k * h->nv, st.data() + (size_t)k * L + mjmpc::LANES, sizeof(double) * h->nv);
+    }
+    return 0;
+}
+
 int mjmpc_arm_solver_failures(mjmpc_arm_t h, uint32_t* count) { return read_counter(h, 0, count); }
 int mjmpc_arm_diverged(mjmpc_arm_t h, uint32_t* count) { return read_counter(h, 1, count); }
 int mjmpc_arm_env_resets(mjmpc_arm_t h, uint32_t* count) { return read_counter(h, ARM_DIAG_ENV_RESETS, count); }

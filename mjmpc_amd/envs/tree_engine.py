@@ -87,28 +87,3 @@ class TreeRolloutEngine(RolloutEngine):
             blob = np.ascontiguousarray(model.blob, np.float64)
         _lib.check(self._lib.mjmpc_tree_set_env_model(self._h, None if blob is None else blob.ctypes.data_as(_lib._dp)))
         self.real_env_blob = blob
-
-    def get_state_device(self):
-        """The device-resident state as the task's state dictionary (one D2H copy; synchronises the stream)."""
-        qp, qv = np.zeros(self.model.nq), np.zeros(self.model.nv)
-        _lib.check(self._lib.mjmpc_tree_get_state(self._h, qp.ctypes.data_as(_lib._dp), qv.ctypes.data_as(_lib._dp), self._stream()))
-        if self.on_env_reset != "ignore":
-            self.check_env_resets("the device-resident env (step_state)")     # (the host has synchronised anyway)
-        if self.forward_task:
-            return dict(qpos=qp, qvel=qv)
-        return dict(qp=qp, qv=qv, qa=np.zeros(self.model.nv), target_pos=self._state["target_pos"].copy(), timestep=0)
-
-    # ------------------------------------------------------------------ raw state shards (episode batches: control/batched.py)
-    def set_shard_states_raw(self, states):
-        """``len(states)`` unpacked states (``_unpack``) become the engine's state shards, whatever ``num_shards`` is: an
-        episode batch's real envs.  ``set_env_state`` / ``get_env_state`` do not know about them."""
-        arr = self._pack_shard_states(states)
-        _lib.check(self._lib.mjmpc_tree_set_shard_states(self._h, arr.ctypes.data_as(_lib._dp), len(states), self._stream()))
-        self._n_raw_shards = len(states)
-
-    def get_shard_states(self):
-        """The state shards of ``set_shard_states_raw`` -> (qpos [n, nq], qvel [n, nv]) (one D2H copy; synchronises the stream)."""
-        qp, qv = np.zeros((self._n_raw_shards, self.model.nq)), np.zeros((self._n_raw_shards, self.model.nv))
-        _lib.check(self._lib.mjmpc_tree_get_shard_states(self._h, qp.ctypes.data_as(_lib._dp), qv.ctypes.data_as(_lib._dp),
-                                                         self._stream()))
-        return qp, qv

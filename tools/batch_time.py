@@ -8,7 +8,12 @@ the same way.  The sequential loop of E episodes costs E times that per control 
 the same shape).  One JSON line per configuration, then a table.
 
     python tools/batch_time.py [--models half_cheetah,swimmer,sawyer] [--E 1,4,16,64] [--P 256,1024] [--H 16,32]
-        [--model-shards K] [--controller mppi|cem|pfmpc|dmd|random_shooting|mppiq] [--repeats R]
+        [--model-shards K] [--controller mppi|cem|pfmpc|dmd|random_shooting|mppiq] [--repeats R] [--engine tree|arm]
+
+--engine arm: the batch runs on ``ArmRolloutEngine`` (``engine="arm"``; the models the arm kernels run: sawyer) and
+the sequential baseline is the single-episode loop on that engine, as ``make_engine`` gives it to a user: the same controller on
+``make_device_rollout_fn(ArmRolloutEngine)`` - for MPPI the fused two-launch step where the engine supports the shape.  The
+per-launch split names the arm entry points.  No dynamics randomization (--model-shards) on this engine.
 
 --controller cem: ``BatchedCEM`` (full covariance, elite_frac 0.1, beta 0.45) against the single-episode fused CEM
 step (CEM, noise_mode='device', graph replay).  --repeats R: every configuration is timed R times, batch and single runs
@@ -110,10 +115,10 @@ CONTROLLERS = {
 LAUNCHES = {name: c["launches"] for name, c in CONTROLLERS.items() if "launches" in c}
 
 
-def make_batch(raw, E, P, H, lam, cov, controller):
+def make_batch(raw, E, P, H, lam, cov, controller, engine="tree"):
     from mjmpc_amd import control
     cls, args = CONTROLLERS[controller]["batch"]
-    return getattr(control, cls)(raw, E, H, P, *args(lam, cov), FILT, "null", [123 + i * 12345 for i in range(E)])
+    return getattr(control, cls)(raw, E, H, P, *args(lam, cov), FILT, "null", [123 + i * 12345 for i in range(E)], engine=engine)
 
 
 class _TimedLib:
@@ -138,11 +143,16 @@ class _TimedLib:
         return timed
 
 
-def launch_split(raw, E, P, H, lam, cov, steps, warmup, controller="pfmpc"):
+def launch_names(controller, engine="tree"):
+    """The library calls the split times: the rollout and the env step are the engine kind's."""
+    return tuple(n.replace("mjmpc_tree_", "mjmpc_%s_" % engine) for n in LAUNCHES[controller])
+
+
+def launch_split(raw, E, P, H, lam, cov, steps, warmup, controller="pfmpc", engine="tree"):
     """ms per library call of one batched PFMPC / DMD-MPC / random-shooting / MPPIQ step (mean over ``steps`` steps)."""
     import torch
-    names = LAUNCHES[controller]
-    b = make_batch(raw, E, P, H, lam, cov, controller)
+    names = launch_names(controller, engine)
+    b = make_batch(raw, E, P, H, lam, cov, controller, engine)
     b.on_env_reset = "ignore"
     for _ in range(warmup):
         b.step()
@@ -155,9 +165,9 @@ def launch_split(raw, E, P, H, lam, cov, steps, warmup, controller="pfmpc"):
     return {n: sum(s.elapsed_time(e) for s, e in timed.events[n]) / steps for n in names}
 
 
-def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
+def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi", engine="tree"):
     import torch
-    b = make_batch(raw, E, P, H, lam, cov, controller)
+    b = make_batch(raw, E, P, H, lam, cov, controller, engine)
     b.on_env_reset = "ignore"
     if K:
         b.randomize_dynamics(dyn_cfg(raw), [123 + i * 12345 for i in range(E)], K)
@@ -173,13 +183,13 @@ def time_batch(raw, E, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     return s.elapsed_time(e) / steps
 
 
-def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
+def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi", engine="tree"):
     import torch
     from mjmpc_amd import control
     from mjmpc_amd.control.controller import resident_state
-    from mjmpc_amd.envs.arm_engine import make_device_rollout_fn
+    from mjmpc_amd.envs.arm_engine import ArmRolloutEngine, make_device_rollout_fn
     from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    eng = TreeRolloutEngine(raw, num_shards=max(K, 1))
+    eng = (ArmRolloutEngine if engine == "arm" else TreeRolloutEngine)(raw, num_shards=max(K, 1))
     eng.on_env_reset = "ignore"
     if K:
         eng.randomize_dynamics(dyn_cfg(raw), 123)
@@ -205,6 +215,8 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi"):
     e.record()
     torch.cuda.synchronize()
     took, complaint = CONTROLLERS[controller].get("took", (None, ""))
+    if engine == "arm":         # (the arm engine's single path takes its own branches - the fused iteration where it has one)
+        took = None
     if took is not None and not took(c):
         raise SystemExit(complaint.format(P=P, H=H))
     eng.close()
@@ -222,7 +234,10 @@ def main():
     ap.add_argument("--model-shards", type=int, default=0, help="randomized model shards per episode (0: no randomization)")
     ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting", "mppiq"])
     ap.add_argument("--repeats", type=int, default=1, help="timings per configuration, batch and single runs alternating")
+    ap.add_argument("--engine", default="tree", choices=["tree", "arm"], help="the engine of the batch and of the single-episode loop")
     args = ap.parse_args()
+    if args.engine == "arm" and args.model_shards:
+        raise SystemExit("--model-shards needs --engine tree (an arm batch rolls out one model block)")
     from mjmpc_amd import _lib
     _lib.require_gpu()          # (no GPU: no numbers)
     ms = models()
@@ -233,18 +248,23 @@ def main():
         for H in [int(x) for x in args.H.split(",")]:
             for P in [int(x) for x in args.P.split(",")]:
                 if args.repeats <= 1:
-                    single = time_single(raw, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller)
+                    single = time_single(raw, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller,
+                                         args.engine)
                 for E in [int(x) for x in args.E.split(",")]:
                     spread = None
                     if args.repeats > 1:        # batch, single, batch, single, ...: medians, and the single path's own spread
                         bs, ss = [], []
                         for _ in range(args.repeats):
-                            bs.append(time_batch(raw, E, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller))
-                            ss.append(time_single(raw, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller))
+                            bs.append(time_batch(raw, E, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller,
+                                                 args.engine))
+                            ss.append(time_single(raw, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller,
+                                                  args.engine))
                         batch, single, spread = sorted(bs)[len(bs) // 2], sorted(ss)[len(ss) // 2], max(ss) - min(ss)
                     else:
-                        batch = time_batch(raw, E, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller)
-                    row = dict(model=name, controller=args.controller, E=E, P=P, H=H, model_shards=args.model_shards,
+                        batch = time_batch(raw, E, P, H, lam, cov, args.steps, args.warmup, args.model_shards, args.controller,
+                                           args.engine)
+                    row = dict(model=name, controller=args.controller, engine=args.engine, E=E, P=P, H=H,
+                               model_shards=args.model_shards,
                                batch_ms_per_step=round(batch, 4),
                                batch_episode_steps_per_s=round(1e3 * E / batch, 1), single_ms_per_step=round(single, 4),
                                sequential_ms_per_step=round(E * single, 4), speedup=round(E * single / batch, 2))
@@ -253,7 +273,7 @@ def main():
                     rows.append(row)
                     print(json.dumps(row), flush=True)
                     if args.controller in LAUNCHES and not args.model_shards:
-                        split = launch_split(raw, E, P, H, lam, cov, args.steps, args.warmup, args.controller)
+                        split = launch_split(raw, E, P, H, lam, cov, args.steps, args.warmup, args.controller, args.engine)
                         splits.append((name, E, P, H, split))
                         print(json.dumps(dict(model=name, controller=args.controller, E=E, P=P, H=H,
                                               launch_ms={k: round(v, 4) for k, v in split.items()})), flush=True)
@@ -265,7 +285,7 @@ def main():
         print("single path, max - min over its repeats (ms): "
               + ", ".join("%d x %d: %.3f" % (r["E"], r["P"], r["single_spread_ms"]) for r in rows))
     if splits:
-        names = LAUNCHES[args.controller]
+        names = launch_names(args.controller, args.engine)
         short = [n.replace("mjmpc_", "").replace("_batch", "") for n in names]
         print("per-launch split of one batched step (ms, device events around each library call)")
         print("%-13s %3s %5s %3s " % ("model", "E", "P", "H") + " ".join("%18s" % n for n in short))
