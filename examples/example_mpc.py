@@ -22,6 +22,7 @@ import yaml
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mjmpc_amd.envs.arm_engine import ArmRolloutEngine, make_device_rollout_fn, make_rollout_fn   # noqa: E402
+from mjmpc_amd.envs.cost_terms import cost_terms_from_config                                     # noqa: E402
 from mjmpc_amd.envs.locomotion_env import HalfCheetahEnv, SwimmerEnv                             # noqa: E402
 from mjmpc_amd.envs.reacher_env import ContinualReacher7DOFEnv, HandTreeEnv, Reacher7DOFEnv      # noqa: E402
 from mjmpc_amd.envs.synthetic_env import CartPoleEnv, DoorEnv, DoublePendulumEnv, GripperEnv, TrayEnv        # noqa: E402
@@ -79,6 +80,11 @@ def main():
     env = ENVS[exp["env_name"]](dtype=args.dtype)                    # the "real" environment
     env.real_env_step(True)
     sim = make_sim(exp["env_name"], args.dtype, num_cpu)             # the rollout engine
+    if exp.get("cost_terms"):
+        # user-defined cost terms: the plans and the controlled env are costed by the same table (before any rollout_fn
+        # is made: with terms set the closures offer the controllers no fused launch)
+        for eng in (sim, env.engine):
+            eng.set_cost_terms(cost_terms_from_config(exp["cost_terms"], eng))
     if args.dyn_randomize_config:
         with open(args.dyn_randomize_config) as f:
             default_params, randomized = sim.randomize_dynamics(yaml.safe_load(f), base_seed=exp["seed"])

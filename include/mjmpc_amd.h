@@ -37,7 +37,7 @@ extern "C" {
  *      fewer motors than dofs). */
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
- *      and the DMD-MPC episode batches'.) */
+ *      the DMD-MPC episode batches' and mjmpc_cost_terms.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -785,6 +785,23 @@ int mjmpc_pf_gather_shift_batch(int E, int64_t M, int H, int A, const double* d_
                                 const int64_t* d_step, double* d_sets_out, double* d_gathered, void* d_ws, void* stream);
 int mjmpc_pf_finish_batch(int E, int64_t M, int H, int A, const void* d_ws, double* d_means, double* d_actions,
                           int64_t* d_step_counter, void* stream);
+
+/* User-defined cost terms: a second launch behind mjmpc_{arm,tree}_rollout / _rollout_cl / _step_state that turns
+ * the next observations (d_next_obs, dtype [P][H][d_obs]) and the actions (d_actions, dtype [P][H][A]; may be NULL if no row
+ * reads an action) of every (particle, step) into a cost, in place in d_costs (dtype [P][H]).  d_terms: float64 [n_terms][8]
+ * on the device, 1 <= n_terms <= 128, a row being  kind, source, index, weight, target, group, when, reserved:
+ *   v = next_obs[p][t][index] (source 0) or actions[p][t][index] (source 1) as double,  r = v - target;
+ *   kind 0 ABS  w |r|;   1 SQUARE  w r^2;   3 COS  w (1 - cos r);
+ *   kind 2 NORM: consecutive rows of kind 2 with the same group > 0 add  w_first sqrt(sum r^2)  once, at the group's last row;
+ *   when = 1: the row counts only at t = H - 1, and only if `terminal` is non-zero (a real env's step is no plan's last step).
+ * cost[p][t] = the sum over the rows in row order, accumulated in double and rounded to dtype; with keep_builtin the cost
+ * already in d_costs is the first addend.  The incoming cost is read either way: where it is not finite the outgoing cost is
+ * +inf (a particle that reset under set_reset_returns "inf" keeps weighing nothing).  The table's contents - kinds, indices
+ * inside d_obs / A, contiguous groups with one `when`, finite numbers - are the caller's to check (envs/cost_terms.py does):
+ * the kernel assumes a valid table.  Refused before anything is launched: null d_next_obs / d_terms / d_costs, P < 1, H < 1,
+ * d_obs < 1, A < 0, n_terms outside 1 .. 128, an unknown dtype, a row of more than 60 KiB. */
+int mjmpc_cost_terms(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                     const double* d_terms, int n_terms, int keep_builtin, int terminal, void* d_costs, void* stream);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,7 @@ SIGNATURES = {
     "mjmpc_pf_gather_shift_batch": (_int, [_int, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, _vp, ctypes.c_uint64, _vp, _vp, _vp,
                                            _vp, _vp]),
     "mjmpc_pf_finish_batch": (_int, [_int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_cost_terms": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
 }
 
 _LIB = None

@@ -1,0 +1,162 @@
+// User-defined cost terms: a second, bandwidth-bound launch behind a rollout that turns the next observations
+// and the actions of every (particle, step) into a cost from a table of terms.  The rollout kernels keep their built-in
+// costs and are not touched: the terms live neither in the model block (its length is part of the ABI) nor in the rollout
+// translation units (an edit there moves the register allocation of every instantiation).
+//
+// A table row is eight doubles - kind, source, index, weight, target, group, when, reserved (include/mjmpc_amd.h):
+//   v = next_obs[p][t][index] (source 0) or actions[p][t][index] (source 1), as double;  r = v - target
+//   kind 0 ABS     w |r|
+//   kind 1 SQUARE  w r^2
+//   kind 2 NORM    consecutive rows of one group > 0: w_first sqrt(sum r^2), once, at the group's last row
+//   kind 3 COS     w (1 - cos r), formed as 2 w sin^2(r / 2): no cancellation near r = 0
+//   when = 1       the row counts only at t = H - 1 and only if the launch says `terminal`
+// The cost of (p, t) is the sum over the rows in row order, in double whatever the storage type, behind the incoming cost
+// when keep_builtin is set; an incoming cost that is not finite leaves as +inf either way (a particle that reset
+// under set_reset_returns("inf"), or diverged, weighs nothing in the updates).
+//
+// Shape: the elements e = p H + t of a launch are independent and their observation rows lie back to back, so a workgroup
+// takes `rows` (64, fewer for very wide rows) consecutive elements, copies their rows into LDS with unit-stride loads (lane i
+// reads word i of the tile) and then lane j walks the table over row j of the tile.  Read straight from memory, lane j's gathers would be d_obs words
+// apart: one 64-byte request per lane and per row of the table.  The LDS rows are padded to an odd number of words, which
+// spreads the lanes' column reads over all banks.  The table is decoded once per workgroup into LDS; every lane reads the
+// same entry at the same time (a broadcast).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/mjmpc_amd.h"
+
+namespace mjmpc {
+int set_error(int code, const char* what, const char* detail);      // capi.hip: the message mjmpc_last_error() returns
+
+namespace {
+
+constexpr int CT_WG = 256;
+constexpr int CT_ROWS = 64;                 // elements per workgroup: four wavefronts copy the tile, one walks the table.  Small
+                                            // tiles put many workgroups in flight; measured against one-wavefront workgroups
+                                            // and against a walk that fetches rows ahead (both slower): profiles/r16_cost_terms.txt
+constexpr int CT_MAX_TERMS = 128;
+constexpr int CT_LDS_BYTES = 60 * 1024;     // the tile's share of a workgroup's 64 KiB (the decoded table takes 3.5 KiB)
+
+// a decoded row's flags
+constexpr int CT_ACTION = 1, CT_TERMINAL = 2, CT_GROUP_FIRST = 4, CT_GROUP_LAST = 8;
+
+// the odd row pitch in words of the tile
+__host__ __device__ inline int ct_pitch(int n) { return n | 1; }
+
+// copy `rows` rows of `width` words, back to back in memory from src, to LDS rows of `pitch` words; unit stride over the lanes
+template <typename T>
+__device__ __forceinline__ void ct_stage(const T* __restrict__ src, int rows, int width, int pitch, T* dst) {
+    const int n = rows * width;
+    int i = threadIdx.x, r = i / width, c = i - r * width;
+    const int dr = CT_WG / width, dc = CT_WG - dr * width;
+    for (; i < n; i += CT_WG) {
+        dst[r * pitch + c] = src[i];
+        r += dr;
+        c += dc;
+        if (c >= width) { c -= width; ++r; }
+    }
+}
+
+// grid: ceil(n / rows) workgroups of CT_WG; dynamic LDS: rows (pitch(d_obs) + pitch(A)) words of T
+template <typename T>
+__global__ __launch_bounds__(CT_WG) void cost_terms_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
+                                                           const double* __restrict__ terms, int n_terms, long n, int H,
+                                                           int d_obs, int A, int rows, int keep_builtin, int terminal,
+                                                           T* __restrict__ costs) {
+    extern __shared__ double ct_tile_raw[];
+    __shared__ double s_w[CT_MAX_TERMS], s_target[CT_MAX_TERMS];
+    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS];
+    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
+    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
+    T* const tile_a = tile_o + (long)rows * po;
+    const long e0 = (long)blockIdx.x * rows;
+    const int mine = n - e0 < rows ? (int)(n - e0) : rows;
+
+    for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
+        const double* row = terms + 8 * k;
+        const int kind = (int)row[0];
+        const double group = row[5];
+        int f = (row[1] != 0.0 ? CT_ACTION : 0) | (row[6] != 0.0 ? CT_TERMINAL : 0);
+        if (kind == 2) {
+            if (k == 0 || (int)terms[8 * (k - 1)] != 2 || terms[8 * (k - 1) + 5] != group) f |= CT_GROUP_FIRST;
+            if (k == n_terms - 1 || (int)terms[8 * (k + 1)] != 2 || terms[8 * (k + 1) + 5] != group) f |= CT_GROUP_LAST;
+        }
+        s_kind[k] = kind;
+        s_col[k] = (int)row[2];
+        s_flags[k] = f;
+        s_w[k] = row[3];
+        s_target[k] = row[4];
+    }
+    ct_stage(nobs + e0 * d_obs, mine, d_obs, po, tile_o);
+    if (act) ct_stage(act + e0 * A, mine, A, pa, tile_a);
+    __syncthreads();
+
+    const int j = threadIdx.x;
+    if (j >= mine) return;
+    const long e = e0 + j;
+    const bool last_step = terminal && (int)(e % H) == H - 1;
+    const T incoming = costs[e];
+    double acc = keep_builtin ? (double)incoming : 0.0;
+    double sq = 0.0, w_group = 0.0;
+    const T* const my_o = tile_o + j * po;
+    const T* const my_a = tile_a + j * pa;
+    for (int k = 0; k < n_terms; ++k) {
+        const int f = s_flags[k], kind = s_kind[k];
+        if ((f & CT_TERMINAL) && !last_step) continue;
+        const double r = (double)((f & CT_ACTION) ? my_a[s_col[k]] : my_o[s_col[k]]) - s_target[k];
+        const double w = s_w[k];
+        if (kind == 0) {
+            acc += w * fabs(r);
+        } else if (kind == 1) {
+            acc += w * (r * r);
+        } else if (kind == 2) {
+            if (f & CT_GROUP_FIRST) { sq = 0.0; w_group = w; }
+            sq += r * r;
+            if (f & CT_GROUP_LAST) acc += w_group * sqrt(sq);
+        } else {
+            const double s = sin(0.5 * r);
+            acc += w * (2.0 * s * s);
+        }
+    }
+    costs[e] = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
+}
+
+int bad(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms", detail); }
+
+template <typename T>
+int launch(int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions, const double* d_terms,
+           int n_terms, int keep_builtin, int terminal, void* d_costs, void* stream) {
+    const long n = (long)P * H;
+    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
+    if (row_bytes > CT_LDS_BYTES) return bad("an observation and action row of more than 60 KiB");
+    int rows = CT_ROWS;
+    while (rows * row_bytes > CT_LDS_BYTES) rows >>= 1;
+    const long blocks = (n + rows - 1) / rows;
+    if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
+    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
+    hipLaunchKernelGGL(cost_terms_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
+                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, n, H, d_obs, A, rows, keep_builtin,
+                       terminal, (T*)d_costs);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms", hipGetErrorString(e));
+}
+
+}  // namespace
+}  // namespace mjmpc
+
+extern "C" int mjmpc_cost_terms(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                                const double* d_terms, int n_terms, int keep_builtin, int terminal, void* d_costs,
+                                void* stream) {
+    if (!d_next_obs || !d_terms || !d_costs) return mjmpc::bad("null argument");
+    if (P < 1 || H < 1 || d_obs < 1 || A < 0) return mjmpc::bad("needs P >= 1, H >= 1, d_obs >= 1 and A >= 0");
+    if (P > ((int64_t)1 << 40)) return mjmpc::bad("more than 2^40 particles");
+    if (d_actions && A < 1) return mjmpc::bad("actions of width 0");
+    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return mjmpc::bad("n_terms must be 1 .. 128");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return mjmpc::bad("dtype must be MJMPC_F32 or MJMPC_F64");
+    if (dtype == MJMPC_F32)
+        return mjmpc::launch<float>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_costs,
+                                    stream);
+    return mjmpc::launch<double>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_costs,
+                                 stream);
+}

@@ -16,7 +16,7 @@ import numpy as np
 
 from .. import _lib
 from ..models.compile import principal_inertia
-from ..models.raw import RawModel
+from ..models.raw import TASK_FORWARD, RawModel
 from ._resets import EnvResetWatch, SimulationUnstableError  # noqa: F401
 from .seeding import np_random
 
@@ -67,6 +67,10 @@ class RolloutEngine(EnvResetWatch):
     forward_task = False            # the locomotion envs' {qpos, qvel} state dictionaries
     _fused_checks_shards = False    # rollout_fused refuses an indivisible population in Python (else the C layer does)
     _shard_states_set_state = False     # a per-shard set_env_state also makes shard 0's state ``_state``
+    _cost_terms = None              # set_cost_terms: the builder, its table on the device, whether a row reads an action
+    _terms_dev = None
+    _terms_read_actions = False
+    _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
 
     def __init__(self, model, device=0, dtype="f64", num_shards=1):
         self.raw = model if isinstance(model, RawModel) else None
@@ -254,9 +258,18 @@ class RolloutEngine(EnvResetWatch):
         act = self._buffer("act", (P, H, A)) if want_actions else None
         obs = self._buffer("obs", (P, H, self.d_obs)) if want_obs else None
         nobs = self._buffer("nobs", (P, H, self.d_obs)) if want_obs else None
+        # cost terms read the next observations (and the actions): the launch writes them whether or not the caller asked
+        t_nobs, t_act = nobs, act
+        if self._terms_dev is not None:
+            t_nobs = nobs if nobs is not None else self._buffer("terms_nobs", (P, H, self.d_obs))
+            if self._terms_read_actions and act is None:
+                t_act = self._buffer("terms_act", (P, H, A))
         fn = self._fn("rollout_cl" if closed else "rollout")
-        _lib.check(fn(self._h, self._code, P, H, _ptr(mean_d), _ptr(noise_d), _ptr(costs), _ptr(act), _ptr(obs),
-                      _ptr(nobs), self._stream()))
+        _lib.check(fn(self._h, self._code, P, H, _ptr(mean_d), _ptr(noise_d), _ptr(costs), _ptr(t_act), _ptr(obs),
+                      _ptr(t_nobs), self._stream()))
+        if self._terms_dev is not None:
+            # (a one-particle rollout under real_step_guard is the controlled env's step: never a plan's last step)
+            self._launch_cost_terms(P, H, t_nobs, t_act, costs, terminal=not self._in_real_step)
         return costs, act, obs, nobs
 
     def rollout_fused(self, num_particles, horizon, mean, raw_noise, filter_coeffs, gamma_seq, q0_out=None):
@@ -264,6 +277,7 @@ class RolloutEngine(EnvResetWatch):
         launch (``mjmpc_*_rollout_fused``).  All arguments are CUDA tensors (``filter_coeffs`` may be
         None; ``q0_out``: a float64 [P] tensor the cost-to-go is written to instead of the engine's own
         buffer).  Returns (costs, actions, q0)."""
+        self._refuse_with_terms("rollout_fused")
         if self._fused_checks_shards and num_particles % self.num_shards != 0:
             raise AssertionError("Number of particles must be divisible by number of shards")
         torch = _torch()
@@ -285,7 +299,61 @@ class RolloutEngine(EnvResetWatch):
         cost = self._buffer("step_cost", (1,))
         nobs = self._buffer("step_obs", (self.d_obs,))
         _lib.check(self._fn("step_state")(self._h, self._code, _ptr(a), _ptr(cost), _ptr(nobs), self._stream()))
+        if self._terms_dev is not None:
+            act = None
+            if self._terms_read_actions:
+                act = self._buffer("step_act", (self.d_action,))
+                act.copy_(a)                # (into the engine's storage type; a launch, no allocation: capturable)
+            self._launch_cost_terms(1, 1, nobs, act, cost, terminal=False)
         return cost, nobs
+
+    # ------------------------------------------------------------------ user-defined cost terms (envs/cost_terms.py)
+    def obs_layout(self):
+        """Named slices of the observation, as the kernels write it.  Reach and orient tasks: ``qpos`` (nq entries,
+        MuJoCo's layout), ``qvel``, ``site`` (the tracked site) and ``site_minus_target``.  Forward task: ``qpos`` - the
+        entries ``qpos[obs_skip:]``, so the block's entry 0 is ``qpos[obs_skip]`` - and ``qvel``."""
+        m, nq = self.model, self._nq
+        if getattr(m, "task", None) == TASK_FORWARD:
+            n = nq - m.obs_skip
+            return dict(qpos=slice(0, n), qvel=slice(n, n + m.nv))
+        n = nq + m.nv
+        return dict(qpos=slice(0, nq), qvel=slice(nq, n), site=slice(n, n + 3), site_minus_target=slice(n + 3, n + 6))
+
+    def set_cost_terms(self, terms):
+        """From now on ``rollout_device`` (both modes), everything built on it (``rollout``, the env classes' ``step``) and
+        ``step_state`` return the cost of ``terms`` (a ``CostTerms``; ``keep_builtin``: added to the built-in cost) instead
+        of the built-in one: a second launch (``mjmpc_cost_terms``) behind the rollout on the same stream.  Rows marked
+        terminal count at a rollout's last step, never in a step of the controlled env (``step_state``, a rollout under
+        ``real_step_guard``).  The fused launches evaluate the built-in cost inside the rollout kernel and refuse to run
+        while terms are set; ``make_device_rollout_fn`` then offers the controllers only the generic iteration - set the
+        terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  Not covered: episode batches,
+        ``AnalyticRolloutEngine``, world sizes above 1."""
+        if self._closure_terms is not None and self._closure_terms != (terms is not None):
+            raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
+                               "controllers %s; set the terms first, then call make_device_rollout_fn"
+                               % (("with", "no fused launches") if self._closure_terms else ("without", "the fused launches")))
+        if terms is None:
+            self._cost_terms = self._terms_dev = None
+            self._terms_read_actions = False
+            return
+        table = np.ascontiguousarray(terms.table(self), np.float64)       # (ValueError before anything reaches the device)
+        torch = _torch()
+        self._terms_dev = torch.from_numpy(table).to(self.device)
+        self._terms_read_actions = bool(np.any(table[:, 1] != 0))
+        self._cost_terms = terms
+
+    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal):
+        t = self._terms_dev
+        _lib.check(self._lib.mjmpc_cost_terms(self._code, P, H, self.d_obs, self.d_action, _ptr(nobs),
+                                              _ptr(act if self._terms_read_actions else None), _ptr(t), t.shape[0],
+                                              int(self._cost_terms.keep_builtin), int(bool(terminal)), _ptr(costs),
+                                              self._stream()))
+
+    def _refuse_with_terms(self, what):
+        if self._cost_terms is not None:
+            raise RuntimeError("%s evaluates the built-in cost inside the rollout kernel and cannot see the table of "
+                               "set_cost_terms; use rollout_device (a rollout_fn made by make_device_rollout_fn after "
+                               "set_cost_terms takes the generic iteration), or set_cost_terms(None)" % what)
 
     def get_state_device(self):
         """The device-resident state as the task's state dictionary (one D2H copy; synchronises the stream)."""
@@ -366,6 +434,12 @@ def make_device_rollout_fn(sim_env):
                     infos={"total_time": np.array([time.time() - t0] * sim_env.num_shards)})
     rollout_fn.accepts_device = True          # controllers may hand over their device-resident mean
     rollout_fn.engine = sim_env
+    if isinstance(sim_env, RolloutEngine):
+        sim_env._closure_terms = sim_env._cost_terms is not None
+        if sim_env._closure_terms:
+            # the fused launches cost inside the rollout kernel and cannot see the table: without them on the closure every
+            # controller takes the generic device iteration (rollout_device + its update launches), captured or eager
+            return rollout_fn
     if hasattr(sim_env, "rollout_fused"):   # filter + cost-to-go fused into the launch (graph fast path)
         rollout_fn.fused = sim_env.rollout_fused
     if hasattr(sim_env, "mppi_step"):       # the whole iteration in one launch (captured iterations of MPPI / DMD-MPC)

@@ -30,6 +30,7 @@ class EnvResetWatch:
     on_env_reset = "raise"
     _env_resets_seen = 0
     _abi = "arm"
+    _in_real_step = False           # inside real_step_guard: cost terms marked terminal do not count (envs/cost_terms.py)
 
     def env_resets(self):
         """Resets of the device-resident real env since the engine was made (synchronises the device)."""
@@ -55,13 +56,18 @@ class EnvResetWatch:
 
     @contextlib.contextmanager
     def real_step_guard(self, where):
-        """Around a host-synchronous step of the controlled env (a one-particle rollout): any reset in it is the real env's."""
-        if self.on_env_reset == "ignore":
+        """Around a host-synchronous step of the controlled env (a one-particle rollout): any reset in it is the real env's.
+        The engine is marked "inside a real step" for the whole body, in the "ignore" mode too."""
+        was, self._in_real_step = self._in_real_step, True
+        try:
+            if self.on_env_reset == "ignore":
+                yield
+                return
+            before = self.diverged_substeps()
             yield
-            return
-        before = self.diverged_substeps()
-        yield
-        new = self.diverged_substeps() - before
+            new = self.diverged_substeps() - before
+        finally:
+            self._in_real_step = was
         if new > 0:
             self._env_reset_event(new, where)
 

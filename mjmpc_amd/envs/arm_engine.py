@@ -73,6 +73,7 @@ class ArmRolloutEngine(RolloutEngine):
         ``DeviceUpdater.sample_noise``, coloured by the device-resident factor ``chol`` (``chol_full``: its whole lower
         triangle - CEM's adapting covariance), filtered on the fly.  Returns (costs, actions, q0) device tensors; nothing
         but the model, the state, the mean and the factor is read from memory."""
+        self._refuse_with_terms("rollout_sampled")
         P, H, A = int(num_particles), int(horizon), self.d_action
         costs, act = self._buffer("costs", (P, H)), self._buffer("act", (P, H, A))
         q0 = self._q0_buffer(P, q0_out)
@@ -92,6 +93,7 @@ class ArmRolloutEngine(RolloutEngine):
         float64 (H,), ``filter_coeffs`` float64 (3,) or None, ``chol`` float64 (A,A), ``step_counter`` int64 (1,));
         ``action_slots`` is a pinned host tensor (2, A+1).  ``record`` (float64 (2 + H*A,)): sharded runs - this GPU's
         softmax record instead of the update.  Returns (costs, actions, q0) device tensors when ``want_trajectories``."""
+        self._refuse_with_terms("mppi_step")
         launch, out = self.mppi_step_launcher(num_particles, horizon, mean, mean_out, gamma_seq, filter_coeffs, chol, seed,
                                               offset, particle_offset, step_counter, lam, step_size, shift_mode, action_out,
                                               action_slots, record, env_step, want_trajectories)
@@ -106,6 +108,7 @@ class ArmRolloutEngine(RolloutEngine):
         calls every step.  ``bind_stream=False``: on the stream that is current when ``launch()`` is called (a launcher
         that is also called under stream capture must say so, or its kernels stay out of the graph).  The tensors must
         stay alive (and in place) while the launcher is in use."""
+        self._refuse_with_terms("mppi_step_launcher")
         P, H, A = int(num_particles), int(horizon), self.d_action
         costs = act = q0 = None
         if want_trajectories:
@@ -134,6 +137,7 @@ class ArmRolloutEngine(RolloutEngine):
                               action_out, action_slots, env_step):
         """Sharded runs: the launch behind the record all-gather (``mjmpc_arm_mppi_combine``) with its arguments bound;
         ``launch()`` enqueues it on the stream that is current WHEN IT IS CALLED (it is called under stream capture)."""
+        self._refuse_with_terms("mppi_combine_launcher")
         scost = self._buffer("step_cost", (1,))         # (bound whether or not this launcher steps the env: the parameter
         snobs = self._buffer("step_obs", (self.d_obs,))  #  block of the call then never changes between launchers)
         keep = (records, mean, mean_out, step_counter, action_out, action_slots, scost, snobs)

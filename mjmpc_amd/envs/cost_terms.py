@@ -1,0 +1,195 @@
+"""User-defined cost terms: a table of terms over the next observation and the action of every (particle,
+step), evaluated on the device by a second launch behind the rollout (``mjmpc_cost_terms``, csrc/cost_terms.hip) in place
+of, or on top of, the cost the rollout kernel has built in.
+
+    terms = CostTerms(engine)
+    terms.norm(obs="site_minus_target", weight=5.0)
+    terms.cos(obs="qpos", index=1)
+    terms.square(obs="qvel", weight=0.01)
+    terms.square(action=0, weight=0.001)
+    terms.square(obs="qvel", weight=1.0, terminal=True)
+    engine.set_cost_terms(terms)                    # before make_device_rollout_fn(engine)
+
+A table row is eight float64: ``kind, source, index, weight, target, group, when, reserved``.  ``v`` is entry ``index`` of
+the next observation (``source`` 0) or of the action (``source`` 1); ``r = v - target``:
+
+* kind 0 ABS ``w |r|``, kind 1 SQUARE ``w r^2``, kind 3 COS ``w (1 - cos r)``;
+* kind 2 NORM: consecutive rows with one ``group`` > 0 add ``w sqrt(sum r^2)`` once, ``w`` the first row's weight;
+* ``when`` 1: the row counts only at a rollout's last step, never in a step of the controlled env.
+
+``obs=`` names a block of ``engine.obs_layout()`` (``index=`` counts inside it; left out: every entry) or gives absolute
+indices into the observation; ``action=`` gives action indices (``True`` or ``"all"``: the block, with ``index=``).
+Everything is checked here, on the host: the kernel assumes a valid table.
+"""
+import numpy as np
+
+from ..models.raw import TASK_REACH
+
+KIND_ABS, KIND_SQUARE, KIND_NORM, KIND_COS = 0, 1, 2, 3
+KINDS = {"abs": KIND_ABS, "square": KIND_SQUARE, "norm": KIND_NORM, "cos": KIND_COS}
+MAX_TERMS = 128
+ROW_LEN = 8
+
+
+def _dims(engine):
+    return int(engine.model.d_obs), int(engine.model.nu)
+
+
+def _finite(x, what):
+    x = np.asarray(x, np.float64)
+    if not np.all(np.isfinite(x)):
+        raise ValueError("cost term: %s must be finite, got %r" % (what, x.tolist()))
+    return x
+
+
+class CostTerms:
+    """A builder of the table.  With an ``engine`` every term is resolved and checked as it is added; without one the
+    terms are kept as written and ``table(engine)`` / ``engine.set_cost_terms`` resolves them."""
+
+    def __init__(self, engine=None, keep_builtin=False):
+        self.engine = engine
+        self.keep_builtin = bool(keep_builtin)
+        self._terms = []            # (kind, source block or None, indices or None, action?, weight, target, terminal)
+
+    # ------------------------------------------------------------------ the four kinds
+    def abs(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
+        return self._add(KIND_ABS, obs, action, index, weight, target, terminal)
+
+    def square(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
+        return self._add(KIND_SQUARE, obs, action, index, weight, target, terminal)
+
+    def cos(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
+        return self._add(KIND_COS, obs, action, index, weight, target, terminal)
+
+    def norm(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
+        """``weight * sqrt(sum_i (v_i - target_i)^2)`` over the indices: one group of the table."""
+        return self._add(KIND_NORM, obs, action, index, weight, target, terminal)
+
+    @classmethod
+    def builtin_reach(cls, engine, keep_builtin=False):
+        """The reach task's built-in cost ``|site - target|_1 + 5 |site - target|_2`` as terms: three ABS rows on
+        ``site_minus_target`` and one NORM group of weight 5 over the same three entries.  Refused for forward and
+        orient models (forward progress reads ``qpos[0]``, which the observation leaves out): add to their built-in cost
+        with ``keep_builtin=True`` instead."""
+        if getattr(engine.model, "task", TASK_REACH) != TASK_REACH:
+            raise ValueError("builtin_reach restates the reach task's cost; this model's task is not reach - use "
+                             "CostTerms(engine, keep_builtin=True) to add terms to its built-in cost")
+        self = cls(engine, keep_builtin=keep_builtin)
+        self.abs(obs="site_minus_target")
+        self.norm(obs="site_minus_target", weight=5.0)
+        return self
+
+    # ------------------------------------------------------------------ the table
+    def __len__(self):
+        """Rows of the table (terms that name a block count its entries: needs the engine)."""
+        return sum(len(self._resolve(t, self.engine)[0]) for t in self._terms)
+
+    def table(self, engine=None):
+        """The ``[K][8]`` float64 array for ``engine`` (default: the builder's own)."""
+        engine = engine if engine is not None else self.engine
+        rows, group = [], 0
+        for t in self._terms:
+            (kind, _, _, _, weight, _, terminal), idx, source, targets = (t,) + self._resolve(t, engine)
+            if kind == KIND_NORM:
+                group += 1              # a fresh id per norm: neighbouring groups never merge
+            for i, tg in zip(idx, targets):
+                rows.append([kind, source, i, weight, tg, group if kind == KIND_NORM else 0, 1.0 if terminal else 0.0, 0.0])
+        if not rows:
+            raise ValueError("cost terms: an empty table (set_cost_terms(None) restores the built-in cost)")
+        if len(rows) > MAX_TERMS:
+            raise ValueError("cost terms: %d rows, the table holds at most %d" % (len(rows), MAX_TERMS))
+        return np.asarray(rows, np.float64).reshape(-1, ROW_LEN)
+
+    # ------------------------------------------------------------------ internals
+    def _add(self, kind, obs, action, index, weight, target, terminal):
+        if (obs is None) == (action is None):
+            raise ValueError("cost term: give exactly one of obs= and action=")
+        is_action = action is not None
+        block = None
+        if is_action:
+            if isinstance(action, str) and action != "all":
+                raise ValueError("unknown action block %r (an index, a list of indices, True or 'all')" % (action,))
+            if not (action is True or isinstance(action, str)):
+                if index is not None:
+                    raise ValueError("cost term: action= already gives the indices; drop index=")
+                index = action
+        elif isinstance(obs, str):
+            block = obs
+        else:
+            if index is not None:
+                raise ValueError("cost term: obs= already gives the indices; drop index=")
+            index = obs
+        if index is not None:
+            index = [int(i) for i in np.atleast_1d(np.asarray(index)).tolist()]
+            if not index:
+                raise ValueError("cost term: an empty index list")
+        weight = float(_finite(weight, "weight"))
+        target = _finite(target, "target")
+        if target.ndim > 1 or (index is not None and target.ndim == 1 and target.size != len(index)):
+            raise ValueError("cost term: target must be a number or one number per index")
+        term = (int(kind), block, index, is_action, weight, target, bool(terminal))
+        if self.engine is not None:
+            self._resolve(term, self.engine)        # refuse now what the engine would refuse later
+        self._terms.append(term)
+        if self.engine is not None and len(self) > MAX_TERMS:
+            self._terms.pop()
+            raise ValueError("cost terms: the table holds at most %d rows" % MAX_TERMS)
+        return self
+
+    @staticmethod
+    def _resolve(term, engine):
+        """-> (absolute indices, source, one target per index) of a term, checked against the engine's dimensions."""
+        _, block, index, is_action, _, target, _ = term
+        if engine is None:
+            if block is not None or index is None:
+                raise ValueError("cost terms that name a block or take every entry need an engine: CostTerms(engine) or "
+                                 "table(engine)")
+            lo, n, limit, what = 0, None, None, "action" if is_action else "observation"
+        elif is_action:
+            lo, n, limit, what = 0, _dims(engine)[1], _dims(engine)[1], "action"
+        elif block is None:
+            lo, n, limit, what = 0, _dims(engine)[0], _dims(engine)[0], "observation"
+        else:
+            layout = engine.obs_layout()
+            if block not in layout:
+                raise ValueError("unknown observation block %r (this engine has %s)" % (block, ", ".join(layout)))
+            sl = layout[block]
+            lo, n, limit, what = sl.start, sl.stop - sl.start, _dims(engine)[0], "block %r" % block
+        idx = list(range(n)) if index is None else index
+        for i in idx:
+            if i < 0 or (n is not None and i >= n):
+                raise ValueError("cost term: index %d outside the %s (%s entries)" % (i, what, n))
+        idx = [lo + i for i in idx]
+        assert limit is None or all(i < limit for i in idx)
+        targets = np.broadcast_to(target, (len(idx),)) if target.ndim == 0 else target
+        if len(targets) != len(idx):
+            raise ValueError("cost term: target must be a number or one number per index")
+        return idx, 1.0 if is_action else 0.0, [float(x) for x in targets]
+
+
+_TERM_KEYS = {"kind", "obs", "action", "index", "weight", "target", "terminal"}
+
+
+def cost_terms_from_config(block, engine):
+    """A config's ``cost_terms`` block -> ``CostTerms`` for ``engine``:
+
+        cost_terms:
+          keep_builtin: false
+          terms:
+            - {kind: norm, obs: site_minus_target, weight: 5.0}
+            - {kind: square, action: 0, weight: 0.001}
+            - {kind: square, obs: qvel, weight: 1.0, terminal: true}
+    """
+    if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms"}:
+        raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin'")
+    terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
+    for entry in block.get("terms") or []:
+        if not isinstance(entry, dict) or set(entry) - _TERM_KEYS:
+            raise ValueError("cost_terms: a term takes %s, got %r" % (sorted(_TERM_KEYS), entry))
+        kind = entry.get("kind")
+        if kind not in KINDS:
+            raise ValueError("cost_terms: unknown kind %r (one of %s)" % (kind, ", ".join(KINDS)))
+        kw = {k: entry[k] for k in ("obs", "action", "index", "weight", "target", "terminal") if k in entry}
+        getattr(terms, kind)(**kw)
+    terms.table()                   # (an empty block is refused here)
+    return terms
