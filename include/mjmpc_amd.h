@@ -201,6 +201,12 @@ int mjmpc_arm_get_state(mjmpc_arm_t h, double* qpos, double* qvel, void* stream)
 int mjmpc_arm_rollout_fused_batch(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
                                   const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
                                   double* d_q0, void* stream);
+/* mjmpc_arm_rollout_fused_batch with the next observations of every (particle, step) as well: d_next_obs dtype
+ * [P_total][H][d_obs] or NULL (then it is mjmpc_arm_rollout_fused_batch); episode e's rows carry site - target with state
+ * shard e's target.  Costs, actions and q0 are those of mjmpc_arm_rollout_fused_batch, bit for bit. */
+int mjmpc_arm_rollout_fused_batch_obs(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means,
+                                      const void* d_noise, const double* d_filter_coeffs, const double* d_gseq, void* d_costs,
+                                      void* d_actions, double* d_q0, void* d_next_obs, void* stream);
 /* env.step of every episode's real env in one launch (as mjmpc_arm_step_state per state shard, bit for bit, resets
  * counted as there): d_actions float64 [E][nu], d_costs dtype [E], d_next_obs dtype [E][d_obs] or NULL; every state shard is
  * advanced in place. */
@@ -302,6 +308,12 @@ int mjmpc_tree_get_state(mjmpc_tree_t h, double* qpos, double* qvel, void* strea
 int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
                                    const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
                                    double* d_q0, void* stream);
+/* mjmpc_tree_rollout_fused_batch with the next observations of every (particle, step) as well: d_next_obs dtype
+ * [P_total][H][d_obs] or NULL (then it is mjmpc_tree_rollout_fused_batch); episode e's rows are those mjmpc_tree_rollout writes
+ * on a single-state engine at state e, also under mjmpc_tree_set_batch_models. */
+int mjmpc_tree_rollout_fused_batch_obs(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means,
+                                       const void* d_noise, const double* d_filter_coeffs, const double* d_gseq, void* d_costs,
+                                       void* d_actions, double* d_q0, void* d_next_obs, void* stream);
 /* env.step of every episode's real env in one launch (examples/example_mpc.py:165-168, as mjmpc_tree_step_state per state
  * shard, bit for bit, resets counted as there): d_actions float64 [E][nu], d_costs dtype [E], d_next_obs dtype [E][d_obs]
  * or NULL; every state shard is advanced in place. */
@@ -802,6 +814,20 @@ int mjmpc_pf_finish_batch(int E, int64_t M, int H, int A, const void* d_ws, doub
  * d_obs < 1, A < 0, n_terms outside 1 .. 128, an unknown dtype, a row of more than 60 KiB. */
 int mjmpc_cost_terms(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
                      const double* d_terms, int n_terms, int keep_builtin, int terminal, void* d_costs, void* stream);
+
+/* mjmpc_cost_terms for an episode batch, one launch: the costs of E * P particles (d_costs dtype [E P][H],
+ * d_next_obs dtype [E P][H][d_obs], d_actions dtype [E P][H][A] or NULL; the episode of particle p is p / P) with the row
+ * semantics of mjmpc_cost_terms.  per_episode = 0: d_terms is float64 [n_terms][8]; per_episode = 1: [E][n_terms][8] - kind,
+ * source, index, group and when are read from episode 0's rows (the caller checks that the episodes agree), weight and target
+ * from the particle's own episode.  The costs are bit for bit those of mjmpc_cost_terms on that episode's rows with that
+ * episode's table.  d_gseq (float64 [H]) and d_q0 (float64 [E P]) go together or are both NULL: q0[p] = the sum over
+ * t = 0 .. H - 1, in this order, of gseq[t] * (double)cost[p][t] with the costs as stored (rounded to dtype), every product and
+ * every sum rounded on its own (no fused multiply-add), +inf where the sum is not finite.  Refused before anything is
+ * launched: null d_next_obs / d_terms / d_costs, E, P, H or d_obs < 1, A < 0, actions with A < 1, n_terms outside 1 .. 128, an
+ * unknown dtype, one of d_gseq / d_q0 without the other, a row of more than 56 KiB. */
+int mjmpc_cost_terms_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                           const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal, void* d_costs,
+                           const double* d_gseq, double* d_q0, void* stream);
 
 #ifdef __cplusplus
 }

@@ -37,6 +37,7 @@ SIGNATURES = {
     "mjmpc_arm_step_state": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_arm_get_state": (_int, [_vp, _dp, _dp, _vp]),
     "mjmpc_arm_rollout_fused_batch": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_arm_rollout_fused_batch_obs": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_arm_step_shard_states": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_arm_get_shard_states": (_int, [_vp, _dp, _dp, _vp]),
     "mjmpc_arm_mppi_combine": (_int, [_vp, _int, _vp, _int, _int, _vp, _vp, _vp, ctypes.c_double, _int, _vp, _vp, _int, _vp, _vp, _vp]),
@@ -57,6 +58,7 @@ SIGNATURES = {
     "mjmpc_tree_step_state": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_get_state": (_int, [_vp, _dp, _dp, _vp]),
     "mjmpc_tree_rollout_fused_batch": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mjmpc_tree_rollout_fused_batch_obs": (_int, [_vp, _int, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_step_shard_states": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_tree_get_shard_states": (_int, [_vp, _dp, _dp, _vp]),
     "mjmpc_tree_set_batch_models": (_int, [_vp, _dp, _int, _int]),
@@ -151,6 +153,8 @@ SIGNATURES = {
                                            _vp, _vp]),
     "mjmpc_pf_finish_batch": (_int, [_int, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp]),
     "mjmpc_cost_terms": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
+    "mjmpc_cost_terms_batch": (_int, [_int, _int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp,
+                                      _vp, _vp]),
 }
 
 _LIB = None

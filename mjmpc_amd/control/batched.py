@@ -43,7 +43,9 @@ are, bit for bit, those of a plain ``mjmpc_arm_rollout_fused`` launch of all ``E
 mean (the arm kernels choose their launch shape from the grid), its env steps those of ``mjmpc_arm_step_state``.  Dynamics
 randomization stays with ``engine="tree"``.  The classes share
 ``_EpisodeBatch``: the engine, the state shards, the buffers, the rollout launch, the env step, ``run``, dynamics
-randomization, the step frame, the bound checks and the covariance status.
+randomization, the step frame, the bound checks, the covariance status and ``set_cost_terms``: a user-defined
+cost (``envs/cost_terms.py``) for every class on both engines, one table for the batch or one per episode with its own weights
+and targets.
 """
 import ctypes
 
@@ -85,6 +87,9 @@ class _EpisodeBatch:
 
     _status = None      # int32 [E] on the device in the batches whose kernels can flag an episode's covariance
     _engine_kind = "tree"   # ``engine=``: "tree" (TreeRolloutEngine) or "arm" (ArmRolloutEngine)
+    _terms = None           # set_cost_terms: (tables on the device, rows, per episode?, keep_builtin, a row reads an action?)
+    _terms_nobs = None      # ... the rollouts' next observations [E P][H][d_obs] (only while terms are set)
+    _terms_env = None       # ... the real-env step's own next observations [E][d_obs] and actions [E][A] in the batch's dtype
 
     def _pick_engine(self, engine, num_particles):
         """The first refusals of every constructor: the ``engine`` keyword, and what the arm engine asks of the population."""
@@ -313,6 +318,64 @@ class _EpisodeBatch:
         _lib.check(self.lib.mjmpc_tree_set_batch_models(self.engine._h, None, 0, 0))
         self.shard_blobs = None
 
+    # ------------------------------------------------------------------ user-defined cost terms
+    def obs_layout(self):
+        """Named slices of the observation (``RolloutEngine.obs_layout``): what ``CostTerms`` resolves ``obs=`` against."""
+        return self.engine.obs_layout()
+
+    @staticmethod
+    def _resolve_cost_terms(terms, engine, E):
+        """``set_cost_terms``'s argument, resolved and checked against ``engine`` on the host -> the tables float64
+        ``[1 or E][K][8]`` (one ``CostTerms``: one table for every episode; a list: one per episode), ``keep_builtin`` and
+        whether a row reads an action.  ``ValueError`` for anything else."""
+        from ..envs.cost_terms import CostTerms
+        per_episode = isinstance(terms, (list, tuple))
+        each = list(terms) if per_episode else [terms]
+        if per_episode and len(each) != E:
+            raise ValueError("set_cost_terms takes one CostTerms for every episode or one per episode (%d), got %d"
+                             % (E, len(each)))
+        if not all(isinstance(t, CostTerms) for t in each):
+            raise ValueError("set_cost_terms takes a CostTerms, a list of them or None")
+        tables = [np.ascontiguousarray(t.table(engine), np.float64) for t in each]    # (an empty table, an index outside)
+        keep, first = each[0].keep_builtin, tables[0]
+        structure = [0, 1, 2, 5, 6, 7]              # kind, source, index, group, when, reserved: shared by the batch
+        for e, (t, table) in enumerate(zip(each, tables)):
+            if table.shape != first.shape:
+                raise ValueError("set_cost_terms: episode %d's table has %d rows, episode 0's %d (the episodes share the "
+                                 "rows; weights and targets may differ)" % (e, len(table), len(first)))
+            if t.keep_builtin != keep:
+                raise ValueError("set_cost_terms: episode %d's keep_builtin differs from episode 0's" % e)
+            if not np.array_equal(table[:, structure], first[:, structure]):
+                raise ValueError("set_cost_terms: episode %d's rows differ from episode 0's in kind, source, index, group or "
+                                 "when (only weights and targets may differ between the episodes)" % e)
+        return np.stack(tables), bool(keep), bool(np.any(first[:, 1] != 0))
+
+    def set_cost_terms(self, terms):
+        """From the next step on the rollouts and the real-env steps of every episode cost what ``terms`` say instead of
+        the built-in cost (``envs/cost_terms.py``; ``keep_builtin``: on top of it).  ``terms``: a ``CostTerms`` for every
+        episode, a list of ``num_episodes`` of them - the same rows with each episode's own weights and targets, e.g. a goal
+        per episode or a sweep of the weights - or ``None``, which restores the built-in cost exactly.  The rollout launch
+        then also writes the next observations (``mjmpc_<engine>_rollout_fused_batch_obs``) and one launch behind it
+        (``mjmpc_cost_terms_batch``) rewrites the costs and forms the cost-to-go; the real-env step is followed by the same
+        launch without the terminal rows.  Everything is checked on the host first (``ValueError``); callable between steps."""
+        if terms is None:
+            self._terms = self._terms_nobs = self._terms_env = None
+            return
+        tables, keep, reads_actions = self._resolve_cost_terms(terms, self.engine, self.num_episodes)
+        torch, E, tdt, dev = self.torch, self.num_episodes, self._tdtype, self.device
+        self._terms = (self._upload(tables), tables.shape[1], int(tables.shape[0] > 1), int(keep), reads_actions)
+        self._terms_nobs = torch.empty((E * self.num_particles, self.horizon, self.d_obs), dtype=tdt, device=dev)
+        # the real-env step's own next observations (a caller may pass none) and its actions in the batch's dtype
+        self._terms_env = (torch.empty((E, self.d_obs), dtype=tdt, device=dev),
+                           torch.empty((E, self.d_action), dtype=tdt, device=dev) if reads_actions else None)
+
+    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s):
+        """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s)."""
+        tables, K, per_episode, keep, reads_actions = self._terms
+        _lib.check(self.lib.mjmpc_cost_terms_batch(self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs),
+                                                   _vp(act) if reads_actions else None, _vp(tables), K, per_episode, keep,
+                                                   terminal, _vp(costs), _vp(gseq), _vp(q0), s))
+
     # ------------------------------------------------------------------ control steps
     def step(self, _out=None):
         """Enqueue one control step of every episode - the subclass's ``_launches``, then the real-env step - without a host
@@ -334,6 +397,15 @@ class _EpisodeBatch:
         deviations from the means, ``_noise`` by default; ``filtered=False``: they are filtered already; ``gseq=False`` /
         ``q0=False``: no discount sequence / no cost-to-go (the update forms its own)."""
         E, P, H = self.num_episodes, self.num_particles, self.horizon
+        if self._terms is not None:
+            # the rollout with its next observations and no cost-to-go, then the terms: costs in place, q0 from the new costs
+            _lib.check(self._fn("rollout_fused_batch_obs")(
+                self.engine._h, self._code, E * P, H, _vp(self._means), _vp(self._noise if noise is None else noise),
+                _vp(self._coeffs) if filtered else None, None, _vp(self._costs), _vp(self._actions), None,
+                _vp(self._terms_nobs), s))
+            self._launch_cost_terms(P, H, self._terms_nobs, self._actions, self._costs, 1, self._gseq if q0 else None,
+                                    self._q0 if q0 else None, s)
+            return
         _lib.check(self._fn("rollout_fused_batch")(
             self.engine._h, self._code, E * P, H, _vp(self._means), _vp(self._noise if noise is None else noise),
             _vp(self._coeffs) if filtered else None, _vp(self._gseq) if gseq else None, _vp(self._costs), _vp(self._actions),
@@ -346,8 +418,17 @@ class _EpisodeBatch:
                                                      0, _vp(self._step_dev), s))
 
     def _env_step(self, act, cost, nobs, s):
-        """The E real envs take their episode's action in one launch."""
+        """The E real envs take their episode's action in one launch; with cost terms a second launch costs the steps (no
+        terminal rows: a real env's step is no plan's last step)."""
+        if self._terms is None:
+            _lib.check(self._fn("step_shard_states")(self.engine._h, self._code, _vp(act), _vp(cost), _vp(nobs), s))
+            return
+        own_obs, act_t = self._terms_env
+        nobs = own_obs if nobs is None else nobs
         _lib.check(self._fn("step_shard_states")(self.engine._h, self._code, _vp(act), _vp(cost), _vp(nobs), s))
+        if act_t is not None:
+            act_t.copy_(act)                # (into the batch's dtype, as step_state does)
+        self._launch_cost_terms(1, 1, nobs, act_t, cost, 0, None, None, s)
 
     def run(self, T):
         """``T`` control steps of every episode -> actions ``[T][E][A]`` (float64), real-env costs ``[T][E]`` and next

@@ -1983,7 +1983,8 @@ hipError_t launch_arm_rollout(const T* model, const double* state, long P, int H
     // workgroup each (the single step's wave: DUO, one live particle), `state_out` the state shards themselves (always the DUO
     // twin: MJMPC_ARM_DUO=0 moves the single step to the one-wave kernel, not this launch)
     if (eb && (XJ || mono || fuse.clw || obs || fuse.state_shard_size <= 0 || fuse.shard_size > 0)) return hipErrorInvalidValue;
-    if (eb == 1 && (state_out || nobs || fuse.state_shard_size % LANES != 0 || P % fuse.state_shard_size != 0)) return hipErrorInvalidValue;
+    // (eb == 1 may ask for the next observations: the store sits in the body every shape runs, behind the episode's `tgt`)
+    if (eb == 1 && (state_out || fuse.state_shard_size % LANES != 0 || P % fuse.state_shard_size != 0)) return hipErrorInvalidValue;
     if (eb == 2 && (!state_out || H != 1 || noise || act || fuse.state_shard_size != LANES)) return hipErrorInvalidValue;
     const unsigned grid = eb == 2 ? (unsigned)P : (unsigned)((P + LANES - 1) / LANES);
     // Cap the resident waves per SIMD at what this launch needs (2, or - f32 only, f64 does not fit - 3): the

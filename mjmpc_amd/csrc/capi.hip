@@ -924,9 +924,10 @@ static int arm_batch_shape(const mjmpc_arm_s* h, int* E) {
     return 0;
 }
 
-int mjmpc_arm_rollout_fused_batch(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
-                                  const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
-                                  double* d_q0, void* stream) {
+// the batch rollout of both entries; d_next_obs: dtype [P_total][H][d_obs] or null
+static int arm_rollout_batch(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                             const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions, double* d_q0,
+                             void* d_next_obs, void* stream) {
     if (!h || !d_means || !d_noise || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
     if ((d_q0 != nullptr) != (d_gseq != nullptr)) return fail(MJMPC_E_BADARG, "d_q0 and d_gseq go together");
     if (H < 1) return fail(MJMPC_E_BADARG, "horizon %d", H);
@@ -946,9 +947,23 @@ int mjmpc_arm_rollout_fused_batch(mjmpc_arm_t h, int dtype, int64_t P_total, int
     return with_dtype(dtype, "arm_rollout_fused_batch launch", [&](auto tag) {
         using T = decltype(tag);
         return mjmpc::launch_arm_rollout<T>(model<T>(h), h->shard_states, (long)P_total, H, h->nu, d_means, (const T*)d_noise,
-                                            (T*)d_costs, (T*)d_actions, nullptr, nullptr, nullptr, h->diag, (hipStream_t)stream,
-                                            fuse, nullptr, 1);
+                                            (T*)d_costs, (T*)d_actions, nullptr, (T*)d_next_obs, nullptr, h->diag,
+                                            (hipStream_t)stream, fuse, nullptr, 1);
     });
+}
+
+int mjmpc_arm_rollout_fused_batch(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                                  const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
+                                  double* d_q0, void* stream) {
+    return arm_rollout_batch(h, dtype, P_total, H, d_means, d_noise, d_filter_coeffs, d_gseq, d_costs, d_actions, d_q0, nullptr,
+                             stream);
+}
+
+int mjmpc_arm_rollout_fused_batch_obs(mjmpc_arm_t h, int dtype, int64_t P_total, int H, const double* d_means,
+                                      const void* d_noise, const double* d_filter_coeffs, const double* d_gseq, void* d_costs,
+                                      void* d_actions, double* d_q0, void* d_next_obs, void* stream) {
+    return arm_rollout_batch(h, dtype, P_total, H, d_means, d_noise, d_filter_coeffs, d_gseq, d_costs, d_actions, d_q0,
+                             d_next_obs, stream);
 }
 
 int mjmpc_arm_step_shard_states(mjmpc_arm_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream) {
@@ -1270,9 +1285,10 @@ int mjmpc_tree_get_state(mjmpc_tree_t h, double* qpos, double* qvel, void* strea
 }
 
 /* ---- episode batches: the engine's E state shards are the batch's E real envs ---------------------------- */
-int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
-                                   const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
-                                   double* d_q0, void* stream) {
+// the batch rollout of both entries; d_next_obs: dtype [P_total][H][d_obs] or null
+static int tree_rollout_batch(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                              const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions, double* d_q0,
+                              void* d_next_obs, void* stream) {
     if (!h || !d_means || !d_noise || !d_costs) return fail(MJMPC_E_BADARG, "null argument");
     if ((d_q0 != nullptr) != (d_gseq != nullptr)) return fail(MJMPC_E_BADARG, "d_q0 and d_gseq go together");
     if (H < 1) return fail(MJMPC_E_BADARG, "horizon %d", H);
@@ -1289,6 +1305,7 @@ int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, i
     c.noise = d_noise;
     c.cost = d_costs;
     c.act = d_actions;
+    c.nobs = d_next_obs;
     c.fuse.filt = d_filter_coeffs;
     c.fuse.gseq = d_gseq;
     c.fuse.q0_out = d_q0;
@@ -1309,6 +1326,20 @@ int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, i
         c.fuse.batch_k = K;
     }
     return tree_issue(h, dtype, c, (hipStream_t)stream, "tree_rollout_fused_batch launch");
+}
+
+int mjmpc_tree_rollout_fused_batch(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means, const void* d_noise,
+                                   const double* d_filter_coeffs, const double* d_gseq, void* d_costs, void* d_actions,
+                                   double* d_q0, void* stream) {
+    return tree_rollout_batch(h, dtype, P_total, H, d_means, d_noise, d_filter_coeffs, d_gseq, d_costs, d_actions, d_q0, nullptr,
+                              stream);
+}
+
+int mjmpc_tree_rollout_fused_batch_obs(mjmpc_tree_t h, int dtype, int64_t P_total, int H, const double* d_means,
+                                       const void* d_noise, const double* d_filter_coeffs, const double* d_gseq, void* d_costs,
+                                       void* d_actions, double* d_q0, void* d_next_obs, void* stream) {
+    return tree_rollout_batch(h, dtype, P_total, H, d_means, d_noise, d_filter_coeffs, d_gseq, d_costs, d_actions, d_q0,
+                              d_next_obs, stream);
 }
 
 int mjmpc_tree_step_shard_states(mjmpc_tree_t h, int dtype, const double* d_actions, void* d_costs, void* d_next_obs, void* stream) {

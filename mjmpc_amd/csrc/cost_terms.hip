@@ -37,6 +37,8 @@ constexpr int CT_ROWS = 64;                 // elements per workgroup: four wave
                                             // and against a walk that fetches rows ahead (both slower): profiles/r16_cost_terms.txt
 constexpr int CT_MAX_TERMS = 128;
 constexpr int CT_LDS_BYTES = 60 * 1024;     // the tile's share of a workgroup's 64 KiB (the decoded table takes 3.5 KiB)
+constexpr int CT_BATCH_LDS_BYTES = 56 * 1024;   // cost_terms_batch_kernel's tile: two sets of weights and targets and a chunk's
+                                                // costs stand beside it (6 KiB)
 
 // a decoded row's flags
 constexpr int CT_ACTION = 1, CT_TERMINAL = 2, CT_GROUP_FIRST = 4, CT_GROUP_LAST = 8;
@@ -58,6 +60,64 @@ __device__ __forceinline__ void ct_stage(const T* __restrict__ src, int rows, in
     }
 }
 
+// decode the structural columns of a table (kind, source, index, group, when) into LDS: `terms` is [n_terms][8]
+__device__ __forceinline__ void ct_decode(const double* __restrict__ terms, int n_terms, int* s_kind, int* s_col, int* s_flags) {
+    for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
+        const double* row = terms + 8 * k;
+        const int kind = (int)row[0];
+        const double group = row[5];
+        int f = (row[1] != 0.0 ? CT_ACTION : 0) | (row[6] != 0.0 ? CT_TERMINAL : 0);
+        if (kind == 2) {
+            if (k == 0 || (int)terms[8 * (k - 1)] != 2 || terms[8 * (k - 1) + 5] != group) f |= CT_GROUP_FIRST;
+            if (k == n_terms - 1 || (int)terms[8 * (k + 1)] != 2 || terms[8 * (k + 1) + 5] != group) f |= CT_GROUP_LAST;
+        }
+        s_kind[k] = kind;
+        s_col[k] = (int)row[2];
+        s_flags[k] = f;
+    }
+}
+
+// the weights and targets of a table into LDS
+__device__ __forceinline__ void ct_decode_values(const double* __restrict__ terms, int n_terms, double* s_w, double* s_target) {
+    for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
+        s_w[k] = terms[8 * k + 3];
+        s_target[k] = terms[8 * k + 4];
+    }
+}
+
+// where a walk takes row k's weight and target from: two arrays in LDS
+struct CtArrays {
+    const double *w, *target;
+    __device__ __forceinline__ double weight(int k) const { return w[k]; }
+    __device__ __forceinline__ double goal(int k) const { return target[k]; }
+};
+
+// one element's walk over the table: its observation row my_o and action row my_a (LDS), `acc` the first addend
+template <typename T, typename V>
+__device__ __forceinline__ double ct_walk(const int* s_kind, const int* s_col, const int* s_flags, int n_terms, const T* my_o,
+                                          const T* my_a, bool last_step, double acc, const V values) {
+    double sq = 0.0, w_group = 0.0;
+    for (int k = 0; k < n_terms; ++k) {
+        const int f = s_flags[k], kind = s_kind[k];
+        if ((f & CT_TERMINAL) && !last_step) continue;
+        const double r = (double)((f & CT_ACTION) ? my_a[s_col[k]] : my_o[s_col[k]]) - values.goal(k);
+        const double w = values.weight(k);
+        if (kind == 0) {
+            acc += w * fabs(r);
+        } else if (kind == 1) {
+            acc += w * (r * r);
+        } else if (kind == 2) {
+            if (f & CT_GROUP_FIRST) { sq = 0.0; w_group = w; }
+            sq += r * r;
+            if (f & CT_GROUP_LAST) acc += w_group * sqrt(sq);
+        } else {
+            const double s = sin(0.5 * r);
+            acc += w * (2.0 * s * s);
+        }
+    }
+    return acc;
+}
+
 // grid: ceil(n / rows) workgroups of CT_WG; dynamic LDS: rows (pitch(d_obs) + pitch(A)) words of T
 template <typename T>
 __global__ __launch_bounds__(CT_WG) void cost_terms_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
@@ -73,21 +133,8 @@ __global__ __launch_bounds__(CT_WG) void cost_terms_kernel(const T* __restrict__
     const long e0 = (long)blockIdx.x * rows;
     const int mine = n - e0 < rows ? (int)(n - e0) : rows;
 
-    for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
-        const double* row = terms + 8 * k;
-        const int kind = (int)row[0];
-        const double group = row[5];
-        int f = (row[1] != 0.0 ? CT_ACTION : 0) | (row[6] != 0.0 ? CT_TERMINAL : 0);
-        if (kind == 2) {
-            if (k == 0 || (int)terms[8 * (k - 1)] != 2 || terms[8 * (k - 1) + 5] != group) f |= CT_GROUP_FIRST;
-            if (k == n_terms - 1 || (int)terms[8 * (k + 1)] != 2 || terms[8 * (k + 1) + 5] != group) f |= CT_GROUP_LAST;
-        }
-        s_kind[k] = kind;
-        s_col[k] = (int)row[2];
-        s_flags[k] = f;
-        s_w[k] = row[3];
-        s_target[k] = row[4];
-    }
+    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
+    ct_decode_values(terms, n_terms, s_w, s_target);
     ct_stage(nobs + e0 * d_obs, mine, d_obs, po, tile_o);
     if (act) ct_stage(act + e0 * A, mine, A, pa, tile_a);
     __syncthreads();
@@ -97,29 +144,79 @@ __global__ __launch_bounds__(CT_WG) void cost_terms_kernel(const T* __restrict__
     const long e = e0 + j;
     const bool last_step = terminal && (int)(e % H) == H - 1;
     const T incoming = costs[e];
-    double acc = keep_builtin ? (double)incoming : 0.0;
-    double sq = 0.0, w_group = 0.0;
-    const T* const my_o = tile_o + j * po;
-    const T* const my_a = tile_a + j * pa;
-    for (int k = 0; k < n_terms; ++k) {
-        const int f = s_flags[k], kind = s_kind[k];
-        if ((f & CT_TERMINAL) && !last_step) continue;
-        const double r = (double)((f & CT_ACTION) ? my_a[s_col[k]] : my_o[s_col[k]]) - s_target[k];
-        const double w = s_w[k];
-        if (kind == 0) {
-            acc += w * fabs(r);
-        } else if (kind == 1) {
-            acc += w * (r * r);
-        } else if (kind == 2) {
-            if (f & CT_GROUP_FIRST) { sq = 0.0; w_group = w; }
-            sq += r * r;
-            if (f & CT_GROUP_LAST) acc += w_group * sqrt(sq);
-        } else {
-            const double s = sin(0.5 * r);
-            acc += w * (2.0 * s * s);
+    const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa, last_step,
+                               keep_builtin ? (double)incoming : 0.0, CtArrays{s_w, s_target});
+    costs[e] = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
+}
+
+// The episode batches' launch: the costs of E P particles, [E P][H], with one table for all or one per episode
+// (the structural columns are episode 0's; weight and target the particle's own episode's), and in the same launch the
+// discounted cost-to-go q0[p] = sum_t gseq[t] cost[p][t] of the costs as stored, forward, every product and sum rounded.
+// A workgroup owns `ppw` whole particles - as many as fit the tile's `rows` elements, one if H is longer, and with a table per
+// episode no more than an episode holds - and takes their ppw H elements in chunks of `rows`: stage, walk (lane j = element j
+// of the chunk), store the cost and leave gseq[t] cost in LDS, then thread s < ppw carries particle s's sum on over the
+// chunk's elements of that particle.  So a particle's costs meet in one thread whatever H is, the products are formed by all
+// lanes and only the additions are serial, and the observations are read once.  ppw <= P consecutive particles cross at most
+// one episode boundary: two sets of weights and targets are decoded into LDS and a lane picks its episode's.
+// grid: ceil(E P / ppw) workgroups of CT_WG; dynamic LDS as cost_terms_kernel's
+template <typename T>
+__global__ __launch_bounds__(CT_WG) void cost_terms_batch_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
+                                                                 const double* __restrict__ terms, int n_terms, long np, long P,
+                                                                 int H, int d_obs, int A, int rows, int ppw, int per_episode,
+                                                                 int keep_builtin, int terminal, T* __restrict__ costs,
+                                                                 const double* __restrict__ gseq, double* __restrict__ q0) {
+    extern __shared__ double ct_tile_raw[];
+    __shared__ double s_w[2][CT_MAX_TERMS], s_target[2][CT_MAX_TERMS], s_gc[CT_ROWS];
+    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS];
+    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
+    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
+    T* const tile_a = tile_o + (long)rows * po;
+    const long p0 = (long)blockIdx.x * ppw;                         // my first particle
+    const int my_p = np - p0 < ppw ? (int)(np - p0) : ppw;          // my particles
+    const long e0 = p0 * H;
+    const int my_n = my_p * H;                                      // my elements (ppw > 1 only where ppw H <= rows)
+    // my particles from `second` on belong to the episode after my first particle's
+    int second = my_p;
+    if (per_episode) {
+        const long ep0 = p0 / P, next = (ep0 + 1) * P - p0;
+        ct_decode_values(terms + ep0 * 8L * n_terms, n_terms, s_w[0], s_target[0]);
+        if (next < my_p) {
+            second = (int)next;
+            ct_decode_values(terms + (ep0 + 1) * 8L * n_terms, n_terms, s_w[1], s_target[1]);
+        }
+    } else {
+        ct_decode_values(terms, n_terms, s_w[0], s_target[0]);
+    }
+    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
+    double q = 0.0;                                                 // thread s < my_p: particle p0 + s's sum so far
+    const int j = threadIdx.x;
+    for (int c0 = 0; c0 < my_n; c0 += rows) {
+        const int mine = my_n - c0 < rows ? my_n - c0 : rows;
+        ct_stage(nobs + (e0 + c0) * d_obs, mine, d_obs, po, tile_o);
+        if (act) ct_stage(act + (e0 + c0) * A, mine, A, pa, tile_a);
+        __syncthreads();
+        if (j < mine) {
+            const int le = c0 + j, pl = le / H, t = le - pl * H;    // my element: particle pl of the workgroup's, step t
+            const double g = gseq ? gseq[t] : 0.0;
+            const T incoming = costs[e0 + le];
+            const int slot = pl >= second;
+            const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa,
+                                       terminal && t == H - 1, keep_builtin ? (double)incoming : 0.0,
+                                       CtArrays{s_w[slot], s_target[slot]});
+            const T out = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
+            costs[e0 + le] = out;
+            s_gc[j] = g * (double)out;
+        }
+        __syncthreads();
+        if (q0 && j < my_p) {
+            // my particle's elements are [j H, (j + 1) H) of the workgroup's; this chunk holds [c0, c0 + mine)
+            const int lo = j * H > c0 ? j * H : c0;
+            const int hi = (j + 1) * H < c0 + mine ? (j + 1) * H : c0 + mine;
+#pragma unroll 4
+            for (int i = lo; i < hi; ++i) q += s_gc[i - c0];
         }
     }
-    costs[e] = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
+    if (q0 && j < my_p) q0[p0 + j] = fabs(q) < (double)INFINITY ? q : (double)INFINITY;
 }
 
 int bad(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms", detail); }
@@ -142,8 +239,50 @@ int launch(int64_t P, int H, int d_obs, int A, const void* d_next_obs, const voi
     return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms", hipGetErrorString(e));
 }
 
+int bad_batch(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_batch", detail); }
+
+template <typename T>
+int launch_batch(int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                 const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal, void* d_costs,
+                 const double* d_gseq, double* d_q0, void* stream) {
+    const long np = (long)E * P;
+    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
+    if (row_bytes > CT_BATCH_LDS_BYTES) return bad_batch("an observation and action row of more than 56 KiB");
+    int rows = CT_ROWS;
+    while (rows * row_bytes > CT_BATCH_LDS_BYTES) rows >>= 1;
+    int ppw = H >= rows ? 1 : rows / H;             // whole particles per workgroup ...
+    if (per_episode && ppw > P) ppw = (int)P;       // ... of at most two episodes
+    const long blocks = (np + ppw - 1) / ppw;
+    if (blocks > INT32_MAX) return bad_batch("more than 2^31 workgroups");
+    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
+    hipLaunchKernelGGL(cost_terms_batch_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
+                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, np, (long)P, H, d_obs, A, rows, ppw,
+                       per_episode, keep_builtin, terminal, (T*)d_costs, d_gseq, d_q0);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_batch", hipGetErrorString(e));
+}
+
 }  // namespace
 }  // namespace mjmpc
+
+extern "C" int mjmpc_cost_terms_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                      const void* d_actions, const double* d_terms, int n_terms, int per_episode,
+                                      int keep_builtin, int terminal, void* d_costs, const double* d_gseq, double* d_q0,
+                                      void* stream) {
+    using mjmpc::bad_batch;
+    if (!d_next_obs || !d_terms || !d_costs) return bad_batch("null argument");
+    if (E < 1 || P < 1 || H < 1 || d_obs < 1 || A < 0) return bad_batch("needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 0");
+    if (P > ((int64_t)1 << 40) / E) return bad_batch("more than 2^40 particles");
+    if (d_actions && A < 1) return bad_batch("actions of width 0");
+    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_batch("n_terms must be 1 .. 128");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_batch("dtype must be MJMPC_F32 or MJMPC_F64");
+    if ((d_gseq != nullptr) != (d_q0 != nullptr)) return bad_batch("d_gseq and d_q0 go together");
+    if (dtype == MJMPC_F32)
+        return mjmpc::launch_batch<float>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
+                                          keep_builtin, terminal, d_costs, d_gseq, d_q0, stream);
+    return mjmpc::launch_batch<double>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
+                                       keep_builtin, terminal, d_costs, d_gseq, d_q0, stream);
+}
 
 extern "C" int mjmpc_cost_terms(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
                                 const double* d_terms, int n_terms, int keep_builtin, int terminal, void* d_costs,

@@ -326,7 +326,8 @@ class RolloutEngine(EnvResetWatch):
         terminal count at a rollout's last step, never in a step of the controlled env (``step_state``, a rollout under
         ``real_step_guard``).  The fused launches evaluate the built-in cost inside the rollout kernel and refuse to run
         while terms are set; ``make_device_rollout_fn`` then offers the controllers only the generic iteration - set the
-        terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  Not covered: episode batches,
+        terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  The episode batches have their own
+        ``set_cost_terms`` (``control/batched.py``, DESIGN 10.8: one table for the batch or one per episode).  Not covered:
         ``AnalyticRolloutEngine``, world sizes above 1."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "

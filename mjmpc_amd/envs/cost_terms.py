@@ -170,7 +170,13 @@ class CostTerms:
 _TERM_KEYS = {"kind", "obs", "action", "index", "weight", "target", "terminal"}
 
 
-def cost_terms_from_config(block, engine):
+def _per_episode_value(value, E):
+    """A term's ``weight`` / ``target`` in a config for a batch of ``E`` episodes -> its E values if it is a list of E entries
+    (one per episode: a number, or for ``target`` one number per index), else None (one value for every episode)."""
+    return list(value) if E is not None and isinstance(value, (list, tuple)) and len(value) == E else None
+
+
+def cost_terms_from_config(block, engine, num_episodes=None):
     """A config's ``cost_terms`` block -> ``CostTerms`` for ``engine``:
 
         cost_terms:
@@ -179,17 +185,35 @@ def cost_terms_from_config(block, engine):
             - {kind: norm, obs: site_minus_target, weight: 5.0}
             - {kind: square, action: 0, weight: 0.001}
             - {kind: square, obs: qvel, weight: 1.0, terminal: true}
-    """
+
+    ``num_episodes`` (an episode batch's): a ``weight`` or ``target`` that is a list of ``num_episodes`` entries holds one
+    value per episode (a target entry may itself be one number per index) and the result is a list of ``num_episodes``
+    ``CostTerms``, one table per episode for ``_EpisodeBatch.set_cost_terms``; without such a list one ``CostTerms`` as ever.
+    A ``weight`` list of another length is refused; a ``target`` list of another length is one number per index."""
     if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms"}:
         raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin'")
-    terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
-    for entry in block.get("terms") or []:
+    E = None if num_episodes is None else int(num_episodes)
+    entries = block.get("terms") or []
+    per_episode = False
+    for entry in entries:
         if not isinstance(entry, dict) or set(entry) - _TERM_KEYS:
             raise ValueError("cost_terms: a term takes %s, got %r" % (sorted(_TERM_KEYS), entry))
-        kind = entry.get("kind")
-        if kind not in KINDS:
-            raise ValueError("cost_terms: unknown kind %r (one of %s)" % (kind, ", ".join(KINDS)))
-        kw = {k: entry[k] for k in ("obs", "action", "index", "weight", "target", "terminal") if k in entry}
-        getattr(terms, kind)(**kw)
-    terms.table()                   # (an empty block is refused here)
-    return terms
+        if entry.get("kind") not in KINDS:
+            raise ValueError("cost_terms: unknown kind %r (one of %s)" % (entry.get("kind"), ", ".join(KINDS)))
+        if isinstance(entry.get("weight"), (list, tuple)) and _per_episode_value(entry["weight"], E) is None:
+            raise ValueError("cost_terms: a list-valued weight holds one weight per episode%s, got %d"
+                             % ("" if E is None else " (%d)" % E, len(entry["weight"])))
+        per_episode = per_episode or any(_per_episode_value(entry.get(k), E) is not None for k in ("weight", "target"))
+    out = []
+    for e in range(E if per_episode else 1):
+        terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
+        for entry in entries:
+            kw = {k: entry[k] for k in ("obs", "action", "index", "weight", "target", "terminal") if k in entry}
+            for k in ("weight", "target"):
+                each = _per_episode_value(kw.get(k), E)
+                if each is not None:
+                    kw[k] = each[e]
+            getattr(terms, entry["kind"])(**kw)
+        terms.table()               # (an empty block is refused here)
+        out.append(terms)
+    return out if per_episode else out[0]

@@ -9,6 +9,7 @@ the same shape).  One JSON line per configuration, then a table.
 
     python tools/batch_time.py [--models half_cheetah,swimmer,sawyer] [--E 1,4,16,64] [--P 256,1024] [--H 16,32]
         [--model-shards K] [--controller mppi|cem|pfmpc|dmd|random_shooting|mppiq] [--repeats R] [--engine tree|arm]
+        [--cost-terms]
 
 --engine arm: the batch runs on ``ArmRolloutEngine`` (``engine="arm"``; the models the arm kernels run: sawyer) and
 the sequential baseline is the single-episode loop on that engine, as ``make_engine`` gives it to a user: the same controller on
@@ -35,6 +36,13 @@ record, combine, tail, env step), with the per-launch split of one batched step 
 --controller mppiq: ``BatchedMPPIQ`` (alpha 1, time-based weights, td_lam 0.9, beta = the model's lam) against the
 single-episode captured MPPIQ loop (MPPIQ, noise_mode='device', graph replay: draw, rollout, TD(lambda) returns, weights,
 maxima, partial moments, record, combine, tail, env step), with the per-launch split of one batched step as for pfmpc.
+
+--cost-terms: instead of the comparison with the sequential loop, every configuration's batch is timed without
+and with user-defined cost terms (``set_cost_terms``: ``CostTerms.builtin_reach`` for sawyer, ``keep_builtin`` plus four rows for
+the forward-task models), the two batches alive in one process and their windows of --steps steps alternating, --repeats windows
+each (median, min, max).  Then ``mjmpc_cost_terms_batch`` (with its cost-to-go) alone against ``mjmpc_cost_terms`` alone and
+against a minimal launch (``mjmpc_cost_terms`` on one element) on the same buffers, 4096 x 32 and 2048 x 32 with the reacher's
+widths, the six-row and the 32-row table of profiles/r16_cost_terms.txt, windows of 200 launches alternating.
 
 --model-shards K: the batch rolls out K randomized model shards per episode (a set per episode, body masses
 +- 20 %) and the single-episode path is the sequential dynamics-randomized loop - a K-shard engine with randomized blocks
@@ -223,6 +231,129 @@ def time_single(raw, P, H, lam, cov, steps, warmup, K=0, controller="mppi", engi
     return s.elapsed_time(e) / steps
 
 
+def batch_terms(name, b):
+    """--cost-terms: the table a model's batch is timed with."""
+    from mjmpc_amd.envs.cost_terms import CostTerms
+    if name == "sawyer":
+        return CostTerms.builtin_reach(b.engine)
+    t = CostTerms(b.engine, keep_builtin=True)
+    t.square(obs="qvel", index=0, weight=0.1, target=1.0)
+    t.abs(obs="qpos", index=1, weight=0.5)
+    t.square(action=0, weight=0.01)
+    t.square(obs="qvel", index=2, weight=0.2, terminal=True)
+    return t
+
+
+def _median(xs):
+    return sorted(xs)[len(xs) // 2]
+
+
+def time_with_and_without_terms(raw, name, E, P, H, lam, cov, steps, warmup, repeats, controller, engine):
+    """ms per batched step -> {variant: [windows]}: one batch without and one with terms, windows alternating."""
+    import torch
+    batches = {}
+    for variant in ("builtin", "terms"):
+        b = batches[variant] = make_batch(raw, E, P, H, lam, cov, controller, engine)
+        b.on_env_reset = "ignore"
+        if variant == "terms":
+            b.set_cost_terms(batch_terms(name, b))
+        for _ in range(warmup):
+            b.step()
+    torch.cuda.synchronize()
+    out = {v: [] for v in batches}
+    for _ in range(repeats):
+        for variant, b in batches.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(steps):
+                b.step()
+            e.record()
+            torch.cuda.synchronize()
+            out[variant].append(s.elapsed_time(e) / steps)
+    for b in batches.values():
+        b.close()
+    return out
+
+
+def time_terms_kernels(E=16, windows=7, launches=200):
+    """us per launch -> {table: {variant: [windows]}} at E x 256 particles, H 32, d_obs 20, A 7 (f64), the variants alternating."""
+    import ctypes
+    import numpy as np
+    import torch
+    from mjmpc_amd import _lib
+    from mjmpc_amd.envs.arm_engine import ArmRolloutEngine
+    from mjmpc_amd.envs.cost_terms import CostTerms
+    from mjmpc_amd.models.reacher7dof import reacher7dof_raw
+    lib = _lib.require_gpu()
+    host = ArmRolloutEngine.host_only(reacher7dof_raw())
+    mixed = CostTerms(host).square(obs="qvel", weight=0.01).square(action=True, weight=0.001).cos(obs="qpos", weight=0.1)
+    mixed.abs(obs="site_minus_target").norm(obs="site_minus_target", weight=5.0).square(obs="qvel", index=[0, 1, 2, 3, 4],
+                                                                                         weight=1.0, terminal=True)
+    P, H, D, A = 256, 32, 20, 7
+    N = E * P
+    rng = np.random.default_rng(0)
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()        # noqa: E731
+    nobs, act, costs = dev(rng.uniform(-1, 1, (N, H, D))), dev(rng.uniform(-1, 1, (N, H, A))), dev(rng.uniform(0, 1, (N, H)))
+    gseq, q0 = dev(np.cumprod([1.0] + [0.99] * (H - 1))), torch.empty(N, dtype=torch.float64, device="cuda")
+    vp = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())     # noqa: E731
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    out = {}
+    for label, terms in (("builtin_reach (6 rows)", CostTerms.builtin_reach(host)), ("mixed (32 rows)", mixed)):
+        table = terms.table()
+        per_episode = dev(np.stack([table] * E))
+        tab, K = dev(table), len(table)
+        a = act if np.any(table[:, 1] != 0) else None
+        variants = {
+            "mjmpc_cost_terms": lambda: lib.mjmpc_cost_terms(_lib.F64, N, H, D, A, vp(nobs), vp(a), vp(tab), K, 0, 1, vp(costs), stream),
+            "minimal launch (mjmpc_cost_terms on one element)":
+                lambda: lib.mjmpc_cost_terms(_lib.F64, 1, 1, D, A, vp(nobs), vp(a), vp(tab), K, 0, 1, vp(costs), stream),
+            "mjmpc_cost_terms_batch, no q0":
+                lambda: lib.mjmpc_cost_terms_batch(_lib.F64, E, P, H, D, A, vp(nobs), vp(a), vp(tab), K, 0, 0, 1, vp(costs), None, None, stream),
+            "mjmpc_cost_terms_batch + q0":
+                lambda: lib.mjmpc_cost_terms_batch(_lib.F64, E, P, H, D, A, vp(nobs), vp(a), vp(tab), K, 0, 0, 1, vp(costs), vp(gseq), vp(q0), stream),
+            "mjmpc_cost_terms_batch + q0, a table per episode":
+                lambda: lib.mjmpc_cost_terms_batch(_lib.F64, E, P, H, D, A, vp(nobs), vp(a), vp(per_episode), K, 1, 0, 1, vp(costs), vp(gseq), vp(q0), stream),
+        }
+        for fn in variants.values():
+            for _ in range(50):
+                _lib.check(fn())
+        torch.cuda.synchronize()
+        res = out[label] = {v: [] for v in variants}
+        for _ in range(windows):
+            for v, fn in variants.items():
+                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s.record()
+                for _ in range(launches):
+                    fn()
+                e.record()
+                torch.cuda.synchronize()
+                res[v].append(1e3 * s.elapsed_time(e) / launches)
+    return out
+
+
+def main_cost_terms(args):
+    ms = models()
+    for name in args.models.split(","):
+        fn, lam, cov = ms[name]
+        raw = fn()
+        for H in [int(x) for x in args.H.split(",")]:
+            for P in [int(x) for x in args.P.split(",")]:
+                for E in [int(x) for x in args.E.split(",")]:
+                    w = time_with_and_without_terms(raw, name, E, P, H, lam, cov, args.steps, args.warmup, max(args.repeats, 3),
+                                                    args.controller, args.engine)
+                    row = dict(model=name, controller=args.controller, engine=args.engine, E=E, P=P, H=H)
+                    for v, xs in w.items():
+                        row[v + "_ms_per_step"] = dict(median=round(_median(xs), 4), min=round(min(xs), 4), max=round(max(xs), 4))
+                    row["terms_over_builtin"] = round(_median(w["terms"]) / _median(w["builtin"]), 4)
+                    print(json.dumps(row), flush=True)
+    # (16 x 256 x 32 elements are 8 workgroups per CU on 256 CUs, 8 x 256 x 32 are 4: one round of workgroups for both kernels)
+    for E in (16, 8):
+        for label, res in time_terms_kernels(E).items():
+            for v, xs in res.items():
+                print("%5d x 32  %-24s %-52s median %8.2f us  (min %8.2f, max %8.2f)"
+                      % (E * 256, label, v, _median(xs), min(xs), max(xs)), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", default="half_cheetah,swimmer,sawyer")
@@ -235,7 +366,13 @@ def main():
     ap.add_argument("--controller", default="mppi", choices=["mppi", "cem", "pfmpc", "dmd", "random_shooting", "mppiq"])
     ap.add_argument("--repeats", type=int, default=1, help="timings per configuration, batch and single runs alternating")
     ap.add_argument("--engine", default="tree", choices=["tree", "arm"], help="the engine of the batch and of the single-episode loop")
+    ap.add_argument("--cost-terms", action="store_true", help="time every batch without and with user-defined cost terms, "
+                    "then mjmpc_cost_terms_batch alone (DESIGN 10.8)")
     args = ap.parse_args()
+    if args.cost_terms:
+        from mjmpc_amd import _lib
+        _lib.require_gpu()
+        return main_cost_terms(args)
     if args.engine == "arm" and args.model_shards:
         raise SystemExit("--model-shards needs --engine tree (an arm batch rolls out one model block)")
     from mjmpc_amd import _lib
