@@ -80,11 +80,16 @@ def main():
     env = ENVS[exp["env_name"]](dtype=args.dtype)                    # the "real" environment
     env.real_env_step(True)
     sim = make_sim(exp["env_name"], args.dtype, num_cpu)             # the rollout engine
+    tracks = False
     if exp.get("cost_terms"):
         # user-defined cost terms: the plans and the controlled env are costed by the same table (before any rollout_fn
         # is made: with terms set the closures offer the controllers no fused launch)
         for eng in (sim, env.engine):
-            eng.set_cost_terms(cost_terms_from_config(exp["cost_terms"], eng))
+            terms = cost_terms_from_config(exp["cost_terms"], eng)
+            eng.set_cost_terms(terms)
+        # terms with a reference: the controlled env's engine counts its own steps; the rollout engine cannot
+        # see them and is told the env time before every plan
+        tracks = terms.tracked
     if args.dyn_randomize_config:
         with open(args.dyn_randomize_config) as f:
             default_params, randomized = sim.randomize_dynamics(yaml.safe_load(f), base_seed=exp["seed"])
@@ -106,6 +111,8 @@ def main():
         episode_seed = exp["seed"] + i * 12345                       # consistent episodes, as in the reference
         params["seed"] = episode_seed
         env.reset(seed=episode_seed)
+        if tracks:
+            env.engine.set_track_step(0)                             # an episode starts at env time 0
         policy = MPCPolicy(controller_type=controller_type, param_dict=params, batch_size=1)
         ctrl = policy.controller
         ctrl.set_sim_state_fn = sim.set_env_state
@@ -117,8 +124,10 @@ def main():
         if args.graph and device_path and controller_type != "pfmpc":
             ctrl.enable_graph()
         rewards, infos, actions, observations = [], [], [], []
-        for _ in range(exp["max_ep_length"]):
+        for k in range(exp["max_ep_length"]):
             state = deepcopy(env.get_env_state())
+            if tracks:
+                sim.set_track_step(k)
             t0 = time.perf_counter()
             action, _ = policy.get_action(state, calc_val=False)
             t_ctrl += time.perf_counter() - t0

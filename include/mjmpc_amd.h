@@ -37,7 +37,7 @@ extern "C" {
  *      fewer motors than dofs). */
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
- *      the DMD-MPC episode batches' and mjmpc_cost_terms.) */
+ *      the DMD-MPC episode batches', mjmpc_cost_terms and mjmpc_cost_terms_track / _track_batch.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -828,6 +828,34 @@ int mjmpc_cost_terms(int dtype, int64_t P, int H, int d_obs, int A, const void* 
 int mjmpc_cost_terms_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
                            const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal, void* d_costs,
                            const double* d_gseq, double* d_q0, void* stream);
+
+/* Cost terms that track a reference trajectory: mjmpc_cost_terms with a goal that moves with env time.  A row
+ * whose `reserved` column holds 1 + c (c >= 0) takes its goal from column c of d_ref, float64 [n_ref][n_cols] on the device
+ * (reference row n = the goal for env time n), instead of its `target` column; rows with reserved = 0 are as ever.  d_step is
+ * an int64 counter ON THE DEVICE, read by the kernel - a captured graph or a launch tape freezes the pointer, not the value.
+ * With the base time b = *d_step + step_bias, element (p, t) compares an observation row with reference row b + t + 1 and an
+ * action row with reference row b + t; a row index outside [0, n_ref - 1] is clamped to it (periodic = 0: the last goal is
+ * held) or taken mod n_ref, non-negative (periodic != 0).  Everything else - kinds, groups, when, keep_builtin, non-finite
+ * incoming costs, the order and the rounding - is mjmpc_cost_terms': r = v - goal is one subtraction, so a reference that is
+ * constant in time costs bit for bit what the same table with that target does.  advance != 0: the launch leaves *d_step + 1
+ * in the counter, behind its reads; only for P = H = 1 (the controlled env's step: one workgroup).  Refused before anything
+ * is launched: what mjmpc_cost_terms refuses, null d_ref / d_step, n_ref outside 1 .. 2^20, n_cols outside 1 .. 128,
+ * advance with P * H != 1.  A tracked row's column c < n_cols is the caller's to check (envs/cost_terms.py does). */
+int mjmpc_cost_terms_track(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                           const double* d_terms, int n_terms, int keep_builtin, int terminal, const double* d_ref,
+                           int64_t n_ref, int n_cols, int periodic, int64_t* d_step, int64_t step_bias, int advance,
+                           void* d_costs, void* stream);
+
+/* mjmpc_cost_terms_batch with tracked rows.  ref_per_episode = 0: d_ref is float64 [n_ref][n_cols]; ref_per_episode = 1:
+ * [E][n_ref][n_cols], a particle reads its own episode's.  The counter is only read (the episode batches' update launches
+ * advance theirs).  Costs and cost-to-go are bit for bit those of mjmpc_cost_terms_track per episode and of
+ * mjmpc_cost_terms_batch's cost-to-go.  Refused: what mjmpc_cost_terms_batch refuses, null d_ref / d_step, n_ref outside
+ * 1 .. 2^20, n_cols outside 1 .. 128. */
+int mjmpc_cost_terms_track_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                 const void* d_actions, const double* d_terms, int n_terms, int per_episode, int keep_builtin,
+                                 int terminal, const double* d_ref, int64_t n_ref, int n_cols, int ref_per_episode, int periodic,
+                                 const int64_t* d_step, int64_t step_bias, void* d_costs, const double* d_gseq, double* d_q0,
+                                 void* stream);
 
 #ifdef __cplusplus
 }

@@ -155,6 +155,10 @@ SIGNATURES = {
     "mjmpc_cost_terms": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "mjmpc_cost_terms_batch": (_int, [_int, _int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp,
                                       _vp, _vp]),
+    "mjmpc_cost_terms_track": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _i64, _int, _int, _vp,
+                                      _i64, _int, _vp, _vp]),
+    "mjmpc_cost_terms_track_batch": (_int, [_int, _int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _i64,
+                                            _int, _int, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

@@ -87,6 +87,8 @@ class _EpisodeBatch:
 
     _status = None      # int32 [E] on the device in the batches whose kernels can flag an episode's covariance
     _engine_kind = "tree"   # ``engine=``: "tree" (TreeRolloutEngine) or "arm" (ArmRolloutEngine)
+    _track = None           # tracked terms: (references on the device [1 or E][N][R], N, R, per episode?, periodic)
+    _track_bias = 0         # env time of the references = _step_dev + _track_bias (set_track_step)
     _terms = None           # set_cost_terms: (tables on the device, rows, per episode?, keep_builtin, a row reads an action?)
     _terms_nobs = None      # ... the rollouts' next observations [E P][H][d_obs] (only while terms are set)
     _terms_env = None       # ... the real-env step's own next observations [E][d_obs] and actions [E][A] in the batch's dtype
@@ -273,6 +275,7 @@ class _EpisodeBatch:
         self._means.copy_(self.torch.from_numpy(self.init_mean))
         self._step_dev.zero_()
         self.num_steps = 0
+        self._track_bias = 0
 
     # ------------------------------------------------------------------ dynamics randomization
     def randomize_dynamics(self, param_dict, base_seed, num_shards):
@@ -350,6 +353,29 @@ class _EpisodeBatch:
                                  "when (only weights and targets may differ between the episodes)" % e)
         return np.stack(tables), bool(keep), bool(np.any(first[:, 1] != 0))
 
+    @staticmethod
+    def _resolve_tracking(terms, engine, E):
+        """The references of ``set_cost_terms``'s argument (already through ``_resolve_cost_terms``: the rows agree, the
+        ``reserved`` column - which rows are tracked - included) -> ``(float64 [1 or E][N][R], periodic)``, or ``None`` without a
+        tracked term.  The values may differ between the episodes; ``N`` and ``periodic`` are structure: ``ValueError``."""
+        each = list(terms) if isinstance(terms, (list, tuple)) else [terms]
+        refs = [t.reference_table(engine) for t in each]
+        if refs[0] is None:
+            return None
+        for e, (t, r) in enumerate(zip(each, refs)):
+            if r.shape[0] != refs[0].shape[0]:
+                raise ValueError("set_cost_terms: episode %d's reference has %d rows, episode 0's %d (the episodes share N; "
+                                 "the values may differ)" % (e, r.shape[0], refs[0].shape[0]))
+            if t.periodic != each[0].periodic:
+                raise ValueError("set_cost_terms: episode %d's periodic differs from episode 0's" % e)
+        return np.ascontiguousarray(np.stack(refs), np.float64), bool(each[0].periodic)
+
+    def set_track_step(self, n):
+        """The env time of the tracked terms' references at the next control step becomes ``n``: reference row
+        ``n + t + 1`` is the goal of the next plan's step ``t``.  Host side (``_track_bias = n - num_steps``: the device step
+        counter goes on keying the noise); ``reset()`` puts the env time back to the step count, 0."""
+        self._track_bias = int(n) - self.num_steps
+
     def set_cost_terms(self, terms):
         """From the next step on the rollouts and the real-env steps of every episode cost what ``terms`` say instead of
         the built-in cost (``envs/cost_terms.py``; ``keep_builtin``: on top of it).  ``terms``: a ``CostTerms`` for every
@@ -357,11 +383,17 @@ class _EpisodeBatch:
         per episode or a sweep of the weights - or ``None``, which restores the built-in cost exactly.  The rollout launch
         then also writes the next observations (``mjmpc_<engine>_rollout_fused_batch_obs``) and one launch behind it
         (``mjmpc_cost_terms_batch``) rewrites the costs and forms the cost-to-go; the real-env step is followed by the same
-        launch without the terminal rows.  Everything is checked on the host first (``ValueError``); callable between steps."""
+        launch without the terminal rows.  Terms with a ``reference=`` (per episode the values may differ, ``N``,
+        ``periodic`` and the tracked rows not) read their goals at env time ``num_steps`` (``set_track_step``: another) + the
+        plan step through ``mjmpc_cost_terms_track_batch``.  Everything is checked on the host first (``ValueError``);
+        callable between steps."""
         if terms is None:
-            self._terms = self._terms_nobs = self._terms_env = None
+            self._terms = self._terms_nobs = self._terms_env = self._track = None
             return
         tables, keep, reads_actions = self._resolve_cost_terms(terms, self.engine, self.num_episodes)
+        track = self._resolve_tracking(terms, self.engine, self.num_episodes)
+        self._track = None if track is None else (self._upload(track[0]), track[0].shape[1], track[0].shape[2],
+                                                  int(track[0].shape[0] > 1), int(track[1]))
         torch, E, tdt, dev = self.torch, self.num_episodes, self._tdtype, self.device
         self._terms = (self._upload(tables), tables.shape[1], int(tables.shape[0] > 1), int(keep), reads_actions)
         self._terms_nobs = torch.empty((E * self.num_particles, self.horizon, self.d_obs), dtype=tdt, device=dev)
@@ -369,9 +401,17 @@ class _EpisodeBatch:
         self._terms_env = (torch.empty((E, self.d_obs), dtype=tdt, device=dev),
                            torch.empty((E, self.d_action), dtype=tdt, device=dev) if reads_actions else None)
 
-    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s):
-        """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s)."""
+    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s, bias=0):
+        """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s); with tracked terms
+        ``mjmpc_cost_terms_track_batch`` at env time ``_step_dev + bias``."""
         tables, K, per_episode, keep, reads_actions = self._terms
+        if self._track is not None:
+            refs, N, R, ref_per_episode, periodic = self._track
+            _lib.check(self.lib.mjmpc_cost_terms_track_batch(
+                self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs), _vp(act) if reads_actions else None,
+                _vp(tables), K, per_episode, keep, terminal, _vp(refs), N, R, ref_per_episode, periodic, _vp(self._step_dev),
+                bias, _vp(costs), _vp(gseq), _vp(q0), s))
+            return
         _lib.check(self.lib.mjmpc_cost_terms_batch(self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs),
                                                    _vp(act) if reads_actions else None, _vp(tables), K, per_episode, keep,
                                                    terminal, _vp(costs), _vp(gseq), _vp(q0), s))
@@ -404,7 +444,7 @@ class _EpisodeBatch:
                 _vp(self._coeffs) if filtered else None, None, _vp(self._costs), _vp(self._actions), None,
                 _vp(self._terms_nobs), s))
             self._launch_cost_terms(P, H, self._terms_nobs, self._actions, self._costs, 1, self._gseq if q0 else None,
-                                    self._q0 if q0 else None, s)
+                                    self._q0 if q0 else None, s, bias=self._track_bias)
             return
         _lib.check(self._fn("rollout_fused_batch")(
             self.engine._h, self._code, E * P, H, _vp(self._means), _vp(self._noise if noise is None else noise),
@@ -428,7 +468,8 @@ class _EpisodeBatch:
         _lib.check(self._fn("step_shard_states")(self.engine._h, self._code, _vp(act), _vp(cost), _vp(nobs), s))
         if act_t is not None:
             act_t.copy_(act)                # (into the batch's dtype, as step_state does)
-        self._launch_cost_terms(1, 1, nobs, act_t, cost, 0, None, None, s)
+        # (every class's update launch has advanced _step_dev by now: the step that was planned at _step_dev - 1)
+        self._launch_cost_terms(1, 1, nobs, act_t, cost, 0, None, None, s, bias=self._track_bias - 1)
 
     def run(self, T):
         """``T`` control steps of every episode -> actions ``[T][E][A]`` (float64), real-env costs ``[T][E]`` and next
@@ -525,11 +566,50 @@ class BatchedMPPI(_EpisodeBatch):
         """Enqueue one control step of every episode (sampling, rollouts, update, action, shift, real-env step) without a
         host synchronisation.  The actions, real-env costs and next observations stay on the device."""
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        if self._track is not None:
+            return self._launches_tracked(act, s)
         self._draw(s)
         self._rollout(s)
         _lib.check(self.lib.mjmpc_mppi_fused_update_batch(self._code, E, P, H, A, _vp(self._q0), _vp(self._actions),
                                                           _vp(self._lam), _vp(self._step), _SHIFT_MODES[self.base_action],
                                                           _vp(self._means), _vp(act), _vp(self._step_dev), _vp(self._ws), s))
+
+
+    _generic = None         # tracked terms: (workspace, covariances nobody reads, zero growth) of the general update
+
+    def set_cost_terms(self, terms):
+        """``_EpisodeBatch.set_cost_terms``.  With tracked terms the step takes the general softmax update - what the
+        single-episode MPPI runs once its costs come from a launch behind the rollout - in place of the fused one: an episode
+        of the batch stays, bit for bit, the sequential loop on an engine with the same tracked terms."""
+        super().set_cost_terms(terms)           # (every refusal of the terms themselves, before anything else)
+        self._generic = None
+        if self._track is None:
+            return
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        nbytes = self.lib.mjmpc_dmd_batch_workspace_bytes(E, P, H, A)
+        if nbytes <= 0:
+            super().set_cost_terms(None)
+            raise ValueError("no general-update workspace for tracked terms with E = %d, P = %d, H = %d, A = %d (A <= 64)"
+                             % (E, P, H, A))
+        f64 = dict(dtype=self.torch.float64, device=self.device)
+        self._generic = (self._workspace(nbytes), self.torch.zeros((E, A, A), **f64), self.torch.zeros(E, **f64))
+
+    def _launches_tracked(self, act, s):
+        """The step with tracked terms: draw + filter, the plain rollout costed by the terms, then ``mjmpc_dmd_update_batch`` -
+        row e is ``mjmpc_softmax_stats`` + ``mjmpc_softmax_combine`` + ``mjmpc_step_tail``, the single-episode MPPI's general
+        iteration - with a covariance per episode that it adapts and nobody reads (the draw keeps the static factors) and
+        no growth."""
+        E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
+        ws, covs, beta = self._generic
+        # (the draw of _draw with the filter as a pass of its own, then the plain rollout: the single path's launches)
+        _lib.check(self.lib.mjmpc_sample_noise_cov_batch(self._code, E, _vp(self._noise), P, H, A, _vp(self._chols),
+                                                         _vp(self._coeffs_unless_identity()), _vp(self._seeds), 0,
+                                                         _vp(self._step_dev), 1, s))
+        self._rollout(s, filtered=False, gseq=False, q0=False)
+        _lib.check(self.lib.mjmpc_dmd_update_batch(self._code, E, P, H, A, _vp(self._costs), _vp(self._actions), _vp(self._gseq),
+                                                   _vp(self._lam), _vp(self._step), 1, _vp(beta),
+                                                   _SHIFT_MODES[self.base_action], _vp(self._means), _vp(covs), _vp(act),
+                                                   _vp(self._step_dev), _vp(ws), s))
 
 
 def _cem_limits():

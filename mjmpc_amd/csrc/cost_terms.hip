@@ -219,6 +219,176 @@ __global__ __launch_bounds__(CT_WG) void cost_terms_batch_kernel(const T* __rest
     if (q0 && j < my_p) q0[p0 + j] = fabs(q) < (double)INFINITY ? q : (double)INFINITY;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Terms that track a reference trajectory.  A tracked row's `reserved` column holds 1 + c, c its column of the
+// reference `ref` (float64 [n_ref][n_cols]; row n = the goal for env time n).  A launch's base time is b = *step + bias, a
+// counter on the device: a captured graph or a launch tape freezes the pointer, not the value.  Element (p, t) compares its
+// observation rows with reference row b + t + 1 and its action rows with row b + t, clamped to [0, n_ref - 1] or taken
+// mod n_ref.  b is reduced once per workgroup (it is uniform) into a 32-bit base; a lane adds its t in 32 bits: n_ref <= 2^20.
+constexpr int CT_MAX_REF_ROWS = 1 << 20;
+
+struct CtClock {
+    int base, n, periodic;      // periodic: base = b mod n in [0, n); else b clamped to [-2^31, n - 1]
+};
+
+__device__ __forceinline__ CtClock ct_clock(long b, int n, int periodic) {
+    if (periodic) {
+        long m = b % n;
+        if (m < 0) m += n;
+        return CtClock{(int)m, n, 1};
+    }
+    const long lo = -(1L << 31);        // lo + t < 0 for every t < 2^31: all of such a launch holds the first goal
+    return CtClock{(int)(b < lo ? lo : b > n - 1 ? (long)(n - 1) : b), n, 0};
+}
+
+// the reference rows of step t >= 0: the observation's (time b + t + 1) and the action's (time b + t)
+__device__ __forceinline__ void ct_ref_rows(const CtClock c, int t, int& n_obs, int& n_act) {
+    if (c.periodic) {
+        const unsigned a = ((unsigned)c.base + (unsigned)t) % (unsigned)c.n;        // base < 2^20, t < 2^31
+        n_act = (int)a;
+        n_obs = (int)a + 1 == c.n ? 0 : (int)a + 1;
+    } else {
+        const unsigned top = (unsigned)(c.n - 1);
+        unsigned up = (unsigned)c.base + (unsigned)t;               // (used only where base >= 0: below 2^32)
+        up = up < top ? up : top;
+        const int s = c.base < 0 ? c.base + t : (int)up;            // min(b + t, n - 1) or, from a negative base, b + t < 2^31 - 1
+        n_act = s < 0 ? 0 : s > c.n - 1 ? c.n - 1 : s;
+        n_obs = s + 1 < 0 ? 0 : s + 1 > c.n - 1 ? c.n - 1 : s + 1;
+    }
+}
+
+// a table's reference columns into LDS: -1 for a row with a constant target.  A column beyond the reference (the host
+// builder never writes one) is held inside it: the walk must not read past `ref` whatever the table says.
+__device__ __forceinline__ void ct_decode_ref_cols(const double* __restrict__ terms, int n_terms, int n_cols, int* s_rcol) {
+    for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
+        const int c = (int)terms[8 * k + 7] - 1;
+        s_rcol[k] = c < 0 ? -1 : c < n_cols ? c : n_cols - 1;
+    }
+}
+
+// where a walk over a table with tracked rows takes row k's goal from: the element's two reference rows, read through the
+// cache (a launch's window is (H + 1) n_cols doubles, the same few KB for every workgroup), or the constant target
+struct CtTracked {
+    const double *w, *target;
+    const int *rcol, *flags;
+    const double *ref_o, *ref_a;
+    __device__ __forceinline__ double weight(int k) const { return w[k]; }
+    __device__ __forceinline__ double goal(int k) const {
+        const int c = rcol[k];
+        return c < 0 ? target[k] : ((flags[k] & CT_ACTION) ? ref_a : ref_o)[c];
+    }
+};
+
+// cost_terms_kernel with tracked rows.  advance (host: only for P = H = 1, one workgroup): every lane takes its copy of the
+// counter before the barrier, the one walking lane stores counter + 1 behind its walk.
+template <typename T>
+__global__ __launch_bounds__(CT_WG) void cost_terms_track_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
+                                                                 const double* __restrict__ terms, int n_terms, long n, int H,
+                                                                 int d_obs, int A, int rows, int keep_builtin, int terminal,
+                                                                 const double* __restrict__ ref, int n_ref, int n_cols,
+                                                                 int periodic, int64_t* step, int64_t bias, int advance,
+                                                                 T* __restrict__ costs) {
+    extern __shared__ double ct_tile_raw[];
+    __shared__ double s_w[CT_MAX_TERMS], s_target[CT_MAX_TERMS];
+    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS], s_rcol[CT_MAX_TERMS];
+    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
+    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
+    T* const tile_a = tile_o + (long)rows * po;
+    const long e0 = (long)blockIdx.x * rows;
+    const int mine = n - e0 < rows ? (int)(n - e0) : rows;
+    const int64_t now = *step;
+    const CtClock clock = ct_clock((long)(now + bias), n_ref, periodic);
+
+    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
+    ct_decode_values(terms, n_terms, s_w, s_target);
+    ct_decode_ref_cols(terms, n_terms, n_cols, s_rcol);
+    ct_stage(nobs + e0 * d_obs, mine, d_obs, po, tile_o);
+    if (act) ct_stage(act + e0 * A, mine, A, pa, tile_a);
+    __syncthreads();
+
+    const int j = threadIdx.x;
+    if (j >= mine) return;
+    const long e = e0 + j;
+    const int t = (int)(e % H);
+    int n_obs, n_act;
+    ct_ref_rows(clock, t, n_obs, n_act);
+    const T incoming = costs[e];
+    const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa, terminal && t == H - 1,
+                               keep_builtin ? (double)incoming : 0.0,
+                               CtTracked{s_w, s_target, s_rcol, s_flags, ref + (long)n_obs * n_cols, ref + (long)n_act * n_cols});
+    costs[e] = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
+    if (advance) *step = now + 1;       // (n = 1: this lane is the launch's only one behind the barrier)
+}
+
+// cost_terms_batch_kernel with tracked rows: one reference for the batch or one per episode ([E][n_ref][n_cols], the
+// particle's own episode's).  The counter is only read: the batch classes' update launches advance it.
+template <typename T>
+__global__ __launch_bounds__(CT_WG) void cost_terms_track_batch_kernel(
+    const T* __restrict__ nobs, const T* __restrict__ act, const double* __restrict__ terms, int n_terms, long np, long P, int H,
+    int d_obs, int A, int rows, int ppw, int per_episode, int keep_builtin, int terminal, const double* __restrict__ ref,
+    int n_ref, int n_cols, int ref_per_episode, int periodic, const int64_t* __restrict__ step, int64_t bias,
+    T* __restrict__ costs, const double* __restrict__ gseq, double* __restrict__ q0) {
+    extern __shared__ double ct_tile_raw[];
+    __shared__ double s_w[2][CT_MAX_TERMS], s_target[2][CT_MAX_TERMS], s_gc[CT_ROWS];
+    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS], s_rcol[CT_MAX_TERMS];
+    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
+    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
+    T* const tile_a = tile_o + (long)rows * po;
+    const long p0 = (long)blockIdx.x * ppw;
+    const int my_p = np - p0 < ppw ? (int)(np - p0) : ppw;
+    const long e0 = p0 * H;
+    const int my_n = my_p * H;
+    const CtClock clock = ct_clock((long)(*step + bias), n_ref, periodic);
+    // my particles from `second` on belong to the episode after my first particle's (the host keeps ppw <= P whenever
+    // the tables or the references are per episode)
+    int second = my_p;
+    const long ep0 = p0 / P;
+    if ((per_episode || ref_per_episode) && (ep0 + 1) * P - p0 < my_p) second = (int)((ep0 + 1) * P - p0);
+    if (per_episode) {
+        ct_decode_values(terms + ep0 * 8L * n_terms, n_terms, s_w[0], s_target[0]);
+        if (second < my_p) ct_decode_values(terms + (ep0 + 1) * 8L * n_terms, n_terms, s_w[1], s_target[1]);
+    } else {
+        ct_decode_values(terms, n_terms, s_w[0], s_target[0]);
+    }
+    const long ref_len = (long)n_ref * n_cols;
+    const double* const ref0 = ref + (ref_per_episode ? ep0 * ref_len : 0);
+    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
+    ct_decode_ref_cols(terms, n_terms, n_cols, s_rcol);
+    double q = 0.0;
+    const int j = threadIdx.x;
+    for (int c0 = 0; c0 < my_n; c0 += rows) {
+        const int mine = my_n - c0 < rows ? my_n - c0 : rows;
+        ct_stage(nobs + (e0 + c0) * d_obs, mine, d_obs, po, tile_o);
+        if (act) ct_stage(act + (e0 + c0) * A, mine, A, pa, tile_a);
+        __syncthreads();
+        if (j < mine) {
+            const int le = c0 + j, pl = le / H, t = le - pl * H;
+            const double g = gseq ? gseq[t] : 0.0;
+            const T incoming = costs[e0 + le];
+            const int slot = pl >= second;
+            const double* const my_ref = ref0 + (ref_per_episode && slot ? ref_len : 0);
+            int n_obs, n_act;
+            ct_ref_rows(clock, t, n_obs, n_act);
+            const int ws = per_episode ? slot : 0;
+            const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa,
+                                       terminal && t == H - 1, keep_builtin ? (double)incoming : 0.0,
+                                       CtTracked{s_w[ws], s_target[ws], s_rcol, s_flags, my_ref + (long)n_obs * n_cols,
+                                                 my_ref + (long)n_act * n_cols});
+            const T out = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
+            costs[e0 + le] = out;
+            s_gc[j] = g * (double)out;
+        }
+        __syncthreads();
+        if (q0 && j < my_p) {
+            const int lo = j * H > c0 ? j * H : c0;
+            const int hi = (j + 1) * H < c0 + mine ? (j + 1) * H : c0 + mine;
+#pragma unroll 4
+            for (int i = lo; i < hi; ++i) q += s_gc[i - c0];
+        }
+    }
+    if (q0 && j < my_p) q0[p0 + j] = fabs(q) < (double)INFINITY ? q : (double)INFINITY;
+}
+
 int bad(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms", detail); }
 
 template <typename T>
@@ -262,8 +432,101 @@ int launch_batch(int E, int64_t P, int H, int d_obs, int A, const void* d_next_o
     return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_batch", hipGetErrorString(e));
 }
 
+int bad_track(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_track", detail); }
+
+template <typename T>
+int launch_track(int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions, const double* d_terms,
+                 int n_terms, int keep_builtin, int terminal, const double* d_ref, int n_ref, int n_cols, int periodic,
+                 int64_t* d_step, int64_t step_bias, int advance, void* d_costs, void* stream) {
+    const long n = (long)P * H;
+    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
+    if (row_bytes > CT_LDS_BYTES) return bad_track("an observation and action row of more than 60 KiB");
+    int rows = CT_ROWS;
+    while (rows * row_bytes > CT_LDS_BYTES) rows >>= 1;
+    const long blocks = (n + rows - 1) / rows;
+    if (blocks > INT32_MAX) return bad_track("more than 2^31 workgroups");
+    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
+    hipLaunchKernelGGL(cost_terms_track_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
+                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, n, H, d_obs, A, rows, keep_builtin,
+                       terminal, d_ref, n_ref, n_cols, periodic, d_step, step_bias, advance, (T*)d_costs);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_track", hipGetErrorString(e));
+}
+
+int bad_track_batch(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_track_batch", detail); }
+
+template <typename T>
+int launch_track_batch(int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                       const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal,
+                       const double* d_ref, int n_ref, int n_cols, int ref_per_episode, int periodic, const int64_t* d_step,
+                       int64_t step_bias, void* d_costs, const double* d_gseq, double* d_q0, void* stream) {
+    const long np = (long)E * P;
+    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
+    if (row_bytes > CT_BATCH_LDS_BYTES) return bad_track_batch("an observation and action row of more than 56 KiB");
+    int rows = CT_ROWS;
+    while (rows * row_bytes > CT_BATCH_LDS_BYTES) rows >>= 1;
+    int ppw = H >= rows ? 1 : rows / H;                                     // whole particles per workgroup ...
+    if ((per_episode || ref_per_episode) && ppw > P) ppw = (int)P;          // ... of at most two episodes
+    const long blocks = (np + ppw - 1) / ppw;
+    if (blocks > INT32_MAX) return bad_track_batch("more than 2^31 workgroups");
+    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
+    hipLaunchKernelGGL(cost_terms_track_batch_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
+                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, np, (long)P, H, d_obs, A, rows, ppw,
+                       per_episode, keep_builtin, terminal, d_ref, n_ref, n_cols, ref_per_episode, periodic, d_step, step_bias,
+                       (T*)d_costs, d_gseq, d_q0);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_track_batch", hipGetErrorString(e));
+}
+
 }  // namespace
 }  // namespace mjmpc
+
+extern "C" int mjmpc_cost_terms_track(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                      const void* d_actions, const double* d_terms, int n_terms, int keep_builtin, int terminal,
+                                      const double* d_ref, int64_t n_ref, int n_cols, int periodic, int64_t* d_step,
+                                      int64_t step_bias, int advance, void* d_costs, void* stream) {
+    using mjmpc::bad_track;
+    if (!d_next_obs || !d_terms || !d_costs || !d_ref || !d_step) return bad_track("null argument");
+    if (P < 1 || H < 1 || d_obs < 1 || A < 0) return bad_track("needs P >= 1, H >= 1, d_obs >= 1 and A >= 0");
+    if (P > ((int64_t)1 << 40)) return bad_track("more than 2^40 particles");
+    if (d_actions && A < 1) return bad_track("actions of width 0");
+    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_track("n_terms must be 1 .. 128");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_track("dtype must be MJMPC_F32 or MJMPC_F64");
+    if (n_ref < 1 || n_ref > mjmpc::CT_MAX_REF_ROWS) return bad_track("n_ref must be 1 .. 2^20");
+    if (n_cols < 1 || n_cols > mjmpc::CT_MAX_TERMS) return bad_track("n_cols must be 1 .. 128");
+    if (advance && (P != 1 || H != 1)) return bad_track("advance needs P = H = 1 (one workgroup owns the counter)");
+    if (dtype == MJMPC_F32)
+        return mjmpc::launch_track<float>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal,
+                                          d_ref, (int)n_ref, n_cols, periodic != 0, d_step, step_bias, advance != 0, d_costs,
+                                          stream);
+    return mjmpc::launch_track<double>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_ref,
+                                       (int)n_ref, n_cols, periodic != 0, d_step, step_bias, advance != 0, d_costs, stream);
+}
+
+extern "C" int mjmpc_cost_terms_track_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                            const void* d_actions, const double* d_terms, int n_terms, int per_episode,
+                                            int keep_builtin, int terminal, const double* d_ref, int64_t n_ref, int n_cols,
+                                            int ref_per_episode, int periodic, const int64_t* d_step, int64_t step_bias,
+                                            void* d_costs, const double* d_gseq, double* d_q0, void* stream) {
+    using mjmpc::bad_track_batch;
+    if (!d_next_obs || !d_terms || !d_costs || !d_ref || !d_step) return bad_track_batch("null argument");
+    if (E < 1 || P < 1 || H < 1 || d_obs < 1 || A < 0)
+        return bad_track_batch("needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 0");
+    if (P > ((int64_t)1 << 40) / E) return bad_track_batch("more than 2^40 particles");
+    if (d_actions && A < 1) return bad_track_batch("actions of width 0");
+    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_track_batch("n_terms must be 1 .. 128");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_track_batch("dtype must be MJMPC_F32 or MJMPC_F64");
+    if ((d_gseq != nullptr) != (d_q0 != nullptr)) return bad_track_batch("d_gseq and d_q0 go together");
+    if (n_ref < 1 || n_ref > mjmpc::CT_MAX_REF_ROWS) return bad_track_batch("n_ref must be 1 .. 2^20");
+    if (n_cols < 1 || n_cols > mjmpc::CT_MAX_TERMS) return bad_track_batch("n_cols must be 1 .. 128");
+    if (dtype == MJMPC_F32)
+        return mjmpc::launch_track_batch<float>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
+                                                keep_builtin, terminal, d_ref, (int)n_ref, n_cols, ref_per_episode != 0,
+                                                periodic != 0, d_step, step_bias, d_costs, d_gseq, d_q0, stream);
+    return mjmpc::launch_track_batch<double>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
+                                             keep_builtin, terminal, d_ref, (int)n_ref, n_cols, ref_per_episode != 0,
+                                             periodic != 0, d_step, step_bias, d_costs, d_gseq, d_q0, stream);
+}
 
 extern "C" int mjmpc_cost_terms_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
                                       const void* d_actions, const double* d_terms, int n_terms, int per_episode,

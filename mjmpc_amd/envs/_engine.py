@@ -70,6 +70,9 @@ class RolloutEngine(EnvResetWatch):
     _cost_terms = None              # set_cost_terms: the builder, its table on the device, whether a row reads an action
     _terms_dev = None
     _terms_read_actions = False
+    _track_ref = None               # tracked terms: the reference [N][R] and the env-time counter, on the device
+    _track_step = None
+    _track_periodic = 0
     _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
 
     def __init__(self, model, device=0, dtype="f64", num_shards=1):
@@ -260,6 +263,9 @@ class RolloutEngine(EnvResetWatch):
         nobs = self._buffer("nobs", (P, H, self.d_obs)) if want_obs else None
         # cost terms read the next observations (and the actions): the launch writes them whether or not the caller asked
         t_nobs, t_act = nobs, act
+        if self._track_step is not None and self._in_real_step and (P, H) != (1, 1):
+            raise ValueError("a rollout under real_step_guard advances the tracked cost terms' env time by one step: it must "
+                             "be one particle and one step, got (%d, %d)" % (P, H))
         if self._terms_dev is not None:
             t_nobs = nobs if nobs is not None else self._buffer("terms_nobs", (P, H, self.d_obs))
             if self._terms_read_actions and act is None:
@@ -269,7 +275,7 @@ class RolloutEngine(EnvResetWatch):
                       _ptr(t_nobs), self._stream()))
         if self._terms_dev is not None:
             # (a one-particle rollout under real_step_guard is the controlled env's step: never a plan's last step)
-            self._launch_cost_terms(P, H, t_nobs, t_act, costs, terminal=not self._in_real_step)
+            self._launch_cost_terms(P, H, t_nobs, t_act, costs, terminal=not self._in_real_step, advance=self._in_real_step)
         return costs, act, obs, nobs
 
     def rollout_fused(self, num_particles, horizon, mean, raw_noise, filter_coeffs, gamma_seq, q0_out=None):
@@ -304,7 +310,7 @@ class RolloutEngine(EnvResetWatch):
             if self._terms_read_actions:
                 act = self._buffer("step_act", (self.d_action,))
                 act.copy_(a)                # (into the engine's storage type; a launch, no allocation: capturable)
-            self._launch_cost_terms(1, 1, nobs, act, cost, terminal=False)
+            self._launch_cost_terms(1, 1, nobs, act, cost, terminal=False, advance=True)
         return cost, nobs
 
     # ------------------------------------------------------------------ user-defined cost terms (envs/cost_terms.py)
@@ -328,27 +334,63 @@ class RolloutEngine(EnvResetWatch):
         while terms are set; ``make_device_rollout_fn`` then offers the controllers only the generic iteration - set the
         terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  The episode batches have their own
         ``set_cost_terms`` (``control/batched.py``, DESIGN 10.8: one table for the batch or one per episode).  Not covered:
-        ``AnalyticRolloutEngine``, world sizes above 1."""
+        ``AnalyticRolloutEngine``, world sizes above 1.
+
+        Terms with a ``reference=`` are costed by ``mjmpc_cost_terms_track``: their reference goes to the device
+        with an env-time counter (``track_step()``, 0 now) that every plan reads and every step of the controlled env
+        (``step_state``, a ``(1, 1)`` rollout under ``real_step_guard``) advances by one inside its launch; a guarded rollout
+        of another shape raises ``ValueError``.  ``set_track_step(n)`` tells an engine that only plans what time it is."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
                                "controllers %s; set the terms first, then call make_device_rollout_fn"
                                % (("with", "no fused launches") if self._closure_terms else ("without", "the fused launches")))
         if terms is None:
-            self._cost_terms = self._terms_dev = None
+            self._cost_terms = self._terms_dev = self._track_ref = self._track_step = None
             self._terms_read_actions = False
             return
         table = np.ascontiguousarray(terms.table(self), np.float64)       # (ValueError before anything reaches the device)
+        ref = terms.reference_table(self)
         torch = _torch()
         self._terms_dev = torch.from_numpy(table).to(self.device)
         self._terms_read_actions = bool(np.any(table[:, 1] != 0))
         self._cost_terms = terms
+        self._track_ref = self._track_step = None
+        if ref is not None:
+            # tracked terms (DESIGN 12.1): the reference and the env-time counter live on the device; time 0 is now
+            self._track_ref = torch.from_numpy(ref).to(self.device)
+            self._track_periodic = int(terms.periodic)
+            self._track_step = torch.zeros(1, dtype=torch.int64, device=self.device)
 
-    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal):
+    def set_track_step(self, n):
+        """The env time of the tracked terms' reference becomes ``n``: a fill of the device counter in stream
+        order, no synchronisation.  For loops whose controlled env is another object, whose steps this engine cannot see:
+        call it before each plan.  ``step_state`` and a rollout under ``real_step_guard`` advance the counter by one
+        themselves; ``set_cost_terms`` resets it to 0; ``set_env_state`` leaves it alone - a state does not say what
+        time it is.  A host edit like ``set_env_state``: with a controller's ``lookahead``, ``reset()`` it first."""
+        if self._track_step is None:
+            raise RuntimeError("set_track_step: no tracked cost terms are set (CostTerms with reference=)")
+        self._track_step.fill_(int(n))
+
+    def track_step(self):
+        """The env time of the tracked terms' reference, read back from the device (synchronises the stream)."""
+        if self._track_step is None:
+            raise RuntimeError("track_step: no tracked cost terms are set (CostTerms with reference=)")
+        return int(self._track_step.item())
+
+    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, advance=False):
         t = self._terms_dev
-        _lib.check(self._lib.mjmpc_cost_terms(self._code, P, H, self.d_obs, self.d_action, _ptr(nobs),
-                                              _ptr(act if self._terms_read_actions else None), _ptr(t), t.shape[0],
-                                              int(self._cost_terms.keep_builtin), int(bool(terminal)), _ptr(costs),
-                                              self._stream()))
+        act = _ptr(act if self._terms_read_actions else None)
+        keep = int(self._cost_terms.keep_builtin)
+        if self._track_step is None:
+            _lib.check(self._lib.mjmpc_cost_terms(self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t),
+                                                  t.shape[0], keep, int(bool(terminal)), _ptr(costs), self._stream()))
+            return
+        # (the advance is part of the library launch, not a torch op: a captured iteration keeps its launch tape)
+        r = self._track_ref
+        _lib.check(self._lib.mjmpc_cost_terms_track(self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t),
+                                                    t.shape[0], keep, int(bool(terminal)), _ptr(r), r.shape[0], r.shape[1],
+                                                    self._track_periodic, _ptr(self._track_step), 0, int(bool(advance)),
+                                                    _ptr(costs), self._stream()))
 
     def _refuse_with_terms(self, what):
         if self._cost_terms is not None:

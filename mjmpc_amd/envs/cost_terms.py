@@ -20,6 +20,15 @@ the next observation (``source`` 0) or of the action (``source`` 1); ``r = v - t
 ``obs=`` names a block of ``engine.obs_layout()`` (``index=`` counts inside it; left out: every entry) or gives absolute
 indices into the observation; ``action=`` gives action indices (``True`` or ``"all"``: the block, with ``index=``).
 Everything is checked here, on the host: the kernel assumes a valid table.
+
+A term may follow a reference trajectory instead of a constant target: ``reference=`` is ``[N]`` (one value for
+all its indices) or ``[N][n_idx]``, row ``n`` the goal for env time ``n``; beyond the last row the goal is held, or with
+``periodic=True`` the reference starts over.  Step ``t`` of a plan made at env time ``s`` compares its next observation with
+row ``s + t + 1`` and its action with row ``s + t``.  All tracked terms of a table share ``N`` and ``periodic``.  A tracked
+row's ``reserved`` column holds 1 + its column of ``reference_table()`` and its ``target`` column the first goal; the env time
+is a counter on the device (``engine.set_track_step`` / ``track_step``; the controlled env's steps advance it).
+
+    terms.square(obs="qpos", index=0, weight=0.5, reference=np.repeat([0.0, 0.4, 0.0, -0.4], 50), periodic=True)
 """
 import numpy as np
 
@@ -29,6 +38,7 @@ KIND_ABS, KIND_SQUARE, KIND_NORM, KIND_COS = 0, 1, 2, 3
 KINDS = {"abs": KIND_ABS, "square": KIND_SQUARE, "norm": KIND_NORM, "cos": KIND_COS}
 MAX_TERMS = 128
 ROW_LEN = 8
+MAX_REFERENCE_ROWS = 1 << 20    # (the kernel's per-lane index arithmetic is 32-bit)
 
 
 def _dims(engine):
@@ -49,21 +59,59 @@ class CostTerms:
     def __init__(self, engine=None, keep_builtin=False):
         self.engine = engine
         self.keep_builtin = bool(keep_builtin)
-        self._terms = []            # (kind, source block or None, indices or None, action?, weight, target, terminal)
+        # (kind, source block or None, indices or None, action?, weight, target, terminal, reference [N] / [N][n_idx] or None)
+        self._terms = []
+        self._periodic = None       # the tracked terms' shared `periodic` (None: no tracked term yet)
 
     # ------------------------------------------------------------------ the four kinds
-    def abs(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
-        return self._add(KIND_ABS, obs, action, index, weight, target, terminal)
+    def abs(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+            periodic=False):
+        return self._add(KIND_ABS, obs, action, index, weight, target, terminal, reference, periodic)
 
-    def square(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
-        return self._add(KIND_SQUARE, obs, action, index, weight, target, terminal)
+    def square(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+               periodic=False):
+        return self._add(KIND_SQUARE, obs, action, index, weight, target, terminal, reference, periodic)
 
-    def cos(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
-        return self._add(KIND_COS, obs, action, index, weight, target, terminal)
+    def cos(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+            periodic=False):
+        return self._add(KIND_COS, obs, action, index, weight, target, terminal, reference, periodic)
 
-    def norm(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False):
+    def norm(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+             periodic=False):
         """``weight * sqrt(sum_i (v_i - target_i)^2)`` over the indices: one group of the table."""
-        return self._add(KIND_NORM, obs, action, index, weight, target, terminal)
+        return self._add(KIND_NORM, obs, action, index, weight, target, terminal, reference, periodic)
+
+    # ------------------------------------------------------------------ tracked terms (DESIGN 12.1)
+    @property
+    def tracked(self):
+        """Whether a term takes a ``reference=``."""
+        return any(t[7] is not None for t in self._terms)
+
+    @property
+    def periodic(self):
+        """The tracked terms' ``periodic`` (False without one)."""
+        return bool(self._periodic)
+
+    def reference_table(self, engine=None):
+        """The float64 ``[N][R]`` reference of the table's ``R`` tracked rows, in row order - column ``c`` belongs to the
+        row whose ``reserved`` column holds ``1 + c`` -, or ``None`` without a tracked term."""
+        engine = engine if engine is not None else self.engine
+        cols = []
+        for t in self._terms:
+            if t[7] is not None:
+                n_idx = len(self._resolve(t, engine)[0])
+                cols.append(self._reference_columns(t[7], n_idx))
+        return np.ascontiguousarray(np.concatenate(cols, axis=1), np.float64) if cols else None
+
+    @staticmethod
+    def _reference_columns(reference, n_idx):
+        """A term's reference as ``[N][n_idx]``: ``[N]`` holds one value for all its indices."""
+        if reference.ndim == 1:
+            return np.repeat(reference[:, None], n_idx, axis=1)
+        if reference.shape[1] != n_idx:
+            raise ValueError("cost term: reference must be [N] or [N][%d] (one column per index), got %s"
+                             % (n_idx, list(reference.shape)))
+        return reference
 
     @classmethod
     def builtin_reach(cls, engine, keep_builtin=False):
@@ -87,13 +135,19 @@ class CostTerms:
     def table(self, engine=None):
         """The ``[K][8]`` float64 array for ``engine`` (default: the builder's own)."""
         engine = engine if engine is not None else self.engine
-        rows, group = [], 0
+        rows, group, col = [], 0, 0
         for t in self._terms:
-            (kind, _, _, _, weight, _, terminal), idx, source, targets = (t,) + self._resolve(t, engine)
+            (kind, _, _, _, weight, _, terminal, reference), idx, source, targets = (t,) + self._resolve(t, engine)
             if kind == KIND_NORM:
                 group += 1              # a fresh id per norm: neighbouring groups never merge
-            for i, tg in zip(idx, targets):
-                rows.append([kind, source, i, weight, tg, group if kind == KIND_NORM else 0, 1.0 if terminal else 0.0, 0.0])
+            reserved = [0.0] * len(idx)
+            if reference is not None:
+                # a tracked row: 1 + its column of reference_table(); the target column holds the first goal
+                targets = [float(x) for x in self._reference_columns(reference, len(idx))[0]]
+                reserved = [1.0 + col + c for c in range(len(idx))]
+                col += len(idx)
+            for i, tg, rs in zip(idx, targets, reserved):
+                rows.append([kind, source, i, weight, tg, group if kind == KIND_NORM else 0, 1.0 if terminal else 0.0, rs])
         if not rows:
             raise ValueError("cost terms: an empty table (set_cost_terms(None) restores the built-in cost)")
         if len(rows) > MAX_TERMS:
@@ -101,7 +155,7 @@ class CostTerms:
         return np.asarray(rows, np.float64).reshape(-1, ROW_LEN)
 
     # ------------------------------------------------------------------ internals
-    def _add(self, kind, obs, action, index, weight, target, terminal):
+    def _add(self, kind, obs, action, index, weight, target, terminal, reference=None, periodic=False):
         if (obs is None) == (action is None):
             raise ValueError("cost term: give exactly one of obs= and action=")
         is_action = action is not None
@@ -127,19 +181,40 @@ class CostTerms:
         target = _finite(target, "target")
         if target.ndim > 1 or (index is not None and target.ndim == 1 and target.size != len(index)):
             raise ValueError("cost term: target must be a number or one number per index")
-        term = (int(kind), block, index, is_action, weight, target, bool(terminal))
+        if reference is not None:
+            if target.ndim != 0 or float(target) != 0.0:
+                raise ValueError("cost term: give a constant target= or a reference=, not both")
+            reference = np.array(_finite(reference, "reference"), np.float64)       # (a copy: the caller's array stays theirs)
+            if reference.ndim not in (1, 2) or (reference.ndim == 2 and index is not None and reference.shape[1] != len(index)):
+                raise ValueError("cost term: reference must be [N] or [N][n_idx] (one column per index), got shape %s"
+                                 % (list(reference.shape),))
+            if not 1 <= reference.shape[0] <= MAX_REFERENCE_ROWS:
+                raise ValueError("cost term: a reference holds 1 .. 2^20 rows, got %d" % reference.shape[0])
+            for other in self._terms:
+                if other[7] is not None and other[7].shape[0] != reference.shape[0]:
+                    raise ValueError("cost terms: the tracked terms of a table share one N; this reference has %d rows, an "
+                                     "earlier one %d" % (reference.shape[0], other[7].shape[0]))
+            if self._periodic is not None and self._periodic != bool(periodic):
+                raise ValueError("cost terms: the tracked terms of a table share one periodic=")
+        elif periodic:
+            raise ValueError("cost term: periodic= goes with a reference=")
+        term = (int(kind), block, index, is_action, weight, target, bool(terminal), reference)
         if self.engine is not None:
-            self._resolve(term, self.engine)        # refuse now what the engine would refuse later
+            n_idx = len(self._resolve(term, self.engine)[0])    # refuse now what the engine would refuse later
+            if reference is not None:
+                self._reference_columns(reference, n_idx)
         self._terms.append(term)
         if self.engine is not None and len(self) > MAX_TERMS:
             self._terms.pop()
             raise ValueError("cost terms: the table holds at most %d rows" % MAX_TERMS)
+        if reference is not None:
+            self._periodic = bool(periodic)
         return self
 
     @staticmethod
     def _resolve(term, engine):
         """-> (absolute indices, source, one target per index) of a term, checked against the engine's dimensions."""
-        _, block, index, is_action, _, target, _ = term
+        _, block, index, is_action, _, target = term[:6]
         if engine is None:
             if block is not None or index is None:
                 raise ValueError("cost terms that name a block or take every entry need an engine: CostTerms(engine) or "
@@ -167,7 +242,41 @@ class CostTerms:
         return idx, 1.0 if is_action else 0.0, [float(x) for x in targets]
 
 
-_TERM_KEYS = {"kind", "obs", "action", "index", "weight", "target", "terminal"}
+_TERM_KEYS = {"kind", "obs", "action", "index", "weight", "target", "terminal", "reference", "repeat", "periodic"}
+
+
+def _depth(value):
+    """Nesting depth of a config list: 0 for a number."""
+    d = 0
+    while isinstance(value, (list, tuple)):
+        if not value:
+            raise ValueError("cost_terms: an empty list in a reference")
+        value, d = value[0], d + 1
+    return d
+
+
+def _per_episode_reference(value, E):
+    """A term's ``reference`` in a config -> its E references if it holds one per episode, else None.  A reference is a
+    list of N numbers or of N lists (one number per index); a list of lists of lists is one reference per episode, and so -
+    the list-valued ``weight`` / ``target`` rule - is a list of ``E`` lists of numbers in a batch of ``E`` episodes."""
+    d = _depth(value)
+    if d not in (1, 2, 3):
+        raise ValueError("cost_terms: a reference is a list of N numbers or of N lists (or one such list per episode)")
+    if d == 3 or (d == 2 and E is not None and len(value) == E):
+        if E is None or len(value) != E:
+            raise ValueError("cost_terms: a reference per episode holds one reference per episode%s, got %d"
+                             % ("" if E is None else " (%d)" % E, len(value)))
+        return list(value)
+    return None
+
+
+def _expanded(reference, repeat):
+    """``repeat: k``: every entry of the reference holds for k env steps."""
+    try:
+        ref = np.asarray(reference, np.float64)
+    except ValueError as e:
+        raise ValueError("cost_terms: a ragged reference: %s" % (e,)) from e
+    return np.repeat(ref, repeat, axis=0) if ref.ndim >= 1 else ref
 
 
 def _per_episode_value(value, E):
@@ -189,7 +298,11 @@ def cost_terms_from_config(block, engine, num_episodes=None):
     ``num_episodes`` (an episode batch's): a ``weight`` or ``target`` that is a list of ``num_episodes`` entries holds one
     value per episode (a target entry may itself be one number per index) and the result is a list of ``num_episodes``
     ``CostTerms``, one table per episode for ``_EpisodeBatch.set_cost_terms``; without such a list one ``CostTerms`` as ever.
-    A ``weight`` list of another length is refused; a ``target`` list of another length is one number per index."""
+    A ``weight`` list of another length is refused; a ``target`` list of another length is one number per index.
+
+    A term may give ``reference:`` - a list of N numbers or of N lists (one number per index) - in place of ``target``,
+    ``repeat: k`` (every entry holds for k env steps, expanded here) and ``periodic:``.  A ``reference`` that is a
+    list of references - three levels, or a list of ``num_episodes`` lists of numbers - holds one per episode."""
     if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms"}:
         raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin'")
     E = None if num_episodes is None else int(num_episodes)
@@ -204,6 +317,13 @@ def cost_terms_from_config(block, engine, num_episodes=None):
             raise ValueError("cost_terms: a list-valued weight holds one weight per episode%s, got %d"
                              % ("" if E is None else " (%d)" % E, len(entry["weight"])))
         per_episode = per_episode or any(_per_episode_value(entry.get(k), E) is not None for k in ("weight", "target"))
+        if "reference" in entry:
+            per_episode = per_episode or _per_episode_reference(entry["reference"], E) is not None
+            repeat = entry.get("repeat", 1)
+            if isinstance(repeat, bool) or not isinstance(repeat, int) or repeat < 1:
+                raise ValueError("cost_terms: repeat must be a whole number >= 1, got %r" % (repeat,))
+        elif "repeat" in entry or "periodic" in entry:
+            raise ValueError("cost_terms: repeat and periodic go with a reference, got %r" % (entry,))
     out = []
     for e in range(E if per_episode else 1):
         terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
@@ -213,6 +333,10 @@ def cost_terms_from_config(block, engine, num_episodes=None):
                 each = _per_episode_value(kw.get(k), E)
                 if each is not None:
                     kw[k] = each[e]
+            if "reference" in entry:
+                each = _per_episode_reference(entry["reference"], E)
+                kw["reference"] = _expanded(entry["reference"] if each is None else each[e], entry.get("repeat", 1))
+                kw["periodic"] = bool(entry.get("periodic", False))
             getattr(terms, entry["kind"])(**kw)
         terms.table()               # (an empty block is refused here)
         out.append(terms)
