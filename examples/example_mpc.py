@@ -80,7 +80,7 @@ def main():
     env = ENVS[exp["env_name"]](dtype=args.dtype)                    # the "real" environment
     env.real_env_step(True)
     sim = make_sim(exp["env_name"], args.dtype, num_cpu)             # the rollout engine
-    tracks = False
+    tracks = rates = False
     if exp.get("cost_terms"):
         # user-defined cost terms: the plans and the controlled env are costed by the same table (before any rollout_fn
         # is made: with terms set the closures offer the controllers no fused launch)
@@ -90,6 +90,9 @@ def main():
         # terms with a reference: the controlled env's engine counts its own steps; the rollout engine cannot
         # see them and is told the env time before every plan
         tracks = terms.tracked
+        # action-rate terms: likewise the controlled env's engine records the actions it applies; the rollout
+        # engine is told the last one before every plan
+        rates = terms.reads_action_rate
     if args.dyn_randomize_config:
         with open(args.dyn_randomize_config) as f:
             default_params, randomized = sim.randomize_dynamics(yaml.safe_load(f), base_seed=exp["seed"])
@@ -113,6 +116,8 @@ def main():
         env.reset(seed=episode_seed)
         if tracks:
             env.engine.set_track_step(0)                             # an episode starts at env time 0
+        if rates:
+            env.engine.set_prev_action(None)                         # ... and no action has been applied in it yet
         policy = MPCPolicy(controller_type=controller_type, param_dict=params, batch_size=1)
         ctrl = policy.controller
         ctrl.set_sim_state_fn = sim.set_env_state
@@ -128,6 +133,8 @@ def main():
             state = deepcopy(env.get_env_state())
             if tracks:
                 sim.set_track_step(k)
+            if rates:
+                sim.set_prev_action(np.asarray(actions[-1], np.float64).reshape(-1) if actions else None)
             t0 = time.perf_counter()
             action, _ = policy.get_action(state, calc_val=False)
             t_ctrl += time.perf_counter() - t0

@@ -37,7 +37,8 @@ extern "C" {
  *      fewer motors than dofs). */
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
- *      the DMD-MPC episode batches', mjmpc_cost_terms and mjmpc_cost_terms_track / _track_batch.) */
+ *      the DMD-MPC episode batches', mjmpc_cost_terms, mjmpc_cost_terms_track / _track_batch and mjmpc_cost_terms_rate /
+ *      _rate_batch.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -856,6 +857,40 @@ int mjmpc_cost_terms_track_batch(int dtype, int E, int64_t P, int H, int d_obs, 
                                  int terminal, const double* d_ref, int64_t n_ref, int n_cols, int ref_per_episode, int periodic,
                                  const int64_t* d_step, int64_t step_bias, void* d_costs, const double* d_gseq, double* d_q0,
                                  void* stream);
+
+/* Action-rate rows and one-sided kinds: mjmpc_cost_terms_track with two more sources of cost.  The entry serves
+ * every row of the entries above and
+ *   source 2, the action rate:  v = (double)actions[p][t][index] - (double)actions[p][t-1][index]  for t >= 1, and for t = 0
+ *     v = (double)actions[p][0][index] - d_prev_action[index], d_prev_action being float64 [A] on the device: the action last
+ *     applied to the controlled env.  An entry that is NaN says that no action has been applied yet: v = 0 for it, as for every
+ *     entry when d_prev_action is NULL.  r = v - target (or the tracked goal: a tracked rate row reads the ACTION-time
+ *     reference row b + t), and every kind applies, NORM groups over rate rows included;
+ *   kind 4 ABOVE  w max(0, r);   5 BELOW  w max(0, -r);   6 ABOVE_SQUARE  w max(0, r)^2;   7 BELOW_SQUARE  w max(0, -r)^2:
+ *     zero on one side of the bound `target` (or the tracked goal).
+ * The subtraction of the two actions is one correctly rounded double operation on values that convert exactly; order,
+ * rounding, `when`, keep_builtin and non-finite incoming costs are mjmpc_cost_terms'.  d_actions is required.  d_ref and
+ * d_step go together: both NULL for a table without tracked rows (n_ref, n_cols, periodic and step_bias are then ignored).
+ * advance != 0 (only for P = H = 1): behind its reads the launch leaves *d_step + 1 in the counter, where one is given, and
+ * the element's action row, as double, in d_prev_action, where that is given - the controlled env's step records the action
+ * it applied in the launch that costs it, so a captured graph or a launch tape carries it along.  Refused before anything
+ * is launched: null d_next_obs / d_actions / d_terms / d_costs, one of d_ref / d_step without the other, P, H, d_obs or A < 1,
+ * n_terms outside 1 .. 128, an unknown dtype, with a reference n_ref outside 1 .. 2^20 or n_cols outside 1 .. 128, advance
+ * with P * H != 1, an observation row and two action rows of more than 60 KiB. */
+int mjmpc_cost_terms_rate(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                          const double* d_terms, int n_terms, int keep_builtin, int terminal, const double* d_ref,
+                          int64_t n_ref, int n_cols, int periodic, int64_t* d_step, int64_t step_bias, int advance,
+                          double* d_prev_action, void* d_costs, void* stream);
+
+/* mjmpc_cost_terms_track_batch with the rows of mjmpc_cost_terms_rate.  d_prev_actions: float64 [E][A] or NULL, a particle
+ * reads its own episode's row at t = 0.  advance_prev != 0 (only for P = H = 1): the element of episode e stores its action
+ * row, as double, into row e behind its reads.  The counter is only read.  Costs and cost-to-go are bit for bit those of
+ * mjmpc_cost_terms_rate per episode and of mjmpc_cost_terms_batch's cost-to-go.  Refused: what mjmpc_cost_terms_rate
+ * refuses (E < 1, one of d_gseq / d_q0 without the other, advance_prev with P * H != 1; the row limit is 56 KiB). */
+int mjmpc_cost_terms_rate_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                const void* d_actions, const double* d_terms, int n_terms, int per_episode, int keep_builtin,
+                                int terminal, const double* d_ref, int64_t n_ref, int n_cols, int ref_per_episode, int periodic,
+                                const int64_t* d_step, int64_t step_bias, double* d_prev_actions, int advance_prev,
+                                void* d_costs, const double* d_gseq, double* d_q0, void* stream);
 
 #ifdef __cplusplus
 }

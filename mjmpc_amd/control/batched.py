@@ -89,6 +89,8 @@ class _EpisodeBatch:
     _engine_kind = "tree"   # ``engine=``: "tree" (TreeRolloutEngine) or "arm" (ArmRolloutEngine)
     _track = None           # tracked terms: (references on the device [1 or E][N][R], N, R, per episode?, periodic)
     _track_bias = 0         # env time of the references = _step_dev + _track_bias (set_track_step)
+    _rate = False           # the tables hold action-rate rows or one-sided kinds: mjmpc_cost_terms_rate_batch
+    _prev_actions = None    # ... with rate rows every episode's last applied action, float64 [E][A] on the device (NaN: none yet)
     _terms = None           # set_cost_terms: (tables on the device, rows, per episode?, keep_builtin, a row reads an action?)
     _terms_nobs = None      # ... the rollouts' next observations [E P][H][d_obs] (only while terms are set)
     _terms_env = None       # ... the real-env step's own next observations [E][d_obs] and actions [E][A] in the batch's dtype
@@ -276,6 +278,8 @@ class _EpisodeBatch:
         self._step_dev.zero_()
         self.num_steps = 0
         self._track_bias = 0
+        if self._prev_actions is not None:
+            self._prev_actions.fill_(float("nan"))      # (no action has been applied in the new episodes)
 
     # ------------------------------------------------------------------ dynamics randomization
     def randomize_dynamics(self, param_dict, base_seed, num_shards):
@@ -385,13 +389,20 @@ class _EpisodeBatch:
         (``mjmpc_cost_terms_batch``) rewrites the costs and forms the cost-to-go; the real-env step is followed by the same
         launch without the terminal rows.  Terms with a ``reference=`` (per episode the values may differ, ``N``,
         ``periodic`` and the tracked rows not) read their goals at env time ``num_steps`` (``set_track_step``: another) + the
-        plan step through ``mjmpc_cost_terms_track_batch``.  Everything is checked on the host first (``ValueError``);
-        callable between steps."""
+        plan step through ``mjmpc_cost_terms_track_batch``.  Tables with ``action_rate=`` rows or one-sided kinds
+        go through ``mjmpc_cost_terms_rate_batch``, tracked or not; with rate rows every episode's last applied action lives
+        on the device (``_prev_actions``, NaN now and after ``reset()``: the first rate of an episode is 0) - the plans read
+        it, the launch that costs the real-env step reads it and then records the step's action.  Everything is checked on the
+        host first (``ValueError``); callable between steps."""
         if terms is None:
-            self._terms = self._terms_nobs = self._terms_env = self._track = None
+            self._terms = self._terms_nobs = self._terms_env = self._track = self._prev_actions = None
+            self._rate = False
             return
         tables, keep, reads_actions = self._resolve_cost_terms(terms, self.engine, self.num_episodes)
         track = self._resolve_tracking(terms, self.engine, self.num_episodes)
+        rate_rows = bool(np.any(tables[0][:, 1] == 2))
+        self._rate = rate_rows or bool(np.any(tables[0][:, 0] >= 4))
+        reads_actions = reads_actions or self._rate         # (the rate entry wants the actions)
         self._track = None if track is None else (self._upload(track[0]), track[0].shape[1], track[0].shape[2],
                                                   int(track[0].shape[0] > 1), int(track[1]))
         torch, E, tdt, dev = self.torch, self.num_episodes, self._tdtype, self.device
@@ -400,11 +411,21 @@ class _EpisodeBatch:
         # the real-env step's own next observations (a caller may pass none) and its actions in the batch's dtype
         self._terms_env = (torch.empty((E, self.d_obs), dtype=tdt, device=dev),
                            torch.empty((E, self.d_action), dtype=tdt, device=dev) if reads_actions else None)
+        self._prev_actions = (torch.full((E, self.d_action), float("nan"), dtype=torch.float64, device=dev) if rate_rows
+                              else None)
 
-    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s, bias=0):
+    def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s, bias=0, advance_prev=0):
         """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s); with tracked terms
-        ``mjmpc_cost_terms_track_batch`` at env time ``_step_dev + bias``."""
+        ``mjmpc_cost_terms_track_batch`` at env time ``_step_dev + bias``; with rate rows or one-sided kinds
+        ``mjmpc_cost_terms_rate_batch`` (``advance_prev``: the E elements record their actions in ``_prev_actions``)."""
         tables, K, per_episode, keep, reads_actions = self._terms
+        if self._rate:
+            refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)
+            _lib.check(self.lib.mjmpc_cost_terms_rate_batch(
+                self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs), _vp(act), _vp(tables), K, per_episode,
+                keep, terminal, _vp(refs), N, R, ref_per_episode, periodic, _vp(self._step_dev) if refs is not None else None,
+                bias, _vp(self._prev_actions), advance_prev, _vp(costs), _vp(gseq), _vp(q0), s))
+            return
         if self._track is not None:
             refs, N, R, ref_per_episode, periodic = self._track
             _lib.check(self.lib.mjmpc_cost_terms_track_batch(
@@ -469,7 +490,7 @@ class _EpisodeBatch:
         if act_t is not None:
             act_t.copy_(act)                # (into the batch's dtype, as step_state does)
         # (every class's update launch has advanced _step_dev by now: the step that was planned at _step_dev - 1)
-        self._launch_cost_terms(1, 1, nobs, act_t, cost, 0, None, None, s, bias=self._track_bias - 1)
+        self._launch_cost_terms(1, 1, nobs, act_t, cost, 0, None, None, s, bias=self._track_bias - 1, advance_prev=1)
 
     def run(self, T):
         """``T`` control steps of every episode -> actions ``[T][E][A]`` (float64), real-env costs ``[T][E]`` and next
@@ -566,7 +587,7 @@ class BatchedMPPI(_EpisodeBatch):
         """Enqueue one control step of every episode (sampling, rollouts, update, action, shift, real-env step) without a
         host synchronisation.  The actions, real-env costs and next observations stay on the device."""
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
-        if self._track is not None:
+        if self._generic is not None:           # (tracked terms; rate rows or one-sided kinds, DESIGN 12.2)
             return self._launches_tracked(act, s)
         self._draw(s)
         self._rollout(s)
@@ -580,16 +601,18 @@ class BatchedMPPI(_EpisodeBatch):
     def set_cost_terms(self, terms):
         """``_EpisodeBatch.set_cost_terms``.  With tracked terms the step takes the general softmax update - what the
         single-episode MPPI runs once its costs come from a launch behind the rollout - in place of the fused one: an episode
-        of the batch stays, bit for bit, the sequential loop on an engine with the same tracked terms."""
+        of the batch stays, bit for bit, the sequential loop on an engine with the same tracked terms.  Tables with action-rate
+        rows or one-sided kinds (DESIGN 12.2) take the same step, tracked or not, and are that loop bit for bit as well;
+        every other table keeps the fused update."""
         super().set_cost_terms(terms)           # (every refusal of the terms themselves, before anything else)
         self._generic = None
-        if self._track is None:
+        if self._track is None and not self._rate:
             return
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
         nbytes = self.lib.mjmpc_dmd_batch_workspace_bytes(E, P, H, A)
         if nbytes <= 0:
             super().set_cost_terms(None)
-            raise ValueError("no general-update workspace for tracked terms with E = %d, P = %d, H = %d, A = %d (A <= 64)"
+            raise ValueError("no general-update workspace for tracked or rate terms with E = %d, P = %d, H = %d, A = %d (A <= 64)"
                              % (E, P, H, A))
         f64 = dict(dtype=self.torch.float64, device=self.device)
         self._generic = (self._workspace(nbytes), self.torch.zeros((E, A, A), **f64), self.torch.zeros(E, **f64))

@@ -73,6 +73,8 @@ class RolloutEngine(EnvResetWatch):
     _track_ref = None               # tracked terms: the reference [N][R] and the env-time counter, on the device
     _track_step = None
     _track_periodic = 0
+    _terms_rate = False             # the table holds action-rate rows or one-sided kinds: mjmpc_cost_terms_rate
+    _prev_action = None             # ... with rate rows the action last applied to the controlled env, float64 [A] on the device
     _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
 
     def __init__(self, model, device=0, dtype="f64", num_shards=1):
@@ -266,6 +268,9 @@ class RolloutEngine(EnvResetWatch):
         if self._track_step is not None and self._in_real_step and (P, H) != (1, 1):
             raise ValueError("a rollout under real_step_guard advances the tracked cost terms' env time by one step: it must "
                              "be one particle and one step, got (%d, %d)" % (P, H))
+        if self._prev_action is not None and self._in_real_step and (P, H) != (1, 1):
+            raise ValueError("a rollout under real_step_guard records the action it applied for the action-rate cost terms: it "
+                             "must be one particle and one step, got (%d, %d)" % (P, H))
         if self._terms_dev is not None:
             t_nobs = nobs if nobs is not None else self._buffer("terms_nobs", (P, H, self.d_obs))
             if self._terms_read_actions and act is None:
@@ -333,28 +338,39 @@ class RolloutEngine(EnvResetWatch):
         ``real_step_guard``).  The fused launches evaluate the built-in cost inside the rollout kernel and refuse to run
         while terms are set; ``make_device_rollout_fn`` then offers the controllers only the generic iteration - set the
         terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  The episode batches have their own
-        ``set_cost_terms`` (``control/batched.py``, DESIGN 10.8: one table for the batch or one per episode).  Not covered:
-        ``AnalyticRolloutEngine``, world sizes above 1.
+        ``set_cost_terms`` (``control/batched.py``, DESIGN 10.8: one table for the batch or one per episode).  Covered: both
+        rollout engines and all six episode-batch classes, with constant targets, tracked references, action rates and
+        one-sided bounds.  Not covered: the fused launches, ``AnalyticRolloutEngine``, world sizes above 1.
 
         Terms with a ``reference=`` are costed by ``mjmpc_cost_terms_track``: their reference goes to the device
         with an env-time counter (``track_step()``, 0 now) that every plan reads and every step of the controlled env
         (``step_state``, a ``(1, 1)`` rollout under ``real_step_guard``) advances by one inside its launch; a guarded rollout
-        of another shape raises ``ValueError``.  ``set_track_step(n)`` tells an engine that only plans what time it is."""
+        of another shape raises ``ValueError``.  ``set_track_step(n)`` tells an engine that only plans what time it is.
+
+        Terms with ``action_rate=`` rows or a one-sided kind are costed by ``mjmpc_cost_terms_rate``, tracked or
+        not.  With rate rows the engine keeps the action last applied to the controlled env on the device (``prev_action()``,
+        all NaN now: nothing applied, the first rate is 0): every plan's first step reads it and every step of the controlled
+        env records its action there inside its launch, with the same restriction on guarded rollouts.
+        ``set_prev_action(a)`` tells an engine that only plans which action was applied."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
                                "controllers %s; set the terms first, then call make_device_rollout_fn"
                                % (("with", "no fused launches") if self._closure_terms else ("without", "the fused launches")))
         if terms is None:
-            self._cost_terms = self._terms_dev = self._track_ref = self._track_step = None
-            self._terms_read_actions = False
+            self._cost_terms = self._terms_dev = self._track_ref = self._track_step = self._prev_action = None
+            self._terms_read_actions = self._terms_rate = False
             return
         table = np.ascontiguousarray(terms.table(self), np.float64)       # (ValueError before anything reaches the device)
         ref = terms.reference_table(self)
         torch = _torch()
         self._terms_dev = torch.from_numpy(table).to(self.device)
-        self._terms_read_actions = bool(np.any(table[:, 1] != 0))
+        self._terms_rate = bool(terms.needs_rate_entry)
+        self._terms_read_actions = bool(np.any(table[:, 1] != 0)) or self._terms_rate      # (the rate entry wants the actions)
         self._cost_terms = terms
-        self._track_ref = self._track_step = None
+        self._track_ref = self._track_step = self._prev_action = None
+        if terms.reads_action_rate:
+            # rate rows (DESIGN 12.2): the previous action lives on the device; NaN: none has been applied yet
+            self._prev_action = torch.full((self.d_action,), float("nan"), dtype=torch.float64, device=self.device)
         if ref is not None:
             # tracked terms (DESIGN 12.1): the reference and the env-time counter live on the device; time 0 is now
             self._track_ref = torch.from_numpy(ref).to(self.device)
@@ -377,10 +393,39 @@ class RolloutEngine(EnvResetWatch):
             raise RuntimeError("track_step: no tracked cost terms are set (CostTerms with reference=)")
         return int(self._track_step.item())
 
+    def set_prev_action(self, action):
+        """The action last applied to the controlled env, as the action-rate terms see it, becomes ``action``
+        (numpy ``(A,)`` or a CUDA float64 tensor; ``None``: no action yet - an episode's start, where the first rate is 0): a
+        copy or a fill in stream order, no synchronisation.  For loops whose controlled env is another object: call it before
+        each plan, beside ``set_track_step``.  ``step_state`` and a rollout under ``real_step_guard`` record their action
+        themselves; ``set_cost_terms`` resets it to "none"; ``set_env_state`` leaves it alone.  A host edit like
+        ``set_env_state``: with a controller's ``lookahead``, ``reset()`` it first."""
+        if self._prev_action is None:
+            raise RuntimeError("set_prev_action: no action-rate cost terms are set (CostTerms with action_rate=)")
+        if action is None:
+            self._prev_action.fill_(float("nan"))
+        else:
+            self._prev_action.copy_(self._as_device(action, _torch().float64, (self.d_action,)), non_blocking=True)
+
+    def prev_action(self):
+        """The action-rate terms' previous action, float64 ``(A,)`` read back from the device (synchronises the stream); NaN
+        entries: no action has been applied yet."""
+        if self._prev_action is None:
+            raise RuntimeError("prev_action: no action-rate cost terms are set (CostTerms with action_rate=)")
+        return self._prev_action.cpu().numpy().copy()
+
     def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, advance=False):
         t = self._terms_dev
         act = _ptr(act if self._terms_read_actions else None)
         keep = int(self._cost_terms.keep_builtin)
+        if self._terms_rate:
+            # (DESIGN 12.2; tracked or not, and as below the advance - counter and previous action - is part of the launch)
+            r = self._track_ref
+            _lib.check(self._lib.mjmpc_cost_terms_rate(
+                self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t), t.shape[0], keep, int(bool(terminal)),
+                _ptr(r), 0 if r is None else r.shape[0], 0 if r is None else r.shape[1], self._track_periodic,
+                _ptr(self._track_step), 0, int(bool(advance)), _ptr(self._prev_action), _ptr(costs), self._stream()))
+            return
         if self._track_step is None:
             _lib.check(self._lib.mjmpc_cost_terms(self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t),
                                                   t.shape[0], keep, int(bool(terminal)), _ptr(costs), self._stream()))

@@ -29,13 +29,27 @@ row's ``reserved`` column holds 1 + its column of ``reference_table()`` and its 
 is a counter on the device (``engine.set_track_step`` / ``track_step``; the controlled env's steps advance it).
 
     terms.square(obs="qpos", index=0, weight=0.5, reference=np.repeat([0.0, 0.4, 0.0, -0.4], 50), periodic=True)
+
+Action rates and one-sided kinds.  ``action_rate=`` (what ``action=`` takes) makes rows of ``source`` 2:
+``v = u_t - u_{t-1}``, the change of the action from the step before - at a plan's first step from the action last applied
+to the controlled env, which the engine keeps on the device (``engine.set_prev_action`` / ``prev_action``; before the first
+step the rate is 0).  The kinds 4 .. 7 are zero on one side of the bound ``target``: ABOVE ``w max(0, r)``, BELOW
+``w max(0, -r)``, ABOVE_SQUARE and BELOW_SQUARE their squares.  A table with either is costed by ``mjmpc_cost_terms_rate``
+(``needs_rate_entry``); every other table is what it was, byte for byte.
+
+    terms.square(action_rate="all", weight=0.1)                         # smooth controls
+    terms.outside(obs="qpos", index=0, low=-2.0, high=2.0, weight=10.0)  # the cart stays within +-2 m
+    terms.above(obs="qvel", index=1, target=3.0)                        # joint speed below 3 rad/s, linear beyond it
 """
 import numpy as np
 
 from ..models.raw import TASK_REACH
 
 KIND_ABS, KIND_SQUARE, KIND_NORM, KIND_COS = 0, 1, 2, 3
-KINDS = {"abs": KIND_ABS, "square": KIND_SQUARE, "norm": KIND_NORM, "cos": KIND_COS}
+KIND_ABOVE, KIND_BELOW, KIND_ABOVE_SQUARE, KIND_BELOW_SQUARE = 4, 5, 6, 7
+KINDS = {"abs": KIND_ABS, "square": KIND_SQUARE, "norm": KIND_NORM, "cos": KIND_COS, "above": KIND_ABOVE, "below": KIND_BELOW,
+         "above_square": KIND_ABOVE_SQUARE, "below_square": KIND_BELOW_SQUARE}
+SOURCE_OBS, SOURCE_ACTION, SOURCE_ACTION_RATE = 0, 1, 2
 MAX_TERMS = 128
 ROW_LEN = 8
 MAX_REFERENCE_ROWS = 1 << 20    # (the kernel's per-lane index arithmetic is 32-bit)
@@ -59,27 +73,82 @@ class CostTerms:
     def __init__(self, engine=None, keep_builtin=False):
         self.engine = engine
         self.keep_builtin = bool(keep_builtin)
-        # (kind, source block or None, indices or None, action?, weight, target, terminal, reference [N] / [N][n_idx] or None)
+        # (kind, source block or None, indices or None, source 0 / 1 / 2 (non-zero: it indexes the action), weight, target,
+        #  terminal, reference [N] / [N][n_idx] or None)
         self._terms = []
         self._periodic = None       # the tracked terms' shared `periodic` (None: no tracked term yet)
 
-    # ------------------------------------------------------------------ the four kinds
+    # ------------------------------------------------------------------ the kinds
     def abs(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
-            periodic=False):
-        return self._add(KIND_ABS, obs, action, index, weight, target, terminal, reference, periodic)
+            periodic=False, action_rate=None):
+        return self._add(KIND_ABS, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
 
     def square(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
-               periodic=False):
-        return self._add(KIND_SQUARE, obs, action, index, weight, target, terminal, reference, periodic)
+               periodic=False, action_rate=None):
+        return self._add(KIND_SQUARE, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
 
     def cos(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
-            periodic=False):
-        return self._add(KIND_COS, obs, action, index, weight, target, terminal, reference, periodic)
+            periodic=False, action_rate=None):
+        return self._add(KIND_COS, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
 
     def norm(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
-             periodic=False):
+             periodic=False, action_rate=None):
         """``weight * sqrt(sum_i (v_i - target_i)^2)`` over the indices: one group of the table."""
-        return self._add(KIND_NORM, obs, action, index, weight, target, terminal, reference, periodic)
+        return self._add(KIND_NORM, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
+
+    # ------------------------------------------------------------------ one-sided kinds (DESIGN 12.2): `target` is the bound
+    def above(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+              periodic=False, action_rate=None):
+        """``weight * max(0, v - target)``: nothing up to the bound, linear above it."""
+        return self._add(KIND_ABOVE, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
+
+    def below(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+              periodic=False, action_rate=None):
+        """``weight * max(0, target - v)``: nothing down to the bound, linear below it."""
+        return self._add(KIND_BELOW, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
+
+    def above_square(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+                     periodic=False, action_rate=None):
+        """``weight * max(0, v - target)^2``."""
+        return self._add(KIND_ABOVE_SQUARE, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
+
+    def below_square(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+                     periodic=False, action_rate=None):
+        """``weight * max(0, target - v)^2``."""
+        return self._add(KIND_BELOW_SQUARE, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
+
+    def outside(self, obs=None, action=None, index=None, low=None, high=None, weight=1.0, squared=True, terminal=False,
+                action_rate=None):
+        """A soft band: nothing inside ``[low, high]``, outside it ``weight`` times the distance to the band (``squared``: its
+        square).  Adds the ``below`` row or rows at ``low`` and then the ``above`` row or rows at ``high``; either bound may
+        be left out (``None``), each is a number or one number per index."""
+        if low is None and high is None:
+            raise ValueError("cost term: outside needs low=, high= or both")
+        if low is not None and high is not None and np.any(_finite(low, "low") > _finite(high, "high")):
+            raise ValueError("cost term: outside needs low <= high, got low %r, high %r" % (low, high))
+        n = len(self._terms)
+        try:
+            if low is not None:
+                self._add(KIND_BELOW_SQUARE if squared else KIND_BELOW, obs, action, index, weight, low, terminal, None, False,
+                          action_rate)
+            if high is not None:
+                self._add(KIND_ABOVE_SQUARE if squared else KIND_ABOVE, obs, action, index, weight, high, terminal, None, False,
+                          action_rate)
+        except ValueError:
+            del self._terms[n:]         # (both rows or neither)
+            raise
+        return self
+
+    @property
+    def needs_rate_entry(self):
+        """Whether the table holds an action-rate row or a one-sided kind: rows only ``mjmpc_cost_terms_rate`` and
+        ``mjmpc_cost_terms_rate_batch`` serve."""
+        return any(t[3] == SOURCE_ACTION_RATE or t[0] >= KIND_ABOVE for t in self._terms)
+
+    @property
+    def reads_action_rate(self):
+        """Whether a row reads an action rate: the engine then keeps the previous action."""
+        return any(t[3] == SOURCE_ACTION_RATE for t in self._terms)
 
     # ------------------------------------------------------------------ tracked terms (DESIGN 12.1)
     @property
@@ -155,17 +224,19 @@ class CostTerms:
         return np.asarray(rows, np.float64).reshape(-1, ROW_LEN)
 
     # ------------------------------------------------------------------ internals
-    def _add(self, kind, obs, action, index, weight, target, terminal, reference=None, periodic=False):
-        if (obs is None) == (action is None):
-            raise ValueError("cost term: give exactly one of obs= and action=")
-        is_action = action is not None
+    def _add(self, kind, obs, action, index, weight, target, terminal, reference=None, periodic=False, action_rate=None):
+        if (obs is not None) + (action is not None) + (action_rate is not None) != 1:
+            raise ValueError("cost term: give exactly one of obs=, action= and action_rate=")
+        source = SOURCE_ACTION if action is not None else SOURCE_ACTION_RATE if action_rate is not None else SOURCE_OBS
         block = None
-        if is_action:
+        if source:
+            what = "action" if action is not None else "action_rate"
+            action = action if action is not None else action_rate
             if isinstance(action, str) and action != "all":
-                raise ValueError("unknown action block %r (an index, a list of indices, True or 'all')" % (action,))
+                raise ValueError("unknown %s block %r (an index, a list of indices, True or 'all')" % (what, action))
             if not (action is True or isinstance(action, str)):
                 if index is not None:
-                    raise ValueError("cost term: action= already gives the indices; drop index=")
+                    raise ValueError("cost term: %s= already gives the indices; drop index=" % what)
                 index = action
         elif isinstance(obs, str):
             block = obs
@@ -198,7 +269,7 @@ class CostTerms:
                 raise ValueError("cost terms: the tracked terms of a table share one periodic=")
         elif periodic:
             raise ValueError("cost term: periodic= goes with a reference=")
-        term = (int(kind), block, index, is_action, weight, target, bool(terminal), reference)
+        term = (int(kind), block, index, source, weight, target, bool(terminal), reference)
         if self.engine is not None:
             n_idx = len(self._resolve(term, self.engine)[0])    # refuse now what the engine would refuse later
             if reference is not None:
@@ -214,13 +285,13 @@ class CostTerms:
     @staticmethod
     def _resolve(term, engine):
         """-> (absolute indices, source, one target per index) of a term, checked against the engine's dimensions."""
-        _, block, index, is_action, _, target = term[:6]
+        _, block, index, source, _, target = term[:6]
         if engine is None:
             if block is not None or index is None:
                 raise ValueError("cost terms that name a block or take every entry need an engine: CostTerms(engine) or "
                                  "table(engine)")
-            lo, n, limit, what = 0, None, None, "action" if is_action else "observation"
-        elif is_action:
+            lo, n, limit, what = 0, None, None, "action" if source else "observation"
+        elif source:
             lo, n, limit, what = 0, _dims(engine)[1], _dims(engine)[1], "action"
         elif block is None:
             lo, n, limit, what = 0, _dims(engine)[0], _dims(engine)[0], "observation"
@@ -239,10 +310,12 @@ class CostTerms:
         targets = np.broadcast_to(target, (len(idx),)) if target.ndim == 0 else target
         if len(targets) != len(idx):
             raise ValueError("cost term: target must be a number or one number per index")
-        return idx, 1.0 if is_action else 0.0, [float(x) for x in targets]
+        return idx, float(source), [float(x) for x in targets]
 
 
-_TERM_KEYS = {"kind", "obs", "action", "index", "weight", "target", "terminal", "reference", "repeat", "periodic"}
+_TERM_KEYS = {"kind", "obs", "action", "action_rate", "index", "weight", "target", "terminal", "reference", "repeat",
+              "periodic"}
+_OUTSIDE_KEYS = {"kind", "obs", "action", "action_rate", "index", "weight", "low", "high", "squared", "terminal"}
 
 
 def _depth(value):
@@ -302,21 +375,28 @@ def cost_terms_from_config(block, engine, num_episodes=None):
 
     A term may give ``reference:`` - a list of N numbers or of N lists (one number per index) - in place of ``target``,
     ``repeat: k`` (every entry holds for k env steps, expanded here) and ``periodic:``.  A ``reference`` that is a
-    list of references - three levels, or a list of ``num_episodes`` lists of numbers - holds one per episode."""
+    list of references - three levels, or a list of ``num_episodes`` lists of numbers - holds one per episode.
+
+    DESIGN 12.2: ``action_rate:`` stands where ``action:`` may; the kinds ``above``, ``below``, ``above_square`` and
+    ``below_square`` take the bound as ``target``; ``{kind: outside, obs: qpos, index: 0, low: -2.0, high: 2.0, weight: 10.0}``
+    is ``CostTerms.outside`` (``squared:`` as there; ``weight``, ``low`` and ``high`` may hold one value per episode)."""
     if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms"}:
         raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin'")
     E = None if num_episodes is None else int(num_episodes)
     entries = block.get("terms") or []
     per_episode = False
     for entry in entries:
-        if not isinstance(entry, dict) or set(entry) - _TERM_KEYS:
-            raise ValueError("cost_terms: a term takes %s, got %r" % (sorted(_TERM_KEYS), entry))
-        if entry.get("kind") not in KINDS:
-            raise ValueError("cost_terms: unknown kind %r (one of %s)" % (entry.get("kind"), ", ".join(KINDS)))
+        outside = isinstance(entry, dict) and entry.get("kind") == "outside"
+        keys = _OUTSIDE_KEYS if outside else _TERM_KEYS
+        if not isinstance(entry, dict) or set(entry) - keys:
+            raise ValueError("cost_terms: a term takes %s, got %r" % (sorted(keys), entry))
+        if entry.get("kind") not in KINDS and not outside:
+            raise ValueError("cost_terms: unknown kind %r (one of %s, outside)" % (entry.get("kind"), ", ".join(KINDS)))
         if isinstance(entry.get("weight"), (list, tuple)) and _per_episode_value(entry["weight"], E) is None:
             raise ValueError("cost_terms: a list-valued weight holds one weight per episode%s, got %d"
                              % ("" if E is None else " (%d)" % E, len(entry["weight"])))
-        per_episode = per_episode or any(_per_episode_value(entry.get(k), E) is not None for k in ("weight", "target"))
+        per_episode = per_episode or any(_per_episode_value(entry.get(k), E) is not None
+                                          for k in ("weight", "target", "low", "high"))
         if "reference" in entry:
             per_episode = per_episode or _per_episode_reference(entry["reference"], E) is not None
             repeat = entry.get("repeat", 1)
@@ -328,8 +408,9 @@ def cost_terms_from_config(block, engine, num_episodes=None):
     for e in range(E if per_episode else 1):
         terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
         for entry in entries:
-            kw = {k: entry[k] for k in ("obs", "action", "index", "weight", "target", "terminal") if k in entry}
-            for k in ("weight", "target"):
+            kw = {k: entry[k] for k in ("obs", "action", "action_rate", "index", "weight", "target", "terminal", "low", "high",
+                                        "squared") if k in entry}
+            for k in ("weight", "target", "low", "high"):
                 each = _per_episode_value(kw.get(k), E)
                 if each is not None:
                     kw[k] = each[e]
