@@ -1,14 +1,25 @@
-// User-defined cost terms: a second, bandwidth-bound launch behind a rollout that turns the next observations
-// and the actions of every (particle, step) into a cost from a table of terms.  The rollout kernels keep their built-in
-// costs and are not touched: the terms live neither in the model block (its length is part of the ABI) nor in the rollout
-// translation units (an edit there moves the register allocation of every instantiation).
+// User-defined cost terms: a second, bandwidth-bound launch behind a rollout that turns the next
+// observations and the actions of every (particle, step) into a cost from a table of terms.  The rollout kernels keep their
+// built-in costs and are not touched: the terms live neither in the model block (its length is part of the ABI) nor in the
+// rollout translation units (an edit there moves the register allocation of every instantiation).
 //
 // A table row is eight doubles - kind, source, index, weight, target, group, when, reserved (include/mjmpc_amd.h):
-//   v = next_obs[p][t][index] (source 0) or actions[p][t][index] (source 1), as double;  r = v - target
+//   source 0       v = next_obs[p][t][index], as double
+//   source 1       v = actions[p][t][index]
+//   source 2       v = actions[p][t][index] - actions[p][t - 1][index], the action rate (rate entries only).  At t = 0 the
+//                  step before is entry `index` of the launch's previous-action vector `prev` (float64 [A]); where that is
+//                  NaN, or without `prev`, nothing has been applied yet and v = 0
+//   reserved       0: the goal is the row's `target`.  1 + c (track and rate entries with a reference `ref`, float64
+//                  [n_ref][n_cols]): the goal is column c of a reference row - row b + t + 1 for an observation, row b + t for an
+//                  action (source 1 or 2), clamped to [0, n_ref - 1] or taken mod n_ref (`periodic`), b = *step + bias, a
+//                  counter on the device: a captured graph or a launch tape freezes the pointer, not the value
+//   r = v - goal
 //   kind 0 ABS     w |r|
 //   kind 1 SQUARE  w r^2
 //   kind 2 NORM    consecutive rows of one group > 0: w_first sqrt(sum r^2), once, at the group's last row
 //   kind 3 COS     w (1 - cos r), formed as 2 w sin^2(r / 2): no cancellation near r = 0
+//   kind 4 ABOVE   w max(0, r)             kind 5 BELOW         w max(0, -r)            (4 .. 7: rate entries only)
+//   kind 6 ABOVE_SQUARE  w max(0, r)^2     kind 7 BELOW_SQUARE  w max(0, -r)^2
 //   when = 1       the row counts only at t = H - 1 and only if the launch says `terminal`
 // The cost of (p, t) is the sum over the rows in row order, in double whatever the storage type, behind the incoming cost
 // when keep_builtin is set; an incoming cost that is not finite leaves as +inf either way (a particle that reset
@@ -16,13 +27,24 @@
 //
 // Shape: the elements e = p H + t of a launch are independent and their observation rows lie back to back, so a workgroup
 // takes `rows` (64, fewer for very wide rows) consecutive elements, copies their rows into LDS with unit-stride loads (lane i
-// reads word i of the tile) and then lane j walks the table over row j of the tile.  Read straight from memory, lane j's gathers would be d_obs words
-// apart: one 64-byte request per lane and per row of the table.  The LDS rows are padded to an odd number of words, which
-// spreads the lanes' column reads over all banks.  The table is decoded once per workgroup into LDS; every lane reads the
-// same entry at the same time (a broadcast).
+// reads word i of the tile) and then lane j walks the table over row j of the tile.  Read straight from memory, lane j's
+// gathers would be d_obs words apart: one 64-byte request per lane and per row of the table.  The LDS rows are padded to an
+// odd number of words, which spreads the lanes' column reads over all banks.  The table is decoded once per workgroup into
+// LDS; every lane reads the same entry at the same time (a broadcast).
+// The tile: `rows` observation rows, then - where the launch has actions - `rows` action rows; the rate kernels put one more
+// action row in front of those, the row of the element before the tile's first (which may lie in another workgroup's tile),
+// so lane j's action row is tile row j + 1 and its previous one tile row j, whatever j is: no lane goes to memory for it.
+//
+// Two kernel templates carry the six entries: cost_terms_flat_kernel (one tile per workgroup) and cost_terms_batch_kernel
+// (whole particles per workgroup, for the episode batches), each over <T, TRACK, RATE>:
+//   TRACK   rows may be tracked (`ref` given).  Off: the reference, the counter and the reference columns are compiled out.
+//   RATE    source 2 and the kinds 4 .. 7, the leading action row, `prev`.  Off: they are compiled out, and a null `act` means
+//           "no action tile".
+// Both are template flags and not run-time tests: that variant was measured slower (profiles/r19_rate.txt).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <initializer_list>
 
 #include "../../include/mjmpc_amd.h"
 
@@ -36,13 +58,14 @@ constexpr int CT_ROWS = 64;                 // elements per workgroup: four wave
                                             // tiles put many workgroups in flight; measured against one-wavefront workgroups
                                             // and against a walk that fetches rows ahead (both slower): profiles/r16_cost_terms.txt
 constexpr int CT_MAX_TERMS = 128;
-constexpr int CT_LDS_BYTES = 60 * 1024;     // the tile's share of a workgroup's 64 KiB (the decoded table takes 3.5 KiB)
+constexpr int CT_MAX_REF_ROWS = 1 << 20;    // a lane adds its t to the launch's base time in 32 bits (ct_ref_rows)
+constexpr int CT_LDS_BYTES = 60 * 1024;     // the tile's share of a workgroup's 64 KiB (the decoded table takes 3.5 - 4 KiB)
 constexpr int CT_BATCH_LDS_BYTES = 56 * 1024;   // cost_terms_batch_kernel's tile: two sets of weights and targets and a chunk's
-                                                // costs stand beside it (6 KiB)
+                                                // costs stand beside it (6 - 6.5 KiB)
 
 // a decoded row's flags
 constexpr int CT_ACTION = 1, CT_TERMINAL = 2, CT_GROUP_FIRST = 4, CT_GROUP_LAST = 8;
-constexpr int CT_RATE = 16;                 // (only the extended decode, X, sets it: source 2)
+constexpr int CT_RATE = 16;                 // (only the RATE decode sets it: source 2)
 
 // the odd row pitch in words of the tile
 __host__ __device__ inline int ct_pitch(int n) { return n | 1; }
@@ -61,9 +84,16 @@ __device__ __forceinline__ void ct_stage(const T* __restrict__ src, int rows, in
     }
 }
 
+// RATE: stage the action rows of elements [first, first + mine) behind tile row 0, and row first - 1 into it where there is one
+template <typename T>
+__device__ __forceinline__ void ct_stage_actions(const T* __restrict__ act, long first, int mine, int A, int pa, T* tile_a) {
+    if (first > 0) ct_stage(act + (first - 1) * A, mine + 1, A, pa, tile_a);
+    else ct_stage(act, mine, A, pa, tile_a + pa);
+}
+
 // decode the structural columns of a table (kind, source, index, group, when) into LDS: `terms` is [n_terms][8].
-// X (the kernels of DESIGN 12.2): a row of source 2 reads the action tile like one of source 1 and is marked CT_RATE.
-template <bool X = false>
+// RATE: a row of source 2 reads the action tile like one of source 1 and is marked CT_RATE.
+template <bool RATE>
 __device__ __forceinline__ void ct_decode(const double* __restrict__ terms, int n_terms, int* s_kind, int* s_col, int* s_flags) {
     for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
         const double* row = terms + 8 * k;
@@ -74,7 +104,7 @@ __device__ __forceinline__ void ct_decode(const double* __restrict__ terms, int 
             if (k == 0 || (int)terms[8 * (k - 1)] != 2 || terms[8 * (k - 1) + 5] != group) f |= CT_GROUP_FIRST;
             if (k == n_terms - 1 || (int)terms[8 * (k + 1)] != 2 || terms[8 * (k + 1) + 5] != group) f |= CT_GROUP_LAST;
         }
-        if constexpr (X) {
+        if constexpr (RATE) {
             if (row[1] == 2.0) f |= CT_RATE;
         }
         s_kind[k] = kind;
@@ -91,169 +121,16 @@ __device__ __forceinline__ void ct_decode_values(const double* __restrict__ term
     }
 }
 
-// where a walk takes row k's weight and target from: two arrays in LDS
-struct CtArrays {
-    const double *w, *target;
-    __device__ __forceinline__ double weight(int k) const { return w[k]; }
-    __device__ __forceinline__ double goal(int k) const { return target[k]; }
-};
-
-// one element's walk over the table: its observation row my_o and action row my_a (LDS), `acc` the first addend.
-// X (the instantiations without it are the code they were): a CT_RATE row reads the action minus the action of
-// the step before - the tile row in front of my_a, which its kernel staged, or at the first step of a plan entry `col` of
-// `prev` (float64, through the cache; NaN or no `prev`: nothing has been applied yet and the rate is 0) - and the kinds
-// 4 .. 7 are the one-sided ABOVE w max(0, r), BELOW w max(0, -r), ABOVE_SQUARE and BELOW_SQUARE.
-template <bool X = false, typename T, typename V>
-__device__ __forceinline__ double ct_walk(const int* s_kind, const int* s_col, const int* s_flags, int n_terms, const T* my_o,
-                                          const T* my_a, bool last_step, double acc, const V values, int pa = 0,
-                                          bool first_step = false, const double* prev = nullptr) {
-    double sq = 0.0, w_group = 0.0;
-    for (int k = 0; k < n_terms; ++k) {
-        const int f = s_flags[k], kind = s_kind[k];
-        if ((f & CT_TERMINAL) && !last_step) continue;
-        double v = (double)((f & CT_ACTION) ? my_a[s_col[k]] : my_o[s_col[k]]);
-        if constexpr (X) {
-            if (f & CT_RATE) {
-                const int c = s_col[k];
-                if (first_step) {
-                    const double before = prev ? prev[c] : (double)NAN;
-                    v = before == before ? v - before : 0.0;
-                } else {
-                    v -= (double)my_a[c - pa];
-                }
-            }
-        }
-        const double r = v - values.goal(k);
-        const double w = values.weight(k);
-        if (kind == 0) {
-            acc += w * fabs(r);
-        } else if (kind == 1) {
-            acc += w * (r * r);
-        } else if (kind == 2) {
-            if (f & CT_GROUP_FIRST) { sq = 0.0; w_group = w; }
-            sq += r * r;
-            if (f & CT_GROUP_LAST) acc += w_group * sqrt(sq);
-        } else if (!X || kind == 3) {
-            const double s = sin(0.5 * r);
-            acc += w * (2.0 * s * s);
-        } else {
-            const double side = (kind & 1) ? -r : r;                // 5, 7: below the bound
-            const double m = side > 0.0 ? side : 0.0;
-            acc += w * (kind >= 6 ? m * m : m);
-        }
+// TRACK: a table's reference columns into LDS, -1 for a row with a constant target.  A column beyond the reference (the host
+// builder never writes one) is held inside it: the walk must not read past `ref` whatever the table says.
+__device__ __forceinline__ void ct_decode_ref_cols(const double* __restrict__ terms, int n_terms, int n_cols, int* s_rcol) {
+    for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
+        const int c = (int)terms[8 * k + 7] - 1;
+        s_rcol[k] = c < 0 ? -1 : c < n_cols ? c : n_cols - 1;
     }
-    return acc;
 }
 
-// grid: ceil(n / rows) workgroups of CT_WG; dynamic LDS: rows (pitch(d_obs) + pitch(A)) words of T
-template <typename T>
-__global__ __launch_bounds__(CT_WG) void cost_terms_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
-                                                           const double* __restrict__ terms, int n_terms, long n, int H,
-                                                           int d_obs, int A, int rows, int keep_builtin, int terminal,
-                                                           T* __restrict__ costs) {
-    extern __shared__ double ct_tile_raw[];
-    __shared__ double s_w[CT_MAX_TERMS], s_target[CT_MAX_TERMS];
-    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS];
-    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
-    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
-    T* const tile_a = tile_o + (long)rows * po;
-    const long e0 = (long)blockIdx.x * rows;
-    const int mine = n - e0 < rows ? (int)(n - e0) : rows;
-
-    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
-    ct_decode_values(terms, n_terms, s_w, s_target);
-    ct_stage(nobs + e0 * d_obs, mine, d_obs, po, tile_o);
-    if (act) ct_stage(act + e0 * A, mine, A, pa, tile_a);
-    __syncthreads();
-
-    const int j = threadIdx.x;
-    if (j >= mine) return;
-    const long e = e0 + j;
-    const bool last_step = terminal && (int)(e % H) == H - 1;
-    const T incoming = costs[e];
-    const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa, last_step,
-                               keep_builtin ? (double)incoming : 0.0, CtArrays{s_w, s_target});
-    costs[e] = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
-}
-
-// The episode batches' launch (DESIGN 10.8): the costs of E P particles, [E P][H], with one table for all or one per episode
-// (the structural columns are episode 0's; weight and target the particle's own episode's), and in the same launch the
-// discounted cost-to-go q0[p] = sum_t gseq[t] cost[p][t] of the costs as stored, forward, every product and sum rounded.
-// A workgroup owns `ppw` whole particles - as many as fit the tile's `rows` elements, one if H is longer, and with a table per
-// episode no more than an episode holds - and takes their ppw H elements in chunks of `rows`: stage, walk (lane j = element j
-// of the chunk), store the cost and leave gseq[t] cost in LDS, then thread s < ppw carries particle s's sum on over the
-// chunk's elements of that particle.  So a particle's costs meet in one thread whatever H is, the products are formed by all
-// lanes and only the additions are serial, and the observations are read once.  ppw <= P consecutive particles cross at most
-// one episode boundary: two sets of weights and targets are decoded into LDS and a lane picks its episode's.
-// grid: ceil(E P / ppw) workgroups of CT_WG; dynamic LDS as cost_terms_kernel's
-template <typename T>
-__global__ __launch_bounds__(CT_WG) void cost_terms_batch_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
-                                                                 const double* __restrict__ terms, int n_terms, long np, long P,
-                                                                 int H, int d_obs, int A, int rows, int ppw, int per_episode,
-                                                                 int keep_builtin, int terminal, T* __restrict__ costs,
-                                                                 const double* __restrict__ gseq, double* __restrict__ q0) {
-    extern __shared__ double ct_tile_raw[];
-    __shared__ double s_w[2][CT_MAX_TERMS], s_target[2][CT_MAX_TERMS], s_gc[CT_ROWS];
-    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS];
-    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
-    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
-    T* const tile_a = tile_o + (long)rows * po;
-    const long p0 = (long)blockIdx.x * ppw;                         // my first particle
-    const int my_p = np - p0 < ppw ? (int)(np - p0) : ppw;          // my particles
-    const long e0 = p0 * H;
-    const int my_n = my_p * H;                                      // my elements (ppw > 1 only where ppw H <= rows)
-    // my particles from `second` on belong to the episode after my first particle's
-    int second = my_p;
-    if (per_episode) {
-        const long ep0 = p0 / P, next = (ep0 + 1) * P - p0;
-        ct_decode_values(terms + ep0 * 8L * n_terms, n_terms, s_w[0], s_target[0]);
-        if (next < my_p) {
-            second = (int)next;
-            ct_decode_values(terms + (ep0 + 1) * 8L * n_terms, n_terms, s_w[1], s_target[1]);
-        }
-    } else {
-        ct_decode_values(terms, n_terms, s_w[0], s_target[0]);
-    }
-    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
-    double q = 0.0;                                                 // thread s < my_p: particle p0 + s's sum so far
-    const int j = threadIdx.x;
-    for (int c0 = 0; c0 < my_n; c0 += rows) {
-        const int mine = my_n - c0 < rows ? my_n - c0 : rows;
-        ct_stage(nobs + (e0 + c0) * d_obs, mine, d_obs, po, tile_o);
-        if (act) ct_stage(act + (e0 + c0) * A, mine, A, pa, tile_a);
-        __syncthreads();
-        if (j < mine) {
-            const int le = c0 + j, pl = le / H, t = le - pl * H;    // my element: particle pl of the workgroup's, step t
-            const double g = gseq ? gseq[t] : 0.0;
-            const T incoming = costs[e0 + le];
-            const int slot = pl >= second;
-            const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa,
-                                       terminal && t == H - 1, keep_builtin ? (double)incoming : 0.0,
-                                       CtArrays{s_w[slot], s_target[slot]});
-            const T out = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
-            costs[e0 + le] = out;
-            s_gc[j] = g * (double)out;
-        }
-        __syncthreads();
-        if (q0 && j < my_p) {
-            // my particle's elements are [j H, (j + 1) H) of the workgroup's; this chunk holds [c0, c0 + mine)
-            const int lo = j * H > c0 ? j * H : c0;
-            const int hi = (j + 1) * H < c0 + mine ? (j + 1) * H : c0 + mine;
-#pragma unroll 4
-            for (int i = lo; i < hi; ++i) q += s_gc[i - c0];
-        }
-    }
-    if (q0 && j < my_p) q0[p0 + j] = fabs(q) < (double)INFINITY ? q : (double)INFINITY;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Terms that track a reference trajectory.  A tracked row's `reserved` column holds 1 + c, c its column of the
-// reference `ref` (float64 [n_ref][n_cols]; row n = the goal for env time n).  A launch's base time is b = *step + bias, a
-// counter on the device: a captured graph or a launch tape freezes the pointer, not the value.  Element (p, t) compares its
-// observation rows with reference row b + t + 1 and its action rows with row b + t, clamped to [0, n_ref - 1] or taken
-// mod n_ref.  b is reduced once per workgroup (it is uniform) into a 32-bit base; a lane adds its t in 32 bits: n_ref <= 2^20.
-constexpr int CT_MAX_REF_ROWS = 1 << 20;
-
+// TRACK: a launch's base time b, reduced once per workgroup (it is uniform) into 32 bits; a lane adds its t: n_ref <= 2^20
 struct CtClock {
     int base, n, periodic;      // periodic: base = b mod n in [0, n); else b clamped to [-2^31, n - 1]
 };
@@ -284,17 +161,15 @@ __device__ __forceinline__ void ct_ref_rows(const CtClock c, int t, int& n_obs, 
     }
 }
 
-// a table's reference columns into LDS: -1 for a row with a constant target.  A column beyond the reference (the host
-// builder never writes one) is held inside it: the walk must not read past `ref` whatever the table says.
-__device__ __forceinline__ void ct_decode_ref_cols(const double* __restrict__ terms, int n_terms, int n_cols, int* s_rcol) {
-    for (int k = threadIdx.x; k < n_terms; k += CT_WG) {
-        const int c = (int)terms[8 * k + 7] - 1;
-        s_rcol[k] = c < 0 ? -1 : c < n_cols ? c : n_cols - 1;
-    }
-}
+// where a walk takes row k's weight and goal from: two arrays in LDS ...
+struct CtArrays {
+    const double *w, *target;
+    __device__ __forceinline__ double weight(int k) const { return w[k]; }
+    __device__ __forceinline__ double goal(int k) const { return target[k]; }
+};
 
-// where a walk over a table with tracked rows takes row k's goal from: the element's two reference rows, read through the
-// cache (a launch's window is (H + 1) n_cols doubles, the same few KB for every workgroup), or the constant target
+// ... or (TRACK) the element's two reference rows, read through the cache (a launch's window is (H + 1) n_cols doubles, the
+// same few KB for every workgroup), for a row with a reference column
 struct CtTracked {
     const double *w, *target;
     const int *rcol, *flags;
@@ -306,136 +181,57 @@ struct CtTracked {
     }
 };
 
-// cost_terms_kernel with tracked rows.  advance (host: only for P = H = 1, one workgroup): every lane takes its copy of the
-// counter before the barrier, the one walking lane stores counter + 1 behind its walk.
-template <typename T>
-__global__ __launch_bounds__(CT_WG) void cost_terms_track_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
-                                                                 const double* __restrict__ terms, int n_terms, long n, int H,
-                                                                 int d_obs, int A, int rows, int keep_builtin, int terminal,
-                                                                 const double* __restrict__ ref, int n_ref, int n_cols,
-                                                                 int periodic, int64_t* step, int64_t bias, int advance,
-                                                                 T* __restrict__ costs) {
-    extern __shared__ double ct_tile_raw[];
-    __shared__ double s_w[CT_MAX_TERMS], s_target[CT_MAX_TERMS];
-    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS], s_rcol[CT_MAX_TERMS];
-    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
-    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
-    T* const tile_a = tile_o + (long)rows * po;
-    const long e0 = (long)blockIdx.x * rows;
-    const int mine = n - e0 < rows ? (int)(n - e0) : rows;
-    const int64_t now = *step;
-    const CtClock clock = ct_clock((long)(now + bias), n_ref, periodic);
-
-    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
-    ct_decode_values(terms, n_terms, s_w, s_target);
-    ct_decode_ref_cols(terms, n_terms, n_cols, s_rcol);
-    ct_stage(nobs + e0 * d_obs, mine, d_obs, po, tile_o);
-    if (act) ct_stage(act + e0 * A, mine, A, pa, tile_a);
-    __syncthreads();
-
-    const int j = threadIdx.x;
-    if (j >= mine) return;
-    const long e = e0 + j;
-    const int t = (int)(e % H);
-    int n_obs, n_act;
-    ct_ref_rows(clock, t, n_obs, n_act);
-    const T incoming = costs[e];
-    const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa, terminal && t == H - 1,
-                               keep_builtin ? (double)incoming : 0.0,
-                               CtTracked{s_w, s_target, s_rcol, s_flags, ref + (long)n_obs * n_cols, ref + (long)n_act * n_cols});
-    costs[e] = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
-    if (advance) *step = now + 1;       // (n = 1: this lane is the launch's only one behind the barrier)
-}
-
-// cost_terms_batch_kernel with tracked rows: one reference for the batch or one per episode ([E][n_ref][n_cols], the
-// particle's own episode's).  The counter is only read: the batch classes' update launches advance it.
-template <typename T>
-__global__ __launch_bounds__(CT_WG) void cost_terms_track_batch_kernel(
-    const T* __restrict__ nobs, const T* __restrict__ act, const double* __restrict__ terms, int n_terms, long np, long P, int H,
-    int d_obs, int A, int rows, int ppw, int per_episode, int keep_builtin, int terminal, const double* __restrict__ ref,
-    int n_ref, int n_cols, int ref_per_episode, int periodic, const int64_t* __restrict__ step, int64_t bias,
-    T* __restrict__ costs, const double* __restrict__ gseq, double* __restrict__ q0) {
-    extern __shared__ double ct_tile_raw[];
-    __shared__ double s_w[2][CT_MAX_TERMS], s_target[2][CT_MAX_TERMS], s_gc[CT_ROWS];
-    __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS], s_rcol[CT_MAX_TERMS];
-    const int po = ct_pitch(d_obs), pa = act ? ct_pitch(A) : 0;
-    T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
-    T* const tile_a = tile_o + (long)rows * po;
-    const long p0 = (long)blockIdx.x * ppw;
-    const int my_p = np - p0 < ppw ? (int)(np - p0) : ppw;
-    const long e0 = p0 * H;
-    const int my_n = my_p * H;
-    const CtClock clock = ct_clock((long)(*step + bias), n_ref, periodic);
-    // my particles from `second` on belong to the episode after my first particle's (the host keeps ppw <= P whenever
-    // the tables or the references are per episode)
-    int second = my_p;
-    const long ep0 = p0 / P;
-    if ((per_episode || ref_per_episode) && (ep0 + 1) * P - p0 < my_p) second = (int)((ep0 + 1) * P - p0);
-    if (per_episode) {
-        ct_decode_values(terms + ep0 * 8L * n_terms, n_terms, s_w[0], s_target[0]);
-        if (second < my_p) ct_decode_values(terms + (ep0 + 1) * 8L * n_terms, n_terms, s_w[1], s_target[1]);
-    } else {
-        ct_decode_values(terms, n_terms, s_w[0], s_target[0]);
-    }
-    const long ref_len = (long)n_ref * n_cols;
-    const double* const ref0 = ref + (ref_per_episode ? ep0 * ref_len : 0);
-    ct_decode(terms, n_terms, s_kind, s_col, s_flags);
-    ct_decode_ref_cols(terms, n_terms, n_cols, s_rcol);
-    double q = 0.0;
-    const int j = threadIdx.x;
-    for (int c0 = 0; c0 < my_n; c0 += rows) {
-        const int mine = my_n - c0 < rows ? my_n - c0 : rows;
-        ct_stage(nobs + (e0 + c0) * d_obs, mine, d_obs, po, tile_o);
-        if (act) ct_stage(act + (e0 + c0) * A, mine, A, pa, tile_a);
-        __syncthreads();
-        if (j < mine) {
-            const int le = c0 + j, pl = le / H, t = le - pl * H;
-            const double g = gseq ? gseq[t] : 0.0;
-            const T incoming = costs[e0 + le];
-            const int slot = pl >= second;
-            const double* const my_ref = ref0 + (ref_per_episode && slot ? ref_len : 0);
-            int n_obs, n_act;
-            ct_ref_rows(clock, t, n_obs, n_act);
-            const int ws = per_episode ? slot : 0;
-            const double acc = ct_walk(s_kind, s_col, s_flags, n_terms, tile_o + j * po, tile_a + j * pa,
-                                       terminal && t == H - 1, keep_builtin ? (double)incoming : 0.0,
-                                       CtTracked{s_w[ws], s_target[ws], s_rcol, s_flags, my_ref + (long)n_obs * n_cols,
-                                                 my_ref + (long)n_act * n_cols});
-            const T out = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
-            costs[e0 + le] = out;
-            s_gc[j] = g * (double)out;
+// one element's walk over the table: its observation row my_o and action row my_a (LDS), `acc` the first addend.
+// RATE: a CT_RATE row reads the action minus the action of the step before - the tile row in front of my_a (`pa` words), or
+// at the first step of a plan entry `col` of `prev` (through the cache) - and the kinds 4 .. 7 exist.
+template <bool RATE, typename T, typename V>
+__device__ __forceinline__ double ct_walk(const int* s_kind, const int* s_col, const int* s_flags, int n_terms, const T* my_o,
+                                          const T* my_a, bool last_step, double acc, const V values, int pa, bool first_step,
+                                          const double* prev) {
+    double sq = 0.0, w_group = 0.0;
+    for (int k = 0; k < n_terms; ++k) {
+        const int f = s_flags[k], kind = s_kind[k];
+        if ((f & CT_TERMINAL) && !last_step) continue;
+        double v = (double)((f & CT_ACTION) ? my_a[s_col[k]] : my_o[s_col[k]]);
+        if constexpr (RATE) {
+            if (f & CT_RATE) {
+                const int c = s_col[k];
+                if (first_step) {
+                    const double before = prev ? prev[c] : (double)NAN;
+                    v = before == before ? v - before : 0.0;
+                } else {
+                    v -= (double)my_a[c - pa];
+                }
+            }
         }
-        __syncthreads();
-        if (q0 && j < my_p) {
-            const int lo = j * H > c0 ? j * H : c0;
-            const int hi = (j + 1) * H < c0 + mine ? (j + 1) * H : c0 + mine;
-#pragma unroll 4
-            for (int i = lo; i < hi; ++i) q += s_gc[i - c0];
+        const double r = v - values.goal(k);
+        const double w = values.weight(k);
+        if (kind == 0) {
+            acc += w * fabs(r);
+        } else if (kind == 1) {
+            acc += w * (r * r);
+        } else if (kind == 2) {
+            if (f & CT_GROUP_FIRST) { sq = 0.0; w_group = w; }
+            sq += r * r;
+            if (f & CT_GROUP_LAST) acc += w_group * sqrt(sq);
+        } else if (!RATE || kind == 3) {
+            const double s = sin(0.5 * r);
+            acc += w * (2.0 * s * s);
+        } else {
+            const double side = (kind & 1) ? -r : r;                // 5, 7: below the bound
+            const double m = side > 0.0 ? side : 0.0;
+            acc += w * (kind >= 6 ? m * m : m);
         }
     }
-    if (q0 && j < my_p) q0[p0 + j] = fabs(q) < (double)INFINITY ? q : (double)INFINITY;
+    return acc;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// Action-rate rows and one-sided kinds.  A row of source 2 reads u_t - u_{t-1}: the action row of the element
-// before, which may lie in another workgroup's tile.  So a tile (or a batch chunk) of these kernels holds one more action row
-// in front - the row of element e0 - 1 where e0 > 0 - and lane j's action row is tile row j + 1, its previous one tile row j,
-// whatever j is: no lane goes to memory for it.  Only the lanes at t = 0 leave the tile, for the launch's previous-action
-// vector `prev` (float64 [A], through the cache).  TRACK: rows may be tracked as in the kernels above; without it the
-// reference, the counter and their decode are compiled out (measured against the run-time test: profiles/r19_rate.txt).
-
-// stage the action rows of elements [first, first + mine) behind tile row 0, and row first - 1 into it where there is one
-template <typename T>
-__device__ __forceinline__ void ct_stage_actions(const T* __restrict__ act, long first, int mine, int A, int pa, T* tile_a) {
-    if (first > 0) ct_stage(act + (first - 1) * A, mine + 1, A, pa, tile_a);
-    else ct_stage(act, mine, A, pa, tile_a + pa);
-}
-
-// grid: ceil(n / rows) workgroups of CT_WG; dynamic LDS: rows pitch(d_obs) + (rows + 1) pitch(A) words of T.
-// advance (host: only for P = H = 1, one workgroup): the one walking lane stores counter + 1 (TRACK) and its action row
-// into `prev` behind its walk - the lane that read them.
-template <typename T, bool TRACK>
-__global__ __launch_bounds__(CT_WG) void cost_terms_rate_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
+// grid: ceil(n / rows) workgroups of CT_WG; dynamic LDS: ct_tile()'s.
+// advance (host: only for P = H = 1, one workgroup): every lane takes its copy of the counter before the barrier; the one
+// walking lane stores counter + 1 (TRACK) and its action row into `prev` (RATE, with a `prev`) behind its walk - the lane
+// that read them.
+template <typename T, bool TRACK, bool RATE>
+__global__ __launch_bounds__(CT_WG) void cost_terms_flat_kernel(const T* __restrict__ nobs, const T* __restrict__ act,
                                                                 const double* __restrict__ terms, int n_terms, long n, int H,
                                                                 int d_obs, int A, int rows, int keep_builtin, int terminal,
                                                                 const double* __restrict__ ref, int n_ref, int n_cols,
@@ -444,7 +240,7 @@ __global__ __launch_bounds__(CT_WG) void cost_terms_rate_kernel(const T* __restr
     extern __shared__ double ct_tile_raw[];
     __shared__ double s_w[CT_MAX_TERMS], s_target[CT_MAX_TERMS];
     __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS], s_rcol[TRACK ? CT_MAX_TERMS : 1];
-    const int po = ct_pitch(d_obs), pa = ct_pitch(A);
+    const int po = ct_pitch(d_obs), pa = (RATE || act) ? ct_pitch(A) : 0;
     T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
     T* const tile_a = tile_o + (long)rows * po;
     const long e0 = (long)blockIdx.x * rows;
@@ -456,47 +252,60 @@ __global__ __launch_bounds__(CT_WG) void cost_terms_rate_kernel(const T* __restr
         clock = ct_clock((long)(now + bias), n_ref, periodic);
         ct_decode_ref_cols(terms, n_terms, n_cols, s_rcol);
     }
-    ct_decode<true>(terms, n_terms, s_kind, s_col, s_flags);
+    ct_decode<RATE>(terms, n_terms, s_kind, s_col, s_flags);
     ct_decode_values(terms, n_terms, s_w, s_target);
     ct_stage(nobs + e0 * d_obs, mine, d_obs, po, tile_o);
-    ct_stage_actions(act, e0, mine, A, pa, tile_a);
+    if constexpr (RATE) ct_stage_actions(act, e0, mine, A, pa, tile_a);
+    else if (act) ct_stage(act + e0 * A, mine, A, pa, tile_a);
     __syncthreads();
 
     const int j = threadIdx.x;
     if (j >= mine) return;
     const long e = e0 + j;
-    const int t = (int)(e % H);
+    const int t = (TRACK || RATE || terminal) ? (int)(e % H) : 0;   // (a 64-bit remainder: not paid where nothing reads t)
     const T* const my_o = tile_o + j * po;
-    const T* const my_a = tile_a + (j + 1) * pa;
+    const T* const my_a = tile_a + (j + RATE) * pa;
     const T incoming = costs[e];
     const double first = keep_builtin ? (double)incoming : 0.0;
     double acc;
     if constexpr (TRACK) {
         int n_obs, n_act;
         ct_ref_rows(clock, t, n_obs, n_act);
-        acc = ct_walk<true>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
+        acc = ct_walk<RATE>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
                             CtTracked{s_w, s_target, s_rcol, s_flags, ref + (long)n_obs * n_cols, ref + (long)n_act * n_cols},
                             pa, t == 0, prev);
     } else {
-        acc = ct_walk<true>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
+        acc = ct_walk<RATE>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
                             CtArrays{s_w, s_target}, pa, t == 0, prev);
     }
     costs[e] = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
     if (advance) {                      // (n = 1: this lane is the launch's only one behind the barrier)
         if constexpr (TRACK) *step = now + 1;
-        if (prev)
-            for (int c = 0; c < A; ++c) prev[c] = (double)my_a[c];
+        if constexpr (RATE) {
+            if (prev)
+                for (int c = 0; c < A; ++c) prev[c] = (double)my_a[c];
+        }
     }
 }
 
-// The episode batches' launch with rate rows and one-sided kinds: cost_terms_track_batch_kernel's shape, every chunk with
-// the action row in front of it (element e0 + c0 - 1).  `prev` is [E][A], the lane's own episode's row by the `slot` that
-// picks its weights; advance_prev (host: only for P = H = 1, so a workgroup is one element): the element of episode e
-// stores its action row into row e behind its walk.  The counter is only read.
-// (waves_per_eu 5: left alone the tracked instantiations take 99 - 100 VGPRs, one allocation step past the five waves per
-// SIMD of the kernels above; held to five they take 95, with no spill to scratch)
-template <typename T, bool TRACK>
-__global__ __launch_bounds__(CT_WG) __attribute__((amdgpu_waves_per_eu(5))) void cost_terms_rate_batch_kernel(
+// The episode batches' launch (DESIGN 10.8): the costs of E P particles, [E P][H], with one table for all or one per episode
+// (the structural columns are episode 0's; weight and target the particle's own episode's), and in the same launch the
+// discounted cost-to-go q0[p] = sum_t gseq[t] cost[p][t] of the costs as stored, forward, every product and sum rounded.
+// A workgroup owns `ppw` whole particles - as many as fit the tile's `rows` elements, one if H is longer, and no more than an
+// episode holds where anything is per episode - and takes their ppw H elements in chunks of `rows`: stage (RATE: every chunk
+// with the action row in front of it), walk (lane j = element j of the chunk), store the cost and leave gseq[t] cost in LDS,
+// then thread s < ppw carries particle s's sum on over the chunk's elements of that particle.  So a particle's costs meet in
+// one thread whatever H is, the products are formed by all lanes and only the additions are serial, and the observations are
+// read once.  ppw <= P consecutive particles cross at most one episode boundary: two sets of weights and targets are decoded
+// into LDS and a lane picks its episode's by its `slot`, as it picks its reference ([E][n_ref][n_cols] with ref_per_episode)
+// and its row of `prev` ([E][A]).  The counter is only read: the batch classes' update launches advance it.
+// advance_prev (host: only for P = H = 1, so a workgroup is one element): the element of episode e stores its action row into
+// row e of `prev` behind its walk.
+// grid: ceil(E P / ppw) workgroups of CT_WG; dynamic LDS as cost_terms_flat_kernel's
+// (waves_per_eu 5: left alone the tracked instantiations take 97 - 100 VGPRs, one allocation step past the five waves per SIMD
+// of the others; held to five they take 94 - 95, with no spill to scratch: profiles/r20_cost_terms_unify_resources.txt)
+template <typename T, bool TRACK, bool RATE>
+__global__ __launch_bounds__(CT_WG) __attribute__((amdgpu_waves_per_eu(5))) void cost_terms_batch_kernel(
     const T* __restrict__ nobs, const T* __restrict__ act, const double* __restrict__ terms, int n_terms, long np, long P, int H,
     int d_obs, int A, int rows, int ppw, int per_episode, int keep_builtin, int terminal, const double* __restrict__ ref,
     int n_ref, int n_cols, int ref_per_episode, int periodic, const int64_t* __restrict__ step, int64_t bias, double* prev,
@@ -504,71 +313,81 @@ __global__ __launch_bounds__(CT_WG) __attribute__((amdgpu_waves_per_eu(5))) void
     extern __shared__ double ct_tile_raw[];
     __shared__ double s_w[2][CT_MAX_TERMS], s_target[2][CT_MAX_TERMS], s_gc[CT_ROWS];
     __shared__ int s_kind[CT_MAX_TERMS], s_col[CT_MAX_TERMS], s_flags[CT_MAX_TERMS], s_rcol[TRACK ? CT_MAX_TERMS : 1];
-    const int po = ct_pitch(d_obs), pa = ct_pitch(A);
+    const int po = ct_pitch(d_obs), pa = (RATE || act) ? ct_pitch(A) : 0;
     T* const tile_o = reinterpret_cast<T*>(ct_tile_raw);
     T* const tile_a = tile_o + (long)rows * po;
-    const long p0 = (long)blockIdx.x * ppw;
-    const int my_p = np - p0 < ppw ? (int)(np - p0) : ppw;
+    const long p0 = (long)blockIdx.x * ppw;                         // my first particle
+    const int my_p = np - p0 < ppw ? (int)(np - p0) : ppw;          // my particles
     const long e0 = p0 * H;
-    const int my_n = my_p * H;
+    const int my_n = my_p * H;                                      // my elements (ppw > 1 only where ppw H <= rows)
     CtClock clock{0, 1, 0};
     if constexpr (TRACK) {
         clock = ct_clock((long)(*step + bias), n_ref, periodic);
         ct_decode_ref_cols(terms, n_terms, n_cols, s_rcol);
     }
-    // my particles from `second` on belong to the episode after my first particle's (the host keeps ppw <= P whenever the
-    // tables, the references or the previous actions are per episode)
+    // my first particle's episode, ep0, and the first of my particles that belongs to the episode after it, `second`: looked
+    // for only where the tables, the references or the previous actions are per episode (the host keeps ppw <= P there).
+    // (One table for all goes straight to its decode: with the split in front of this `if` the launch measured 3 % slower.)
+    long ep0 = 0;
     int second = my_p;
-    const long ep0 = p0 / P;
-    if ((per_episode || ref_per_episode || prev) && (ep0 + 1) * P - p0 < my_p) second = (int)((ep0 + 1) * P - p0);
+    auto split = [&] {
+        ep0 = p0 / P;
+        if ((ep0 + 1) * P - p0 < my_p) second = (int)((ep0 + 1) * P - p0);
+    };
     if (per_episode) {
+        split();
         ct_decode_values(terms + ep0 * 8L * n_terms, n_terms, s_w[0], s_target[0]);
         if (second < my_p) ct_decode_values(terms + (ep0 + 1) * 8L * n_terms, n_terms, s_w[1], s_target[1]);
     } else {
+        if ((TRACK && ref_per_episode) || (RATE && prev)) split();
         ct_decode_values(terms, n_terms, s_w[0], s_target[0]);
     }
     const long ref_len = (long)n_ref * n_cols;
     const double* const ref0 = TRACK ? ref + (ref_per_episode ? ep0 * ref_len : 0) : nullptr;
-    double* const prev0 = prev ? prev + ep0 * A : nullptr;
-    ct_decode<true>(terms, n_terms, s_kind, s_col, s_flags);
-    double q = 0.0;
+    double* const prev0 = RATE && prev ? prev + ep0 * A : nullptr;
+    ct_decode<RATE>(terms, n_terms, s_kind, s_col, s_flags);
+    double q = 0.0;                                                 // thread s < my_p: particle p0 + s's sum so far
     const int j = threadIdx.x;
     for (int c0 = 0; c0 < my_n; c0 += rows) {
         const int mine = my_n - c0 < rows ? my_n - c0 : rows;
         ct_stage(nobs + (e0 + c0) * d_obs, mine, d_obs, po, tile_o);
-        ct_stage_actions(act, e0 + c0, mine, A, pa, tile_a);
+        if constexpr (RATE) ct_stage_actions(act, e0 + c0, mine, A, pa, tile_a);
+        else if (act) ct_stage(act + (e0 + c0) * A, mine, A, pa, tile_a);
         __syncthreads();
         if (j < mine) {
-            const int le = c0 + j, pl = le / H, t = le - pl * H;
+            const int le = c0 + j, pl = le / H, t = le - pl * H;    // my element: particle pl of the workgroup's, step t
             const double g = gseq ? gseq[t] : 0.0;
             const T incoming = costs[e0 + le];
             const int slot = pl >= second;
             const int ws = per_episode ? slot : 0;
             double* const my_prev = prev0 ? prev0 + (slot ? A : 0) : nullptr;
             const T* const my_o = tile_o + j * po;
-            const T* const my_a = tile_a + (j + 1) * pa;
+            const T* const my_a = tile_a + (j + RATE) * pa;
             const double first = keep_builtin ? (double)incoming : 0.0;
             double acc;
             if constexpr (TRACK) {
                 const double* const my_ref = ref0 + (ref_per_episode && slot ? ref_len : 0);
                 int n_obs, n_act;
                 ct_ref_rows(clock, t, n_obs, n_act);
-                acc = ct_walk<true>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
+                acc = ct_walk<RATE>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
                                     CtTracked{s_w[ws], s_target[ws], s_rcol, s_flags, my_ref + (long)n_obs * n_cols,
                                               my_ref + (long)n_act * n_cols},
                                     pa, t == 0, my_prev);
             } else {
-                acc = ct_walk<true>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
+                acc = ct_walk<RATE>(s_kind, s_col, s_flags, n_terms, my_o, my_a, terminal && t == H - 1, first,
                                     CtArrays{s_w[ws], s_target[ws]}, pa, t == 0, my_prev);
             }
             const T out = fabs((double)incoming) < (double)INFINITY ? (T)acc : (T)INFINITY;
             costs[e0 + le] = out;
             s_gc[j] = g * (double)out;
-            if (advance_prev && my_prev)        // (P = H = 1: this lane is its workgroup's only one)
-                for (int c = 0; c < A; ++c) my_prev[c] = (double)my_a[c];
+            if constexpr (RATE) {
+                if (advance_prev && my_prev)        // (P = H = 1: this lane is its workgroup's only one)
+                    for (int c = 0; c < A; ++c) my_prev[c] = (double)my_a[c];
+            }
         }
         __syncthreads();
         if (q0 && j < my_p) {
+            // my particle's elements are [j H, (j + 1) H) of the workgroup's; this chunk holds [c0, c0 + mine)
             const int lo = j * H > c0 ? j * H : c0;
             const int hi = (j + 1) * H < c0 + mine ? (j + 1) * H : c0 + mine;
 #pragma unroll 4
@@ -578,177 +397,190 @@ __global__ __launch_bounds__(CT_WG) __attribute__((amdgpu_waves_per_eu(5))) void
     if (q0 && j < my_p) q0[p0 + j] = fabs(q) < (double)INFINITY ? q : (double)INFINITY;
 }
 
-int bad(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms", detail); }
+// ---- the host side: one tile sizing, one launch per kernel template, one check per concern ---------------------------------
 
-template <typename T>
-int launch(int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions, const double* d_terms,
-           int n_terms, int keep_builtin, int terminal, void* d_costs, void* stream) {
-    const long n = (long)P * H;
-    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
-    if (row_bytes > CT_LDS_BYTES) return bad("an observation and action row of more than 60 KiB");
-    int rows = CT_ROWS;
-    while (rows * row_bytes > CT_LDS_BYTES) rows >>= 1;
-    const long blocks = (n + rows - 1) / rows;
-    if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
-    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
-    hipLaunchKernelGGL(cost_terms_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
-                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, n, H, d_obs, A, rows, keep_builtin,
-                       terminal, (T*)d_costs);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms", hipGetErrorString(e));
-}
+int bad(const char* entry, const char* detail) { return set_error(MJMPC_E_BADARG, entry, detail); }
 
-int bad_batch(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_batch", detail); }
+// the tile inside `budget` bytes: `rows` observation rows of `word` bytes a word, as many action rows where the launch has
+// actions, and one more in front of those for a rate kernel; rows = 0: one row does not fit
+struct CtTile {
+    int rows;
+    size_t lds;
+};
 
-template <typename T>
-int launch_batch(int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
-                 const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal, void* d_costs,
-                 const double* d_gseq, double* d_q0, void* stream) {
-    const long np = (long)E * P;
-    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
-    if (row_bytes > CT_BATCH_LDS_BYTES) return bad_batch("an observation and action row of more than 56 KiB");
-    int rows = CT_ROWS;
-    while (rows * row_bytes > CT_BATCH_LDS_BYTES) rows >>= 1;
-    int ppw = H >= rows ? 1 : rows / H;             // whole particles per workgroup ...
-    if (per_episode && ppw > P) ppw = (int)P;       // ... of at most two episodes
-    const long blocks = (np + ppw - 1) / ppw;
-    if (blocks > INT32_MAX) return bad_batch("more than 2^31 workgroups");
-    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
-    hipLaunchKernelGGL(cost_terms_batch_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
-                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, np, (long)P, H, d_obs, A, rows, ppw,
-                       per_episode, keep_builtin, terminal, (T*)d_costs, d_gseq, d_q0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_batch", hipGetErrorString(e));
-}
-
-int bad_track(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_track", detail); }
-
-template <typename T>
-int launch_track(int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions, const double* d_terms,
-                 int n_terms, int keep_builtin, int terminal, const double* d_ref, int n_ref, int n_cols, int periodic,
-                 int64_t* d_step, int64_t step_bias, int advance, void* d_costs, void* stream) {
-    const long n = (long)P * H;
-    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
-    if (row_bytes > CT_LDS_BYTES) return bad_track("an observation and action row of more than 60 KiB");
-    int rows = CT_ROWS;
-    while (rows * row_bytes > CT_LDS_BYTES) rows >>= 1;
-    const long blocks = (n + rows - 1) / rows;
-    if (blocks > INT32_MAX) return bad_track("more than 2^31 workgroups");
-    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
-    hipLaunchKernelGGL(cost_terms_track_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
-                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, n, H, d_obs, A, rows, keep_builtin,
-                       terminal, d_ref, n_ref, n_cols, periodic, d_step, step_bias, advance, (T*)d_costs);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_track", hipGetErrorString(e));
-}
-
-int bad_track_batch(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_track_batch", detail); }
-
-template <typename T>
-int launch_track_batch(int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
-                       const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal,
-                       const double* d_ref, int n_ref, int n_cols, int ref_per_episode, int periodic, const int64_t* d_step,
-                       int64_t step_bias, void* d_costs, const double* d_gseq, double* d_q0, void* stream) {
-    const long np = (long)E * P;
-    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + (d_actions ? ct_pitch(A) : 0));
-    if (row_bytes > CT_BATCH_LDS_BYTES) return bad_track_batch("an observation and action row of more than 56 KiB");
-    int rows = CT_ROWS;
-    while (rows * row_bytes > CT_BATCH_LDS_BYTES) rows >>= 1;
-    int ppw = H >= rows ? 1 : rows / H;                                     // whole particles per workgroup ...
-    if ((per_episode || ref_per_episode) && ppw > P) ppw = (int)P;          // ... of at most two episodes
-    const long blocks = (np + ppw - 1) / ppw;
-    if (blocks > INT32_MAX) return bad_track_batch("more than 2^31 workgroups");
-    const size_t lds = (size_t)((rows * row_bytes + 7) / 8 * 8);
-    hipLaunchKernelGGL(cost_terms_track_batch_kernel<T>, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream,
-                       (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, np, (long)P, H, d_obs, A, rows, ppw,
-                       per_episode, keep_builtin, terminal, d_ref, n_ref, n_cols, ref_per_episode, periodic, d_step, step_bias,
-                       (T*)d_costs, d_gseq, d_q0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_track_batch", hipGetErrorString(e));
-}
-
-int bad_rate(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_rate", detail); }
-
-// the tile of the rate kernels: `rows` observation rows and rows + 1 action rows inside `budget` bytes -> rows, 0 if one does not fit
-template <typename T>
-int rate_rows(int d_obs, int A, long budget, size_t* lds) {
-    const long row_bytes = (long)sizeof(T) * (ct_pitch(d_obs) + ct_pitch(A)), extra = (long)sizeof(T) * ct_pitch(A);
-    if (row_bytes + extra > budget) return 0;
+CtTile ct_tile(long word, int d_obs, int A, bool actions, bool leading_row, long budget) {
+    const long row_bytes = word * (ct_pitch(d_obs) + (actions ? ct_pitch(A) : 0)), extra = leading_row ? word * ct_pitch(A) : 0;
+    if (row_bytes + extra > budget) return CtTile{0, 0};
     int rows = CT_ROWS;
     while (rows * row_bytes + extra > budget) rows >>= 1;
-    *lds = (size_t)((rows * row_bytes + extra + 7) / 8 * 8);
-    return rows;
+    return CtTile{rows, (size_t)((rows * row_bytes + extra + 7) / 8 * 8)};
 }
 
-template <typename T>
-int launch_rate(int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions, const double* d_terms,
-                int n_terms, int keep_builtin, int terminal, const double* d_ref, int n_ref, int n_cols, int periodic,
-                int64_t* d_step, int64_t step_bias, int advance, double* d_prev, void* d_costs, void* stream) {
+// a launch of `blocks` workgroups in the storage type of `dtype`: `launch(zero of T)` issues it
+template <typename Launch>
+int ct_dispatch(const char* entry, long blocks, int dtype, Launch launch) {
+    if (blocks > INT32_MAX) return bad(entry, "more than 2^31 workgroups");
+    if (dtype == MJMPC_F32) launch(0.0f);
+    else launch(0.0);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, entry, hipGetErrorString(e));
+}
+
+// the flat entries: `rate` names the two with the leading action row; d_ref, d_step and d_prev may be null
+int launch_flat(const char* entry, bool rate, int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                const void* d_actions, const double* d_terms, int n_terms, int keep_builtin, int terminal, const double* d_ref,
+                int64_t n_ref, int n_cols, int periodic, int64_t* d_step, int64_t step_bias, int advance, double* d_prev,
+                void* d_costs, void* stream) {
     const long n = (long)P * H;
-    size_t lds = 0;
-    const int rows = rate_rows<T>(d_obs, A, CT_LDS_BYTES, &lds);
-    if (!rows) return bad_rate("an observation row and two action rows of more than 60 KiB");
-    const long blocks = (n + rows - 1) / rows;
-    if (blocks > INT32_MAX) return bad_rate("more than 2^31 workgroups");
-    auto* const kernel = d_ref ? cost_terms_rate_kernel<T, true> : cost_terms_rate_kernel<T, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream, (const T*)d_next_obs,
-                       (const T*)d_actions, d_terms, n_terms, n, H, d_obs, A, rows, keep_builtin, terminal, d_ref, n_ref,
-                       n_cols, periodic, d_step, step_bias, advance, d_prev, (T*)d_costs);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_rate", hipGetErrorString(e));
+    const CtTile tile = ct_tile(dtype == MJMPC_F32 ? 4 : 8, d_obs, A, d_actions != nullptr, rate, CT_LDS_BYTES);
+    if (!tile.rows)
+        return bad(entry, rate ? "an observation row and two action rows of more than 60 KiB"
+                               : "an observation and action row of more than 60 KiB");
+    if (!d_ref) n_ref = n_cols = 1;
+    const long blocks = (n + tile.rows - 1) / tile.rows;
+    return ct_dispatch(entry, blocks, dtype, [&](auto zero) {
+        using T = decltype(zero);
+        auto* const kernel = rate ? (d_ref ? cost_terms_flat_kernel<T, true, true> : cost_terms_flat_kernel<T, false, true>)
+                                  : (d_ref ? cost_terms_flat_kernel<T, true, false> : cost_terms_flat_kernel<T, false, false>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CT_WG), tile.lds, (hipStream_t)stream,
+                           (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, n, H, d_obs, A, tile.rows, keep_builtin,
+                           terminal, d_ref, (int)n_ref, n_cols, periodic != 0, d_step, step_bias, advance != 0, d_prev,
+                           (T*)d_costs);
+    });
 }
 
-int bad_rate_batch(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_cost_terms_rate_batch", detail); }
-
-template <typename T>
-int launch_rate_batch(int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
-                      const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal,
-                      const double* d_ref, int n_ref, int n_cols, int ref_per_episode, int periodic, const int64_t* d_step,
-                      int64_t step_bias, double* d_prev, int advance_prev, void* d_costs, const double* d_gseq, double* d_q0,
-                      void* stream) {
+// the batch entries.  ppw: whole particles per workgroup, of at most two episodes
+int launch_batch(const char* entry, bool rate, int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                 const void* d_actions, const double* d_terms, int n_terms, int per_episode, int keep_builtin, int terminal,
+                 const double* d_ref, int64_t n_ref, int n_cols, int ref_per_episode, int periodic, const int64_t* d_step,
+                 int64_t step_bias, double* d_prev, int advance_prev, void* d_costs, const double* d_gseq, double* d_q0,
+                 void* stream) {
     const long np = (long)E * P;
-    size_t lds = 0;
-    const int rows = rate_rows<T>(d_obs, A, CT_BATCH_LDS_BYTES, &lds);
-    if (!rows) return bad_rate_batch("an observation row and two action rows of more than 56 KiB");
-    int ppw = H >= rows ? 1 : rows / H;                                             // whole particles per workgroup ...
-    if ((per_episode || ref_per_episode || d_prev) && ppw > P) ppw = (int)P;        // ... of at most two episodes
+    const CtTile tile = ct_tile(dtype == MJMPC_F32 ? 4 : 8, d_obs, A, d_actions != nullptr, rate, CT_BATCH_LDS_BYTES);
+    if (!tile.rows)
+        return bad(entry, rate ? "an observation row and two action rows of more than 56 KiB"
+                               : "an observation and action row of more than 56 KiB");
+    if (!d_ref) { n_ref = n_cols = 1; ref_per_episode = 0; }
+    int ppw = H >= tile.rows ? 1 : tile.rows / H;
+    if ((per_episode || ref_per_episode || d_prev) && ppw > P) ppw = (int)P;
     const long blocks = (np + ppw - 1) / ppw;
-    if (blocks > INT32_MAX) return bad_rate_batch("more than 2^31 workgroups");
-    auto* const kernel = d_ref ? cost_terms_rate_batch_kernel<T, true> : cost_terms_rate_batch_kernel<T, false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CT_WG), lds, (hipStream_t)stream, (const T*)d_next_obs,
-                       (const T*)d_actions, d_terms, n_terms, np, (long)P, H, d_obs, A, rows, ppw, per_episode, keep_builtin,
-                       terminal, d_ref, n_ref, n_cols, ref_per_episode, periodic, d_step, step_bias, d_prev, advance_prev,
-                       (T*)d_costs, d_gseq, d_q0);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_cost_terms_rate_batch", hipGetErrorString(e));
+    return ct_dispatch(entry, blocks, dtype, [&](auto zero) {
+        using T = decltype(zero);
+        auto* const kernel = rate ? (d_ref ? cost_terms_batch_kernel<T, true, true> : cost_terms_batch_kernel<T, false, true>)
+                                  : (d_ref ? cost_terms_batch_kernel<T, true, false> : cost_terms_batch_kernel<T, false, false>);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(CT_WG), tile.lds, (hipStream_t)stream,
+                           (const T*)d_next_obs, (const T*)d_actions, d_terms, n_terms, np, (long)P, H, d_obs, A, tile.rows, ppw,
+                           per_episode != 0, keep_builtin, terminal, d_ref, (int)n_ref, n_cols, ref_per_episode != 0,
+                           periodic != 0, d_step, step_bias, d_prev, advance_prev != 0, (T*)d_costs, d_gseq, d_q0);
+    });
 }
+
+// The argument checks, one per concern: each returns its refusal or null.  An entry lists the ones that apply to it in its
+// own order, with its own wording where the rule is its own, and refuses with the first that is not null.
+const char* ct_first(std::initializer_list<const char*> refusals) {
+    for (const char* r : refusals)
+        if (r) return r;
+    return nullptr;
+}
+
+const char* ct_not_null(bool all_given) { return all_given ? nullptr : "null argument"; }
+
+const char* ct_together(const void* a, const void* b, const char* refusal) { return (a != nullptr) == (b != nullptr) ? nullptr : refusal; }
+
+// every size at least 1, A at least min_A (`needs`: the entry's sentence), no action pointer with A = 0, E P <= 2^40
+const char* ct_sizes(int E, int64_t P, int H, int d_obs, int A, int min_A, const void* d_actions, const char* needs) {
+    if (E < 1 || P < 1 || H < 1 || d_obs < 1 || A < min_A) return needs;
+    if (P > ((int64_t)1 << 40) / E) return "more than 2^40 particles";
+    return d_actions && A < 1 ? "actions of width 0" : nullptr;
+}
+
+const char* ct_n_terms(int n_terms) { return n_terms < 1 || n_terms > CT_MAX_TERMS ? "n_terms must be 1 .. 128" : nullptr; }
+
+const char* ct_dtype(int dtype) { return dtype != MJMPC_F32 && dtype != MJMPC_F64 ? "dtype must be MJMPC_F32 or MJMPC_F64" : nullptr; }
+
+const char* ct_reference(const double* d_ref, int64_t n_ref, int n_cols) {
+    if (d_ref && (n_ref < 1 || n_ref > CT_MAX_REF_ROWS)) return "n_ref must be 1 .. 2^20";
+    return d_ref && (n_cols < 1 || n_cols > CT_MAX_TERMS) ? "n_cols must be 1 .. 128" : nullptr;
+}
+
+const char* ct_advance(int advance, int64_t P, int H, const char* refusal) { return advance && (P != 1 || H != 1) ? refusal : nullptr; }
 
 }  // namespace
 }  // namespace mjmpc
+
+using namespace mjmpc;
+
+extern "C" int mjmpc_cost_terms(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                                const double* d_terms, int n_terms, int keep_builtin, int terminal, void* d_costs,
+                                void* stream) {
+    const char* const entry = "mjmpc_cost_terms";
+    const char* const refusal = ct_first({ct_not_null(d_next_obs && d_terms && d_costs),
+                                          ct_sizes(1, P, H, d_obs, A, 0, d_actions, "needs P >= 1, H >= 1, d_obs >= 1 and A >= 0"),
+                                          ct_n_terms(n_terms), ct_dtype(dtype)});
+    if (refusal) return bad(entry, refusal);
+    return launch_flat(entry, false, dtype, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal,
+                       nullptr, 0, 0, 0, nullptr, 0, 0, nullptr, d_costs, stream);
+}
+
+extern "C" int mjmpc_cost_terms_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                      const void* d_actions, const double* d_terms, int n_terms, int per_episode,
+                                      int keep_builtin, int terminal, void* d_costs, const double* d_gseq, double* d_q0,
+                                      void* stream) {
+    const char* const entry = "mjmpc_cost_terms_batch";
+    const char* const refusal =
+        ct_first({ct_not_null(d_next_obs && d_terms && d_costs),
+                  ct_sizes(E, P, H, d_obs, A, 0, d_actions, "needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 0"),
+                  ct_n_terms(n_terms), ct_dtype(dtype), ct_together(d_gseq, d_q0, "d_gseq and d_q0 go together")});
+    if (refusal) return bad(entry, refusal);
+    return launch_batch(entry, false, dtype, E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode,
+                        keep_builtin, terminal, nullptr, 0, 0, 0, 0, nullptr, 0, nullptr, 0, d_costs, d_gseq, d_q0, stream);
+}
+
+extern "C" int mjmpc_cost_terms_track(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                      const void* d_actions, const double* d_terms, int n_terms, int keep_builtin, int terminal,
+                                      const double* d_ref, int64_t n_ref, int n_cols, int periodic, int64_t* d_step,
+                                      int64_t step_bias, int advance, void* d_costs, void* stream) {
+    const char* const entry = "mjmpc_cost_terms_track";
+    const char* const refusal =
+        ct_first({ct_not_null(d_next_obs && d_terms && d_costs && d_ref && d_step),
+                  ct_sizes(1, P, H, d_obs, A, 0, d_actions, "needs P >= 1, H >= 1, d_obs >= 1 and A >= 0"), ct_n_terms(n_terms),
+                  ct_dtype(dtype), ct_reference(d_ref, n_ref, n_cols),
+                  ct_advance(advance, P, H, "advance needs P = H = 1 (one workgroup owns the counter)")});
+    if (refusal) return bad(entry, refusal);
+    return launch_flat(entry, false, dtype, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal,
+                       d_ref, n_ref, n_cols, periodic, d_step, step_bias, advance, nullptr, d_costs, stream);
+}
+
+extern "C" int mjmpc_cost_terms_track_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                            const void* d_actions, const double* d_terms, int n_terms, int per_episode,
+                                            int keep_builtin, int terminal, const double* d_ref, int64_t n_ref, int n_cols,
+                                            int ref_per_episode, int periodic, const int64_t* d_step, int64_t step_bias,
+                                            void* d_costs, const double* d_gseq, double* d_q0, void* stream) {
+    const char* const entry = "mjmpc_cost_terms_track_batch";
+    const char* const refusal =
+        ct_first({ct_not_null(d_next_obs && d_terms && d_costs && d_ref && d_step),
+                  ct_sizes(E, P, H, d_obs, A, 0, d_actions, "needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 0"),
+                  ct_n_terms(n_terms), ct_dtype(dtype), ct_together(d_gseq, d_q0, "d_gseq and d_q0 go together"),
+                  ct_reference(d_ref, n_ref, n_cols)});
+    if (refusal) return bad(entry, refusal);
+    return launch_batch(entry, false, dtype, E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode,
+                        keep_builtin, terminal, d_ref, n_ref, n_cols, ref_per_episode, periodic, d_step, step_bias, nullptr, 0,
+                        d_costs, d_gseq, d_q0, stream);
+}
 
 extern "C" int mjmpc_cost_terms_rate(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
                                      const void* d_actions, const double* d_terms, int n_terms, int keep_builtin, int terminal,
                                      const double* d_ref, int64_t n_ref, int n_cols, int periodic, int64_t* d_step,
                                      int64_t step_bias, int advance, double* d_prev_action, void* d_costs, void* stream) {
-    using mjmpc::bad_rate;
-    if (!d_next_obs || !d_actions || !d_terms || !d_costs) return bad_rate("null argument");
-    if ((d_ref != nullptr) != (d_step != nullptr)) return bad_rate("d_ref and d_step go together");
-    if (P < 1 || H < 1 || d_obs < 1 || A < 1) return bad_rate("needs P >= 1, H >= 1, d_obs >= 1 and A >= 1");
-    if (P > ((int64_t)1 << 40)) return bad_rate("more than 2^40 particles");
-    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_rate("n_terms must be 1 .. 128");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_rate("dtype must be MJMPC_F32 or MJMPC_F64");
-    if (d_ref && (n_ref < 1 || n_ref > mjmpc::CT_MAX_REF_ROWS)) return bad_rate("n_ref must be 1 .. 2^20");
-    if (d_ref && (n_cols < 1 || n_cols > mjmpc::CT_MAX_TERMS)) return bad_rate("n_cols must be 1 .. 128");
-    if (advance && (P != 1 || H != 1))
-        return bad_rate("advance needs P = H = 1 (one workgroup owns the counter and the previous action)");
-    if (!d_ref) n_ref = n_cols = 1;
-    if (dtype == MJMPC_F32)
-        return mjmpc::launch_rate<float>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_ref,
-                                         (int)n_ref, n_cols, periodic != 0, d_step, step_bias, advance != 0, d_prev_action,
-                                         d_costs, stream);
-    return mjmpc::launch_rate<double>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_ref,
-                                      (int)n_ref, n_cols, periodic != 0, d_step, step_bias, advance != 0, d_prev_action, d_costs,
-                                      stream);
+    const char* const entry = "mjmpc_cost_terms_rate";
+    const char* const refusal = ct_first(
+        {ct_not_null(d_next_obs && d_actions && d_terms && d_costs), ct_together(d_ref, d_step, "d_ref and d_step go together"),
+         ct_sizes(1, P, H, d_obs, A, 1, d_actions, "needs P >= 1, H >= 1, d_obs >= 1 and A >= 1"), ct_n_terms(n_terms),
+         ct_dtype(dtype), ct_reference(d_ref, n_ref, n_cols),
+         ct_advance(advance, P, H, "advance needs P = H = 1 (one workgroup owns the counter and the previous action)")});
+    if (refusal) return bad(entry, refusal);
+    return launch_flat(entry, true, dtype, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal,
+                       d_ref, n_ref, n_cols, periodic, d_step, step_bias, advance, d_prev_action, d_costs, stream);
 }
 
 extern "C" int mjmpc_cost_terms_rate_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
@@ -757,109 +589,14 @@ extern "C" int mjmpc_cost_terms_rate_batch(int dtype, int E, int64_t P, int H, i
                                            int ref_per_episode, int periodic, const int64_t* d_step, int64_t step_bias,
                                            double* d_prev_actions, int advance_prev, void* d_costs, const double* d_gseq,
                                            double* d_q0, void* stream) {
-    using mjmpc::bad_rate_batch;
-    if (!d_next_obs || !d_actions || !d_terms || !d_costs) return bad_rate_batch("null argument");
-    if ((d_ref != nullptr) != (d_step != nullptr)) return bad_rate_batch("d_ref and d_step go together");
-    if (E < 1 || P < 1 || H < 1 || d_obs < 1 || A < 1)
-        return bad_rate_batch("needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 1");
-    if (P > ((int64_t)1 << 40) / E) return bad_rate_batch("more than 2^40 particles");
-    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_rate_batch("n_terms must be 1 .. 128");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_rate_batch("dtype must be MJMPC_F32 or MJMPC_F64");
-    if ((d_gseq != nullptr) != (d_q0 != nullptr)) return bad_rate_batch("d_gseq and d_q0 go together");
-    if (d_ref && (n_ref < 1 || n_ref > mjmpc::CT_MAX_REF_ROWS)) return bad_rate_batch("n_ref must be 1 .. 2^20");
-    if (d_ref && (n_cols < 1 || n_cols > mjmpc::CT_MAX_TERMS)) return bad_rate_batch("n_cols must be 1 .. 128");
-    if (advance_prev && (P != 1 || H != 1))
-        return bad_rate_batch("advance_prev needs P = H = 1 (one workgroup per episode owns its previous action)");
-    if (!d_ref) { n_ref = n_cols = 1; ref_per_episode = 0; }
-    if (dtype == MJMPC_F32)
-        return mjmpc::launch_rate_batch<float>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
-                                               keep_builtin, terminal, d_ref, (int)n_ref, n_cols, ref_per_episode != 0,
-                                               periodic != 0, d_step, step_bias, d_prev_actions, advance_prev != 0, d_costs,
-                                               d_gseq, d_q0, stream);
-    return mjmpc::launch_rate_batch<double>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
-                                            keep_builtin, terminal, d_ref, (int)n_ref, n_cols, ref_per_episode != 0,
-                                            periodic != 0, d_step, step_bias, d_prev_actions, advance_prev != 0, d_costs,
-                                            d_gseq, d_q0, stream);
-}
-
-extern "C" int mjmpc_cost_terms_track(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
-                                      const void* d_actions, const double* d_terms, int n_terms, int keep_builtin, int terminal,
-                                      const double* d_ref, int64_t n_ref, int n_cols, int periodic, int64_t* d_step,
-                                      int64_t step_bias, int advance, void* d_costs, void* stream) {
-    using mjmpc::bad_track;
-    if (!d_next_obs || !d_terms || !d_costs || !d_ref || !d_step) return bad_track("null argument");
-    if (P < 1 || H < 1 || d_obs < 1 || A < 0) return bad_track("needs P >= 1, H >= 1, d_obs >= 1 and A >= 0");
-    if (P > ((int64_t)1 << 40)) return bad_track("more than 2^40 particles");
-    if (d_actions && A < 1) return bad_track("actions of width 0");
-    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_track("n_terms must be 1 .. 128");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_track("dtype must be MJMPC_F32 or MJMPC_F64");
-    if (n_ref < 1 || n_ref > mjmpc::CT_MAX_REF_ROWS) return bad_track("n_ref must be 1 .. 2^20");
-    if (n_cols < 1 || n_cols > mjmpc::CT_MAX_TERMS) return bad_track("n_cols must be 1 .. 128");
-    if (advance && (P != 1 || H != 1)) return bad_track("advance needs P = H = 1 (one workgroup owns the counter)");
-    if (dtype == MJMPC_F32)
-        return mjmpc::launch_track<float>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal,
-                                          d_ref, (int)n_ref, n_cols, periodic != 0, d_step, step_bias, advance != 0, d_costs,
-                                          stream);
-    return mjmpc::launch_track<double>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_ref,
-                                       (int)n_ref, n_cols, periodic != 0, d_step, step_bias, advance != 0, d_costs, stream);
-}
-
-extern "C" int mjmpc_cost_terms_track_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
-                                            const void* d_actions, const double* d_terms, int n_terms, int per_episode,
-                                            int keep_builtin, int terminal, const double* d_ref, int64_t n_ref, int n_cols,
-                                            int ref_per_episode, int periodic, const int64_t* d_step, int64_t step_bias,
-                                            void* d_costs, const double* d_gseq, double* d_q0, void* stream) {
-    using mjmpc::bad_track_batch;
-    if (!d_next_obs || !d_terms || !d_costs || !d_ref || !d_step) return bad_track_batch("null argument");
-    if (E < 1 || P < 1 || H < 1 || d_obs < 1 || A < 0)
-        return bad_track_batch("needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 0");
-    if (P > ((int64_t)1 << 40) / E) return bad_track_batch("more than 2^40 particles");
-    if (d_actions && A < 1) return bad_track_batch("actions of width 0");
-    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_track_batch("n_terms must be 1 .. 128");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_track_batch("dtype must be MJMPC_F32 or MJMPC_F64");
-    if ((d_gseq != nullptr) != (d_q0 != nullptr)) return bad_track_batch("d_gseq and d_q0 go together");
-    if (n_ref < 1 || n_ref > mjmpc::CT_MAX_REF_ROWS) return bad_track_batch("n_ref must be 1 .. 2^20");
-    if (n_cols < 1 || n_cols > mjmpc::CT_MAX_TERMS) return bad_track_batch("n_cols must be 1 .. 128");
-    if (dtype == MJMPC_F32)
-        return mjmpc::launch_track_batch<float>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
-                                                keep_builtin, terminal, d_ref, (int)n_ref, n_cols, ref_per_episode != 0,
-                                                periodic != 0, d_step, step_bias, d_costs, d_gseq, d_q0, stream);
-    return mjmpc::launch_track_batch<double>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
-                                             keep_builtin, terminal, d_ref, (int)n_ref, n_cols, ref_per_episode != 0,
-                                             periodic != 0, d_step, step_bias, d_costs, d_gseq, d_q0, stream);
-}
-
-extern "C" int mjmpc_cost_terms_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
-                                      const void* d_actions, const double* d_terms, int n_terms, int per_episode,
-                                      int keep_builtin, int terminal, void* d_costs, const double* d_gseq, double* d_q0,
-                                      void* stream) {
-    using mjmpc::bad_batch;
-    if (!d_next_obs || !d_terms || !d_costs) return bad_batch("null argument");
-    if (E < 1 || P < 1 || H < 1 || d_obs < 1 || A < 0) return bad_batch("needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 0");
-    if (P > ((int64_t)1 << 40) / E) return bad_batch("more than 2^40 particles");
-    if (d_actions && A < 1) return bad_batch("actions of width 0");
-    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return bad_batch("n_terms must be 1 .. 128");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_batch("dtype must be MJMPC_F32 or MJMPC_F64");
-    if ((d_gseq != nullptr) != (d_q0 != nullptr)) return bad_batch("d_gseq and d_q0 go together");
-    if (dtype == MJMPC_F32)
-        return mjmpc::launch_batch<float>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
-                                          keep_builtin, terminal, d_costs, d_gseq, d_q0, stream);
-    return mjmpc::launch_batch<double>(E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode != 0,
-                                       keep_builtin, terminal, d_costs, d_gseq, d_q0, stream);
-}
-
-extern "C" int mjmpc_cost_terms(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
-                                const double* d_terms, int n_terms, int keep_builtin, int terminal, void* d_costs,
-                                void* stream) {
-    if (!d_next_obs || !d_terms || !d_costs) return mjmpc::bad("null argument");
-    if (P < 1 || H < 1 || d_obs < 1 || A < 0) return mjmpc::bad("needs P >= 1, H >= 1, d_obs >= 1 and A >= 0");
-    if (P > ((int64_t)1 << 40)) return mjmpc::bad("more than 2^40 particles");
-    if (d_actions && A < 1) return mjmpc::bad("actions of width 0");
-    if (n_terms < 1 || n_terms > mjmpc::CT_MAX_TERMS) return mjmpc::bad("n_terms must be 1 .. 128");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return mjmpc::bad("dtype must be MJMPC_F32 or MJMPC_F64");
-    if (dtype == MJMPC_F32)
-        return mjmpc::launch<float>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_costs,
-                                    stream);
-    return mjmpc::launch<double>(P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, keep_builtin, terminal, d_costs,
-                                 stream);
+    const char* const entry = "mjmpc_cost_terms_rate_batch";
+    const char* const refusal = ct_first(
+        {ct_not_null(d_next_obs && d_actions && d_terms && d_costs), ct_together(d_ref, d_step, "d_ref and d_step go together"),
+         ct_sizes(E, P, H, d_obs, A, 1, d_actions, "needs E >= 1, P >= 1, H >= 1, d_obs >= 1 and A >= 1"), ct_n_terms(n_terms),
+         ct_dtype(dtype), ct_together(d_gseq, d_q0, "d_gseq and d_q0 go together"), ct_reference(d_ref, n_ref, n_cols),
+         ct_advance(advance_prev, P, H, "advance_prev needs P = H = 1 (one workgroup per episode owns its previous action)")});
+    if (refusal) return bad(entry, refusal);
+    return launch_batch(entry, true, dtype, E, P, H, d_obs, A, d_next_obs, d_actions, d_terms, n_terms, per_episode,
+                        keep_builtin, terminal, d_ref, n_ref, n_cols, ref_per_episode, periodic, d_step, step_bias,
+                        d_prev_actions, advance_prev, d_costs, d_gseq, d_q0, stream);
 }

@@ -1,6 +1,7 @@
 """What tests/test_batched_terms_gpu.py shares: the models with their start states, the tables (one for the
-batch or one per episode), the single-episode reference with terms on its own engine, the raw entry-point calls and the
-reference batch whose two engine launches are rebuilt from ``mjmpc_cost_terms`` per episode and a numpy cost-to-go."""
+batch or one per episode), the single-episode reference with terms on its own engine, the raw calls of the six cost-term
+entry points (tests/test_tracking_gpu.py and tests/test_rate_terms_gpu.py use them too) and the reference batch whose two
+engine launches are rebuilt from ``mjmpc_cost_terms`` per episode and a numpy cost-to-go."""
 import ctypes
 
 import numpy as np
@@ -154,6 +155,56 @@ def cost_terms_batch(tables, E, nobs, act, costs, keep, terminal, f32, gseq=None
                                           (0 if act is None else act.shape[2]) if A is None else A, _vp(nobs), _vp(act),
                                           _vp(tables), tables.shape[1], int(tables.shape[0] > 1), int(keep), int(terminal),
                                           _vp(costs), _vp(gseq), _vp(q0), stream()))
+
+
+def cost_terms_track(d_tab, d_ref, periodic, counter, bias, advance, nobs, act, costs, keep, terminal, f32):
+    """``mjmpc_cost_terms_track`` on device tensors ([P][H][..]), in place in ``costs``."""
+    from mjmpc_amd import _lib
+    lib = _lib.require_gpu()
+    Pn, Hn, d_obs = nobs.shape
+    _lib.check(lib.mjmpc_cost_terms_track(_lib.F32 if f32 else _lib.F64, Pn, Hn, d_obs, 0 if act is None else act.shape[2],
+                                          _vp(nobs), _vp(act), _vp(d_tab), d_tab.shape[0], int(keep), int(terminal), _vp(d_ref),
+                                          d_ref.shape[0], d_ref.shape[1], int(periodic), _vp(counter), int(bias), int(advance),
+                                          _vp(costs), stream()))
+
+
+def cost_terms_track_batch(d_tabs, d_refs, periodic, counter, bias, E, nobs, act, costs, keep, terminal, f32, gseq=None, q0=None,
+                           A=None):
+    """``mjmpc_cost_terms_track_batch`` on device tensors ([E P][H][..]); ``d_tabs``: [1 or E][K][8], ``d_refs``: [1 or E][N][R]."""
+    from mjmpc_amd import _lib
+    lib = _lib.require_gpu()
+    N, Hn, d_obs = nobs.shape
+    _lib.check(lib.mjmpc_cost_terms_track_batch(
+        _lib.F32 if f32 else _lib.F64, E, N // E, Hn, d_obs, (0 if act is None else act.shape[2]) if A is None else A, _vp(nobs),
+        _vp(act), _vp(d_tabs), d_tabs.shape[1], int(d_tabs.shape[0] > 1), int(keep), int(terminal), _vp(d_refs), d_refs.shape[1],
+        d_refs.shape[2], int(d_refs.shape[0] > 1), int(periodic), _vp(counter), int(bias), _vp(costs), _vp(gseq), _vp(q0),
+        stream()))
+
+
+def cost_terms_rate(d_tab, d_ref, periodic, counter, bias, advance, prev, nobs, act, costs, keep, terminal, f32):
+    """``mjmpc_cost_terms_rate`` on device tensors ([P][H][..]), in place in ``costs``; ``d_ref`` / ``counter`` / ``prev`` may
+    be ``None``."""
+    from mjmpc_amd import _lib
+    lib = _lib.require_gpu()
+    Pn, Hn, d_obs = nobs.shape
+    _lib.check(lib.mjmpc_cost_terms_rate(
+        _lib.F32 if f32 else _lib.F64, Pn, Hn, d_obs, act.shape[2], _vp(nobs), _vp(act), _vp(d_tab), d_tab.shape[0], int(keep),
+        int(terminal), _vp(d_ref), 0 if d_ref is None else d_ref.shape[0], 0 if d_ref is None else d_ref.shape[1], int(periodic),
+        _vp(counter), int(bias), int(advance), _vp(prev), _vp(costs), stream()))
+
+
+def cost_terms_rate_batch(d_tabs, d_refs, periodic, counter, bias, E, prevs, advance_prev, nobs, act, costs, keep, terminal, f32,
+                          gseq=None, q0=None):
+    """``mjmpc_cost_terms_rate_batch`` on device tensors ([E P][H][..]); ``d_tabs``: [1 or E][K][8], ``d_refs``: [1 or E][N][R] or
+    ``None``, ``prevs``: [E][A] or ``None``."""
+    from mjmpc_amd import _lib
+    lib = _lib.require_gpu()
+    N, Hn, d_obs = nobs.shape
+    _lib.check(lib.mjmpc_cost_terms_rate_batch(
+        _lib.F32 if f32 else _lib.F64, E, N // E, Hn, d_obs, act.shape[2], _vp(nobs), _vp(act), _vp(d_tabs), d_tabs.shape[1],
+        int(d_tabs.shape[0] > 1), int(keep), int(terminal), _vp(d_refs), 0 if d_refs is None else d_refs.shape[1],
+        0 if d_refs is None else d_refs.shape[2], int(d_refs is not None and d_refs.shape[0] > 1), int(periodic), _vp(counter),
+        int(bias), _vp(prevs), int(advance_prev), _vp(costs), _vp(gseq), _vp(q0), stream()))
 
 
 def numpy_q0(costs, gseq):

@@ -1,9 +1,13 @@
-"""Shared by tests/test_cost_terms_cpu.py and tests/test_cost_terms_gpu.py: the numpy restatement of a cost-term table's
+"""Shared by tests/test_cost_terms_cpu.py and the cost-term GPU tests: the numpy restatement of a cost-term table's
 row semantics (plain loops in row order, float64 accumulation - written from the row format, not from ``CostTerms`` or the
-kernel), the derived error bound, and random valid tables."""
+kernel), the derived error bound, random valid tables, and the engines, noise and MPPI of the GPU tests' closed loops."""
 import numpy as np
 
+from batched_cases import FILT
+
 ABS, SQUARE, NORM, COS = 0, 1, 2, 3
+REACHER_START = dict(qp=np.array([0.1, 0.2, 0.0, -0.5, 0.0, -0.3, 0.0]), qv=np.zeros(7), target_pos=np.array([0.2, -0.1, 0.2]))
+P, H = 64, 8
 
 
 def restate(table, next_obs, actions, incoming, keep_builtin, terminal):
@@ -96,3 +100,33 @@ def mixed_terms(engine, CostTerms):
     t.cos(obs="qpos", index=0, weight=0.3, target=0.2)
     t.square(obs="qvel", index=0, weight=0.5, terminal=True)
     return t
+
+
+def _engine(model, dtype="f64"):
+    """The arm engine on the reacher or the tree engine on a synthetic model ('cartpole', 'tray'), at the model's start
+    state (inside every model's stable range in the existing tests)."""
+    if model == "reacher":
+        from mjmpc_amd.envs.arm_engine import ArmRolloutEngine
+        from mjmpc_amd.models.reacher7dof import reacher7dof_raw
+        eng = ArmRolloutEngine(reacher7dof_raw(), dtype=dtype)
+        eng.set_env_state(REACHER_START)
+        return eng
+    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
+    from mjmpc_amd.models.synthetic import start_state, synthetic_raw
+    raw = synthetic_raw(model)
+    eng = TreeRolloutEngine(raw, dtype=dtype)
+    st = start_state(model, raw)
+    eng.set_env_state(dict(qp=st["qp"], qv=st["qv"], target_pos=st["target_pos"]))
+    return eng
+
+
+def _noise(eng, seed=3, cov=0.1):
+    return np.sqrt(cov) * np.random.default_rng(seed).standard_normal((P, H, eng.d_action))
+
+
+def _mppi(eng, **over):
+    from mjmpc_amd import control
+    kw = dict(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, num_particles=P, n_iters=1, gamma=0.98,
+              action_lows=eng.action_lows, action_highs=eng.action_highs, filter_coeffs=FILT, seed=11, base_action="null",
+              noise_mode="device", init_cov=0.1, lam=0.05, step_size=0.8, alpha=1)
+    return control.MPPI(**dict(kw, **over))

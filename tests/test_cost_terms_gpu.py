@@ -6,12 +6,10 @@ import ctypes
 import numpy as np
 import pytest
 
-from cost_terms_cases import bound, mixed_terms, random_table, restate
+from cost_terms_cases import H, P, _engine, _noise, bound, mixed_terms, random_table, restate
 
 pytestmark = pytest.mark.gpu
 
-REACHER_START = dict(qp=np.array([0.1, 0.2, 0.0, -0.5, 0.0, -0.3, 0.0]), qv=np.zeros(7), target_pos=np.array([0.2, -0.1, 0.2]))
-P, H = 64, 8
 FILT = [0.25, 0.8, 0.0]
 
 
@@ -22,27 +20,6 @@ def _torch():
 
 def _vp(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def _engine(model, dtype="f64"):
-    """An engine at the model's start state (inside every model's stable range in the existing tests)."""
-    if model == "reacher":
-        from mjmpc_amd.envs.arm_engine import ArmRolloutEngine
-        from mjmpc_amd.models.reacher7dof import reacher7dof_raw
-        eng = ArmRolloutEngine(reacher7dof_raw(), dtype=dtype)
-        eng.set_env_state(REACHER_START)
-        return eng
-    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    from mjmpc_amd.models.synthetic import start_state, synthetic_raw
-    raw = synthetic_raw(model)
-    eng = TreeRolloutEngine(raw, dtype=dtype)
-    st = start_state(model, raw)
-    eng.set_env_state(dict(qp=st["qp"], qv=st["qv"], target_pos=st["target_pos"]))
-    return eng
-
-
-def _noise(eng, seed=3, cov=0.1):
-    return np.sqrt(cov) * np.random.default_rng(seed).standard_normal((P, H, eng.d_action))
 
 
 # ---- 1. the kernel against the restatement ------------------------------------------------------------------------------

@@ -4,8 +4,9 @@
    tests/cost_terms_cases.py - tile boundaries in mid-particle and at t = 0, a tile of fewer than 64 rows, every ``prev``
    (finite, NaN, one NaN entry, NULL), with and without a reference, ``advance``; a pointed case whose cost IS the rate;
    ``mjmpc_cost_terms_rate_batch`` against the single entry per episode, bit for bit; old tables through the new entries
-   against the old entries, bit for bit.  2. the engines: ``rollout_device`` against the restatement, ``step_state`` and the env
-   classes' ``step`` record the applied action, eager / hipGraph / launch-tape loops agree.  3. the six episode-batch classes:
+   against the old entries, bit for bit; all six entries at the widths that put a tile exactly on its LDS budget.  2. the
+   engines: ``rollout_device`` against the restatement, ``step_state`` and the env classes' ``step`` record the applied
+   action, eager / hipGraph / launch-tape loops agree.  3. the six episode-batch classes:
    real-env costs from consecutive published actions, ``_prev_actions``, ``reset()``; ``BatchedMPPI`` against sequential
    single-episode captured loops.  4. tables that need no new entry, and ``None``, cost what they did and never reach it."""
 
@@ -16,35 +17,12 @@ import batched_cases as bc
 import batched_terms_cases as btc
 import rate_cases as rc
 import tracking_cases as tc
-from batched_cases import FILT, _torch, _vp
-from cost_terms_cases import bound, mixed_terms, random_table
+from batched_cases import FILT, _torch
+from cost_terms_cases import H, P, _engine, _mppi, _noise, bound, mixed_terms, random_table, restate
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = ["f64", "f32"]
-REACHER_START = dict(qp=np.array([0.1, 0.2, 0.0, -0.5, 0.0, -0.3, 0.0]), qv=np.zeros(7), target_pos=np.array([0.2, -0.1, 0.2]))
-P, H = 64, 8
-
-
-def _engine(model, dtype="f64"):
-    """The tree engine on the synthetic cart-pole or the arm engine on the reacher, at a start state."""
-    if model == "reacher":
-        from mjmpc_amd.envs.arm_engine import ArmRolloutEngine
-        from mjmpc_amd.models.reacher7dof import reacher7dof_raw
-        eng = ArmRolloutEngine(reacher7dof_raw(), dtype=dtype)
-        eng.set_env_state(REACHER_START)
-        return eng
-    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    from mjmpc_amd.models.synthetic import start_state, synthetic_raw
-    raw = synthetic_raw(model)
-    eng = TreeRolloutEngine(raw, dtype=dtype)
-    st = start_state(model, raw)
-    eng.set_env_state(dict(qp=st["qp"], qv=st["qv"], target_pos=st["target_pos"]))
-    return eng
-
-
-def _noise(eng, seed=3, cov=0.1):
-    return np.sqrt(cov) * np.random.default_rng(seed).standard_normal((P, H, eng.d_action))
 
 
 def _seen(x, f32):
@@ -53,32 +31,6 @@ def _seen(x, f32):
 
 
 # ---- 1. the entry points ------------------------------------------------------------------------------------------------
-def _rate(d_tab, d_ref, periodic, counter, bias, advance, prev, nobs, act, costs, keep, terminal, f32):
-    """``mjmpc_cost_terms_rate`` on device tensors ([P][H][..]), in place in ``costs``; ``d_ref`` / ``counter`` / ``prev`` may
-    be ``None``."""
-    from mjmpc_amd import _lib
-    lib = _lib.require_gpu()
-    Pn, Hn, d_obs = nobs.shape
-    _lib.check(lib.mjmpc_cost_terms_rate(
-        _lib.F32 if f32 else _lib.F64, Pn, Hn, d_obs, act.shape[2], _vp(nobs), _vp(act), _vp(d_tab), d_tab.shape[0], int(keep),
-        int(terminal), _vp(d_ref), 0 if d_ref is None else d_ref.shape[0], 0 if d_ref is None else d_ref.shape[1], int(periodic),
-        _vp(counter), int(bias), int(advance), _vp(prev), _vp(costs), btc.stream()))
-
-
-def _rate_batch(d_tabs, d_refs, periodic, counter, bias, E, prevs, advance_prev, nobs, act, costs, keep, terminal, f32, gseq=None,
-                q0=None):
-    """``mjmpc_cost_terms_rate_batch`` on device tensors ([E P][H][..]); ``d_tabs``: [1 or E][K][8], ``d_refs``: [1 or E][N][R] or
-    ``None``, ``prevs``: [E][A] or ``None``."""
-    from mjmpc_amd import _lib
-    lib = _lib.require_gpu()
-    N, Hn, d_obs = nobs.shape
-    _lib.check(lib.mjmpc_cost_terms_rate_batch(
-        _lib.F32 if f32 else _lib.F64, E, N // E, Hn, d_obs, act.shape[2], _vp(nobs), _vp(act), _vp(d_tabs), d_tabs.shape[1],
-        int(d_tabs.shape[0] > 1), int(keep), int(terminal), _vp(d_refs), 0 if d_refs is None else d_refs.shape[1],
-        0 if d_refs is None else d_refs.shape[2], int(d_refs is not None and d_refs.shape[0] > 1), int(periodic), _vp(counter),
-        int(bias), _vp(prevs), int(advance_prev), _vp(costs), _vp(gseq), _vp(q0), btc.stream()))
-
-
 # (P, H): a workgroup boundary in mid-particle (64 = 12 particles and 4 steps: the previous row lies in another tile); a
 # boundary that is a particle's t = 0; H above a tile; every element a t = 0; the controlled env's step
 SHAPES = [(24, 5), (2, 64), (3, 70), (8, 1), (1, 1)]
@@ -133,7 +85,7 @@ def test_rate_kernel_matches_the_restatement(d_obs, A, K, f32):
                     cin.reshape(-1)[4], cin.reshape(-1)[Pn * Hn - 2] = np.inf, np.nan
                 costs = torch.from_numpy(cin).to(tdt).cuda()
                 cin_seen = costs.cpu().numpy().astype(np.float64)
-                _rate(d_tab, d_ref, periodic, counter, bias, advance, prev, nobs, act, costs, keep, terminal, f32)
+                btc.cost_terms_rate(d_tab, d_ref, periodic, counter, bias, advance, prev, nobs, act, costs, keep, terminal, f32)
                 torch.cuda.synchronize()
                 where = (Pn, Hn, reference, how, now, bias, keep, terminal, advance)
                 if counter is not None:
@@ -167,7 +119,7 @@ def test_rate_kernel_reads_the_step_before(f32):
         for prev_h in (np.array([5.0, -2.0]), np.array([0.0, np.nan]), None):
             costs = torch.zeros((Pn, Hn), dtype=tdt, device="cuda")
             prev = None if prev_h is None else torch.from_numpy(prev_h).cuda()
-            _rate(table, None, 0, None, 0, 0, prev, nobs, act, costs, 0, 1, f32)
+            btc.cost_terms_rate(table, None, 0, None, 0, 0, prev, nobs, act, costs, 0, 1, f32)
             want = np.tile(t, (Pn, 1))
             want[:, 0] = 0.0 if prev_h is None or np.isnan(prev_h[1]) else np.abs(1000.0 * np.arange(Pn) - prev_h[1])
             assert np.array_equal(costs.cpu().numpy().astype(np.float64), want), (Pn, Hn, prev_h)
@@ -220,11 +172,13 @@ def test_rate_batch_kernel_equals_the_single_kernel_per_episode(f32):
             for e in range(E):
                 rows = slice(e * Pn, (e + 1) * Pn)
                 one_counter = None if counter is None else counter.clone()
-                _rate(d_tabs[e if tab_pe else 0], None if d_refs is None else d_refs[e if ref_pe else 0], periodic, one_counter,
-                      bias, advance, None if want_prev is None else want_prev[e], nobs[rows], act[rows], want[rows], 1, 1, f32)
+                btc.cost_terms_rate(d_tabs[e if tab_pe else 0], None if d_refs is None else d_refs[e if ref_pe else 0], periodic,
+                                    one_counter, bias, advance, None if want_prev is None else want_prev[e], nobs[rows], act[rows],
+                                    want[rows], 1, 1, f32)
             got, q0 = d_cin.clone(), torch.full((n,), -7.0, dtype=torch.float64, device="cuda")
             got_prev = torch.from_numpy(prev_h).cuda() if with_prev else None
-            _rate_batch(d_tabs, d_refs, periodic, counter, bias, E, got_prev, advance, nobs, act, got, 1, 1, f32, gseq, q0)
+            btc.cost_terms_rate_batch(d_tabs, d_refs, periodic, counter, bias, E, got_prev, advance, nobs, act, got, 1, 1, f32, gseq,
+                                      q0)
             torch.cuda.synchronize()
             where = (E, Pn, Hn, tab_pe, ref_pe, periodic, now, bias, with_prev)
             got_h = got.cpu().numpy()
@@ -241,7 +195,6 @@ def test_rate_batch_kernel_equals_the_single_kernel_per_episode(f32):
 @pytest.mark.parametrize("f32", [False, True], ids=DTYPES)
 def test_old_tables_through_the_new_entries_equal_the_old_entries(f32):
     """Kinds 0 .. 3 and sources 0 / 1, NULL ``prev``: the four new kernels against the four old ones, bit for bit."""
-    from test_tracking_gpu import _track, _track_batch
     torch = _torch()
     rng = np.random.default_rng(79)
     tdt = btc.tdtype(f32)
@@ -264,27 +217,109 @@ def test_old_tables_through_the_new_entries_equal_the_old_entries(f32):
         pairs = []
         old, new = d_cin.clone(), d_cin.clone()
         btc.cost_terms(d_tab, nobs, act, old, 1, 1, f32)
-        _rate(d_tab, None, 0, None, 0, 0, None, nobs, act, new, 1, 1, f32)
+        btc.cost_terms_rate(d_tab, None, 0, None, 0, 0, None, nobs, act, new, 1, 1, f32)
         pairs.append(("single", old, new))
         old, new = d_cin.clone(), d_cin.clone()
-        _track(d_tracked, d_ref, 1, counter, -1, 0, nobs, act, old, 0, 1, f32)
-        _rate(d_tracked, d_ref, 1, counter, -1, 0, None, nobs, act, new, 0, 1, f32)
+        btc.cost_terms_track(d_tracked, d_ref, 1, counter, -1, 0, nobs, act, old, 0, 1, f32)
+        btc.cost_terms_rate(d_tracked, d_ref, 1, counter, -1, 0, None, nobs, act, new, 0, 1, f32)
         pairs.append(("tracked", old, new))
         old, new = d_cin.clone(), d_cin.clone()
         q_old, q_new = (torch.full((n,), -7.0, dtype=torch.float64, device="cuda") for _ in range(2))
         btc.cost_terms_batch(d_tabs, E, nobs, act, old, 1, 1, f32, gseq, q_old)
-        _rate_batch(d_tabs, None, 0, None, 0, E, None, 0, nobs, act, new, 1, 1, f32, gseq, q_new)
+        btc.cost_terms_rate_batch(d_tabs, None, 0, None, 0, E, None, 0, nobs, act, new, 1, 1, f32, gseq, q_new)
         pairs += [("batch", old, new), ("batch q0", q_old, q_new)]
         old, new = d_cin.clone(), d_cin.clone()
         q_old, q_new = (torch.full((n,), -7.0, dtype=torch.float64, device="cuda") for _ in range(2))
         d_trs = torch.from_numpy(np.ascontiguousarray(np.stack([tracked] * E))).cuda()
-        _track_batch(d_trs, d_ref[None], 0, counter, 0, E, nobs, act, old, 1, 1, f32, gseq, q_old)
-        _rate_batch(d_trs, d_ref[None], 0, counter, 0, E, None, 0, nobs, act, new, 1, 1, f32, gseq, q_new)
+        btc.cost_terms_track_batch(d_trs, d_ref[None], 0, counter, 0, E, nobs, act, old, 1, 1, f32, gseq, q_old)
+        btc.cost_terms_rate_batch(d_trs, d_ref[None], 0, counter, 0, E, None, 0, nobs, act, new, 1, 1, f32, gseq, q_new)
         pairs += [("tracked batch", old, new), ("tracked batch q0", q_old, q_new)]
         torch.cuda.synchronize()
         for what, a, b in pairs:
             a, b = a.cpu().numpy(), b.cpu().numpy()
             assert np.all(np.isfinite(a.reshape(-1)[5:])) and np.array_equal(a, b), (what, E, Pn, Hn)
+
+
+def test_tile_rows_at_the_lds_budget():
+    """f64 rows that put a 64-row tile exactly on a budget, through all six entries (one tile-sizing function serves them).
+    (109, 3): pitches 109 + 3 = 112 words, 64 x 112 x 8 = 57344 bytes = the batch budget - the plain and tracked batch entries
+    keep 64 rows, the rate batch entry's one more action row takes it to 32, every flat entry keeps 64.  (117, 3): pitches
+    117 + 3 = 120 words, 64 x 120 x 8 = 61440 bytes = the flat budget - flat plain and tracked keep 64 rows, flat rate drops to
+    32, every batch entry runs at 32.  Each flat entry against its numpy restatement per episode, each batch entry against its
+    flat entry bit for bit, q0 against the forward loop."""
+    torch = _torch()
+    rng = np.random.default_rng(80)
+    f32, K, N, periodic, now, bias = False, 9, 6, 1, 4, -1
+    for d_obs, A in [(109, 3), (117, 3)]:
+        for E, Pn, Hn in [(2, 3, 70), (3, 1, 1)]:
+            n = E * Pn
+            nobs_h, act_h = rng.uniform(-5.0, 5.0, (n, Hn, d_obs)), rng.uniform(-5.0, 5.0, (n, Hn, A))
+            nobs, act = torch.from_numpy(nobs_h).cuda(), torch.from_numpy(act_h).cuda()
+            gseq_h = np.cumprod([1.0] + [0.93] * (Hn - 1))
+            gseq = torch.from_numpy(gseq_h).cuda()
+            plain = random_table(rng, K, d_obs, A)
+            tracked, ref0 = tc.track_rows(rng, plain, N)
+            extended, ref1 = tc.track_rows(rng, rc.random_extended_table(rng, K, d_obs, A), N)
+            advance = int((Pn, Hn) == (1, 1))
+            for entry, base, ref in [("plain", plain, None), ("track", tracked, ref0), ("rate", extended, ref1)]:
+                tables = np.stack([base] * E)                       # a table, a reference and a previous action per episode
+                tables[1:, :, 3] = rng.uniform(-2.0, 2.0, (E - 1, K))
+                tables[1:, :, 4] = rng.uniform(-5.0, 5.0, (E - 1, K))
+                d_tabs = torch.from_numpy(np.ascontiguousarray(tables)).cuda()
+                refs = d_refs = counter = None
+                if ref is not None:
+                    refs = np.stack([ref] * E)
+                    refs[1:] = rng.uniform(-5.0, 5.0, (E - 1,) + ref.shape)
+                    d_refs = torch.from_numpy(np.ascontiguousarray(refs)).cuda()
+                    counter = torch.full((1,), now, dtype=torch.int64, device="cuda")
+                prev_h = rng.uniform(-5.0, 5.0, (E, A))
+                prev_h[E - 1, 0] = np.nan
+                cin = rng.uniform(-3.0, 3.0, (n, Hn))
+                if n * Hn >= 15:
+                    cin.reshape(-1)[4], cin.reshape(-1)[n * Hn - 2] = np.inf, np.nan
+                d_cin = torch.from_numpy(cin).cuda()
+                want = d_cin.clone()
+                want_prev, got_prev = (torch.from_numpy(prev_h).cuda() for _ in range(2))
+                got, q0 = d_cin.clone(), torch.full((n,), -7.0, dtype=torch.float64, device="cuda")
+                where = (d_obs, A, E, Pn, Hn, entry)
+                for e in range(E):
+                    rows = slice(e * Pn, (e + 1) * Pn)
+                    if entry == "plain":
+                        btc.cost_terms(d_tabs[e], nobs[rows], act[rows], want[rows], 1, 1, f32)
+                        ref_cost, mag = restate(tables[e], nobs_h[rows], act_h[rows], cin[rows], 1, 1)
+                    elif entry == "track":
+                        btc.cost_terms_track(d_tabs[e], d_refs[e], periodic, counter, bias, 0, nobs[rows], act[rows], want[rows],
+                                             1, 1, f32)
+                        ref_cost, mag = tc.restate(tables[e], refs[e], periodic, now + bias, nobs_h[rows], act_h[rows], cin[rows],
+                                                   1, 1)
+                    else:
+                        btc.cost_terms_rate(d_tabs[e], d_refs[e], periodic, counter.clone(), bias, advance, want_prev[e],
+                                            nobs[rows], act[rows], want[rows], 1, 1, f32)
+                        ref_cost, mag = rc.restate(tables[e], nobs_h[rows], act_h[rows], prev_h[e], cin[rows], 1, 1, refs[e],
+                                                   periodic, now + bias)
+                    flat = want[rows].cpu().numpy()
+                    bad = ~np.isfinite(cin[rows])
+                    assert np.all(np.isposinf(flat[bad])) and np.all(np.isposinf(ref_cost[bad])), where + (e,)
+                    err = np.abs(flat[~bad] - ref_cost[~bad])
+                    tol = bound(tables[e], ref_cost, mag, f32)[~bad]
+                    assert np.all(err <= tol), "%s: error %.3g over the bound by %.3g" % (where + (e,), err.max(),
+                                                                                        (err - tol).max())
+                if entry == "plain":
+                    btc.cost_terms_batch(d_tabs, E, nobs, act, got, 1, 1, f32, gseq, q0)
+                elif entry == "track":
+                    btc.cost_terms_track_batch(d_tabs, d_refs, periodic, counter, bias, E, nobs, act, got, 1, 1, f32, gseq, q0)
+                else:
+                    btc.cost_terms_rate_batch(d_tabs, d_refs, periodic, counter, bias, E, got_prev, advance, nobs, act, got, 1, 1,
+                                              f32, gseq, q0)
+                torch.cuda.synchronize()
+                got_h = got.cpu().numpy()
+                assert counter is None or int(counter.item()) == now, where
+                assert np.array_equal(got_h, want.cpu().numpy()), where
+                assert np.array_equal(q0.cpu().numpy(), btc.numpy_q0(got_h, gseq_h)), where
+                assert np.sum(~np.isfinite(got_h)) == (2 if n * Hn >= 15 else 0), where
+                if entry == "rate":
+                    assert np.array_equal(got_prev.cpu().numpy(), want_prev.cpu().numpy(), equal_nan=True), where
+                    assert np.array_equal(got_prev.cpu().numpy(), act_h[:, 0] if advance else prev_h, equal_nan=True), where
 
 
 # ---- 2. the engines -------------------------------------------------------------------------------------------------------
@@ -374,14 +409,6 @@ def test_step_state_and_env_steps_record_the_applied_action(model, dtype):
     eng.set_cost_terms(None)
     assert not eng._terms_rate and eng._prev_action is None
     eng.close()
-
-
-def _mppi(eng, **over):
-    from mjmpc_amd import control
-    kw = dict(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, num_particles=P, n_iters=1, gamma=0.98,
-              action_lows=eng.action_lows, action_highs=eng.action_highs, filter_coeffs=FILT, seed=11, base_action="null",
-              noise_mode="device", init_cov=0.1, lam=0.05, step_size=0.8, alpha=1)
-    return control.MPPI(**dict(kw, **over))
 
 
 def _loop(model, dtype, mode, T=4):

@@ -16,60 +16,14 @@ import batched_cases as bc
 import batched_terms_cases as btc
 import tracking_cases as tc
 from batched_cases import FILT, _torch, _vp
-from cost_terms_cases import bound, random_table
+from cost_terms_cases import H, P, _engine, _mppi, _noise, bound, random_table
 
 pytestmark = pytest.mark.gpu
 
 DTYPES = ["f64", "f32"]
-REACHER_START = dict(qp=np.array([0.1, 0.2, 0.0, -0.5, 0.0, -0.3, 0.0]), qv=np.zeros(7), target_pos=np.array([0.2, -0.1, 0.2]))
-P, H = 64, 8
-
-
-def _engine(model, dtype="f64"):
-    """The tree engine on the synthetic cart-pole or the arm engine on the reacher, at a start state."""
-    if model == "reacher":
-        from mjmpc_amd.envs.arm_engine import ArmRolloutEngine
-        from mjmpc_amd.models.reacher7dof import reacher7dof_raw
-        eng = ArmRolloutEngine(reacher7dof_raw(), dtype=dtype)
-        eng.set_env_state(REACHER_START)
-        return eng
-    from mjmpc_amd.envs.tree_engine import TreeRolloutEngine
-    from mjmpc_amd.models.synthetic import start_state, synthetic_raw
-    raw = synthetic_raw(model)
-    eng = TreeRolloutEngine(raw, dtype=dtype)
-    st = start_state(model, raw)
-    eng.set_env_state(dict(qp=st["qp"], qv=st["qv"], target_pos=st["target_pos"]))
-    return eng
-
-
-def _noise(eng, seed=3, cov=0.1):
-    return np.sqrt(cov) * np.random.default_rng(seed).standard_normal((P, H, eng.d_action))
 
 
 # ---- 1. the entry points ------------------------------------------------------------------------------------------------
-def _track(d_tab, d_ref, periodic, counter, bias, advance, nobs, act, costs, keep, terminal, f32):
-    """``mjmpc_cost_terms_track`` on device tensors ([P][H][..]), in place in ``costs``."""
-    from mjmpc_amd import _lib
-    lib = _lib.require_gpu()
-    Pn, Hn, d_obs = nobs.shape
-    _lib.check(lib.mjmpc_cost_terms_track(_lib.F32 if f32 else _lib.F64, Pn, Hn, d_obs, 0 if act is None else act.shape[2],
-                                          _vp(nobs), _vp(act), _vp(d_tab), d_tab.shape[0], int(keep), int(terminal), _vp(d_ref),
-                                          d_ref.shape[0], d_ref.shape[1], int(periodic), _vp(counter), int(bias), int(advance),
-                                          _vp(costs), btc.stream()))
-
-
-def _track_batch(d_tabs, d_refs, periodic, counter, bias, E, nobs, act, costs, keep, terminal, f32, gseq=None, q0=None, A=None):
-    """``mjmpc_cost_terms_track_batch`` on device tensors ([E P][H][..]); ``d_tabs``: [1 or E][K][8], ``d_refs``: [1 or E][N][R]."""
-    from mjmpc_amd import _lib
-    lib = _lib.require_gpu()
-    N, Hn, d_obs = nobs.shape
-    _lib.check(lib.mjmpc_cost_terms_track_batch(
-        _lib.F32 if f32 else _lib.F64, E, N // E, Hn, d_obs, (0 if act is None else act.shape[2]) if A is None else A, _vp(nobs),
-        _vp(act), _vp(d_tabs), d_tabs.shape[1], int(d_tabs.shape[0] > 1), int(keep), int(terminal), _vp(d_refs), d_refs.shape[1],
-        d_refs.shape[2], int(d_refs.shape[0] > 1), int(periodic), _vp(counter), int(bias), _vp(costs), _vp(gseq), _vp(q0),
-        btc.stream()))
-
-
 # (P, H): two workgroups, the last partial; one step per particle; the controlled env's step
 SHAPES = [(24, 5), (8, 1), (1, 1)]
 
@@ -104,7 +58,7 @@ def test_track_kernel_matches_the_restatement(d_obs, A, K, f32):
                         costs = torch.from_numpy(cin).to(tdt).cuda()
                         cin_seen = costs.cpu().numpy().astype(np.float64)
                         counter = torch.full((1,), now, dtype=torch.int64, device="cuda")
-                        _track(d_tab, d_ref, periodic, counter, bias, advance, nobs, act, costs, keep, terminal, f32)
+                        btc.cost_terms_track(d_tab, d_ref, periodic, counter, bias, advance, nobs, act, costs, keep, terminal, f32)
                         torch.cuda.synchronize()
                         where = (Pn, Hn, N, now, bias, periodic, keep, terminal, advance)
                         assert int(counter.item()) == now + advance, where
@@ -137,7 +91,7 @@ def test_track_kernel_reads_the_row_the_contract_names():
     ]:
         costs = torch.zeros((2, Hn), dtype=torch.float64, device="cuda")
         counter = torch.full((1,), now, dtype=torch.int64, device="cuda")
-        _track(d_tab, d_ref, periodic, counter, 0, 0, nobs, act, costs, 0, 1, False)
+        btc.cost_terms_track(d_tab, d_ref, periodic, counter, 0, 0, nobs, act, costs, 0, 1, False)
         want = ref[obs_rows, 0] + ref[act_rows, 1]
         assert np.array_equal(costs.cpu().numpy(), np.stack([want, want])), (now, periodic)
 
@@ -176,10 +130,10 @@ def test_track_batch_kernel_equals_the_single_kernel_per_episode(f32):
             want = d_cin.clone()
             for e in range(E):
                 rows = slice(e * Pn, (e + 1) * Pn)
-                _track(d_tabs[e if tab_pe else 0], d_refs[e if ref_pe else 0], periodic, counter, bias, 0, nobs[rows], act[rows],
-                       want[rows], 1, 1, f32)
+                btc.cost_terms_track(d_tabs[e if tab_pe else 0], d_refs[e if ref_pe else 0], periodic, counter, bias, 0, nobs[rows],
+                                     act[rows], want[rows], 1, 1, f32)
             got, q0 = d_cin.clone(), torch.full((n,), -7.0, dtype=torch.float64, device="cuda")
-            _track_batch(d_tabs, d_refs, periodic, counter, bias, E, nobs, act, got, 1, 1, f32, gseq, q0)
+            btc.cost_terms_track_batch(d_tabs, d_refs, periodic, counter, bias, E, nobs, act, got, 1, 1, f32, gseq, q0)
             torch.cuda.synchronize()
             where = (E, Pn, Hn, tab_pe, ref_pe, periodic, now, bias)
             got_h = got.cpu().numpy()
@@ -228,14 +182,6 @@ def test_a_constant_reference_equals_the_constant_target_bit_for_bit(model, dtyp
 
 
 # ---- 3. closed loops ------------------------------------------------------------------------------------------------------
-def _mppi(eng, **over):
-    from mjmpc_amd import control
-    kw = dict(d_state=eng.d_state, d_obs=eng.d_obs, d_action=eng.d_action, horizon=H, num_particles=P, n_iters=1, gamma=0.98,
-              action_lows=eng.action_lows, action_highs=eng.action_highs, filter_coeffs=FILT, seed=11, base_action="null",
-              noise_mode="device", init_cov=0.1, lam=0.05, step_size=0.8, alpha=1)
-    return control.MPPI(**dict(kw, **over))
-
-
 def _loop(model, dtype, make_terms, mode, T=6):
     """``T`` control steps of MPPI on an engine that is its own real env: ``mode`` 'eager', 'graph' (hipGraph replay) or 'tape'.
     -> actions [T][A], real costs [T], real next observations [T][d_obs], final env time, launch_mode, the terms."""
@@ -520,8 +466,8 @@ def _as_separate_tracked_launches(b):
 
     def track(e, nobs, act, costs, terminal):
         counter.fill_(b.num_steps + b._track_bias)
-        _track(tables[e if per_episode else 0], refs[e if ref_per_episode else 0], periodic, counter, 0, 0, nobs,
-               act if reads else None, costs, keep, terminal, f32)
+        btc.cost_terms_track(tables[e if per_episode else 0], refs[e if ref_per_episode else 0], periodic, counter, 0, 0, nobs,
+                             act if reads else None, costs, keep, terminal, f32)
 
     def rollout(s, noise=None, filtered=True, gseq=True, q0=True):
         nobs = torch.empty((E * Pn, Hn, b.d_obs), dtype=b._tdtype, device=b.device)
