@@ -37,8 +37,8 @@ extern "C" {
  *      fewer motors than dofs). */
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
- *      the DMD-MPC episode batches', mjmpc_cost_terms, mjmpc_cost_terms_track / _track_batch and mjmpc_cost_terms_rate /
- *      _rate_batch.) */
+ *      the DMD-MPC episode batches', mjmpc_cost_terms, mjmpc_cost_terms_track / _track_batch, mjmpc_cost_terms_rate /
+ *      _rate_batch and mjmpc_cost_terms_quad / _quad_batch.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -891,6 +891,36 @@ int mjmpc_cost_terms_rate_batch(int dtype, int E, int64_t P, int H, int d_obs, i
                                 int terminal, const double* d_ref, int64_t n_ref, int n_cols, int ref_per_episode, int periodic,
                                 const int64_t* d_step, int64_t step_bias, double* d_prev_actions, int advance_prev,
                                 void* d_costs, const double* d_gseq, double* d_q0, void* stream);
+
+/* Quadratic forms and signed linear rows: mjmpc_cost_terms_rate with two more kinds.  The entry serves every row
+ * of the entries above and
+ *   kind 8 QUAD: consecutive rows of kind 8 with one group > 0 form a vector r_i = v_i - goal_i, i = 0 .. n-1, n <= 32, every
+ *     row with its own source (0, 1 or 2), index and target or reference column.  At the group's last row the group adds
+ *     w_first * sum_i sum_j r_i Q_ij r_j once, w_first being the first row's weight; `when` is the group's (all rows share it).
+ *     Q is the group's matrix in the pool d_quad, float64 [quad_len] on the device: the groups' matrices back to back in table
+ *     order, each n x n, row-major and symmetric (the kernel reads the diagonal and the entries below it, twice each).  A group's
+ *     offset is the sum of n^2 over the QUAD groups before it.  Q need not be positive semi-definite;
+ *   kind 9 LINEAR: w r, signed.
+ * Order, rounding, `when`, keep_builtin, non-finite incoming costs, d_ref / d_step, advance and d_prev_action are
+ * mjmpc_cost_terms_rate's; a table without a row of kind 8 or 9 gives that entry's result bit for bit.  The kernel never reads
+ * beyond quad_len and never holds more than min(32, floor(sqrt(quad_len))) entries of a group, whatever the table says.  The
+ * groups' scratch comes out of the tile: the row limit is 59 KiB less 512 bytes for every row the largest possible group has
+ * (43 KiB at quad_len = 4096).  Refused before anything is launched: what mjmpc_cost_terms_rate refuses, null d_quad, quad_len
+ * outside 1 .. 4096, an observation row and two action rows beyond that limit (the message names it in bytes). */
+int mjmpc_cost_terms_quad(int dtype, int64_t P, int H, int d_obs, int A, const void* d_next_obs, const void* d_actions,
+                          const double* d_terms, int n_terms, int keep_builtin, int terminal, const double* d_ref,
+                          int64_t n_ref, int n_cols, int periodic, int64_t* d_step, int64_t step_bias, int advance,
+                          double* d_prev_action, const double* d_quad, int quad_len, void* d_costs, void* stream);
+
+/* mjmpc_cost_terms_rate_batch with the rows of mjmpc_cost_terms_quad; one pool d_quad for all episodes.  Costs and cost-to-go
+ * are bit for bit those of mjmpc_cost_terms_quad per episode and of mjmpc_cost_terms_batch's cost-to-go.  Refused: what
+ * mjmpc_cost_terms_rate_batch refuses, null d_quad, quad_len outside 1 .. 4096; the row limit is 55 KiB less the scratch. */
+int mjmpc_cost_terms_quad_batch(int dtype, int E, int64_t P, int H, int d_obs, int A, const void* d_next_obs,
+                                const void* d_actions, const double* d_terms, int n_terms, int per_episode, int keep_builtin,
+                                int terminal, const double* d_ref, int64_t n_ref, int n_cols, int ref_per_episode, int periodic,
+                                const int64_t* d_step, int64_t step_bias, double* d_prev_actions, int advance_prev,
+                                const double* d_quad, int quad_len, void* d_costs, const double* d_gseq, double* d_q0,
+                                void* stream);
 
 #ifdef __cplusplus
 }

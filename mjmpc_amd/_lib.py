@@ -163,6 +163,10 @@ SIGNATURES = {
                                      _i64, _int, _vp, _vp, _vp]),
     "mjmpc_cost_terms_rate_batch": (_int, [_int, _int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _i64,
                                            _int, _int, _int, _vp, _i64, _vp, _int, _vp, _vp, _vp, _vp]),
+    "mjmpc_cost_terms_quad": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _i64, _int, _int, _vp,
+                                     _i64, _int, _vp, _vp, _int, _vp, _vp]),
+    "mjmpc_cost_terms_quad_batch": (_int, [_int, _int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _i64,
+                                           _int, _int, _int, _vp, _i64, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp]),
 }
 
 _LIB = None

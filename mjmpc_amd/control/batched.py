@@ -91,6 +91,8 @@ class _EpisodeBatch:
     _track_bias = 0         # env time of the references = _step_dev + _track_bias (set_track_step)
     _rate = False           # the tables hold action-rate rows or one-sided kinds: mjmpc_cost_terms_rate_batch
     _prev_actions = None    # ... with rate rows every episode's last applied action, float64 [E][A] on the device (NaN: none yet)
+    _quad = None            # the tables hold quadratic groups or signed linear rows: mjmpc_cost_terms_quad_batch with
+                            # this pool of matrices on the device, one for all episodes
     _terms = None           # set_cost_terms: (tables on the device, rows, per episode?, keep_builtin, a row reads an action?)
     _terms_nobs = None      # ... the rollouts' next observations [E P][H][d_obs] (only while terms are set)
     _terms_env = None       # ... the real-env step's own next observations [E][d_obs] and actions [E][A] in the batch's dtype
@@ -355,6 +357,12 @@ class _EpisodeBatch:
             if not np.array_equal(table[:, structure], first[:, structure]):
                 raise ValueError("set_cost_terms: episode %d's rows differ from episode 0's in kind, source, index, group or "
                                  "when (only weights and targets may differ between the episodes)" % e)
+        pool = each[0].quad_table(engine)           # (one pool of matrices for the batch)
+        for e, t in enumerate(each):
+            other = t.quad_table(engine)
+            if pool is not None and not np.array_equal(other, pool):
+                raise ValueError("set_cost_terms: episode %d's quadratic matrices differ from episode 0's (the episodes share "
+                                 "one pool of matrices; weights, targets and references may differ)" % e)
         return np.stack(tables), bool(keep), bool(np.any(first[:, 1] != 0))
 
     @staticmethod
@@ -392,17 +400,25 @@ class _EpisodeBatch:
         plan step through ``mjmpc_cost_terms_track_batch``.  Tables with ``action_rate=`` rows or one-sided kinds
         go through ``mjmpc_cost_terms_rate_batch``, tracked or not; with rate rows every episode's last applied action lives
         on the device (``_prev_actions``, NaN now and after ``reset()``: the first rate of an episode is 0) - the plans read
-        it, the launch that costs the real-env step reads it and then records the step's action.  Everything is checked on the
-        host first (``ValueError``); callable between steps."""
+        it, the launch that costs the real-env step reads it and then records the step's action.  Tables with a quadratic group
+        or a signed linear row go through ``mjmpc_cost_terms_quad_batch``, which serves every row: the groups'
+        matrices are one pool for the batch - per episode the weights, targets and references may differ, the matrices not
+        (``ValueError`` naming the episode).  Everything is checked on the host first (``ValueError``); callable between
+        steps."""
         if terms is None:
-            self._terms = self._terms_nobs = self._terms_env = self._track = self._prev_actions = None
+            self._terms = self._terms_nobs = self._terms_env = self._track = self._prev_actions = self._quad = None
             self._rate = False
             return
         tables, keep, reads_actions = self._resolve_cost_terms(terms, self.engine, self.num_episodes)
         track = self._resolve_tracking(terms, self.engine, self.num_episodes)
         rate_rows = bool(np.any(tables[0][:, 1] == 2))
-        self._rate = rate_rows or bool(np.any(tables[0][:, 0] >= 4))
-        reads_actions = reads_actions or self._rate         # (the rate entry wants the actions)
+        kinds = tables[0][:, 0]
+        self._rate = rate_rows or bool(np.any((kinds >= 4) & (kinds <= 7)))
+        self._quad = None
+        if np.any(kinds >= 8):
+            pool = (terms[0] if isinstance(terms, (list, tuple)) else terms).quad_table(self.engine)
+            self._quad = self._upload(pool if pool is not None else np.zeros(1))    # (linear rows alone: one zero nothing reads)
+        reads_actions = reads_actions or self._rate or self._quad is not None       # (the rate and quad entries want the actions)
         self._track = None if track is None else (self._upload(track[0]), track[0].shape[1], track[0].shape[2],
                                                   int(track[0].shape[0] > 1), int(track[1]))
         torch, E, tdt, dev = self.torch, self.num_episodes, self._tdtype, self.device
@@ -419,6 +435,14 @@ class _EpisodeBatch:
         ``mjmpc_cost_terms_track_batch`` at env time ``_step_dev + bias``; with rate rows or one-sided kinds
         ``mjmpc_cost_terms_rate_batch`` (``advance_prev``: the E elements record their actions in ``_prev_actions``)."""
         tables, K, per_episode, keep, reads_actions = self._terms
+        if self._quad is not None:
+            refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)
+            _lib.check(self.lib.mjmpc_cost_terms_quad_batch(
+                self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs), _vp(act), _vp(tables), K, per_episode,
+                keep, terminal, _vp(refs), N, R, ref_per_episode, periodic, _vp(self._step_dev) if refs is not None else None,
+                bias, _vp(self._prev_actions), advance_prev, _vp(self._quad), self._quad.shape[0], _vp(costs), _vp(gseq),
+                _vp(q0), s))
+            return
         if self._rate:
             refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)
             _lib.check(self.lib.mjmpc_cost_terms_rate_batch(
@@ -602,11 +626,11 @@ class BatchedMPPI(_EpisodeBatch):
         """``_EpisodeBatch.set_cost_terms``.  With tracked terms the step takes the general softmax update - what the
         single-episode MPPI runs once its costs come from a launch behind the rollout - in place of the fused one: an episode
         of the batch stays, bit for bit, the sequential loop on an engine with the same tracked terms.  Tables with action-rate
-        rows or one-sided kinds (DESIGN 12.2) take the same step, tracked or not, and are that loop bit for bit as well;
-        every other table keeps the fused update."""
+        rows or one-sided kinds and tables with quadratic groups or linear rows take the same step,
+        tracked or not, and are that loop bit for bit as well; every other table keeps the fused update."""
         super().set_cost_terms(terms)           # (every refusal of the terms themselves, before anything else)
         self._generic = None
-        if self._track is None and not self._rate:
+        if self._track is None and not self._rate and self._quad is None:
             return
         E, P, H, A = self.num_episodes, self.num_particles, self.horizon, self.d_action
         nbytes = self.lib.mjmpc_dmd_batch_workspace_bytes(E, P, H, A)

@@ -75,6 +75,8 @@ class RolloutEngine(EnvResetWatch):
     _track_periodic = 0
     _terms_rate = False             # the table holds action-rate rows or one-sided kinds: mjmpc_cost_terms_rate
     _prev_action = None             # ... with rate rows the action last applied to the controlled env, float64 [A] on the device
+    _terms_quad = None              # the table holds quadratic groups or signed linear rows: mjmpc_cost_terms_quad
+                                    # with this pool of matrices, float64 on the device (one zero without a group)
     _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
 
     def __init__(self, model, device=0, dtype="f64", num_shards=1):
@@ -339,8 +341,8 @@ class RolloutEngine(EnvResetWatch):
         while terms are set; ``make_device_rollout_fn`` then offers the controllers only the generic iteration - set the
         terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  The episode batches have their own
         ``set_cost_terms`` (``control/batched.py``, DESIGN 10.8: one table for the batch or one per episode).  Covered: both
-        rollout engines and all six episode-batch classes, with constant targets, tracked references, action rates and
-        one-sided bounds.  Not covered: the fused launches, ``AnalyticRolloutEngine``, world sizes above 1.
+        rollout engines and all six episode-batch classes, with constant targets, tracked references, action rates,
+        one-sided bounds, quadratic forms with full matrices and signed linear rows.  Not covered: the fused launches, ``AnalyticRolloutEngine``, world sizes above 1.
 
         Terms with a ``reference=`` are costed by ``mjmpc_cost_terms_track``: their reference goes to the device
         with an env-time counter (``track_step()``, 0 now) that every plan reads and every step of the controlled env
@@ -351,21 +353,32 @@ class RolloutEngine(EnvResetWatch):
         not.  With rate rows the engine keeps the action last applied to the controlled env on the device (``prev_action()``,
         all NaN now: nothing applied, the first rate is 0): every plan's first step reads it and every step of the controlled
         env records its action there inside its launch, with the same restriction on guarded rollouts.
-        ``set_prev_action(a)`` tells an engine that only plans which action was applied."""
+        ``set_prev_action(a)`` tells an engine that only plans which action was applied.
+
+        Terms with a quadratic group or a signed linear row are costed by ``mjmpc_cost_terms_quad``, which serves
+        every other row too: the groups' matrices go to the device as one pool (``CostTerms.quad_table``); counter and previous
+        action behave exactly as on the rate path."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
                                "controllers %s; set the terms first, then call make_device_rollout_fn"
                                % (("with", "no fused launches") if self._closure_terms else ("without", "the fused launches")))
         if terms is None:
             self._cost_terms = self._terms_dev = self._track_ref = self._track_step = self._prev_action = None
+            self._terms_quad = None
             self._terms_read_actions = self._terms_rate = False
             return
         table = np.ascontiguousarray(terms.table(self), np.float64)       # (ValueError before anything reaches the device)
         ref = terms.reference_table(self)
+        pool = terms.quad_table(self)
         torch = _torch()
         self._terms_dev = torch.from_numpy(table).to(self.device)
         self._terms_rate = bool(terms.needs_rate_entry)
-        self._terms_read_actions = bool(np.any(table[:, 1] != 0)) or self._terms_rate      # (the rate entry wants the actions)
+        self._terms_quad = None
+        if terms.needs_quad_entry:
+            # (DESIGN 12.3; a table with linear rows alone still hands the entry a pool: one zero nothing reads)
+            self._terms_quad = torch.from_numpy(pool if pool is not None else np.zeros(1)).to(self.device)
+        # (the rate and quad entries want the actions)
+        self._terms_read_actions = bool(np.any(table[:, 1] != 0)) or self._terms_rate or self._terms_quad is not None
         self._cost_terms = terms
         self._track_ref = self._track_step = self._prev_action = None
         if terms.reads_action_rate:
@@ -418,6 +431,15 @@ class RolloutEngine(EnvResetWatch):
         t = self._terms_dev
         act = _ptr(act if self._terms_read_actions else None)
         keep = int(self._cost_terms.keep_builtin)
+        if self._terms_quad is not None:
+            # (the rate entry's arguments and the pool)
+            r, q = self._track_ref, self._terms_quad
+            _lib.check(self._lib.mjmpc_cost_terms_quad(
+                self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t), t.shape[0], keep, int(bool(terminal)),
+                _ptr(r), 0 if r is None else r.shape[0], 0 if r is None else r.shape[1], self._track_periodic,
+                _ptr(self._track_step), 0, int(bool(advance)), _ptr(self._prev_action), _ptr(q), q.shape[0], _ptr(costs),
+                self._stream()))
+            return
         if self._terms_rate:
             # (tracked or not, and as below the advance - counter and previous action - is part of the launch)
             r = self._track_ref

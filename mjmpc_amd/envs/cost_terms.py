@@ -40,6 +40,18 @@ step the rate is 0).  The kinds 4 .. 7 are zero on one side of the bound ``targe
     terms.square(action_rate="all", weight=0.1)                         # smooth controls
     terms.outside(obs="qpos", index=0, low=-2.0, high=2.0, weight=10.0)  # the cart stays within +-2 m
     terms.above(obs="qvel", index=1, target=3.0)                        # joint speed below 3 rad/s, linear beyond it
+
+Quadratic forms and signed linear rows.  ``quadratic`` adds one group of kind 8 QUAD rows over its indices:
+``weight * sum_ij r_i Q_ij r_j`` with ``r_i = v_i - goal_i``, ``Q`` the ``matrix=`` (``[n][n]``, stored as ``(M + M') / 2``, or
+``[n]`` for a diagonal; ``n <= 32``; it may be indefinite).  The matrices of a table live in a pool beside it (``quad_table()``,
+float64, back to back in table order).  ``parts=`` concatenates rows of several sources into one vector, each part resolved like
+a term of its own.  ``linear`` is kind 9, ``weight * r`` with its sign.  A table with either is costed by
+``mjmpc_cost_terms_quad`` (``needs_quad_entry``); every other table is what it was.
+
+    terms.quadratic(obs=[0, 1, 2, 3], matrix=Q, target=[0.0, np.pi, 0.0, 0.0])      # (x - x*)' Q (x - x*)
+    terms.quadratic(obs=[0, 1, 2, 3], matrix=P_riccati, terminal=True)              # x' P x at a plan's last step
+    terms.quadratic(parts=[dict(obs="qpos"), dict(obs="qvel"), dict(action="all")], matrix=QNR)
+    terms.linear(obs="qvel", index=0, weight=-1.0)                                  # reward forward velocity
 """
 import numpy as np
 
@@ -49,8 +61,11 @@ KIND_ABS, KIND_SQUARE, KIND_NORM, KIND_COS = 0, 1, 2, 3
 KIND_ABOVE, KIND_BELOW, KIND_ABOVE_SQUARE, KIND_BELOW_SQUARE = 4, 5, 6, 7
 KINDS = {"abs": KIND_ABS, "square": KIND_SQUARE, "norm": KIND_NORM, "cos": KIND_COS, "above": KIND_ABOVE, "below": KIND_BELOW,
          "above_square": KIND_ABOVE_SQUARE, "below_square": KIND_BELOW_SQUARE}
+KIND_QUAD, KIND_LINEAR = 8, 9
+KINDS.update(quadratic=KIND_QUAD, linear=KIND_LINEAR)
 SOURCE_OBS, SOURCE_ACTION, SOURCE_ACTION_RATE = 0, 1, 2
 MAX_TERMS = 128
+MAX_QUAD = 32                   # rows of a quadratic group
 ROW_LEN = 8
 MAX_REFERENCE_ROWS = 1 << 20    # (the kernel's per-lane index arithmetic is 32-bit)
 
@@ -74,7 +89,8 @@ class CostTerms:
         self.engine = engine
         self.keep_builtin = bool(keep_builtin)
         # (kind, source block or None, indices or None, source 0 / 1 / 2 (non-zero: it indexes the action), weight, target,
-        #  terminal, reference [N] / [N][n_idx] or None)
+        #  terminal, reference [N] / [N][n_idx] or None, quad: None, or for a part of a quadratic group its matrix [n][n] (the
+        #  group's first part) or False (a later part))
         self._terms = []
         self._periodic = None       # the tracked terms' shared `periodic` (None: no tracked term yet)
 
@@ -139,11 +155,94 @@ class CostTerms:
             raise
         return self
 
+    # ------------------------------------------------------------------ quadratic forms and signed linear rows
+    def linear(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
+               periodic=False, action_rate=None):
+        """``weight * (v - target)``, signed: a reward where the weight is negative."""
+        return self._add(KIND_LINEAR, obs, action, index, weight, target, terminal, reference, periodic, action_rate)
+
+    def quadratic(self, obs=None, action=None, action_rate=None, index=None, matrix=None, weight=1.0, target=0.0,
+                  terminal=False, reference=None, periodic=False, parts=None):
+        """``weight * sum_ij r_i Q_ij r_j`` over the indices, ``r_i = v_i - target_i`` (or the tracked goal): one group of the
+        table.  ``matrix``: ``[n][n]`` - kept as ``(M + M') / 2``, the same form - or ``[n]`` for a diagonal; finite, not
+        necessarily positive semi-definite; ``n <= 32``.  ``parts=``: a list of ``dict(obs= / action= / action_rate=, index=,
+        target=, reference=)`` whose rows are concatenated in order into the one vector the matrix applies to - a form over
+        mixed sources such as ``[x; u]' [[Q, N], [N', R]] [x; u]``."""
+        if matrix is None:
+            raise ValueError("cost term: quadratic needs matrix=")
+        try:
+            Q = np.array(_finite(matrix, "matrix"), np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError("cost term: matrix must be [n][n] or [n] finite numbers: %s" % (e,)) from e
+        if Q.ndim == 1 and Q.size >= 1:
+            Q = np.diag(Q)
+        if Q.ndim != 2 or Q.shape[0] != Q.shape[1] or Q.shape[0] < 1:
+            raise ValueError("cost term: matrix must be square, [n][n], or [n] for a diagonal, got shape %s"
+                             % (list(np.shape(matrix)),))
+        if Q.shape[0] > MAX_QUAD:
+            raise ValueError("cost term: a quadratic group holds at most %d rows, the matrix has %d" % (MAX_QUAD, Q.shape[0]))
+        Q = 0.5 * (Q + Q.T)
+        if parts is None:
+            parts = [dict(obs=obs, action=action, action_rate=action_rate, index=index, target=target, reference=reference)]
+        elif obs is not None or action is not None or action_rate is not None or index is not None or reference is not None \
+                or np.ndim(target) != 0 or float(target) != 0.0:
+            raise ValueError("cost term: with parts= the sources, indices, targets and references go into the parts")
+        if not isinstance(parts, (list, tuple)) or not parts or not all(isinstance(p, dict) for p in parts):
+            raise ValueError("cost term: parts= is a list of dict(obs= / action= / action_rate=, index=, target=, reference=)")
+        if periodic and not any(p.get("reference") is not None for p in parts):
+            raise ValueError("cost term: periodic= goes with a reference=")
+        n0, periodic0 = len(self._terms), self._periodic
+        try:
+            for k, part in enumerate(parts):
+                if set(part) - _PART_KEYS:
+                    raise ValueError("cost term: a part takes %s, got %r" % (sorted(_PART_KEYS), part))
+                self._add(KIND_QUAD, part.get("obs"), part.get("action"), part.get("index"), weight, part.get("target", 0.0),
+                          terminal, part.get("reference"), periodic and part.get("reference") is not None,
+                          part.get("action_rate"), quad=Q if k == 0 else False)
+            if self.engine is not None or all(t[2] is not None for t in self._terms[n0:]):
+                self._quad_groups(self.engine)              # (the matrix against the rows it applies to)
+        except ValueError:
+            del self._terms[n0:]            # (the whole group or nothing)
+            self._periodic = periodic0
+            raise
+        return self
+
+    def _quad_groups(self, engine):
+        """-> [(matrix [n][n], rows)] of the quadratic groups in table order, each matrix checked against its rows."""
+        groups = []
+        for t in self._terms:
+            if t[8] is None:
+                continue
+            n_idx = len(self._resolve(t, engine)[0])
+            if t[8] is False:
+                groups[-1][1] += n_idx
+            else:
+                groups.append([t[8], n_idx])
+        for Q, n in groups:
+            if Q.shape[0] != n:
+                raise ValueError("cost term: the matrix is %d x %d, the group has %d rows" % (Q.shape[0], Q.shape[0], n))
+        return groups
+
+    def quad_table(self, engine=None):
+        """The float64 pool of the quadratic groups' matrices - ``n x n`` row-major and symmetric, back to back in table order:
+        a group's offset is the sum of ``n^2`` over the groups before it -, or ``None`` without a quadratic group."""
+        groups = self._quad_groups(engine if engine is not None else self.engine)
+        if not groups:
+            return None
+        return np.ascontiguousarray(np.concatenate([Q.reshape(-1) for Q, _ in groups]), np.float64)
+
+    @property
+    def needs_quad_entry(self):
+        """Whether the table holds a quadratic group or a signed linear row: rows only ``mjmpc_cost_terms_quad`` and
+        ``mjmpc_cost_terms_quad_batch`` serve."""
+        return any(t[0] in (KIND_QUAD, KIND_LINEAR) for t in self._terms)
+
     @property
     def needs_rate_entry(self):
         """Whether the table holds an action-rate row or a one-sided kind: rows only ``mjmpc_cost_terms_rate`` and
-        ``mjmpc_cost_terms_rate_batch`` serve."""
-        return any(t[3] == SOURCE_ACTION_RATE or t[0] >= KIND_ABOVE for t in self._terms)
+        ``mjmpc_cost_terms_rate_batch`` serve - or, with ``needs_quad_entry``, the quad entries, which serve
+        every row."""
+        return any(t[3] == SOURCE_ACTION_RATE or KIND_ABOVE <= t[0] <= KIND_BELOW_SQUARE for t in self._terms)
 
     @property
     def reads_action_rate(self):
@@ -206,9 +305,9 @@ class CostTerms:
         engine = engine if engine is not None else self.engine
         rows, group, col = [], 0, 0
         for t in self._terms:
-            (kind, _, _, _, weight, _, terminal, reference), idx, source, targets = (t,) + self._resolve(t, engine)
-            if kind == KIND_NORM:
-                group += 1              # a fresh id per norm: neighbouring groups never merge
+            (kind, _, _, _, weight, _, terminal, reference, quad), idx, source, targets = (t,) + self._resolve(t, engine)
+            if kind == KIND_NORM or (kind == KIND_QUAD and quad is not False):
+                group += 1              # a fresh id per norm and per quadratic: neighbouring groups never merge
             reserved = [0.0] * len(idx)
             if reference is not None:
                 # a tracked row: 1 + its column of reference_table(); the target column holds the first goal
@@ -216,15 +315,18 @@ class CostTerms:
                 reserved = [1.0 + col + c for c in range(len(idx))]
                 col += len(idx)
             for i, tg, rs in zip(idx, targets, reserved):
-                rows.append([kind, source, i, weight, tg, group if kind == KIND_NORM else 0, 1.0 if terminal else 0.0, rs])
+                rows.append([kind, source, i, weight, tg, group if kind in (KIND_NORM, KIND_QUAD) else 0,
+                             1.0 if terminal else 0.0, rs])
         if not rows:
             raise ValueError("cost terms: an empty table (set_cost_terms(None) restores the built-in cost)")
         if len(rows) > MAX_TERMS:
             raise ValueError("cost terms: %d rows, the table holds at most %d" % (len(rows), MAX_TERMS))
+        self._quad_groups(engine)       # (a matrix that does not fit its rows is refused here at the latest)
         return np.asarray(rows, np.float64).reshape(-1, ROW_LEN)
 
     # ------------------------------------------------------------------ internals
-    def _add(self, kind, obs, action, index, weight, target, terminal, reference=None, periodic=False, action_rate=None):
+    def _add(self, kind, obs, action, index, weight, target, terminal, reference=None, periodic=False, action_rate=None,
+             quad=None):
         if (obs is not None) + (action is not None) + (action_rate is not None) != 1:
             raise ValueError("cost term: give exactly one of obs=, action= and action_rate=")
         source = SOURCE_ACTION if action is not None else SOURCE_ACTION_RATE if action_rate is not None else SOURCE_OBS
@@ -269,7 +371,7 @@ class CostTerms:
                 raise ValueError("cost terms: the tracked terms of a table share one periodic=")
         elif periodic:
             raise ValueError("cost term: periodic= goes with a reference=")
-        term = (int(kind), block, index, source, weight, target, bool(terminal), reference)
+        term = (int(kind), block, index, source, weight, target, bool(terminal), reference, quad)
         if self.engine is not None:
             n_idx = len(self._resolve(term, self.engine)[0])    # refuse now what the engine would refuse later
             if reference is not None:
@@ -315,6 +417,8 @@ class CostTerms:
 
 _TERM_KEYS = {"kind", "obs", "action", "action_rate", "index", "weight", "target", "terminal", "reference", "repeat",
               "periodic"}
+_QUADRATIC_KEYS = _TERM_KEYS | {"matrix", "parts"}
+_PART_KEYS = {"obs", "action", "action_rate", "index", "target", "reference"}
 _OUTSIDE_KEYS = {"kind", "obs", "action", "action_rate", "index", "weight", "low", "high", "squared", "terminal"}
 
 
@@ -379,7 +483,12 @@ def cost_terms_from_config(block, engine, num_episodes=None):
 
     DESIGN 12.2: ``action_rate:`` stands where ``action:`` may; the kinds ``above``, ``below``, ``above_square`` and
     ``below_square`` take the bound as ``target``; ``{kind: outside, obs: qpos, index: 0, low: -2.0, high: 2.0, weight: 10.0}``
-    is ``CostTerms.outside`` (``squared:`` as there; ``weight``, ``low`` and ``high`` may hold one value per episode)."""
+    is ``CostTerms.outside`` (``squared:`` as there; ``weight``, ``low`` and ``high`` may hold one value per episode).
+
+    DESIGN 12.3: ``{kind: quadratic, obs: [0, 1, 2, 3], matrix: [[..], ..], weight: 1.0}`` is ``CostTerms.quadratic``
+    (``matrix:`` ``[n][n]`` or ``[n]``; ``parts:`` a list of mappings with ``obs`` / ``action`` / ``action_rate``, ``index``,
+    ``target``, ``reference``, as there); ``kind: linear`` takes what ``square`` takes.  ``weight`` (and outside ``parts:``
+    ``target`` and ``reference``) may hold one value per episode; the matrix is the batch's."""
     if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms"}:
         raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin'")
     E = None if num_episodes is None else int(num_episodes)
@@ -387,7 +496,8 @@ def cost_terms_from_config(block, engine, num_episodes=None):
     per_episode = False
     for entry in entries:
         outside = isinstance(entry, dict) and entry.get("kind") == "outside"
-        keys = _OUTSIDE_KEYS if outside else _TERM_KEYS
+        keys = _OUTSIDE_KEYS if outside else _QUADRATIC_KEYS if isinstance(entry, dict) and entry.get("kind") == "quadratic" \
+            else _TERM_KEYS
         if not isinstance(entry, dict) or set(entry) - keys:
             raise ValueError("cost_terms: a term takes %s, got %r" % (sorted(keys), entry))
         if entry.get("kind") not in KINDS and not outside:
@@ -402,6 +512,9 @@ def cost_terms_from_config(block, engine, num_episodes=None):
             repeat = entry.get("repeat", 1)
             if isinstance(repeat, bool) or not isinstance(repeat, int) or repeat < 1:
                 raise ValueError("cost_terms: repeat must be a whole number >= 1, got %r" % (repeat,))
+        elif "periodic" in entry and "repeat" not in entry and any(isinstance(p, dict) and "reference" in p
+                                                                   for p in entry.get("parts") or []):
+            pass                    # (a quadratic whose parts carry the references)
         elif "repeat" in entry or "periodic" in entry:
             raise ValueError("cost_terms: repeat and periodic go with a reference, got %r" % (entry,))
     out = []
@@ -409,7 +522,7 @@ def cost_terms_from_config(block, engine, num_episodes=None):
         terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
         for entry in entries:
             kw = {k: entry[k] for k in ("obs", "action", "action_rate", "index", "weight", "target", "terminal", "low", "high",
-                                        "squared") if k in entry}
+                                        "squared", "matrix", "parts") if k in entry}
             for k in ("weight", "target", "low", "high"):
                 each = _per_episode_value(kw.get(k), E)
                 if each is not None:
@@ -418,6 +531,8 @@ def cost_terms_from_config(block, engine, num_episodes=None):
                 each = _per_episode_reference(entry["reference"], E)
                 kw["reference"] = _expanded(entry["reference"] if each is None else each[e], entry.get("repeat", 1))
                 kw["periodic"] = bool(entry.get("periodic", False))
+            elif "periodic" in entry:
+                kw["periodic"] = bool(entry["periodic"])
             getattr(terms, entry["kind"])(**kw)
         terms.table()               # (an empty block is refused here)
         out.append(terms)
