@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .raw import GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_SPHERE, RawModel
+from .raw import GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_SPHERE, RawModel, _solimp5
 
 LANES = 8          # lanes per particle in the HIP kernel
 MAX_LINKS = 7
@@ -153,6 +153,21 @@ def compile_arm(raw: RawModel, overrides=None, base: "ArmModel" = None) -> ArmMo
     if (raw.solref_limit is not None and tuple(raw.solref_limit) != tuple(raw.solref)) or \
             (raw.solimp_limit is not None and tuple(raw.solimp_limit) != tuple(raw.solimp)):
         raise ValueError("arm kernel: joint limits share the contacts' solref / solimp")
+    # the kernels carry ONE solver set (sol_K .. sol_power below): an element with a set of its own would be simulated with
+    # the model's.  A set equal to the model's is fine (solmix / priority cannot matter then).
+
+    def _own_set(solref, solimp, m_solref, m_solimp):
+        return (solref is not None and tuple(float(x) for x in solref) != tuple(float(x) for x in m_solref)) or \
+            (solimp is not None and _solimp5(solimp) != _solimp5(m_solimp))
+    colliding = [g for b in raw.bodies for g in b.geoms if g.collide] + ([raw.plane] if raw.plane is not None else [])
+    if any(_own_set(g.solref, g.solimp, raw.solref, raw.solimp) for g in colliding):
+        raise ValueError("arm kernel: the colliding geom and the plane share the model's solref / solimp "
+                         "(per-geom sets: the tree engine)")
+    lim_ref = raw.solref if raw.solref_limit is None else raw.solref_limit
+    lim_imp = raw.solimp if raw.solimp_limit is None else raw.solimp_limit
+    if any(j.limited and _own_set(j.solref_limit, j.solimp_limit, lim_ref, lim_imp) for j in joints):
+        raise ValueError("arm kernel: the limited joints share the model's solreflimit / solimplimit "
+                         "(per-joint sets: the tree engine)")
     # ---- per-body inertial + pose at qpos0 ------------------------------------------------
     R0 = [None] * nb
     p0 = [None] * nb

@@ -37,7 +37,7 @@ STATES = [
 def test_f64_matches_oracle(engines, ref_arm, si):
     eng = engines["f64"]
     st = STATES[si]
-    P, H = 200, 32                     # P not a multiple of 8: ragged last wavefront
+    P, H = 203, 32                     # P not a multiple of 8: ragged last wavefront
     rs = np.random.RandomState(10 + si)
     mean = 0.3 * rs.standard_normal((H, 7))
     noise = _noise(P, H, 7, 20 + si)
