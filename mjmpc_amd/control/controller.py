@@ -23,6 +23,7 @@ Extra constructor keywords (all optional, defaults reproduce the reference bit f
 """
 import copy
 import ctypes
+import gc
 import inspect
 from abc import ABC, abstractmethod
 
@@ -686,6 +687,12 @@ class OLGaussianMPC(Controller):
         self.dev.cov.copy_(keep[2])
         self._noise_valid = False       # the dry run left the samples of step + 1 behind
         err = None
+        # The capture is in the runtime's global mode: a graph, stream or engine of an earlier controller that the cycle
+        # collector happened to finalise inside it (hipGraphExecDestroy, hipStreamDestroy, hipFree on this or any thread)
+        # invalidates it.  Dead cycles go now, and the collector stays off until the captures below have ended.
+        gc_was_on = gc.isenabled()
+        gc.collect()
+        gc.disable()
         try:
             if sharded_mono:
                 # the iteration reads one buffer of the mean and writes the other: one graph per direction, replayed in
@@ -719,6 +726,9 @@ class OLGaussianMPC(Controller):
                 self._graph = g
         except Exception as e:          # e.g. a collective that cannot be captured
             err = e
+        finally:
+            if gc_was_on:
+                gc.enable()
         # Sharded runs decide TOGETHER (one all-reduce outside the capture): a rank that fell back alone would
         # issue a different collective sequence than its peers.  Every rank then runs eagerly, or none does.
         if not self.dev.comm.all_agree(err is None, self.dev.device):

@@ -15,7 +15,7 @@ import time
 import numpy as np
 
 from .. import _lib
-from ..models.compile import principal_inertia
+from ..models.compile import principal_inertia, require_f32_power_ratio
 from ..models.raw import TASK_FORWARD, RawModel
 from ._resets import EnvResetWatch, SimulationUnstableError  # noqa: F401
 from .seeding import np_random
@@ -87,6 +87,8 @@ class RolloutEngine(EnvResetWatch):
             raise TypeError("model must be a RawModel or a compiled %s" % self._model_type.__name__)
         if dtype not in _DT:
             raise ValueError("dtype must be 'f32' or 'f64'")
+        if dtype == "f32":
+            require_f32_power_ratio(model)      # (a solimp power ratio beyond float32: refused)
         self.model, self.dtype = model, dtype
         self._code, self._np = _DT[dtype]
         self.num_shards = int(num_shards)       # reported like the reference's num_cpu (infos['total_time'])

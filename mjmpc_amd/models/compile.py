@@ -53,6 +53,29 @@ def _offsets():
 
 ARM_OFFSETS = _offsets()
 
+# The kernels evaluate solimp's y = x^p / mid^(p-1) as num * (1 / den), num = xa^p and den = ma^(p-1) by repeated
+# multiplication (xa, ma = x, mid below mid; 1 - x, 1 - mid above).  In single precision den leaves the normal range once
+# min(mid, 1 - mid)^(p - 1) < 1.2e-38: its reciprocal is no number the row can use, and every row on that side of mid -
+# every friction-loss row, r = 0 - gets a wrong D and aref (measured at power 31, mid 0.05: finite steps off by order 1,
+# profiles/r23_solver_sets.txt).  The compilers record the smallest den of the model's sets
+# (``f32_power_den``); an f32 engine refuses a model below this threshold: the smallest normal with eight orders of room,
+# so that the reciprocal and its Newton step stay normal.  Double precision cannot get there (1e-4^63 = 1e-252).
+F32_POWER_DEN_MIN = 1e-30
+
+
+def power_ratio_den(mid, power):
+    """The smallest denominator the kernels' power loop can form for this (clamped) mid and integer power."""
+    return float(min(mid, 1.0 - mid)) ** (int(power) - 1)
+
+
+def require_f32_power_ratio(model):
+    """Raise NotImplementedError for a compiled model one of whose solimp sets an f32 kernel cannot evaluate."""
+    den = getattr(model, "f32_power_den", 1.0)
+    if den < F32_POWER_DEN_MIN:
+        raise NotImplementedError("single precision: a solimp set has min(mid, 1 - mid)^(power - 1) = %.3g, below %g - the "
+                                  "impedance's power ratio leaves the float32 range; run the model in f64 or lower the power"
+                                  % (den, F32_POWER_DEN_MIN))
+
 
 def _quat2mat(q):
     w, x, y, z = np.asarray(q, float) / np.linalg.norm(q)
@@ -342,10 +365,12 @@ def compile_arm(raw: RawModel, overrides=None, base: "ArmModel" = None) -> ArmMo
         dof_iw, body_iw = base.dof_invweight0.copy(), base.body_invweight0.copy()
     blob = np.concatenate([f[name] for name, _ in ARM_LAYOUT]).astype(np.float64)
     assert blob.size == ARM_BLOB_LEN
-    return ArmModel(blob=blob, nv=nv, nu=len(raw.actuators), d_obs=2 * nv + 6,
-                    timestep=raw.timestep, frame_skip=raw.frame_skip,
-                    target_default=np.asarray(raw.target_pos, float),
-                    ctrl_lo=ctrl_lo, ctrl_hi=ctrl_hi,
-                    body_mass=mass, body_ipos=ipos, body_inertia=inert,
-                    body_invweight0=body_iw, dof_invweight0=dof_iw,
-                    link_of_body=link_of_body)
+    am = ArmModel(blob=blob, nv=nv, nu=len(raw.actuators), d_obs=2 * nv + 6,
+                  timestep=raw.timestep, frame_skip=raw.frame_skip,
+                  target_default=np.asarray(raw.target_pos, float),
+                  ctrl_lo=ctrl_lo, ctrl_hi=ctrl_hi,
+                  body_mass=mass, body_ipos=ipos, body_inertia=inert,
+                  body_invweight0=body_iw, dof_invweight0=dof_iw,
+                  link_of_body=link_of_body)
+    am.f32_power_den = power_ratio_den(mid, power)      # (an f32 engine checks it: require_f32_power_ratio)
+    return am

@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from .compile import _geom_inertial, _quat2mat, _shift_inertia, principal_inertia
+from .compile import _geom_inertial, _quat2mat, _shift_inertia, power_ratio_den, principal_inertia
 from .raw import (EQ_CONNECT, EQ_JOINT, EQ_WELD, GEOM_BOX, GEOM_CAPSULE, GEOM_CYLINDER, GEOM_SPHERE, JOINT_BALL, JOINT_FREE, JOINT_HINGE, JOINT_SLIDE,
                   TASK_FORWARD, TASK_ORIENT, TASK_REACH, RawModel, mix_contact_solver)
 
@@ -643,6 +643,7 @@ def compile_tree(raw: RawModel, overrides=None, base: "TreeModel" = None) -> Tre
         mid, width, power = np.clip(mid, MJ_MINIMP, MJ_MAXIMP), max(width, 0.0), max(power, 1.0)
         if power != int(power) or power > 64:
             raise NotImplementedError("solimp power must be an integer in [1, 64] (MuJoCo's default is 2), got %r" % (power,))
+        power_den[0] = min(power_den[0], power_ratio_den(mid, power))      # (what an f32 engine checks: compile.py)
         K, B = (-tc / (dmax * dmax), -dr / dmax) if direct else (1.0 / (dmax * dmax * tc * tc * dr * dr), 2.0 / (dmax * tc))
         if width <= 1e-15:                                          # MuJoCo getimpedance: a flat impedance
             dmin = dmax = 0.5 * (dmin + dmax)
@@ -655,6 +656,7 @@ def compile_tree(raw: RawModel, overrides=None, base: "TreeModel" = None) -> Tre
     # the model's distinct solver-parameter sets (contacts after mj_contactParam's mixing, joint limits, friction loss,
     # tendon limits): a table in the block, an index per record / dof
     sol_classes = []
+    power_den = [1.0]
 
     def sol_class(solref, solimp):
         vals = tuple(float(x) for x in sol_values(solref, solimp))
@@ -959,4 +961,5 @@ def compile_tree(raw: RawModel, overrides=None, base: "TreeModel" = None) -> Tre
     tm.tendon_invweight0 = tendon_iw
     tm.body_invweight0_rot = base.body_invweight0_rot.copy() if base is not None else body_iw_rot
     tm.general = bool(gen)
+    tm.f32_power_den = power_den[0]
     return tm

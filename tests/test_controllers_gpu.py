@@ -530,6 +530,59 @@ def test_capture_failure_falls_back_to_eager(raw_arm, monkeypatch):
     np.testing.assert_allclose(a_eager, a_graph, rtol=0, atol=1e-9)
 
 
+def test_no_garbage_collection_inside_the_capture(raw_arm):
+    """controller.py, _capture_iteration: the capture is in the runtime's global mode, so an earlier controller's graph,
+    stream or engine finalised by the cycle collector while it is open invalidates it (hipErrorStreamCaptureInvalidated,
+    seen once in the whole suite at the third controller of one test).  Dead cycles are collected before the capture, the
+    collector is off while the stream is capturing, and it is back on afterwards."""
+    import gc
+    import torch
+    from mjmpc_amd.control import MPPI
+    from mjmpc_amd.envs.arm_engine import ArmRolloutEngine, make_device_rollout_fn
+
+    eng = ArmRolloutEngine(raw_arm, dtype="f64")
+    c = MPPI(d_state=eng.d_state, d_obs=eng.d_obs, d_action=7, horizon=16, init_cov=1.0, base_action="null",
+             lam=0.05, num_particles=256, step_size=1.0, alpha=1, gamma=1.0, n_iters=1,
+             action_lows=eng.action_lows, action_highs=eng.action_highs, filter_coeffs=[0.25, 0.8, 0.0], seed=5,
+             noise_mode="device")
+    c.rollout_fn = make_device_rollout_fn(eng)
+    c.set_sim_state_fn = lambda s: None
+    eng.set_env_state(dict(qp=np.array([0.1, 0.2, 0.0, -0.5, 0.0, -0.3, 0.0]), qv=np.zeros(7),
+                           target_pos=np.array([0.2, -0.1, 0.2])))
+    c.enable_graph(post_step=eng.step_state, mono=False)         # (a captured iteration, as in the test above)
+
+    events = []
+
+    class Dead:
+        def __del__(self):
+            events.append("finalised")
+
+    seen, inner = [], c._device_iteration
+
+    def watched():
+        if torch.cuda.is_current_stream_capturing():
+            seen.append((gc.isenabled(), list(events)))
+        return inner()
+
+    c._device_iteration = watched
+    assert gc.isenabled()
+    gc.collect()
+    gc.disable()                # (so that the cycle below is still there when the capture begins)
+    try:
+        d = Dead()
+        d.me = d
+        del d
+        assert events == []
+    finally:
+        gc.enable()
+    a, _ = c.optimize({})
+    torch.cuda.synchronize()
+    assert c._graph is not None and not getattr(c, "graph_fallback", False)
+    assert seen and all(s == (False, ["finalised"]) for s in seen), seen
+    assert gc.isenabled() and np.all(np.isfinite(a))
+    eng.close()
+
+
 def test_semidefinite_covariance_samples_and_indefinite_raises():
     """The device-resident covariance path factors cov on the GPU.  numpy's multivariate_normal (the reference's
     sampler) accepts a positive SEMI-definite covariance; so does the kernel (zero column on a vanished pivot).

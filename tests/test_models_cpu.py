@@ -124,6 +124,39 @@ def test_impedance_power_must_be_a_small_integer():
             compile_arm(dataclasses.replace(raw, solimp=(0.9, 0.95, 0.001, 0.5, bad)))
 
 
+def test_f32_refuses_a_power_ratio_beyond_its_range():
+    """The kernels divide xa^p by ma^(p-1), ma = min(mid, 1 - mid) at worst: below 1e-30 (float32's smallest normal is 1.2e-38)
+    a single-precision engine refuses the model, whichever of its sets holds the pair - the model's, a joint's, an equality's;
+    double precision runs it (1e-4^63 = 1e-252), so the compilers themselves accept it and only record the number."""
+    import dataclasses
+    import pytest
+    from solver_set_cases import DESIGNED_SETS, F32_REFUSED, designed_model
+    from mjmpc_amd.models.compile import F32_POWER_DEN_MIN, compile_arm, require_f32_power_ratio
+    from mjmpc_amd.models.compile_tree import compile_tree
+    from mjmpc_amd.models.reacher7dof import reacher7dof_raw
+    raw = reacher7dof_raw()
+    for mid, power, ok in ((0.5, 64.0, True), (0.05, 24.0, True), (0.05, 25.0, False), (0.05, 31.0, False), (0.95, 31.0, False),
+                           (1e-4, 8.0, True), (1e-4, 9.0, False), (0.3, 1.0, True)):
+        for compiler in (compile_arm, compile_tree):
+            m = compiler(dataclasses.replace(raw, solimp=(0.9, 0.95, 0.001, mid, power)))
+            assert (m.f32_power_den >= F32_POWER_DEN_MIN) == ok, (mid, power, m.f32_power_den)
+            if ok:
+                require_f32_power_ratio(m)
+            else:
+                with pytest.raises(NotImplementedError, match="single precision"):
+                    require_f32_power_ratio(m)
+    # mid 0 is clamped to 1e-4 by the tree compiler, as MuJoCo does, before the ratio is judged
+    assert compile_tree(dataclasses.replace(raw, solimp=(0.9, 0.95, 0.001, 0.0, 8.0))).f32_power_den == pytest.approx(1e-28)
+    for kind in ("limit", "friction_loss", "joint_equality", "pair", "tendon_limit"):
+        for name, sol in DESIGNED_SETS.items():
+            m = compile_tree(designed_model(kind, sol))
+            if name in F32_REFUSED:
+                with pytest.raises(NotImplementedError):
+                    require_f32_power_ratio(m)
+            else:
+                require_f32_power_ratio(m)
+
+
 def test_loader_position_servos_pairs_and_self_collision(tmp_path):
     """Round 3's MJCF additions on a small model: an object on a slide + hinge, a two-link manipulator with <position> servos,
     an explicit <contact><pair>, and MuJoCo's contype / conaffinity rule for body geoms against each other."""
