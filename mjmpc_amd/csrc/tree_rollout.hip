@@ -1709,15 +1709,24 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
 
     // my place on the path of every contact point (5 bits each: 1 + the distance from the point's link up to me, 0 if I
     // am not on that path) - a constant of the model; the contact code reads it instead of two LDS tables
+    // (DP = 32: the root of a 32-link path sits at distance 31, code 32 - one more than five bits hold; own_far marks those
+    // points and their five bits stay 0)
     unsigned long long own_path0 = 0;
     unsigned own_path1 = 0;
+    unsigned own_far = 0;
     {
         const int ns_ = min((int)M[T_N_SPHERE], NS);
         const bool dof_ = l < (int)M[T_NV];
         for (int s = 0; s < ns_; ++s) {
             const T* sp = M + T_SPH + s * TREE_SPH_STRIDE;
             const int idx = (int)sp[11] - depth;
-            const int code = (dof_ && idx >= 0 && idx < DP && AT[idx * PL + (int)sp[0]] == l) ? idx + 1 : 0;
+            int code = (dof_ && idx >= 0 && idx < DP && AT[idx * PL + (int)sp[0]] == l) ? idx + 1 : 0;
+            if constexpr (DP == 32) {
+                if (code == 32) {
+                    own_far |= 1u << s;
+                    code = 0;
+                }
+            }
             if (s < 12) own_path0 |= (unsigned long long)code << (5 * s);
             else own_path1 |= (unsigned)code << (5 * (s - 12));
         }
@@ -2557,7 +2566,8 @@ __global__ __launch_bounds__(64 * wg_waves(DP, FRIC, sizeof(T), PL), min_waves(s
             // (or the point is not in contact for my particle)
             // (where I sit on the point's path is a constant of the model, packed once per launch: own_path)
             auto own_idx = [&](int s) -> int {
-                const int code = s < 12 ? (int)((own_path0 >> (5 * s)) & 31ull) : (int)((own_path1 >> (5 * (s - 12))) & 31u);
+                int code = s < 12 ? (int)((own_path0 >> (5 * s)) & 31ull) : (int)((own_path1 >> (5 * (s - 12))) & 31u);
+                if constexpr (DP == 32) code = ((own_far >> s) & 1u) ? 32 : code;
                 return ((cinst >> s) & 1u) ? code - 1 : -1;
             };
             for (unsigned um = ucinst; um; um &= um - 1) {
