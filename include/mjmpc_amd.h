@@ -38,7 +38,7 @@ extern "C" {
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
  *      the DMD-MPC episode batches', mjmpc_cost_terms, mjmpc_cost_terms_track / _track_batch, mjmpc_cost_terms_rate /
- *      _rate_batch and mjmpc_cost_terms_quad / _quad_batch.) */
+ *      _rate_batch, mjmpc_cost_terms_quad / _quad_batch and mjmpc_points.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -921,6 +921,36 @@ int mjmpc_cost_terms_quad_batch(int dtype, int E, int64_t P, int H, int d_obs, i
                                 const int64_t* d_step, int64_t step_bias, double* d_prev_actions, int advance_prev,
                                 const double* d_quad, int quad_len, void* d_costs, const double* d_gseq, double* d_q0,
                                 void* stream);
+
+/* World positions of points on any bodies as observation entries, one launch in front of any cost entry above.
+ * For each of N observation rows (d_obs_rows, dtype [N][d_obs]; N = P H, or E P H for an episode batch: rows are independent)
+ * the kernel reads qpos - nq entries in MuJoCo's layout, from entry 0 of the row, as the reach / orient observation has them -,
+ * runs the points program over it in double and writes the augmented row d_out, dtype [N][d_obs + 3 n_points + 3 n_diff]: the
+ * observation's d_obs entries bit for bit, then world x, y, z of every point in program order, then a - b of every difference,
+ * one double subtraction per component; every new entry is rounded once to dtype.  The cost entries then take d_out with
+ * d_obs + 3 n_points + 3 n_diff as their d_obs.  The positions are those of the row's own qpos (the built-in `site` block of
+ * the observation lags one substep).
+ *
+ * The points program d_program is float64 [n_rows + n_diff][16] on the device.  Its first n_rows rows hold, for every point
+ * in turn, the nodes of the path from the root to the point's body in order - one per jointed body; a body without a joint is
+ * folded into the fixed pose of the node (or the point) behind it by the host, so a path holds at most 33 nodes - and then the
+ * point itself, which closes the path:
+ *   [0] kind: 0 POINT, 1 HINGE, 2 SLIDE, 3 BALL, 4 FREE          [1] the joint's qpos address   [2] qpos0 (hinge, slide)
+ *   [3 .. 5]   node: the body's position in the frame before it; POINT: the point's position in the frame of the last node
+ *   [6 .. 9]   node: the body's orientation in the frame before it, a unit quaternion (w, x, y, z)
+ *   [10 .. 12] the joint's unit axis in the body frame (hinge, slide)
+ *   [13 .. 15] the joint's anchor in the body frame (hinge, ball)
+ * A path starts at the world frame.  A node moves the frame to frame o (position, orientation) and applies its joint: a hinge
+ * turns the frame by q - qpos0 about the axis through the anchor and a ball by qpos[adr .. adr + 4], the anchor held fixed; a
+ * slide moves it by q - qpos0 along the axis; a free joint replaces the frame by qpos[adr .. adr + 3], qpos[adr + 3 .. adr + 7]
+ * (MuJoCo's mj_kinematics).  The quaternions of qpos rotate as q / |q|.  The last n_diff rows are {5, a, b, 0 ..}: point a minus
+ * point b, both indices in program order.  The table's contents are the caller's to check (envs/cost_terms.py builds it); the
+ * kernel holds every qpos address inside nq and every point index inside n_points whatever the table says.
+ * MJMPC_E_BADARG before anything is launched: a null pointer, an unknown dtype, N or d_obs below 1, nq outside 1 .. d_obs,
+ * n_points outside 1 .. 16, n_diff outside 0 .. 16, n_rows outside n_points .. 544, an observation row that does not fit the
+ * tile with its points (60 KiB of LDS). */
+int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void* d_obs_rows, const double* d_program, int n_rows,
+                 int n_points, int n_diff, void* d_out, void* stream);
 
 #ifdef __cplusplus
 }

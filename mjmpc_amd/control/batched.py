@@ -93,6 +93,8 @@ class _EpisodeBatch:
     _prev_actions = None    # ... with rate rows every episode's last applied action, float64 [E][A] on the device (NaN: none yet)
     _quad = None            # the tables hold quadratic groups or signed linear rows: mjmpc_cost_terms_quad_batch with
                             # this pool of matrices on the device, one for all episodes
+    _points = None          # the tables name points: (program, n_rows, n_points, n_diff, d_obs + n_extra, the augmented
+                            # observations of the rollouts [E P][H][.] and of the real-env steps [E][.])
     _terms = None           # set_cost_terms: (tables on the device, rows, per episode?, keep_builtin, a row reads an action?)
     _terms_nobs = None      # ... the rollouts' next observations [E P][H][d_obs] (only while terms are set)
     _terms_env = None       # ... the real-env step's own next observations [E][d_obs] and actions [E][A] in the batch's dtype
@@ -196,6 +198,7 @@ class _EpisodeBatch:
         self.lib = self.engine._lib
         self.model = model
         self.raw = raw_model if isinstance(raw_model, RawModel) else None
+        self.engine.raw = self.raw      # (the engine was made from the compiled model; CostTerms.point reads the bodies' poses)
         self.shard_blobs = None         # randomize_dynamics: the model blocks of the rollouts, [sets][num_shards][blob length]
         A = model.nu
         self.num_episodes, self.horizon, self.num_particles, self.d_action = E, H, P, A
@@ -363,6 +366,13 @@ class _EpisodeBatch:
             if pool is not None and not np.array_equal(other, pool):
                 raise ValueError("set_cost_terms: episode %d's quadratic matrices differ from episode 0's (the episodes share "
                                  "one pool of matrices; weights, targets and references may differ)" % e)
+        points = each[0].points_table(engine)       # (one points program for the batch)
+        for e, t in enumerate(each):
+            other = t.points_table(engine)
+            if (other is None) != (points is None) or (points is not None and (
+                    other[1:] != points[1:] or not np.array_equal(other[0], points[0]))):
+                raise ValueError("set_cost_terms: episode %d's points or differences differ from episode 0's (the episodes "
+                                 "share them; weights, targets and references may differ)" % e)
         return np.stack(tables), bool(keep), bool(np.any(first[:, 1] != 0))
 
     @staticmethod
@@ -403,10 +413,13 @@ class _EpisodeBatch:
         it, the launch that costs the real-env step reads it and then records the step's action.  Tables with a quadratic group
         or a signed linear row go through ``mjmpc_cost_terms_quad_batch``, which serves every row: the groups'
         matrices are one pool for the batch - per episode the weights, targets and references may differ, the matrices not
-        (``ValueError`` naming the episode).  Everything is checked on the host first (``ValueError``); callable between
-        steps."""
+        (``ValueError`` naming the episode).  Tables with points or differences put ``mjmpc_points`` over the
+        ``E P H`` rows between the rollout and the cost entry, as the single engines do; the episodes share the points and
+        differences (``ValueError`` naming the episode) and keep their own weights, targets and references.  Everything is
+        checked on the host first (``ValueError``); callable between steps."""
         if terms is None:
             self._terms = self._terms_nobs = self._terms_env = self._track = self._prev_actions = self._quad = None
+            self._points = None
             self._rate = False
             return
         tables, keep, reads_actions = self._resolve_cost_terms(terms, self.engine, self.num_episodes)
@@ -429,16 +442,33 @@ class _EpisodeBatch:
                            torch.empty((E, self.d_action), dtype=tdt, device=dev) if reads_actions else None)
         self._prev_actions = (torch.full((E, self.d_action), float("nan"), dtype=torch.float64, device=dev) if rate_rows
                               else None)
+        self._points = None
+        first = terms[0] if isinstance(terms, (list, tuple)) else terms
+        points = first.points_table(self.engine)
+        if points is not None:
+            #  one program for the batch; the augmented rows of the rollouts' and of the real-env steps' observations
+            d_aug = self.d_obs + first.n_extra
+            self._points = (self._upload(points[0]),) + tuple(points[1:]) + (
+                d_aug, torch.empty((E * self.num_particles, self.horizon, d_aug), dtype=tdt, device=dev),
+                torch.empty((E, d_aug), dtype=tdt, device=dev))
 
     def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s, bias=0, advance_prev=0):
         """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s); with tracked terms
         ``mjmpc_cost_terms_track_batch`` at env time ``_step_dev + bias``; with rate rows or one-sided kinds
         ``mjmpc_cost_terms_rate_batch`` (``advance_prev``: the E elements record their actions in ``_prev_actions``)."""
         tables, K, per_episode, keep, reads_actions = self._terms
+        d_obs = self.d_obs
+        if self._points is not None:
+            # (DESIGN 12.4) the same launch as the single engines', over E P H rows: the cost entry reads the augmented rows
+            program, n_rows, n_points, n_diff, d_aug, aug_rollout, aug_env = self._points
+            aug = aug_rollout if nobs is self._terms_nobs else aug_env
+            _lib.check(self.lib.mjmpc_points(self._code, self.num_episodes * P * H, d_obs, self.engine._nq, _vp(nobs),
+                                             _vp(program), n_rows, n_points, n_diff, _vp(aug), s))
+            nobs, d_obs = aug, d_aug
         if self._quad is not None:
             refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)
             _lib.check(self.lib.mjmpc_cost_terms_quad_batch(
-                self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs), _vp(act), _vp(tables), K, per_episode,
+                self._code, self.num_episodes, P, H, d_obs, self.d_action, _vp(nobs), _vp(act), _vp(tables), K, per_episode,
                 keep, terminal, _vp(refs), N, R, ref_per_episode, periodic, _vp(self._step_dev) if refs is not None else None,
                 bias, _vp(self._prev_actions), advance_prev, _vp(self._quad), self._quad.shape[0], _vp(costs), _vp(gseq),
                 _vp(q0), s))
@@ -446,18 +476,18 @@ class _EpisodeBatch:
         if self._rate:
             refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)
             _lib.check(self.lib.mjmpc_cost_terms_rate_batch(
-                self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs), _vp(act), _vp(tables), K, per_episode,
+                self._code, self.num_episodes, P, H, d_obs, self.d_action, _vp(nobs), _vp(act), _vp(tables), K, per_episode,
                 keep, terminal, _vp(refs), N, R, ref_per_episode, periodic, _vp(self._step_dev) if refs is not None else None,
                 bias, _vp(self._prev_actions), advance_prev, _vp(costs), _vp(gseq), _vp(q0), s))
             return
         if self._track is not None:
             refs, N, R, ref_per_episode, periodic = self._track
             _lib.check(self.lib.mjmpc_cost_terms_track_batch(
-                self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs), _vp(act) if reads_actions else None,
+                self._code, self.num_episodes, P, H, d_obs, self.d_action, _vp(nobs), _vp(act) if reads_actions else None,
                 _vp(tables), K, per_episode, keep, terminal, _vp(refs), N, R, ref_per_episode, periodic, _vp(self._step_dev),
                 bias, _vp(costs), _vp(gseq), _vp(q0), s))
             return
-        _lib.check(self.lib.mjmpc_cost_terms_batch(self._code, self.num_episodes, P, H, self.d_obs, self.d_action, _vp(nobs),
+        _lib.check(self.lib.mjmpc_cost_terms_batch(self._code, self.num_episodes, P, H, d_obs, self.d_action, _vp(nobs),
                                                    _vp(act) if reads_actions else None, _vp(tables), K, per_episode, keep,
                                                    terminal, _vp(costs), _vp(gseq), _vp(q0), s))
 

@@ -1,0 +1,220 @@
+// World positions of user-named points for the cost terms: a launch between a rollout and its
+// cost launch that copies every observation row into an augmented row and appends, in double whatever the storage type, the
+// world positions of up to 16 points on any bodies and up to 16 differences of two points.  The cost kernels then read these
+// entries as ordinary observation entries: nothing in cost_terms.hip or in a rollout translation unit changes.
+//
+// The points program (float64 [n_rows + n_diff][16], include/mjmpc_amd.h) is wave-uniform: every lane walks the same rows over
+// its own qpos.  A row is one node of a point's path from the root (fixed pose in the parent's frame, then the joint), or the
+// point itself, which closes the path:
+//   col 0        kind: 0 POINT, 1 HINGE, 2 SLIDE, 3 BALL, 4 FREE
+//   col 1, 2     qpos address of the joint, qpos0 (hinge / slide: MJCF ref)
+//   col 3 .. 5   node: the body's position in its parent's frame; POINT: the point in the frame of the last node
+//   col 6 .. 9   node: the body's orientation in its parent's frame, a unit quaternion (w, x, y, z)
+//   col 10 .. 12 unit joint axis (hinge, slide), body frame          col 13 .. 15 anchor (hinge, ball), body frame
+// The semantics are MuJoCo's mj_kinematics, as the test oracle's kinematics() states them: the frame moves to
+// parent o (pos, quat); a hinge turns it by q - qpos0 about the axis through the anchor and a ball by the stored quaternion,
+// the anchor held fixed; a slide moves it by q - qpos0 along the axis; a free joint replaces it by qpos[adr .. adr + 7].  The
+// quaternions of qpos are used as stored - no normalised copy is written anywhere - and rotate as q / |q|, which is what
+// the oracle's quat2mat does.  Only the current frame (a position and a unit quaternion: 7 doubles) lives in registers; paths
+// that share ancestors recompute them: no per-lane frame storage, no scratch.  Measured, the launch is bound by the nodes'
+// arithmetic (2.5 - 4 us per node over 4096 x 32 rows, much of it the hinge's double-precision sincos), not by the bytes it
+// moves: profiles/r25_points.txt.
+// The n_diff rows behind the paths are {5, a, b}: the entry point a - point b, one double subtraction per component.
+//
+// Shape (cost_terms.hip's): a workgroup takes `rows` consecutive observation rows - they lie back to back in memory -, copies
+// them into LDS with unit-stride loads (odd row pitch: the lanes' column reads spread over the banks), lane j walks the program
+// over row j and parks its points in LDS as doubles, laid out [entry][lane] (lane-consecutive, no bank conflict); then all
+// lanes write the augmented tile, which is back to back in memory too, with unit stride: the observation's words as they came
+// (bit for bit), the points rounded once to the storage type, the differences formed from the parked doubles and rounded once.
+// Node rows are one address for all lanes, read const __restrict__ through the scalar cache; the joint-kind branch is uniform.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/mjmpc_amd.h"
+
+namespace mjmpc {
+int set_error(int code, const char* what, const char* detail);      // capi.hip: the message mjmpc_last_error() returns
+
+namespace {
+
+constexpr int PT_WG = 256;                  // threads of a workgroup and the most rows of its tile: one lane a row.  Tiles of 64
+                                            // and 128 rows (as many threads) measured within 2 % of it: profiles/r25_points.txt
+constexpr int PT_ROW = 16;                  // doubles of a program row
+constexpr int PT_MAX_POINTS = 16, PT_MAX_DIFF = 16, PT_MAX_NODES = 33;
+constexpr int PT_MAX_ROWS = PT_MAX_POINTS * (PT_MAX_NODES + 1);
+constexpr int PT_LDS_BYTES = 60 * 1024;     // the tile's share of a workgroup's 64 KiB
+
+__host__ __device__ inline int pt_pitch(int n) { return n | 1; }
+
+struct PtFrame {
+    double p[3], q[4];      // origin in the world; orientation, a unit quaternion (w, x, y, z)
+};
+
+// v turned by the unit quaternion q: v + 2 w (u x v) + 2 u x (u x v)
+__device__ __forceinline__ void pt_rotate(const double* q, double x, double y, double z, double* out) {
+    const double tx = 2.0 * (q[2] * z - q[3] * y), ty = 2.0 * (q[3] * x - q[1] * z), tz = 2.0 * (q[1] * y - q[2] * x);
+    out[0] = x + q[0] * tx + (q[2] * tz - q[3] * ty);
+    out[1] = y + q[0] * ty + (q[3] * tx - q[1] * tz);
+    out[2] = z + q[0] * tz + (q[1] * ty - q[2] * tx);
+}
+
+// q <- q * (w, x, y, z)
+__device__ __forceinline__ void pt_mul(double* q, double w, double x, double y, double z) {
+    const double a = q[0], b = q[1], c = q[2], d = q[3];
+    q[0] = a * w - b * x - c * y - d * z;
+    q[1] = a * x + b * w + c * z - d * y;
+    q[2] = a * y - b * z + c * w + d * x;
+    q[3] = a * z + b * y - c * x + d * w;
+}
+
+// grid: ceil(n / rows) workgroups of max(rows, 64) threads; dynamic LDS: rows x pitch(d_obs) words of T, then 3 n_points x rows doubles
+template <typename T>
+__global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs, const double* __restrict__ prog, int n_rows,
+                                                       int n_points, int n_diff, long n, int d_obs, int nq, int rows,
+                                                       T* __restrict__ out) {
+    extern __shared__ double pt_tile_raw[];
+    __shared__ int s_da[PT_MAX_DIFF], s_db[PT_MAX_DIFF];
+    const int po = pt_pitch(d_obs);
+    T* const tile = reinterpret_cast<T*>(pt_tile_raw);
+    double* const pts = pt_tile_raw + ((long)rows * po * sizeof(T) + 7) / 8;
+    const long e0 = (long)blockIdx.x * rows;
+    const int mine = n - e0 < rows ? (int)(n - e0) : rows;
+    const int j = threadIdx.x, wg = blockDim.x;
+
+    if (j < n_diff) {                       // a difference's two points, held below n_points whatever the table says
+        const double* row = prog + (long)PT_ROW * (n_rows + j);
+        const int a = (int)row[1], b = (int)row[2];
+        s_da[j] = a < 0 ? 0 : a < n_points ? a : n_points - 1;
+        s_db[j] = b < 0 ? 0 : b < n_points ? b : n_points - 1;
+    }
+    {                                       // the tile: unit stride over the lanes
+        const T* __restrict__ src = obs + e0 * d_obs;
+        const int total = mine * d_obs;
+        int i = j, r = i / d_obs, c = i - r * d_obs;
+        const int dr = wg / d_obs, dc = wg - dr * d_obs;
+        for (; i < total; i += wg) {
+            tile[r * po + c] = src[i];
+            r += dr;
+            c += dc;
+            if (c >= d_obs) { c -= d_obs; ++r; }
+        }
+    }
+    __syncthreads();
+
+    if (j < mine) {
+        const T* const my = tile + j * po;
+        // entry i of my qpos, held inside it whatever the table says
+        auto qpos = [&](int i) { return (double)my[i < 0 ? 0 : i < nq ? i : nq - 1]; };
+        PtFrame f{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
+        int point = 0;
+        for (int k = 0; k < n_rows; ++k) {
+            const double* __restrict__ row = prog + (long)PT_ROW * k;
+            const int kind = (int)row[0];
+            double t[3];
+            if (kind == 0) {                // the point closes its path; the next one starts at the world frame
+                pt_rotate(f.q, row[3], row[4], row[5], t);
+                if (point < n_points) {
+                    pts[(3 * point + 0) * rows + j] = f.p[0] + t[0];
+                    pts[(3 * point + 1) * rows + j] = f.p[1] + t[1];
+                    pts[(3 * point + 2) * rows + j] = f.p[2] + t[2];
+                }
+                ++point;
+                f = PtFrame{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
+                continue;
+            }
+            const int adr = (int)row[1];
+            if (kind == 4) {                // free: the frame is qpos' own
+                const double w = qpos(adr + 3), x = qpos(adr + 4), y = qpos(adr + 5), z = qpos(adr + 6);
+                const double s = 1.0 / sqrt(w * w + x * x + y * y + z * z);
+                f = PtFrame{{qpos(adr), qpos(adr + 1), qpos(adr + 2)}, {w * s, x * s, y * s, z * s}};
+                continue;
+            }
+            pt_rotate(f.q, row[3], row[4], row[5], t);
+            f.p[0] += t[0]; f.p[1] += t[1]; f.p[2] += t[2];
+            pt_mul(f.q, row[6], row[7], row[8], row[9]);
+            if (kind == 2) {                // slide: along the axis, no rotation
+                const double d = qpos(adr) - row[2];
+                pt_rotate(f.q, row[10], row[11], row[12], t);
+                f.p[0] += t[0] * d; f.p[1] += t[1] * d; f.p[2] += t[2] * d;
+                continue;
+            }
+            // hinge, ball: about the anchor, which stays where it is
+            double anchor[3];
+            pt_rotate(f.q, row[13], row[14], row[15], t);
+            anchor[0] = f.p[0] + t[0]; anchor[1] = f.p[1] + t[1]; anchor[2] = f.p[2] + t[2];
+            if (kind == 1) {
+                const double half = 0.5 * (qpos(adr) - row[2]);
+                double sn, cs;
+                sincos(half, &sn, &cs);
+                pt_mul(f.q, cs, row[10] * sn, row[11] * sn, row[12] * sn);
+            } else {
+                const double w = qpos(adr), x = qpos(adr + 1), y = qpos(adr + 2), z = qpos(adr + 3);
+                const double s = 1.0 / sqrt(w * w + x * x + y * y + z * z);
+                pt_mul(f.q, w * s, x * s, y * s, z * s);
+            }
+            pt_rotate(f.q, row[13], row[14], row[15], t);
+            f.p[0] = anchor[0] - t[0]; f.p[1] = anchor[1] - t[1]; f.p[2] = anchor[2] - t[2];
+        }
+    }
+    __syncthreads();
+
+    {                                       // the augmented tile: unit stride over the lanes
+        const int d_pts = 3 * n_points, d_aug = d_obs + d_pts + 3 * n_diff;
+        T* __restrict__ dst = out + e0 * d_aug;
+        const long total = (long)mine * d_aug;
+        int r = j / d_aug, c = j - r * d_aug;
+        const int dr = wg / d_aug, dc = wg - dr * d_aug;
+        for (long i = j; i < total; i += wg) {
+            T v;
+            if (c < d_obs) {
+                v = tile[r * po + c];
+            } else if (c < d_obs + d_pts) {
+                v = (T)pts[(c - d_obs) * rows + r];
+            } else {
+                const int m = c - d_obs - d_pts, d = m / 3, ax = m - 3 * d;
+                v = (T)(pts[(3 * s_da[d] + ax) * rows + r] - pts[(3 * s_db[d] + ax) * rows + r]);
+            }
+            dst[i] = v;
+            r += dr;
+            c += dc;
+            if (c >= d_aug) { c -= d_aug; ++r; }
+        }
+    }
+}
+
+int bad(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_points", detail); }
+
+}  // namespace
+}  // namespace mjmpc
+
+extern "C" int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void* d_obs_rows, const double* d_program, int n_rows,
+                            int n_points, int n_diff, void* d_out, void* stream) {
+    using namespace mjmpc;
+    if (!d_obs_rows || !d_program || !d_out) return bad("null pointer");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad("unknown dtype");
+    if (N < 1 || d_obs < 1) return bad("N and d_obs must be >= 1");
+    if (nq < 1 || nq > d_obs) return bad("nq must be in 1 .. d_obs: qpos opens the observation");
+    if (n_points < 1 || n_points > PT_MAX_POINTS) return bad("n_points must be in 1 .. 16");
+    if (n_diff < 0 || n_diff > PT_MAX_DIFF) return bad("n_diff must be in 0 .. 16");
+    if (n_rows < n_points || n_rows > PT_MAX_ROWS) return bad("n_rows must be in n_points .. 544 (16 paths of 33 nodes and a point)");
+    const long word = dtype == MJMPC_F32 ? 4 : 8;
+    const long pts_bytes = 8L * 3 * n_points;                       // a row's parked points
+    if ((long)d_obs > (PT_LDS_BYTES - pts_bytes - 8) / word - 1)
+        return bad("an observation row and its points of more than 60 KiB");
+    int rows = PT_WG;
+    auto lds = [&](int r) { return (r * word * pt_pitch(d_obs) + 7) / 8 * 8 + r * pts_bytes; };
+    while (lds(rows) > PT_LDS_BYTES) rows >>= 1;
+    const long blocks = ((long)N + rows - 1) / rows;
+    if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
+    if (dtype == MJMPC_F32)
+        hipLaunchKernelGGL(points_kernel<float>, dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), (size_t)lds(rows), (hipStream_t)stream,
+                           (const float*)d_obs_rows, d_program, n_rows, n_points, n_diff, (long)N, d_obs, nq, rows, (float*)d_out);
+    else
+        hipLaunchKernelGGL(points_kernel<double>, dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), (size_t)lds(rows), (hipStream_t)stream,
+                           (const double*)d_obs_rows, d_program, n_rows, n_points, n_diff, (long)N, d_obs, nq, rows,
+                           (double*)d_out);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_points", hipGetErrorString(e));
+}

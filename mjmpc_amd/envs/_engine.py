@@ -77,6 +77,8 @@ class RolloutEngine(EnvResetWatch):
     _prev_action = None             # ... with rate rows the action last applied to the controlled env, float64 [A] on the device
     _terms_quad = None              # the table holds quadratic groups or signed linear rows: mjmpc_cost_terms_quad
                                     # with this pool of matrices, float64 on the device (one zero without a group)
+    _points = None                  # the table names points: (program on the device, n_rows, n_points, n_diff, n_extra)
+    _points_last = None             # ... the augmented observations of the last cost launch (cost_observations)
     _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
 
     def __init__(self, model, device=0, dtype="f64", num_shards=1):
@@ -344,7 +346,7 @@ class RolloutEngine(EnvResetWatch):
         terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  The episode batches have their own
         ``set_cost_terms`` (``control/batched.py``, DESIGN 10.8: one table for the batch or one per episode).  Covered: both
         rollout engines and all six episode-batch classes, with constant targets, tracked references, action rates,
-        one-sided bounds, quadratic forms with full matrices and signed linear rows.  Not covered: the fused launches, ``AnalyticRolloutEngine``, world sizes above 1.
+        one-sided bounds, quadratic forms with full matrices, signed linear rows and world positions of points on any body.  Not covered: the fused launches, ``AnalyticRolloutEngine``, world sizes above 1.
 
         Terms with a ``reference=`` are costed by ``mjmpc_cost_terms_track``: their reference goes to the device
         with an env-time counter (``track_step()``, 0 now) that every plan reads and every step of the controlled env
@@ -359,20 +361,32 @@ class RolloutEngine(EnvResetWatch):
 
         Terms with a quadratic group or a signed linear row are costed by ``mjmpc_cost_terms_quad``, which serves
         every other row too: the groups' matrices go to the device as one pool (``CostTerms.quad_table``); counter and previous
-        action behave exactly as on the rate path."""
+        action behave exactly as on the rate path.
+
+        Terms that name points or differences (``CostTerms.point`` / ``difference``) put one launch,
+        ``mjmpc_points``, in front of whichever cost entry the table takes: it copies the next observations into a buffer of the
+        engine's with the world positions of the points, at each row's own ``qpos``, behind every row, and the cost entry reads
+        that buffer with ``d_obs + n_extra`` entries a row (``cost_observations()`` returns it).  The observations a rollout
+        returns keep their width; the counter, the previous action, ``terminal`` and the guard behave as without points; a table
+        without points launches nothing new."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
                                "controllers %s; set the terms first, then call make_device_rollout_fn"
                                % (("with", "no fused launches") if self._closure_terms else ("without", "the fused launches")))
         if terms is None:
             self._cost_terms = self._terms_dev = self._track_ref = self._track_step = self._prev_action = None
-            self._terms_quad = None
+            self._terms_quad = self._points = self._points_last = None
             self._terms_read_actions = self._terms_rate = False
             return
         table = np.ascontiguousarray(terms.table(self), np.float64)       # (ValueError before anything reaches the device)
         ref = terms.reference_table(self)
         pool = terms.quad_table(self)
+        points = terms.points_table(self)
         torch = _torch()
+        self._points = self._points_last = None
+        if points is not None:
+            # (DESIGN 12.4: every cost launch is preceded by mjmpc_points into a buffer of the engine's)
+            self._points = (torch.from_numpy(points[0]).to(self.device),) + tuple(points[1:]) + (int(terms.n_extra),)
         self._terms_dev = torch.from_numpy(table).to(self.device)
         self._terms_rate = bool(terms.needs_rate_entry)
         self._terms_quad = None
@@ -429,7 +443,27 @@ class RolloutEngine(EnvResetWatch):
             raise RuntimeError("prev_action: no action-rate cost terms are set (CostTerms with action_rate=)")
         return self._prev_action.cpu().numpy().copy()
 
+    def cost_observations(self):
+        """The augmented observations of the last cost launch with points: ``[P][H][d_obs + n_extra]`` (a
+        ``step_state``: ``[d_obs + n_extra]``) in the engine's dtype, on the device - the next observations bit for bit, then
+        three entries per point and per difference.  The engine's own buffer: the next launch of that shape rewrites it."""
+        if self._points is None or self._points_last is None:
+            raise RuntimeError("cost_observations: no cost terms with points have been launched (CostTerms.point)")
+        return self._points_last
+
     def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, advance=False):
+        d_obs = self.d_obs
+        if self._points is not None:
+            # (DESIGN 12.4) the world positions first: the cost entry below then sees d_obs + n_extra entries a row.  The
+            # controlled env's step has a buffer of its own, so a loop of plans and steps never reallocates (captures)
+            program, n_rows, n_points, n_diff, n_extra = self._points
+            step = (P, H) == (1, 1)
+            aug = self._buffer("points_step" if step else "points_obs",
+                               (self.d_obs + n_extra,) if nobs.dim() == 1 else (P, H, self.d_obs + n_extra))
+            _lib.check(self._lib.mjmpc_points(self._code, P * H, self.d_obs, self._nq, _ptr(nobs), _ptr(program), n_rows,
+                                              n_points, n_diff, _ptr(aug), self._stream()))
+            self._points_last = nobs = aug
+            d_obs += n_extra
         t = self._terms_dev
         act = _ptr(act if self._terms_read_actions else None)
         keep = int(self._cost_terms.keep_builtin)
@@ -437,7 +471,7 @@ class RolloutEngine(EnvResetWatch):
             # (the rate entry's arguments and the pool)
             r, q = self._track_ref, self._terms_quad
             _lib.check(self._lib.mjmpc_cost_terms_quad(
-                self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t), t.shape[0], keep, int(bool(terminal)),
+                self._code, P, H, d_obs, self.d_action, _ptr(nobs), act, _ptr(t), t.shape[0], keep, int(bool(terminal)),
                 _ptr(r), 0 if r is None else r.shape[0], 0 if r is None else r.shape[1], self._track_periodic,
                 _ptr(self._track_step), 0, int(bool(advance)), _ptr(self._prev_action), _ptr(q), q.shape[0], _ptr(costs),
                 self._stream()))
@@ -446,17 +480,17 @@ class RolloutEngine(EnvResetWatch):
             # (tracked or not, and as below the advance - counter and previous action - is part of the launch)
             r = self._track_ref
             _lib.check(self._lib.mjmpc_cost_terms_rate(
-                self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t), t.shape[0], keep, int(bool(terminal)),
+                self._code, P, H, d_obs, self.d_action, _ptr(nobs), act, _ptr(t), t.shape[0], keep, int(bool(terminal)),
                 _ptr(r), 0 if r is None else r.shape[0], 0 if r is None else r.shape[1], self._track_periodic,
                 _ptr(self._track_step), 0, int(bool(advance)), _ptr(self._prev_action), _ptr(costs), self._stream()))
             return
         if self._track_step is None:
-            _lib.check(self._lib.mjmpc_cost_terms(self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t),
+            _lib.check(self._lib.mjmpc_cost_terms(self._code, P, H, d_obs, self.d_action, _ptr(nobs), act, _ptr(t),
                                                   t.shape[0], keep, int(bool(terminal)), _ptr(costs), self._stream()))
             return
         # (the advance is part of the library launch, not a torch op: a captured iteration keeps its launch tape)
         r = self._track_ref
-        _lib.check(self._lib.mjmpc_cost_terms_track(self._code, P, H, self.d_obs, self.d_action, _ptr(nobs), act, _ptr(t),
+        _lib.check(self._lib.mjmpc_cost_terms_track(self._code, P, H, d_obs, self.d_action, _ptr(nobs), act, _ptr(t),
                                                     t.shape[0], keep, int(bool(terminal)), _ptr(r), r.shape[0], r.shape[1],
                                                     self._track_periodic, _ptr(self._track_step), 0, int(bool(advance)),
                                                     _ptr(costs), self._stream()))

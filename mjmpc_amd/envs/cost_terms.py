@@ -52,10 +52,24 @@ a term of its own.  ``linear`` is kind 9, ``weight * r`` with its sign.  A table
     terms.quadratic(obs=[0, 1, 2, 3], matrix=P_riccati, terminal=True)              # x' P x at a plan's last step
     terms.quadratic(parts=[dict(obs="qpos"), dict(obs="qvel"), dict(action="all")], matrix=QNR)
     terms.linear(obs="qvel", index=0, weight=-1.0)                                  # reward forward velocity
+
+World positions of points.  ``point`` names a point on any body - ``body=`` with ``pos=`` in the body frame, or
+``site=``, a body-attached site of the model (``RawModel.sites``) - and ``difference`` the vector from one point to another.
+Each is a block of three entries (world x, y, z) behind the observation, in definition order, which every kind above takes like
+any other block: the engine launches ``mjmpc_points`` (csrc/points.hip) in front of the cost entry, which copies each next
+observation into an augmented row ``[d_obs + n_extra]`` and appends the positions, computed in double from the row's own
+``qpos`` by the points program (``points_table()``; the row format: include/mjmpc_amd.h).  They are the positions AT that
+``qpos``; the built-in ``site`` block lags one substep and is not expected to equal a point on the same body.
+
+    terms.point("tray", body="wrist", pos=(0.0, 0.0, 0.02))
+    terms.point("glass", body="glass")
+    terms.difference("glass_from_tray", "glass", "tray")
+    terms.norm(obs="glass_from_tray", index=[0, 1], weight=3.0)             # the glass over the tray's centre
+    terms.below_square(obs="glass", index=2, target=0.45, weight=10.0)      # ... and not below 0.45 m
 """
 import numpy as np
 
-from ..models.raw import TASK_REACH
+from ..models.raw import JOINT_BALL, JOINT_FREE, JOINT_HINGE, JOINT_SLIDE, TASK_FORWARD, TASK_REACH
 
 KIND_ABS, KIND_SQUARE, KIND_NORM, KIND_COS = 0, 1, 2, 3
 KIND_ABOVE, KIND_BELOW, KIND_ABOVE_SQUARE, KIND_BELOW_SQUARE = 4, 5, 6, 7
@@ -81,6 +95,73 @@ def _finite(x, what):
     return x
 
 
+MAX_POINTS = 16
+MAX_DIFFERENCES = 16
+MAX_PATH_NODES = 33             # jointed bodies on a point's path (welded ones are folded into the pose behind them)
+POINT_ROW_LEN = 16
+POINT_ROW, DIFFERENCE_ROW = 0, 5
+_JOINT_KINDS = {JOINT_HINGE: 1, JOINT_SLIDE: 2, JOINT_BALL: 3, JOINT_FREE: 4}
+
+
+def _quat_mul(a, b):
+    return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3],
+                     a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                     a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1],
+                     a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
+
+
+def _quat_rotate(q, v):
+    t = 2.0 * np.cross(q[1:], v)
+    return v + q[0] * t + np.cross(q[1:], t)
+
+
+def points_program(raw, points, differences=()):
+    """The points program of ``mjmpc_points`` (row format: include/mjmpc_amd.h) for ``points`` - ``[(body index, position in
+    the body frame)]`` - and ``differences`` - ``[(a, b)]``, indices into ``points`` - on ``raw``: float64
+    ``[n_rows + len(differences)][16]`` and ``n_rows``.  A point's path holds one node per jointed body from the root to its
+    body; a body without a joint is folded into the fixed pose of the node - or the point - behind it."""
+    qadr, adr = {}, 0
+    for i, b in enumerate(raw.bodies):
+        if b.joint is not None:
+            qadr[i] = adr
+            adr += b.joint.nq
+    rows = []
+    for body, pos in points:
+        chain = []
+        while body >= 0:
+            chain.append(body)
+            body = raw.bodies[body].parent
+        at, turn = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])       # the welded bodies' pose, waiting for the next node
+        nodes = 0
+        for i in reversed(chain):
+            b = raw.bodies[i]
+            quat = np.asarray(b.quat, float) / np.linalg.norm(b.quat)
+            at, turn = at + _quat_rotate(turn, np.asarray(b.pos, float)), _quat_mul(turn, quat)
+            if b.joint is None:
+                continue
+            j, row = b.joint, np.zeros(POINT_ROW_LEN)
+            norm = np.linalg.norm(j.axis)
+            row[0], row[1] = _JOINT_KINDS[j.type], qadr[i]
+            row[2] = float(j.ref) if j.type in (JOINT_HINGE, JOINT_SLIDE) else 0.0
+            row[3:6], row[6:10] = at, turn
+            row[10:13] = np.asarray(j.axis, float) / norm if norm > 0 else 0.0
+            row[13:16] = j.pos
+            rows.append(row)
+            nodes += 1
+            at, turn = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
+        if nodes > MAX_PATH_NODES:
+            raise ValueError("cost terms: a point's path holds %d jointed bodies, at most %d" % (nodes, MAX_PATH_NODES))
+        row = np.zeros(POINT_ROW_LEN)
+        row[0], row[3:6] = POINT_ROW, at + _quat_rotate(turn, np.asarray(pos, float))
+        rows.append(row)
+    n_rows = len(rows)
+    for a, b in differences:
+        row = np.zeros(POINT_ROW_LEN)
+        row[0], row[1], row[2] = DIFFERENCE_ROW, a, b
+        rows.append(row)
+    return np.ascontiguousarray(np.stack(rows), np.float64), n_rows
+
+
 class CostTerms:
     """A builder of the table.  With an ``engine`` every term is resolved and checked as it is added; without one the
     terms are kept as written and ``table(engine)`` / ``engine.set_cost_terms`` resolves them."""
@@ -93,6 +174,97 @@ class CostTerms:
         #  group's first part) or False (a later part))
         self._terms = []
         self._periodic = None       # the tracked terms' shared `periodic` (None: no tracked term yet)
+        self._points = []           # (name, body index, position in the body frame)
+        self._differences = []      # (name, point a, point b): indices into _points
+
+    # ------------------------------------------------------------------ world positions of points
+    def _raw_for_points(self, what):
+        if self.engine is None:
+            raise ValueError("cost terms: %s needs an engine - CostTerms(engine): a point is resolved against its model" % what)
+        m = self.engine.model
+        if getattr(m, "task", None) == TASK_FORWARD and getattr(m, "obs_skip", 0) > 0:
+            raise ValueError("cost terms: this model's observation leaves out the first %d entries of qpos (a forward task "
+                             "with obs_skip): world positions cannot be formed from it" % m.obs_skip)
+        if getattr(self.engine, "raw", None) is None:
+            raise ValueError("cost terms: %s needs an engine built from a RawModel (the bodies' poses are read from it)" % what)
+        return self.engine.raw
+
+    def _check_block_name(self, name):
+        if not isinstance(name, str) or not name:
+            raise ValueError("cost terms: a point or difference takes a name, got %r" % (name,))
+        if name in self.engine.obs_layout():
+            raise ValueError("cost terms: %r is a block of this engine's observation already" % name)
+        if any(name == p[0] for p in self._points) or any(name == d[0] for d in self._differences):
+            raise ValueError("cost terms: a point or difference named %r exists already" % name)
+
+    def point(self, name, body=None, site=None, pos=None):
+        """A block ``name`` of three entries behind the observation: the world position of the point ``pos`` (body frame,
+        default its origin) of ``body``, or of the body-attached ``site`` (``RawModel.sites``), at the row's own ``qpos``.
+        At most 16 points a table."""
+        raw = self._raw_for_points("point")
+        self._check_block_name(name)
+        if (body is None) == (site is None):
+            raise ValueError("cost terms: point takes body= or site=")
+        if site is not None:
+            if pos is not None:
+                raise ValueError("cost terms: a site has its own position; drop pos=")
+            if site not in raw.sites:
+                raise ValueError("cost terms: unknown site %r (this model has %s)" % (site, ", ".join(sorted(raw.sites)) or "none"))
+            index, pos = raw.sites[site]
+        else:
+            names = [b.name for b in raw.bodies]
+            if body not in names:
+                raise ValueError("cost terms: unknown body %r (this model has %s)" % (body, ", ".join(names)))
+            index = names.index(body)
+        pos = _finite((0.0, 0.0, 0.0) if pos is None else pos, "pos")
+        if pos.shape != (3,):
+            raise ValueError("cost terms: pos must be three numbers, got %r" % (pos.tolist(),))
+        if len(self._points) >= MAX_POINTS:
+            raise ValueError("cost terms: a table holds at most %d points" % MAX_POINTS)
+        if self._differences:
+            raise ValueError("cost terms: define the points before the differences (their blocks stand in that order)")
+        points_program(raw, [(int(index), pos)])            # (a path too long is refused here)
+        self._points.append((name, int(index), pos.copy()))
+        return self
+
+    def difference(self, name, a, b):
+        """A block ``name`` of three entries behind the points' blocks: point ``a`` minus point ``b`` (world frame), one
+        double subtraction per component.  At most 16 differences a table."""
+        self._raw_for_points("difference")
+        self._check_block_name(name)
+        known = [p[0] for p in self._points]
+        for x in (a, b):
+            if x not in known:
+                raise ValueError("cost terms: unknown point %r (defined: %s)" % (x, ", ".join(known) or "none"))
+        if len(self._differences) >= MAX_DIFFERENCES:
+            raise ValueError("cost terms: a table holds at most %d differences" % MAX_DIFFERENCES)
+        self._differences.append((name, known.index(a), known.index(b)))
+        return self
+
+    @property
+    def n_extra(self):
+        """Entries the points and differences add behind the observation: three each."""
+        return 3 * (len(self._points) + len(self._differences))
+
+    def points_layout(self, engine=None):
+        """Named slices of the points' and differences' blocks in the augmented row, in definition order."""
+        engine = engine if engine is not None else self.engine
+        d, out = (_dims(engine)[0] if engine is not None else 0), {}
+        for k, entry in enumerate(self._points + self._differences):
+            out[entry[0]] = slice(d + 3 * k, d + 3 * k + 3)
+        return out
+
+    def points_table(self, engine=None):
+        """``(program, n_rows, n_points, n_differences)`` - the points program of ``mjmpc_points``, float64
+        ``[n_rows + n_differences][16]`` (``points_program``) -, or ``None`` for a table without points."""
+        if not self._points:
+            return None
+        engine = engine if engine is not None else self.engine
+        raw = getattr(engine, "raw", None)
+        if raw is None:
+            raise ValueError("cost terms: points need an engine built from a RawModel")
+        program, n_rows = points_program(raw, [(b, p) for _, b, p in self._points], [(a, b) for _, a, b in self._differences])
+        return program, n_rows, len(self._points), len(self._differences)
 
     # ------------------------------------------------------------------ the kinds
     def abs(self, obs=None, action=None, index=None, weight=1.0, target=0.0, terminal=False, reference=None,
@@ -384,10 +556,11 @@ class CostTerms:
             self._periodic = bool(periodic)
         return self
 
-    @staticmethod
-    def _resolve(term, engine):
-        """-> (absolute indices, source, one target per index) of a term, checked against the engine's dimensions."""
+    def _resolve(self, term, engine):
+        """-> (absolute indices, source, one target per index) of a term, checked against the engine's dimensions (the
+        observation's: with the points' and differences' blocks behind it)."""
         _, block, index, source, _, target = term[:6]
+        extra = self.n_extra
         if engine is None:
             if block is not None or index is None:
                 raise ValueError("cost terms that name a block or take every entry need an engine: CostTerms(engine) or "
@@ -396,13 +569,15 @@ class CostTerms:
         elif source:
             lo, n, limit, what = 0, _dims(engine)[1], _dims(engine)[1], "action"
         elif block is None:
-            lo, n, limit, what = 0, _dims(engine)[0], _dims(engine)[0], "observation"
+            lo, n, limit, what = 0, _dims(engine)[0] + extra, _dims(engine)[0] + extra, "observation"
         else:
             layout = engine.obs_layout()
+            if extra:
+                layout = dict(layout, **self.points_layout(engine))
             if block not in layout:
                 raise ValueError("unknown observation block %r (this engine has %s)" % (block, ", ".join(layout)))
             sl = layout[block]
-            lo, n, limit, what = sl.start, sl.stop - sl.start, _dims(engine)[0], "block %r" % block
+            lo, n, limit, what = sl.start, sl.stop - sl.start, _dims(engine)[0] + extra, "block %r" % block
         idx = list(range(n)) if index is None else index
         for i in idx:
             if i < 0 or (n is not None and i >= n):
@@ -488,9 +663,20 @@ def cost_terms_from_config(block, engine, num_episodes=None):
     DESIGN 12.3: ``{kind: quadratic, obs: [0, 1, 2, 3], matrix: [[..], ..], weight: 1.0}`` is ``CostTerms.quadratic``
     (``matrix:`` ``[n][n]`` or ``[n]``; ``parts:`` a list of mappings with ``obs`` / ``action`` / ``action_rate``, ``index``,
     ``target``, ``reference``, as there); ``kind: linear`` takes what ``square`` takes.  ``weight`` (and outside ``parts:``
-    ``target`` and ``reference``) may hold one value per episode; the matrix is the batch's."""
-    if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms"}:
-        raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin'")
+    ``target`` and ``reference``) may hold one value per episode; the matrix is the batch's.
+
+    DESIGN 12.4: beside ``terms:`` the block may hold ``points:`` - a list of ``{name: tray, body: wrist, pos: [0, 0, 0.02]}`` or
+    ``{name: tip, site: finger}`` - and ``differences:`` - ``{name: glass_from_tray, a: glass, b: tray}`` -, defined in that
+    order before the terms, which name them like any block; every episode of a batch gets the same ones."""
+    if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms", "points", "differences"}:
+        raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin', 'points' and 'differences'")
+    point_entries, difference_entries = block.get("points") or [], block.get("differences") or []
+    for entry in point_entries:
+        if not isinstance(entry, dict) or "name" not in entry or set(entry) - {"name", "body", "site", "pos"}:
+            raise ValueError("cost_terms: a point takes name and body or site, optionally pos, got %r" % (entry,))
+    for entry in difference_entries:
+        if not isinstance(entry, dict) or set(entry) != {"name", "a", "b"}:
+            raise ValueError("cost_terms: a difference takes name, a and b, got %r" % (entry,))
     E = None if num_episodes is None else int(num_episodes)
     entries = block.get("terms") or []
     per_episode = False
@@ -520,6 +706,10 @@ def cost_terms_from_config(block, engine, num_episodes=None):
     out = []
     for e in range(E if per_episode else 1):
         terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
+        for entry in point_entries:         # (the same points and differences for every episode)
+            terms.point(entry["name"], body=entry.get("body"), site=entry.get("site"), pos=entry.get("pos"))
+        for entry in difference_entries:
+            terms.difference(entry["name"], entry["a"], entry["b"])
         for entry in entries:
             kw = {k: entry[k] for k in ("obs", "action", "action_rate", "index", "weight", "target", "terminal", "low", "high",
                                         "squared", "matrix", "parts") if k in entry}

@@ -676,7 +676,8 @@ def load_mjcf(path, hand_site="finger", target_site="target", frame_skip=2, task
                    timestep=timestep, frame_skip=frame_skip, gravity=gravity, solref=solref, solimp=full_solimp(solimp),
                    solref_limit=lsolref, solimp_limit=full_solimp(lsolimp), density=density, viscosity=viscosity, cone=cone, impratio=impratio, integrator=integrator,
                    task=task, ctrl_cost=ctrl_cost, obs_skip=obs_skip, pairs=pairs, pair_params=pair_params, world_geoms=world_geoms,
-                   equalities=equalities, tendons=tendons, solref_friction=fsolref, solimp_friction=full_solimp(fsolimp))
+                   equalities=equalities, tendons=tendons, solref_friction=fsolref, solimp_friction=full_solimp(fsolimp),
+                   sites={k: (b, [float(x) for x in p]) for k, (b, p) in sites.items() if k is not None and b >= 0})
     return _apply_flags(raw, flags)
 
 

@@ -274,6 +274,9 @@ class RawModel:
     tendons: List[RawTendon] = field(default_factory=list)
     solref_friction: Sequence[float] = (0.02, 1.0)  # friction-loss rows (MJCF solreffriction / solimpfriction)
     solimp_friction: Sequence[float] = (0.9, 0.95, 0.001, 0.5, 2.0)
+    # every body-attached MJCF <site> by name -> (body index, position in the body frame): what ``CostTerms.point(site=)``
+    # resolves.  Not serialised: ``to_flat()`` and the model blocks carry the one tracked site, as ever
+    sites: dict = field(default_factory=dict)
 
     # ------------------------------------------------------------------
     @property
