@@ -38,7 +38,7 @@ extern "C" {
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
  *      the DMD-MPC episode batches', mjmpc_cost_terms, mjmpc_cost_terms_track / _track_batch, mjmpc_cost_terms_rate /
- *      _rate_batch, mjmpc_cost_terms_quad / _quad_batch and mjmpc_points.) */
+ *      _rate_batch, mjmpc_cost_terms_quad / _quad_batch, mjmpc_points and mjmpc_points_motion.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -951,6 +951,35 @@ int mjmpc_cost_terms_quad_batch(int dtype, int E, int64_t P, int H, int d_obs, i
  * tile with its points (60 KiB of LDS). */
 int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void* d_obs_rows, const double* d_program, int n_rows,
                  int n_points, int n_diff, void* d_out, void* stream);
+
+/* Body axes and velocities beside the points: mjmpc_points with qvel.  Rows, d_out, rounding and the differences
+ * are as above, with n_out output slots of three entries for n_points; qvel is entries nq .. nq + nv of a row (nq + nv <= d_obs)
+ * with MuJoCo's meaning: a hinge's or slide's dof is a rate about or along the joint axis, a hinge turning about its anchor; a
+ * ball joint's three dofs are the angular velocity in the child body's frame; a free joint's six are the linear velocity in the
+ * world frame, then the angular velocity in the body's frame.  d_dofadr, int32 [n_rows] on the device, holds each node row's
+ * first qvel address (ignored for closing rows: the 16 columns of a node row are all taken, so the addresses stand beside the
+ * table).
+ *
+ * Node rows are those of mjmpc_points exactly.  Beside the frame the walk carries the world linear velocity v of the frame's
+ * origin and the world angular velocity w of the frame:
+ *   fixed pose  v += w x (R pos)
+ *   slide       v += w x (a d) + a qd                  (a: the axis in the world, d = q - qpos0)
+ *   hinge       the anchor's velocity v + w x r_a is taken; w += a qd; the origin's velocity is the anchor's - w x (R' local)
+ *   ball        as the hinge, with w += R' omega_local
+ *   free        v = qvel[0 .. 3], w = R qvel[3 .. 6]
+ * A closing row is {kind, keep, slot, x, y, z, 0 ..}:
+ *   [0] kind   0 POINT: p + R (x, y, z)    6 AXIS: R (x, y, z)    7 VELOCITY: v + w x (R (x, y, z))    8 ANGULAR: w
+ *   [1] keep   1: the next closing row stands on the same frame, which is kept; 0: the next row starts at the world frame, at rest
+ *   [2] slot   the output's place in d_out: entries d_obs + 3 slot .. + 3
+ *   [3 .. 5]   the offset (POINT, VELOCITY) or the axis (AXIS) in the frame of the last node
+ * so all outputs on one body share one walk (a point and its velocity are nodes + 2 rows) and slots need not be in program
+ * order.  The trailing n_diff rows {5, a, b} index output slots.  The kernel holds every qpos address inside nq, every dof
+ * address inside nv and every slot inside n_out whatever the tables say (a closing row with a slot outside writes nothing); a
+ * slot that no closing row names reads as 0.
+ * MJMPC_E_BADARG before anything is launched: what mjmpc_points refuses (n_out for n_points), a null d_dofadr, nv below 1 or
+ * nq + nv above d_obs. */
+int mjmpc_points_motion(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
+                        const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, void* d_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -94,7 +94,8 @@ class _EpisodeBatch:
     _quad = None            # the tables hold quadratic groups or signed linear rows: mjmpc_cost_terms_quad_batch with
                             # this pool of matrices on the device, one for all episodes
     _points = None          # the tables name points: (program, n_rows, n_points, n_diff, d_obs + n_extra, the augmented
-                            # observations of the rollouts [E P][H][.] and of the real-env steps [E][.])
+                            # observations of the rollouts [E P][H][.] and of the real-env steps [E][.], the node rows' qvel
+                            # addresses - None without axes and velocities)
     _terms = None           # set_cost_terms: (tables on the device, rows, per episode?, keep_builtin, a row reads an action?)
     _terms_nobs = None      # ... the rollouts' next observations [E P][H][d_obs] (only while terms are set)
     _terms_env = None       # ... the real-env step's own next observations [E][d_obs] and actions [E][A] in the batch's dtype
@@ -370,7 +371,8 @@ class _EpisodeBatch:
         for e, t in enumerate(each):
             other = t.points_table(engine)
             if (other is None) != (points is None) or (points is not None and (
-                    other[1:] != points[1:] or not np.array_equal(other[0], points[0]))):
+                    len(other) != len(points) or other[1:4] != points[1:4] or not np.array_equal(other[0], points[0]))):
+                # (a fifth entry, the dof addresses, follows from the program and the model)
                 raise ValueError("set_cost_terms: episode %d's points or differences differ from episode 0's (the episodes "
                                  "share them; weights, targets and references may differ)" % e)
         return np.stack(tables), bool(keep), bool(np.any(first[:, 1] != 0))
@@ -415,7 +417,8 @@ class _EpisodeBatch:
         matrices are one pool for the batch - per episode the weights, targets and references may differ, the matrices not
         (``ValueError`` naming the episode).  Tables with points or differences put ``mjmpc_points`` over the
         ``E P H`` rows between the rollout and the cost entry, as the single engines do; the episodes share the points and
-        differences (``ValueError`` naming the episode) and keep their own weights, targets and references.  Everything is
+        differences (``ValueError`` naming the episode) and keep their own weights, targets and references; with axes,
+        velocities or angular velocities the launch is ``mjmpc_points_motion``, shared in the same way.  Everything is
         checked on the host first (``ValueError``); callable between steps."""
         if terms is None:
             self._terms = self._terms_nobs = self._terms_env = self._track = self._prev_actions = self._quad = None
@@ -448,9 +451,11 @@ class _EpisodeBatch:
         if points is not None:
             #  one program for the batch; the augmented rows of the rollouts' and of the real-env steps' observations
             d_aug = self.d_obs + first.n_extra
-            self._points = (self._upload(points[0]),) + tuple(points[1:]) + (
+            self._points = (self._upload(points[0]),) + tuple(points[1:4]) + (
                 d_aug, torch.empty((E * self.num_particles, self.horizon, d_aug), dtype=tdt, device=dev),
-                torch.empty((E, d_aug), dtype=tdt, device=dev))
+                torch.empty((E, d_aug), dtype=tdt, device=dev),
+                #  with axes or velocities the node rows' qvel addresses: mjmpc_points_motion
+                torch.from_numpy(points[4]).to(dev) if len(points) > 4 else None)
 
     def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s, bias=0, advance_prev=0):
         """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s); with tracked terms
@@ -460,10 +465,15 @@ class _EpisodeBatch:
         d_obs = self.d_obs
         if self._points is not None:
             #  the same launch as the single engines', over E P H rows: the cost entry reads the augmented rows
-            program, n_rows, n_points, n_diff, d_aug, aug_rollout, aug_env = self._points
+            program, n_rows, n_points, n_diff, d_aug, aug_rollout, aug_env, dofadr = self._points
             aug = aug_rollout if nobs is self._terms_nobs else aug_env
-            _lib.check(self.lib.mjmpc_points(self._code, self.num_episodes * P * H, d_obs, self.engine._nq, _vp(nobs),
-                                             _vp(program), n_rows, n_points, n_diff, _vp(aug), s))
+            if dofadr is None:
+                _lib.check(self.lib.mjmpc_points(self._code, self.num_episodes * P * H, d_obs, self.engine._nq, _vp(nobs),
+                                                 _vp(program), n_rows, n_points, n_diff, _vp(aug), s))
+            else:
+                _lib.check(self.lib.mjmpc_points_motion(self._code, self.num_episodes * P * H, d_obs, self.engine._nq,
+                                                        self.model.nv, _vp(nobs), _vp(program), _vp(dofadr), n_rows, n_points,
+                                                        n_diff, _vp(aug), s))
             nobs, d_obs = aug, d_aug
         if self._quad is not None:
             refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)

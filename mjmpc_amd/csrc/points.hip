@@ -21,6 +21,19 @@
 // moves: profiles/r25_points.txt.
 // The n_diff rows behind the paths are {5, a, b}: the entry point a - point b, one double subtraction per component.
 //
+// Axes and velocities (mjmpc_points_motion): the MOTION = true instantiation of the same kernel carries, beside the
+// frame, the world linear velocity v of the frame's origin and the world angular velocity w of the frame (6 more doubles) and
+// reads qvel - entries nq .. nq + nv of the row - at the dof address d_dofadr[k] of node row k, with MuJoCo's meaning of qvel:
+//   fixed pose  v += w x (R pos)                     slide  v += w x (a d) + a qd  (a: the axis in the world)
+//   hinge       the anchor's velocity v + w x r_a is taken, then w += a qd, then the origin's is the anchor's - w x (R' local)
+//   ball        as the hinge, with w += R' omega_local: the three rates are the angular velocity in the child's frame
+//   free        v = qvel[0:3] (world), w = R qvel[3:6] (body frame)
+// Its closing rows name their output slot (col 2) and kind (col 0): 0 POINT p + R off, 6 AXIS R a, 7 VELOCITY v + w x (R off),
+// 8 ANGULAR w; col 1 = 1 keeps the frame for the next closing row, so that all outputs on one body share one walk (a point and
+// its velocity: nodes + 2 rows).  Every slot is cleared first: one that no closing row names reads as 0.  The kind branch is
+// uniform, the dof addresses are wave-uniform reads like the rows.  mjmpc_points launches the MOTION = false instantiation,
+// whose walk is the code it always was (registers, LDS, scratch: profiles/r26_motion_resources.txt).
+//
 // Shape (cost_terms.hip's): a workgroup takes `rows` consecutive observation rows - they lie back to back in memory -, copies
 // them into LDS with unit-stride loads (odd row pitch: the lanes' column reads spread over the banks), lane j walks the program
 // over row j and parks its points in LDS as doubles, laid out [entry][lane] (lane-consecutive, no bank conflict); then all
@@ -69,11 +82,110 @@ __device__ __forceinline__ void pt_mul(double* q, double w, double x, double y, 
     q[3] = a * z + b * y - c * x + d * w;
 }
 
-// grid: ceil(n / rows) workgroups of max(rows, 64) threads; dynamic LDS: rows x pitch(d_obs) words of T, then 3 n_points x rows doubles
+__device__ __forceinline__ void pt_cross(const double* a, const double* b, double* out) {
+    out[0] = a[1] * b[2] - a[2] * b[1];
+    out[1] = a[2] * b[0] - a[0] * b[2];
+    out[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// The walk of the MOTION instantiation over one row `my`: frame, origin velocity v and angular velocity w; the
+// outputs go to pts[(3 slot + c) * rows] (pts: this lane's column of the parked entries).
 template <typename T>
+__device__ __forceinline__ void pt_walk_motion(const T* my, const double* __restrict__ prog, const int32_t* __restrict__ dofadr,
+                                               int n_rows, int n_out, int nq, int nv, double* pts, int rows) {
+    // entry i of my qpos / qvel, held inside it whatever the tables say
+    auto qpos = [&](int i) { return (double)my[i < 0 ? 0 : i < nq ? i : nq - 1]; };
+    auto qvel = [&](int i) { return (double)my[nq + (i < 0 ? 0 : i < nv ? i : nv - 1)]; };
+    for (int e = 0; e < 3 * n_out; ++e) pts[e * rows] = 0.0;
+    PtFrame f{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
+    double v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < n_rows; ++k) {
+        const double* __restrict__ row = prog + (long)PT_ROW * k;
+        const int kind = (int)row[0];
+        double t[3], c[3];
+        if (kind == 0 || kind >= 6) {       // a closing row: its output into its slot; the frame kept or reset
+            const int slot = (int)row[2];
+            double o[3];
+            if (kind == 8) {
+                o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+            } else {
+                pt_rotate(f.q, row[3], row[4], row[5], t);
+                if (kind == 0) {
+                    o[0] = f.p[0] + t[0]; o[1] = f.p[1] + t[1]; o[2] = f.p[2] + t[2];
+                } else if (kind == 7) {
+                    pt_cross(w, t, c);
+                    o[0] = v[0] + c[0]; o[1] = v[1] + c[1]; o[2] = v[2] + c[2];
+                } else {
+                    o[0] = t[0]; o[1] = t[1]; o[2] = t[2];
+                }
+            }
+            if (slot >= 0 && slot < n_out) {
+                pts[(3 * slot + 0) * rows] = o[0];
+                pts[(3 * slot + 1) * rows] = o[1];
+                pts[(3 * slot + 2) * rows] = o[2];
+            }
+            if (row[1] == 0.0) {
+                f = PtFrame{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
+                v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = 0.0;
+            }
+            continue;
+        }
+        const int adr = (int)row[1], dof = dofadr[k];
+        if (kind == 4) {                    // free: the frame is qpos' own, the linear rates the world's, the angular the body's
+            const double qw = qpos(adr + 3), x = qpos(adr + 4), y = qpos(adr + 5), z = qpos(adr + 6);
+            const double s = 1.0 / sqrt(qw * qw + x * x + y * y + z * z);
+            f = PtFrame{{qpos(adr), qpos(adr + 1), qpos(adr + 2)}, {qw * s, x * s, y * s, z * s}};
+            v[0] = qvel(dof); v[1] = qvel(dof + 1); v[2] = qvel(dof + 2);
+            pt_rotate(f.q, qvel(dof + 3), qvel(dof + 4), qvel(dof + 5), w);
+            continue;
+        }
+        pt_rotate(f.q, row[3], row[4], row[5], t);
+        pt_cross(w, t, c);
+        v[0] += c[0]; v[1] += c[1]; v[2] += c[2];
+        f.p[0] += t[0]; f.p[1] += t[1]; f.p[2] += t[2];
+        pt_mul(f.q, row[6], row[7], row[8], row[9]);
+        if (kind == 2) {                    // slide: along the axis; the displaced origin is carried round by w
+            const double d = qpos(adr) - row[2], qd = qvel(dof);
+            pt_rotate(f.q, row[10], row[11], row[12], t);
+            double ad[3] = {t[0] * d, t[1] * d, t[2] * d};
+            pt_cross(w, ad, c);
+            v[0] += c[0] + t[0] * qd; v[1] += c[1] + t[1] * qd; v[2] += c[2] + t[2] * qd;
+            f.p[0] += ad[0]; f.p[1] += ad[1]; f.p[2] += ad[2];
+            continue;
+        }
+        // hinge, ball: about the anchor, which stays where it is and moves as the frame before the joint moves it
+        double anchor[3];
+        pt_rotate(f.q, row[13], row[14], row[15], t);
+        pt_cross(w, t, c);
+        anchor[0] = f.p[0] + t[0]; anchor[1] = f.p[1] + t[1]; anchor[2] = f.p[2] + t[2];
+        v[0] += c[0]; v[1] += c[1]; v[2] += c[2];                  // (the anchor's velocity)
+        if (kind == 1) {
+            const double half = 0.5 * (qpos(adr) - row[2]), qd = qvel(dof);
+            double sn, cs;
+            sincos(half, &sn, &cs);
+            pt_mul(f.q, cs, row[10] * sn, row[11] * sn, row[12] * sn);
+            pt_rotate(f.q, row[10], row[11], row[12], t);
+            w[0] += t[0] * qd; w[1] += t[1] * qd; w[2] += t[2] * qd;
+        } else {
+            const double qw = qpos(adr), x = qpos(adr + 1), y = qpos(adr + 2), z = qpos(adr + 3);
+            const double s = 1.0 / sqrt(qw * qw + x * x + y * y + z * z);
+            pt_mul(f.q, qw * s, x * s, y * s, z * s);
+            pt_rotate(f.q, qvel(dof), qvel(dof + 1), qvel(dof + 2), t);
+            w[0] += t[0]; w[1] += t[1]; w[2] += t[2];
+        }
+        pt_rotate(f.q, row[13], row[14], row[15], t);
+        pt_cross(w, t, c);
+        f.p[0] = anchor[0] - t[0]; f.p[1] = anchor[1] - t[1]; f.p[2] = anchor[2] - t[2];
+        v[0] -= c[0]; v[1] -= c[1]; v[2] -= c[2];
+    }
+}
+
+// grid: ceil(n / rows) workgroups of max(rows, 64) threads; dynamic LDS: rows x pitch(d_obs) words of T, then 3 n_points x rows doubles
+// MOTION: n_points counts the output slots; nv and dofadr are read by that instantiation alone
+template <typename T, bool MOTION>
 __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs, const double* __restrict__ prog, int n_rows,
                                                        int n_points, int n_diff, long n, int d_obs, int nq, int rows,
-                                                       T* __restrict__ out) {
+                                                       T* __restrict__ out, int nv, const int32_t* __restrict__ dofadr) {
     extern __shared__ double pt_tile_raw[];
     __shared__ int s_da[PT_MAX_DIFF], s_db[PT_MAX_DIFF];
     const int po = pt_pitch(d_obs);
@@ -103,7 +215,9 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
     }
     __syncthreads();
 
-    if (j < mine) {
+    if constexpr (MOTION) {
+        if (j < mine) pt_walk_motion(tile + j * po, prog, dofadr, n_rows, n_points, nq, nv, pts + j, rows);
+    } else if (j < mine) {
         const T* const my = tile + j * po;
         // entry i of my qpos, held inside it whatever the table says
         auto qpos = [&](int i) { return (double)my[i < 0 ? 0 : i < nq ? i : nq - 1]; };
@@ -185,6 +299,19 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
 }
 
 int bad(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_points", detail); }
+int bad_motion(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_points_motion", detail); }
+
+// the rows of a tile and its LDS bytes: the largest power of two up to PT_WG whose tile and parked entries fit PT_LDS_BYTES
+struct PtShape {
+    int rows;
+    size_t lds;
+};
+PtShape pt_shape(int d_obs, long word, long pts_bytes) {
+    int rows = PT_WG;
+    auto lds = [&](int r) { return (r * word * pt_pitch(d_obs) + 7) / 8 * 8 + r * pts_bytes; };
+    while (lds(rows) > PT_LDS_BYTES) rows >>= 1;
+    return PtShape{rows, (size_t)lds(rows)};
+}
 
 }  // namespace
 }  // namespace mjmpc
@@ -203,18 +330,50 @@ extern "C" int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void*
     const long pts_bytes = 8L * 3 * n_points;                       // a row's parked points
     if ((long)d_obs > (PT_LDS_BYTES - pts_bytes - 8) / word - 1)
         return bad("an observation row and its points of more than 60 KiB");
-    int rows = PT_WG;
-    auto lds = [&](int r) { return (r * word * pt_pitch(d_obs) + 7) / 8 * 8 + r * pts_bytes; };
-    while (lds(rows) > PT_LDS_BYTES) rows >>= 1;
+    const PtShape sh = pt_shape(d_obs, word, pts_bytes);
+    const int rows = sh.rows;
     const long blocks = ((long)N + rows - 1) / rows;
     if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
     if (dtype == MJMPC_F32)
-        hipLaunchKernelGGL(points_kernel<float>, dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), (size_t)lds(rows), (hipStream_t)stream,
-                           (const float*)d_obs_rows, d_program, n_rows, n_points, n_diff, (long)N, d_obs, nq, rows, (float*)d_out);
+        hipLaunchKernelGGL((points_kernel<float, false>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
+                           (const float*)d_obs_rows, d_program, n_rows, n_points, n_diff, (long)N, d_obs, nq, rows, (float*)d_out,
+                           0, (const int32_t*)nullptr);
     else
-        hipLaunchKernelGGL(points_kernel<double>, dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), (size_t)lds(rows), (hipStream_t)stream,
+        hipLaunchKernelGGL((points_kernel<double, false>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
                            (const double*)d_obs_rows, d_program, n_rows, n_points, n_diff, (long)N, d_obs, nq, rows,
-                           (double*)d_out);
+                           (double*)d_out, 0, (const int32_t*)nullptr);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_points", hipGetErrorString(e));
+}
+
+extern "C" int mjmpc_points_motion(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
+                                   const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, void* d_out, void* stream) {
+    using namespace mjmpc;
+    if (!d_obs_rows || !d_program || !d_out) return bad_motion("null pointer");
+    if (!d_dofadr) return bad_motion("null d_dofadr: the node rows' qvel addresses");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_motion("unknown dtype");
+    if (N < 1 || d_obs < 1) return bad_motion("N and d_obs must be >= 1");
+    if (nq < 1 || nq > d_obs) return bad_motion("nq must be in 1 .. d_obs: qpos opens the observation");
+    if (nv < 1 || (long)nq + nv > d_obs) return bad_motion("nv must be >= 1 and nq + nv <= d_obs: qvel follows qpos");
+    if (n_out < 1 || n_out > PT_MAX_POINTS) return bad_motion("n_out must be in 1 .. 16");
+    if (n_diff < 0 || n_diff > PT_MAX_DIFF) return bad_motion("n_diff must be in 0 .. 16");
+    if (n_rows < n_out || n_rows > PT_MAX_ROWS) return bad_motion("n_rows must be in n_out .. 544 (16 paths of 33 nodes and an output)");
+    const long word = dtype == MJMPC_F32 ? 4 : 8;
+    const long pts_bytes = 8L * 3 * n_out;                          // a row's parked outputs
+    if ((long)d_obs > (PT_LDS_BYTES - pts_bytes - 8) / word - 1)
+        return bad_motion("an observation row and its outputs of more than 60 KiB");
+    const PtShape sh = pt_shape(d_obs, word, pts_bytes);
+    const int rows = sh.rows;
+    const long blocks = ((long)N + rows - 1) / rows;
+    if (blocks > INT32_MAX) return bad_motion("more than 2^31 workgroups");
+    if (dtype == MJMPC_F32)
+        hipLaunchKernelGGL((points_kernel<float, true>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
+                           (const float*)d_obs_rows, d_program, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (float*)d_out, nv,
+                           d_dofadr);
+    else
+        hipLaunchKernelGGL((points_kernel<double, true>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
+                           (const double*)d_obs_rows, d_program, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (double*)d_out,
+                           nv, d_dofadr);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_points_motion", hipGetErrorString(e));
 }

@@ -77,7 +77,8 @@ class RolloutEngine(EnvResetWatch):
     _prev_action = None             # ... with rate rows the action last applied to the controlled env, float64 [A] on the device
     _terms_quad = None              # the table holds quadratic groups or signed linear rows: mjmpc_cost_terms_quad
                                     # with this pool of matrices, float64 on the device (one zero without a group)
-    _points = None                  # the table names points: (program on the device, n_rows, n_points, n_diff, n_extra)
+    _points = None                  # the table names points: (program on the device, n_rows, n_points, n_diff, n_extra,
+                                    # the node rows' qvel addresses on the device - None without axes and velocities)
     _points_last = None             # ... the augmented observations of the last cost launch (cost_observations)
     _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
 
@@ -346,7 +347,7 @@ class RolloutEngine(EnvResetWatch):
         terms first, then make the ``rollout_fn``.  ``None`` restores the built-in cost.  The episode batches have their own
         ``set_cost_terms`` (``control/batched.py``, DESIGN 10.8: one table for the batch or one per episode).  Covered: both
         rollout engines and all six episode-batch classes, with constant targets, tracked references, action rates,
-        one-sided bounds, quadratic forms with full matrices, signed linear rows and world positions of points on any body.  Not covered: the fused launches, ``AnalyticRolloutEngine``, world sizes above 1.
+        one-sided bounds, quadratic forms with full matrices, signed linear rows, world positions of points on any body, world directions of body axes and world linear and angular velocities.  Not covered: the fused launches, ``AnalyticRolloutEngine``, world sizes above 1.
 
         Terms with a ``reference=`` are costed by ``mjmpc_cost_terms_track``: their reference goes to the device
         with an env-time counter (``track_step()``, 0 now) that every plan reads and every step of the controlled env
@@ -368,7 +369,9 @@ class RolloutEngine(EnvResetWatch):
         engine's with the world positions of the points, at each row's own ``qpos``, behind every row, and the cost entry reads
         that buffer with ``d_obs + n_extra`` entries a row (``cost_observations()`` returns it).  The observations a rollout
         returns keep their width; the counter, the previous action, ``terminal`` and the guard behave as without points; a table
-        without points launches nothing new."""
+        without points launches nothing new.  With an axis, a velocity or an angular velocity (``CostTerms.axis`` / ``velocity`` /
+        ``angular_velocity``) that launch is ``mjmpc_points_motion``, which reads the row's ``qvel`` too; everything
+        else is as with points."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
                                "controllers %s; set the terms first, then call make_device_rollout_fn"
@@ -386,7 +389,10 @@ class RolloutEngine(EnvResetWatch):
         self._points = self._points_last = None
         if points is not None:
             # (every cost launch is preceded by mjmpc_points into a buffer of the engine's)
-            self._points = (torch.from_numpy(points[0]).to(self.device),) + tuple(points[1:]) + (int(terms.n_extra),)
+            # (with an axis or a velocity the table has a fifth entry, the node rows' qvel addresses, and the
+            # launch is mjmpc_points_motion)
+            dofadr = torch.from_numpy(points[4]).to(self.device) if len(points) > 4 else None
+            self._points = (torch.from_numpy(points[0]).to(self.device),) + tuple(points[1:4]) + (int(terms.n_extra), dofadr)
         self._terms_dev = torch.from_numpy(table).to(self.device)
         self._terms_rate = bool(terms.needs_rate_entry)
         self._terms_quad = None
@@ -456,12 +462,18 @@ class RolloutEngine(EnvResetWatch):
         if self._points is not None:
             #  the world positions first: the cost entry below then sees d_obs + n_extra entries a row.  The
             # controlled env's step has a buffer of its own, so a loop of plans and steps never reallocates (captures)
-            program, n_rows, n_points, n_diff, n_extra = self._points
+            program, n_rows, n_points, n_diff, n_extra, dofadr = self._points
             step = (P, H) == (1, 1)
             aug = self._buffer("points_step" if step else "points_obs",
                                (self.d_obs + n_extra,) if nobs.dim() == 1 else (P, H, self.d_obs + n_extra))
-            _lib.check(self._lib.mjmpc_points(self._code, P * H, self.d_obs, self._nq, _ptr(nobs), _ptr(program), n_rows,
-                                              n_points, n_diff, _ptr(aug), self._stream()))
+            if dofadr is None:
+                _lib.check(self._lib.mjmpc_points(self._code, P * H, self.d_obs, self._nq, _ptr(nobs), _ptr(program), n_rows,
+                                                  n_points, n_diff, _ptr(aug), self._stream()))
+            else:
+                #  axes, velocities: the same launch with qvel - the nv entries behind qpos - and the dof addresses
+                _lib.check(self._lib.mjmpc_points_motion(self._code, P * H, self.d_obs, self._nq, self.model.nv, _ptr(nobs),
+                                                         _ptr(program), _ptr(dofadr), n_rows, n_points, n_diff, _ptr(aug),
+                                                         self._stream()))
             self._points_last = nobs = aug
             d_obs += n_extra
         t = self._terms_dev

@@ -66,6 +66,20 @@ observation into an augmented row ``[d_obs + n_extra]`` and appends the position
     terms.difference("glass_from_tray", "glass", "tray")
     terms.norm(obs="glass_from_tray", index=[0, 1], weight=3.0)             # the glass over the tray's centre
     terms.below_square(obs="glass", index=2, target=0.45, weight=10.0)      # ... and not below 0.45 m
+
+Axes and velocities.  ``axis`` gives the world direction of a body-fixed unit vector, ``velocity`` the world linear
+velocity of a named point and ``angular_velocity`` the world angular velocity of a body, from the row's own ``qpos`` and ``qvel``
+with MuJoCo's meaning of ``qvel`` (a ball joint's and a free joint's angular rates are in the body's frame).  They are blocks
+like a point's - points, axes, velocities and angular velocities stand in definition order, at most 16 together, the
+differences behind them - and ``difference`` takes two of one kind.  A table with any of them launches
+``mjmpc_points_motion`` in place of ``mjmpc_points``; all outputs on one body share one walk of its path.
+
+    terms.axis("glass_up", body="glass", axis=(0, 0, 1))
+    terms.linear(obs="glass_up", index=2, weight=-2.0)                      # upright: reward the world z of the glass's z axis
+    terms.velocity("glass_vel", "glass")
+    terms.velocity("tray_vel", "tray")
+    terms.difference("slip", "glass_vel", "tray_vel")
+    terms.norm(obs="slip", weight=0.5)                                      # the glass at rest relative to the tray
 """
 import numpy as np
 
@@ -100,6 +114,7 @@ MAX_DIFFERENCES = 16
 MAX_PATH_NODES = 33             # jointed bodies on a point's path (welded ones are folded into the pose behind them)
 POINT_ROW_LEN = 16
 POINT_ROW, DIFFERENCE_ROW = 0, 5
+AXIS_ROW, VELOCITY_ROW, ANGULAR_ROW = 6, 7, 8      # the further closing rows of mjmpc_points_motion
 _JOINT_KINDS = {JOINT_HINGE: 1, JOINT_SLIDE: 2, JOINT_BALL: 3, JOINT_FREE: 4}
 
 
@@ -115,42 +130,56 @@ def _quat_rotate(q, v):
     return v + q[0] * t + np.cross(q[1:], t)
 
 
+def _addresses(raw):
+    """-> ({body: first qpos address of its joint}, {body: first qvel address})."""
+    qadr, dadr, q, d = {}, {}, 0, 0
+    for i, b in enumerate(raw.bodies):
+        if b.joint is not None:
+            qadr[i], dadr[i] = q, d
+            q, d = q + b.joint.nq, d + b.joint.ndof
+    return qadr, dadr
+
+
+def _path(raw, body, qadr, dadr):
+    """The node rows of the path from the root to ``body``, their dof addresses and the pose ``(at, turn)`` of the welded
+    bodies behind the last node, which the closing row takes up."""
+    chain = []
+    while body >= 0:
+        chain.append(body)
+        body = raw.bodies[body].parent
+    at, turn = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])       # the welded bodies' pose, waiting for the next node
+    rows, dofs = [], []
+    for i in reversed(chain):
+        b = raw.bodies[i]
+        quat = np.asarray(b.quat, float) / np.linalg.norm(b.quat)
+        at, turn = at + _quat_rotate(turn, np.asarray(b.pos, float)), _quat_mul(turn, quat)
+        if b.joint is None:
+            continue
+        j, row = b.joint, np.zeros(POINT_ROW_LEN)
+        norm = np.linalg.norm(j.axis)
+        row[0], row[1] = _JOINT_KINDS[j.type], qadr[i]
+        row[2] = float(j.ref) if j.type in (JOINT_HINGE, JOINT_SLIDE) else 0.0
+        row[3:6], row[6:10] = at, turn
+        row[10:13] = np.asarray(j.axis, float) / norm if norm > 0 else 0.0
+        row[13:16] = j.pos
+        rows.append(row)
+        dofs.append(dadr[i])
+        at, turn = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
+    if len(rows) > MAX_PATH_NODES:
+        raise ValueError("cost terms: a point's path holds %d jointed bodies, at most %d" % (len(rows), MAX_PATH_NODES))
+    return rows, dofs, at, turn
+
+
 def points_program(raw, points, differences=()):
     """The points program of ``mjmpc_points`` (row format: include/mjmpc_amd.h) for ``points`` - ``[(body index, position in
     the body frame)]`` - and ``differences`` - ``[(a, b)]``, indices into ``points`` - on ``raw``: float64
     ``[n_rows + len(differences)][16]`` and ``n_rows``.  A point's path holds one node per jointed body from the root to its
     body; a body without a joint is folded into the fixed pose of the node - or the point - behind it."""
-    qadr, adr = {}, 0
-    for i, b in enumerate(raw.bodies):
-        if b.joint is not None:
-            qadr[i] = adr
-            adr += b.joint.nq
+    qadr, dadr = _addresses(raw)
     rows = []
     for body, pos in points:
-        chain = []
-        while body >= 0:
-            chain.append(body)
-            body = raw.bodies[body].parent
-        at, turn = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])       # the welded bodies' pose, waiting for the next node
-        nodes = 0
-        for i in reversed(chain):
-            b = raw.bodies[i]
-            quat = np.asarray(b.quat, float) / np.linalg.norm(b.quat)
-            at, turn = at + _quat_rotate(turn, np.asarray(b.pos, float)), _quat_mul(turn, quat)
-            if b.joint is None:
-                continue
-            j, row = b.joint, np.zeros(POINT_ROW_LEN)
-            norm = np.linalg.norm(j.axis)
-            row[0], row[1] = _JOINT_KINDS[j.type], qadr[i]
-            row[2] = float(j.ref) if j.type in (JOINT_HINGE, JOINT_SLIDE) else 0.0
-            row[3:6], row[6:10] = at, turn
-            row[10:13] = np.asarray(j.axis, float) / norm if norm > 0 else 0.0
-            row[13:16] = j.pos
-            rows.append(row)
-            nodes += 1
-            at, turn = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
-        if nodes > MAX_PATH_NODES:
-            raise ValueError("cost terms: a point's path holds %d jointed bodies, at most %d" % (nodes, MAX_PATH_NODES))
+        nodes, _, at, turn = _path(raw, body, qadr, dadr)
+        rows.extend(nodes)
         row = np.zeros(POINT_ROW_LEN)
         row[0], row[3:6] = POINT_ROW, at + _quat_rotate(turn, np.asarray(pos, float))
         rows.append(row)
@@ -160,6 +189,41 @@ def points_program(raw, points, differences=()):
         row[0], row[1], row[2] = DIFFERENCE_ROW, a, b
         rows.append(row)
     return np.ascontiguousarray(np.stack(rows), np.float64), n_rows
+
+
+def motion_program(raw, outputs, differences=()):
+    """The program of ``mjmpc_points_motion`` (row format: include/mjmpc_amd.h) for ``outputs`` -
+    ``[(kind, body index, vector)]``, kind POINT_ROW / AXIS_ROW / VELOCITY_ROW / ANGULAR_ROW, the vector a position or an
+    axis in the body frame - and ``differences`` - ``[(a, b)]``, indices into ``outputs``: float64
+    ``[n_rows + len(differences)][16]``, ``n_rows`` and the node rows' first ``qvel`` addresses, int32 ``[n_rows]`` (0 on a
+    closing row).  All outputs on one body share one walk, placed where the first of them was defined: the path's nodes, then
+    one closing row per output with its slot - its index in ``outputs`` - in column 2 and 1 in column 1 on all but the last."""
+    qadr, dadr = _addresses(raw)
+    order = []
+    for _, body, _ in outputs:
+        if body not in order:
+            order.append(body)
+    rows, dofs = [], []
+    for body in order:
+        nodes, node_dofs, at, turn = _path(raw, body, qadr, dadr)
+        rows.extend(nodes)
+        dofs.extend(node_dofs)
+        mine = [(slot, o) for slot, o in enumerate(outputs) if o[1] == body]
+        for k, (slot, (kind, _, vec)) in enumerate(mine):
+            row = np.zeros(POINT_ROW_LEN)
+            row[0], row[1], row[2] = kind, float(k + 1 < len(mine)), slot
+            if kind in (POINT_ROW, VELOCITY_ROW):
+                row[3:6] = at + _quat_rotate(turn, np.asarray(vec, float))
+            elif kind == AXIS_ROW:
+                row[3:6] = _quat_rotate(turn, np.asarray(vec, float))
+            rows.append(row)
+            dofs.append(0)
+    n_rows = len(rows)
+    for a, b in differences:
+        row = np.zeros(POINT_ROW_LEN)
+        row[0], row[1], row[2] = DIFFERENCE_ROW, a, b
+        rows.append(row)
+    return np.ascontiguousarray(np.stack(rows), np.float64), n_rows, np.ascontiguousarray(dofs, np.int32)
 
 
 class CostTerms:
@@ -174,10 +238,11 @@ class CostTerms:
         #  group's first part) or False (a later part))
         self._terms = []
         self._periodic = None       # the tracked terms' shared `periodic` (None: no tracked term yet)
-        self._points = []           # (name, body index, position in the body frame)
-        self._differences = []      # (name, point a, point b): indices into _points
+        self._points = []           # the outputs (name, body index, position or axis in the body frame, closing kind): points
+                                    # (DESIGN 12.4), axes, velocities and angular velocities, in definition order
+        self._differences = []      # (name, output a, output b): indices into _points
 
-    # ------------------------------------------------------------------ world positions of points
+    # ------------------------------------------------------------------ world positions of points and motion (12.5)
     def _raw_for_points(self, what):
         if self.engine is None:
             raise ValueError("cost terms: %s needs an engine - CostTerms(engine): a point is resolved against its model" % what)
@@ -197,6 +262,21 @@ class CostTerms:
         if any(name == p[0] for p in self._points) or any(name == d[0] for d in self._differences):
             raise ValueError("cost terms: a point or difference named %r exists already" % name)
 
+    def _body_index(self, raw, body):
+        names = [b.name for b in raw.bodies]
+        if body not in names:
+            raise ValueError("cost terms: unknown body %r (this model has %s)" % (body, ", ".join(names)))
+        return names.index(body)
+
+    def _add_output(self, raw, name, index, vec, kind):
+        if len(self._points) >= MAX_POINTS:
+            raise ValueError("cost terms: a table holds at most %d points, axes, velocities and angular velocities" % MAX_POINTS)
+        if self._differences:
+            raise ValueError("cost terms: define the points before the differences (their blocks stand in that order)")
+        points_program(raw, [(int(index), np.zeros(3))])    # (a path too long is refused here)
+        self._points.append((name, int(index), np.array(vec, np.float64), kind))
+        return self
+
     def point(self, name, body=None, site=None, pos=None):
         """A block ``name`` of three entries behind the observation: the world position of the point ``pos`` (body frame,
         default its origin) of ``body``, or of the body-attached ``site`` (``RawModel.sites``), at the row's own ``qpos``.
@@ -212,42 +292,80 @@ class CostTerms:
                 raise ValueError("cost terms: unknown site %r (this model has %s)" % (site, ", ".join(sorted(raw.sites)) or "none"))
             index, pos = raw.sites[site]
         else:
-            names = [b.name for b in raw.bodies]
-            if body not in names:
-                raise ValueError("cost terms: unknown body %r (this model has %s)" % (body, ", ".join(names)))
-            index = names.index(body)
+            index = self._body_index(raw, body)
         pos = _finite((0.0, 0.0, 0.0) if pos is None else pos, "pos")
         if pos.shape != (3,):
             raise ValueError("cost terms: pos must be three numbers, got %r" % (pos.tolist(),))
-        if len(self._points) >= MAX_POINTS:
-            raise ValueError("cost terms: a table holds at most %d points" % MAX_POINTS)
-        if self._differences:
-            raise ValueError("cost terms: define the points before the differences (their blocks stand in that order)")
-        points_program(raw, [(int(index), pos)])            # (a path too long is refused here)
-        self._points.append((name, int(index), pos.copy()))
-        return self
+        return self._add_output(raw, name, index, pos, POINT_ROW)
+
+    def axis(self, name, body=None, axis=None):
+        """A block ``name`` of three entries: the world direction of the body-fixed vector ``axis`` of ``body`` (normalised
+        here), at the row's own ``qpos``.  Upright is then ``linear(obs=name, index=2, weight=-w)``."""
+        raw = self._raw_for_points("axis")
+        self._check_block_name(name)
+        if body is None:
+            raise ValueError("cost terms: axis takes body=")
+        index = self._body_index(raw, body)
+        if axis is None:
+            raise ValueError("cost terms: axis takes axis=(x, y, z)")
+        vec = _finite(axis, "axis")
+        if vec.shape != (3,):
+            raise ValueError("cost terms: axis must be three numbers, got %r" % (vec.tolist(),))
+        norm = float(np.linalg.norm(vec))
+        if not norm > 0.0 or not np.isfinite(norm):
+            raise ValueError("cost terms: axis must not be zero, got %r" % (vec.tolist(),))
+        return self._add_output(raw, name, index, vec / norm, AXIS_ROW)
+
+    def velocity(self, name, point):
+        """A block ``name`` of three entries: the world linear velocity of ``point``, a point named with ``point(...)``, from
+        the row's own ``qpos`` and ``qvel`` with MuJoCo's meaning of ``qvel``.  It shares the point's walk."""
+        raw = self._raw_for_points("velocity")
+        self._check_block_name(name)
+        known = [p for p in self._points if p[3] == POINT_ROW and p[0] == point]
+        if not known:
+            raise ValueError("cost terms: unknown point %r (defined: %s)"
+                             % (point, ", ".join(p[0] for p in self._points if p[3] == POINT_ROW) or "none"))
+        return self._add_output(raw, name, known[0][1], known[0][2], VELOCITY_ROW)
+
+    def angular_velocity(self, name, body=None):
+        """A block ``name`` of three entries: the world angular velocity of ``body``."""
+        raw = self._raw_for_points("angular_velocity")
+        self._check_block_name(name)
+        if body is None:
+            raise ValueError("cost terms: angular_velocity takes body=")
+        return self._add_output(raw, name, self._body_index(raw, body), np.zeros(3), ANGULAR_ROW)
 
     def difference(self, name, a, b):
-        """A block ``name`` of three entries behind the points' blocks: point ``a`` minus point ``b`` (world frame), one
-        double subtraction per component.  At most 16 differences a table."""
+        """A block ``name`` of three entries behind the outputs' blocks: ``a`` minus ``b`` (world frame), one double subtraction
+        per component - two points, two axes, two velocities or two angular velocities.  At most 16 differences a table."""
         self._raw_for_points("difference")
         self._check_block_name(name)
         known = [p[0] for p in self._points]
         for x in (a, b):
             if x not in known:
-                raise ValueError("cost terms: unknown point %r (defined: %s)" % (x, ", ".join(known) or "none"))
+                raise ValueError("cost terms: unknown point, axis or velocity %r (defined: %s)" % (x, ", ".join(known) or "none"))
+        ia, ib = known.index(a), known.index(b)
+        if self._points[ia][3] != self._points[ib][3]:
+            raise ValueError("cost terms: a difference takes two points, two axes, two velocities or two angular velocities; "
+                             "%r and %r are of different kinds" % (a, b))
         if len(self._differences) >= MAX_DIFFERENCES:
             raise ValueError("cost terms: a table holds at most %d differences" % MAX_DIFFERENCES)
-        self._differences.append((name, known.index(a), known.index(b)))
+        self._differences.append((name, ia, ib))
         return self
 
     @property
     def n_extra(self):
-        """Entries the points and differences add behind the observation: three each."""
+        """Entries the outputs and differences add behind the observation: three each."""
         return 3 * (len(self._points) + len(self._differences))
 
+    @property
+    def needs_motion_entry(self):
+        """Whether an axis, a velocity or an angular velocity is defined: ``mjmpc_points_motion`` instead of ``mjmpc_points``."""
+        return any(p[3] != POINT_ROW for p in self._points)
+
     def points_layout(self, engine=None):
-        """Named slices of the points' and differences' blocks in the augmented row, in definition order."""
+        """Named slices of the outputs' (points, axes, velocities, angular velocities) and differences' blocks in the augmented
+        row, in definition order."""
         engine = engine if engine is not None else self.engine
         d, out = (_dims(engine)[0] if engine is not None else 0), {}
         for k, entry in enumerate(self._points + self._differences):
@@ -256,14 +374,20 @@ class CostTerms:
 
     def points_table(self, engine=None):
         """``(program, n_rows, n_points, n_differences)`` - the points program of ``mjmpc_points``, float64
-        ``[n_rows + n_differences][16]`` (``points_program``) -, or ``None`` for a table without points."""
+        ``[n_rows + n_differences][16]`` (``points_program``) -, or ``None`` for a table without points.  With an axis, a
+        velocity or an angular velocity: ``(program, n_rows, n_outputs, n_differences, dofadr)``, the program and
+        the node rows' ``qvel`` addresses (int32 ``[n_rows]``) of ``mjmpc_points_motion`` (``motion_program``)."""
         if not self._points:
             return None
         engine = engine if engine is not None else self.engine
         raw = getattr(engine, "raw", None)
         if raw is None:
             raise ValueError("cost terms: points need an engine built from a RawModel")
-        program, n_rows = points_program(raw, [(b, p) for _, b, p in self._points], [(a, b) for _, a, b in self._differences])
+        differences = [(a, b) for _, a, b in self._differences]
+        if self.needs_motion_entry:
+            program, n_rows, dofadr = motion_program(raw, [(k, b, p) for _, b, p, k in self._points], differences)
+            return program, n_rows, len(self._points), len(self._differences), dofadr
+        program, n_rows = points_program(raw, [(b, p) for _, b, p, _ in self._points], differences)
         return program, n_rows, len(self._points), len(self._differences)
 
     # ------------------------------------------------------------------ the kinds
@@ -667,10 +791,27 @@ def cost_terms_from_config(block, engine, num_episodes=None):
 
     DESIGN 12.4: beside ``terms:`` the block may hold ``points:`` - a list of ``{name: tray, body: wrist, pos: [0, 0, 0.02]}`` or
     ``{name: tip, site: finger}`` - and ``differences:`` - ``{name: glass_from_tray, a: glass, b: tray}`` -, defined in that
-    order before the terms, which name them like any block; every episode of a batch gets the same ones."""
-    if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms", "points", "differences"}:
-        raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin', 'points' and 'differences'")
+    order before the terms, which name them like any block; every episode of a batch gets the same ones.
+
+    DESIGN 12.5: ``axes:`` - ``{name: glass_up, body: glass, axis: [0, 0, 1]}`` -, ``velocities:`` - ``{name: glass_vel, point:
+    glass}`` - and ``angular_velocities:`` - ``{name: glass_spin, body: glass}`` - stand between ``points:`` and
+    ``differences:``, and their blocks in that order: points, axes, velocities, angular velocities, differences."""
+    if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms", "points", "differences", "axes", "velocities",
+                                                     "angular_velocities"}:
+        raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin', 'points', 'axes', "
+                         "'velocities', 'angular_velocities' and 'differences'")
     point_entries, difference_entries = block.get("points") or [], block.get("differences") or []
+    axis_entries, velocity_entries = block.get("axes") or [], block.get("velocities") or []
+    angular_entries = block.get("angular_velocities") or []
+    for entry in axis_entries:
+        if not isinstance(entry, dict) or set(entry) != {"name", "body", "axis"}:
+            raise ValueError("cost_terms: an axis takes name, body and axis, got %r" % (entry,))
+    for entry in velocity_entries:
+        if not isinstance(entry, dict) or set(entry) != {"name", "point"}:
+            raise ValueError("cost_terms: a velocity takes name and point, got %r" % (entry,))
+    for entry in angular_entries:
+        if not isinstance(entry, dict) or set(entry) != {"name", "body"}:
+            raise ValueError("cost_terms: an angular velocity takes name and body, got %r" % (entry,))
     for entry in point_entries:
         if not isinstance(entry, dict) or "name" not in entry or set(entry) - {"name", "body", "site", "pos"}:
             raise ValueError("cost_terms: a point takes name and body or site, optionally pos, got %r" % (entry,))
@@ -708,6 +849,12 @@ def cost_terms_from_config(block, engine, num_episodes=None):
         terms = CostTerms(engine, keep_builtin=bool(block.get("keep_builtin", False)))
         for entry in point_entries:         # (the same points and differences for every episode)
             terms.point(entry["name"], body=entry.get("body"), site=entry.get("site"), pos=entry.get("pos"))
+        for entry in axis_entries:          # 
+            terms.axis(entry["name"], body=entry["body"], axis=entry["axis"])
+        for entry in velocity_entries:
+            terms.velocity(entry["name"], entry["point"])
+        for entry in angular_entries:
+            terms.angular_velocity(entry["name"], body=entry["body"])
         for entry in difference_entries:
             terms.difference(entry["name"], entry["a"], entry["b"])
         for entry in entries:
