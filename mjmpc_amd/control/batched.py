@@ -52,6 +52,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
+from ..envs.cost_terms import launch_points
 from ._device import noise_factor
 from .controller import _SHIFT_MODES, _seed_value
 
@@ -467,13 +468,8 @@ class _EpisodeBatch:
             #  the same launch as the single engines', over E P H rows: the cost entry reads the augmented rows
             program, n_rows, n_points, n_diff, d_aug, aug_rollout, aug_env, dofadr = self._points
             aug = aug_rollout if nobs is self._terms_nobs else aug_env
-            if dofadr is None:
-                _lib.check(self.lib.mjmpc_points(self._code, self.num_episodes * P * H, d_obs, self.engine._nq, _vp(nobs),
-                                                 _vp(program), n_rows, n_points, n_diff, _vp(aug), s))
-            else:
-                _lib.check(self.lib.mjmpc_points_motion(self._code, self.num_episodes * P * H, d_obs, self.engine._nq,
-                                                        self.model.nv, _vp(nobs), _vp(program), _vp(dofadr), n_rows, n_points,
-                                                        n_diff, _vp(aug), s))
+            _lib.check(launch_points(self.lib, self._code, self.num_episodes * P * H, d_obs, self.engine._nq, self.model.nv,
+                                     _vp(nobs), _vp(program), _vp(dofadr), n_rows, n_points, n_diff, _vp(aug), s))
             nobs, d_obs = aug, d_aug
         if self._quad is not None:
             refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)

@@ -1,44 +1,31 @@
-// World positions of user-named points for the cost terms: a launch between a rollout and its
-// cost launch that copies every observation row into an augmented row and appends, in double whatever the storage type, the
-// world positions of up to 16 points on any bodies and up to 16 differences of two points.  The cost kernels then read these
-// entries as ordinary observation entries: nothing in cost_terms.hip or in a rollout translation unit changes.
+// World positions of user-named points for the cost terms and, with MOTION, body axes and velocities beside them
+// (DESIGN 12.5): a launch between a rollout and its cost launch that copies every observation row into an augmented row and
+// appends, in double whatever the storage type, up to 16 outputs of three entries on any bodies and up to 16 differences of two
+// outputs.  The cost kernels then read these entries as ordinary observation entries: nothing in cost_terms.hip or in a rollout
+// translation unit changes.
 //
-// The points program (float64 [n_rows + n_diff][16], include/mjmpc_amd.h) is wave-uniform: every lane walks the same rows over
-// its own qpos.  A row is one node of a point's path from the root (fixed pose in the parent's frame, then the joint), or the
-// point itself, which closes the path:
-//   col 0        kind: 0 POINT, 1 HINGE, 2 SLIDE, 3 BALL, 4 FREE
-//   col 1, 2     qpos address of the joint, qpos0 (hinge / slide: MJCF ref)
-//   col 3 .. 5   node: the body's position in its parent's frame; POINT: the point in the frame of the last node
-//   col 6 .. 9   node: the body's orientation in its parent's frame, a unit quaternion (w, x, y, z)
-//   col 10 .. 12 unit joint axis (hinge, slide), body frame          col 13 .. 15 anchor (hinge, ball), body frame
-// The semantics are MuJoCo's mj_kinematics, as the test oracle's kinematics() states them: the frame moves to
-// parent o (pos, quat); a hinge turns it by q - qpos0 about the axis through the anchor and a ball by the stored quaternion,
-// the anchor held fixed; a slide moves it by q - qpos0 along the axis; a free joint replaces it by qpos[adr .. adr + 7].  The
-// quaternions of qpos are used as stored - no normalised copy is written anywhere - and rotate as q / |q|, which is what
-// the oracle's quat2mat does.  Only the current frame (a position and a unit quaternion: 7 doubles) lives in registers; paths
-// that share ancestors recompute them: no per-lane frame storage, no scratch.  Measured, the launch is bound by the nodes'
-// arithmetic (2.5 - 4 us per node over 4096 x 32 rows, much of it the hinge's double-precision sincos), not by the bytes it
-// moves: profiles/r25_points.txt.
-// The n_diff rows behind the paths are {5, a, b}: the entry point a - point b, one double subtraction per component.
+// The program (float64 [n_rows + n_diff][16]; the row format: include/mjmpc_amd.h) is wave-uniform: every lane walks the same
+// rows over its own qpos - one walk, pt_walk<T, MOTION>, for both entries.  A node row moves the frame as MuJoCo's
+// mj_kinematics does, as the test oracle's kinematics() states it; a closing row writes an output.  The quaternions of qpos are
+// used as stored - no normalised copy is written anywhere - and rotate as q / |q|, which is what the oracle's quat2mat does.
+// Only the current frame (a position and a unit quaternion: 7 doubles) lives in registers; paths that share ancestors
+// recompute them: no per-lane frame storage, no scratch.  Measured, the launch is bound by the nodes' arithmetic (2.5 - 4 us
+// per node over 4096 x 32 rows, much of it the hinge's double-precision sincos), not by the bytes it moves:
+// profiles/r25_points.txt.  The n_diff rows behind the walks are {5, a, b}: output a - output b, one double subtraction per
+// component.
 //
-// Axes and velocities (mjmpc_points_motion): the MOTION = true instantiation of the same kernel carries, beside the
-// frame, the world linear velocity v of the frame's origin and the world angular velocity w of the frame (6 more doubles) and
-// reads qvel - entries nq .. nq + nv of the row - at the dof address d_dofadr[k] of node row k, with MuJoCo's meaning of qvel:
-//   fixed pose  v += w x (R pos)                     slide  v += w x (a d) + a qd  (a: the axis in the world)
-//   hinge       the anchor's velocity v + w x r_a is taken, then w += a qd, then the origin's is the anchor's - w x (R' local)
-//   ball        as the hinge, with w += R' omega_local: the three rates are the angular velocity in the child's frame
-//   free        v = qvel[0:3] (world), w = R qvel[3:6] (body frame)
-// Its closing rows name their output slot (col 2) and kind (col 0): 0 POINT p + R off, 6 AXIS R a, 7 VELOCITY v + w x (R off),
-// 8 ANGULAR w; col 1 = 1 keeps the frame for the next closing row, so that all outputs on one body share one walk (a point and
-// its velocity: nodes + 2 rows).  Every slot is cleared first: one that no closing row names reads as 0.  The kind branch is
-// uniform, the dof addresses are wave-uniform reads like the rows.  mjmpc_points launches the MOTION = false instantiation,
-// whose walk is the code it always was (registers, LDS, scratch: profiles/r26_motion_resources.txt).
+// The MOTION part (mjmpc_points_motion) carries, beside the frame, the world linear velocity v of the frame's origin and the
+// world angular velocity w of the frame (6 more doubles), reads qvel - entries nq .. nq + nv of the row - at the dof address
+// d_dofadr[k] of node row k, takes a closing row's slot and keep flag from the row and clears every slot first: one that no
+// closing row names reads as 0.  Without it (mjmpc_points) a closing row is a point, the slots are the points in program order,
+// every point closes its walk and nothing is cleared.  The kind branch is uniform, the dof addresses are wave-uniform reads
+// like the rows.  Registers, LDS, scratch of the four instantiations: profiles/r27_points_one_walk.txt.
 //
 // Shape (cost_terms.hip's): a workgroup takes `rows` consecutive observation rows - they lie back to back in memory -, copies
 // them into LDS with unit-stride loads (odd row pitch: the lanes' column reads spread over the banks), lane j walks the program
-// over row j and parks its points in LDS as doubles, laid out [entry][lane] (lane-consecutive, no bank conflict); then all
+// over row j and parks its outputs in LDS as doubles, laid out [entry][lane] (lane-consecutive, no bank conflict); then all
 // lanes write the augmented tile, which is back to back in memory too, with unit stride: the observation's words as they came
-// (bit for bit), the points rounded once to the storage type, the differences formed from the parked doubles and rounded once.
+// (bit for bit), the outputs rounded once to the storage type, the differences formed from the parked doubles and rounded once.
 // Node rows are one address for all lanes, read const __restrict__ through the scalar cache; the joint-kind branch is uniform.
 #include <hip/hip_runtime.h>
 
@@ -88,95 +75,130 @@ __device__ __forceinline__ void pt_cross(const double* a, const double* b, doubl
     out[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// The walk of the MOTION instantiation over one row `my`: frame, origin velocity v and angular velocity w; the
-// outputs go to pts[(3 slot + c) * rows] (pts: this lane's column of the parked entries).
-template <typename T>
-__device__ __forceinline__ void pt_walk_motion(const T* my, const double* __restrict__ prog, const int32_t* __restrict__ dofadr,
-                                               int n_rows, int n_out, int nq, int nv, double* pts, int rows) {
+// The output o of a closing row on the frame f: kind 0 POINT p + R off - without MOTION the only one - and, with v and w,
+// 6 AXIS R a, 7 VELOCITY v + w x (R off), 8 ANGULAR w
+template <bool MOTION>
+__device__ __forceinline__ void pt_output(int kind, const PtFrame& f, const double* v, const double* w,
+                                          const double* __restrict__ row, double* o) {
+    if constexpr (MOTION) {
+        if (kind == 8) {
+            o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
+            return;
+        }
+    }
+    double t[3], c[3];
+    pt_rotate(f.q, row[3], row[4], row[5], t);
+    if (kind == 0) {
+        o[0] = f.p[0] + t[0]; o[1] = f.p[1] + t[1]; o[2] = f.p[2] + t[2];
+    } else if constexpr (MOTION) {
+        if (kind == 7) {
+            pt_cross(w, t, c);
+            o[0] = v[0] + c[0]; o[1] = v[1] + c[1]; o[2] = v[2] + c[2];
+        } else {
+            o[0] = t[0]; o[1] = t[1]; o[2] = t[2];
+        }
+    }
+}
+
+// The walk over one row `my`: the frame and, with MOTION, its origin's velocity v and its angular velocity w; the outputs go
+// to pts[(3 slot + c) * rows] (pts: this lane's column of the parked entries).  nv and dofadr are read with MOTION alone.
+template <typename T, bool MOTION>
+__device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ prog, const int32_t* __restrict__ dofadr,
+                                        int n_rows, int n_out, int nq, int nv, double* pts, int rows) {
     // entry i of my qpos / qvel, held inside it whatever the tables say
     auto qpos = [&](int i) { return (double)my[i < 0 ? 0 : i < nq ? i : nq - 1]; };
-    auto qvel = [&](int i) { return (double)my[nq + (i < 0 ? 0 : i < nv ? i : nv - 1)]; };
-    for (int e = 0; e < 3 * n_out; ++e) pts[e * rows] = 0.0;
+    [[maybe_unused]] auto qvel = [&](int i) { return (double)my[nq + (i < 0 ? 0 : i < nv ? i : nv - 1)]; };
+    if constexpr (MOTION)
+        for (int e = 0; e < 3 * n_out; ++e) pts[e * rows] = 0.0;
     PtFrame f{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
-    double v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+    [[maybe_unused]] double v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+    int point = 0;                          // the closing rows so far: without MOTION a row's slot
     for (int k = 0; k < n_rows; ++k) {
         const double* __restrict__ row = prog + (long)PT_ROW * k;
         const int kind = (int)row[0];
-        double t[3], c[3];
-        if (kind == 0 || kind >= 6) {       // a closing row: its output into its slot; the frame kept or reset
-            const int slot = (int)row[2];
+        double t[3];
+        [[maybe_unused]] double c[3];
+        if (kind == 0 || (MOTION && kind >= 6)) {       // a closing row: its output into its slot; the frame kept or reset
             double o[3];
-            if (kind == 8) {
-                o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
-            } else {
-                pt_rotate(f.q, row[3], row[4], row[5], t);
-                if (kind == 0) {
-                    o[0] = f.p[0] + t[0]; o[1] = f.p[1] + t[1]; o[2] = f.p[2] + t[2];
-                } else if (kind == 7) {
-                    pt_cross(w, t, c);
-                    o[0] = v[0] + c[0]; o[1] = v[1] + c[1]; o[2] = v[2] + c[2];
-                } else {
-                    o[0] = t[0]; o[1] = t[1]; o[2] = t[2];
-                }
-            }
+            pt_output<MOTION>(kind, f, v, w, row, o);
+            const int slot = MOTION ? (int)row[2] : point;
             if (slot >= 0 && slot < n_out) {
                 pts[(3 * slot + 0) * rows] = o[0];
                 pts[(3 * slot + 1) * rows] = o[1];
                 pts[(3 * slot + 2) * rows] = o[2];
             }
-            if (row[1] == 0.0) {
+            ++point;
+            if (!MOTION || row[1] == 0.0) {             // the next walk starts at the world frame, at rest
                 f = PtFrame{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
-                v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = 0.0;
+                if constexpr (MOTION) v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = 0.0;
             }
             continue;
         }
-        const int adr = (int)row[1], dof = dofadr[k];
+        const int adr = (int)row[1];
+        [[maybe_unused]] int dof = 0;
+        if constexpr (MOTION) dof = dofadr[k];
         if (kind == 4) {                    // free: the frame is qpos' own, the linear rates the world's, the angular the body's
             const double qw = qpos(adr + 3), x = qpos(adr + 4), y = qpos(adr + 5), z = qpos(adr + 6);
             const double s = 1.0 / sqrt(qw * qw + x * x + y * y + z * z);
             f = PtFrame{{qpos(adr), qpos(adr + 1), qpos(adr + 2)}, {qw * s, x * s, y * s, z * s}};
-            v[0] = qvel(dof); v[1] = qvel(dof + 1); v[2] = qvel(dof + 2);
-            pt_rotate(f.q, qvel(dof + 3), qvel(dof + 4), qvel(dof + 5), w);
+            if constexpr (MOTION) {
+                v[0] = qvel(dof); v[1] = qvel(dof + 1); v[2] = qvel(dof + 2);
+                pt_rotate(f.q, qvel(dof + 3), qvel(dof + 4), qvel(dof + 5), w);
+            }
             continue;
         }
         pt_rotate(f.q, row[3], row[4], row[5], t);
-        pt_cross(w, t, c);
-        v[0] += c[0]; v[1] += c[1]; v[2] += c[2];
+        if constexpr (MOTION) {
+            pt_cross(w, t, c);
+            v[0] += c[0]; v[1] += c[1]; v[2] += c[2];
+        }
         f.p[0] += t[0]; f.p[1] += t[1]; f.p[2] += t[2];
         pt_mul(f.q, row[6], row[7], row[8], row[9]);
-        if (kind == 2) {                    // slide: along the axis; the displaced origin is carried round by w
-            const double d = qpos(adr) - row[2], qd = qvel(dof);
+        if (kind == 2) {                    // slide: along the axis, no rotation
+            const double d = qpos(adr) - row[2];
             pt_rotate(f.q, row[10], row[11], row[12], t);
-            double ad[3] = {t[0] * d, t[1] * d, t[2] * d};
-            pt_cross(w, ad, c);
-            v[0] += c[0] + t[0] * qd; v[1] += c[1] + t[1] * qd; v[2] += c[2] + t[2] * qd;
+            const double ad[3] = {t[0] * d, t[1] * d, t[2] * d};
+            if constexpr (MOTION) {         // the displaced origin is carried round by w
+                const double qd = qvel(dof);
+                pt_cross(w, ad, c);
+                v[0] += c[0] + t[0] * qd; v[1] += c[1] + t[1] * qd; v[2] += c[2] + t[2] * qd;
+            }
             f.p[0] += ad[0]; f.p[1] += ad[1]; f.p[2] += ad[2];
             continue;
         }
         // hinge, ball: about the anchor, which stays where it is and moves as the frame before the joint moves it
         double anchor[3];
         pt_rotate(f.q, row[13], row[14], row[15], t);
-        pt_cross(w, t, c);
         anchor[0] = f.p[0] + t[0]; anchor[1] = f.p[1] + t[1]; anchor[2] = f.p[2] + t[2];
-        v[0] += c[0]; v[1] += c[1]; v[2] += c[2];                  // (the anchor's velocity)
+        if constexpr (MOTION) {
+            pt_cross(w, t, c);
+            v[0] += c[0]; v[1] += c[1]; v[2] += c[2];              // (the anchor's velocity)
+        }
         if (kind == 1) {
-            const double half = 0.5 * (qpos(adr) - row[2]), qd = qvel(dof);
+            const double half = 0.5 * (qpos(adr) - row[2]);
             double sn, cs;
             sincos(half, &sn, &cs);
             pt_mul(f.q, cs, row[10] * sn, row[11] * sn, row[12] * sn);
-            pt_rotate(f.q, row[10], row[11], row[12], t);
-            w[0] += t[0] * qd; w[1] += t[1] * qd; w[2] += t[2] * qd;
+            if constexpr (MOTION) {
+                const double qd = qvel(dof);
+                pt_rotate(f.q, row[10], row[11], row[12], t);
+                w[0] += t[0] * qd; w[1] += t[1] * qd; w[2] += t[2] * qd;
+            }
         } else {
             const double qw = qpos(adr), x = qpos(adr + 1), y = qpos(adr + 2), z = qpos(adr + 3);
             const double s = 1.0 / sqrt(qw * qw + x * x + y * y + z * z);
             pt_mul(f.q, qw * s, x * s, y * s, z * s);
-            pt_rotate(f.q, qvel(dof), qvel(dof + 1), qvel(dof + 2), t);
-            w[0] += t[0]; w[1] += t[1]; w[2] += t[2];
+            if constexpr (MOTION) {
+                pt_rotate(f.q, qvel(dof), qvel(dof + 1), qvel(dof + 2), t);
+                w[0] += t[0]; w[1] += t[1]; w[2] += t[2];
+            }
         }
         pt_rotate(f.q, row[13], row[14], row[15], t);
-        pt_cross(w, t, c);
         f.p[0] = anchor[0] - t[0]; f.p[1] = anchor[1] - t[1]; f.p[2] = anchor[2] - t[2];
-        v[0] -= c[0]; v[1] -= c[1]; v[2] -= c[2];
+        if constexpr (MOTION) {
+            pt_cross(w, t, c);
+            v[0] -= c[0]; v[1] -= c[1]; v[2] -= c[2];
+        }
     }
 }
 
@@ -215,63 +237,7 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
     }
     __syncthreads();
 
-    if constexpr (MOTION) {
-        if (j < mine) pt_walk_motion(tile + j * po, prog, dofadr, n_rows, n_points, nq, nv, pts + j, rows);
-    } else if (j < mine) {
-        const T* const my = tile + j * po;
-        // entry i of my qpos, held inside it whatever the table says
-        auto qpos = [&](int i) { return (double)my[i < 0 ? 0 : i < nq ? i : nq - 1]; };
-        PtFrame f{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
-        int point = 0;
-        for (int k = 0; k < n_rows; ++k) {
-            const double* __restrict__ row = prog + (long)PT_ROW * k;
-            const int kind = (int)row[0];
-            double t[3];
-            if (kind == 0) {                // the point closes its path; the next one starts at the world frame
-                pt_rotate(f.q, row[3], row[4], row[5], t);
-                if (point < n_points) {
-                    pts[(3 * point + 0) * rows + j] = f.p[0] + t[0];
-                    pts[(3 * point + 1) * rows + j] = f.p[1] + t[1];
-                    pts[(3 * point + 2) * rows + j] = f.p[2] + t[2];
-                }
-                ++point;
-                f = PtFrame{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
-                continue;
-            }
-            const int adr = (int)row[1];
-            if (kind == 4) {                // free: the frame is qpos' own
-                const double w = qpos(adr + 3), x = qpos(adr + 4), y = qpos(adr + 5), z = qpos(adr + 6);
-                const double s = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-                f = PtFrame{{qpos(adr), qpos(adr + 1), qpos(adr + 2)}, {w * s, x * s, y * s, z * s}};
-                continue;
-            }
-            pt_rotate(f.q, row[3], row[4], row[5], t);
-            f.p[0] += t[0]; f.p[1] += t[1]; f.p[2] += t[2];
-            pt_mul(f.q, row[6], row[7], row[8], row[9]);
-            if (kind == 2) {                // slide: along the axis, no rotation
-                const double d = qpos(adr) - row[2];
-                pt_rotate(f.q, row[10], row[11], row[12], t);
-                f.p[0] += t[0] * d; f.p[1] += t[1] * d; f.p[2] += t[2] * d;
-                continue;
-            }
-            // hinge, ball: about the anchor, which stays where it is
-            double anchor[3];
-            pt_rotate(f.q, row[13], row[14], row[15], t);
-            anchor[0] = f.p[0] + t[0]; anchor[1] = f.p[1] + t[1]; anchor[2] = f.p[2] + t[2];
-            if (kind == 1) {
-                const double half = 0.5 * (qpos(adr) - row[2]);
-                double sn, cs;
-                sincos(half, &sn, &cs);
-                pt_mul(f.q, cs, row[10] * sn, row[11] * sn, row[12] * sn);
-            } else {
-                const double w = qpos(adr), x = qpos(adr + 1), y = qpos(adr + 2), z = qpos(adr + 3);
-                const double s = 1.0 / sqrt(w * w + x * x + y * y + z * z);
-                pt_mul(f.q, w * s, x * s, y * s, z * s);
-            }
-            pt_rotate(f.q, row[13], row[14], row[15], t);
-            f.p[0] = anchor[0] - t[0]; f.p[1] = anchor[1] - t[1]; f.p[2] = anchor[2] - t[2];
-        }
-    }
+    if (j < mine) pt_walk<T, MOTION>(tile + j * po, prog, dofadr, n_rows, n_points, nq, nv, pts + j, rows);
     __syncthreads();
 
     {                                       // the augmented tile: unit stride over the lanes
@@ -298,19 +264,43 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
     }
 }
 
-int bad(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_points", detail); }
-int bad_motion(const char* detail) { return set_error(MJMPC_E_BADARG, "mjmpc_points_motion", detail); }
-
-// the rows of a tile and its LDS bytes: the largest power of two up to PT_WG whose tile and parked entries fit PT_LDS_BYTES
-struct PtShape {
-    int rows;
-    size_t lds;
-};
-PtShape pt_shape(int d_obs, long word, long pts_bytes) {
-    int rows = PT_WG;
+// Both entries: the checks, the tile - the largest power of two of rows up to PT_WG whose rows and parked outputs fit
+// PT_LDS_BYTES - and the launch.  `motion`: mjmpc_points_motion, which alone reads (and checks) nv and dofadr and calls its
+// outputs n_out where mjmpc_points says n_points.
+int launch_points(const char* entry, bool motion, int dtype, int64_t N, int d_obs, int nq, int nv, const void* obs,
+                  const double* prog, const int32_t* dofadr, int n_rows, int n_out, int n_diff, void* out, void* stream) {
+    auto bad = [&](const char* detail) { return set_error(MJMPC_E_BADARG, entry, detail); };
+    if (!obs || !prog || !out) return bad("null pointer");
+    if (motion && !dofadr) return bad("null d_dofadr: the node rows' qvel addresses");
+    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad("unknown dtype");
+    if (N < 1 || d_obs < 1) return bad("N and d_obs must be >= 1");
+    if (nq < 1 || nq > d_obs) return bad("nq must be in 1 .. d_obs: qpos opens the observation");
+    if (motion && (nv < 1 || (long)nq + nv > d_obs)) return bad("nv must be >= 1 and nq + nv <= d_obs: qvel follows qpos");
+    if (n_out < 1 || n_out > PT_MAX_POINTS) return bad(motion ? "n_out must be in 1 .. 16" : "n_points must be in 1 .. 16");
+    if (n_diff < 0 || n_diff > PT_MAX_DIFF) return bad("n_diff must be in 0 .. 16");
+    if (n_rows < n_out || n_rows > PT_MAX_ROWS)
+        return bad(motion ? "n_rows must be in n_out .. 544 (16 paths of 33 nodes and an output)"
+                          : "n_rows must be in n_points .. 544 (16 paths of 33 nodes and a point)");
+    const long word = dtype == MJMPC_F32 ? 4 : 8;
+    const long pts_bytes = 8L * 3 * n_out;                          // a row's parked outputs
+    if ((long)d_obs > (PT_LDS_BYTES - pts_bytes - 8) / word - 1)
+        return bad(motion ? "an observation row and its outputs of more than 60 KiB"
+                          : "an observation row and its points of more than 60 KiB");
     auto lds = [&](int r) { return (r * word * pt_pitch(d_obs) + 7) / 8 * 8 + r * pts_bytes; };
+    int rows = PT_WG;
     while (lds(rows) > PT_LDS_BYTES) rows >>= 1;
-    return PtShape{rows, (size_t)lds(rows)};
+    const long blocks = ((long)N + rows - 1) / rows;
+    if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
+    auto launch = [&](auto zero) {
+        using T = decltype(zero);
+        auto* const kernel = motion ? points_kernel<T, true> : points_kernel<T, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), (size_t)lds(rows), (hipStream_t)stream,
+                           (const T*)obs, prog, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (T*)out, nv, dofadr);
+    };
+    if (dtype == MJMPC_F32) launch(0.0f);
+    else launch(0.0);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error((int)e, entry, hipGetErrorString(e));
 }
 
 }  // namespace
@@ -318,62 +308,12 @@ PtShape pt_shape(int d_obs, long word, long pts_bytes) {
 
 extern "C" int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void* d_obs_rows, const double* d_program, int n_rows,
                             int n_points, int n_diff, void* d_out, void* stream) {
-    using namespace mjmpc;
-    if (!d_obs_rows || !d_program || !d_out) return bad("null pointer");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad("unknown dtype");
-    if (N < 1 || d_obs < 1) return bad("N and d_obs must be >= 1");
-    if (nq < 1 || nq > d_obs) return bad("nq must be in 1 .. d_obs: qpos opens the observation");
-    if (n_points < 1 || n_points > PT_MAX_POINTS) return bad("n_points must be in 1 .. 16");
-    if (n_diff < 0 || n_diff > PT_MAX_DIFF) return bad("n_diff must be in 0 .. 16");
-    if (n_rows < n_points || n_rows > PT_MAX_ROWS) return bad("n_rows must be in n_points .. 544 (16 paths of 33 nodes and a point)");
-    const long word = dtype == MJMPC_F32 ? 4 : 8;
-    const long pts_bytes = 8L * 3 * n_points;                       // a row's parked points
-    if ((long)d_obs > (PT_LDS_BYTES - pts_bytes - 8) / word - 1)
-        return bad("an observation row and its points of more than 60 KiB");
-    const PtShape sh = pt_shape(d_obs, word, pts_bytes);
-    const int rows = sh.rows;
-    const long blocks = ((long)N + rows - 1) / rows;
-    if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
-    if (dtype == MJMPC_F32)
-        hipLaunchKernelGGL((points_kernel<float, false>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
-                           (const float*)d_obs_rows, d_program, n_rows, n_points, n_diff, (long)N, d_obs, nq, rows, (float*)d_out,
-                           0, (const int32_t*)nullptr);
-    else
-        hipLaunchKernelGGL((points_kernel<double, false>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
-                           (const double*)d_obs_rows, d_program, n_rows, n_points, n_diff, (long)N, d_obs, nq, rows,
-                           (double*)d_out, 0, (const int32_t*)nullptr);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_points", hipGetErrorString(e));
+    return mjmpc::launch_points("mjmpc_points", false, dtype, N, d_obs, nq, 0, d_obs_rows, d_program, nullptr, n_rows, n_points,
+                                n_diff, d_out, stream);
 }
 
 extern "C" int mjmpc_points_motion(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
                                    const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, void* d_out, void* stream) {
-    using namespace mjmpc;
-    if (!d_obs_rows || !d_program || !d_out) return bad_motion("null pointer");
-    if (!d_dofadr) return bad_motion("null d_dofadr: the node rows' qvel addresses");
-    if (dtype != MJMPC_F32 && dtype != MJMPC_F64) return bad_motion("unknown dtype");
-    if (N < 1 || d_obs < 1) return bad_motion("N and d_obs must be >= 1");
-    if (nq < 1 || nq > d_obs) return bad_motion("nq must be in 1 .. d_obs: qpos opens the observation");
-    if (nv < 1 || (long)nq + nv > d_obs) return bad_motion("nv must be >= 1 and nq + nv <= d_obs: qvel follows qpos");
-    if (n_out < 1 || n_out > PT_MAX_POINTS) return bad_motion("n_out must be in 1 .. 16");
-    if (n_diff < 0 || n_diff > PT_MAX_DIFF) return bad_motion("n_diff must be in 0 .. 16");
-    if (n_rows < n_out || n_rows > PT_MAX_ROWS) return bad_motion("n_rows must be in n_out .. 544 (16 paths of 33 nodes and an output)");
-    const long word = dtype == MJMPC_F32 ? 4 : 8;
-    const long pts_bytes = 8L * 3 * n_out;                          // a row's parked outputs
-    if ((long)d_obs > (PT_LDS_BYTES - pts_bytes - 8) / word - 1)
-        return bad_motion("an observation row and its outputs of more than 60 KiB");
-    const PtShape sh = pt_shape(d_obs, word, pts_bytes);
-    const int rows = sh.rows;
-    const long blocks = ((long)N + rows - 1) / rows;
-    if (blocks > INT32_MAX) return bad_motion("more than 2^31 workgroups");
-    if (dtype == MJMPC_F32)
-        hipLaunchKernelGGL((points_kernel<float, true>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
-                           (const float*)d_obs_rows, d_program, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (float*)d_out, nv,
-                           d_dofadr);
-    else
-        hipLaunchKernelGGL((points_kernel<double, true>), dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), sh.lds, (hipStream_t)stream,
-                           (const double*)d_obs_rows, d_program, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (double*)d_out,
-                           nv, d_dofadr);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_error((int)e, "mjmpc_points_motion", hipGetErrorString(e));
+    return mjmpc::launch_points("mjmpc_points_motion", true, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr, n_rows,
+                                n_out, n_diff, d_out, stream);
 }

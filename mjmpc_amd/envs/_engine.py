@@ -18,6 +18,7 @@ from .. import _lib
 from ..models.compile import principal_inertia, require_f32_power_ratio
 from ..models.raw import TASK_FORWARD, RawModel
 from ._resets import EnvResetWatch, SimulationUnstableError  # noqa: F401
+from .cost_terms import launch_points
 from .seeding import np_random
 
 _DT = {"f32": (_lib.F32, np.float32), "f64": (_lib.F64, np.float64)}
@@ -466,14 +467,9 @@ class RolloutEngine(EnvResetWatch):
             step = (P, H) == (1, 1)
             aug = self._buffer("points_step" if step else "points_obs",
                                (self.d_obs + n_extra,) if nobs.dim() == 1 else (P, H, self.d_obs + n_extra))
-            if dofadr is None:
-                _lib.check(self._lib.mjmpc_points(self._code, P * H, self.d_obs, self._nq, _ptr(nobs), _ptr(program), n_rows,
-                                                  n_points, n_diff, _ptr(aug), self._stream()))
-            else:
-                #  axes, velocities: the same launch with qvel - the nv entries behind qpos - and the dof addresses
-                _lib.check(self._lib.mjmpc_points_motion(self._code, P * H, self.d_obs, self._nq, self.model.nv, _ptr(nobs),
-                                                         _ptr(program), _ptr(dofadr), n_rows, n_points, n_diff, _ptr(aug),
-                                                         self._stream()))
+            #  with axes or velocities - a dof-address table - the launch reads qvel, the nv entries behind qpos, too
+            _lib.check(launch_points(self._lib, self._code, P * H, self.d_obs, self._nq, self.model.nv, _ptr(nobs), _ptr(program),
+                                     _ptr(dofadr), n_rows, n_points, n_diff, _ptr(aug), self._stream()))
             self._points_last = nobs = aug
             d_obs += n_extra
         t = self._terms_dev

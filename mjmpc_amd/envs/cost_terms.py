@@ -170,48 +170,20 @@ def _path(raw, body, qadr, dadr):
     return rows, dofs, at, turn
 
 
-def points_program(raw, points, differences=()):
-    """The points program of ``mjmpc_points`` (row format: include/mjmpc_amd.h) for ``points`` - ``[(body index, position in
-    the body frame)]`` - and ``differences`` - ``[(a, b)]``, indices into ``points`` - on ``raw``: float64
-    ``[n_rows + len(differences)][16]`` and ``n_rows``.  A point's path holds one node per jointed body from the root to its
-    body; a body without a joint is folded into the fixed pose of the node - or the point - behind it."""
+def _program(raw, walks, differences):
+    """The rows behind ``points_program`` and ``motion_program`` for ``walks`` - ``[(body index, [(kind, slot, vector)])]``:
+    per walk the nodes of the body's path, then one closing row per output with its slot in column 2 and 1 in column 1 on all
+    but the walk's last - and the ``differences`` rows behind them: float64 ``[n_rows + len(differences)][16]``, ``n_rows``
+    and the node rows' first ``qvel`` addresses, int32 ``[n_rows]`` (0 on a closing row)."""
     qadr, dadr = _addresses(raw)
-    rows = []
-    for body, pos in points:
-        nodes, _, at, turn = _path(raw, body, qadr, dadr)
-        rows.extend(nodes)
-        row = np.zeros(POINT_ROW_LEN)
-        row[0], row[3:6] = POINT_ROW, at + _quat_rotate(turn, np.asarray(pos, float))
-        rows.append(row)
-    n_rows = len(rows)
-    for a, b in differences:
-        row = np.zeros(POINT_ROW_LEN)
-        row[0], row[1], row[2] = DIFFERENCE_ROW, a, b
-        rows.append(row)
-    return np.ascontiguousarray(np.stack(rows), np.float64), n_rows
-
-
-def motion_program(raw, outputs, differences=()):
-    """The program of ``mjmpc_points_motion`` (DESIGN 12.5; row format: include/mjmpc_amd.h) for ``outputs`` -
-    ``[(kind, body index, vector)]``, kind POINT_ROW / AXIS_ROW / VELOCITY_ROW / ANGULAR_ROW, the vector a position or an
-    axis in the body frame - and ``differences`` - ``[(a, b)]``, indices into ``outputs``: float64
-    ``[n_rows + len(differences)][16]``, ``n_rows`` and the node rows' first ``qvel`` addresses, int32 ``[n_rows]`` (0 on a
-    closing row).  All outputs on one body share one walk, placed where the first of them was defined: the path's nodes, then
-    one closing row per output with its slot - its index in ``outputs`` - in column 2 and 1 in column 1 on all but the last."""
-    qadr, dadr = _addresses(raw)
-    order = []
-    for _, body, _ in outputs:
-        if body not in order:
-            order.append(body)
     rows, dofs = [], []
-    for body in order:
+    for body, outputs in walks:
         nodes, node_dofs, at, turn = _path(raw, body, qadr, dadr)
         rows.extend(nodes)
         dofs.extend(node_dofs)
-        mine = [(slot, o) for slot, o in enumerate(outputs) if o[1] == body]
-        for k, (slot, (kind, _, vec)) in enumerate(mine):
+        for k, (kind, slot, vec) in enumerate(outputs):
             row = np.zeros(POINT_ROW_LEN)
-            row[0], row[1], row[2] = kind, float(k + 1 < len(mine)), slot
+            row[0], row[1], row[2] = kind, float(k + 1 < len(outputs)), slot
             if kind in (POINT_ROW, VELOCITY_ROW):
                 row[3:6] = at + _quat_rotate(turn, np.asarray(vec, float))
             elif kind == AXIS_ROW:
@@ -224,6 +196,36 @@ def motion_program(raw, outputs, differences=()):
         row[0], row[1], row[2] = DIFFERENCE_ROW, a, b
         rows.append(row)
     return np.ascontiguousarray(np.stack(rows), np.float64), n_rows, np.ascontiguousarray(dofs, np.int32)
+
+
+def points_program(raw, points, differences=()):
+    """The points program of ``mjmpc_points`` (row format: include/mjmpc_amd.h) for ``points`` - ``[(body index, position in
+    the body frame)]`` - and ``differences`` - ``[(a, b)]``, indices into ``points`` - on ``raw``: float64
+    ``[n_rows + len(differences)][16]`` and ``n_rows``.  A point's path holds one node per jointed body from the root to its
+    body; a body without a joint is folded into the fixed pose of the node - or the point - behind it.  One walk per point, in
+    definition order; columns 1 and 2 of its closing row are 0 (the kernel counts the points itself)."""
+    return _program(raw, [(body, [(POINT_ROW, 0, pos)]) for body, pos in points], differences)[:2]
+
+
+def motion_program(raw, outputs, differences=()):
+    """The program of ``mjmpc_points_motion`` (DESIGN 12.5; row format: include/mjmpc_amd.h) for ``outputs`` -
+    ``[(kind, body index, vector)]``, kind POINT_ROW / AXIS_ROW / VELOCITY_ROW / ANGULAR_ROW, the vector a position or an
+    axis in the body frame - and ``differences`` - ``[(a, b)]``, indices into ``outputs``: float64
+    ``[n_rows + len(differences)][16]``, ``n_rows`` and the node rows' first ``qvel`` addresses, int32 ``[n_rows]`` (0 on a
+    closing row).  All outputs on one body share one walk, placed where the first of them was defined: the path's nodes, then
+    one closing row per output with its slot - its index in ``outputs`` - in column 2 and 1 in column 1 on all but the last."""
+    bodies = list(dict.fromkeys(body for _, body, _ in outputs))
+    return _program(raw, [(body, [(kind, slot, vec) for slot, (kind, b, vec) in enumerate(outputs) if b == body])
+                          for body in bodies], differences)
+
+
+def launch_points(lib, code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, out, stream):
+    """The one launch in front of a cost entry over ``n`` observation rows, the device arrays given as
+    pointers: ``mjmpc_points`` without a dof-address table, ``mjmpc_points_motion`` - which reads the ``nv`` entries of ``qvel``
+    behind ``qpos`` too - with one.  -> the entry's return code."""
+    if dofadr is None:
+        return lib.mjmpc_points(code, n, d_obs, nq, obs, program, n_rows, n_out, n_diff, out, stream)
+    return lib.mjmpc_points_motion(code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, out, stream)
 
 
 class CostTerms:
@@ -273,7 +275,7 @@ class CostTerms:
             raise ValueError("cost terms: a table holds at most %d points, axes, velocities and angular velocities" % MAX_POINTS)
         if self._differences:
             raise ValueError("cost terms: define the points before the differences (their blocks stand in that order)")
-        points_program(raw, [(int(index), np.zeros(3))])    # (a path too long is refused here)
+        _path(raw, int(index), *_addresses(raw))            # (a path too long is refused here)
         self._points.append((name, int(index), np.array(vec, np.float64), kind))
         return self
 

@@ -293,6 +293,42 @@ def test_a_points_only_table_is_the_parents(monkeypatch):
     assert Lib.calls == ["mjmpc_points", "mjmpc_cost_terms"]
 
 
+def test_programs_are_the_recorded_ones_byte_for_byte():
+    """``points_program`` and ``motion_program`` - called directly and through ``CostTerms.points_table()`` - over every case of
+    points_cases and motion_cases against tests/golden/points_programs.npz: every program, ``n_rows`` and, for motion, ``dofadr``,
+    byte for byte and dtype for dtype.  The file was written by the two builders of commit 897adae - the last with a row loop of
+    their own each - over the same cases (keys ``points/<case>/...`` and ``motion/<case>/...``)."""
+    from mjmpc_amd.envs import cost_terms as ct
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "points_programs.npz")
+    compared = 0
+
+    def same(got, key):
+        nonlocal compared
+        want = golden[key]
+        assert got.dtype == want.dtype and got.shape == want.shape and got.tobytes() == want.tobytes(), key
+        compared += 1
+
+    with np.load(path) as golden:
+        for name in pc.case_names():
+            raw, kind, points, differences = pc.case(name)
+            table = pc.add_points(ct.CostTerms(pc.host_engine(raw, kind)), points, differences).points_table()
+            direct = ct.points_program(raw, *pc.resolved(raw, points, differences))
+            for program, n_rows in (table[:2], direct):
+                same(program, "points/%s/program" % name)
+                assert n_rows == int(golden["points/%s/n_rows" % name]) and isinstance(n_rows, int)
+            assert len(table) == 4 and len(direct) == 2
+        for name in mc.case_names():
+            raw, kind, outputs, differences = mc.case(name)
+            table = mc.add_outputs(ct.CostTerms(pc.host_engine(raw, kind)), outputs, differences).points_table()
+            direct = ct.motion_program(raw, *mc.resolved(raw, outputs, differences))
+            for program, n_rows, dofadr in (table[:2] + table[4:], direct):
+                same(program, "motion/%s/program" % name)
+                same(dofadr, "motion/%s/dofadr" % name)
+                assert n_rows == int(golden["motion/%s/n_rows" % name]) and isinstance(n_rows, int)
+            assert len(table) == 5 and len(direct) == 3
+        assert len(golden.files) == 5 * len(pc.case_names()) and compared == 6 * len(pc.case_names())
+
+
 def test_config_blocks_parse_to_the_same_table_as_the_calls():
     from mjmpc_amd.envs.cost_terms import CostTerms, cost_terms_from_config
     raw, eng, _, _, _ = _terms("tray")
