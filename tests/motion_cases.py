@@ -20,79 +20,102 @@ FD_H = 2.5e-4
 
 
 # ---------------------------------------------------------------------------------------------------------- the interpreter
-def _mats(quats):
+def _mats(quats, dtype=float):
     """Rotation matrices [N][3][3] of quaternions [N][4] (w, x, y, z), each used as q / |q|."""
-    w, x, y, z = (np.asarray(quats, float) / np.linalg.norm(quats, axis=-1, keepdims=True)).T
+    w, x, y, z = (np.asarray(quats, dtype) / np.linalg.norm(quats, axis=-1, keepdims=True)).T
     return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], -1),
                      np.stack([2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)], -1),
                      np.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], -1)], -2)
 
 
-def _turns(u, angles):
+def _turns(u, angles, dtype=float):
     """Rotation matrices [N][3][3] by ``angles`` [N] about the unit axis ``u`` (Rodrigues)."""
-    K = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]])
-    a = np.asarray(angles, float)[:, None, None]
-    return np.eye(3) + np.sin(a) * K + (1.0 - np.cos(a)) * (K @ K)
+    K = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]], dtype)
+    a = np.asarray(angles, dtype)[:, None, None]
+    return np.eye(3, dtype=dtype) + np.sin(a) * K + (1.0 - np.cos(a)) * (K @ K)
 
 
-def interpret(program, n_rows, dofadr, n_out, q, qd, wrong=None):
+def interpret(program, n_rows, dofadr, n_out, q, qd, wrong=None, dtype=float, slots_in_order=False, guards=False):
     """The augmented entries of ``(qpos, qvel)`` - one state, or ``[N][nq]`` and ``[N][nv]`` and then ``[N][.]`` -: three per
     output slot, then three per difference.  ``wrong``: one of the deliberately wrong variants the oracle comparison must catch -
     'ball_world' (a ball joint's rates read in the world frame), 'free_world' (a free joint's angular rates read in the world
     frame), 'hinge_lever' (the hinge's anchor taken to move with the origin and the origin with the anchor: its lever arm
-    dropped) and 'slide_carry' (the slide's ``w x (a d)`` dropped)."""
-    program, q, qd = np.asarray(program, float), np.asarray(q, float), np.asarray(qd, float)
+    dropped) and 'slide_carry' (the slide's ``w x (a d)`` dropped); points_cases' 'anchor' (the hinge turns about the body
+    origin) is taken too.  ``dtype``: the type every array and intermediate is held in (``np.longdouble``: 80-bit on x86).
+    ``slots_in_order``: the program as ``mjmpc_points`` reads it - a closing row's slot is the count of closing rows before it,
+    every closing row ends its walk, ``dofadr`` and ``qd`` may be None.  ``guards``: the kernel's documented ones
+    (include/mjmpc_amd.h) - every qpos index is held inside ``0 .. nq - 1`` and every dof index inside ``0 .. nv - 1``, each on
+    its own; a closing row whose slot is outside ``0 .. n_out - 1`` writes nothing; a difference's indices are held inside
+    ``0 .. n_out - 1`` (a slot no row names reads as 0 either way)."""
+    program, q = np.asarray(program, dtype), np.asarray(q, dtype)
+    qd = np.zeros(q.shape[:-1] + (6,), dtype) if qd is None else np.asarray(qd, dtype)       # (6: a free joint's dofs)
     if q.ndim == 1:
-        return interpret(program, n_rows, dofadr, n_out, q[None], qd[None], wrong)[0]
+        return interpret(program, n_rows, dofadr, n_out, q[None], qd[None], wrong, dtype, slots_in_order, guards)[0]
     N = len(q)
+    if dofadr is None:
+        dofadr = np.zeros(n_rows, np.int32)
 
     def rot(R, x):                                  # R x for every state; x [3] or [N][3]
         return np.einsum("nij,nj->ni", R, np.broadcast_to(x, (N, 3)))
 
     def rest():
-        return np.zeros((N, 3)), np.broadcast_to(np.eye(3), (N, 3, 3)).copy(), np.zeros((N, 3)), np.zeros((N, 3))
+        return (np.zeros((N, 3), dtype), np.broadcast_to(np.eye(3, dtype=dtype), (N, 3, 3)).copy(), np.zeros((N, 3), dtype),
+                np.zeros((N, 3), dtype))
 
-    out = np.zeros((N, n_out, 3))
+    def take(x, adr, n):                            # entries adr .. adr + n of every state
+        if guards:
+            return x[:, np.clip(np.arange(adr, adr + n), 0, x.shape[1] - 1)]
+        return x[:, adr:adr + n].copy()
+
+    out = np.zeros((N, n_out, 3), dtype)
     p, R, v, w = rest()
+    closed = 0
     for k, row in enumerate(program[:n_rows]):
         kind = int(row[0])
         if kind in CLOSING:
             x = rot(R, row[3:6])
-            out[:, int(row[2])] = {POINT: p + x, AXIS: x, VELOCITY: v + np.cross(w, x), ANGULAR: w}[kind]
-            if row[1] == 0:
+            slot = closed if slots_in_order else int(row[2])
+            closed += 1
+            if not guards or 0 <= slot < n_out:
+                out[:, slot] = {POINT: p + x, AXIS: x, VELOCITY: v + np.cross(w, x), ANGULAR: w}[kind]
+            if slots_in_order or row[1] == 0:
                 p, R, v, w = rest()
             continue
         adr, dof = int(row[1]), int(dofadr[k])
         if kind == FREE:
-            p, R = q[:, adr:adr + 3].copy(), _mats(q[:, adr + 3:adr + 7])
-            v = qd[:, dof:dof + 3].copy()
-            w = qd[:, dof + 3:dof + 6].copy() if wrong == "free_world" else rot(R, qd[:, dof + 3:dof + 6])
+            p, R = take(q, adr, 3), _mats(take(q, adr + 3, 4), dtype)
+            v = take(qd, dof, 3)
+            w = take(qd, dof + 3, 3) if wrong == "free_world" else rot(R, take(qd, dof + 3, 3))
             continue
         t = rot(R, row[3:6])
         p, v = p + t, v + np.cross(w, t)
-        R = R @ _mats(row[None, 6:10])
-        d = q[:, adr] - row[2]
+        R = R @ _mats(row[None, 6:10], dtype)
+        d = take(q, adr, 1)[:, 0] - row[2]
         if kind == SLIDE:
             a = rot(R, row[10:13])
-            v = v + (0.0 if wrong == "slide_carry" else np.cross(w, a * d[:, None])) + a * qd[:, dof, None]
+            v = v + (0.0 if wrong == "slide_carry" else np.cross(w, a * d[:, None])) + a * take(qd, dof, 1)
             p = p + a * d[:, None]
             continue
         assert kind in (HINGE, BALL), kind
         lever = not (wrong == "hinge_lever" and kind == HINGE)
-        r = rot(R, row[13:16])
+        local = np.zeros(3, dtype) if (wrong == "anchor" and kind == HINGE) else row[13:16]
+        r = rot(R, local)
         anchor, v_anchor = p + r, v + (np.cross(w, r) if lever else 0.0)
         if kind == HINGE:
-            R = R @ _turns(row[10:13], d)
-            w = w + rot(R, row[10:13]) * qd[:, dof, None]
+            R = R @ _turns(row[10:13], d, dtype)
+            w = w + rot(R, row[10:13]) * take(qd, dof, 1)
         else:
-            R = R @ _mats(q[:, adr:adr + 4])
-            w = w + (qd[:, dof:dof + 3] if wrong == "ball_world" else rot(R, qd[:, dof:dof + 3]))
-        r = rot(R, row[13:16])
+            R = R @ _mats(take(q, adr, 4), dtype)
+            w = w + (take(qd, dof, 3) if wrong == "ball_world" else rot(R, take(qd, dof, 3)))
+        r = rot(R, local)
         p, v = anchor - r, v_anchor - (np.cross(w, r) if lever else 0.0)
     blocks = [out[:, i] for i in range(n_out)]
     for row in program[n_rows:]:
         assert int(row[0]) == DIFFERENCE
-        blocks.append(out[:, int(row[1])] - out[:, int(row[2])])
+        a, b = int(row[1]), int(row[2])
+        if guards:
+            a, b = min(max(a, 0), n_out - 1), min(max(b, 0), n_out - 1)
+        blocks.append(out[:, a] - out[:, b])
     return np.concatenate(blocks, axis=1)
 
 

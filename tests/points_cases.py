@@ -11,49 +11,61 @@ POINT, HINGE, SLIDE, BALL, FREE, DIFFERENCE = 0, 1, 2, 3, 4, 5
 
 
 # ---------------------------------------------------------------------------------------------------------- the interpreter
-def _quat2mat(q):
-    w, x, y, z = np.asarray(q, float) / np.linalg.norm(q)
+def _quat2mat(q, dtype=float):
+    w, x, y, z = np.asarray(q, dtype) / np.linalg.norm(q)
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
                      [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]], dtype)
 
 
-def _axis_angle(u, a):
-    K = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]])
-    return np.eye(3) + np.sin(a) * K + (1.0 - np.cos(a)) * (K @ K)
+def _axis_angle(u, a, dtype=float):
+    K = np.array([[0.0, -u[2], u[1]], [u[2], 0.0, -u[0]], [-u[1], u[0], 0.0]], dtype)
+    return np.eye(3, dtype=dtype) + np.sin(a) * K + (1.0 - np.cos(a)) * (K @ K)
 
 
-def interpret(program, n_rows, q, wrong=None):
+def interpret(program, n_rows, q, wrong=None, dtype=float, guards=False, n_points=None):
     """The augmented entries of one qpos ``q``: x, y, z of every point, then of every difference.  ``wrong``: 'anchor' (the
     hinge turns about the body origin, the anchor dropped) or 'qpos0' (qpos0 not subtracted) - the two deliberately wrong
-    builds the oracle comparison must catch."""
-    program = np.asarray(program, float)
-    q = np.asarray(q, float)
-    points, p, R = [], np.zeros(3), np.eye(3)
+    builds the oracle comparison must catch.  ``dtype``: the type every array and intermediate is held in (``np.longdouble``:
+    80-bit on x86).  ``guards``: the kernel's documented ones (include/mjmpc_amd.h) - every qpos index is held inside
+    ``0 .. nq - 1`` on its own, a point behind the ``n_points``-th is written nowhere and a difference's indices are held inside
+    ``0 .. n_points - 1``."""
+    program = np.asarray(program, dtype)
+    q = np.asarray(q, dtype)
+
+    def qpos(adr, n):
+        return q[np.clip(np.arange(adr, adr + n), 0, len(q) - 1)] if guards else q[adr:adr + n]
+
+    points, p, R = [], np.zeros(3, dtype), np.eye(3, dtype=dtype)
     for row in program[:n_rows]:
         kind, adr = int(row[0]), int(row[1])
         if kind == POINT:
             points.append(p + R @ row[3:6])
-            p, R = np.zeros(3), np.eye(3)
+            p, R = np.zeros(3, dtype), np.eye(3, dtype=dtype)
             continue
         if kind == FREE:
-            p, R = q[adr:adr + 3].copy(), _quat2mat(q[adr + 3:adr + 7])
+            p, R = qpos(adr, 3).copy(), _quat2mat(qpos(adr + 3, 4), dtype)
             continue
         p = p + R @ row[3:6]
-        R = R @ _quat2mat(row[6:10])
-        d = q[adr] - (0.0 if wrong == "qpos0" else row[2])
+        R = R @ _quat2mat(row[6:10], dtype)
+        d = qpos(adr, 1)[0] - (0.0 if wrong == "qpos0" else row[2])
         if kind == SLIDE:
             p = p + (R @ row[10:13]) * d
             continue
         assert kind in (HINGE, BALL), kind
-        local = np.zeros(3) if (wrong == "anchor" and kind == HINGE) else row[13:16]
+        local = np.zeros(3, dtype) if (wrong == "anchor" and kind == HINGE) else row[13:16]
         anchor = p + R @ local
-        R = R @ (_axis_angle(row[10:13], d) if kind == HINGE else _quat2mat(q[adr:adr + 4]))
+        R = R @ (_axis_angle(row[10:13], d, dtype) if kind == HINGE else _quat2mat(qpos(adr, 4), dtype))
         p = anchor - R @ local
+    if guards:
+        points = points[:len(points) if n_points is None else n_points]
     out = list(points)
     for row in program[n_rows:]:
         assert int(row[0]) == DIFFERENCE
-        out.append(points[int(row[1])] - points[int(row[2])])
+        a, b = int(row[1]), int(row[2])
+        if guards:
+            a, b = min(max(a, 0), len(points) - 1), min(max(b, 0), len(points) - 1)
+        out.append(points[a] - points[b])
     return np.concatenate(out)
 
 
