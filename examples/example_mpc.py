@@ -23,7 +23,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from mjmpc_amd.envs.arm_engine import ArmRolloutEngine, make_device_rollout_fn, make_rollout_fn   # noqa: E402
 from mjmpc_amd.envs.cost_terms import cost_terms_from_config                                     # noqa: E402
-from mjmpc_amd.envs.locomotion_env import HalfCheetahEnv, SwimmerEnv                             # noqa: E402
+from mjmpc_amd.envs.locomotion_env import (HalfCheetahEnv, HalfCheetahStateEnv, SwimmerEnv,      # noqa: E402
+                                            half_cheetah_state_raw)
 from mjmpc_amd.envs.reacher_env import ContinualReacher7DOFEnv, HandTreeEnv, Reacher7DOFEnv      # noqa: E402
 from mjmpc_amd.envs.synthetic_env import CartPoleEnv, DoorEnv, DoublePendulumEnv, GripperEnv, TrayEnv        # noqa: E402
 from mjmpc_amd.envs.tree_engine import TreeRolloutEngine                                         # noqa: E402
@@ -41,11 +42,13 @@ ENVS = {"reacher_7dof-v0": Reacher7DOFEnv, "continual_reacher-v0": ContinualReac
         # round 4: synthetic MJCF models of the kinds the reference's other experiment files name (general kernel instantiation)
         "cartpole_friction-v0": CartPoleEnv, "tray_glass_synthetic-v0": TrayEnv, "door_latch_synthetic-v0": DoorEnv,
         "pen_gripper_synthetic-v0": GripperEnv,      # (round 5: capsule / box and cylinder / plane contacts, joint ref / margin)
-        "double_pendulum_rk4-v0": DoublePendulumEnv}     # (a model that asks for MuJoCo's RK4 integrator)
+        "double_pendulum_rk4-v0": DoublePendulumEnv,     # (a model that asks for MuJoCo's RK4 integrator)
+        # HalfCheetah observing all of qpos: what cost terms on world points and centres of mass need
+        "HalfCheetah_state-v0": HalfCheetahStateEnv}
 TREE_MODELS = {"hand_tree-v0": hand24_raw, "Swimmer-v0": swimmer_raw, "HalfCheetah-v0": half_cheetah_raw,
                "cartpole_friction-v0": lambda: synthetic_raw("cartpole"), "tray_glass_synthetic-v0": lambda: synthetic_raw("tray"),
                "door_latch_synthetic-v0": lambda: synthetic_raw("door"), "pen_gripper_synthetic-v0": lambda: synthetic_raw("gripper"),
-               "double_pendulum_rk4-v0": lambda: synthetic_raw("double_pendulum")}
+               "double_pendulum_rk4-v0": lambda: synthetic_raw("double_pendulum"), "HalfCheetah_state-v0": half_cheetah_state_raw}
 
 
 def make_sim(env_name, dtype, num_shards):
@@ -147,7 +150,7 @@ def main():
             ep_rewards[i] += reward
         trajectories.append(dict(observations=np.array(observations), actions=np.array(actions),
                                  rewards=np.array(rewards), env_infos=dict(goal_achieved=np.array(infos))))
-        if exp["env_name"] in ("Swimmer-v0", "HalfCheetah-v0"):
+        if exp["env_name"] in ("Swimmer-v0", "HalfCheetah-v0", "HalfCheetah_state-v0"):
             print("episode %d: reward %.3f, forward progress %.3f m" % (i, ep_rewards[i], env.get_env_state()["qpos"][0]))
         else:
             print("episode %d: reward %.3f, final distance to target %.4f (closest %.4f)"

@@ -152,7 +152,7 @@ def main():
 
     rewards = -costs.astype(np.float64).sum(axis=0)
     for i in range(E):
-        if exp["env_name"] in ("Swimmer-v0", "HalfCheetah-v0"):
+        if exp["env_name"] in ("Swimmer-v0", "HalfCheetah-v0", "HalfCheetah_state-v0"):
             print("episode %d: reward %.3f, forward progress %.3f m" % (i, rewards[i], final[i]["qpos"][0]))
         else:
             print("episode %d: reward %.3f, final distance to target %.4f"

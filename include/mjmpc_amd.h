@@ -38,7 +38,7 @@ extern "C" {
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
  *      the DMD-MPC episode batches', mjmpc_cost_terms, mjmpc_cost_terms_track / _track_batch, mjmpc_cost_terms_rate /
- *      _rate_batch, mjmpc_cost_terms_quad / _quad_batch, mjmpc_points and mjmpc_points_motion.) */
+ *      _rate_batch, mjmpc_cost_terms_quad / _quad_batch, mjmpc_points, mjmpc_points_motion and mjmpc_points_tree.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -984,6 +984,32 @@ int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void* d_obs_rows
  * rows, all described above. */
 int mjmpc_points_motion(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
                         const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, void* d_out, void* stream);
+
+/* The centre of mass of a subtree of bodies and its velocity beside the points, axes and velocities:
+ * mjmpc_points_motion - every row kind above with the same meaning, the same d_dofadr, slots and guards - with two
+ * accumulators S and Sv beside the walk, n_levels saved frames (0 .. 4) and the row kinds
+ *   9 MASS          {9, 0, 0, cx, cy, cz, share}   on the current frame: S += share (p + R c), Sv += share (v + w x (R c)), with
+ *                                                  c the centre of mass of the node's rigid group in the node's frame and share
+ *                                                  its mass over the subtree's (the host divides, the kernel never does).  The
+ *                                                  frame is kept
+ *   10 SAVE         {10, level}                    the frame, v and w are stored at `level`
+ *   11 RESTORE      {11, level}                    they are loaded from `level`; level -1 is the world frame at rest
+ *   12 COM          {12, keep, slot}               a closing row (keep and slot as above) that writes S to `slot`
+ *   13 COM_VELOCITY {13, keep, slot}               a closing row that writes Sv to `slot`
+ * S and Sv are zero at the program's start and are zeroed again whenever a closing row with keep = 0 resets the frame.  A
+ * centre of mass is one walk of its own: the nodes of the path from the root to the subtree's root body, then the subtree in
+ * depth-first order - every rigid group its node row and its MASS row, a SAVE in front of the first child of a node with
+ * several children in the walk, a RESTORE in front of each further child (a level is free again once its last child has
+ * begun; several root bodies restore to level -1) - then COM and, on the same walk, COM_VELOCITY.  So every jointed body of the
+ * subtree is visited once.
+ *   guards     every level holds the world frame at rest until a SAVE names it, so a RESTORE of a level never saved gives that; a
+ *              SAVE with a level outside 0 .. n_levels - 1 writes nothing and a RESTORE with one gives the world frame at rest;
+ *              slots, qpos and dof addresses are held as in mjmpc_points_motion.
+ * The saved frames stand in the tile beside a row's outputs: 104 n_levels more bytes a row.  MJMPC_E_BADARG before anything is
+ * launched: what mjmpc_points_motion refuses, n_levels outside 0 .. 4, an observation row that does not fit the tile with its
+ * outputs and saved frames. */
+int mjmpc_points_tree(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
+                      const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* d_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -169,6 +169,7 @@ SIGNATURES = {
                                            _int, _int, _int, _vp, _i64, _vp, _int, _vp, _int, _vp, _vp, _vp, _vp]),
     "mjmpc_points": (_int, [_int, _i64, _int, _int, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "mjmpc_points_motion": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
+    "mjmpc_points_tree": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
 }
 
 _LIB = None

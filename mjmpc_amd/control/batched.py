@@ -52,7 +52,7 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from ..envs.cost_terms import launch_points
+from ..envs.cost_terms import launch_points, refuse_mass_randomization
 from ._device import noise_factor
 from .controller import _SHIFT_MODES, _seed_value
 
@@ -94,6 +94,9 @@ class _EpisodeBatch:
     _prev_actions = None    # ... with rate rows every episode's last applied action, float64 [E][A] on the device (NaN: none yet)
     _quad = None            # the tables hold quadratic groups or signed linear rows: mjmpc_cost_terms_quad_batch with
                             # this pool of matrices on the device, one for all episodes
+    _cost_terms_set = None  # set_cost_terms' argument, _mass_randomized: randomize_dynamics drew body_mass (DESIGN 12.6 refuses a
+    _mass_randomized = None  # centre of mass beside it)
+    _points_levels = None   # ... the saved frames of its program: a centre of mass, mjmpc_points_tree
     _points = None          # the tables name points: (program, n_rows, n_points, n_diff, d_obs + n_extra, the augmented
                             # observations of the rollouts [E P][H][.] and of the real-env steps [E][.], the node rows' qvel
                             # addresses - None without axes and velocities)
@@ -308,6 +311,7 @@ class _EpisodeBatch:
             raise ValueError("num_particles (%d) must divide into num_shards (%d) shards, 1 .. 65535" % (self.num_particles, K))
         if self.raw is None:
             raise ValueError("randomize_dynamics needs the batch to be built from a RawModel")
+        refuse_mass_randomization(self._cost_terms_set, param_dict)      # (no centre of mass over randomized masses)
         per_episode = isinstance(base_seed, (list, tuple, np.ndarray))
         if per_episode and len(base_seed) != E:
             raise ValueError("base_seed takes one int or one per episode (%d), got %d" % (E, len(base_seed)))
@@ -324,6 +328,7 @@ class _EpisodeBatch:
         blobs = np.ascontiguousarray(np.stack(blobs), np.float64)
         _lib.check(self.lib.mjmpc_tree_set_batch_models(self.engine._h, blobs.ctypes.data_as(_lib._dp), len(blobs), K))
         self.shard_blobs = blobs
+        self._mass_randomized = {"body_mass": param_dict["body_mass"]} if "body_mass" in param_dict else None
         return (defaults, rand) if per_episode else (defaults[0], rand[0])
 
     def clear_dynamics(self):
@@ -331,6 +336,7 @@ class _EpisodeBatch:
         self._tree_only("clear_dynamics")
         _lib.check(self.lib.mjmpc_tree_set_batch_models(self.engine._h, None, 0, 0))
         self.shard_blobs = None
+        self._mass_randomized = None
 
     # ------------------------------------------------------------------ user-defined cost terms
     def obs_layout(self):
@@ -419,14 +425,17 @@ class _EpisodeBatch:
         (``ValueError`` naming the episode).  Tables with points or differences put ``mjmpc_points`` over the
         ``E P H`` rows between the rollout and the cost entry, as the single engines do; the episodes share the points and
         differences (``ValueError`` naming the episode) and keep their own weights, targets and references; with axes,
-        velocities or angular velocities the launch is ``mjmpc_points_motion``, shared in the same way.  Everything is
+        velocities or angular velocities the launch is ``mjmpc_points_motion``, shared in the same way, with a centre
+        of mass ``mjmpc_points_tree`` - refused beside a ``randomize_dynamics`` of ``body_mass``.  Everything is
         checked on the host first (``ValueError``); callable between steps."""
         if terms is None:
             self._terms = self._terms_nobs = self._terms_env = self._track = self._prev_actions = self._quad = None
-            self._points = None
+            self._points = self._cost_terms_set = self._points_levels = None
             self._rate = False
             return
         tables, keep, reads_actions = self._resolve_cost_terms(terms, self.engine, self.num_episodes)
+        refuse_mass_randomization(terms, self._mass_randomized)         # (DESIGN 12.6)
+        self._cost_terms_set = terms
         track = self._resolve_tracking(terms, self.engine, self.num_episodes)
         rate_rows = bool(np.any(tables[0][:, 1] == 2))
         kinds = tables[0][:, 0]
@@ -446,7 +455,7 @@ class _EpisodeBatch:
                            torch.empty((E, self.d_action), dtype=tdt, device=dev) if reads_actions else None)
         self._prev_actions = (torch.full((E, self.d_action), float("nan"), dtype=torch.float64, device=dev) if rate_rows
                               else None)
-        self._points = None
+        self._points = self._points_levels = None
         first = terms[0] if isinstance(terms, (list, tuple)) else terms
         points = first.points_table(self.engine)
         if points is not None:
@@ -457,6 +466,8 @@ class _EpisodeBatch:
                 torch.empty((E, d_aug), dtype=tdt, device=dev),
                 #  with axes or velocities the node rows' qvel addresses: mjmpc_points_motion
                 torch.from_numpy(points[4]).to(dev) if len(points) > 4 else None)
+            #  with a centre of mass the saved frames of the program: mjmpc_points_tree
+            self._points_levels = points[5] if len(points) > 5 else None
 
     def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s, bias=0, advance_prev=0):
         """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s); with tracked terms
@@ -469,7 +480,7 @@ class _EpisodeBatch:
             program, n_rows, n_points, n_diff, d_aug, aug_rollout, aug_env, dofadr = self._points
             aug = aug_rollout if nobs is self._terms_nobs else aug_env
             _lib.check(launch_points(self.lib, self._code, self.num_episodes * P * H, d_obs, self.engine._nq, self.model.nv,
-                                     _vp(nobs), _vp(program), _vp(dofadr), n_rows, n_points, n_diff, _vp(aug), s))
+                                     _vp(nobs), _vp(program), _vp(dofadr), n_rows, n_points, n_diff, _vp(aug), s, self._points_levels))
             nobs, d_obs = aug, d_aug
         if self._quad is not None:
             refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)

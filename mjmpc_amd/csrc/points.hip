@@ -21,6 +21,14 @@
 // every point closes its walk and nothing is cleared.  The kind branch is uniform, the dof addresses are wave-uniform reads
 // like the rows.  Registers, LDS, scratch of the four instantiations: profiles/r27_points_one_walk.txt.
 //
+// The TREE part (mjmpc_points_tree) adds the centre of mass of a subtree and its velocity: a MASS row adds the
+// current frame's group, weighted by its share of the subtree's mass, to two accumulators S and Sv (6 more doubles), SAVE and
+// RESTORE rows put the frame with v and w away at a branch point and fetch it for the next child, so every body of the subtree
+// is visited once, and the closing rows COM and COM_VELOCITY write S and Sv.  The saved frames live in LDS behind the parked
+// outputs as doubles [level][component][lane] - 13 components, lane-consecutive like the outputs, 104 n_levels bytes a row -:
+// a level is a run-time value, and a per-lane array indexed by one would go to scratch.  Every lane first writes the world
+// frame at rest to its levels, so a RESTORE of a level never saved is defined.  Resources: profiles/r29_com_resources.txt.
+//
 // Shape (cost_terms.hip's): a workgroup takes `rows` consecutive observation rows - they lie back to back in memory -, copies
 // them into LDS with unit-stride loads (odd row pitch: the lanes' column reads spread over the banks), lane j walks the program
 // over row j and parks its outputs in LDS as doubles, laid out [entry][lane] (lane-consecutive, no bank conflict); then all
@@ -45,6 +53,8 @@ constexpr int PT_ROW = 16;                  // doubles of a program row
 constexpr int PT_MAX_POINTS = 16, PT_MAX_DIFF = 16, PT_MAX_NODES = 33;
 constexpr int PT_MAX_ROWS = PT_MAX_POINTS * (PT_MAX_NODES + 1);
 constexpr int PT_LDS_BYTES = 60 * 1024;     // the tile's share of a workgroup's 64 KiB
+constexpr int PT_MAX_LEVELS = 4;            // saved frames of a TREE program
+constexpr int PT_LEVEL = 13;                // doubles of a saved frame: p, q, v, w
 
 __host__ __device__ inline int pt_pitch(int n) { return n | 1; }
 
@@ -102,9 +112,13 @@ __device__ __forceinline__ void pt_output(int kind, const PtFrame& f, const doub
 
 // The walk over one row `my`: the frame and, with MOTION, its origin's velocity v and its angular velocity w; the outputs go
 // to pts[(3 slot + c) * rows] (pts: this lane's column of the parked entries).  nv and dofadr are read with MOTION alone.
-template <typename T, bool MOTION>
+// TREE (with MOTION): the accumulators S and Sv of the MASS rows and the saved frames lv[(PT_LEVEL level + c) * rows] (lv:
+// this lane's column of them), n_levels of them.
+template <typename T, bool MOTION, bool TREE>
 __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ prog, const int32_t* __restrict__ dofadr,
-                                        int n_rows, int n_out, int nq, int nv, double* pts, int rows) {
+                                        int n_rows, int n_out, int nq, int nv, double* pts, int rows,
+                                        [[maybe_unused]] double* lv, [[maybe_unused]] int n_levels) {
+    static_assert(MOTION || !TREE, "the tree walk carries v and w");
     // entry i of my qpos / qvel, held inside it whatever the tables say
     auto qpos = [&](int i) { return (double)my[i < 0 ? 0 : i < nq ? i : nq - 1]; };
     [[maybe_unused]] auto qvel = [&](int i) { return (double)my[nq + (i < 0 ? 0 : i < nv ? i : nv - 1)]; };
@@ -112,15 +126,57 @@ __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ 
         for (int e = 0; e < 3 * n_out; ++e) pts[e * rows] = 0.0;
     PtFrame f{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
     [[maybe_unused]] double v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
+    [[maybe_unused]] double S[3] = {0.0, 0.0, 0.0}, Sv[3] = {0.0, 0.0, 0.0};
+    if constexpr (TREE) {                   // every level holds the world frame at rest until a SAVE says otherwise
+        for (int l = 0; l < n_levels; ++l)
+            for (int e = 0; e < PT_LEVEL; ++e) lv[(PT_LEVEL * l + e) * rows] = e == 3 ? 1.0 : 0.0;
+    }
     int point = 0;                          // the closing rows so far: without MOTION a row's slot
     for (int k = 0; k < n_rows; ++k) {
         const double* __restrict__ row = prog + (long)PT_ROW * k;
         const int kind = (int)row[0];
         double t[3];
         [[maybe_unused]] double c[3];
-        if (kind == 0 || (MOTION && kind >= 6)) {       // a closing row: its output into its slot; the frame kept or reset
+        if constexpr (TREE) {
+            if (kind == 9) {                // MASS: the group's centre c and its share of the subtree's mass; the frame is kept
+                const double share = row[6];
+                pt_rotate(f.q, row[3], row[4], row[5], t);
+                pt_cross(w, t, c);
+                S[0] += share * (f.p[0] + t[0]); S[1] += share * (f.p[1] + t[1]); S[2] += share * (f.p[2] + t[2]);
+                Sv[0] += share * (v[0] + c[0]); Sv[1] += share * (v[1] + c[1]); Sv[2] += share * (v[2] + c[2]);
+                continue;
+            }
+            if (kind == 10 || kind == 11) { // SAVE, RESTORE: the frame, v and w to and from a level; -1: the world frame at rest
+                const int level = (int)row[1];
+                const bool held = level >= 0 && level < n_levels;
+                double* const at = lv + (long)PT_LEVEL * (held ? level : 0) * rows;
+                if (kind == 10) {
+                    if (held) {
+                        for (int e = 0; e < 3; ++e) at[e * rows] = f.p[e];
+                        for (int e = 0; e < 4; ++e) at[(3 + e) * rows] = f.q[e];
+                        for (int e = 0; e < 3; ++e) at[(7 + e) * rows] = v[e];
+                        for (int e = 0; e < 3; ++e) at[(10 + e) * rows] = w[e];
+                    }
+                } else if (held) {
+                    for (int e = 0; e < 3; ++e) f.p[e] = at[e * rows];
+                    for (int e = 0; e < 4; ++e) f.q[e] = at[(3 + e) * rows];
+                    for (int e = 0; e < 3; ++e) v[e] = at[(7 + e) * rows];
+                    for (int e = 0; e < 3; ++e) w[e] = at[(10 + e) * rows];
+                } else {
+                    f = PtFrame{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
+                    v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = 0.0;
+                }
+                continue;
+            }
+        }
+        // a closing row: its output into its slot; the frame kept or reset
+        if (kind == 0 || (MOTION && !TREE && kind >= 6) || (TREE && ((kind >= 6 && kind <= 8) || kind >= 12))) {
             double o[3];
-            pt_output<MOTION>(kind, f, v, w, row, o);
+            if (TREE && kind >= 12) {       // COM, COM_VELOCITY: the accumulators
+                for (int e = 0; e < 3; ++e) o[e] = kind == 12 ? S[e] : Sv[e];
+            } else {
+                pt_output<MOTION>(kind, f, v, w, row, o);
+            }
             const int slot = MOTION ? (int)row[2] : point;
             if (slot >= 0 && slot < n_out) {
                 pts[(3 * slot + 0) * rows] = o[0];
@@ -131,6 +187,7 @@ __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ 
             if (!MOTION || row[1] == 0.0) {             // the next walk starts at the world frame, at rest
                 f = PtFrame{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
                 if constexpr (MOTION) v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = 0.0;
+                if constexpr (TREE) S[0] = S[1] = S[2] = Sv[0] = Sv[1] = Sv[2] = 0.0;
             }
             continue;
         }
@@ -204,10 +261,12 @@ __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ 
 
 // grid: ceil(n / rows) workgroups of max(rows, 64) threads; dynamic LDS: rows x pitch(d_obs) words of T, then 3 n_points x rows doubles
 // MOTION: n_points counts the output slots; nv and dofadr are read by that instantiation alone
-template <typename T, bool MOTION>
+// TREE: behind the parked outputs PT_LEVEL n_levels x rows doubles, the saved frames; n_levels is read by that instantiation alone
+template <typename T, bool MOTION, bool TREE>
 __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs, const double* __restrict__ prog, int n_rows,
                                                        int n_points, int n_diff, long n, int d_obs, int nq, int rows,
-                                                       T* __restrict__ out, int nv, const int32_t* __restrict__ dofadr) {
+                                                       T* __restrict__ out, int nv, const int32_t* __restrict__ dofadr,
+                                                       int n_levels) {
     extern __shared__ double pt_tile_raw[];
     __shared__ int s_da[PT_MAX_DIFF], s_db[PT_MAX_DIFF];
     const int po = pt_pitch(d_obs);
@@ -237,7 +296,9 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
     }
     __syncthreads();
 
-    if (j < mine) pt_walk<T, MOTION>(tile + j * po, prog, dofadr, n_rows, n_points, nq, nv, pts + j, rows);
+    if (j < mine)
+        pt_walk<T, MOTION, TREE>(tile + j * po, prog, dofadr, n_rows, n_points, nq, nv, pts + j, rows,
+                                 pts + (long)3 * n_points * rows + j, n_levels);
     __syncthreads();
 
     {                                       // the augmented tile: unit stride over the lanes
@@ -264,11 +325,13 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
     }
 }
 
-// Both entries: the checks, the tile - the largest power of two of rows up to PT_WG whose rows and parked outputs fit
-// PT_LDS_BYTES - and the launch.  `motion`: mjmpc_points_motion, which alone reads (and checks) nv and dofadr and calls its
-// outputs n_out where mjmpc_points says n_points.
-int launch_points(const char* entry, bool motion, int dtype, int64_t N, int d_obs, int nq, int nv, const void* obs,
-                  const double* prog, const int32_t* dofadr, int n_rows, int n_out, int n_diff, void* out, void* stream) {
+// The three entries: the checks, the tile - the largest power of two of rows up to PT_WG whose rows, parked outputs and saved
+// frames fit PT_LDS_BYTES - and the launch.  `motion`: mjmpc_points_motion and mjmpc_points_tree, which alone read (and check)
+// nv and dofadr and call their outputs n_out where mjmpc_points says n_points; `tree`: mjmpc_points_tree, which alone reads
+// (and checks) n_levels.
+int launch_points(const char* entry, bool motion, bool tree, int dtype, int64_t N, int d_obs, int nq, int nv, const void* obs,
+                  const double* prog, const int32_t* dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* out,
+                  void* stream) {
     auto bad = [&](const char* detail) { return set_error(MJMPC_E_BADARG, entry, detail); };
     if (!obs || !prog || !out) return bad("null pointer");
     if (motion && !dofadr) return bad("null d_dofadr: the node rows' qvel addresses");
@@ -281,11 +344,13 @@ int launch_points(const char* entry, bool motion, int dtype, int64_t N, int d_ob
     if (n_rows < n_out || n_rows > PT_MAX_ROWS)
         return bad(motion ? "n_rows must be in n_out .. 544 (16 paths of 33 nodes and an output)"
                           : "n_rows must be in n_points .. 544 (16 paths of 33 nodes and a point)");
+    if (tree && (n_levels < 0 || n_levels > PT_MAX_LEVELS)) return bad("n_levels must be in 0 .. 4");
     const long word = dtype == MJMPC_F32 ? 4 : 8;
-    const long pts_bytes = 8L * 3 * n_out;                          // a row's parked outputs
+    const long pts_bytes = 8L * 3 * n_out + (tree ? 8L * PT_LEVEL * n_levels : 0);     // a row's parked outputs and saved frames
     if ((long)d_obs > (PT_LDS_BYTES - pts_bytes - 8) / word - 1)
-        return bad(motion ? "an observation row and its outputs of more than 60 KiB"
-                          : "an observation row and its points of more than 60 KiB");
+        return bad(tree ? "an observation row, its outputs and its saved frames of more than 60 KiB"
+                   : motion ? "an observation row and its outputs of more than 60 KiB"
+                            : "an observation row and its points of more than 60 KiB");
     auto lds = [&](int r) { return (r * word * pt_pitch(d_obs) + 7) / 8 * 8 + r * pts_bytes; };
     int rows = PT_WG;
     while (lds(rows) > PT_LDS_BYTES) rows >>= 1;
@@ -293,9 +358,10 @@ int launch_points(const char* entry, bool motion, int dtype, int64_t N, int d_ob
     if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
     auto launch = [&](auto zero) {
         using T = decltype(zero);
-        auto* const kernel = motion ? points_kernel<T, true> : points_kernel<T, false>;
+        auto* const kernel = tree ? points_kernel<T, true, true> : motion ? points_kernel<T, true, false>
+                                                                          : points_kernel<T, false, false>;
         hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), (size_t)lds(rows), (hipStream_t)stream,
-                           (const T*)obs, prog, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (T*)out, nv, dofadr);
+                           (const T*)obs, prog, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (T*)out, nv, dofadr, n_levels);
     };
     if (dtype == MJMPC_F32) launch(0.0f);
     else launch(0.0);
@@ -308,12 +374,19 @@ int launch_points(const char* entry, bool motion, int dtype, int64_t N, int d_ob
 
 extern "C" int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void* d_obs_rows, const double* d_program, int n_rows,
                             int n_points, int n_diff, void* d_out, void* stream) {
-    return mjmpc::launch_points("mjmpc_points", false, dtype, N, d_obs, nq, 0, d_obs_rows, d_program, nullptr, n_rows, n_points,
-                                n_diff, d_out, stream);
+    return mjmpc::launch_points("mjmpc_points", false, false, dtype, N, d_obs, nq, 0, d_obs_rows, d_program, nullptr, n_rows,
+                                n_points, n_diff, 0, d_out, stream);
 }
 
 extern "C" int mjmpc_points_motion(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
                                    const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, void* d_out, void* stream) {
-    return mjmpc::launch_points("mjmpc_points_motion", true, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr, n_rows,
-                                n_out, n_diff, d_out, stream);
+    return mjmpc::launch_points("mjmpc_points_motion", true, false, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr,
+                                n_rows, n_out, n_diff, 0, d_out, stream);
+}
+
+extern "C" int mjmpc_points_tree(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
+                                 const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* d_out,
+                                 void* stream) {
+    return mjmpc::launch_points("mjmpc_points_tree", true, true, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr,
+                                n_rows, n_out, n_diff, n_levels, d_out, stream);
 }

@@ -18,7 +18,7 @@ from .. import _lib
 from ..models.compile import principal_inertia, require_f32_power_ratio
 from ..models.raw import TASK_FORWARD, RawModel
 from ._resets import EnvResetWatch, SimulationUnstableError  # noqa: F401
-from .cost_terms import launch_points
+from .cost_terms import launch_points, refuse_mass_randomization
 from .seeding import np_random
 
 _DT = {"f32": (_lib.F32, np.float32), "f64": (_lib.F64, np.float64)}
@@ -80,6 +80,8 @@ class RolloutEngine(EnvResetWatch):
                                     # with this pool of matrices, float64 on the device (one zero without a group)
     _points = None                  # the table names points: (program on the device, n_rows, n_points, n_diff, n_extra,
                                     # the node rows' qvel addresses on the device - None without axes and velocities)
+    _points_levels = None           # ... the saved frames of its program: a centre of mass, mjmpc_points_tree
+    _mass_randomized = None         # randomize_dynamics drew body_mass: its param_dict (DESIGN 12.6 refuses a centre of mass then)
     _points_last = None             # ... the augmented observations of the last cost launch (cost_observations)
     _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
 
@@ -209,10 +211,13 @@ class RolloutEngine(EnvResetWatch):
         Returns (default_params, randomized_params), one dict per shard."""
         if self.raw is None:
             raise ValueError("randomize_dynamics needs the engine to be built from a RawModel")
+        refuse_mass_randomization(self._cost_terms, param_dict)     # (DESIGN 12.6: no centre of mass over randomized masses)
         seeds = [int(base_seed) + i * 12345 for i in range(self.num_shards)]
         blobs = draw_shard_models(self, param_dict, seeds, self.default_dyn_params, self.randomized_dyn_params)
         _lib.check(self._fn("set_shard_models")(self._h, blobs.ctypes.data_as(_lib._dp), self.num_shards))
         self.shard_blobs = blobs
+        if "body_mass" in param_dict:
+            self._mass_randomized = {"body_mass": param_dict["body_mass"]}
         return self.default_dyn_params, self.randomized_dyn_params
 
     @classmethod
@@ -371,7 +376,9 @@ class RolloutEngine(EnvResetWatch):
         that buffer with ``d_obs + n_extra`` entries a row (``cost_observations()`` returns it).  The observations a rollout
         returns keep their width; the counter, the previous action, ``terminal`` and the guard behave as without points; a table
         without points launches nothing new.  With an axis, a velocity or an angular velocity (``CostTerms.axis`` / ``velocity`` /
-        ``angular_velocity``) that launch is ``mjmpc_points_motion``, which reads the row's ``qvel`` too; everything
+        ``angular_velocity``) that launch is ``mjmpc_points_motion``, which reads the row's ``qvel`` too; with a centre
+        of mass (``CostTerms.com`` / ``com_velocity``) it is ``mjmpc_points_tree``, and the table is refused
+        (``ValueError``) once ``randomize_dynamics`` has drawn ``body_mass``, as that call is refused after this one; everything
         else is as with points."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
@@ -379,21 +386,24 @@ class RolloutEngine(EnvResetWatch):
                                % (("with", "no fused launches") if self._closure_terms else ("without", "the fused launches")))
         if terms is None:
             self._cost_terms = self._terms_dev = self._track_ref = self._track_step = self._prev_action = None
-            self._terms_quad = self._points = self._points_last = None
+            self._terms_quad = self._points = self._points_last = self._points_levels = None
             self._terms_read_actions = self._terms_rate = False
             return
         table = np.ascontiguousarray(terms.table(self), np.float64)       # (ValueError before anything reaches the device)
+        refuse_mass_randomization(terms, self._mass_randomized)           # 
         ref = terms.reference_table(self)
         pool = terms.quad_table(self)
         points = terms.points_table(self)
         torch = _torch()
-        self._points = self._points_last = None
+        self._points = self._points_last = self._points_levels = None
         if points is not None:
             # (every cost launch is preceded by mjmpc_points into a buffer of the engine's)
             # (with an axis or a velocity the table has a fifth entry, the node rows' qvel addresses, and the
             # launch is mjmpc_points_motion)
             dofadr = torch.from_numpy(points[4]).to(self.device) if len(points) > 4 else None
+            # (with a centre of mass a sixth, the saved frames of the program, and the launch is mjmpc_points_tree)
             self._points = (torch.from_numpy(points[0]).to(self.device),) + tuple(points[1:4]) + (int(terms.n_extra), dofadr)
+            self._points_levels = points[5] if len(points) > 5 else None
         self._terms_dev = torch.from_numpy(table).to(self.device)
         self._terms_rate = bool(terms.needs_rate_entry)
         self._terms_quad = None
@@ -469,7 +479,7 @@ class RolloutEngine(EnvResetWatch):
                                (self.d_obs + n_extra,) if nobs.dim() == 1 else (P, H, self.d_obs + n_extra))
             #  with axes or velocities - a dof-address table - the launch reads qvel, the nv entries behind qpos, too
             _lib.check(launch_points(self._lib, self._code, P * H, self.d_obs, self._nq, self.model.nv, _ptr(nobs), _ptr(program),
-                                     _ptr(dofadr), n_rows, n_points, n_diff, _ptr(aug), self._stream()))
+                                     _ptr(dofadr), n_rows, n_points, n_diff, _ptr(aug), self._stream(), self._points_levels))
             self._points_last = nobs = aug
             d_obs += n_extra
         t = self._terms_dev

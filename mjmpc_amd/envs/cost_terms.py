@@ -80,6 +80,20 @@ differences behind them - and ``difference`` takes two of one kind.  A table wit
     terms.velocity("tray_vel", "tray")
     terms.difference("slip", "glass_vel", "tray_vel")
     terms.norm(obs="slip", weight=0.5)                                      # the glass at rest relative to the tray
+
+Centres of mass.  ``com`` gives the world position of the centre of mass of a body and all its descendants
+(``body=None``: of the whole model) and ``com_velocity`` its world velocity - the subtree's linear momentum over its mass -,
+with the masses and inertial positions the engine's model compiler computes for the nominal model.  They are outputs like a
+point and a velocity - in definition order, counted among the 16 - and ``difference`` takes a centre of mass with a centre of
+mass or a point, its velocity with another or with a ``velocity``.  A table with either launches ``mjmpc_points_tree`` for its
+whole program: one walk per centre of mass that visits every jointed body of the subtree once, saving the frame at a branch
+point (at most 4 frames saved at a time).  Such a table cannot be combined with ``randomize_dynamics`` of ``body_mass``: every
+shard would have a centre of mass of its own.
+
+    terms.com("body_com")                                                   # the whole model
+    terms.com_velocity("body_vel", "body_com")
+    terms.linear(obs="body_vel", index=0, weight=-1.0)                      # forward progress of the centre of mass
+    terms.outside(obs="body_com", index=2, low=-0.15, high=0.25, weight=5.0)
 """
 import numpy as np
 
@@ -115,6 +129,10 @@ MAX_PATH_NODES = 33             # jointed bodies on a point's path (welded ones 
 POINT_ROW_LEN = 16
 POINT_ROW, DIFFERENCE_ROW = 0, 5
 AXIS_ROW, VELOCITY_ROW, ANGULAR_ROW = 6, 7, 8      # the further closing rows of mjmpc_points_motion
+MASS_ROW, SAVE_ROW, RESTORE_ROW, COM_ROW, COM_VELOCITY_ROW = 9, 10, 11, 12, 13     # mjmpc_points_tree's
+MAX_LEVELS = 4                  # frames a tree program may have saved at a time
+MAX_PROGRAM_ROWS = 544
+_POSITIONS, _VELOCITIES = (POINT_ROW, COM_ROW), (VELOCITY_ROW, COM_VELOCITY_ROW)  # what a difference may mix
 _JOINT_KINDS = {JOINT_HINGE: 1, JOINT_SLIDE: 2, JOINT_BALL: 3, JOINT_FREE: 4}
 
 
@@ -177,8 +195,9 @@ def _program(raw, walks, differences):
     and the node rows' first ``qvel`` addresses, int32 ``[n_rows]`` (0 on a closing row)."""
     qadr, dadr = _addresses(raw)
     rows, dofs = [], []
-    for body, outputs in walks:
-        nodes, node_dofs, at, turn = _path(raw, body, qadr, dadr)
+    for body, outputs, *tree in walks:
+        # (a centre of mass, DESIGN 12.6, brings the rows of its walk; its closing rows take no vector)
+        nodes, node_dofs, at, turn = tree[0] + (None, None) if tree else _path(raw, body, qadr, dadr)
         rows.extend(nodes)
         dofs.extend(node_dofs)
         for k, (kind, slot, vec) in enumerate(outputs):
@@ -219,13 +238,143 @@ def motion_program(raw, outputs, differences=()):
                           for body in bodies], differences)
 
 
-def launch_points(lib, code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, out, stream):
-    """The one launch in front of a cost entry (DESIGN 12.4 / 12.5) over ``n`` observation rows, the device arrays given as
+def inertials(engine):
+    """``(mass [nb], ipos [nb][3])`` per raw body as the engine's own model compiler computes them for the nominal model:
+    ``model.body_mass`` and ``model.body_ipos`` (models/compile.py) or ``body_inertials`` (models/compile_tree.py)."""
+    ipos = getattr(engine.model, "body_ipos", None)
+    if ipos is None:
+        from ..models.compile_tree import body_inertials
+        ipos = body_inertials(engine.raw)[3]
+    return np.asarray(engine.model.body_mass, np.float64), np.asarray(ipos, np.float64).reshape(-1, 3)
+
+
+def com_walk(raw, body, mass, ipos):
+    """The rows of one centre-of-mass walk (row format: include/mjmpc_amd.h) without its closing rows, for the
+    subtree of ``body`` (-1: every body) with the bodies' ``mass`` and ``ipos``: ``(rows, dofs, n_levels)``.  First the nodes of
+    the path from the root to the subtree's root, then the subtree in depth-first order: a body without a joint is folded into
+    the jointed body it is welded to, every such rigid group has its node row and, unless it is massless, its MASS row - its
+    centre of mass in the node's frame and its share ``m / M`` of the subtree's mass -, a SAVE stands in front of the first
+    child of a node with several children, a RESTORE in front of each further one, and a level is free again once its last
+    child has begun.  Several root bodies restore to level -1, the world frame."""
+    qadr, dadr = _addresses(raw)
+    nb = len(raw.bodies)
+    inside = [i == body or body < 0 for i in range(nb)]
+    for i, b in enumerate(raw.bodies):              # (parents first)
+        inside[i] = inside[i] or (b.parent >= 0 and inside[b.parent])
+    total = float(sum(mass[i] for i in range(nb) if inside[i]))
+    if not total > 0.0 or not np.isfinite(total):
+        raise ValueError("cost terms: the bodies of this centre of mass weigh %r together" % total)
+
+    def node_of(i):                                 # the jointed body whose frame carries body i; -1: the world
+        while i >= 0 and raw.bodies[i].joint is None:
+            i = raw.bodies[i].parent
+        return i
+
+    moment, weight, kids = {}, {}, {}               # per node: sum m c in its frame, sum m; its jointed children in the walk
+    for i in range(nb):
+        if not inside[i]:
+            continue
+        n = node_of(i)
+        if raw.bodies[i].joint is not None:
+            kids.setdefault(node_of(raw.bodies[i].parent), []).append(i)
+            at, turn = np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])
+        else:
+            at, turn = _path(raw, i, qadr, dadr)[2:]
+        moment[n] = moment.get(n, 0.0) + mass[i] * (at + _quat_rotate(turn, ipos[i]))
+        weight[n] = weight.get(n, 0.0) + mass[i]
+
+    rows, dofs, free, used = [], [], list(range(len(raw.bodies) + 1)), [0]
+
+    def plain(kind, level):
+        row = np.zeros(POINT_ROW_LEN)
+        row[0], row[1] = kind, level
+        rows.append(row)
+        dofs.append(0)
+
+    def mass_row(n):
+        if weight.get(n, 0.0) > 0.0:
+            row = np.zeros(POINT_ROW_LEN)
+            row[0], row[3:6], row[6] = MASS_ROW, moment[n] / weight[n], weight[n] / total
+            rows.append(row)
+            dofs.append(0)
+
+    def children(n, world):
+        below = kids.get(n, [])
+        level = -1
+        if len(below) > 1 and not world:
+            level = free.pop(0)
+            used[0] = max(used[0], level + 1)
+            plain(SAVE_ROW, level)
+        for k, child in enumerate(below):
+            if k > 0:
+                plain(RESTORE_ROW, level)
+            if k == len(below) - 1 and level >= 0:
+                free.insert(0, level)
+                free.sort()
+            node_rows, node_dofs = _path(raw, child, qadr, dadr)[:2]
+            rows.append(node_rows[-1])
+            dofs.append(node_dofs[-1])
+            mass_row(child)
+            children(child, False)
+
+    top = node_of(body) if body >= 0 else -1        # the frame the subtree hangs on: a node above it, its own root, or the world
+    if body >= 0 and raw.bodies[body].joint is not None:
+        top = node_of(raw.bodies[body].parent)
+    if top >= 0:
+        rows, dofs = [list(x) for x in _path(raw, top, qadr, dadr)[:2]]
+    mass_row(top)                                   # (the subtree's bodies welded to that frame, if any)
+    children(top, top < 0)
+    if used[0] > MAX_LEVELS:
+        raise ValueError("cost terms: this centre of mass needs %d saved frames at a time (nested branch points), the kernel "
+                         "has %d" % (used[0], MAX_LEVELS))
+    return rows, dofs, used[0]
+
+
+def tree_program(raw, outputs, differences=(), mass=None, ipos=None):
+    """The program of ``mjmpc_points_tree`` (row format: include/mjmpc_amd.h) for ``outputs`` - ``motion_program``'s
+    ``[(kind, body index, vector)]`` and, for a centre of mass, ``(COM_ROW, body index or -1 for the whole model, None)`` and
+    ``(COM_VELOCITY_ROW, index in outputs of its centre of mass, None)`` - with the bodies' ``mass`` and ``ipos``: the program,
+    ``n_rows``, the dof addresses and ``n_levels``, the saved frames it uses.  The outputs on one body share one walk as in
+    ``motion_program``; a centre of mass is a walk of its own (``com_walk``), closed by its COM row and, on the same walk, its
+    COM_VELOCITY row; every walk stands where its first output was defined."""
+    keys = [("com", k) if kind == COM_ROW else ("com", int(b)) if kind == COM_VELOCITY_ROW else ("body", int(b))
+            for k, (kind, b, _) in enumerate(outputs)]
+    walks, n_levels = [], 0
+    for key in dict.fromkeys(keys):
+        closing = [(kind, slot, vec) for slot, (kind, _, vec) in enumerate(outputs) if keys[slot] == key]
+        if key[0] == "com":
+            rows, dofs, levels = com_walk(raw, int(outputs[key[1]][1]), mass, ipos)
+            n_levels = max(n_levels, levels)
+            walks.append((None, closing, (rows, dofs)))
+        else:
+            walks.append((key[1], closing))
+    program, n_rows, dofadr = _program(raw, walks, differences)
+    if n_rows > MAX_PROGRAM_ROWS:
+        raise ValueError("cost terms: the points program has %d rows, at most %d" % (n_rows, MAX_PROGRAM_ROWS))
+    return program, n_rows, dofadr, n_levels
+
+
+def launch_points(lib, code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, out, stream, n_levels=None):
+    """The one launch in front of a cost entry (DESIGN 12.4 - 12.6) over ``n`` observation rows, the device arrays given as
     pointers: ``mjmpc_points`` without a dof-address table, ``mjmpc_points_motion`` - which reads the ``nv`` entries of ``qvel``
-    behind ``qpos`` too - with one.  -> the entry's return code."""
+    behind ``qpos`` too - with one, ``mjmpc_points_tree`` with ``n_levels`` as well (a table that holds a centre of mass).
+    -> the entry's return code."""
+    if n_levels is not None:
+        return lib.mjmpc_points_tree(code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, n_levels, out, stream)
     if dofadr is None:
         return lib.mjmpc_points(code, n, d_obs, nq, obs, program, n_rows, n_out, n_diff, out, stream)
     return lib.mjmpc_points_motion(code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, out, stream)
+
+
+def refuse_mass_randomization(terms, param_dict):
+    """``ValueError`` if ``terms`` (a ``CostTerms``, a list of them or ``None``) hold a centre of mass while ``param_dict``
+    (``randomize_dynamics``'s, or ``None``) randomizes ``body_mass``: every shard would have a centre of mass of its own and
+    one program could not serve them.  The engines and the episode batches call it from ``set_cost_terms`` and
+    from ``randomize_dynamics``, whichever comes second."""
+    each = terms if isinstance(terms, (list, tuple)) else [terms]
+    if param_dict and "body_mass" in param_dict and any(t is not None and t.needs_tree_entry for t in each):
+        raise ValueError("cost terms with a centre of mass (com / com_velocity) cannot be combined with randomize_dynamics of "
+                         "body_mass: every shard would have a centre of mass of its own, and the shards share one program")
 
 
 class CostTerms:
@@ -243,6 +392,7 @@ class CostTerms:
         self._points = []           # the outputs (name, body index, position or axis in the body frame, closing kind): points
                                     # (DESIGN 12.4), axes, velocities and angular velocities, in definition order
         self._differences = []      # (name, output a, output b): indices into _points
+        self._com_of = {}           # a COM velocity's index in _points -> its centre of mass's
 
     # ------------------------------------------------------------------ world positions of points and motion (12.5)
     def _raw_for_points(self, what):
@@ -275,7 +425,8 @@ class CostTerms:
             raise ValueError("cost terms: a table holds at most %d points, axes, velocities and angular velocities" % MAX_POINTS)
         if self._differences:
             raise ValueError("cost terms: define the points before the differences (their blocks stand in that order)")
-        _path(raw, int(index), *_addresses(raw))            # (a path too long is refused here)
+        if int(index) >= 0:
+            _path(raw, int(index), *_addresses(raw))        # (a path too long is refused here)
         self._points.append((name, int(index), np.array(vec, np.float64), kind))
         return self
 
@@ -337,9 +488,36 @@ class CostTerms:
             raise ValueError("cost terms: angular_velocity takes body=")
         return self._add_output(raw, name, self._body_index(raw, body), np.zeros(3), ANGULAR_ROW)
 
+    def com(self, name, body=None):
+        """A block ``name`` of three entries: the world position of the centre of mass of ``body`` and all its descendants
+        (``None``: of every body of the model) at the row's own ``qpos``, with the nominal model's masses and
+        inertial positions.  An output like a point; a subtree of mass 0 or one whose walk needs more than 4 saved frames at
+        a time is refused."""
+        raw = self._raw_for_points("com")
+        self._check_block_name(name)
+        index = -1 if body is None else self._body_index(raw, body)
+        if len(self._points) < MAX_POINTS and not self._differences:
+            com_walk(raw, index, *inertials(self.engine))       # (what the walk refuses is refused here)
+        return self._add_output(raw, name, index, np.zeros(3), COM_ROW)
+
+    def com_velocity(self, name, com):
+        """A block ``name`` of three entries: the world velocity of ``com``, a centre of mass named with ``com(...)`` - the
+        subtree's linear momentum over its mass, from the row's own ``qpos`` and ``qvel`` with MuJoCo's meaning of ``qvel``
+        (DESIGN 12.5, 12.6).  It shares the walk of its centre of mass."""
+        raw = self._raw_for_points("com_velocity")
+        self._check_block_name(name)
+        known = [k for k, p in enumerate(self._points) if p[3] == COM_ROW and p[0] == com]
+        if not known:
+            raise ValueError("cost terms: unknown centre of mass %r (defined: %s)"
+                             % (com, ", ".join(p[0] for p in self._points if p[3] == COM_ROW) or "none"))
+        self._add_output(raw, name, self._points[known[0]][1], np.zeros(3), COM_VELOCITY_ROW)
+        self._com_of[len(self._points) - 1] = known[0]
+        return self
+
     def difference(self, name, a, b):
         """A block ``name`` of three entries behind the outputs' blocks: ``a`` minus ``b`` (world frame), one double subtraction
-        per component - two points, two axes, two velocities or two angular velocities.  At most 16 differences a table."""
+        per component - two points, two axes, two velocities or two angular velocities; a centre of mass counts as a point
+        and its velocity as a velocity.  At most 16 differences a table."""
         self._raw_for_points("difference")
         self._check_block_name(name)
         known = [p[0] for p in self._points]
@@ -347,7 +525,8 @@ class CostTerms:
             if x not in known:
                 raise ValueError("cost terms: unknown point, axis or velocity %r (defined: %s)" % (x, ", ".join(known) or "none"))
         ia, ib = known.index(a), known.index(b)
-        if self._points[ia][3] != self._points[ib][3]:
+        ka, kb = self._points[ia][3], self._points[ib][3]
+        if ka != kb and not any(ka in both and kb in both for both in (_POSITIONS, _VELOCITIES)):
             raise ValueError("cost terms: a difference takes two points, two axes, two velocities or two angular velocities; "
                              "%r and %r are of different kinds" % (a, b))
         if len(self._differences) >= MAX_DIFFERENCES:
@@ -365,6 +544,11 @@ class CostTerms:
         """Whether an axis, a velocity or an angular velocity is defined: ``mjmpc_points_motion`` instead of ``mjmpc_points``."""
         return any(p[3] != POINT_ROW for p in self._points)
 
+    @property
+    def needs_tree_entry(self):
+        """Whether a centre of mass is defined: ``mjmpc_points_tree`` for the whole program."""
+        return any(p[3] in (COM_ROW, COM_VELOCITY_ROW) for p in self._points)
+
     def points_layout(self, engine=None):
         """Named slices of the outputs' (points, axes, velocities, angular velocities) and differences' blocks in the augmented
         row, in definition order."""
@@ -378,7 +562,9 @@ class CostTerms:
         """``(program, n_rows, n_points, n_differences)`` - the points program of ``mjmpc_points``, float64
         ``[n_rows + n_differences][16]`` (``points_program``) -, or ``None`` for a table without points.  With an axis, a
         velocity or an angular velocity: ``(program, n_rows, n_outputs, n_differences, dofadr)``, the program and
-        the node rows' ``qvel`` addresses (int32 ``[n_rows]``) of ``mjmpc_points_motion`` (``motion_program``)."""
+        the node rows' ``qvel`` addresses (int32 ``[n_rows]``) of ``mjmpc_points_motion`` (``motion_program``).  With a centre of
+        mass: ``(program, n_rows, n_outputs, n_differences, dofadr, n_levels)`` of ``mjmpc_points_tree``
+        (``tree_program``)."""
         if not self._points:
             return None
         engine = engine if engine is not None else self.engine
@@ -386,6 +572,11 @@ class CostTerms:
         if raw is None:
             raise ValueError("cost terms: points need an engine built from a RawModel")
         differences = [(a, b) for _, a, b in self._differences]
+        if self.needs_tree_entry:
+            outputs = [(k, self._com_of[i] if k == COM_VELOCITY_ROW else b, None if k in (COM_ROW, COM_VELOCITY_ROW) else p)
+                       for i, (_, b, p, k) in enumerate(self._points)]
+            program, n_rows, dofadr, n_levels = tree_program(raw, outputs, differences, *inertials(engine))
+            return program, n_rows, len(self._points), len(self._differences), dofadr, n_levels
         if self.needs_motion_entry:
             program, n_rows, dofadr = motion_program(raw, [(k, b, p) for _, b, p, k in self._points], differences)
             return program, n_rows, len(self._points), len(self._differences), dofadr
@@ -797,11 +988,21 @@ def cost_terms_from_config(block, engine, num_episodes=None):
 
     DESIGN 12.5: ``axes:`` - ``{name: glass_up, body: glass, axis: [0, 0, 1]}`` -, ``velocities:`` - ``{name: glass_vel, point:
     glass}`` - and ``angular_velocities:`` - ``{name: glass_spin, body: glass}`` - stand between ``points:`` and
-    ``differences:``, and their blocks in that order: points, axes, velocities, angular velocities, differences."""
+    ``differences:``, and their blocks in that order: points, axes, velocities, angular velocities, differences.
+
+    DESIGN 12.6: ``coms:`` - ``{name: body_com}`` for the whole model or ``{name: leg_com, body: bthigh}`` for a subtree - and
+    ``com_velocities:`` - ``{name: body_vel, com: body_com}`` - stand between ``angular_velocities:`` and ``differences:``."""
     if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms", "points", "differences", "axes", "velocities",
-                                                     "angular_velocities"}:
+                                                     "angular_velocities", "coms", "com_velocities"}:
         raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin', 'points', 'axes', "
-                         "'velocities', 'angular_velocities' and 'differences'")
+                         "'velocities', 'angular_velocities', 'coms', 'com_velocities' and 'differences'")
+    com_entries, com_velocity_entries = block.get("coms") or [], block.get("com_velocities") or []
+    for entry in com_entries:
+        if not isinstance(entry, dict) or "name" not in entry or set(entry) - {"name", "body"}:
+            raise ValueError("cost_terms: a com takes name and optionally body, got %r" % (entry,))
+    for entry in com_velocity_entries:
+        if not isinstance(entry, dict) or set(entry) != {"name", "com"}:
+            raise ValueError("cost_terms: a com velocity takes name and com, got %r" % (entry,))
     point_entries, difference_entries = block.get("points") or [], block.get("differences") or []
     axis_entries, velocity_entries = block.get("axes") or [], block.get("velocities") or []
     angular_entries = block.get("angular_velocities") or []
@@ -857,6 +1058,10 @@ def cost_terms_from_config(block, engine, num_episodes=None):
             terms.velocity(entry["name"], entry["point"])
         for entry in angular_entries:
             terms.angular_velocity(entry["name"], body=entry["body"])
+        for entry in com_entries:           # 
+            terms.com(entry["name"], body=entry.get("body"))
+        for entry in com_velocity_entries:
+            terms.com_velocity(entry["name"], entry["com"])
         for entry in difference_entries:
             terms.difference(entry["name"], entry["a"], entry["b"])
         for entry in entries:

@@ -106,3 +106,15 @@ class HalfCheetahEnv(_ForwardEnv):
         qvel = self.init_qvel + self.np_random.randn(self.nv) * .1
         self.set_state(qpos, qvel)
         return self._get_obs()
+
+
+def half_cheetah_state_raw():
+    """``half_cheetah_raw`` observing the whole state: ``obs = [qpos, qvel]``.  What cost terms on world points and centres of
+    mass need: they are formed from the row's own ``qpos``, all of it."""
+    return dataclasses.replace(half_cheetah_raw(), obs_skip=0)
+
+
+class HalfCheetahStateEnv(HalfCheetahEnv):
+    """``HalfCheetahEnv`` with ``obs = [qpos, qvel]`` (``half_cheetah_state_raw``); dynamics, rewards and resets are its."""
+    raw_fn = staticmethod(half_cheetah_state_raw)
+
