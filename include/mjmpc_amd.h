@@ -38,7 +38,8 @@ extern "C" {
 /*   (entry points that are only ADDED keep the version - every existing caller still works: the episode batches', the
  *      device-resident particle filter's, mjmpc_tree_set_batch_models, mjmpc_tree_set_env_model, the CEM episode batches'
  *      the DMD-MPC episode batches', mjmpc_cost_terms, mjmpc_cost_terms_track / _track_batch, mjmpc_cost_terms_rate /
- *      _rate_batch, mjmpc_cost_terms_quad / _quad_batch, mjmpc_points, mjmpc_points_motion and mjmpc_points_tree.) */
+ *      _rate_batch, mjmpc_cost_terms_quad / _quad_batch, mjmpc_points, mjmpc_points_motion, mjmpc_points_tree and
+ *      mjmpc_points_orient.) */
 #define MJMPC_ABI_VERSION 4
 
 #define MJMPC_F32 0
@@ -1010,6 +1011,30 @@ int mjmpc_points_motion(int dtype, int64_t N, int d_obs, int nq, int nv, const v
  * outputs and saved frames. */
 int mjmpc_points_tree(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
                       const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* d_out, void* stream);
+
+/* The orientation error of a body as three entries beside everything above: mjmpc_points_tree - every row kind
+ * above with the same meaning, the same arguments, tile, slots and guards - with a held quaternion h beside the walk and two
+ * row kinds, which have this meaning at this entry only:
+ *   14 HOLD         {14}                           h <- the frame's orientation f.q; the frame, v and w go back to the world
+ *                                                  frame at rest; S and Sv are left alone
+ *   15 ORIENTATION  {15, keep, slot, ow, ox, oy, oz, gw, gx, gy, gz, rel}
+ *                                                  a closing row (keep and slot as above): b = f.q * o, a = rel ? h * g : g,
+ *                                                  e = conj(a) * b, and Log(e) goes to `slot`: the rotation vector theta u that
+ *                                                  takes the goal frame a to the body's frame b, written in the goal frame
+ * h is the identity at the program's start, so rel = 1 with no HOLD before it reads the world frame.  o and g are unit
+ * quaternions (w, x, y, z), normalised by the host.  An absolute orientation (rel = 0) shares its body's walk with the other
+ * outputs on that body; a relative one is a walk of its own: the path to the other body, HOLD, the path to the body, the
+ * closing row.
+ *
+ * The log map, for e = (w, x, y, z), in double:
+ *   if w < 0, all four are negated (w == 0 keeps the stored sign);
+ *   s = sqrt(x^2 + y^2 + z^2);
+ *   k = 2 / w if s < 2^-26 (relative error s^2 / 3 < 1e-16), else k = 2 atan2(s, w) / s;
+ *   r = k (x, y, z).
+ * So theta = |r| lies in [0, pi], e the identity gives exactly 0, and near theta = pi the sign of r follows that of w.
+ * MJMPC_E_BADARG before anything is launched: what mjmpc_points_tree refuses. */
+int mjmpc_points_orient(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
+                        const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* d_out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,7 @@ SIGNATURES = {
     "mjmpc_points": (_int, [_int, _i64, _int, _int, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "mjmpc_points_motion": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "mjmpc_points_tree": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
+    "mjmpc_points_orient": (_int, [_int, _i64, _int, _int, _int, _vp, _vp, _vp, _int, _int, _int, _int, _vp, _vp]),
 }
 
 _LIB = None

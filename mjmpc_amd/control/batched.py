@@ -97,6 +97,7 @@ class _EpisodeBatch:
     _cost_terms_set = None  # set_cost_terms' argument, _mass_randomized: randomize_dynamics drew body_mass (DESIGN 12.6 refuses a
     _mass_randomized = None  # centre of mass beside it)
     _points_levels = None   # ... the saved frames of its program: a centre of mass, mjmpc_points_tree
+    _points_orient = False  # ... whether it holds an orientation: mjmpc_points_orient
     _points = None          # the tables name points: (program, n_rows, n_points, n_diff, d_obs + n_extra, the augmented
                             # observations of the rollouts [E P][H][.] and of the real-env steps [E][.], the node rows' qvel
                             # addresses - None without axes and velocities)
@@ -426,12 +427,13 @@ class _EpisodeBatch:
         ``E P H`` rows between the rollout and the cost entry, as the single engines do; the episodes share the points and
         differences (``ValueError`` naming the episode) and keep their own weights, targets and references; with axes,
         velocities or angular velocities the launch is ``mjmpc_points_motion``, shared in the same way, with a centre
-        of mass ``mjmpc_points_tree`` - refused beside a ``randomize_dynamics`` of ``body_mass``.  Everything is
+        of mass ``mjmpc_points_tree`` - refused beside a ``randomize_dynamics`` of ``body_mass`` -, with an
+        orientation ``mjmpc_points_orient``.  Everything is
         checked on the host first (``ValueError``); callable between steps."""
         if terms is None:
             self._terms = self._terms_nobs = self._terms_env = self._track = self._prev_actions = self._quad = None
             self._points = self._cost_terms_set = self._points_levels = None
-            self._rate = False
+            self._rate = self._points_orient = False
             return
         tables, keep, reads_actions = self._resolve_cost_terms(terms, self.engine, self.num_episodes)
         refuse_mass_randomization(terms, self._mass_randomized)         # (DESIGN 12.6)
@@ -456,6 +458,7 @@ class _EpisodeBatch:
         self._prev_actions = (torch.full((E, self.d_action), float("nan"), dtype=torch.float64, device=dev) if rate_rows
                               else None)
         self._points = self._points_levels = None
+        self._points_orient = False
         first = terms[0] if isinstance(terms, (list, tuple)) else terms
         points = first.points_table(self.engine)
         if points is not None:
@@ -468,6 +471,8 @@ class _EpisodeBatch:
                 torch.from_numpy(points[4]).to(dev) if len(points) > 4 else None)
             #  with a centre of mass the saved frames of the program: mjmpc_points_tree
             self._points_levels = points[5] if len(points) > 5 else None
+            #  with an orientation the whole program goes through mjmpc_points_orient
+            self._points_orient = len(points) > 6
 
     def _launch_cost_terms(self, P, H, nobs, act, costs, terminal, gseq, q0, s, bias=0, advance_prev=0):
         """``mjmpc_cost_terms_batch`` on ``[E P][H]`` costs with the batch's table(s); with tracked terms
@@ -480,7 +485,8 @@ class _EpisodeBatch:
             program, n_rows, n_points, n_diff, d_aug, aug_rollout, aug_env, dofadr = self._points
             aug = aug_rollout if nobs is self._terms_nobs else aug_env
             _lib.check(launch_points(self.lib, self._code, self.num_episodes * P * H, d_obs, self.engine._nq, self.model.nv,
-                                     _vp(nobs), _vp(program), _vp(dofadr), n_rows, n_points, n_diff, _vp(aug), s, self._points_levels))
+                                     _vp(nobs), _vp(program), _vp(dofadr), n_rows, n_points, n_diff, _vp(aug), s, self._points_levels,
+                                     self._points_orient))
             nobs, d_obs = aug, d_aug
         if self._quad is not None:
             refs, N, R, ref_per_episode, periodic = self._track if self._track is not None else (None, 0, 0, 0, 0)

@@ -29,6 +29,12 @@
 // a level is a run-time value, and a per-lane array indexed by one would go to scratch.  Every lane first writes the world
 // frame at rest to its levels, so a RESTORE of a level never saved is defined.  Resources: profiles/r29_com_resources.txt.
 //
+// The ORIENT part (mjmpc_points_orient; with TREE) adds the orientation error of a body as three entries: the
+// rotation vector Log(conj(a) * q_body * o) from a goal frame a - a constant world quaternion, or the frame a HOLD row took from
+// an earlier path of the same walk, times a constant - to the body's frame.  The held quaternion h is 4 more doubles in
+// registers; nothing more stands in LDS, so the tile is the tree entry's.  The log map is the header's, statement by statement.
+// Resources: profiles/r30_orient_resources.txt.
+//
 // Shape (cost_terms.hip's): a workgroup takes `rows` consecutive observation rows - they lie back to back in memory -, copies
 // them into LDS with unit-stride loads (odd row pitch: the lanes' column reads spread over the banks), lane j walks the program
 // over row j and parks its outputs in LDS as doubles, laid out [entry][lane] (lane-consecutive, no bank conflict); then all
@@ -85,6 +91,16 @@ __device__ __forceinline__ void pt_cross(const double* a, const double* b, doubl
     out[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// The rotation vector of the unit quaternion e (w, x, y, z), as include/mjmpc_amd.h states it: the half with w >= 0 is taken,
+// s = |(x, y, z)|, and r = k (x, y, z) with k = 2 / w below s = 2^-26 (relative error s^2 / 3) and 2 atan2(s, w) / s from there
+__device__ __forceinline__ void pt_log(const double* e, double* r) {
+    const bool flip = e[0] < 0.0;
+    const double w = flip ? -e[0] : e[0], x = flip ? -e[1] : e[1], y = flip ? -e[2] : e[2], z = flip ? -e[3] : e[3];
+    const double s = sqrt(x * x + y * y + z * z);
+    const double k = s < 0x1p-26 ? 2.0 / w : 2.0 * atan2(s, w) / s;
+    r[0] = k * x; r[1] = k * y; r[2] = k * z;
+}
+
 // The output o of a closing row on the frame f: kind 0 POINT p + R off - without MOTION the only one - and, with v and w,
 // 6 AXIS R a, 7 VELOCITY v + w x (R off), 8 ANGULAR w
 template <bool MOTION>
@@ -113,12 +129,14 @@ __device__ __forceinline__ void pt_output(int kind, const PtFrame& f, const doub
 // The walk over one row `my`: the frame and, with MOTION, its origin's velocity v and its angular velocity w; the outputs go
 // to pts[(3 slot + c) * rows] (pts: this lane's column of the parked entries).  nv and dofadr are read with MOTION alone.
 // TREE (with MOTION): the accumulators S and Sv of the MASS rows and the saved frames lv[(PT_LEVEL level + c) * rows] (lv:
-// this lane's column of them), n_levels of them.
-template <typename T, bool MOTION, bool TREE>
+// this lane's column of them), n_levels of them.  ORIENT (with TREE): the held quaternion h of the HOLD rows and the closing row
+// ORIENTATION; in the other instantiations the kinds 14 and 15 are what they were.
+template <typename T, bool MOTION, bool TREE, bool ORIENT>
 __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ prog, const int32_t* __restrict__ dofadr,
                                         int n_rows, int n_out, int nq, int nv, double* pts, int rows,
                                         [[maybe_unused]] double* lv, [[maybe_unused]] int n_levels) {
     static_assert(MOTION || !TREE, "the tree walk carries v and w");
+    static_assert(TREE || !ORIENT, "the orientation walk is the tree walk's superset");
     // entry i of my qpos / qvel, held inside it whatever the tables say
     auto qpos = [&](int i) { return (double)my[i < 0 ? 0 : i < nq ? i : nq - 1]; };
     [[maybe_unused]] auto qvel = [&](int i) { return (double)my[nq + (i < 0 ? 0 : i < nv ? i : nv - 1)]; };
@@ -127,6 +145,7 @@ __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ 
     PtFrame f{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
     [[maybe_unused]] double v[3] = {0.0, 0.0, 0.0}, w[3] = {0.0, 0.0, 0.0};
     [[maybe_unused]] double S[3] = {0.0, 0.0, 0.0}, Sv[3] = {0.0, 0.0, 0.0};
+    [[maybe_unused]] double h[4] = {1.0, 0.0, 0.0, 0.0};       // ORIENT: the held quaternion, the identity until a HOLD row
     if constexpr (TREE) {                   // every level holds the world frame at rest until a SAVE says otherwise
         for (int l = 0; l < n_levels; ++l)
             for (int e = 0; e < PT_LEVEL; ++e) lv[(PT_LEVEL * l + e) * rows] = e == 3 ? 1.0 : 0.0;
@@ -169,10 +188,27 @@ __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ 
                 continue;
             }
         }
+        if constexpr (ORIENT) {
+            if (kind == 14) {               // HOLD: the frame's orientation is put by; the next path starts at the world, at rest
+                for (int e = 0; e < 4; ++e) h[e] = f.q[e];
+                f = PtFrame{{0.0, 0.0, 0.0}, {1.0, 0.0, 0.0, 0.0}};
+                v[0] = v[1] = v[2] = w[0] = w[1] = w[2] = 0.0;
+                continue;
+            }
+        }
         // a closing row: its output into its slot; the frame kept or reset
         if (kind == 0 || (MOTION && !TREE && kind >= 6) || (TREE && ((kind >= 6 && kind <= 8) || kind >= 12))) {
             double o[3];
-            if (TREE && kind >= 12) {       // COM, COM_VELOCITY: the accumulators
+            if (ORIENT && kind == 15) {     // ORIENTATION: Log(conj(a) b), b = q o, a = g or h g
+                double a[4] = {1.0, 0.0, 0.0, 0.0}, b[4] = {f.q[0], f.q[1], f.q[2], f.q[3]};
+                if (row[11] != 0.0)
+                    for (int e = 0; e < 4; ++e) a[e] = h[e];
+                pt_mul(a, row[7], row[8], row[9], row[10]);
+                pt_mul(b, row[3], row[4], row[5], row[6]);
+                a[1] = -a[1]; a[2] = -a[2]; a[3] = -a[3];
+                pt_mul(a, b[0], b[1], b[2], b[3]);
+                pt_log(a, o);
+            } else if (TREE && kind >= 12) {       // COM, COM_VELOCITY: the accumulators
                 for (int e = 0; e < 3; ++e) o[e] = kind == 12 ? S[e] : Sv[e];
             } else {
                 pt_output<MOTION>(kind, f, v, w, row, o);
@@ -262,7 +298,7 @@ __device__ __forceinline__ void pt_walk(const T* my, const double* __restrict__ 
 // grid: ceil(n / rows) workgroups of max(rows, 64) threads; dynamic LDS: rows x pitch(d_obs) words of T, then 3 n_points x rows doubles
 // MOTION: n_points counts the output slots; nv and dofadr are read by that instantiation alone
 // TREE: behind the parked outputs PT_LEVEL n_levels x rows doubles, the saved frames; n_levels is read by that instantiation alone
-template <typename T, bool MOTION, bool TREE>
+template <typename T, bool MOTION, bool TREE, bool ORIENT>
 __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs, const double* __restrict__ prog, int n_rows,
                                                        int n_points, int n_diff, long n, int d_obs, int nq, int rows,
                                                        T* __restrict__ out, int nv, const int32_t* __restrict__ dofadr,
@@ -297,7 +333,7 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
     __syncthreads();
 
     if (j < mine)
-        pt_walk<T, MOTION, TREE>(tile + j * po, prog, dofadr, n_rows, n_points, nq, nv, pts + j, rows,
+        pt_walk<T, MOTION, TREE, ORIENT>(tile + j * po, prog, dofadr, n_rows, n_points, nq, nv, pts + j, rows,
                                  pts + (long)3 * n_points * rows + j, n_levels);
     __syncthreads();
 
@@ -325,11 +361,11 @@ __global__ __launch_bounds__(PT_WG) void points_kernel(const T* __restrict__ obs
     }
 }
 
-// The three entries: the checks, the tile - the largest power of two of rows up to PT_WG whose rows, parked outputs and saved
+// The four entries: the checks, the tile - the largest power of two of rows up to PT_WG whose rows, parked outputs and saved
 // frames fit PT_LDS_BYTES - and the launch.  `motion`: mjmpc_points_motion and mjmpc_points_tree, which alone read (and check)
 // nv and dofadr and call their outputs n_out where mjmpc_points says n_points; `tree`: mjmpc_points_tree, which alone reads
-// (and checks) n_levels.
-int launch_points(const char* entry, bool motion, bool tree, int dtype, int64_t N, int d_obs, int nq, int nv, const void* obs,
+// (and checks) n_levels; `orient`: mjmpc_points_orient, the tree entry with the rows HOLD and ORIENTATION.
+int launch_points(const char* entry, bool motion, bool tree, bool orient, int dtype, int64_t N, int d_obs, int nq, int nv, const void* obs,
                   const double* prog, const int32_t* dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* out,
                   void* stream) {
     auto bad = [&](const char* detail) { return set_error(MJMPC_E_BADARG, entry, detail); };
@@ -358,8 +394,10 @@ int launch_points(const char* entry, bool motion, bool tree, int dtype, int64_t 
     if (blocks > INT32_MAX) return bad("more than 2^31 workgroups");
     auto launch = [&](auto zero) {
         using T = decltype(zero);
-        auto* const kernel = tree ? points_kernel<T, true, true> : motion ? points_kernel<T, true, false>
-                                                                          : points_kernel<T, false, false>;
+        auto* const kernel = orient   ? points_kernel<T, true, true, true>
+                             : tree   ? points_kernel<T, true, true, false>
+                             : motion ? points_kernel<T, true, false, false>
+                                      : points_kernel<T, false, false, false>;
         hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(rows < 64 ? 64 : rows), (size_t)lds(rows), (hipStream_t)stream,
                            (const T*)obs, prog, n_rows, n_out, n_diff, (long)N, d_obs, nq, rows, (T*)out, nv, dofadr, n_levels);
     };
@@ -374,19 +412,26 @@ int launch_points(const char* entry, bool motion, bool tree, int dtype, int64_t 
 
 extern "C" int mjmpc_points(int dtype, int64_t N, int d_obs, int nq, const void* d_obs_rows, const double* d_program, int n_rows,
                             int n_points, int n_diff, void* d_out, void* stream) {
-    return mjmpc::launch_points("mjmpc_points", false, false, dtype, N, d_obs, nq, 0, d_obs_rows, d_program, nullptr, n_rows,
+    return mjmpc::launch_points("mjmpc_points", false, false, false, dtype, N, d_obs, nq, 0, d_obs_rows, d_program, nullptr, n_rows,
                                 n_points, n_diff, 0, d_out, stream);
 }
 
 extern "C" int mjmpc_points_motion(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
                                    const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, void* d_out, void* stream) {
-    return mjmpc::launch_points("mjmpc_points_motion", true, false, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr,
+    return mjmpc::launch_points("mjmpc_points_motion", true, false, false, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr,
                                 n_rows, n_out, n_diff, 0, d_out, stream);
 }
 
 extern "C" int mjmpc_points_tree(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
                                  const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* d_out,
                                  void* stream) {
-    return mjmpc::launch_points("mjmpc_points_tree", true, true, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr,
+    return mjmpc::launch_points("mjmpc_points_tree", true, true, false, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr,
+                                n_rows, n_out, n_diff, n_levels, d_out, stream);
+}
+
+extern "C" int mjmpc_points_orient(int dtype, int64_t N, int d_obs, int nq, int nv, const void* d_obs_rows, const double* d_program,
+                                   const int32_t* d_dofadr, int n_rows, int n_out, int n_diff, int n_levels, void* d_out,
+                                   void* stream) {
+    return mjmpc::launch_points("mjmpc_points_orient", true, true, true, dtype, N, d_obs, nq, nv, d_obs_rows, d_program, d_dofadr,
                                 n_rows, n_out, n_diff, n_levels, d_out, stream);
 }

@@ -81,6 +81,7 @@ class RolloutEngine(EnvResetWatch):
     _points = None                  # the table names points: (program on the device, n_rows, n_points, n_diff, n_extra,
                                     # the node rows' qvel addresses on the device - None without axes and velocities)
     _points_levels = None           # ... the saved frames of its program: a centre of mass, mjmpc_points_tree
+    _points_orient = False          # ... whether it holds an orientation: mjmpc_points_orient
     _mass_randomized = None         # randomize_dynamics drew body_mass: its param_dict (DESIGN 12.6 refuses a centre of mass then)
     _points_last = None             # ... the augmented observations of the last cost launch (cost_observations)
     _closure_terms = None           # make_device_rollout_fn: whether the closures handed out were made with terms set
@@ -378,7 +379,8 @@ class RolloutEngine(EnvResetWatch):
         without points launches nothing new.  With an axis, a velocity or an angular velocity (``CostTerms.axis`` / ``velocity`` /
         ``angular_velocity``) that launch is ``mjmpc_points_motion``, which reads the row's ``qvel`` too; with a centre
         of mass (``CostTerms.com`` / ``com_velocity``) it is ``mjmpc_points_tree``, and the table is refused
-        (``ValueError``) once ``randomize_dynamics`` has drawn ``body_mass``, as that call is refused after this one; everything
+        (``ValueError``) once ``randomize_dynamics`` has drawn ``body_mass``, as that call is refused after this one; with an
+        orientation (``CostTerms.orientation``) it is ``mjmpc_points_orient`` for the whole program; everything
         else is as with points."""
         if self._closure_terms is not None and self._closure_terms != (terms is not None):
             raise RuntimeError("set_cost_terms: this engine has handed out a rollout_fn made %s cost terms, which offers the "
@@ -387,7 +389,7 @@ class RolloutEngine(EnvResetWatch):
         if terms is None:
             self._cost_terms = self._terms_dev = self._track_ref = self._track_step = self._prev_action = None
             self._terms_quad = self._points = self._points_last = self._points_levels = None
-            self._terms_read_actions = self._terms_rate = False
+            self._terms_read_actions = self._terms_rate = self._points_orient = False
             return
         table = np.ascontiguousarray(terms.table(self), np.float64)       # (ValueError before anything reaches the device)
         refuse_mass_randomization(terms, self._mass_randomized)           # 
@@ -396,6 +398,7 @@ class RolloutEngine(EnvResetWatch):
         points = terms.points_table(self)
         torch = _torch()
         self._points = self._points_last = self._points_levels = None
+        self._points_orient = False
         if points is not None:
             # (every cost launch is preceded by mjmpc_points into a buffer of the engine's)
             # (with an axis or a velocity the table has a fifth entry, the node rows' qvel addresses, and the
@@ -404,6 +407,8 @@ class RolloutEngine(EnvResetWatch):
             # (with a centre of mass a sixth, the saved frames of the program, and the launch is mjmpc_points_tree)
             self._points = (torch.from_numpy(points[0]).to(self.device),) + tuple(points[1:4]) + (int(terms.n_extra), dofadr)
             self._points_levels = points[5] if len(points) > 5 else None
+            # (with an orientation a seventh, and the launch is mjmpc_points_orient)
+            self._points_orient = len(points) > 6
         self._terms_dev = torch.from_numpy(table).to(self.device)
         self._terms_rate = bool(terms.needs_rate_entry)
         self._terms_quad = None
@@ -479,7 +484,8 @@ class RolloutEngine(EnvResetWatch):
                                (self.d_obs + n_extra,) if nobs.dim() == 1 else (P, H, self.d_obs + n_extra))
             #  with axes or velocities - a dof-address table - the launch reads qvel, the nv entries behind qpos, too
             _lib.check(launch_points(self._lib, self._code, P * H, self.d_obs, self._nq, self.model.nv, _ptr(nobs), _ptr(program),
-                                     _ptr(dofadr), n_rows, n_points, n_diff, _ptr(aug), self._stream(), self._points_levels))
+                                     _ptr(dofadr), n_rows, n_points, n_diff, _ptr(aug), self._stream(), self._points_levels,
+                                     self._points_orient))
             self._points_last = nobs = aug
             d_obs += n_extra
         t = self._terms_dev

@@ -94,6 +94,21 @@ shard would have a centre of mass of its own.
     terms.com_velocity("body_vel", "body_com")
     terms.linear(obs="body_vel", index=0, weight=-1.0)                      # forward progress of the centre of mass
     terms.outside(obs="body_com", index=2, low=-0.15, high=0.25, weight=5.0)
+
+Orientations.  ``orientation`` gives the orientation error of a body as three entries: the rotation vector
+``r = theta u`` of the rotation that takes a goal frame to the body's frame (times a body-fixed offset ``quat``), written in the
+goal frame.  The goal is a constant world quaternion ``target`` or, with ``relative_to=``, the frame of another body (times
+``relative_quat``), so the error is relative.  ``r = Log(conj(a) * q_body * o)`` with the log map of include/mjmpc_amd.h:
+``theta`` in ``[0, pi]``, exactly 0 at the goal.  An output like a point - in definition order, counted among the 16 -, so
+``norm`` is the geodesic angle, ``square`` its square, ``quadratic(parts=)`` couples it with an angular velocity and ``outside``
+on a component is a band.  ``difference`` refuses it (subtracting rotation vectors is not a rotation: use ``relative_to``); a
+``reference=`` on the block subtracts component by component.  A table with one launches ``mjmpc_points_orient`` for its whole
+program; an absolute orientation shares its body's walk, a relative one walks both paths.
+
+    terms.orientation("glass_on_tray", body="glass", relative_to="wrist")
+    terms.norm(obs="glass_on_tray", weight=2.0)                            # level AND not spun on the tray: the angle
+    terms.orientation("pen_err", body="pen", target=(0.707, 0.0, 0.707, 0.0))
+    terms.square(obs="pen_err", weight=1.0, terminal=True)
 """
 import numpy as np
 
@@ -130,6 +145,7 @@ POINT_ROW_LEN = 16
 POINT_ROW, DIFFERENCE_ROW = 0, 5
 AXIS_ROW, VELOCITY_ROW, ANGULAR_ROW = 6, 7, 8      # the further closing rows of mjmpc_points_motion
 MASS_ROW, SAVE_ROW, RESTORE_ROW, COM_ROW, COM_VELOCITY_ROW = 9, 10, 11, 12, 13     # mjmpc_points_tree's
+HOLD_ROW, ORIENTATION_ROW = 14, 15                  # mjmpc_points_orient's
 MAX_LEVELS = 4                  # frames a tree program may have saved at a time
 MAX_PROGRAM_ROWS = 544
 _POSITIONS, _VELOCITIES = (POINT_ROW, COM_ROW), (VELOCITY_ROW, COM_VELOCITY_ROW)  # what a difference may mix
@@ -197,7 +213,8 @@ def _program(raw, walks, differences):
     rows, dofs = [], []
     for body, outputs, *tree in walks:
         # (a centre of mass, DESIGN 12.6, brings the rows of its walk; its closing rows take no vector)
-        nodes, node_dofs, at, turn = tree[0] + (None, None) if tree else _path(raw, body, qadr, dadr)
+        # (a relative orientation, DESIGN 12.7, brings both paths and the welded pose behind the second)
+        nodes, node_dofs, at, turn = (tuple(tree[0]) + (None, None))[:4] if tree else _path(raw, body, qadr, dadr)
         rows.extend(nodes)
         dofs.extend(node_dofs)
         for k, (kind, slot, vec) in enumerate(outputs):
@@ -207,6 +224,8 @@ def _program(raw, walks, differences):
                 row[3:6] = at + _quat_rotate(turn, np.asarray(vec, float))
             elif kind == AXIS_ROW:
                 row[3:6] = _quat_rotate(turn, np.asarray(vec, float))
+            elif kind == ORIENTATION_ROW:       # (o behind the welded pose, the goal, rel)
+                row[3:7], row[7:11], row[11] = _quat_mul(turn, vec[0:4]), vec[4:8], vec[8]
             rows.append(row)
             dofs.append(0)
     n_rows = len(rows)
@@ -336,9 +355,19 @@ def tree_program(raw, outputs, differences=(), mass=None, ipos=None):
     ``(COM_VELOCITY_ROW, index in outputs of its centre of mass, None)`` - with the bodies' ``mass`` and ``ipos``: the program,
     ``n_rows``, the dof addresses and ``n_levels``, the saved frames it uses.  The outputs on one body share one walk as in
     ``motion_program``; a centre of mass is a walk of its own (``com_walk``), closed by its COM row and, on the same walk, its
-    COM_VELOCITY row; every walk stands where its first output was defined."""
-    keys = [("com", k) if kind == COM_ROW else ("com", int(b)) if kind == COM_VELOCITY_ROW else ("body", int(b))
-            for k, (kind, b, _) in enumerate(outputs)]
+    COM_VELOCITY row; every walk stands where its first output was defined.
+
+    The same builder makes the program of ``mjmpc_points_orient``: an orientation is ``(ORIENTATION_ROW, body
+    index, (o[4], g[4], other))`` with the body-fixed offset ``o``, the goal ``g`` and ``other`` the index of the body the error
+    is relative to, or -1.  An absolute one closes its body's walk like any output there; a relative one is a walk of its own:
+    the path to ``other``, a HOLD row, the path to the body, then the closing row with ``rel`` 1 and, as its goal, ``g`` behind
+    the pose of the bodies welded between ``other`` and its last node.  ``mass`` and ``ipos`` are read for a centre of mass
+    only."""
+    def relative(kind, vec):
+        return kind == ORIENTATION_ROW and vec[8] >= 0
+
+    keys = [("com", k) if kind == COM_ROW else ("com", int(b)) if kind == COM_VELOCITY_ROW
+            else ("rel", k) if relative(kind, vec) else ("body", int(b)) for k, (kind, b, vec) in enumerate(outputs)]
     walks, n_levels = [], 0
     for key in dict.fromkeys(keys):
         closing = [(kind, slot, vec) for slot, (kind, _, vec) in enumerate(outputs) if keys[slot] == key]
@@ -346,7 +375,18 @@ def tree_program(raw, outputs, differences=(), mass=None, ipos=None):
             rows, dofs, levels = com_walk(raw, int(outputs[key[1]][1]), mass, ipos)
             n_levels = max(n_levels, levels)
             walks.append((None, closing, (rows, dofs)))
+        elif key[0] == "rel":
+            (kind, slot, vec), body = closing[0], int(outputs[key[1]][1])
+            adr = _addresses(raw)
+            rows, dofs, _, other_turn = _path(raw, int(vec[8]), *adr)
+            nodes, node_dofs, at, turn = _path(raw, body, *adr)
+            hold = np.zeros(POINT_ROW_LEN)
+            hold[0] = HOLD_ROW
+            vec = np.concatenate([vec[0:4], _quat_mul(other_turn, vec[4:8]), [1.0]])
+            walks.append((body, [(kind, slot, vec)], (rows + [hold] + nodes, dofs + [0] + node_dofs, at, turn)))
         else:
+            closing = [(kind, slot, np.concatenate([vec[0:8], [0.0]]) if kind == ORIENTATION_ROW else vec)
+                       for kind, slot, vec in closing]
             walks.append((key[1], closing))
     program, n_rows, dofadr = _program(raw, walks, differences)
     if n_rows > MAX_PROGRAM_ROWS:
@@ -354,11 +394,16 @@ def tree_program(raw, outputs, differences=(), mass=None, ipos=None):
     return program, n_rows, dofadr, n_levels
 
 
-def launch_points(lib, code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, out, stream, n_levels=None):
-    """The one launch in front of a cost entry (DESIGN 12.4 - 12.6) over ``n`` observation rows, the device arrays given as
+def launch_points(lib, code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, out, stream, n_levels=None,
+                  orient=False):
+    """The one launch in front of a cost entry (DESIGN 12.4 - 12.7) over ``n`` observation rows, the device arrays given as
     pointers: ``mjmpc_points`` without a dof-address table, ``mjmpc_points_motion`` - which reads the ``nv`` entries of ``qvel``
     behind ``qpos`` too - with one, ``mjmpc_points_tree`` with ``n_levels`` as well (a table that holds a centre of mass).
+    ``orient``: a table that holds an orientation, whose whole program goes through ``mjmpc_points_orient``.
     -> the entry's return code."""
+    if orient:
+        return lib.mjmpc_points_orient(code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, n_levels or 0, out,
+                                       stream)
     if n_levels is not None:
         return lib.mjmpc_points_tree(code, n, d_obs, nq, nv, obs, program, dofadr, n_rows, n_out, n_diff, n_levels, out, stream)
     if dofadr is None:
@@ -514,6 +559,39 @@ class CostTerms:
         self._com_of[len(self._points) - 1] = known[0]
         return self
 
+    def orientation(self, name, body=None, quat=None, target=None, relative_to=None, relative_quat=None):
+        """A block ``name`` of three entries: the rotation vector ``Log(conj(a) * q_body * o)`` that takes the goal frame ``a``
+        to the frame of ``body`` times the body-fixed offset ``o = quat``, written in the goal frame, at the row's own ``qpos``
+        (the log map: include/mjmpc_amd.h).  ``a`` is the constant world quaternion ``target`` or, with
+        ``relative_to=`` another body, that body's frame times ``relative_quat``.  Quaternions are ``(w, x, y, z)``, normalised
+        here, the identity by default.  An output like a point; ``norm(obs=name)`` is the geodesic angle in ``[0, pi]``."""
+        raw = self._raw_for_points("orientation")
+        self._check_block_name(name)
+        if body is None:
+            raise ValueError("cost terms: orientation takes body=")
+        index = self._body_index(raw, body)
+        if relative_to is not None and target is not None:
+            raise ValueError("cost terms: an orientation takes target= or relative_to=, not both (relative_quat= is the offset "
+                             "on the other body)")
+        if relative_to is None and relative_quat is not None:
+            raise ValueError("cost terms: relative_quat= goes with relative_to=")
+        other = -1 if relative_to is None else self._body_index(raw, relative_to)
+
+        def unit(q, what):
+            q = _finite((1.0, 0.0, 0.0, 0.0) if q is None else q, what)
+            if q.shape != (4,):
+                raise ValueError("cost terms: %s must be four numbers (w, x, y, z), got %r" % (what, q.tolist()))
+            norm = float(np.linalg.norm(q))
+            if not norm > 0.0 or not np.isfinite(norm):
+                raise ValueError("cost terms: %s must not be zero, got %r" % (what, q.tolist()))
+            return q / norm
+
+        vec = np.concatenate([unit(quat, "quat"), unit(relative_quat if relative_to is not None else target,
+                                                       "relative_quat" if relative_to is not None else "target"), [other]])
+        if other >= 0 and len(self._points) < MAX_POINTS and not self._differences:
+            _path(raw, other, *_addresses(raw))             # (a path too long is refused here)
+        return self._add_output(raw, name, index, vec, ORIENTATION_ROW)
+
     def difference(self, name, a, b):
         """A block ``name`` of three entries behind the outputs' blocks: ``a`` minus ``b`` (world frame), one double subtraction
         per component - two points, two axes, two velocities or two angular velocities; a centre of mass counts as a point
@@ -525,6 +603,10 @@ class CostTerms:
             if x not in known:
                 raise ValueError("cost terms: unknown point, axis or velocity %r (defined: %s)" % (x, ", ".join(known) or "none"))
         ia, ib = known.index(a), known.index(b)
+        for x, i in ((a, ia), (b, ib)):
+            if self._points[i][3] == ORIENTATION_ROW:
+                raise ValueError("cost terms: %r is an orientation, and subtracting rotation vectors is not a rotation: define "
+                                 "the error between two bodies with orientation(..., relative_to=)" % x)
         ka, kb = self._points[ia][3], self._points[ib][3]
         if ka != kb and not any(ka in both and kb in both for both in (_POSITIONS, _VELOCITIES)):
             raise ValueError("cost terms: a difference takes two points, two axes, two velocities or two angular velocities; "
@@ -549,6 +631,11 @@ class CostTerms:
         """Whether a centre of mass is defined: ``mjmpc_points_tree`` for the whole program."""
         return any(p[3] in (COM_ROW, COM_VELOCITY_ROW) for p in self._points)
 
+    @property
+    def needs_orient_entry(self):
+        """Whether an orientation is defined: ``mjmpc_points_orient`` for the whole program."""
+        return any(p[3] == ORIENTATION_ROW for p in self._points)
+
     def points_layout(self, engine=None):
         """Named slices of the outputs' (points, axes, velocities, angular velocities) and differences' blocks in the augmented
         row, in definition order."""
@@ -564,7 +651,8 @@ class CostTerms:
         velocity or an angular velocity: ``(program, n_rows, n_outputs, n_differences, dofadr)``, the program and
         the node rows' ``qvel`` addresses (int32 ``[n_rows]``) of ``mjmpc_points_motion`` (``motion_program``).  With a centre of
         mass: ``(program, n_rows, n_outputs, n_differences, dofadr, n_levels)`` of ``mjmpc_points_tree``
-        (``tree_program``)."""
+        (``tree_program``).  With an orientation a seventh entry, ``True``, says that the six are
+        ``mjmpc_points_orient``'s: the whole program goes through that entry, ``n_levels`` 0 without a centre of mass."""
         if not self._points:
             return None
         engine = engine if engine is not None else self.engine
@@ -572,11 +660,13 @@ class CostTerms:
         if raw is None:
             raise ValueError("cost terms: points need an engine built from a RawModel")
         differences = [(a, b) for _, a, b in self._differences]
-        if self.needs_tree_entry:
+        if self.needs_tree_entry or self.needs_orient_entry:
             outputs = [(k, self._com_of[i] if k == COM_VELOCITY_ROW else b, None if k in (COM_ROW, COM_VELOCITY_ROW) else p)
                        for i, (_, b, p, k) in enumerate(self._points)]
-            program, n_rows, dofadr, n_levels = tree_program(raw, outputs, differences, *inertials(engine))
-            return program, n_rows, len(self._points), len(self._differences), dofadr, n_levels
+            program, n_rows, dofadr, n_levels = tree_program(raw, outputs, differences,
+                                                             *(inertials(engine) if self.needs_tree_entry else (None, None)))
+            return (program, n_rows, len(self._points), len(self._differences), dofadr, n_levels) + (
+                (True,) if self.needs_orient_entry else ())
         if self.needs_motion_entry:
             program, n_rows, dofadr = motion_program(raw, [(k, b, p) for _, b, p, k in self._points], differences)
             return program, n_rows, len(self._points), len(self._differences), dofadr
@@ -991,11 +1081,21 @@ def cost_terms_from_config(block, engine, num_episodes=None):
     ``differences:``, and their blocks in that order: points, axes, velocities, angular velocities, differences.
 
     DESIGN 12.6: ``coms:`` - ``{name: body_com}`` for the whole model or ``{name: leg_com, body: bthigh}`` for a subtree - and
-    ``com_velocities:`` - ``{name: body_vel, com: body_com}`` - stand between ``angular_velocities:`` and ``differences:``."""
+    ``com_velocities:`` - ``{name: body_vel, com: body_com}`` - stand between ``angular_velocities:`` and ``differences:``.
+
+    DESIGN 12.7: ``orientations:`` - ``{name: pen_err, body: pen, target: [0.707, 0, 0.707, 0]}`` or ``{name: glass_on_tray, body:
+    glass, relative_to: wrist}``, optionally ``quat:`` and ``relative_quat:`` - stand between ``com_velocities:`` and
+    ``differences:``."""
     if not isinstance(block, dict) or set(block) - {"keep_builtin", "terms", "points", "differences", "axes", "velocities",
-                                                     "angular_velocities", "coms", "com_velocities"}:
+                                                     "angular_velocities", "coms", "com_velocities", "orientations"}:
         raise ValueError("cost_terms: expected a mapping with 'terms' and optionally 'keep_builtin', 'points', 'axes', "
-                         "'velocities', 'angular_velocities', 'coms', 'com_velocities' and 'differences'")
+                         "'velocities', 'angular_velocities', 'coms', 'com_velocities', 'orientations' and 'differences'")
+    orientation_entries = block.get("orientations") or []
+    for entry in orientation_entries:
+        if not isinstance(entry, dict) or not {"name", "body"} <= set(entry) or set(entry) - {
+                "name", "body", "quat", "target", "relative_to", "relative_quat"}:
+            raise ValueError("cost_terms: an orientation takes name and body, optionally quat, target, relative_to and "
+                             "relative_quat, got %r" % (entry,))
     com_entries, com_velocity_entries = block.get("coms") or [], block.get("com_velocities") or []
     for entry in com_entries:
         if not isinstance(entry, dict) or "name" not in entry or set(entry) - {"name", "body"}:
@@ -1062,6 +1162,9 @@ def cost_terms_from_config(block, engine, num_episodes=None):
             terms.com(entry["name"], body=entry.get("body"))
         for entry in com_velocity_entries:
             terms.com_velocity(entry["name"], entry["com"])
+        for entry in orientation_entries:   # 
+            terms.orientation(entry["name"], body=entry["body"], quat=entry.get("quat"), target=entry.get("target"),
+                              relative_to=entry.get("relative_to"), relative_quat=entry.get("relative_quat"))
         for entry in difference_entries:
             terms.difference(entry["name"], entry["a"], entry["b"])
         for entry in entries:
